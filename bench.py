@@ -10,11 +10,19 @@ uses 0x5EED0050+r when N > 1 -- workloads.py).  A step is what the reference's B
 (engine/engine.go:379-406): compress, then decompress, of one buffer, input already resident in HBM.
 value = uncompressed MB (1e6 B) through encode+decode per second, whole job.
 
-After the timed region (N = 1 only) every other BASELINE config runs at the same size and is reported under
+A plain run sets up, warms up, times --steps steps and prints the line (with the per-kernel times that librsn's events
+record inside the timed steps).  `--dump-outputs DIR` then also writes what the last timed step returned -- the compressed
+stream and the decoded buffer -- as float32 .npy files: the first MiB of each, 2^22 bytes at seeded positions and the
+length (DIR/<output>_head.npy, _sample.npy, _size.npy), so that two builds can be compared output for output.
+
+Everything else runs with `--full` only.  After the timed region: the HBM calibration (torch copy and read passes);
+for N > 1 configs[4]'s eight chunks dealt over the ranks and the segment gather; for N = 1 the headline's CPU
+baseline, and every other BASELINE config runs at the same size and is reported under
 `other_configs`: 2b (uniform 0x00..0xFF: the rune path, lossy exactly like the reference), `skewed` (unequal code
 lengths: the general Huffman kernels), 3 (`lzss`, 4096-periodic), 4 (`lzss,huffman` on Zipf text) -- each with
 encode/decode ms, ratio, lossless, a bit-exact check against the oracle on a sample, the dominant kernel, the
-algorithmic-byte fractions of the HBM peak and its own threaded CPU baseline.
+algorithmic-byte fractions of the HBM peak and its own threaded CPU baseline -- and config 1, the host-buffer
+rates, the general Huffman path on 2a and the CLI's cold start.
 
 Kernel timings come from HIP events recorded by librsn on its own launch stream (rsn_prof_*), live inside the
 timed region.  The CPU baseline is oracle/cpu_baseline.c -- the C restatement of the reference (the reference is
@@ -663,6 +671,29 @@ def cold_start(torch, n):
     return out
 
 
+DUMP_HEAD = 1 << 20        # leading bytes of each output written whole (the compressed stream's header and table are at its start)
+DUMP_SAMPLE = 1 << 22      # bytes of each output at seeded positions: 2 outputs x (1 + 4) Mi float32 = 40 MiB in all
+DUMP_SEED = 0x5EED00D0
+
+
+def dump_outputs(torch, outdir, outputs):
+    """--dump-outputs: `outputs` = {name: 1-D uint8 device tensor}, what the last timed step returned.  Per output, as float32:
+    <name>_head.npy (the first DUMP_HEAD bytes), <name>_sample.npy (DUMP_SAMPLE bytes at sorted positions drawn from a fixed
+    seed and the output's length; the whole output when it is no longer), and <name>_size.npy (its length, float64)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in outputs.items():
+        m = int(t.numel())
+        np.save(os.path.join(outdir, name + "_size.npy"), np.array([m], dtype=np.float64))
+        np.save(os.path.join(outdir, name + "_head.npy"), t[:DUMP_HEAD].cpu().numpy().astype(np.float32))
+        if m <= DUMP_SAMPLE:
+            smp = t.cpu().numpy()
+        else:
+            pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, m, size=DUMP_SAMPLE, dtype=np.int64))
+            smp = t[torch.from_numpy(pos).to(t.device)].cpu().numpy()
+        np.save(os.path.join(outdir, name + "_sample.npy"), smp.astype(np.float32))
+
+
 
 def self_launch(n_ranks):
     """`python bench.py --gpus N` without a launcher: this process becomes the launcher's parent -- it starts
@@ -688,15 +719,21 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--mib", type=int, default=1024, help="buffer size per GPU (default: the 1 GiB of BASELINE.json)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baselines")
-    ap.add_argument("--no-others", action="store_true", help="skip the other BASELINE configs after the timed region")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure everything else: the HBM calibration, "
+                    "the CPU baselines, the other BASELINE configs (N = 1), config 5's dealt chunks and the segment gather (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step returned to DIR/*.npy "
+                    "(float32: the head and a seeded sample of the compressed stream and of the decoded buffer, and their lengths)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-others", action="store_true", help="--full: skip the other BASELINE configs after the timed region")
     ap.add_argument("--others", default="1,2b,skewed,3,4,5", help="1 = config 1 (64 KiB, host-buffer API) + the host-API rates at the bench size")
-    ap.add_argument("--no-dealt", action="store_true", help="N > 1: skip config 5's eight dealt chunks (the strong-scaling view)")
+    ap.add_argument("--no-dealt", action="store_true", help="--full, N > 1: skip config 5's eight dealt chunks (the strong-scaling view)")
     ap.add_argument("--profile-only", default="", help="run ONLY these other configs (no headline step, no CPU baselines) and print their entries: "
                     "what scripts/profile.sh puts under rocprofv3, so that a workload's counters hold that workload's launches and nothing else")
     ap.add_argument("--gather-hang-ok", action="store_true", help="exit 0 even when the segment gather is still pending after 120 s")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, one GPU per rank) or gloo (control-flow test: all ranks share GPU 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))            # plain `python bench.py --gpus N`: start the N ranks ourselves (nothing has touched the GPU yet)
@@ -782,10 +819,12 @@ def main():
         ranks = _shard.per_rank(dist, [elapsed / K_ * 1e3, e_ms, d_ms, (2 * n + C_) / (e_ms / 1e3) / 1e9 / HBM_PEAK_GBPS,
                                        (C_ + n) / (d_ms / 1e3) / 1e9 / HBM_PEAK_GBPS, n / (e_ms / 1e3) / 1e9 / HBM_PEAK_GBPS], cdev)
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, {"compressed": c, "decompressed": d})
     lossless = bool(d.numel() == n and torch.equal(d, src))   # checked BEFORE anything else touches dec_buf
     comp_n = int(c.numel())
 
-    # context for the roofline: what a plain device-to-device copy and a read-only pass reach on THIS GPU
+    # --full: context for the roofline: what a plain device-to-device copy and a read-only pass reach on THIS GPU
     # (torch kernels, timed with torch events on torch's stream; not part of the timed region above)
     def _rate(fn, nbytes, reps=10):
         for _ in range(3):
@@ -798,20 +837,21 @@ def main():
         e1.record()
         torch.cuda.synchronize(device)
         return nbytes / (e0.elapsed_time(e1) / reps) / 1e6
-    copy_gbps = _rate(lambda: dec_buf[:n].copy_(src), 2 * n)
-    read_gbps = _rate(lambda: src.view(torch.int64).sum(), n)
+    if args.full:
+        copy_gbps = _rate(lambda: dec_buf[:n].copy_(src), 2 * n)
+        read_gbps = _rate(lambda: src.view(torch.int64).sum(), n)
 
     gather_ms = None
     gather_stuck = False
     dealt = None
-    if dist is not None and not args.no_dealt:
+    if dist is not None and args.full and not args.no_dealt:
         del dec_buf
         torch.cuda.empty_cache()
         try:
             dealt = config5_dealt(torch, dist, device, n, rank, world, args.dist_backend)
         except Exception as e:                              # noqa: BLE001 -- extra information: reported, never instead of the line
             dealt = {"error": "%s: %s" % (type(e).__name__, e)}
-    if dist is not None:
+    if dist is not None and args.full:
         # config 5: compressed segments to rank 0 over RCCL, timed on its own (not part of `value`)
         seg = c.clone() if args.dist_backend == "nccl" else c.cpu()
         fence()
@@ -875,9 +915,10 @@ def main():
             "encode_frac_of_hbm_peak_2N_plus_C": round((2 * n + C) / (enc_ms / 1e3) / 1e9 / HBM_PEAK_GBPS, 4),
             "encode_input_read_frac_of_hbm_peak": round(n / (enc_ms / 1e3) / 1e9 / HBM_PEAK_GBPS, 4),
             "ratio_pct": round(100.0 * C / n, 3), "lossless": lossless,
-            "hbm_calibration_GBps": {"torch_copy_read_plus_write": round(copy_gbps, 1), "torch_read_only_sum": round(read_gbps, 1)},
             "roofline": roofline, "kernels": kernels,
         }
+        if args.full:
+            out["hbm_calibration_GBps"] = {"torch_copy_read_plus_write": round(copy_gbps, 1), "torch_read_only_sum": round(read_gbps, 1)}
         if ranks is not None:
             out["per_rank"] = {"ms_per_step": [round(r[0], 4) for r in ranks], "encode_ms": [round(r[1], 4) for r in ranks],
                                "decode_ms": [round(r[2], 4) for r in ranks],
@@ -894,10 +935,10 @@ def main():
                                   "all_gather of sizes + grouped send/recv of one segment per rank to rank 0")
         if dealt is not None:
             out["config5_dealt"] = dealt
-        if dist is not None and gather_ms is None:
+        if dist is not None and args.full and gather_ms is None:
             out["gather_ms"] = None
             out["gather_note"] = "segment gather did not complete within 120 s" if gather_stuck else "segment gather failed its size check"
-        if world == 1:
+        if world == 1 and args.full:
             from oracle import oracle as O
             O.build()
             cores = O.host_cores()

@@ -9,13 +9,14 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 G=$(python3 -c "import torch; print(torch.cuda.device_count())")
 echo "visible GPUs: $G"
 [ "$G" -lt 2 ] && { echo "one GPU: nothing to check here"; exit 0; }
-mkdir -p gpurun_out
+OUT=${RSN_OUT_DIR:-out}
+mkdir -p $OUT
 for N in 2 4 8; do
   [ "$N" -le "$G" ] || continue
-  timeout 900 python3 bench.py --gpus $N --steps 10 --warmup 2 > gpurun_out/multi_bench_$N.json 2> gpurun_out/multi_bench_$N.err; echo "bench --gpus $N: rc=$?"
-  python3 - $N <<'PY'
+  timeout 900 python3 bench.py --full --gpus $N --steps 10 --warmup 2 > $OUT/multi_bench_$N.json 2> $OUT/multi_bench_$N.err; echo "bench --gpus $N: rc=$?"
+  python3 - $OUT/multi_bench_$N.json <<'PY'
 import json, sys
-j = json.loads(open("gpurun_out/multi_bench_%s.json" % sys.argv[1]).read().strip().splitlines()[-1])
+j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print({k: j.get(k) for k in ("value", "n_gpus", "ms_per_step", "lossless", "frac_of_hbm_peak_all_gpus", "per_rank", "gather_ms", "gather_warmup_ms", "gather_GBps")}, j.get("config5_dealt"))
 PY
 done

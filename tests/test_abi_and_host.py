@@ -240,10 +240,10 @@ def test_host_code_under_address_and_ub_sanitizers(tmp_path):
 
 
 def _reference_checkout(tmp_path):
+    """A writable checkout of the two packages the split edits: tests/golden/raisin_layout holds stand-ins with the reference's
+    package-level layout (function names, imports, call edges), so the recipe is tested without a reference checkout."""
     import shutil
-    ref = "/root/reference/compressor"
-    if not os.path.isdir(ref):
-        pytest.skip("the reference is not on this machine (it never ships to the GPU box)")
+    ref = os.path.join(ROOT, "tests", "golden", "raisin_layout", "compressor")
     root = tmp_path / "raisin"
     for pkg in ("lz", "huffman"):
         shutil.copytree(os.path.join(ref, pkg), root / "compressor" / pkg)
@@ -263,7 +263,7 @@ def _split_module():
 
 
 def test_cgo_recipe_splits_the_reference_packages(tmp_path):
-    """INTEGRATION.md step 1 as a program (VERDICT r3 task 1a): go/overlay/split.py on a copy of the reference's two packages.
+    """INTEGRATION.md step 1 as a program (VERDICT r3 task 1a): go/overlay/split.py on a copy of the two packages (the stand-ins).
     Under both tags every package-level identifier used is defined once, no import is orphaned (lzss.go's `sync` goes with
     CompressAsync), compressorWorker stays where CompressRecursive (lzss.go:203) sees it, and no line is lost."""
     root = _reference_checkout(tmp_path)

@@ -249,7 +249,7 @@ def test_bench_two_ranks_control_flow():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29731", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--mib", "64", "--dist-backend", "gloo"],
+                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--mib", "64", "--dist-backend", "gloo", "--full"],
                          capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -269,6 +269,48 @@ def test_bench_two_ranks_control_flow():
     assert all(0 < x < 1 for x in d5["per_rank"]["encode_frac_of_hbm_peak"]) and 0 < d5["encode_frac_of_hbm_peak"] < 1
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` times --steps steps and prints the headline line alone (the rest is --full's); --dump-outputs
+    writes what the last timed step returned -- float32 / float64 .npy files, 64 MB at most -- and those are the library's bytes for
+    the headline input, the same from run to run."""
+    import torch
+    import workloads as W
+    from raisin_amd import huffman
+    import bench
+
+    def run(outdir, steps):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                              "--mib", "64", "--dump-outputs", str(outdir)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    j = run(tmp_path / "a", 3)
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0 and j["lossless"] is True
+    assert j["metric"] == "encode+decode MB/s" and j["unit"] == "MB/s" and j["higher_is_better"] is True and j["dtype"] == "u8"
+    for key in ("other_configs", "cpu_baseline", "hbm_calibration_GBps", "general_path_2a", "cold_start"):
+        assert key not in j, key
+    names = sorted("%s_%s.npy" % (o, p) for o in ("compressed", "decompressed") for p in ("head", "sample", "size"))
+    assert sorted(os.listdir(tmp_path / "a")) == names
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 << 20
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    n = 64 << 20
+    src = W.uniform_bytes(n, W.SEED_2, 128, "cuda")
+    c = huffman.compress_tensor(src)
+    pos = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, c.numel(), size=bench.DUMP_SAMPLE, dtype=np.int64))
+    assert got["compressed_size"][0] == c.numel() and got["decompressed_size"][0] == n
+    assert np.array_equal(got["compressed_head"], c[:bench.DUMP_HEAD].cpu().numpy().astype(np.float32))
+    assert np.array_equal(got["compressed_sample"], c[torch.from_numpy(pos).cuda()].cpu().numpy().astype(np.float32))
+    pos = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, n, size=bench.DUMP_SAMPLE, dtype=np.int64))
+    assert np.array_equal(got["decompressed_head"], src[:bench.DUMP_HEAD].cpu().numpy().astype(np.float32))
+    assert np.array_equal(got["decompressed_sample"], src[torch.from_numpy(pos).cuda()].cpu().numpy().astype(np.float32))
+    assert run(tmp_path / "b", 1)["steps"] == 1
+    for f in names:
+        assert np.array_equal(np.load(tmp_path / "b" / f), got[f[:-4]]), f
+
+
 def test_bench_two_ranks_over_rccl():
     """bench.py --gpus 2 with the DEFAULT backend (nccl = RCCL, one GPU per rank: init_process_group with a device id, the barrier,
     max-over-ranks on device tensors, gather_segments' all_gather + batch_isend_irecv over xGMI).  Needs two GPUs: skipped on the
@@ -279,7 +321,7 @@ def test_bench_two_ranks_over_rccl():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--mib", "256"], capture_output=True, text=True, env=env, timeout=900)
+                          "--mib", "256", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     j = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert j["n_gpus"] == 2 and j["lossless"] is True and j["value"] > 0
