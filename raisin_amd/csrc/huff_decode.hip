@@ -942,9 +942,12 @@ int huff_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
                 fa.nbytes = upto - A0;
             }
             fa.p0 = p0_all + q0 * L; fa.n_sym = q1 - q0; fa.out = d_out + q0;
-            const dim3 grid((uint32_t)std::min<size_t>(ceil_div((size_t)(q1 - q0), FLAT_SYMS), 256 * 8));
+            const size_t chunks = ceil_div((size_t)(q1 - q0), FLAT_SYMS);
+            dim3 grid;
             switch (L) {
-#define RSN_FLAT_CASE(LL) case LL: RSN_LAUNCH("huff_dec_flat", k_dec_flat<LL>, grid, dim3(FDB), 0, s, fa); break;
+#define RSN_FLAT_CASE(LL) case LL:                                                                                \
+                rc = persistent_grid(c, reinterpret_cast<const void *>(k_dec_flat<LL>), FDB, chunks, &grid); if (rc) return rc; \
+                RSN_LAUNCH("huff_dec_flat", k_dec_flat<LL>, grid, dim3(FDB), 0, s, fa); break;
                 RSN_FLAT_CASE(1) RSN_FLAT_CASE(2) RSN_FLAT_CASE(3) RSN_FLAT_CASE(4) RSN_FLAT_CASE(5) RSN_FLAT_CASE(6)
                 RSN_FLAT_CASE(7)   // ASCII alphabets hold at most 2^7 symbols
 #undef RSN_FLAT_CASE

@@ -717,6 +717,9 @@ __global__ __launch_bounds__(HB) void k_emit_flat(FlatEmitArgs a) {
         } else {
 #pragma unroll
             for (int k = 0; k < 8; k++) w[k] = 0;
+            // (kept rolled: unrolled, its 32 nested branches took the kernel to 106 scalar registers, 36 of them spilled to vector lanes
+            //  and read back inside the chunk loop -- 0.02 ms of the 1 GiB encode)
+#pragma unroll 1
             for (int k = 0; k < 32 && first + k < a.n; k++) w[k >> 2] |= (uint32_t)a.in[first + k] << (8 * (k & 3));
         }
 #pragma unroll
@@ -821,9 +824,14 @@ int hist_ascii_or_rune(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uin
     int rc = dev_buf(c, 1, 256 * 8, &p); if (rc) return rc;
     unsigned long long *d_gh = (unsigned long long *)p;
     RSN_HIP(hipMemsetAsync(d_gh, 0, 256 * 8, s));
-    const uint32_t grid = (uint32_t)std::min<size_t>(n_tiles, 2048);     // persistent blocks (8 loads in flight / other grid sizes: within noise, r01d A/B)
-    if (tile == TILE) RSN_LAUNCH("huff_byte_hist", (k_byte_hist<4, TILE>), dim3(grid), dim3(HB), 0, s, d_in, n, n_tiles, d_tile_hist, d_gh);
-    else RSN_LAUNCH("huff_byte_hist", (k_byte_hist<1, SMALL_TILE>), dim3(grid), dim3(HB), 0, s, d_in, n, n_tiles, d_tile_hist, d_gh);
+    dim3 grid;                                                           // persistent blocks (8 loads in flight: within noise, r01d A/B)
+    if (tile == TILE) {
+        rc = persistent_grid(c, reinterpret_cast<const void *>(k_byte_hist<4, TILE>), HB, n_tiles, &grid); if (rc) return rc;
+        RSN_LAUNCH("huff_byte_hist", (k_byte_hist<4, TILE>), grid, dim3(HB), 0, s, d_in, n, n_tiles, d_tile_hist, d_gh);
+    } else {
+        rc = persistent_grid(c, reinterpret_cast<const void *>(k_byte_hist<1, SMALL_TILE>), HB, n_tiles, &grid); if (rc) return rc;
+        RSN_LAUNCH("huff_byte_hist", (k_byte_hist<1, SMALL_TILE>), grid, dim3(HB), 0, s, d_in, n, n_tiles, d_tile_hist, d_gh);
+    }
     void *hp; rc = pinned_buf(c, 256 * 8, &hp); if (rc) return rc;
     unsigned long long *h = (unsigned long long *)hp;
     RSN_HIP(hipMemcpyAsync(h, d_gh, 256 * 8, hipMemcpyDeviceToHost, s));
@@ -928,9 +936,11 @@ int huff_slice_emit(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, const 
             RSN_HIP(hipMemcpyAsync(p, hcodes, 128 + H, hipMemcpyHostToDevice, s));
             fa.codes = (const uint8_t *)p;
         }
-        const dim3 grid((uint32_t)std::min<size_t>(ceil_div(n, FE_SYMS), 256 * 8));
+        dim3 grid;
         switch (L) {
-#define RSN_FE(LL) case LL: RSN_LAUNCH("huff_emit", k_emit_flat<LL>, grid, dim3(HB), 0, s, fa); break;
+#define RSN_FE(LL) case LL:                                                                                      \
+            rc = persistent_grid(c, reinterpret_cast<const void *>(k_emit_flat<LL>), HB, ceil_div(n, FE_SYMS), &grid); if (rc) return rc; \
+            RSN_LAUNCH("huff_emit", k_emit_flat<LL>, grid, dim3(HB), 0, s, fa); break;
             RSN_FE(1) RSN_FE(2) RSN_FE(3) RSN_FE(4) RSN_FE(5) RSN_FE(6) RSN_FE(7)
 #undef RSN_FE
             default: break;

@@ -9,6 +9,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -74,6 +76,32 @@ int func_dyn_lds(Ctx &c, const void *fn, size_t bytes);
             return c.fail(RSN_ERR_DEVICE, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__),  \
                           __FILE__, __LINE__);                                                     \
     } while (0)
+
+// The grid of a persistent kernel (`fn` at `block` threads, no dynamic LDS) over `work` items: the blocks that are resident at once on
+// c.device -- the occupancy query times the CUs -- and never more than `work`.  A constant grid above the resident count runs its
+// surplus blocks as a second wave after the first has done all of its own work: a quarter of a 1 GiB flat encode at 2 blocks a CU
+// (DESIGN 4.5).  Cached per (function, device, block) under one lock: the library is called from many threads at once.
+inline int persistent_grid(Ctx &c, const void *fn, int block, size_t work, dim3 *grid) {
+    struct Entry { const void *fn; int device, block; uint32_t blocks; };
+    static std::mutex mu;
+    static std::vector<Entry> *seen = new std::vector<Entry>();   // never destroyed: callers may still launch while the process exits
+    uint32_t blocks = 0;
+    {
+        std::lock_guard<std::mutex> lk(mu);
+        for (const Entry &e : *seen)
+            if (e.fn == fn && e.device == c.device && e.block == block) { blocks = e.blocks; break; }
+        if (!blocks) {
+            int per_cu = 0, cus = 0;
+            RSN_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, 0));
+            RSN_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device));
+            if (per_cu < 1 || cus < 1) return c.fail(RSN_ERR_DEVICE, "occupancy query: %d blocks of %d threads a CU on %d CUs", per_cu, block, cus);
+            blocks = (uint32_t)per_cu * (uint32_t)cus;
+            seen->push_back({fn, c.device, block, blocks});
+        }
+    }
+    *grid = dim3((uint32_t)std::min<size_t>(work, blocks));
+    return RSN_OK;
+}
 
 // Brackets a kernel launch with events when profiling is on.
 struct ProfScope {
