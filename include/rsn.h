@@ -102,6 +102,22 @@ RSN_API int rsn_lzss_decompress(const uint8_t *in, size_t n, uint8_t **out, size
 RSN_API int rsn_huffman_compress_batch(size_t n_chunks, const uint8_t *const *ins, const size_t *lens,
                                uint8_t **outs, size_t *out_lens);
 
+/* Batch forms of the other three host-buffer calls, for many independent members at once (engine.CompressFiles /
+ * DecompressFiles loop over files, engine.go:150-154,175-185).  outs[i] / out_lens[i] are byte for byte what the single call
+ * (rsn_huffman_decompress, rsn_lzss_compress(..., window, ...), rsn_lzss_decompress) returns for ins[i], empty members included;
+ * each outs[i] is released with rsn_free.  n == 0 returns RSN_OK.  If any member fails, every outs[i] is NULL, the return code
+ * is that of the lowest-index failing member and rsn_last_error() reads "member <i>: " followed by the single call's message.
+ * Null arrays, or a null ins[i] with a non-zero length, return RSN_ERR_ARG; without a device every call returns RSN_ERR_DEVICE.
+ * Small members run many to a launch, a workgroup each, on the calling thread: LZSS compress inputs of at most
+ * 1 KiB (window <= 0xFFFF), LZSS streams of at most 2 KiB that expand to at most 8 KiB, Huffman streams of a byte alphabet
+ * (2 to 128 symbols, codes of at most 32 bits) with at most 16 KiB of payload and 32 KiB of output.  Every other member -- and
+ * one a kernel hands back -- takes the single call's path, in index order; RSN_BATCH_WORKERS / RSN_BATCH_DEVICES deal those
+ * over workers as rsn_huffman_compress_batch deals its chunks.  The same input bytes may be passed to several calls at once. */
+RSN_API int rsn_huffman_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens);
+RSN_API int rsn_lzss_compress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, int64_t window, uint8_t **outs,
+                                    size_t *out_lens);
+RSN_API int rsn_lzss_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens);
+
 /* ONE stream from `shards` slices of ONE input (intra-file sharding): per-slice histograms are summed, one tree and one
  * header are built, every slice is encoded at its exact bit offset (the format has a single front pad, huffman.go:245-255) by a
  * worker of its own, and the pieces are stitched on the way down.  The result is byte for byte rsn_huffman_compress(in, n).

@@ -36,6 +36,7 @@ SYMBOLS = [
     "rsn_device_set", "rsn_device_count", "rsn_last_error", "rsn_version", "rsn_free", "rsn_trim",
     "rsn_huffman_compress", "rsn_huffman_decompress", "rsn_lzss_compress", "rsn_lzss_decompress", "rsn_lzss_compress_legacy",
     "rsn_huffman_compress_batch", "rsn_huffman_compress_sharded",
+    "rsn_huffman_decompress_batch", "rsn_lzss_compress_batch", "rsn_lzss_decompress_batch",
     "rsn_huffman_compress_bound", "rsn_lzss_compress_bound",
     "rsn_huffman_compress_dev", "rsn_huffman_decompress_dev", "rsn_lzss_compress_dev", "rsn_lzss_decompress_dev",
     "rsn_prof_enable", "rsn_prof_reset", "rsn_prof_get", "rsn_huffman_table",
@@ -98,6 +99,9 @@ def lib():
     L.rsn_huffman_slice_cuts.restype = ctypes.c_int64
     L.rsn_huffman_compress_sharded.argtypes = [ctypes.c_char_p, sz, ctypes.c_int, ctypes.POINTER(u8p), szp]
     L.rsn_huffman_compress_batch.argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.POINTER(u8p), szp]
+    L.rsn_huffman_decompress_batch.argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.POINTER(u8p), szp]
+    L.rsn_lzss_compress_batch.argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.c_int64, ctypes.POINTER(u8p), szp]
+    L.rsn_lzss_decompress_batch.argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.POINTER(u8p), szp]
     _lib = L
     return L
 
@@ -118,6 +122,23 @@ def call_host(fn, data, *extra):
         return ctypes.string_at(out, n.value)
     finally:
         L.rsn_free(out)
+
+
+def call_batch(fn, chunks, *extra):
+    """list of bytes in -> list of bytes out through a batch entry point (rsn_*_batch: n, ins, lens, [extra,] outs, out_lens)."""
+    L = lib()
+    chunks = [bytes(c) for c in chunks]
+    k = len(chunks)
+    ins = (ctypes.c_char_p * max(k, 1))(*chunks)
+    lens = (ctypes.c_size_t * max(k, 1))(*[len(c) for c in chunks])
+    outs = (ctypes.POINTER(ctypes.c_uint8) * max(k, 1))()
+    olens = (ctypes.c_size_t * max(k, 1))()
+    check(fn(k, ins, lens, *extra, outs, olens))
+    try:
+        return [ctypes.string_at(outs[i], olens[i]) for i in range(k)]
+    finally:
+        for i in range(k):
+            L.rsn_free(outs[i])
 
 
 def call_dev(fn, d_in, n, d_out, cap, stream, *extra):

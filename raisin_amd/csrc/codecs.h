@@ -47,6 +47,28 @@ int lzss_small_compress(Ctx &c, const uint8_t *in, size_t n, int64_t window, con
 int lzss_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **out, size_t *out_n);
 int lzss_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t out_cap, size_t *out_n);
 
+// ---- many small members in one launch (the batch calls, rsn_api.hip).  The members `idx` (indexes into ins / lens) are packed
+// into the calling thread's pinned staging in groups of at most SMALL_GROUP_BYTES, and each group is ONE launch of a kernel that gives every
+// member a workgroup of its own.  take(i, p, len) receives member i's result (p: in the staging, valid during the call; a non-zero return
+// stops the call with that code); a member the kernel hands back -- or, for Huffman, one the grouped kernel does not take -- is appended to
+// `back`, in index order, for the caller's single call.  A device failure returns its code with *failed = the group's first member.
+struct SmallMember { uint32_t in_off, n, out_off, status_off; };   // byte offsets into the group's staging
+constexpr size_t SMALL_GROUP_BYTES = (size_t)16 << 20;             // staging of one group (a member larger than that is a group of its own)
+constexpr size_t SMALL_GROUP_MAX = 4096;                           // members of one group
+using SmallTake = std::function<int(size_t i, const uint8_t *p, size_t len)>;
+bool lzss_small_compress_takes(size_t n, int64_t window);          // what lzss_small_compress takes (1 KiB, window <= 0xFFFF)
+bool lzss_small_decompress_takes(size_t n);                        // ... lzss_small_decompress (2 KiB of stream)
+bool huff_batch_decompress_may_take(size_t n);                     // a stream short enough to be looked at by huff_batch_decompress_group
+int lzss_small_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
+                              const SmallTake &take, std::vector<size_t> &back, size_t *failed);
+int lzss_small_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
+                                const SmallTake &take, std::vector<size_t> &back, size_t *failed);
+int huff_batch_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
+                                const SmallTake &take, std::vector<size_t> &back, size_t *failed);
+// until every member's status word (base + off[k]) differs from `pending`: polled for 5 ms, then the stream is queried until a time limit --
+// a kernel that never answers is RSN_ERR_DEVICE, the host never spins for ever
+int group_wait(Ctx &c, hipStream_t s, const uint8_t *base, const std::vector<uint32_t> &off, uint32_t pending, const char *what);
+
 // the decoder in SLICES as the stream lands (a host-buffer call, rsn_api.hip): 1 = not a stream for it (a 5C, huge tokens): the caller decodes it whole;
 // RSN_ERR_CAPACITY: it expands beyond out_cap (what the caller's sample promised)
 int lzss_decode_sliced(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t out_cap, size_t *out_n, const SliceStream &st);

@@ -12,6 +12,7 @@
 //               -> host memcpy:                                                              1 launch, no copy command
 // The host does not wait for the stream either: every block ends by setting a word in pinned memory that the host polls (block_done).
 // 64 KiB of the README's text, host buffer to host buffer: compress 89 -> 32 us, decompress 129 -> 52 us (r05).
+// Many streams at once (rsn_huffman_decompress_batch): k_huff_batch_dec, ONE block per stream with k_small_dec's body.
 // For byte alphabets (every symbol < 0x80); everything else -- runes, a single symbol,
 // foreign headers, malformed streams and their error texts -- returns 1 and takes the general path, which words the errors.
 #include <atomic>
@@ -201,10 +202,12 @@ struct SmallDecArgs {
     uint32_t S, T;            // bits per lane; lanes that have a subsequence
     uint32_t flat;            // every code has this length (0: lengths differ): the boundaries are where the arithmetic says -- as many phases as the code has bits, and none to find
     uint32_t seq;             // this call's number: what a block's flag holds once its map is out
-    uint8_t *hout; uint32_t *status;      // status[b]: FLAG_PENDING, then 0 = block b done, 1 = not for this kernel; status[DEC_BLOCKS]: decoded bytes
-    uint32_t *g_maps, *g_flags;           // device memory: [block][32] (exit << 24 | symbols), [block]
+    uint8_t *hout; uint32_t *status;      // status[b]: FLAG_PENDING, then 0 = block b done, 1 = not for this kernel; status[DEC_BLOCKS]: decoded bytes (batch: status[1])
+    uint32_t *g_maps, *g_flags;           // device memory: [block][32] (exit << 24 | symbols), [block] (k_small_dec only)
+    uint32_t out_max, pad_[3];    // batch: bytes the member's output slot takes (k_small_dec: SMALL_MAX)
     uint16_t child[256];      // [2 * node + bit]: 0x8000 | byte for a leaf, else the internal node
 };
+static_assert(sizeof(SmallDecArgs) % 16 == 0, "a batch table entry is copied in dwords and the next one starts 16-aligned");
 
 // a reader of the big-endian words in LDS: the next bits left-aligned in a register, a word fetched for every 32 consumed
 struct BitReader {
@@ -267,8 +270,12 @@ __device__ __noinline__ void emit_path(const uint32_t *pay, const uint32_t *lut,
     }
 }
 __device__ __forceinline__ uint32_t byte_of(uint32_t packed, uint32_t j) { return (packed >> (8 * j)) & 0xFF; }
-__global__ __launch_bounds__(DT) void k_small_dec(SmallDecArgs a) {
-    __shared__ uint32_t s_pay[DEC_PAY_WORDS];                 // big-endian words of this block's part of the stream
+// The decoder of one block.  MULTI: k_small_dec's up to DEC_BLOCKS blocks of one stream, each waiting for the maps of the blocks before it
+// (they are co-resident: 32 blocks).  !MULTI: the whole stream in this one block, which waits for nobody -- the batch kernel's member.
+// PAY_WORDS / OUT_CAP: the stream words and the output bytes one block holds in LDS.
+template <uint32_t PAY_WORDS, uint32_t OUT_CAP, bool MULTI>
+__device__ __forceinline__ void small_dec_body(const SmallDecArgs &a) {
+    __shared__ uint32_t s_pay[PAY_WORDS];                     // big-endian words of this block's part of the stream
     __shared__ uint32_t s_lut[1u << DEC_K];                   // byte | second byte << 8 | length << 16 | length of both << 21 | two << 26, or 0x80000000 | internal node reached after K bits
     __shared__ uint16_t s_child[256];
     __shared__ uint32_t s_st[DL], s_ex[DL], s_n[DL];          // per lane: its starts (offsets from its subsequence's first bit, a byte each), the exits that belong to them (offsets from the next subsequence's first bit), their number
@@ -276,16 +283,16 @@ __global__ __launch_bounds__(DT) void k_small_dec(SmallDecArgs a) {
     __shared__ uint32_t s_ex32[32], s_cn32[32];               // the block's first lane: exit and symbols for every start in its first 32 bits
     __shared__ uint32_t s_wto[5], s_wc[5][4];                 // the wavefronts' maps
     __shared__ uint32_t s_blk[4][2];                          // entry j of lane 1 -> (exit of the block's last lane, symbols of lanes 1..)
-    __shared__ uint32_t s_all[DEC_BLOCKS * 32];               // the maps of the blocks before this one
+    __shared__ uint32_t s_all[MULTI ? DEC_BLOCKS * 32 : 1];   // the maps of the blocks before this one
     __shared__ uint32_t s_true[3];                            // this block's true entry (a start of its first lane), its first output byte, a failure
-    __shared__ __attribute__((aligned(16))) uint8_t s_out[DEC_OUT_CAP + 32];
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x, n_blk = gridDim.x;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[OUT_CAP + 32];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = MULTI ? blockIdx.x : 0u, n_blk = MULTI ? gridDim.x : 1u;
     const uint32_t S = a.S;
     const uint32_t blk_lo = a.p0 + b * DL * S;                                   // this block's first bit
     const uint32_t wlo = blk_lo >> 5;                                           // ... the word it is in: bit positions below are counted from it
     const uint32_t n_words = DL * S / 32 + 6;
     {   // every load of the staging in flight at once (the bytes are in host memory, a round trip is microseconds); the table meanwhile
-        constexpr int PER = (DEC_PAY_WORDS + DT - 1) / DT;
+        constexpr int PER = (PAY_WORDS + DT - 1) / DT;
         uint32_t v[PER];
         const uint32_t ch = tid < a.n_child ? a.child[tid] : 0u;               // (asked for first: the table is built while the stream's words are on their way)
 #pragma unroll
@@ -448,21 +455,23 @@ __global__ __launch_bounds__(DT) void k_small_dec(SmallDecArgs a) {
         for (int k = 0; k < 4; k++) if ((uint32_t)k < n1 && byte_of(s1, k) == off) j = k;
         return j;
     };
-    if (tid < 32) {
-        uint32_t e = s_ex32[tid], c = s_cn32[tid];
-        if (L > 1 && e != OFF_BAD) { const uint32_t j = lane1_index(e); if (j < 4) { c += s_blk[j][1]; e = s_blk[j][0]; } else e = OFF_BAD; }
-        if (lost) e = OFF_BAD;
-        a.g_maps[b * 32 + tid] = e << 24 | (c & 0xFFFFFFu);
+    if constexpr (MULTI) {                                                      // (one block alone: entered at its first bit, nothing to publish or wait for)
+        if (tid < 32) {
+            uint32_t e = s_ex32[tid], c = s_cn32[tid];
+            if (L > 1 && e != OFF_BAD) { const uint32_t j = lane1_index(e); if (j < 4) { c += s_blk[j][1]; e = s_blk[j][0]; } else e = OFF_BAD; }
+            if (lost) e = OFF_BAD;
+            a.g_maps[b * 32 + tid] = e << 24 | (c & 0xFFFFFFu);
+        }
+        __threadfence();
+        __syncthreads();
+        if (tid == 0) {
+            __hip_atomic_store(&a.g_flags[b], a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            for (uint32_t i = 0; i < b; i++) while (__hip_atomic_load(&a.g_flags[i], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != a.seq) __builtin_amdgcn_s_sleep(1);
+        }
+        __syncthreads();
+        for (uint32_t i = tid; i < b * 32; i += DT) s_all[i] = __hip_atomic_load(&a.g_maps[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
     }
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) {
-        __hip_atomic_store(&a.g_flags[b], a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        for (uint32_t i = 0; i < b; i++) while (__hip_atomic_load(&a.g_flags[i], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != a.seq) __builtin_amdgcn_s_sleep(1);
-    }
-    __syncthreads();
-    for (uint32_t i = tid; i < b * 32; i += DT) s_all[i] = __hip_atomic_load(&a.g_maps[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
     if (tid == 0) {
         uint32_t c = 0, base = 0, fail = lost ? 1u : 0u;                        // (block 0 is entered at its first bit)
         for (uint32_t i = 0; i < b && !fail; i++) {
@@ -495,7 +504,7 @@ __global__ __launch_bounds__(DT) void k_small_dec(SmallDecArgs a) {
     if (real && tid + 1 == L) s_true[0] = blk_cnt_hint;
     __syncthreads();
     const uint32_t blk_cnt = s_true[0];
-    if (bad || blk_cnt + 16 > DEC_OUT_CAP || out_base + blk_cnt > SMALL_MAX) { block_done(&a.status[b], 1); return; }
+    if (bad || blk_cnt + (MULTI ? 16u : 0u) > OUT_CAP || out_base + blk_cnt > (MULTI ? SMALL_MAX : a.out_max)) { block_done(&a.status[b], 1); return; }
     const uint32_t shift = out_base & 15;                                       // LDS byte i + shift <-> output byte out_base + i: 16-byte units line up
     if (real) emit_path(s_pay, s_lut, s_child, a.K, end, my_lo + my_start, my_cnt, s_out + my_at + shift);
     __syncthreads();
@@ -508,8 +517,26 @@ __global__ __launch_bounds__(DT) void k_small_dec(SmallDecArgs a) {
             else for (uint32_t x = max(u0, lo); x < min(u1, hi); x++) dst[x] = s_out[x];
         }
     }
-    if (tid == 0 && b + 1 == n_blk) a.status[DEC_BLOCKS] = out_base + blk_cnt;
+    if (tid == 0 && b + 1 == n_blk) a.status[MULTI ? DEC_BLOCKS : 1u] = out_base + blk_cnt;
     block_done(&a.status[b], 0);
+}
+__global__ __launch_bounds__(DT) void k_small_dec(SmallDecArgs a) { small_dec_body<DEC_PAY_WORDS, DEC_OUT_CAP, true>(a); }
+
+// ---------------------------------------------------------------- decompress, many streams in one launch (the batch call)
+// ONE block per member, whatever the grid: the block copies its member's entry of the table (a SmallDecArgs in pinned memory: the tree,
+// the stream's bounds, where its bytes and its output slot are) into LDS, builds its lookup table from it and decodes the whole stream
+// with k_small_dec's lane maps.  No block waits for another.  What one block holds is the member cutoff: HB_PAY_MAX bytes of payload
+// (256 lanes of at most HB_S_MAX bits) and HB_OUT_MAX decoded bytes (its LDS image of the output).
+constexpr uint32_t HB_S_MAX = 512;
+constexpr uint32_t HB_PAY_MAX = DL * HB_S_MAX / 8;              // 16384 bytes of payload (behind the header's "\\\n" and the pad byte)
+constexpr uint32_t HB_OUT_MAX = 32768;                          // bytes of output
+constexpr uint32_t HB_PAY_WORDS = DL * HB_S_MAX / 32 + 8;
+__global__ __launch_bounds__(DT) void k_huff_batch_dec(const SmallDecArgs *__restrict__ tab) {
+    __shared__ SmallDecArgs s_a;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(tab + blockIdx.x);
+    for (uint32_t i = threadIdx.x; i < sizeof(SmallDecArgs) / 4; i += DT) reinterpret_cast<uint32_t *>(&s_a)[i] = src[i];
+    __syncthreads();
+    small_dec_body<HB_PAY_WORDS, HB_OUT_MAX, false>(s_a);
 }
 
 }  // namespace
@@ -587,7 +614,11 @@ int huff_small_compress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **out
     return RSN_OK;
 }
 
-int huff_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **out, size_t *out_n) {
+namespace {
+// The header parsed, the tree built and the kernel's view of the stream (everything in `a` but where its bytes are, the flags and the
+// output): the stream's bytes from in + *A0 on are what the kernel reads, as a.pay.  `lanes`: subsequences the kernel has at most, of at
+// most s_max bits.  1 = not for the small-input decoder (the caller takes the general one, which also words the errors).
+int small_dec_plan(const uint8_t *in, size_t n, uint32_t lanes, uint32_t s_max, SmallDecArgs &a, size_t *A0, unsigned long long *expect_out) {
     if (n < 8 || n > DEC_STREAM_MAX) return 1;
     // ---- strings.SplitN(content, "\\\n", 2) (huffman.go:261); the counts (huffman.go:196-227)
     size_t sep = (size_t)-1;
@@ -605,6 +636,34 @@ int huff_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **o
     HuffTree tree; HuffCodes codes;
     if (!build_tree(syms, tree, msg) || !assign_codes(tree, codes, msg, false)) return 1;
     if (codes.max_len > 32 || codes.max_len == 0) return 1;
+    // ---- the tree as the kernel wants it (every block fills its lookup table from it)
+    a = SmallDecArgs{};
+    const uint32_t A = tree.n_leaves;
+    const size_t n_int = tree.freq.size() - A;
+    for (size_t i = 0; i < n_int; i++) {
+        const int32_t kids[2] = {tree.left[A + i], tree.right[A + i]};
+        for (int b = 0; b < 2; b++) a.child[2 * i + b] = tree.is_leaf(kids[b]) ? (uint16_t)(0x8000u | tree.rune[kids[b]]) : (uint16_t)(kids[b] - (int32_t)A);
+    }
+    a.root = (uint32_t)(tree.root - (int32_t)A);
+    *A0 = pay & ~(size_t)3;
+    a.pay_words = (uint32_t)((n - *A0 + 3) / 4) + 8;
+    a.p0 = (uint32_t)(8 * (pay - *A0) + diff);
+    a.end = (uint32_t)(8 * (pay - *A0) + nbits);
+    a.K = (uint32_t)std::min<unsigned>(codes.max_len, DEC_K); a.n_child = (uint32_t)(2 * n_int);
+    const uint32_t span = a.end - a.p0;
+    a.S = std::max<uint32_t>(64, (uint32_t)round_up(ceil_div(span, lanes), 32));
+    if (a.S > s_max) return 1;
+    a.T = (uint32_t)ceil_div(span, a.S);
+    a.flat = codes.min_len == codes.max_len ? codes.max_len : 0u;
+    *expect_out = expect;
+    return RSN_OK;
+}
+}  // namespace
+
+int huff_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **out, size_t *out_n) {
+    SmallDecArgs a;
+    size_t A0 = 0; unsigned long long expect = 0;
+    if (small_dec_plan(in, n, DEC_BLOCKS * DL, DEC_S_MAX, a, &A0, &expect) != RSN_OK) return 1;
     int rc = ctx_init(c); if (rc) return rc;
     hipStream_t s = c.own_stream;
     void *pp; rc = pinned_buf(c, PIN_BYTES, &pp); if (rc) return rc;
@@ -616,32 +675,13 @@ int huff_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **o
     static thread_local uint32_t seq = 0;
     static thread_local unsigned long long seq_of = 0;
     if (seq_of != c.bufs[38].gen || ++seq == 0) { seq = 1; seq_of = c.bufs[38].gen; RSN_HIP(hipMemsetAsync(dp, 0, (DEC_BLOCKS * 32 + DEC_BLOCKS) * 4, s)); }
-    // ---- the tree as the kernel wants it (every block fills its lookup table from it)
-    const int K = (int)std::min<unsigned>(codes.max_len, DEC_K);
-    SmallDecArgs a{};
-    const uint32_t A = tree.n_leaves;
-    const size_t n_int = tree.freq.size() - A;
-    for (size_t i = 0; i < n_int; i++) {
-        const int32_t kids[2] = {tree.left[A + i], tree.right[A + i]};
-        for (int b = 0; b < 2; b++) a.child[2 * i + b] = tree.is_leaf(kids[b]) ? (uint16_t)(0x8000u | tree.rune[kids[b]]) : (uint16_t)(kids[b] - (int32_t)A);
-    }
-    a.root = (uint32_t)(tree.root - (int32_t)A);
-    const size_t A0 = pay & ~(size_t)3;
     memcpy(pin + PIN_IN, in + A0, n - A0);
     memset(pin + PIN_IN + (n - A0), 0, 64);
     uint32_t *status = (uint32_t *)(pin + PIN_CNT);
     a.pay = (const uint32_t *)(pin + PIN_IN);
-    a.pay_words = (uint32_t)((n - A0 + 3) / 4) + 8;
-    a.p0 = (uint32_t)(8 * (pay - A0) + diff);
-    a.end = (uint32_t)(8 * (pay - A0) + nbits);
-    a.K = (uint32_t)K; a.n_child = (uint32_t)(2 * n_int);
-    const uint32_t span = a.end - a.p0;
-    a.S = std::max<uint32_t>(64, (uint32_t)round_up(ceil_div(span, DEC_BLOCKS * DL), 32));
-    if (a.S > DEC_S_MAX) return 1;
-    a.T = (uint32_t)ceil_div(span, a.S);
     const uint32_t n_blk = (uint32_t)ceil_div(a.T, DL);
     a.seq = seq;
-    a.flat = codes.min_len == codes.max_len ? codes.max_len : 0u;
+    a.out_max = SMALL_MAX;
     a.hout = pin + PIN_OUT; a.status = status;
     a.g_maps = (uint32_t *)dp; a.g_flags = a.g_maps + DEC_BLOCKS * 32;
     for (uint32_t b = 0; b <= DEC_BLOCKS; b++) status[b] = FLAG_PENDING;
@@ -649,6 +689,63 @@ int huff_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **o
     rc = wait_flags(c, s, status, n_blk); if (rc) return rc;
     for (uint32_t b = 0; b < n_blk; b++) if (status[b] != 0) return 1;
     *out = pin + PIN_OUT; *out_n = status[DEC_BLOCKS];
+    return RSN_OK;
+}
+
+bool huff_batch_decompress_may_take(size_t n) { return n >= 8 && n <= HDR_MAX + 8 + HB_PAY_MAX; }
+
+// Members in groups of at most SMALL_GROUP_BYTES of staging: the table (a SmallDecArgs per member), then per member its stream from the
+// 4-byte boundary the kernel reads from (zero behind it), its output slot and two status words (done / handed back, decoded bytes).
+// A stream the one-block decoder cannot take -- runes, over the cutoff, anything small_dec_plan refuses -- goes to `back` untouched.
+int huff_batch_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
+                                const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    struct Plan { size_t i, A0; unsigned long long expect; SmallDecArgs a; };
+    std::vector<Plan> plans;
+    plans.reserve(idx.size());
+    for (size_t i : idx) {
+        Plan p; p.i = i;
+        if (!huff_batch_decompress_may_take(lens[i]) || small_dec_plan(ins[i], lens[i], DL, HB_S_MAX, p.a, &p.A0, &p.expect) != RSN_OK ||
+            p.expect > HB_OUT_MAX) { back.push_back(i); continue; }
+        plans.push_back(p);
+    }
+    if (plans.empty()) return RSN_OK;
+    int rc = ctx_init(c); if (rc) { *failed = plans[0].i; return rc; }
+    hipStream_t s = c.own_stream;
+    auto need = [&](const Plan &p) { return sizeof(SmallDecArgs) + round_up(lens[p.i] - p.A0, 16) + 64 + round_up(p.expect, 16) + 16 + 16; };
+    std::vector<uint32_t> st;
+    std::vector<size_t> taken_back;
+    for (size_t j = 0; j < plans.size();) {
+        size_t k = j, bytes = 0;
+        while (k < plans.size() && k - j < SMALL_GROUP_MAX && (k == j || bytes + need(plans[k]) <= SMALL_GROUP_BYTES)) bytes += need(plans[k++]);
+        const size_t g = k - j;
+        void *pp; rc = pinned_buf(c, bytes + 64, &pp); if (rc) { *failed = plans[j].i; return rc; }
+        uint8_t *base = (uint8_t *)pp;
+        SmallDecArgs *tab = (SmallDecArgs *)base;
+        size_t at = round_up(g * sizeof(SmallDecArgs), 16);
+        st.assign(g, 0);
+        for (size_t q = 0; q < g; q++) {
+            Plan &p = plans[j + q];
+            const size_t n = lens[p.i], sn = n - p.A0;
+            SmallDecArgs &a = tab[q];
+            a = p.a;
+            memcpy(base + at, ins[p.i] + p.A0, sn); memset(base + at + sn, 0, round_up(sn, 16) + 64 - sn);
+            a.pay = (const uint32_t *)(base + at); at += round_up(sn, 16) + 64;
+            a.hout = base + at; a.out_max = (uint32_t)p.expect; at += round_up(p.expect, 16) + 16;
+            a.status = (uint32_t *)(base + at); a.status[0] = FLAG_PENDING; a.status[1] = 0; st[q] = (uint32_t)at; at += 16;
+        }
+        RSN_LAUNCH("huff_batch_dec", k_huff_batch_dec, dim3((uint32_t)g), dim3(DT), 0, s, (const SmallDecArgs *)tab);
+        rc = group_wait(c, s, base, st, FLAG_PENDING, "huffman batch decompress"); if (rc) { *failed = plans[j].i; return rc; }
+        for (size_t q = 0; q < g; q++) {
+            const size_t i = plans[j + q].i;
+            const uint32_t *w = (const uint32_t *)(base + st[q]);
+            if (w[0] != 0) { taken_back.push_back(i); continue; }
+            rc = take(i, tab[q].hout, w[1]); if (rc) { *failed = i; return rc; }
+        }
+        j = k;
+    }
+    // (members refused up front and members handed back, in index order)
+    back.insert(back.end(), taken_back.begin(), taken_back.end());
+    std::sort(back.begin(), back.end());
     return RSN_OK;
 }
 

@@ -13,10 +13,13 @@
 //   decompress  every '<' parses its token (lzss.go:323-364); literal / token bytes get their output offsets from a scan; every output
 //               byte its source (itself, or the byte `pointer` before it), resolved by pointer doubling; DecodeOpeningSymbols
 //               (lzss.go:391-406) from the parity of the 5C run in front of every byte, a scan, the bytes.
+// Many members at once (rsn_lzss_compress_batch / rsn_lzss_decompress_batch): k_lzss_batch_enc / _dec, the same bodies, a block per member
+// of a group packed into pinned memory.
 // What the path does not take returns 1 and goes through the general path, which also words the errors: inputs above the sizes below,
 // streams whose tokens are malformed or point outside the data, outputs above 8 KiB.
 #include <atomic>
 #include <chrono>
+#include <thread>
 
 #include "codecs.h"
 #include "lzss_match.h"
@@ -75,7 +78,8 @@ __device__ __forceinline__ uint32_t sl_digits(uint32_t v) { return v < 10 ? 1u :
 // (r06, measured: the same search spread over sixteen blocks of two wavefronts with the last block to finish walking the chain was no
 //  faster -- 0.05 / 0.12 / 0.18 ms for 256 / 1024 / 2048 bytes against 0.04 / 0.10 / 0.25 here: what a position's search costs is the
 //  candidates of its wavefront's 64 different positions taken one after the other, not the CU's issue rate; hence the size limit.)
-__global__ __launch_bounds__(SLT) void k_lzss_small_enc(const uint8_t *__restrict__ hin, uint32_t n, uint32_t W, uint8_t *__restrict__ hout, uint32_t *__restrict__ flag) {
+// (the codec of one member: the single call's kernel below and the grouped kernel further down are this body, inlined)
+__device__ __forceinline__ void lzss_small_enc_body(const uint8_t *__restrict__ hin, uint32_t n, uint32_t W, uint8_t *__restrict__ hout, uint32_t *__restrict__ flag) {
     __shared__ __attribute__((aligned(16))) uint8_t s_in[SL_IN_MAX + 16];
     __shared__ __attribute__((aligned(16))) uint8_t s_fc[SL_E_MAX + 48];        // the escaped stream (lzss.go:369-389), zeros behind it
     __shared__ uint32_t s_key[SL_E_MAX];                                        // per position: L << 16 | distance (0: a literal)
@@ -195,7 +199,7 @@ __global__ __launch_bounds__(SLT) void k_lzss_small_enc(const uint8_t *__restric
 }
 
 // ---------------------------------------------------------------- decompress
-__global__ __launch_bounds__(SLT) void k_lzss_small_dec(const uint8_t *__restrict__ hin, uint32_t n, uint8_t *__restrict__ hout, uint32_t *__restrict__ flag) {
+__device__ __forceinline__ void lzss_small_dec_body(const uint8_t *__restrict__ hin, uint32_t n, uint8_t *__restrict__ hout, uint32_t *__restrict__ flag) {
     __shared__ __attribute__((aligned(16))) uint8_t s_in[SL_DEC_IN_MAX + 32];
     __shared__ uint8_t s_cov[SL_DEC_IN_MAX + 32];                                // the byte belongs to a token's text
     __shared__ uint16_t s_src[2][SL_DEC_E_MAX];                                  // per escaped byte: where it comes from (itself: a literal)
@@ -302,6 +306,25 @@ __global__ __launch_bounds__(SLT) void k_lzss_small_dec(const uint8_t *__restric
     sl_done(flag, total);
 }
 
+__global__ __launch_bounds__(SLT) void k_lzss_small_enc(const uint8_t *__restrict__ hin, uint32_t n, uint32_t W, uint8_t *__restrict__ hout, uint32_t *__restrict__ flag) {
+    lzss_small_enc_body(hin, n, W, hout, flag);
+}
+__global__ __launch_bounds__(SLT) void k_lzss_small_dec(const uint8_t *__restrict__ hin, uint32_t n, uint8_t *__restrict__ hout, uint32_t *__restrict__ flag) {
+    lzss_small_dec_body(hin, n, hout, flag);
+}
+
+// ---------------------------------------------------------------- many members, one launch (the batch calls)
+// A block per member, the member table in pinned host memory beside the packed members: the block reads its entry, then does exactly what
+// the single call's kernel does for that member.  No block looks at another: the grid may be far larger than what is resident at once.
+__global__ __launch_bounds__(SLT) void k_lzss_batch_enc(const SmallMember *__restrict__ tab, uint8_t *__restrict__ base, uint32_t W) {
+    const SmallMember m = tab[blockIdx.x];
+    lzss_small_enc_body(base + m.in_off, m.n, W, base + m.out_off, reinterpret_cast<uint32_t *>(base + m.status_off));
+}
+__global__ __launch_bounds__(SLT) void k_lzss_batch_dec(const SmallMember *__restrict__ tab, uint8_t *__restrict__ base) {
+    const SmallMember m = tab[blockIdx.x];
+    lzss_small_dec_body(base + m.in_off, m.n, base + m.out_off, reinterpret_cast<uint32_t *>(base + m.status_off));
+}
+
 int sl_wait(Ctx &c, hipStream_t s, const uint32_t *f) {
     const volatile uint32_t *vf = f;
     const auto t0 = std::chrono::steady_clock::now();
@@ -334,6 +357,81 @@ int lzss_small_compress(Ctx &c, const uint8_t *in, size_t n, int64_t window, con
     if (*flag == SL_NOT_MINE) return 1;
     *out = pin + SP_OUT; *out_n = *flag;
     return RSN_OK;
+}
+
+bool lzss_small_compress_takes(size_t n, int64_t window) { return n != 0 && n <= SL_IN_MAX && window <= 0xFFFF; }
+bool lzss_small_decompress_takes(size_t n) { return n != 0 && n <= SL_DEC_IN_MAX; }
+
+int group_wait(Ctx &c, hipStream_t s, const uint8_t *base, const std::vector<uint32_t> &off, uint32_t pending, const char *what) {
+    auto at = [&](size_t k) { return *reinterpret_cast<const volatile uint32_t *>(base + off[k]); };
+    const auto t0 = std::chrono::steady_clock::now();
+    size_t k = 0;                                                                  // every member before k has answered
+    for (uint32_t spins = 1;; spins++) {
+        while (k < off.size() && at(k) != pending) k++;
+        if (k == off.size()) { std::atomic_thread_fence(std::memory_order_acquire); return RSN_OK; }
+        if ((spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
+        __builtin_ia32_pause();
+    }
+    for (;;) {                                                                     // (a large group, or a busy device: the stream, with a limit)
+        const hipError_t e = hipStreamQuery(s);
+        if (e == hipSuccess) break;
+        if (e != hipErrorNotReady) return c.fail(RSN_ERR_DEVICE, "%s: hipStreamQuery: %s", what, hipGetErrorString(e));
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) return c.fail(RSN_ERR_DEVICE, "%s: the grouped kernel did not finish within 20 s", what);
+        std::this_thread::sleep_for(std::chrono::microseconds(20));
+    }
+    for (; k < off.size(); k++) if (at(k) == pending) return c.fail(RSN_ERR_DEVICE, "%s: the grouped kernel finished without an answer for one of its members", what);
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return RSN_OK;
+}
+
+namespace {
+// The members idx in groups: staging = the table, then per member its bytes (zero behind them), its output slot and its status word.
+int lzss_groups(Ctx &c, bool enc, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
+                const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    int rc = ctx_init(c); if (rc) return rc;
+    hipStream_t s = c.own_stream;
+    const char *what = enc ? "lzss batch compress" : "lzss batch decompress";
+    auto need = [&](size_t n) { return sizeof(SmallMember) + round_up(n, 16) + 32 + (enc ? round_up(2 * n, 16) + 16 : SL_DEC_E_MAX + 16) + 16; };
+    std::vector<uint32_t> st;
+    for (size_t j = 0; j < idx.size();) {
+        size_t k = j, bytes = 0;
+        while (k < idx.size() && k - j < SMALL_GROUP_MAX && (k == j || bytes + need(lens[idx[k]]) <= SMALL_GROUP_BYTES)) bytes += need(lens[idx[k++]]);
+        const size_t g = k - j;
+        void *pp; rc = pinned_buf(c, bytes + 64, &pp); if (rc) { *failed = idx[j]; return rc; }
+        uint8_t *base = (uint8_t *)pp;
+        SmallMember *tab = (SmallMember *)base;
+        size_t at = round_up(g * sizeof(SmallMember), 16);
+        st.assign(g, 0);
+        for (size_t q = 0; q < g; q++) {
+            const size_t i = idx[j + q], n = lens[i];
+            SmallMember &m = tab[q];
+            m.n = (uint32_t)n;
+            m.in_off = (uint32_t)at; memcpy(base + at, ins[i], n); memset(base + at + n, 0, round_up(n, 16) + 32 - n); at += round_up(n, 16) + 32;
+            m.out_off = (uint32_t)at; at += enc ? round_up(2 * n, 16) + 16 : SL_DEC_E_MAX + 16;
+            m.status_off = st[q] = (uint32_t)at; *(uint32_t *)(base + at) = SL_PENDING; at += 16;
+        }
+        if (enc) RSN_LAUNCH("lzss_batch_enc", k_lzss_batch_enc, dim3((uint32_t)g), dim3(SLT), 0, s, (const SmallMember *)tab, base, (uint32_t)(window <= 0 ? 0 : window));
+        else RSN_LAUNCH("lzss_batch_dec", k_lzss_batch_dec, dim3((uint32_t)g), dim3(SLT), 0, s, (const SmallMember *)tab, base);
+        rc = group_wait(c, s, base, st, SL_PENDING, what); if (rc) { *failed = idx[j]; return rc; }
+        for (size_t q = 0; q < g; q++) {
+            const size_t i = idx[j + q];
+            const uint32_t v = *(const uint32_t *)(base + st[q]);
+            if (v == SL_NOT_MINE) { back.push_back(i); continue; }
+            rc = take(i, base + tab[q].out_off, v); if (rc) { *failed = i; return rc; }
+        }
+        j = k;
+    }
+    return RSN_OK;
+}
+}  // namespace
+
+int lzss_small_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
+                              const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    return lzss_groups(c, true, idx, ins, lens, window, take, back, failed);
+}
+int lzss_small_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
+                                const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    return lzss_groups(c, false, idx, ins, lens, 0, take, back, failed);
 }
 
 int lzss_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **out, size_t *out_n) {

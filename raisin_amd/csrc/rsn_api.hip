@@ -764,12 +764,13 @@ static int huffman_decompress_piped(const uint8_t *in, size_t n, uint8_t **out, 
                       });
 }
 
-static int rsn_huffman_decompress_impl(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
+// (small = false: a member the batch's grouped kernel has handed back -- the single call's small-input kernel would hand it back too)
+static int rsn_huffman_decompress_impl(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n, bool small = true) {
     Ctx &c = ctx();
     if (!out || !out_n || (!in && n)) return c.fail(RSN_ERR_ARG, "null argument");
     *out = nullptr; *out_n = 0;
     static const bool serial = getenv("RSN_HOST_SERIAL") != nullptr;     // A/B switch (tests): upload, decode, download, one after the other
-    if (n <= 65536 + 2048) {
+    if (small && n <= 65536 + 2048) {
         const uint8_t *p = nullptr; size_t got = 0;
         const int rc = small_result(c, huff_small_decompress(c, in, n, &p, &got), p, got, out, out_n);
         if (rc != 1) return rc;
@@ -781,14 +782,14 @@ static int rsn_huffman_decompress_impl(const uint8_t *in, size_t n, uint8_t **ou
     return huffman_decompress_serial(in, n, out, out_n);
 }
 
-static int rsn_lzss_compress_impl(const uint8_t *in, size_t n, int64_t window, uint8_t **out, size_t *out_n) {
+static int rsn_lzss_compress_impl(const uint8_t *in, size_t n, int64_t window, uint8_t **out, size_t *out_n, bool small = true) {
     // From 128 MiB up, with the engine's kind of window: the pipeline (piped_call) -- sections of a quarter of the input (at most 256 MiB),
     // each encoded as soon as its bytes are up, its tokens on their way down while the next is encoded.  The upload (19 ms per GiB) and the
     // download (12) disappear under the encoder's 31; what does not: the first section's upload and the last one's download.  For inputs in
     // which nothing needs an escape (so the output is at most the input): the encoder checks the input as it lands and lets the first output
     // byte go only when it has seen the last input byte (the upload is done well before the encoder is); an input with a 5C or an FF in it,
     // and every call under RSN_HOST_SERIAL=1, takes the serial call.
-    if (in && out && out_n && n <= 1024) {                                // (the reference's own table is files of 13-25 bytes, README.md:153-167: one launch, lzss_small.hip)
+    if (small && in && out && out_n && n <= 1024) {                       // (the reference's own table is files of 13-25 bytes, README.md:153-167: one launch, lzss_small.hip)
         Ctx &c = ctx(); const uint8_t *p = nullptr; size_t got = 0;
         *out = nullptr; *out_n = 0;
         const int rc = small_result(c, lzss_small_compress(c, in, n, window, &p, &got), p, got, out, out_n);
@@ -832,8 +833,8 @@ static int rsn_lzss_compress_legacy_impl(const uint8_t *in, size_t n, int64_t wi
     return RSN_OK;
 }
 
-static int rsn_lzss_decompress_impl(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
-    if (in && out && out_n && n <= 2048) {                                // (lzss_small.hip: one launch; what it does not take -- malformed, large output -- goes on below)
+static int rsn_lzss_decompress_impl(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n, bool small = true) {
+    if (small && in && out && out_n && n <= 2048) {                       // (lzss_small.hip: one launch; what it does not take -- malformed, large output -- goes on below)
         Ctx &c = ctx(); const uint8_t *p = nullptr; size_t got = 0;
         *out = nullptr; *out_n = 0;
         const int rc = small_result(c, lzss_small_decompress(c, in, n, &p, &got), p, got, out, out_n);
@@ -1010,6 +1011,57 @@ static int batch_on_device(Ctx &c, const std::vector<size_t> &idx, const uint8_t
 }
 }  // namespace
 
+// Items 0 .. n_items - 1 dealt over the batch workers: item k -> worker k mod G, worker w on device (caller's + w mod D) mod visible, where
+// D = RSN_BATCH_DEVICES (default 1) and G = RSN_BATCH_WORKERS (default D), never more workers than items.  Other devices are an opt-in
+// (ADVICE r3): in the one-process-per-GPU model every rank sees every GPU, and a batch that spread by default would put contexts and ~GiB
+// rings on the other ranks' devices.  work(w, idx) runs worker w's items, in order, on the context of the thread it is called on (ctx());
+// one worker, or no helper thread to be had: on the calling thread and the caller's device.  rcs[w] / msgs[w]: worker w's answer.
+struct DealPlan { int visible, n_dev; size_t n_workers; };
+static DealPlan deal_plan(size_t n_items) {
+    DealPlan d;
+    d.visible = 1;
+    if (hipGetDeviceCount(&d.visible) != hipSuccess || d.visible < 1) d.visible = 1;
+    const char *bd = getenv("RSN_BATCH_DEVICES");
+    const int want_dev = !bd || !*bd ? 1 : (!strcmp(bd, "all") ? d.visible : atoi(bd));
+    d.n_dev = std::max(1, std::min(d.visible, want_dev));
+    d.n_workers = std::min<size_t>((size_t)std::max(1, env_int("RSN_BATCH_WORKERS", d.n_dev)), std::max<size_t>(n_items, 1));
+    return d;
+}
+template <class Work>
+static void deal_items(Ctx &c, size_t n_items, Work work, std::vector<int> &rcs, std::vector<std::string> &msgs) {
+    const DealPlan d = deal_plan(n_items);
+    const int visible = d.visible, n_dev = d.n_dev;
+    const size_t n_workers = d.n_workers;
+    rcs.assign(n_workers, RSN_OK);
+    msgs.assign(n_workers, std::string());
+    if (n_workers <= 1) {                                        // one device, one worker, on the caller's own context
+        std::vector<size_t> idx(n_items);
+        for (size_t i = 0; i < n_items; i++) idx[i] = i;
+        rcs[0] = work((size_t)0, idx);
+        if (rcs[0] != RSN_OK) msgs[0] = c.err;
+        return;
+    }
+    std::vector<HelperPool::Handle> workers(n_workers);
+    const int base = c.device;
+    auto share = [&](size_t w, bool own_thread) {                         // worker w's items; on the caller's thread they stay on the caller's device
+        guarded_call<int>([&] {
+            int rc = own_thread ? rsn_device_set((base + (int)(w % (size_t)n_dev)) % visible) : RSN_OK;
+            if (rc == RSN_OK) {
+                std::vector<size_t> idx;
+                for (size_t k = w; k < n_items; k += n_workers) idx.push_back(k);
+                rc = work(w, idx);
+            }
+            rcs[w] = rc;
+            if (rc != RSN_OK) msgs[w] = rsn_last_error();
+            return 0;
+        }, [&](int code, const char *m) { rcs[w] = code; try { msgs[w] = m; } catch (...) {} return 0; });
+    };
+    for (size_t w = 0; w < n_workers; w++) workers[w] = HelperPool::run((base + (int)(w % (size_t)n_dev)) % visible, [&share, w] { share(w, true); });
+    for (size_t w = 0; w < n_workers; w++) if (!workers[w]) share(w, false);   // no thread to be had for that worker: its items on this one
+    for (auto &t : workers) HelperPool::wait(t);
+    (void)hipSetDevice(c.device);
+}
+
 static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
     Ctx &c = ctx();
     if (!ins || !lens || !outs || !out_lens) return c.fail(RSN_ERR_ARG, "null argument");
@@ -1023,44 +1075,10 @@ static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const
         for (size_t k = 0; k < n_chunks; k++) { if (outs[k]) rsn_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
         return c.fail(rc, "%s", msg);
     };
-    // Other devices are an opt-in: in the one-process-per-GPU model every rank sees every GPU, and a batch that spread
-    // by default would put contexts and ~GiB rings on the other ranks' devices.  RSN_BATCH_DEVICES=<d>|all asks for it.
-    int visible = 1;
-    if (hipGetDeviceCount(&visible) != hipSuccess || visible < 1) visible = 1;
-    const char *bd = getenv("RSN_BATCH_DEVICES");
-    const int want_dev = !bd || !*bd ? 1 : (!strcmp(bd, "all") ? visible : atoi(bd));
-    const int n_dev = std::max(1, std::min(visible, want_dev));
-    const size_t n_workers = std::min<size_t>((size_t)std::max(1, env_int("RSN_BATCH_WORKERS", n_dev)), std::max<size_t>(n_chunks, 1));
-    if (n_workers <= 1) {                                        // one device, one pipeline, on the caller's own context
-        std::vector<size_t> idx(n_chunks);
-        for (size_t i = 0; i < n_chunks; i++) idx[i] = i;
-        const int rc = batch_on_device(c, idx, ins, lens, outs, out_lens);
-        if (rc != RSN_OK) { const std::string m = c.err; return undo(rc, m.c_str()); }
-        return RSN_OK;
-    }
-    // chunk k -> worker k mod G; worker w -> device (caller's + w mod n_dev) mod visible
-    std::vector<int> rcs(n_workers, RSN_OK);
-    std::vector<std::string> msgs(n_workers);
-    std::vector<HelperPool::Handle> workers(n_workers);
-    const int base = c.device;
-    auto share = [&](size_t w, bool own_thread) {                         // worker w's chunks; on the caller's thread they stay on the caller's device
-        guarded_call<int>([&] {
-            int rc = own_thread ? rsn_device_set((base + (int)(w % (size_t)n_dev)) % visible) : RSN_OK;
-            if (rc == RSN_OK) {
-                std::vector<size_t> idx;
-                for (size_t k = w; k < n_chunks; k += n_workers) idx.push_back(k);
-                rc = batch_on_device(ctx(), idx, ins, lens, outs, out_lens);
-            }
-            rcs[w] = rc;
-            if (rc != RSN_OK) msgs[w] = rsn_last_error();
-            return 0;
-        }, [&](int code, const char *m) { rcs[w] = code; try { msgs[w] = m; } catch (...) {} return 0; });
-    };
-    for (size_t w = 0; w < n_workers; w++) workers[w] = HelperPool::run((base + (int)(w % (size_t)n_dev)) % visible, [&share, w] { share(w, true); });
-    for (size_t w = 0; w < n_workers; w++) if (!workers[w]) share(w, false);   // no thread to be had for that worker: its chunks on this one
-    for (auto &t : workers) HelperPool::wait(t);
-    (void)hipSetDevice(c.device);
-    for (size_t w = 0; w < n_workers; w++) if (rcs[w] != RSN_OK) return undo(rcs[w], msgs[w].c_str());
+    std::vector<int> rcs;
+    std::vector<std::string> msgs;
+    deal_items(c, n_chunks, [&](size_t, const std::vector<size_t> &idx) { return batch_on_device(ctx(), idx, ins, lens, outs, out_lens); }, rcs, msgs);
+    for (size_t w = 0; w < rcs.size(); w++) if (rcs[w] != RSN_OK) return undo(rcs[w], msgs[w].c_str());
     return RSN_OK;
 }
 
@@ -1090,6 +1108,105 @@ struct ShardSync {
     }
 };
 }  // namespace
+
+
+// ---- the batch forms of the other three host-buffer calls (rsn.h).  Members that a grouped kernel takes run on the calling
+// thread, ONE launch per group of many (lzss_small.hip / huff_small.hip: a workgroup per member), so rsn_prof_* sees those launches; the
+// rest -- a member a kernel handed back, larger ones, another alphabet -- goes through the single call's implementation, in index order,
+// dealt over the batch workers like the compress batch's chunks (deal_items).  Every outs[i] is what the single call returns for ins[i]; on
+// any failure every outs[i] is NULL and the answer is the lowest-index failing member's code, its message prefixed "member <i>: ".
+// `takes(i)`: member i is for the grouped kernel; `group`: runs those; `single(i, small)`: the single call for member i (small = false:
+// the member was handed back by a grouped kernel whose body the single call's small path shares).
+template <class Takes, class Group, class Single>
+static int small_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens, bool back_skips_small,
+                       Takes takes, Group group, Single single) {
+    Ctx &c = ctx();
+    if (n == 0) return RSN_OK;
+    if (!ins || !lens || !outs || !out_lens) return c.fail(RSN_ERR_ARG, "null argument");
+    for (size_t i = 0; i < n; i++) { outs[i] = nullptr; out_lens[i] = 0; }
+    for (size_t i = 0; i < n; i++) if (!ins[i] && lens[i]) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
+    int rc = ctx_init(c); if (rc) return rc;                              // (no device: RSN_ERR_DEVICE -- there is no CPU path)
+    constexpr size_t NONE = (size_t)-1;
+    struct Fail { size_t at = NONE; int rc = RSN_OK; std::string msg; };
+    Fail f;
+    auto note = [](Fail &x, size_t i, int code, const std::string &m) { if (i < x.at) { x.at = i; x.rc = code; x.msg = m; } };
+    std::vector<size_t> grouped, rest, back;
+    for (size_t i = 0; i < n; i++) (takes(i) ? grouped : rest).push_back(i);
+    if (!grouped.empty()) {
+        size_t failed = NONE;
+        const SmallTake take = [&](size_t i, const uint8_t *p, size_t len) -> int {
+            uint8_t *r = (uint8_t *)result_alloc(len);
+            if (!r) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", len);
+            memcpy(r, p, len);
+            outs[i] = r; out_lens[i] = len;
+            return RSN_OK;
+        };
+        rc = group(c, grouped, take, back, &failed);
+        if (rc != RSN_OK) note(f, failed, rc, c.err);
+    }
+    std::vector<char> handed(back_skips_small ? n : 0, 0);
+    for (size_t i : back) if (back_skips_small) handed[i] = 1;
+    rest.insert(rest.end(), back.begin(), back.end());
+    std::sort(rest.begin(), rest.end());
+    while (!rest.empty() && rest.back() > f.at) rest.pop_back();          // (what lies behind a known failure cannot change the answer)
+    if (!rest.empty()) {
+        std::atomic<size_t> stop{f.at};                                   // the lowest failing member found so far: workers do not go past it
+        std::vector<int> rcs;
+        std::vector<std::string> msgs;
+        std::vector<Fail> wf;
+        std::vector<size_t> cur;
+        wf.resize(deal_plan(rest.size()).n_workers);                      // (deal_items deals over exactly as many)
+        cur.assign(wf.size(), NONE);
+        deal_items(c, rest.size(), [&](size_t w, const std::vector<size_t> &idx) -> int {
+            for (size_t k : idx) {
+                const size_t i = rest[k];
+                if (i > stop.load()) break;
+                cur[w] = i;
+                const int r = single(i, !(back_skips_small && handed[i]));
+                if (r != RSN_OK) {
+                    note(wf[w], i, r, ctx().err);
+                    for (size_t s0 = stop.load(); i < s0 && !stop.compare_exchange_weak(s0, i);) {}
+                    break;
+                }
+            }
+            return RSN_OK;
+        }, rcs, msgs);
+        for (size_t w = 0; w < rcs.size() && w < wf.size(); w++) {
+            if (wf[w].at != NONE) note(f, wf[w].at, wf[w].rc, wf[w].msg);
+            else if (rcs[w] != RSN_OK) note(f, cur[w] == NONE ? 0 : cur[w], rcs[w], msgs[w]);   // (thrown: the member the worker was on)
+        }
+    }
+    if (f.at == NONE) return RSN_OK;
+    for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
+    return c.fail(f.rc, "member %zu: %s", f.at, f.msg.c_str());
+}
+
+static int rsn_huffman_decompress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
+    return small_batch(n, ins, lens, outs, out_lens, false,
+                       [&](size_t i) { return huff_batch_decompress_may_take(lens[i]); },
+                       [&](Ctx &c, const std::vector<size_t> &idx, const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+                           return huff_batch_decompress_group(c, idx, ins, lens, take, back, failed);
+                       },
+                       [&](size_t i, bool small) { return rsn_huffman_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small); });
+}
+
+static int rsn_lzss_compress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, int64_t window, uint8_t **outs, size_t *out_lens) {
+    return small_batch(n, ins, lens, outs, out_lens, true,
+                       [&](size_t i) { return lzss_small_compress_takes(lens[i], window); },
+                       [&](Ctx &c, const std::vector<size_t> &idx, const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+                           return lzss_small_compress_group(c, idx, ins, lens, window, take, back, failed);
+                       },
+                       [&](size_t i, bool small) { return rsn_lzss_compress_impl(ins[i], lens[i], window, &outs[i], &out_lens[i], small); });
+}
+
+static int rsn_lzss_decompress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
+    return small_batch(n, ins, lens, outs, out_lens, true,
+                       [&](size_t i) { return lzss_small_decompress_takes(lens[i]); },
+                       [&](Ctx &c, const std::vector<size_t> &idx, const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+                           return lzss_small_decompress_group(c, idx, ins, lens, take, back, failed);
+                       },
+                       [&](size_t i, bool small) { return rsn_lzss_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small); });
+}
 
 static int rsn_huffman_compress_sharded_impl(const uint8_t *in, size_t n, int shards, uint8_t **out, size_t *out_n) {
     Ctx &c = ctx();
@@ -1337,6 +1454,24 @@ int rsn_lzss_decompress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_
 int rsn_huffman_compress_batch(size_t n_chunks, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
     return guarded_call<int>([&] { return rsn_huffman_compress_batch_impl(n_chunks, ins, lens, outs, out_lens); }, [&](int code, const char *m) {
         if (outs && out_lens) for (size_t k = 0; k < n_chunks; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
+        return boundary_error(code, m);
+    });
+}
+int rsn_huffman_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
+    return guarded_call<int>([&] { return rsn_huffman_decompress_batch_impl(n, ins, lens, outs, out_lens); }, [&](int code, const char *m) {
+        if (outs && out_lens) for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
+        return boundary_error(code, m);
+    });
+}
+int rsn_lzss_compress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, int64_t window, uint8_t **outs, size_t *out_lens) {
+    return guarded_call<int>([&] { return rsn_lzss_compress_batch_impl(n, ins, lens, window, outs, out_lens); }, [&](int code, const char *m) {
+        if (outs && out_lens) for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
+        return boundary_error(code, m);
+    });
+}
+int rsn_lzss_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
+    return guarded_call<int>([&] { return rsn_lzss_decompress_batch_impl(n, ins, lens, outs, out_lens); }, [&](int code, const char *m) {
+        if (outs && out_lens) for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
         return boundary_error(code, m);
     });
 }

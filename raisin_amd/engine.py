@@ -89,13 +89,63 @@ def CompressFile(algorithms, path, output):
 BATCH_BYTES = 4 << 30        # files are read and batched in groups of at most this many bytes: N x 1 GiB inputs never all sit in memory
 
 
+# one-layer lists that go through a batch call: compress (huffman: rsn_huffman_compress_batch; lzss: rsn_lzss_compress_batch, small files many
+# to a launch) and decompress (rsn_lzss_decompress_batch / rsn_huffman_decompress_batch)
+_COMPRESS_BATCH = {"huffman": huffman.CompressBatch, "lzss": lambda datas: lz.CompressAsyncBatch(datas, lz.DefaultWindowSize)}
+_DECOMPRESS_BATCH = {"huffman": huffman.DecompressBatch, "lzss": lz.DecompressBatch}
+
+
+def _groups(files, take_empty):
+    """The files in groups of at most BATCH_BYTES, read in order: yields (group, datas, bad) -- bad: files[i] right behind the group is
+    empty (when the batch does not take empty files) or cannot be read, and is the per-file loop's to meet, in order, after the group."""
+    i = 0
+    while i < len(files):
+        group, datas, size = [], [], 0
+        bad = None
+        while i < len(files):
+            try:
+                fsize = os.path.getsize(files[i])
+                if (fsize == 0 and not take_empty) or (group and size + fsize > BATCH_BYTES):
+                    bad = files[i] if fsize == 0 and not take_empty else None
+                    break
+                d = open(files[i], "rb").read()
+            except OSError:                                  # (ADVICE r4: a file that cannot be read ends the group -- the ones before it are
+                bad = files[i]                               #  done and written first, as the reference's loop would have, engine.go:150-154)
+                break
+            group.append(files[i]); datas.append(d); size += len(d); i += 1
+        yield group, datas, bad
+        if bad is not None:
+            i += 1
+
+
 def CompressFiles(algorithms, files, extension):
-    """engine.go:150-154: one .rsn per input, file after file.  Several files under one Huffman layer go through
-    rsn_huffman_compress_batch -- upload / encode / download overlapped on the device -- in GROUPS of at most BATCH_BYTES, in the loop's
-    order and with the loop's semantics: a file's lines are printed and its .rsn is written before the next group is read, and a file
-    the batch cannot take (empty: the reference panics in heap.Pop, huffman.go:102) or a group that fails falls back to the per-file
-    loop, which stops at the failing file with every earlier .rsn already on disk -- exactly where the reference's loop would stop."""
+    """engine.go:150-154: one .rsn per input, file after file.  Several files under one Huffman or one LZSS layer go through the batch call
+    (Huffman: upload / encode / download overlapped on the device; LZSS: small files many to a launch) in GROUPS of at most BATCH_BYTES, in
+    the loop's order and with the loop's semantics: a file's lines are printed and its .rsn is written before the next group is read, and a
+    file the batch cannot take (empty under Huffman: the reference panics in heap.Pop, huffman.go:102) or a group that fails falls back to
+    the per-file loop, which stops at the failing file with every earlier .rsn already on disk -- exactly where the reference's loop would stop."""
     files = list(files)
+    if len(files) > 1 and list(algorithms) == ["lzss"]:
+        for group, datas, bad in _groups(files, take_empty=True):
+            outs = None
+            if len(group) > 1:
+                try:
+                    outs = _COMPRESS_BATCH["lzss"](datas)
+                except Exception:                               # noqa: BLE001 -- the loop finds the file that fails, after writing the ones before it
+                    outs = None
+            if outs is None:
+                for f in group:
+                    CompressFile(algorithms, f, f + extension)
+            else:
+                for f, data, out in zip(group, datas, outs):
+                    print("Compressing...")
+                    open(f + extension, "wb").write(out)
+                    print("Original bytes: %d" % len(data))
+                    print("Compressed bytes: %d" % len(out))
+                    print("Compression ratio: %.2f%%" % (len(out) / len(data) * 100 if data else float("nan")))
+            if bad is not None:
+                CompressFile(algorithms, bad, bad + extension)   # raises like the reference panics; the earlier files are written
+        return
     if len(files) > 1 and list(algorithms) == ["huffman"]:
         i = 0
         while i < len(files):
@@ -147,11 +197,39 @@ def DecompressFile(algorithms, path, output):
 
 
 def DecompressFiles(algorithms, files, extension):
-    for f in files:
+    """engine.go:175-185: file after file.  Several files under ONE layer (lzss or huffman) go through that codec's batch call in groups of
+    at most BATCH_BYTES, with the loop's semantics: outputs in order, a group written before the next is read, and a group that fails is
+    done again by the loop, which stops at the failing file with everything before it written and nothing after it."""
+    files = list(files)
+
+    def out_path(f):
         path = f + extension
         if extension.strip() in ("", "."):
             path = os.path.splitext(f)[0]
-        DecompressFile(algorithms, f, path)
+        return path
+
+    algorithms = list(algorithms)
+    if len(files) > 1 and len(algorithms) == 1 and algorithms[0] in _DECOMPRESS_BATCH:
+        for group, datas, bad in _groups(files, take_empty=True):
+            outs = None
+            if len(group) > 1:
+                try:
+                    outs = _DECOMPRESS_BATCH[algorithms[0]](datas)
+                except Exception:                               # noqa: BLE001 -- the loop finds the file that fails, after writing the ones before it
+                    outs = None
+            if outs is None:
+                for f in group:
+                    DecompressFile(algorithms, f, out_path(f))
+            else:
+                for f, out in zip(group, outs):
+                    print("Decompressing...")
+                    with open(out_path(f), "wb") as fh:
+                        fh.write(out)
+            if bad is not None:
+                DecompressFile(algorithms, bad, out_path(bad))   # raises where the loop would
+        return
+    for f in files:
+        DecompressFile(algorithms, f, out_path(f))
 
 
 @dataclass

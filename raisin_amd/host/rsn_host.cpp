@@ -212,12 +212,14 @@ int main(int argc, char **argv) {
                 printf("Original bytes: %zu\nCompressed bytes: %zu\nCompression ratio: %.2f%%\n", data.size(), c.size(), (float)c.size() / (float)data.size() * 100.f);   // engine.go:166-169
             };
             auto one_file = [&](const std::string &f) { one_data(f, read_file(f)); };
-            if (files.size() > 1 && algs.size() == 1 && algs[0] == "huffman") {
+            if (files.size() > 1 && algs.size() == 1 && (algs[0] == "huffman" || algs[0] == "lzss")) {
                 // engine.CompressFiles loops over the files, one .rsn each (engine.go:150-154).  Independent inputs of one Huffman layer go
                 // through the batch entry point -- upload, encode and download overlapped on the device (and dealt over devices with
                 // RSN_BATCH_DEVICES) -- in GROUPS of at most 4 GiB, in the loop's order and with its semantics: a group's files are written
                 // before the next group is read, an empty file (the reference panics, huffman.go:102) ends a group, and a group that fails
-                // is done again by the loop, which stops at the failing file with everything before it on disk.
+                // is done again by the loop, which stops at the failing file with everything before it on disk.  One LZSS layer: the same
+                // groups through rsn_lzss_compress_batch (small files many to a launch); its empty files take the loop's turn too.
+                const bool huff = algs[0] == "huffman";
                 constexpr size_t BATCH_BYTES = (size_t)4 << 30;
                 size_t i = 0;
                 Bytes held; bool have_held = false;                 // a file that overflowed the group before: read once, kept for this group
@@ -240,7 +242,9 @@ int main(int argc, char **argv) {
                         std::vector<const uint8_t *> ins; std::vector<size_t> lens;
                         for (auto &d : datas) { ins.push_back(d.data()); lens.push_back(d.size()); }
                         std::vector<uint8_t *> outs(group.size(), nullptr); std::vector<size_t> out_lens(group.size(), 0);
-                        if (rsn_huffman_compress_batch(group.size(), ins.data(), lens.data(), outs.data(), out_lens.data()) == RSN_OK) {
+                        const int brc = huff ? rsn_huffman_compress_batch(group.size(), ins.data(), lens.data(), outs.data(), out_lens.data())
+                                             : rsn_lzss_compress_batch(group.size(), ins.data(), lens.data(), RSN_LZSS_DEFAULT_WINDOW, outs.data(), out_lens.data());
+                        if (brc == RSN_OK) {
                             for (size_t k = 0; k < group.size(); k++) {
                                 printf("Compressing...\n");
                                 write_file(out_name(group[k]), Bytes(outs[k], outs[k] + out_lens[k]));
@@ -259,11 +263,62 @@ int main(int argc, char **argv) {
         } else if (cmd == "decompress") {
             if (algorithm.empty()) algorithm = "lzss,huffman";
             const auto algs = split(algorithm, ',');
-            for (auto &f : files) {
+            auto out_of = [&](const std::string &f) {
                 std::string o = trim_ext(f);                                                        // cli.go:141-143
                 if (files.size() == 1 && !out.empty()) o = out;
                 if (files.size() > 1 && !outext.empty()) o = f + "." + outext;
                 if (o.empty() || o == f) throw std::runtime_error("output path '" + o + "' is empty or is the input itself (" + f + "): give -out / -outext");
+                return o;
+            };
+            auto one_data = [&](const std::string &f, const Bytes &data) {
+                const std::string o = out_of(f);
+                printf("Decompressing...\n");
+                write_file(o, engine::decompress(data, algs));
+            };
+            if (files.size() > 1 && algs.size() == 1 && (algs[0] == "huffman" || algs[0] == "lzss")) {
+                // One layer: the files through its batch call (rsn_huffman_decompress_batch / rsn_lzss_decompress_batch: small streams many
+                // to a launch) in groups of at most 4 GiB, with the loop's semantics -- outputs written in order, a group before the next is
+                // read; a file that cannot be read (or has no output name) ends its group and takes the loop's turn; a group that fails is
+                // done again by the loop, which stops at the failing file with everything before it written and nothing after it.
+                constexpr size_t BATCH_BYTES = (size_t)4 << 30;
+                const bool huff = algs[0] == "huffman";
+                size_t i = 0;
+                Bytes held; bool have_held = false;
+                while (i < files.size()) {
+                    std::vector<std::string> group; std::vector<Bytes> datas; size_t size = 0;
+                    bool bad = false;
+                    while (i < files.size()) {
+                        Bytes d;
+                        if (have_held) { d = std::move(held); have_held = false; }
+                        else {
+                            try { (void)out_of(files[i]); d = read_file(files[i]); }
+                            catch (const std::exception &) { bad = true; break; }
+                        }
+                        if (!group.empty() && size + d.size() > BATCH_BYTES) { held = std::move(d); have_held = true; break; }
+                        size += d.size(); group.push_back(files[i]); datas.push_back(std::move(d)); i++;
+                    }
+                    bool done = false;
+                    if (group.size() > 1) {
+                        std::vector<const uint8_t *> ins; std::vector<size_t> lens;
+                        for (auto &d : datas) { ins.push_back(d.data()); lens.push_back(d.size()); }
+                        std::vector<uint8_t *> outs(group.size(), nullptr); std::vector<size_t> out_lens(group.size(), 0);
+                        const int brc = huff ? rsn_huffman_decompress_batch(group.size(), ins.data(), lens.data(), outs.data(), out_lens.data())
+                                             : rsn_lzss_decompress_batch(group.size(), ins.data(), lens.data(), outs.data(), out_lens.data());
+                        if (brc == RSN_OK) {
+                            for (size_t k = 0; k < group.size(); k++) {
+                                printf("Decompressing...\n");
+                                write_file(out_of(group[k]), Bytes(outs[k], outs[k] + out_lens[k]));
+                                rsn_free(outs[k]);
+                            }
+                            done = true;
+                        }
+                    }
+                    if (!done) for (size_t k = 0; k < group.size(); k++) one_data(group[k], datas[k]);
+                    if (bad) { (void)out_of(files[i]); one_data(files[i], read_file(files[i])); i++; }   // throws where the loop would; everything before it is written
+                }
+            } else
+            for (auto &f : files) {
+                const std::string o = out_of(f);
                 printf("Decompressing...\n");
                 write_file(o, engine::decompress(read_file(f), algs));
             }

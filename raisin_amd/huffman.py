@@ -40,6 +40,19 @@ def CompressBatch(chunks):
             L.rsn_free(outs[i])
 
 
+# What one workgroup of the batch decoder holds (csrc/huff_small.hip HB_PAY_MAX / HB_OUT_MAX): a stream with more payload
+# bytes (behind the header's backslash-newline and the pad byte), or more output, goes through the single call's path inside the batch.
+BATCH_GROUP_PAYLOAD_MAX = 16384
+BATCH_GROUP_OUTPUT_MAX = 32768
+
+
+def DecompressBatch(streams):
+    """Decompress(stream) for every stream of the list in one call (rsn_huffman_decompress_batch): small streams many to a launch, a
+    workgroup each; the rest through the single call's path.  Each result equals Decompress(stream); a failing stream raises for the
+    whole list (the message names the lowest failing index: "member <i>: ...")."""
+    return _lib.call_batch(_lib.lib().rsn_huffman_decompress_batch, streams)
+
+
 class Writer:
     """huffman.go:368-386: Write compresses the whole buffer once and returns len(compressed)."""
 

@@ -23,6 +23,18 @@ def Decompress(fileContents, useProgressBar=False):
     return _lib.call_host(_lib.lib().rsn_lzss_decompress, fileContents)
 
 
+def CompressAsyncBatch(files, maxSearchBufferLength=DefaultWindowSize):
+    """CompressAsync(f, False, maxSearchBufferLength) for every buffer of the list in one call (rsn_lzss_compress_batch): inputs of at most
+    1 KiB many to a launch, a workgroup each; the rest through the single call's path.  Each result equals CompressAsync(f)."""
+    return _lib.call_batch(_lib.lib().rsn_lzss_compress_batch, files, int(maxSearchBufferLength))
+
+
+def DecompressBatch(streams):
+    """Decompress(s) for every stream of the list in one call (rsn_lzss_decompress_batch); each result equals Decompress(s).  A failing
+    stream raises for the whole list (the message names the lowest failing index: "member <i>: ...")."""
+    return _lib.call_batch(_lib.lib().rsn_lzss_decompress_batch, streams)
+
+
 class Writer:
     """lzss.go:29-61"""
 

@@ -1,0 +1,117 @@
+"""The batch calls against a loop of single calls on many SMALL members, host buffer to host buffer.
+
+For K in {16, 256, 4096} members: LZSS compress and decompress of the reference README's 13-byte and 25-byte files and of 1 KiB of text,
+Huffman decompress of those and of 16 KiB and 64 KiB of text.  Every time is the median of REPS runs of the whole list; both sides go
+through ctypes the same way.  `--single` first prints the single calls' own times per call (the small-input paths the batch shares its
+kernels with).  Usage: python scripts/batch_small_bench.py [--single] [--reps R] [--k 16,256,4096]"""
+import argparse
+import ctypes
+import os
+import random
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from raisin_amd import _lib, huffman, lz  # noqa: E402
+
+README = [b"Hello world!\n", b"abcabcabcabcabcabcabcabc\n"]
+WORDS = [b"the", b"quick", b"brown", b"fox", b"jumps", b"over", b"lazy", b"dog", b"compression", b"a", b"I", b"Sam", b"ham"]
+
+
+def text(seed, n):
+    rng = random.Random(seed)
+    t = bytearray()
+    while len(t) < n:
+        t += rng.choice(WORDS) + rng.choice([b" ", b"\n", b", ", b". "])
+    return bytes(t[:n])
+
+
+def members(kind, k):
+    if kind == "13B":
+        return [README[0]] * k
+    if kind == "25B":
+        return [README[1]] * k
+    distinct = [text(i, {"1KiB": 1024, "16KiB": 16 << 10, "64KiB": 64 << 10}[kind]) for i in range(min(k, 64))]
+    return [distinct[i % len(distinct)] for i in range(k)]
+
+
+def timed(fn, reps):
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append(time.perf_counter() - t0)
+    return statistics.median(ts)
+
+
+def batch_fn(L, name, bufs, extra):
+    k = len(bufs)
+    ins = (ctypes.c_char_p * k)(*bufs)
+    lens = (ctypes.c_size_t * k)(*[len(b) for b in bufs])
+    outs = (ctypes.POINTER(ctypes.c_uint8) * k)()
+    olens = (ctypes.c_size_t * k)()
+    fn = getattr(L, name)
+
+    def run():
+        _lib.check(fn(k, ins, lens, *extra, outs, olens))
+        for i in range(k):
+            L.rsn_free(outs[i])
+    return run
+
+
+def loop_fn(L, name, bufs, extra):
+    fn = getattr(L, name)
+    out, n = ctypes.POINTER(ctypes.c_uint8)(), ctypes.c_size_t()
+    lens = [len(b) for b in bufs]
+
+    def run():
+        for b, m in zip(bufs, lens):
+            _lib.check(fn(b, m, *extra, ctypes.byref(out), ctypes.byref(n)))
+            L.rsn_free(out)
+    return run
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--single", action="store_true")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--k", default="16,256,4096")
+    a = ap.parse_args()
+    L = _lib.lib()
+    print("library: %s" % os.path.basename(_lib.LIB_PATH))
+    if a.single:
+        print("single calls, median of %d x 200 calls, us per call:" % a.reps)
+        cases = [("lzss compress", "rsn_lzss_compress", README[0], (4096,)), ("lzss compress", "rsn_lzss_compress", README[1], (4096,)),
+                 ("lzss compress", "rsn_lzss_compress", text(0, 1024), (4096,)),
+                 ("lzss decompress", "rsn_lzss_decompress", lz.CompressAsync(README[0]), ()),
+                 ("lzss decompress", "rsn_lzss_decompress", lz.CompressAsync(README[1]), ()),
+                 ("lzss decompress", "rsn_lzss_decompress", lz.CompressAsync(text(0, 1024)), ()),
+                 ("huffman decompress", "rsn_huffman_decompress", huffman.Compress(text(0, 16 << 10)), ()),
+                 ("huffman decompress", "rsn_huffman_decompress", huffman.Compress(text(0, 64 << 10)), ())]
+        for label, name, data, extra in cases:
+            run = loop_fn(L, name, [data] * 200, extra)
+            run()
+            print("  %-20s %6d B in: %7.1f us" % (label, len(data), timed(run, a.reps) / 200 * 1e6))
+    print("%-20s %6s %5s %10s %10s %8s" % ("call", "member", "K", "batch ms", "loop ms", "loop/batch"))
+    plan = [("lzss compress", "rsn_lzss_compress_batch", "rsn_lzss_compress", ("13B", "25B", "1KiB"), (4096,)),
+            ("lzss decompress", "rsn_lzss_decompress_batch", "rsn_lzss_decompress", ("13B", "25B", "1KiB"), ()),
+            ("huffman decompress", "rsn_huffman_decompress_batch", "rsn_huffman_decompress", ("13B", "25B", "1KiB", "16KiB", "64KiB"), ())]
+    for label, bname, sname, kinds, extra in plan:
+        for kind in kinds:
+            for k in [int(x) for x in a.k.split(",")]:
+                src = members(kind, k)
+                if label == "lzss decompress":
+                    bufs = lz.CompressAsyncBatch(src)
+                elif label == "huffman decompress":
+                    bufs = [huffman.Compress(s) for s in src]
+                else:
+                    bufs = src
+                b, lp = batch_fn(L, bname, bufs, extra), loop_fn(L, sname, bufs, extra)
+                b(), lp()
+                tb, tl = timed(b, a.reps), timed(lp, a.reps)
+                print("%-20s %6s %5d %10.3f %10.3f %8.1fx" % (label, kind, k, tb * 1e3, tl * 1e3, tl / tb), flush=True)
+
+
+if __name__ == "__main__":
+    main()
