@@ -98,6 +98,9 @@ RSN_API int rsn_lzss_decompress(const uint8_t *in, size_t n, uint8_t **out, size
  * device + w) mod visible.  On each device chunk k+1's upload, chunk k's encode and chunk k-1's
  * download run at once.  Nothing is exchanged between devices.  Each outs[i] equals what
  * rsn_huffman_compress() returns for ins[i]; on any error every outs[i] is NULL.
+ * When at least two chunks are of 2 B to 16 KiB, those run grouped first, on the calling thread:
+ * one launch per group, a workgroup per chunk that builds the chunk's own tree.
+ * A grouped chunk with a byte >= 0x80 or a single distinct byte is handed back to the pipeline.
  * (RSN_BATCH_WORKERS, RSN_BATCH_KEEP_MIB: see rsn_api.hip / INTEGRATION.md.) */
 RSN_API int rsn_huffman_compress_batch(size_t n_chunks, const uint8_t *const *ins, const size_t *lens,
                                uint8_t **outs, size_t *out_lens);

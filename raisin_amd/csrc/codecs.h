@@ -59,12 +59,15 @@ using SmallTake = std::function<int(size_t i, const uint8_t *p, size_t len)>;
 bool lzss_small_compress_takes(size_t n, int64_t window);          // what lzss_small_compress takes (1 KiB, window <= 0xFFFF)
 bool lzss_small_decompress_takes(size_t n);                        // ... lzss_small_decompress (2 KiB of stream)
 bool huff_batch_decompress_may_take(size_t n);                     // a stream short enough to be looked at by huff_batch_decompress_group
+bool huff_batch_compress_takes(size_t n);                          // an input huff_batch_compress_group looks at (2 B to 16 KiB)
 int lzss_small_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
                               const SmallTake &take, std::vector<size_t> &back, size_t *failed);
 int lzss_small_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
                                 const SmallTake &take, std::vector<size_t> &back, size_t *failed);
 int huff_batch_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
                                 const SmallTake &take, std::vector<size_t> &back, size_t *failed);
+int huff_batch_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
+                              const SmallTake &take, std::vector<size_t> &back, size_t *failed);
 // until every member's status word (base + off[k]) differs from `pending`: polled for 5 ms, then the stream is queried until a time limit --
 // a kernel that never answers is RSN_ERR_DEVICE, the host never spins for ever
 int group_wait(Ctx &c, hipStream_t s, const uint8_t *base, const std::vector<uint32_t> &off, uint32_t pending, const char *what);

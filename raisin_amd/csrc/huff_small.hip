@@ -13,6 +13,7 @@
 // The host does not wait for the stream either: every block ends by setting a word in pinned memory that the host polls (block_done).
 // 64 KiB of the README's text, host buffer to host buffer: compress 89 -> 32 us, decompress 129 -> 52 us (r05).
 // Many streams at once (rsn_huffman_decompress_batch): k_huff_batch_dec, ONE block per stream with k_small_dec's body.
+// Many inputs at once (rsn_huffman_compress_batch): k_huff_batch_enc, ONE block per input of 2 B to 16 KiB that builds its own tree.
 // For byte alphabets (every symbol < 0x80); everything else -- runes, a single symbol,
 // foreign headers, malformed streams and their error texts -- returns 1 and takes the general path, which words the errors.
 #include <atomic>
@@ -21,6 +22,7 @@
 #include "codecs.h"
 #include "huff_host.h"
 #include "huff_pathmap.h"
+#include "huff_plan_small.h"
 
 namespace rsn {
 namespace {
@@ -539,6 +541,155 @@ __global__ __launch_bounds__(DT) void k_huff_batch_dec(const SmallDecArgs *__res
     small_dec_body<HB_PAY_WORDS, HB_OUT_MAX, false>(s_a);
 }
 
+// ---------------------------------------------------------------- compress, many members in one launch (the batch call)
+// ONE block per member, whatever the grid, and nothing on the host between the histogram and the emit: the block loads its member (a
+// SmallMember entry in pinned memory: where its bytes, its output slot and its status word are) into LDS once and counts it there, ranks
+// the leaves, and ONE wavefront builds the Go-exact tree and codes (huff_plan_small.h -- the code the CPU test checks against the host's
+// build_tree / assign_codes) with the heap, the children and the codes held in VGPRs, a slot per lane: a read is a readlane, a write a select in
+// the one lane, both at a wave-uniform index.  The other wavefronts wait; the header's entries are already in place (a scan of their lengths).  Then every
+// byte's first bit is a block scan of the code lengths and the codes are ORed into an LDS image of the output words, as k_small_emit does.
+// Status word: the stream's length, or HE_BACK -- a byte >= 0x80 (runes, huffman.go:309), fewer than two distinct bytes, a code beyond
+// 24 bits or a header beyond HDR_MAX (none of the last two below the member cutoff: counts below 2^15 give codes of at most 20 bits).
+constexpr uint32_t HE_IN_MAX = 16384;            // member cutoff: 128 symbols code at most 7 bits a byte, so at most 14 KiB of payload
+constexpr uint32_t HE_T = 256;
+constexpr uint32_t HE_PENDING = 0xFFFFFFFFu, HE_BACK = 0xFFFFFFFEu;
+__host__ __device__ constexpr uint32_t he_out_slot(uint32_t n) { return (HDR_MAX + n + 15) & ~15u; }   // bytes; holds header + 7n/8 + pad
+constexpr uint32_t HE_IMG_WORDS = (HDR_MAX + HE_IN_MAX * 7 / 8 + 64) / 4;
+static_assert(he_out_slot(HE_IN_MAX) / 4 >= HE_IMG_WORDS, "the image fits the largest member's slot");
+
+// `R` VGPRs of a wavefront as 64 R slots (slot i: register i / 64 of lane i % 64); every index wave-uniform
+template <int R>
+struct LaneStore {
+    uint32_t r[R];
+    __device__ __forceinline__ uint32_t get(uint32_t i) const {
+        const uint32_t q = i >> 6, l = i & 63;
+        uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)r[0], (int)l);
+#pragma unroll
+        for (int k = 1; k < R; k++) { const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)r[k], (int)l); v = q == (uint32_t)k ? w : v; }
+        return v;
+    }
+    __device__ __forceinline__ void set(uint32_t i, uint32_t v) {              // (a compare and a select: lane i % 64 takes v)
+        const uint32_t q = i >> 6, l = i & 63, me = __lane_id();
+#pragma unroll
+        for (int k = 0; k < R; k++) if (q == (uint32_t)k && me == l) r[k] = v;
+    }
+};
+
+__global__ __launch_bounds__(HE_T) void k_huff_batch_enc(const SmallMember *__restrict__ tab, uint8_t *__restrict__ base) {
+    __shared__ uint4 s_in[HE_IN_MAX / 16];
+    __shared__ uint32_t s_img[HE_IMG_WORDS];          // the output: header bytes, then the code bits (MSB first, words byte-swapped)
+    __shared__ uint32_t s_cnt[HE_T / 64][128];
+    __shared__ uint32_t s_tot[128], s_lf[128], s_tab[128];
+    __shared__ uint8_t s_leaf[128];
+    __shared__ uint32_t s_wave[HE_T / 64 + 1];
+    __shared__ uint32_t s_plan[2];                     // max code length, payload bits
+    const SmallMember m = tab[blockIdx.x];
+    uint32_t *status = reinterpret_cast<uint32_t *>(base + m.status_off);
+    const uint32_t n = m.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (n < 2 || n > HE_IN_MAX) { block_done(status, HE_BACK); return; }    // (the host never sends one)
+    for (uint32_t i = tid; i < HE_T / 64 * 128; i += HE_T) (&s_cnt[0][0])[i] = 0;
+    for (uint32_t i = tid; i < HE_IMG_WORDS; i += HE_T) s_img[i] = 0;
+    __syncthreads();
+    // ---- the member into LDS, counted (huffman.go:306-311)
+    const uint4 *hin = reinterpret_cast<const uint4 *>(base + m.in_off);
+    uint32_t high = 0;
+    for (uint32_t u = tid; u * 16 < n; u += HE_T) {
+        const uint4 v = hin[u];                                          // (pinned host memory; zero behind n)
+        s_in[u] = v;
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        const uint32_t valid = min(16u, n - u * 16);
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const uint32_t b = (w[j >> 2] >> (8 * (j & 3))) & 0xFF;
+            if ((uint32_t)j < valid) { high |= b & 0x80; atomicAdd(&s_cnt[wave][b & 0x7F], 1u); }
+        }
+    }
+    high = __syncthreads_or((int)high);
+    uint32_t c = 0;
+    if (tid < 128) {
+        for (uint32_t w = 0; w < HE_T / 64; w++) c += s_cnt[w][tid];
+        s_tot[tid] = c;
+    }
+    const uint32_t a = (uint32_t)__syncthreads_count(tid < 128 && c != 0);
+    if (high || a < 2) { block_done(status, HE_BACK); return; }
+    // ---- leaves in (count asc, byte asc) order; the header's entries ascending by byte, '\\' first when it would be last (huffman.go:312-318)
+    const bool above_bs = __syncthreads_or(tid > 0x5C && tid < 128 && c != 0);
+    const bool bs_first = s_tot[0x5C] != 0 && !above_bs;
+    const uint32_t e_len = tid < 128 && c ? plan_entry_len(c, tid) : 0u;
+    if (tid < 128 && c) { const uint32_t r = plan_leaf_rank(s_tot, tid); s_lf[r] = c; s_leaf[r] = (uint8_t)tid; }
+    uint32_t e_at = block_excl_scan<HE_T / 64>(e_len, s_wave);
+    const uint32_t E = s_wave[HE_T / 64];                                // bytes of the entries
+    if (bs_first) e_at = tid == 0x5C ? 0u : e_at + plan_entry_len(s_tot[0x5C], 0x5C);
+    if (e_len && E + 3 <= HDR_MAX) plan_entry(c, tid, reinterpret_cast<uint8_t *>(s_img) + e_at);
+    // ---- the tree and the codes: one wavefront (huffman.go:93-127)
+    if (wave == 0) {
+        const uint32_t au = (uint32_t)__builtin_amdgcn_readfirstlane((int)a);
+        LaneStore<2> heap, kids;
+        LaneStore<4> code;
+        heap.r[0] = lane < au ? plan_item(s_lf[lane], lane) : 0u;
+        heap.r[1] = lane + 64 < au ? plan_item(s_lf[lane + 64], lane + 64) : 0u;
+        kids.r[0] = kids.r[1] = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) code.r[k] = 0;
+        const uint32_t root = plan_tree(au, heap, kids);
+        plan_codes(au, root, kids, code);
+        // leaf slot l is lane l of code.r[0], slot 64 + l lane l of code.r[1]
+        uint32_t mx = 0, bits = 0;
+        if (lane < au) { s_tab[s_leaf[lane]] = code.r[0]; mx = code.r[0] >> 24; bits = s_lf[lane] * mx; }
+        if (lane + 64 < au) { const uint32_t l1 = code.r[1] >> 24; s_tab[s_leaf[lane + 64]] = code.r[1]; mx = max(mx, l1); bits += s_lf[lane + 64] * l1; }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64)); bits += (uint32_t)__shfl_xor((int)bits, d, 64); }
+        if (lane == 0) { s_plan[0] = mx; s_plan[1] = bits; }
+    }
+    __syncthreads();
+    const uint32_t max_len = s_plan[0], pay_bits = s_plan[1];
+    const uint32_t H = E + 3, pad = (8 - pay_bits % 8) % 8;              // huffman.go:245-249
+    const uint32_t total = H + (pay_bits + pad) / 8, out_words = (total + 3) / 4;
+    if (max_len > 24 || H > HDR_MAX || out_words > HE_IMG_WORDS || 4 * out_words > he_out_slot(n)) { block_done(status, HE_BACK); return; }
+    if (tid == 0) {
+        uint8_t *h = reinterpret_cast<uint8_t *>(s_img);
+        h[E] = '\\'; h[E + 1] = '\n'; h[E + 2] = (uint8_t)pad;
+    }
+    // ---- the code bits: 16 bytes a lane, 4 KiB a round; a lane's first and last words may be shared with its neighbours (LDS atomics)
+    uint32_t at0 = 8 * H + pad;
+    for (uint32_t r0 = 0; r0 < n; r0 += 16 * HE_T) {
+        const uint32_t lo = r0 + 16 * tid;
+        const uint4 v = lo < n ? s_in[lo / 16] : make_uint4(0, 0, 0, 0);
+        const uint32_t valid = lo < n ? min(16u, n - lo) : 0u;
+        const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+        uint32_t e[16], bits = 0;
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            e[j] = (uint32_t)j < valid ? s_tab[(w4[j >> 2] >> (8 * (j & 3))) & 0x7F] : 0u;
+            bits += e[j] >> 24;
+        }
+        const uint32_t pos0 = at0 + block_excl_scan<HE_T / 64>(bits, s_wave);
+        at0 += s_wave[HE_T / 64];
+        if (bits) {
+            uint32_t w = pos0 >> 5, nacc = pos0 & 31;
+            unsigned long long acc = 0;
+            bool first = true;
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                const uint32_t l = e[j] >> 24;
+                if (l) acc |= (unsigned long long)(e[j] & 0xFFFFFFu) << (64 - nacc - l);
+                nacc += l;
+                if (nacc >= 32) {
+                    const uint32_t be = __builtin_bswap32((uint32_t)(acc >> 32));
+                    if (first) atomicOr(&s_img[w], be); else s_img[w] = be;
+                    first = false;
+                    w++; acc <<= 32; nacc -= 32;
+                }
+            }
+            if (nacc) atomicOr(&s_img[w], __builtin_bswap32((uint32_t)(acc >> 32)));
+        }
+    }
+    __syncthreads();
+    uint32_t *hout = reinterpret_cast<uint32_t *>(base + m.out_off);
+    for (uint32_t i = tid; i < out_words; i += HE_T) hout[i] = s_img[i];
+    block_done(status, total);
+}
+
 }  // namespace
 
 namespace {
@@ -746,6 +897,48 @@ int huff_batch_decompress_group(Ctx &c, const std::vector<size_t> &idx, const ui
     // (members refused up front and members handed back, in index order)
     back.insert(back.end(), taken_back.begin(), taken_back.end());
     std::sort(back.begin(), back.end());
+    return RSN_OK;
+}
+
+bool huff_batch_compress_takes(size_t n) { return n >= 2 && n <= HE_IN_MAX; }
+
+// Members in groups of at most SMALL_GROUP_BYTES of staging: the table (a SmallMember per member), then per member its bytes (zero behind
+// them), its output slot and its status word.  Every member of idx must be one huff_batch_compress_takes; the kernel hands back the
+// rest (runes, a single symbol), and those go to `back` in index order.
+int huff_batch_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
+                              const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    if (idx.empty()) return RSN_OK;
+    int rc = ctx_init(c); if (rc) { *failed = idx[0]; return rc; }
+    hipStream_t s = c.own_stream;
+    auto need = [&](size_t n) { return sizeof(SmallMember) + round_up(n, 16) + 16 + he_out_slot((uint32_t)n) + 16; };
+    std::vector<uint32_t> st;
+    for (size_t j = 0; j < idx.size();) {
+        size_t k = j, bytes = 0;
+        while (k < idx.size() && k - j < SMALL_GROUP_MAX && (k == j || bytes + need(lens[idx[k]]) <= SMALL_GROUP_BYTES)) bytes += need(lens[idx[k++]]);
+        const size_t g = k - j;
+        void *pp; rc = pinned_buf(c, bytes + 64, &pp); if (rc) { *failed = idx[j]; return rc; }
+        uint8_t *base = (uint8_t *)pp;
+        SmallMember *tab = (SmallMember *)base;
+        size_t at = round_up(g * sizeof(SmallMember), 16);
+        st.assign(g, 0);
+        for (size_t q = 0; q < g; q++) {
+            const size_t i = idx[j + q], n = lens[i];
+            SmallMember &m = tab[q];
+            m.n = (uint32_t)n;
+            m.in_off = (uint32_t)at; memcpy(base + at, ins[i], n); memset(base + at + n, 0, round_up(n, 16) + 16 - n); at += round_up(n, 16) + 16;
+            m.out_off = (uint32_t)at; at += he_out_slot((uint32_t)n);
+            m.status_off = st[q] = (uint32_t)at; *(uint32_t *)(base + at) = HE_PENDING; at += 16;
+        }
+        RSN_LAUNCH("huff_batch_enc", k_huff_batch_enc, dim3((uint32_t)g), dim3(HE_T), 0, s, (const SmallMember *)tab, base);
+        rc = group_wait(c, s, base, st, HE_PENDING, "huffman batch compress"); if (rc) { *failed = idx[j]; return rc; }
+        for (size_t q = 0; q < g; q++) {
+            const size_t i = idx[j + q];
+            const uint32_t v = *(const uint32_t *)(base + st[q]);
+            if (v == HE_BACK) { back.push_back(i); continue; }
+            rc = take(i, base + tab[q].out_off, v); if (rc) { *failed = i; return rc; }
+        }
+        j = k;
+    }
     return RSN_OK;
 }
 

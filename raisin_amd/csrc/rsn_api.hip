@@ -1062,6 +1062,9 @@ static void deal_items(Ctx &c, size_t n_items, Work work, std::vector<int> &rcs,
     (void)hipSetDevice(c.device);
 }
 
+// fewer grouped members than this: every member takes the pipeline (a group's one serial tree against the host's)
+constexpr size_t HUFF_GROUP_MIN = 2;
+
 static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
     Ctx &c = ctx();
     if (!ins || !lens || !outs || !out_lens) return c.fail(RSN_ERR_ARG, "null argument");
@@ -1075,9 +1078,36 @@ static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const
         for (size_t k = 0; k < n_chunks; k++) { if (outs[k]) rsn_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
         return c.fail(rc, "%s", msg);
     };
+    // Members of 2 B to 16 KiB run grouped on this thread (huff_batch_compress_group: one launch of k_huff_batch_enc per group, every member
+    // its own workgroup and its own tree) when there are at least HUFF_GROUP_MIN of them.  The rest -- larger members, and the members the
+    // kernel hands back (runes, a single symbol) -- take the pipeline below, as every member did before, dealt over the batch workers.
+    std::vector<size_t> grouped, rest;
+    for (size_t i = 0; i < n_chunks; i++) (huff_batch_compress_takes(lens[i]) ? grouped : rest).push_back(i);
+    if (grouped.size() < HUFF_GROUP_MIN) { rest.insert(rest.end(), grouped.begin(), grouped.end()); grouped.clear(); std::sort(rest.begin(), rest.end()); }
+    if (!grouped.empty()) {
+        std::vector<size_t> back;
+        size_t failed = 0;
+        const SmallTake take = [&](size_t i, const uint8_t *p, size_t len) -> int {
+            uint8_t *r = (uint8_t *)result_alloc(len);
+            if (!r) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", len);
+            memcpy(r, p, len);
+            outs[i] = r; out_lens[i] = len;
+            return RSN_OK;
+        };
+        const int rc = huff_batch_compress_group(c, grouped, ins, lens, take, back, &failed);
+        if (rc != RSN_OK) { const std::string msg = c.err; return undo(rc, msg.c_str()); }
+        rest.insert(rest.end(), back.begin(), back.end());
+        std::sort(rest.begin(), rest.end());
+    }
+    if (rest.empty()) return RSN_OK;
     std::vector<int> rcs;
     std::vector<std::string> msgs;
-    deal_items(c, n_chunks, [&](size_t, const std::vector<size_t> &idx) { return batch_on_device(ctx(), idx, ins, lens, outs, out_lens); }, rcs, msgs);
+    deal_items(c, rest.size(), [&](size_t, const std::vector<size_t> &ks) {
+        std::vector<size_t> idx;
+        idx.reserve(ks.size());
+        for (size_t k : ks) idx.push_back(rest[k]);
+        return batch_on_device(ctx(), idx, ins, lens, outs, out_lens);
+    }, rcs, msgs);
     for (size_t w = 0; w < rcs.size(); w++) if (rcs[w] != RSN_OK) return undo(rcs[w], msgs[w].c_str());
     return RSN_OK;
 }

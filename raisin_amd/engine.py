@@ -95,6 +95,22 @@ _COMPRESS_BATCH = {"huffman": huffman.CompressBatch, "lzss": lambda datas: lz.Co
 _DECOMPRESS_BATCH = {"huffman": huffman.DecompressBatch, "lzss": lz.DecompressBatch}
 
 
+def _layered(algorithms, files):
+    """a multi-file list under two or more layers, every one lzss or huffman (the CLI's default lzss,huffman): each group of files goes
+    through the layers' batch calls in turn"""
+    return len(files) > 1 and len(algorithms) > 1 and all(a in _COMPRESS_BATCH for a in algorithms)
+
+
+def _batch_layers(batches, datas):
+    """datas through the batch calls in turn, each layer's outputs the next one's inputs; None when a call fails (the loop's turn)"""
+    try:
+        for call in batches:
+            datas = call(datas)
+    except Exception:                                           # noqa: BLE001 -- the loop finds the file that fails, after writing the ones before it
+        return None
+    return datas
+
+
 def _groups(files, take_empty):
     """The files in groups of at most BATCH_BYTES, read in order: yields (group, datas, bad) -- bad: files[i] right behind the group is
     empty (when the batch does not take empty files) or cannot be read, and is the per-file loop's to meet, in order, after the group."""
@@ -120,11 +136,29 @@ def _groups(files, take_empty):
 
 def CompressFiles(algorithms, files, extension):
     """engine.go:150-154: one .rsn per input, file after file.  Several files under one Huffman or one LZSS layer go through the batch call
-    (Huffman: upload / encode / download overlapped on the device; LZSS: small files many to a launch) in GROUPS of at most BATCH_BYTES, in
+    (small files many to a launch; larger Huffman inputs: upload / encode / download overlapped on the device), and under several such
+    layers (lzss,huffman) through each layer's batch call in turn, in GROUPS of at most BATCH_BYTES, in
     the loop's order and with the loop's semantics: a file's lines are printed and its .rsn is written before the next group is read, and a
     file the batch cannot take (empty under Huffman: the reference panics in heap.Pop, huffman.go:102) or a group that fails falls back to
     the per-file loop, which stops at the failing file with every earlier .rsn already on disk -- exactly where the reference's loop would stop."""
     files = list(files)
+    if _layered(algorithms, files):
+        # several layers: the same groups through each layer's batch call in order; an empty file ends a group when a layer is Huffman
+        for group, datas, bad in _groups(files, take_empty="huffman" not in algorithms):
+            outs = _batch_layers([_COMPRESS_BATCH[a] for a in algorithms], datas) if len(group) > 1 else None
+            if outs is None:
+                for f in group:
+                    CompressFile(algorithms, f, f + extension)
+            else:
+                for f, data, out in zip(group, datas, outs):
+                    print("Compressing...")
+                    open(f + extension, "wb").write(out)
+                    print("Original bytes: %d" % len(data))
+                    print("Compressed bytes: %d" % len(out))
+                    print("Compression ratio: %.2f%%" % (len(out) / len(data) * 100 if data else float("nan")))
+            if bad is not None:
+                CompressFile(algorithms, bad, bad + extension)   # raises like the reference panics; the earlier files are written
+        return
     if len(files) > 1 and list(algorithms) == ["lzss"]:
         for group, datas, bad in _groups(files, take_empty=True):
             outs = None
@@ -197,7 +231,8 @@ def DecompressFile(algorithms, path, output):
 
 
 def DecompressFiles(algorithms, files, extension):
-    """engine.go:175-185: file after file.  Several files under ONE layer (lzss or huffman) go through that codec's batch call in groups of
+    """engine.go:175-185: file after file.  Several files under ONE layer (lzss or huffman) go through that codec's batch call (under several
+    such layers: each layer's, the last layer first) in groups of
     at most BATCH_BYTES, with the loop's semantics: outputs in order, a group written before the next is read, and a group that fails is
     done again by the loop, which stops at the failing file with everything before it written and nothing after it."""
     files = list(files)
@@ -209,6 +244,21 @@ def DecompressFiles(algorithms, files, extension):
         return path
 
     algorithms = list(algorithms)
+    if _layered(algorithms, files):
+        # several layers: each group through the layers' batch calls, the last layer first
+        for group, datas, bad in _groups(files, take_empty="huffman" not in algorithms):
+            outs = _batch_layers([_DECOMPRESS_BATCH[a] for a in reversed(algorithms)], datas) if len(group) > 1 else None
+            if outs is None:
+                for f in group:
+                    DecompressFile(algorithms, f, out_path(f))
+            else:
+                for f, out in zip(group, outs):
+                    print("Decompressing...")
+                    with open(out_path(f), "wb") as fh:
+                        fh.write(out)
+            if bad is not None:
+                DecompressFile(algorithms, bad, out_path(bad))   # raises where the loop would
+        return
     if len(files) > 1 and len(algorithms) == 1 and algorithms[0] in _DECOMPRESS_BATCH:
         for group, datas, bad in _groups(files, take_empty=True):
             outs = None

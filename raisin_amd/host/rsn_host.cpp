@@ -177,6 +177,35 @@ static std::vector<std::vector<std::string>> parseAlgorithms(const std::string &
     return algs;
 }
 
+// Every member through the layers' batch calls in turn: compress runs the layers in order, layer k's outputs layer k + 1's inputs;
+// decompress runs them in reverse.  false (and res untouched) when a call fails: the caller hands the group to the per-file loop.
+static bool layers_batch(const std::vector<std::string> &algs, bool enc, const std::vector<Bytes> &datas, std::vector<Bytes> &res) {
+    std::vector<Bytes> cur;
+    const std::vector<Bytes> *src = &datas;
+    for (size_t l = 0; l < algs.size(); l++) {
+        const bool huff = (enc ? algs[l] : algs[algs.size() - 1 - l]) == "huffman";
+        const size_t n = src->size();
+        std::vector<const uint8_t *> ins; std::vector<size_t> lens;
+        for (auto &d : *src) { ins.push_back(d.data()); lens.push_back(d.size()); }
+        std::vector<uint8_t *> outs(n, nullptr); std::vector<size_t> out_lens(n, 0);
+        const int brc = enc ? (huff ? rsn_huffman_compress_batch(n, ins.data(), lens.data(), outs.data(), out_lens.data())
+                                    : rsn_lzss_compress_batch(n, ins.data(), lens.data(), RSN_LZSS_DEFAULT_WINDOW, outs.data(), out_lens.data()))
+                            : (huff ? rsn_huffman_decompress_batch(n, ins.data(), lens.data(), outs.data(), out_lens.data())
+                                    : rsn_lzss_decompress_batch(n, ins.data(), lens.data(), outs.data(), out_lens.data()));
+        if (brc != RSN_OK) return false;
+        std::vector<Bytes> next(n);
+        for (size_t k = 0; k < n; k++) { next[k].assign(outs[k], outs[k] + out_lens[k]); rsn_free(outs[k]); }
+        cur.swap(next);
+        src = &cur;
+    }
+    res = std::move(cur);
+    return true;
+}
+static bool batch_layers_only(const std::vector<std::string> &algs) {
+    for (auto &a : algs) if (a != "huffman" && a != "lzss") return false;
+    return !algs.empty();
+}
+
 int main(int argc, char **argv) {
     std::string app = argv[0], cmd, file, algorithm, out, outext; bool has_delete = false, del = false;
     long long timeout_ms = 60000;                                   // engine.go:216; RSN_BENCH_TIMEOUT_MS shortens it for tests
@@ -212,14 +241,14 @@ int main(int argc, char **argv) {
                 printf("Original bytes: %zu\nCompressed bytes: %zu\nCompression ratio: %.2f%%\n", data.size(), c.size(), (float)c.size() / (float)data.size() * 100.f);   // engine.go:166-169
             };
             auto one_file = [&](const std::string &f) { one_data(f, read_file(f)); };
-            if (files.size() > 1 && algs.size() == 1 && (algs[0] == "huffman" || algs[0] == "lzss")) {
+            if (files.size() > 1 && batch_layers_only(algs)) {
                 // engine.CompressFiles loops over the files, one .rsn each (engine.go:150-154).  Independent inputs of one Huffman layer go
                 // through the batch entry point -- upload, encode and download overlapped on the device (and dealt over devices with
                 // RSN_BATCH_DEVICES) -- in GROUPS of at most 4 GiB, in the loop's order and with its semantics: a group's files are written
                 // before the next group is read, an empty file (the reference panics, huffman.go:102) ends a group, and a group that fails
                 // is done again by the loop, which stops at the failing file with everything before it on disk.  One LZSS layer: the same
-                // groups through rsn_lzss_compress_batch (small files many to a launch); its empty files take the loop's turn too.
-                const bool huff = algs[0] == "huffman";
+                // groups through rsn_lzss_compress_batch (small files many to a launch); its empty files take the loop's turn too.  Several
+                // layers (the default lzss,huffman): the same groups through each layer's batch call in turn (layers_batch).
                 constexpr size_t BATCH_BYTES = (size_t)4 << 30;
                 size_t i = 0;
                 Bytes held; bool have_held = false;                 // a file that overflowed the group before: read once, kept for this group
@@ -238,21 +267,14 @@ int main(int argc, char **argv) {
                         size += d.size(); group.push_back(files[i]); datas.push_back(std::move(d)); i++;
                     }
                     bool done = false;
-                    if (group.size() > 1) {
-                        std::vector<const uint8_t *> ins; std::vector<size_t> lens;
-                        for (auto &d : datas) { ins.push_back(d.data()); lens.push_back(d.size()); }
-                        std::vector<uint8_t *> outs(group.size(), nullptr); std::vector<size_t> out_lens(group.size(), 0);
-                        const int brc = huff ? rsn_huffman_compress_batch(group.size(), ins.data(), lens.data(), outs.data(), out_lens.data())
-                                             : rsn_lzss_compress_batch(group.size(), ins.data(), lens.data(), RSN_LZSS_DEFAULT_WINDOW, outs.data(), out_lens.data());
-                        if (brc == RSN_OK) {
-                            for (size_t k = 0; k < group.size(); k++) {
-                                printf("Compressing...\n");
-                                write_file(out_name(group[k]), Bytes(outs[k], outs[k] + out_lens[k]));
-                                rsn_free(outs[k]);
-                                printf("Original bytes: %zu\nCompressed bytes: %zu\nCompression ratio: %.2f%%\n", datas[k].size(), out_lens[k], (float)out_lens[k] / (float)datas[k].size() * 100.f);
-                            }
-                            done = true;
+                    std::vector<Bytes> res;
+                    if (group.size() > 1 && layers_batch(algs, true, datas, res)) {
+                        for (size_t k = 0; k < group.size(); k++) {
+                            printf("Compressing...\n");
+                            write_file(out_name(group[k]), res[k]);
+                            printf("Original bytes: %zu\nCompressed bytes: %zu\nCompression ratio: %.2f%%\n", datas[k].size(), res[k].size(), (float)res[k].size() / (float)datas[k].size() * 100.f);
                         }
+                        done = true;
                     }
                     if (!done) for (size_t k = 0; k < group.size(); k++) one_data(group[k], datas[k]);   // (what was read is not read again)
                     if (bad) one_file(files[i++]);                  // throws where the reference panics; everything before it is on disk
@@ -275,13 +297,15 @@ int main(int argc, char **argv) {
                 printf("Decompressing...\n");
                 write_file(o, engine::decompress(data, algs));
             };
-            if (files.size() > 1 && algs.size() == 1 && (algs[0] == "huffman" || algs[0] == "lzss")) {
+            if (files.size() > 1 && batch_layers_only(algs)) {
                 // One layer: the files through its batch call (rsn_huffman_decompress_batch / rsn_lzss_decompress_batch: small streams many
                 // to a launch) in groups of at most 4 GiB, with the loop's semantics -- outputs written in order, a group before the next is
                 // read; a file that cannot be read (or has no output name) ends its group and takes the loop's turn; a group that fails is
-                // done again by the loop, which stops at the failing file with everything before it written and nothing after it.
+                // done again by the loop, which stops at the failing file with everything before it written and nothing after it.  Several
+                // layers: each layer's batch call in turn, the last layer first (layers_batch); an empty file then ends its group as well
+                // when a layer is Huffman (the reference panics on it), and takes the loop's turn.
                 constexpr size_t BATCH_BYTES = (size_t)4 << 30;
-                const bool huff = algs[0] == "huffman";
+                const bool empty_ends = algs.size() > 1 && std::find(algs.begin(), algs.end(), "huffman") != algs.end();
                 size_t i = 0;
                 Bytes held; bool have_held = false;
                 while (i < files.size()) {
@@ -294,24 +318,18 @@ int main(int argc, char **argv) {
                             try { (void)out_of(files[i]); d = read_file(files[i]); }
                             catch (const std::exception &) { bad = true; break; }
                         }
+                        if (d.empty() && empty_ends) { bad = true; break; }
                         if (!group.empty() && size + d.size() > BATCH_BYTES) { held = std::move(d); have_held = true; break; }
                         size += d.size(); group.push_back(files[i]); datas.push_back(std::move(d)); i++;
                     }
                     bool done = false;
-                    if (group.size() > 1) {
-                        std::vector<const uint8_t *> ins; std::vector<size_t> lens;
-                        for (auto &d : datas) { ins.push_back(d.data()); lens.push_back(d.size()); }
-                        std::vector<uint8_t *> outs(group.size(), nullptr); std::vector<size_t> out_lens(group.size(), 0);
-                        const int brc = huff ? rsn_huffman_decompress_batch(group.size(), ins.data(), lens.data(), outs.data(), out_lens.data())
-                                             : rsn_lzss_decompress_batch(group.size(), ins.data(), lens.data(), outs.data(), out_lens.data());
-                        if (brc == RSN_OK) {
-                            for (size_t k = 0; k < group.size(); k++) {
-                                printf("Decompressing...\n");
-                                write_file(out_of(group[k]), Bytes(outs[k], outs[k] + out_lens[k]));
-                                rsn_free(outs[k]);
-                            }
-                            done = true;
+                    std::vector<Bytes> res;
+                    if (group.size() > 1 && layers_batch(algs, false, datas, res)) {
+                        for (size_t k = 0; k < group.size(); k++) {
+                            printf("Decompressing...\n");
+                            write_file(out_of(group[k]), res[k]);
                         }
+                        done = true;
                     }
                     if (!done) for (size_t k = 0; k < group.size(); k++) one_data(group[k], datas[k]);
                     if (bad) { (void)out_of(files[i]); one_data(files[i], read_file(files[i])); i++; }   // throws where the loop would; everything before it is written

@@ -21,9 +21,11 @@ def CompressSharded(fileContents, shards=0):
 
 
 def CompressBatch(chunks):
-    """One complete .rsn segment per chunk, as engine.CompressFiles writes one file per input (engine.go:150-154):
-    rsn_huffman_compress_batch deals the chunks out over the visible GPUs (chunk k -> device k mod G) and pipelines
-    upload / encode / download per device.  Each result equals Compress(chunk)."""
+    """One complete .rsn segment per chunk, as engine.CompressFiles writes one file per input (engine.go:150-154).
+    rsn_huffman_compress_batch runs chunks of 2 to BATCH_COMPRESS_INPUT_MAX bytes many to a launch, a workgroup each that builds the
+    chunk's own tree on the device (byte alphabets; a chunk with a byte >= 0x80 or a single distinct byte is handed back), when at least
+    two chunks are of that size.  The other chunks are dealt out over the batch workers (chunk k -> device k mod G) and go through a
+    pipeline of upload / encode / download per device.  Each result equals Compress(chunk)."""
     import ctypes
     L = _lib.lib()
     chunks = [bytes(c) for c in chunks]
@@ -39,6 +41,10 @@ def CompressBatch(chunks):
         for i in range(k):
             L.rsn_free(outs[i])
 
+
+# The largest chunk the batch encoder's grouped kernel takes (csrc/huff_small.hip HE_IN_MAX): its output -- at most 7 bits
+# a byte of payload -- stays inside what one workgroup of the batch decoder holds, so the round trip is grouped both ways.
+BATCH_COMPRESS_INPUT_MAX = 16384
 
 # What one workgroup of the batch decoder holds (csrc/huff_small.hip HB_PAY_MAX / HB_OUT_MAX): a stream with more payload
 # bytes (behind the header's backslash-newline and the pad byte), or more output, goes through the single call's path inside the batch.

@@ -1,9 +1,11 @@
 """The batch calls against a loop of single calls on many SMALL members, host buffer to host buffer.
 
 For K in {16, 256, 4096} members: LZSS compress and decompress of the reference README's 13-byte and 25-byte files and of 1 KiB of text,
-Huffman decompress of those and of 16 KiB and 64 KiB of text.  Every time is the median of REPS runs of the whole list; both sides go
-through ctypes the same way.  `--single` first prints the single calls' own times per call (the small-input paths the batch shares its
-kernels with).  Usage: python scripts/batch_small_bench.py [--single] [--reps R] [--k 16,256,4096]"""
+Huffman compress of those and of 16 KiB of text, Huffman decompress of those and of 64 KiB of text, and the CLI's default two layers
+(lzss,huffman: the two batch calls one after the other against a loop of two single calls per member).  Every time is the median of REPS
+runs of the whole list; both sides go through ctypes the same way.  `--single` first prints the single calls' own times per call (the
+small-input paths the batch shares its kernels with).  `--only` runs the rows whose call name contains one of its comma-separated words.
+Usage: python scripts/batch_small_bench.py [--single] [--reps R] [--k 16,256,4096] [--only huffman compress,lzss,huffman]"""
 import argparse
 import ctypes
 import os
@@ -72,12 +74,28 @@ def loop_fn(L, name, bufs, extra):
     return run
 
 
+def layered_fns(L, bufs):
+    """lzss,huffman: both batch calls in turn / both single calls per member"""
+    def batch():
+        k = len(bufs)
+        mid = _lib.call_batch(L.rsn_lzss_compress_batch, bufs, 4096)
+        outs = _lib.call_batch(L.rsn_huffman_compress_batch, mid)
+        assert len(outs) == k
+
+    def loop():
+        for b in bufs:
+            huffman.Compress(lz.CompressAsync(b, False, 4096))
+    return batch, loop
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--single", action="store_true")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--k", default="16,256,4096")
+    ap.add_argument("--only", default="")
     a = ap.parse_args()
+    only = [w for w in a.only.split(",") if w]
     L = _lib.lib()
     print("library: %s" % os.path.basename(_lib.LIB_PATH))
     if a.single:
@@ -87,6 +105,8 @@ def main():
                  ("lzss decompress", "rsn_lzss_decompress", lz.CompressAsync(README[0]), ()),
                  ("lzss decompress", "rsn_lzss_decompress", lz.CompressAsync(README[1]), ()),
                  ("lzss decompress", "rsn_lzss_decompress", lz.CompressAsync(text(0, 1024)), ()),
+                 ("huffman compress", "rsn_huffman_compress", README[0], ()), ("huffman compress", "rsn_huffman_compress", README[1], ()),
+                 ("huffman compress", "rsn_huffman_compress", text(0, 1024), ()), ("huffman compress", "rsn_huffman_compress", text(0, 64 << 10), ()),
                  ("huffman decompress", "rsn_huffman_decompress", huffman.Compress(text(0, 16 << 10)), ()),
                  ("huffman decompress", "rsn_huffman_decompress", huffman.Compress(text(0, 64 << 10)), ())]
         for label, name, data, extra in cases:
@@ -96,8 +116,12 @@ def main():
     print("%-20s %6s %5s %10s %10s %8s" % ("call", "member", "K", "batch ms", "loop ms", "loop/batch"))
     plan = [("lzss compress", "rsn_lzss_compress_batch", "rsn_lzss_compress", ("13B", "25B", "1KiB"), (4096,)),
             ("lzss decompress", "rsn_lzss_decompress_batch", "rsn_lzss_decompress", ("13B", "25B", "1KiB"), ()),
-            ("huffman decompress", "rsn_huffman_decompress_batch", "rsn_huffman_decompress", ("13B", "25B", "1KiB", "16KiB", "64KiB"), ())]
+            ("huffman decompress", "rsn_huffman_decompress_batch", "rsn_huffman_decompress", ("13B", "25B", "1KiB", "16KiB", "64KiB"), ()),
+            ("huffman compress", "rsn_huffman_compress_batch", "rsn_huffman_compress", ("13B", "25B", "1KiB", "16KiB"), ()),
+            ("lzss,huffman", None, None, ("13B", "25B", "1KiB"), ())]
     for label, bname, sname, kinds, extra in plan:
+        if only and not any(w == label or w in label.replace(",", " ").split() for w in only):
+            continue
         for kind in kinds:
             for k in [int(x) for x in a.k.split(",")]:
                 src = members(kind, k)
@@ -107,7 +131,10 @@ def main():
                     bufs = [huffman.Compress(s) for s in src]
                 else:
                     bufs = src
-                b, lp = batch_fn(L, bname, bufs, extra), loop_fn(L, sname, bufs, extra)
+                if bname is None:
+                    b, lp = layered_fns(L, bufs)
+                else:
+                    b, lp = batch_fn(L, bname, bufs, extra), loop_fn(L, sname, bufs, extra)
                 b(), lp()
                 tb, tl = timed(b, a.reps), timed(lp, a.reps)
                 print("%-20s %6s %5d %10.3f %10.3f %8.1fx" % (label, kind, k, tb * 1e3, tl * 1e3, tl / tb), flush=True)
