@@ -153,6 +153,47 @@ RSN_API int rsn_huffman_decompress_dev(const void *d_in, size_t n, void *d_out, 
 RSN_API int rsn_lzss_compress_dev(const void *d_in, size_t n, int64_t window, void *d_out, size_t out_cap, size_t *out_n, void *stream);
 RSN_API int rsn_lzss_decompress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream);
 
+/* ---- layered calls -------------------------------------------------------
+ * The engine's unit of work: a LIST of layers over one buffer (engine.go:443-479; the CLI's default is lzss,huffman).  `layers` is
+ * always in COMPRESS order, as the engine's `algorithms` is; rsn_layers_decompress undoes them last to first.  The result is byte for
+ * byte what the chain of the single calls above returns -- rsn_lzss_compress(..., RSN_LZSS_DEFAULT_WINDOW, ...) / rsn_huffman_compress
+ * in order, rsn_*_decompress in reverse, the Huffman codec's lossy treatment of bytes that are not UTF-8 included -- but between the
+ * layers the stream stays on the device, in the calling thread's scratch: the input goes up once and the last layer's output comes
+ * down once.  n_layers == 0 returns a copy of the input; n_layers == 1 IS the single call (same small-input paths, same pipelining,
+ * same launches).  Host buffers of at most 64 KiB run the chain of single host calls instead: at that size a call is its launches, and
+ * the single calls' one-launch paths read and write pinned host memory without a copy command.
+ * Errors: a null `layers` with n_layers > 0, an unknown layer id or n_layers > RSN_LAYERS_MAX is RSN_ERR_ARG, checked before the
+ * device is touched; without a device RSN_ERR_DEVICE; otherwise the failing layer's own code, and rsn_last_error() reads
+ * "layer <k> (<name>): " followed by the single call's message, k counting in compress order whichever direction runs (Huffman of an
+ * empty stream is RSN_ERR_EMPTY: [lzss, huffman] on an empty input fails in layer 1).  *out stays NULL on every failure.           */
+#define RSN_LAYER_LZSS 1    /* lz.CompressAsync(..., 4096) / lz.Decompress: what engine.Writers["lzss"] does */
+#define RSN_LAYER_HUFFMAN 2
+#define RSN_LAYERS_MAX 8
+RSN_API int rsn_layers_compress(const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n);
+RSN_API int rsn_layers_decompress(const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n);
+/* The same on device buffers, under the contract of the rsn_*_dev calls above: d_in and d_out 16-byte aligned and not overlapping
+ * (RSN_ERR_ARG), synchronised before returning; when d_out is too small -- or NULL / out_cap 0, the size query -- the call returns
+ * RSN_ERR_CAPACITY and stores in *out_n a capacity that would suffice.  The size of a layered result is only known once the chain has
+ * run: the query of two or more layers (and of one compress layer) costs the whole chain, its last layer writing into scratch, and a
+ * buffer that turns out too small costs the chain up to its last layer; a caller that can bound the result (the compress bounds
+ * applied in turn, or the original's size when decompressing) should pass a buffer of that size.                                  */
+RSN_API int rsn_layers_compress_dev(const void *d_in, size_t n, const int *layers, size_t n_layers, void *d_out, size_t out_cap, size_t *out_n, void *stream);
+RSN_API int rsn_layers_decompress_dev(const void *d_in, size_t n, const int *layers, size_t n_layers, void *d_out, size_t out_cap, size_t *out_n, void *stream);
+
+/* engine.BenchmarkFile's body (engine.go:357-441) in one call: upload once, compress, decompress, compare and count the bytes, all on
+ * the device; only `res` comes down -- and the compressed stream, if `compressed` is not NULL (released with rsn_free).  When a layer
+ * fails, `res` is left zeroed and the code is the layer's.                                                                        */
+typedef struct {
+    uint64_t original_n, compressed_n, decompressed_n;
+    int lossless;                    /* decompressed == original, byte for byte and in length */
+    uint64_t first_difference;       /* lowest differing offset; min(original_n, decompressed_n) if one is a prefix of the other; UINT64_MAX if lossless */
+    uint64_t hist_original[256];     /* byte counts of the input             (engine.go:367-370) */
+    uint64_t hist_decompressed[256]; /* byte counts of what came back        (engine.go:412-415) */
+    double compress_ms, decompress_ms; /* host wall clock of the two halves, for the caller's "time taken" */
+} rsn_roundtrip_result;
+RSN_API int rsn_layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size_t n_layers, rsn_roundtrip_result *res,
+                                 uint8_t **compressed, size_t *compressed_n);
+
 /* ---- measurement --------------------------------------------------------
  * When enabled, every kernel launch of the calling thread is bracketed by HIP
  * events on the launch stream; rsn_prof_get() reports per-kernel totals since
@@ -165,6 +206,10 @@ typedef struct {
 RSN_API void rsn_prof_enable(int on);
 RSN_API void rsn_prof_reset(void);
 RSN_API int rsn_prof_get(rsn_prof_entry *entries, int cap); /* returns the number of entries */
+/* Bytes the library has queued on host-to-device and device-to-host COPY COMMANDS since the last rsn_prof_reset(): process-wide
+ * atomic counters, the helper threads' copies included, counted while the most recent rsn_prof_enable() of any thread was (1).
+ * Kernels that read or write pinned host memory directly (the small-input paths) issue no copy command and count nothing. */
+RSN_API void rsn_prof_copied(uint64_t *h2d_bytes, uint64_t *d2h_bytes);
 
 /* Introspection used by the parity tests: the code table the encoder builds for
  * `in` (device buffer not needed; runs the histogram on the device, the tree on

@@ -30,6 +30,14 @@ class ProfEntry(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("launches", ctypes.c_uint64), ("total_ms", ctypes.c_double)]
 
 
+class RoundTripResult(ctypes.Structure):
+    """rsn_roundtrip_result (include/rsn.h)"""
+    _fields_ = [("original_n", ctypes.c_uint64), ("compressed_n", ctypes.c_uint64), ("decompressed_n", ctypes.c_uint64),
+                ("lossless", ctypes.c_int), ("first_difference", ctypes.c_uint64),
+                ("hist_original", ctypes.c_uint64 * 256), ("hist_decompressed", ctypes.c_uint64 * 256),
+                ("compress_ms", ctypes.c_double), ("decompress_ms", ctypes.c_double)]
+
+
 _lib = None
 
 SYMBOLS = [
@@ -41,6 +49,8 @@ SYMBOLS = [
     "rsn_huffman_compress_dev", "rsn_huffman_decompress_dev", "rsn_lzss_compress_dev", "rsn_lzss_decompress_dev",
     "rsn_prof_enable", "rsn_prof_reset", "rsn_prof_get", "rsn_huffman_table",
     "rsn_huffman_plan", "rsn_huffman_parse_header", "rsn_huffman_slice_cuts",
+    "rsn_layers_compress", "rsn_layers_decompress", "rsn_layers_compress_dev", "rsn_layers_decompress_dev", "rsn_layers_roundtrip",
+    "rsn_prof_copied",
 ]
 
 
@@ -102,6 +112,14 @@ def lib():
     L.rsn_huffman_decompress_batch.argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.POINTER(u8p), szp]
     L.rsn_lzss_compress_batch.argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.c_int64, ctypes.POINTER(u8p), szp]
     L.rsn_lzss_decompress_batch.argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.POINTER(u8p), szp]
+    ip = ctypes.POINTER(ctypes.c_int)
+    for name in ("rsn_layers_compress", "rsn_layers_decompress"):
+        getattr(L, name).argtypes = [ctypes.c_char_p, sz, ip, sz, ctypes.POINTER(u8p), szp]
+    for name in ("rsn_layers_compress_dev", "rsn_layers_decompress_dev"):
+        getattr(L, name).argtypes = [vp, sz, ip, sz, vp, sz, szp, vp]
+    L.rsn_layers_roundtrip.argtypes = [ctypes.c_char_p, sz, ip, sz, ctypes.POINTER(RoundTripResult), ctypes.POINTER(u8p), szp]
+    L.rsn_prof_copied.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    L.rsn_prof_copied.restype = None
     _lib = L
     return L
 
@@ -226,6 +244,13 @@ def prof_get():
     arr = (ProfEntry * 64)()
     k = L.rsn_prof_get(arr, 64)
     return {arr[i].name.decode(): (int(arr[i].launches), float(arr[i].total_ms)) for i in range(min(k, 64))}
+
+
+def prof_copied():
+    """(host-to-device, device-to-host) bytes queued on copy commands since prof_reset(), process-wide (rsn_prof_copied)."""
+    up, down = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    lib().rsn_prof_copied(ctypes.byref(up), ctypes.byref(down))
+    return int(up.value), int(down.value)
 
 
 def own_stream(tensor, stream=None):

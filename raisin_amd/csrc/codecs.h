@@ -76,6 +76,11 @@ int group_wait(Ctx &c, hipStream_t s, const uint8_t *base, const std::vector<uin
 // RSN_ERR_CAPACITY: it expands beyond out_cap (what the caller's sample promised)
 int lzss_decode_sliced(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t out_cap, size_t *out_n, const SliceStream &st);
 
+// the layered round trip's two passes (huff_encode.hip, beside k_byte_hist): both only queue work on `s`.  d_hist: 256 counts, zeroed
+// here; *d_first: the lowest offset below n at which d_a and d_b differ, ~0 when none does.  Buffers 16-byte aligned.
+int byte_hist256_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, unsigned long long *d_hist);
+int bytes_differ_dev(Ctx &c, hipStream_t s, const uint8_t *d_a, const uint8_t *d_b, size_t n, unsigned long long *d_first);
+
 // exclusive scan of n counts on the stream (huff_encode.hip); *total (may be null) receives the sum; in and out must not overlap
 int scan_u64(Ctx &c, hipStream_t s, const char *name, const unsigned long long *in, unsigned long long *out, uint32_t n, unsigned long long *total);
 

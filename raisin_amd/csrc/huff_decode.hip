@@ -829,7 +829,7 @@ int huff_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
         if (k > old) {
             if (st && !st->need_in(k)) return c.fail(RSN_ERR_DEVICE, "huffman: the upload of a sliced call failed");
             void *hpin; int prc = pinned_buf(c, k - old + 64, &hpin); if (prc) return prc;
-            RSN_HIP(hipMemcpyAsync(hpin, d_in + old, k - old, hipMemcpyDeviceToHost, s));
+            RSN_HIP(copy_async(hpin, d_in + old, k - old, hipMemcpyDeviceToHost, s));
             RSN_HIP(hipStreamSynchronize(s));
             head.resize(k);
             memcpy(head.data() + old, hpin, k - old);
@@ -842,7 +842,7 @@ int huff_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
         const size_t old = head.size();
         if (st && !st->need_in(sep + 3)) return c.fail(RSN_ERR_DEVICE, "huffman: the upload of a sliced call failed");
         void *hpin; int prc = pinned_buf(c, 64, &hpin); if (prc) return prc;
-        RSN_HIP(hipMemcpyAsync(hpin, d_in + old, sep + 3 - old, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(hpin, d_in + old, sep + 3 - old, hipMemcpyDeviceToHost, s));
         RSN_HIP(hipStreamSynchronize(s));
         head.resize(sep + 3);
         memcpy(head.data() + old, hpin, sep + 3 - old);
@@ -906,7 +906,7 @@ int huff_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
         const size_t k = (size_t)go_encode_rune(tree.rune[0], u);
         *out_n = k;
         if (!d_out || out_cap < k) { return c.fail(RSN_ERR_CAPACITY, "huffman: output needs %zu bytes", k); }
-        RSN_HIP(hipMemcpyAsync(d_out, u, k, hipMemcpyHostToDevice, s));
+        RSN_HIP(copy_async(d_out, u, k, hipMemcpyHostToDevice, s));
         RSN_HIP(hipStreamSynchronize(s));
         return RSN_OK;
     }
@@ -1012,11 +1012,11 @@ int huff_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
         packed.insert(packed.end(), lut.begin(), lut.end());
         packed.insert(packed.end(), reinterpret_cast<const uint32_t *>(child.data()), reinterpret_cast<const uint32_t *>(child.data()) + child.size());
         packed.insert(packed.end(), lut2.begin(), lut2.end());
-        RSN_HIP(hipMemcpyAsync(d_lut, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, s));
+        RSN_HIP(copy_async(d_lut, packed.data(), packed.size() * 4, hipMemcpyHostToDevice, s));
     } else {
-        RSN_HIP(hipMemcpyAsync(d_lut, lut.data(), lut.size() * 4, hipMemcpyHostToDevice, s));
-        RSN_HIP(hipMemcpyAsync(d_child, child.data(), child.size() * 4, hipMemcpyHostToDevice, s));
-        if (!lut2.empty()) RSN_HIP(hipMemcpyAsync(d_lut2, lut2.data(), lut2.size() * 4, hipMemcpyHostToDevice, s));
+        RSN_HIP(copy_async(d_lut, lut.data(), lut.size() * 4, hipMemcpyHostToDevice, s));
+        RSN_HIP(copy_async(d_child, child.data(), child.size() * 4, hipMemcpyHostToDevice, s));
+        if (!lut2.empty()) RSN_HIP(copy_async(d_lut2, lut2.data(), lut2.size() * 4, hipMemcpyHostToDevice, s));
     }
 
     // ---- the payload, whole or slice by slice.  A range is the subsequences of [base, base + 32 n_sub): its first codeword starts at bit p0
@@ -1088,9 +1088,9 @@ int huff_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
     auto offsets_and_bytes = [&]() -> int {                             // D2 + D3 + the read-back of total and final exit, queued
         int rc2 = scan_u64(c, s, "huff_dec_scan", a.blk_bytes, d_blk_off, n_blk, d_total); if (rc2) return rc2;
         rc2 = launch_emit(); if (rc2) return rc2;
-        RSN_HIP(hipMemcpyAsync(&ht->total, d_total, 8, hipMemcpyDeviceToHost, s));
-        RSN_HIP(hipMemcpyAsync(&ht->last_exit, a.exit_rel + (a.n_sub - 1), 2, hipMemcpyDeviceToHost, s));
-        RSN_HIP(hipMemcpyAsync(&ht->stuck, d_stuck, 4, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(&ht->total, d_total, 8, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(&ht->last_exit, a.exit_rel + (a.n_sub - 1), 2, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(&ht->stuck, d_stuck, 4, hipMemcpyDeviceToHost, s));
         return RSN_OK;
     };
     // ---- the phase solver (k_dec_phase): RSN_OK = the arrays hold the true path; 1 = it gave up (the passes go on)
@@ -1121,7 +1121,7 @@ int huff_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
         ht->changed = 1;
         uint2 *hmap = (uint2 *)((uint8_t *)hq + 64);
         r2 = launch_phase(0); if (r2) return r2;
-        RSN_HIP(hipMemcpyAsync(hmap, ph.blk_map, nbk * PH_CAND * 8, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(hmap, ph.blk_map, nbk * PH_CAND * 8, hipMemcpyDeviceToHost, s));
         RSN_HIP(hipStreamSynchronize(s));
         if (dbg2) fprintf(stderr, "huffman decode, phases: +%.3f ms: every entry of every lane walked, the blocks' maps on the host\n", ph_ms());
         // the blocks chained: block 0 is entered at the stream's first code bit (bit 0 of its table), block b + 1 at the bit b left at
@@ -1139,7 +1139,7 @@ int huff_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
             e = m.x;
         }
         if (dbg2) fprintf(stderr, "huffman decode, phases: +%.3f ms: the blocks chained\n", ph_ms());
-        RSN_HIP(hipMemcpyAsync(d_true, tc.data(), nbk, hipMemcpyHostToDevice, s));
+        RSN_HIP(copy_async(d_true, tc.data(), nbk, hipMemcpyHostToDevice, s));
         r2 = launch_phase(2); if (r2) return r2;
         RSN_HIP(hipStreamSynchronize(s));                                     // (tc is host memory: the copy has left it)
         if (dbg2) fprintf(stderr, "huffman decode, phases: +%.3f ms: the true path written\n", ph_ms());
@@ -1156,7 +1156,7 @@ int huff_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
         RSN_LAUNCH("huff_dec_fix_list", k_dec_fix_list, dim3((uint32_t)ceil_div(n_blk, 256)), dim3(256), 0, s, (const uint16_t *)a.exit_rel, (const uint16_t *)a.entry_rel, n_blk, d_fix_list, d_fix_count);
         a.fix_list = d_fix_list; a.fix_count = d_fix_count;
         rc = launch_sync(); if (rc) return rc;
-        RSN_HIP(hipMemcpyAsync(&ht->changed, d_changed, 4, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(&ht->changed, d_changed, 4, hipMemcpyDeviceToHost, s));
     }
     rc = offsets_and_bytes(); if (rc) return rc;                      // ... on the assumption that the one fixing pass settled it (it nearly always does)
     RSN_HIP(hipStreamSynchronize(s));
@@ -1183,8 +1183,8 @@ int huff_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
             RSN_HIP(hipMemsetAsync(d_changed, 0, 8, s));
             RSN_LAUNCH("huff_dec_fix_list", k_dec_fix_list, dim3((uint32_t)ceil_div(n_blk, 256)), dim3(256), 0, s, (const uint16_t *)a.exit_rel, (const uint16_t *)a.entry_rel, n_blk, d_fix_list, d_fix_count);
             rc = launch_sync(); if (rc) return rc;
-            RSN_HIP(hipMemcpyAsync(&ht->changed, d_changed, 4, hipMemcpyDeviceToHost, s));
-            RSN_HIP(hipMemcpyAsync(&ht->stuck, d_stuck, 4, hipMemcpyDeviceToHost, s));
+            RSN_HIP(copy_async(&ht->changed, d_changed, 4, hipMemcpyDeviceToHost, s));
+            RSN_HIP(copy_async(&ht->stuck, d_stuck, 4, hipMemcpyDeviceToHost, s));
             RSN_HIP(hipStreamSynchronize(s));
             if (ht->stuck) {
                 const int prc = phase_solve();

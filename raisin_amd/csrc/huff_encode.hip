@@ -100,6 +100,156 @@ __global__ __launch_bounds__(HB) void k_byte_hist(const uint8_t *__restrict__ in
     if (hi_any & 0x80808080u) atomicAdd(&ghist[128], 1ull);
 }
 
+// ---------------------------------------------------------------- byte counts over all 256 values (the layered round trip, rsn_api.hip)
+// What engine.BenchmarkFile counts on the host (engine.go:367-370, :412-415).  K1's shape with 256 bins: bin-major, COPIES copies of
+// every bin, copy = lane % COPIES.  With 32 copies the copy IS the bank within a 32-lane group (index = bin * 32 + copy: banks copy and
+// copy + 32 of the 64), so a run of one byte never meets itself on one LDS address; with 16, lanes l and l + 16 share a counter.
+// No per-tile output: the LDS counts stay across a block's tiles and are folded into 64-bit registers (thread = bin) every FOLD tiles,
+// long before a 32-bit counter can wrap, and at the end; one atomic per bin and block.
+template <int COPIES, int INFLIGHT>
+__global__ __launch_bounds__(HB) void k_byte_hist256(const uint8_t *__restrict__ in, size_t n, uint32_t n_tiles,
+                                                     unsigned long long *__restrict__ ghist) {
+    static_assert(HB == 256 && (COPIES == 16 || COPIES == 32) && (TILE / ROUND) % INFLIGHT == 0, "a thread per bin, whole batches of loads");
+    constexpr uint32_t FOLD = 1024;                                     // 1024 tiles of 64 KiB: at most 2^26 increments of one counter
+    constexpr int LOG = COPIES == 32 ? 5 : 4;
+    __shared__ uint32_t h[256 * COPIES];
+    const int tid = threadIdx.x;
+    const uint32_t copy = tid & (COPIES - 1);
+    unsigned long long mine = 0;
+    auto add16 = [&](const uint4 &v) {
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            atomicAdd(&h[((w[j] & 0xFF) << LOG) | copy], 1u);
+            atomicAdd(&h[(((w[j] >> 8) & 0xFF) << LOG) | copy], 1u);
+            atomicAdd(&h[(((w[j] >> 16) & 0xFF) << LOG) | copy], 1u);
+            atomicAdd(&h[((w[j] >> 24) << LOG) | copy], 1u);
+        }
+    };
+    auto fold = [&] {                                                   // (called by every thread of the block)
+        __syncthreads();
+        uint32_t s = 0;
+#pragma unroll
+        for (int r = 0; r < COPIES; r++) s += h[(tid << LOG) | ((r + tid) & (COPIES - 1))];   // rotated: conflict-free
+        mine += s;
+        __syncthreads();
+        for (int i = tid; i < 256 * COPIES; i += HB) h[i] = 0;
+        __syncthreads();
+    };
+    for (int i = tid; i < 256 * COPIES; i += HB) h[i] = 0;
+    __syncthreads();
+    uint32_t since = 0;
+    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const size_t base = (size_t)t * TILE;
+        if (base + TILE <= n) {
+            const uint4 *src = reinterpret_cast<const uint4 *>(in + base) + tid;
+#pragma unroll
+            for (int k0 = 0; k0 < TILE / ROUND; k0 += INFLIGHT) {
+                uint4 v[INFLIGHT];
+#pragma unroll
+                for (int k = 0; k < INFLIGHT; k++) v[k] = ld16<true>(src + (k0 + k) * HB);
+#pragma unroll
+                for (int k = 0; k < INFLIGHT; k++) add16(v[k]);
+            }
+        } else {
+            for (int k = 0; k < TILE / ROUND; k++) {
+                const size_t off = base + (size_t)(k * HB + tid) * 16;
+                if (off + 16 <= n) add16(*reinterpret_cast<const uint4 *>(in + off));
+                else if (off < n) for (size_t p = off; p < n; p++) atomicAdd(&h[((uint32_t)in[p] << LOG) | copy], 1u);
+            }
+        }
+        if (++since == FOLD) { fold(); since = 0; }
+    }
+    fold();
+    if (mine) atomicAdd(&ghist[tid], mine);
+}
+
+// ---------------------------------------------------------------- the lowest offset at which two buffers differ (the layered round trip)
+// reflect.DeepEqual of engine.go:424 as a pass over both buffers' first n bytes: 16 B per lane from each, the first differing byte of a
+// lane's 16 from the XOR's lowest set bit, the minimum over the wavefront by shuffles, over the block through one LDS word, and ONE
+// atomicMin per block -- a block's tiles ascend, so its first tile with a difference is its answer and it ends there.  A block whose next
+// tile lies behind an offset somebody has published ends as well.  *first: ~0 before the launch, and after it when nothing differs.
+template <int INFLIGHT>
+__global__ __launch_bounds__(HB) void k_bytes_differ(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, size_t n, uint32_t n_tiles,
+                                                     unsigned long long *__restrict__ first) {
+    static_assert((TILE / ROUND) % INFLIGHT == 0, "whole batches of loads");
+    constexpr unsigned long long NONE = ~0ull;
+    __shared__ unsigned long long s_pub, s_min;
+    const int tid = threadIdx.x;
+    auto diff16 = [](const uint4 &x, const uint4 &y) -> uint32_t {       // index of the first differing byte of the 16, or 16
+        const uint32_t d[4] = {x.x ^ y.x, x.y ^ y.y, x.z ^ y.z, x.w ^ y.w};
+        uint32_t at = 16;
+#pragma unroll
+        for (int j = 3; j >= 0; j--) if (d[j]) at = 4 * j + ((uint32_t)__ffs((int)d[j]) - 1) / 8;
+        return at;
+    };
+    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const size_t base = (size_t)t * TILE;
+        if (tid == 0) { s_pub = __hip_atomic_load(first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); s_min = NONE; }
+        __syncthreads();
+        if (base >= s_pub) return;                                       // (the same word for every thread: the block leaves as one)
+        unsigned long long mine = NONE;
+        if (base + TILE <= n) {
+            const uint4 *pa = reinterpret_cast<const uint4 *>(a + base) + tid, *pb = reinterpret_cast<const uint4 *>(b + base) + tid;
+#pragma unroll
+            for (int k0 = 0; k0 < TILE / ROUND; k0 += INFLIGHT) {
+                uint4 va[INFLIGHT], vb[INFLIGHT];
+#pragma unroll
+                for (int k = 0; k < INFLIGHT; k++) { va[k] = ld16<true>(pa + (k0 + k) * HB); vb[k] = ld16<true>(pb + (k0 + k) * HB); }
+#pragma unroll
+                for (int k = 0; k < INFLIGHT; k++) {
+                    const uint32_t at = diff16(va[k], vb[k]);
+                    if (at < 16 && mine == NONE) mine = base + (size_t)((k0 + k) * HB + tid) * 16 + at;
+                }
+            }
+        } else {
+            for (int k = 0; k < TILE / ROUND && mine == NONE; k++) {
+                const size_t off = base + (size_t)(k * HB + tid) * 16;
+                if (off + 16 <= n) {
+                    const uint32_t at = diff16(*reinterpret_cast<const uint4 *>(a + off), *reinterpret_cast<const uint4 *>(b + off));
+                    if (at < 16) mine = off + at;
+                } else if (off < n) {
+                    for (size_t p = off; p < n; p++) if (a[p] != b[p]) { mine = p; break; }
+                }
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { const unsigned long long o = __shfl_xor(mine, d); mine = o < mine ? o : mine; }
+        if ((tid & 63) == 0 && mine != NONE) atomicMin(&s_min, mine);
+        __syncthreads();
+        const unsigned long long found = s_min;
+        if (found != NONE) { if (tid == 0) atomicMin(first, found); return; }
+        __syncthreads();                                                 // (s_min has been read by all before thread 0 resets it)
+    }
+}
+
+// both passes as the layered round trip queues them (codecs.h); persistent grids from the occupancy query, like K1's
+int byte_hist256_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, unsigned long long *d_hist) {
+    RSN_HIP(hipMemsetAsync(d_hist, 0, 256 * 8, s));
+    if (n == 0) return RSN_OK;
+    const uint32_t n_tiles = (uint32_t)ceil_div(n, (size_t)TILE);
+    static const bool narrow = getenv("RSN_HIST256_COPIES") && atoi(getenv("RSN_HIST256_COPIES")) == 16;   // the shape that lost (LEDGER.md), for the A/B
+    dim3 grid;
+    if (narrow) {
+        int rc = persistent_grid(c, reinterpret_cast<const void *>(k_byte_hist256<16, 4>), HB, n_tiles, &grid); if (rc) return rc;
+        RSN_LAUNCH("byte_hist256", (k_byte_hist256<16, 4>), grid, dim3(HB), 0, s, d_in, n, n_tiles, d_hist);
+    } else {
+        int rc = persistent_grid(c, reinterpret_cast<const void *>(k_byte_hist256<32, 4>), HB, n_tiles, &grid); if (rc) return rc;
+        RSN_LAUNCH("byte_hist256", (k_byte_hist256<32, 4>), grid, dim3(HB), 0, s, d_in, n, n_tiles, d_hist);
+    }
+    return RSN_OK;
+}
+
+int bytes_differ_dev(Ctx &c, hipStream_t s, const uint8_t *d_a, const uint8_t *d_b, size_t n, unsigned long long *d_first) {
+    RSN_HIP(hipMemsetAsync(d_first, 0xFF, 8, s));
+    if (n == 0) return RSN_OK;
+    const uint32_t n_tiles = (uint32_t)ceil_div(n, (size_t)TILE);
+    dim3 grid;
+    int rc = persistent_grid(c, reinterpret_cast<const void *>(k_bytes_differ<4>), HB, n_tiles, &grid); if (rc) return rc;
+    RSN_LAUNCH("bytes_differ", (k_bytes_differ<4>), grid, dim3(HB), 0, s, d_a, d_b, n, n_tiles, d_first);
+    return RSN_OK;
+}
+
 // ---------------------------------------------------------------- Go UTF-8 classification (rune path)
 // Length of the valid sequence starting with b0 (1 ASCII, 2..4), 0 if invalid
 // (=> U+FFFD consuming one byte).  Accept ranges: go1.15 unicode/utf8.
@@ -834,7 +984,7 @@ int hist_ascii_or_rune(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uin
     }
     void *hp; rc = pinned_buf(c, 256 * 8, &hp); if (rc) return rc;
     unsigned long long *h = (unsigned long long *)hp;
-    RSN_HIP(hipMemcpyAsync(h, d_gh, 256 * 8, hipMemcpyDeviceToHost, s));
+    RSN_HIP(copy_async(h, d_gh, 256 * 8, hipMemcpyDeviceToHost, s));
     RSN_HIP(hipStreamSynchronize(s));
     ascii = h[128] == 0;   // no byte >= 0x80 seen
     syms.clear();
@@ -863,13 +1013,13 @@ int hist_ascii_or_rune(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uin
     const bool one_trip = bound * sizeof(HuffSym) <= (1u << 20);      // small inputs: count and pairs in one copy
     rc = pinned_buf(c, 16 + (one_trip ? bound * sizeof(HuffSym) : 0), &hp); if (rc) return rc;
     h = (unsigned long long *)hp;
-    RSN_HIP(hipMemcpyAsync(h, d_cnt, 16 + (one_trip ? bound * sizeof(HuffSym) : 0), hipMemcpyDeviceToHost, s));   // (d_pairs follows d_cnt[2])
+    RSN_HIP(copy_async(h, d_cnt, 16 + (one_trip ? bound * sizeof(HuffSym) : 0), hipMemcpyDeviceToHost, s));   // (d_pairs follows d_cnt[2])
     RSN_HIP(hipStreamSynchronize(s));
     const size_t present = (size_t)h[0];
     if (!one_trip) {
         rc = pinned_buf(c, 16 + present * sizeof(HuffSym), &hp); if (rc) return rc;
         h = (unsigned long long *)hp;
-        RSN_HIP(hipMemcpyAsync(h + 2, d_pairs, present * sizeof(HuffSym), hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(h + 2, d_pairs, present * sizeof(HuffSym), hipMemcpyDeviceToHost, s));
         RSN_HIP(hipStreamSynchronize(s));
     }
     const HuffSym *hs = reinterpret_cast<const HuffSym *>(h + 2);
@@ -913,7 +1063,7 @@ int huff_slice_emit(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, const 
     const size_t H = hdr.size();
     const uint32_t tile = sl.tile, n_tiles = sl.n_tiles;
     if (slice_bits == 0) {   // one distinct symbol: code "" (huffman.go:110-116), no payload bytes
-        if (H) RSN_HIP(hipMemcpyAsync(d_out, hdr.data(), H, hipMemcpyHostToDevice, s));
+        if (H) RSN_HIP(copy_async(d_out, hdr.data(), H, hipMemcpyHostToDevice, s));
         RSN_HIP(hipStreamSynchronize(s));
         return RSN_OK;
     }
@@ -933,7 +1083,7 @@ int huff_slice_emit(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, const 
         memcpy(hcodes + 128, hdr.data(), H);
         if (hcodes != fa.inl) {
             rc = dev_buf(c, 3, 128 + H + 16, &p); if (rc) return rc;
-            RSN_HIP(hipMemcpyAsync(p, hcodes, 128 + H, hipMemcpyHostToDevice, s));
+            RSN_HIP(copy_async(p, hcodes, 128 + H, hipMemcpyHostToDevice, s));
             fa.codes = (const uint8_t *)p;
         }
         dim3 grid;
@@ -961,7 +1111,7 @@ int huff_slice_emit(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, const 
         for (uint32_t i = 0; i < k; i++) hl[i] = RuneCode{tree.rune[i], codes.len[i], codes.code[i]};
         rc = dev_buf(c, 3, (size_t)kMaxRune * 9 + 64 + (size_t)k * sizeof(RuneCode), &p); if (rc) return rc;
         RuneCode *d_list = (RuneCode *)((uint8_t *)p + round_up((size_t)kMaxRune * 9, 64));
-        RSN_HIP(hipMemcpyAsync(d_list, hl, (size_t)k * sizeof(RuneCode), hipMemcpyHostToDevice, s));
+        RSN_HIP(copy_async(d_list, hl, (size_t)k * sizeof(RuneCode), hipMemcpyHostToDevice, s));
         a.code64 = (const unsigned long long *)p;
         d_len8 = (uint8_t *)p + (size_t)kMaxRune * 8;
         RSN_LAUNCH("huff_rune_table", k_rune_table, dim3((k + 255) / 256), dim3(256), 0, s, (const RuneCode *)d_list, k, (unsigned long long *)p, d_len8);
@@ -977,7 +1127,7 @@ int huff_slice_emit(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, const 
             if (codes.max_len <= (unsigned)TAB_LEN_SHIFT) ht->t32[r] = ((uint32_t)codes.len[i] << TAB_LEN_SHIFT) | (uint32_t)codes.code[i];
         }
         rc = dev_buf(c, 3, sizeof(Tab), &p); if (rc) return rc;
-        RSN_HIP(hipMemcpyAsync(p, ht, sizeof(Tab), hipMemcpyHostToDevice, s));
+        RSN_HIP(copy_async(p, ht, sizeof(Tab), hipMemcpyHostToDevice, s));
         Tab *dt = (Tab *)p;
         a.tab32 = dt->t32; a.code64 = dt->c64;
         d_len8 = dt->l8;
@@ -1002,7 +1152,7 @@ int huff_slice_emit(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, const 
     a.tiles_per_block = tiles_per_block; a.n_tiles = n_tiles; a.out_words = (uint32_t *)d_out; a.tile = tile; a.smask = sl.d_smask;
     RSN_LAUNCH("huff_emit_init", k_emit_init, dim3((uint32_t)ceil_div(n_blocks + 1, 256)), dim3(256), 0, s,
                (uint32_t *)d_out, d_tile_off, base_bits, tiles_per_block, n_tiles, n_blocks, base_bits + slice_bits);
-    if (H) RSN_HIP(hipMemcpyAsync(d_out, hdr.data(), H, hipMemcpyHostToDevice, s));
+    if (H) RSN_HIP(copy_async(d_out, hdr.data(), H, hipMemcpyHostToDevice, s));
     if (mode == MODE_ASCII) RSN_LAUNCH("huff_emit", k_emit_ascii32<32>, dim3(n_blocks), dim3(HB), 0, s, a);   // (32 symbols a lane: 48 / 64 measured no better, r02)
     else if (mode == MODE_ASCII_WIDE) RSN_LAUNCH("huff_emit_wide", k_emit<MODE_ASCII_WIDE>, dim3(n_blocks), dim3(HB), 0, s, a);
     else RSN_LAUNCH("huff_emit_rune", k_emit<MODE_RUNE>, dim3(n_blocks), dim3(HB), 0, s, a);

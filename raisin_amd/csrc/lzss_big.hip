@@ -158,7 +158,7 @@ int lzss_encode_big(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32_t E, uint
     rc = scan_u64(c, s, "lzss_scan", d_bbytes, d_boff, n_blk, d_btot); if (rc) return rc;
     void *hp; rc = pinned_buf(c, 64, &hp); if (rc) return rc;
     unsigned long long *h64 = (unsigned long long *)hp;
-    RSN_HIP(hipMemcpyAsync(h64, d_btot, 16, hipMemcpyDeviceToHost, s));
+    RSN_HIP(copy_async(h64, d_btot, 16, hipMemcpyDeviceToHost, s));
     RSN_HIP(hipStreamSynchronize(s));
     if ((uint32_t)h64[1]) return c.fail(RSN_ERR_LIMIT, "lzss: window %u on a stream whose candidates share kilobyte-long prefixes (long runs) is outside "
                                         "the work budget of the large-window search; windows up to 8192 have no such limit", W);

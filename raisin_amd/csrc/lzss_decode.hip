@@ -1275,7 +1275,7 @@ int lzss_unescape(Ctx &c, hipStream_t s, const uint8_t *d_esc, size_t E, bool ha
     RSN_LAUNCH("lzss_une_carry", k_une_carry, dim3(1), dim3(1024), 0, s, (const uint8_t *)d_summ, n_ub, d_inpar);
     RSN_LAUNCH("lzss_une_count", k_une_count, dim3(n_ub), dim3(ZB), 0, s, d_esc, E, (const uint8_t *)d_inpar, d_ulen);
     rc = scan_u64(c, s, "lzss_dec_scan", d_ulen, d_uoff, n_ub, d_utot); if (rc) return rc;
-    RSN_HIP(hipMemcpyAsync(h64, d_utot, 8, hipMemcpyDeviceToHost, s));
+    RSN_HIP(copy_async(h64, d_utot, 8, hipMemcpyDeviceToHost, s));
     RSN_HIP(hipStreamSynchronize(s));
     const size_t total = (size_t)h64[0];
     *out_n = total;
@@ -1367,7 +1367,7 @@ static int lzss_decode_run_tail(Ctx &c, hipStream_t s, const uint8_t *d_in, size
     // ---- where the run begins
     RSN_HIP(hipMemsetAsync(d_brk, 0, 8, s));
     if (t_end > tl) RSN_LAUNCH("lzss_dec_run_start", k_lzd_run_start, dim3((uint32_t)ceil_div((size_t)(t_end - tl), (size_t)4096)), dim3(256), 0, s, d_in, t_end, tl, d_brk);
-    RSN_HIP(hipMemcpyAsync(h_brk, d_brk, 8, hipMemcpyDeviceToHost, s));
+    RSN_HIP(copy_async(h_brk, d_brk, 8, hipMemcpyDeviceToHost, s));
     RSN_HIP(hipStreamSynchronize(s));
     const unsigned long long brk = *h_brk;
     unsigned long long a0 = std::max<unsigned long long>(brk, tl) - tl;   // [a0, t_end) repeats with the token's length and ends in the token
@@ -1422,11 +1422,11 @@ int lzss_decode_impl(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8
     d_need = (unsigned long long *)p; d_span = (uint16_t *)(d_need + n_cb);
     RSN_LAUNCH("lzss_dec_count", k_lzd_count2, dim3(n_cb), dim3(ZB), 0, s, d_in, n, d_blen, d_span, d_need, (uint32_t *)(d_flag + 2), d_flag);
     rc = scan_u64(c, s, "lzss_dec_scan", d_blen, d_boff, n_cb, d_btot); if (rc) return rc;
-    RSN_HIP(hipMemcpyAsync(h64, d_btot, 8, hipMemcpyDeviceToHost, s));
-    RSN_HIP(hipMemcpyAsync((void *)hflag, d_flag, 24, hipMemcpyDeviceToHost, s));
+    RSN_HIP(copy_async(h64, d_btot, 8, hipMemcpyDeviceToHost, s));
+    RSN_HIP(copy_async((void *)hflag, d_flag, 24, hipMemcpyDeviceToHost, s));
     static const bool no_run_tail = getenv("RSN_LZSS_DEC_NO_RUN_TAIL") != nullptr;   // A/B switch (tests): a stream that ends in one token repeated through the ordinary decoder
     const bool run_cand = !esc_dst && d_out && !no_run_tail && n >= ((size_t)1 << 16);
-    if (run_cand) RSN_HIP(hipMemcpyAsync(h_tail, d_in + (n - 64), 64, hipMemcpyDeviceToHost, s));
+    if (run_cand) RSN_HIP(copy_async(h_tail, d_in + (n - 64), 64, hipMemcpyDeviceToHost, s));
     RSN_HIP(hipStreamSynchronize(s));
     if (hflag[0] & 1) return c.fail(RSN_ERR_FORMAT, "lzss: malformed \"<ptr,len>\" token");
     if (hflag[0] & 2) return c.fail(RSN_ERR_FORMAT, "lzss: back-reference outside the decoded data (reference: slice bounds out of range, lzss.go:350)");
@@ -1469,7 +1469,7 @@ int lzss_decode_impl(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8
     } else {
         RSN_HIP(hipMemsetAsync(d_maxptr, 0, 4, s));      // (k_lzd_tiles raises it again)
         RSN_LAUNCH("lzss_dec_tiles", k_lzd_tiles, dim3(n_cb), dim3(ZB), 0, s, d_in, n, d_boff, d_tinfo, d_maxptr, d_flag);
-        RSN_HIP(hipMemcpyAsync((void *)hflag, d_flag, 16, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async((void *)hflag, d_flag, 16, hipMemcpyDeviceToHost, s));
         RSN_HIP(hipStreamSynchronize(s));   // nothing may chase a pointer before every token has been validated
         if (hflag[0]) return c.fail(RSN_ERR_FORMAT, "lzss: back-reference outside the decoded data (reference: slice bounds out of range, lzss.go:350)");
     }
@@ -1511,7 +1511,7 @@ int lzss_decode_impl(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8
                 // (k_lzd_check's verdict before the capacity answer -- a malformed stream is RSN_ERR_FORMAT on the first call,
                 //  whatever the buffer; a round trip on this path only)
                 if (one_pass) {
-                    RSN_HIP(hipMemcpyAsync((void *)hflag, d_flag, 16, hipMemcpyDeviceToHost, s));
+                    RSN_HIP(copy_async((void *)hflag, d_flag, 16, hipMemcpyDeviceToHost, s));
                     RSN_HIP(hipStreamSynchronize(s));
                     if (hflag[0] & 2) return c.fail(RSN_ERR_FORMAT, "lzss: back-reference outside the decoded data (reference: slice bounds out of range, lzss.go:350)");
                 }
@@ -1521,13 +1521,13 @@ int lzss_decode_impl(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8
         }
         RSN_LAUNCH("lzss_dec_emit", k_lzd_emit, dim3(n_groups), dim3(DTH), (size_t)TL * 2 + 16, s, d_desc, TL, n_tiles, dgrp, E, d_gtail, plain ? d_out : d_esc, d_summ, plain ? 1 : 0,
                    (const uint32_t *)d_rt_cnt, (const uint32_t *)d_rt_runs);   // (+16: a run tile reads whole dwords of the tail, up to three bytes past it)
-        RSN_HIP(hipMemcpyAsync((void *)hflag, d_flag, 16, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async((void *)hflag, d_flag, 16, hipMemcpyDeviceToHost, s));
         RSN_HIP(hipStreamSynchronize(s));
         if (hflag[0] & 2) return c.fail(RSN_ERR_FORMAT, "lzss: back-reference outside the decoded data (reference: slice bounds out of range, lzss.go:350)");   // k_lzd_check's verdict
         if (hflag[3]) tile_path = false;                                  // a tile's input did not fit (zero-length tokens): redo with the general path
         else if (plain) return RSN_OK;                                    // bytes are in place
     } else if (one_pass) {                                                // the general path chases pointers through memory: k_lzd_check's verdict first
-        RSN_HIP(hipMemcpyAsync((void *)hflag, d_flag, 16, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async((void *)hflag, d_flag, 16, hipMemcpyDeviceToHost, s));
         RSN_HIP(hipStreamSynchronize(s));
         if (hflag[0] & 2) return c.fail(RSN_ERR_FORMAT, "lzss: back-reference outside the decoded data (reference: slice bounds out of range, lzss.go:350)");
     }
@@ -1540,7 +1540,7 @@ int lzss_decode_impl(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8
             if (round > 40) return c.fail(RSN_ERR_DEVICE, "lzss: pointer jumping did not converge");
             RSN_HIP(hipMemsetAsync(d_flag + 1, 0, 4, s));
             RSN_LAUNCH("lzss_dec_jump", k_lzd_jump, dim3(grid), dim3(ZB), 0, s, d_src, E, d_flag + 1);
-            RSN_HIP(hipMemcpyAsync((void *)hflag, d_flag, 8, hipMemcpyDeviceToHost, s));
+            RSN_HIP(copy_async((void *)hflag, d_flag, 8, hipMemcpyDeviceToHost, s));
             RSN_HIP(hipStreamSynchronize(s));
             if (!hflag[1]) break;
         }
@@ -1578,9 +1578,9 @@ int lzss_decode_sections(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, u
         RSN_LAUNCH("lzss_dec_count", k_lzd_count2, dim3(n_cb), dim3(ZB), 0, s, d_in, n, d_blen, d_span, d_need, (uint32_t *)(d_flag + 2), d_flag);
         rc = scan_u64(c, s, "lzss_dec_scan", d_blen, d_boff, n_cb, d_btot); if (rc) return rc;
         RSN_LAUNCH("lzss_dec_tiles", k_lzd_check, dim3((uint32_t)ceil_div(n_cb, 256)), dim3(256), 0, s, (const unsigned long long *)d_need, (const unsigned long long *)d_boff, n_cb, d_flag);
-        RSN_HIP(hipMemcpyAsync(boff.data(), d_boff, (size_t)n_cb * 8, hipMemcpyDeviceToHost, s));
-        RSN_HIP(hipMemcpyAsync(&boff[n_cb], d_btot, 8, hipMemcpyDeviceToHost, s));
-        RSN_HIP(hipMemcpyAsync(hflag, d_flag, 24, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(boff.data(), d_boff, (size_t)n_cb * 8, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(&boff[n_cb], d_btot, 8, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(hflag, d_flag, 24, hipMemcpyDeviceToHost, s));
         RSN_HIP(hipStreamSynchronize(s));
     }
     if (hflag[0] & 1) return c.fail(RSN_ERR_FORMAT, "lzss: malformed \"<ptr,len>\" token");
@@ -1599,7 +1599,7 @@ int lzss_decode_sections(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, u
         if (q == 0 || q >= n) { *out = std::min(q, n); return RSN_OK; }
         uint8_t buf[2 * MAXTOK];
         const size_t lo = q >= (size_t)MAXTOK ? q - MAXTOK : 0, hi = std::min(n, q + MAXTOK);
-        RSN_HIP(hipMemcpyAsync(buf, d_in + lo, hi - lo, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(buf, d_in + lo, hi - lo, hipMemcpyDeviceToHost, s));
         RSN_HIP(hipStreamSynchronize(s));
         *out = q;
         for (size_t k = q; k-- > lo;) {                                   // the last '<' or '>' before q
@@ -1631,8 +1631,8 @@ int lzss_decode_sections(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, u
         const size_t W = e0 <= hmax ? e0 : hmax + ((e0 - hmax) & 15);
         const size_t vn = W + (c1 - c0);
         if (vn + 64 > sec_buf) { sec_buf = vn + 64 + (vn >> 3); rc = dev_buf(c, 36, sec_buf, &p); if (rc) return rc; d_v = (uint8_t *)p; }
-        if (W) RSN_HIP(hipMemcpyAsync(d_v, d_esc + (e0 - W), W, hipMemcpyDeviceToDevice, s));
-        if (c1 > c0) RSN_HIP(hipMemcpyAsync(d_v + W, d_in + c0, c1 - c0, hipMemcpyDeviceToDevice, s));
+        if (W) RSN_HIP(copy_async(d_v, d_esc + (e0 - W), W, hipMemcpyDeviceToDevice, s));
+        if (c1 > c0) RSN_HIP(copy_async(d_v + W, d_in + c0, c1 - c0, hipMemcpyDeviceToDevice, s));
         size_t got = 0;
         if (vn) {
             rc = lzss_decode_impl(c, s, d_v, vn, nullptr, 0, &got, d_esc + (e0 - W)); if (rc) return rc;
@@ -1702,9 +1702,9 @@ int lzss_decode_sliced(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uin
         volatile int *hflag = (volatile int *)(h64 + 1);
         uint8_t *hcut = (uint8_t *)(h64 + 8);
         const size_t cut_lo = q1 >= (size_t)MAXTOK ? q1 - MAXTOK : 0, cut_hi = std::min(n, q1 + MAXTOK);
-        RSN_HIP(hipMemcpyAsync(h64, d_btot, 8, hipMemcpyDeviceToHost, s));
-        RSN_HIP(hipMemcpyAsync((void *)hflag, d_flag, 24, hipMemcpyDeviceToHost, s));
-        if (b1 < n_cb) RSN_HIP(hipMemcpyAsync(hcut, d_in + cut_lo, cut_hi - cut_lo, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(h64, d_btot, 8, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async((void *)hflag, d_flag, 24, hipMemcpyDeviceToHost, s));
+        if (b1 < n_cb) RSN_HIP(copy_async(hcut, d_in + cut_lo, cut_hi - cut_lo, hipMemcpyDeviceToHost, s));
         RSN_HIP(hipStreamSynchronize(s));
         if (hflag[0] & 1) return c.fail(RSN_ERR_FORMAT, "lzss: malformed \"<ptr,len>\" token");
         if (hflag[0] & 2) return c.fail(RSN_ERR_FORMAT, "lzss: back-reference outside the decoded data (reference: slice bounds out of range, lzss.go:350)");
@@ -1731,8 +1731,8 @@ int lzss_decode_sliced(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uin
         const size_t W = e0 <= hmax ? e0 : hmax + ((e0 - hmax) & 15);
         const size_t vn = W + (c1 - c0);
         if (vn + 64 > sec_buf) { sec_buf = vn + 64 + (vn >> 3); rc = dev_buf(c, 36, sec_buf, &p); if (rc) return rc; d_v = (uint8_t *)p; }
-        if (W) RSN_HIP(hipMemcpyAsync(d_v, d_esc + (e0 - W), W, hipMemcpyDeviceToDevice, s));
-        if (c1 > c0) RSN_HIP(hipMemcpyAsync(d_v + W, d_in + c0, c1 - c0, hipMemcpyDeviceToDevice, s));
+        if (W) RSN_HIP(copy_async(d_v, d_esc + (e0 - W), W, hipMemcpyDeviceToDevice, s));
+        if (c1 > c0) RSN_HIP(copy_async(d_v + W, d_in + c0, c1 - c0, hipMemcpyDeviceToDevice, s));
         RSN_HIP(hipMemsetAsync(d_v + vn, 0, 64, s));
         size_t got = 0;
         if (vn) {

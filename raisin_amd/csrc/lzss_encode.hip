@@ -2181,7 +2181,7 @@ static int lzss_encode_stream(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32
             // 2.4 ms; at 272 blocks of 1024 instead of 136 of 2048 a period broken every 100 KB lost: 4.8 -> 5.6 ms a MiB).
             RSN_HIP(hipMemsetAsync(d_ttot + 3, 0, 8, s));
             RSN_LAUNCH("lzss_scan", k_count_flags, dim3((uint32_t)ceil_div(n_strips, 256)), dim3(256), 0, s, only, n_strips, (unsigned long long *)(d_ttot + 3));
-            RSN_HIP(hipMemcpyAsync(h64 + 3, d_ttot + 3, 8, hipMemcpyDeviceToHost, s));
+            RSN_HIP(copy_async(h64 + 3, d_ttot + 3, 8, hipMemcpyDeviceToHost, s));
             RSN_HIP(hipStreamSynchronize(s));
             const uint64_t flagged = h64[3];
             if (flagged == 0) return RSN_OK;
@@ -2241,7 +2241,7 @@ static int lzss_encode_stream(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32
         RSN_LAUNCH("lzss_sample", k_sample_tiles, dim3(1), dim3(SAMPLE_TILES), 0, s, d_redo_list, SAMPLE_TILES, n_pt);
         ChainArgs hs{d_fc, E, W, d_keys, 2u | halo_bit | (raw ? 8u : 0u), pfrom, nullptr, ChainTail{d_heavy, d_dense, d_tchain, d_dump, d_redo_list, (uint32_t *)(d_ttot + 3), d_step, d_redo_start, nullptr, nullptr}};
         rc = launch_chain("lzss_sample", SAMPLE_TILES, hs); if (rc) return rc;
-        RSN_HIP(hipMemcpyAsync(h64 + 3, d_ttot + 3, 8, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(h64 + 3, d_ttot + 3, 8, hipMemcpyDeviceToHost, s));
         RSN_HIP(hipStreamSynchronize(s));
         if ((uint32_t)h64[3] * 4 >= SAMPLE_TILES * 3) { chain_mode = false; rc = need_copy(); if (rc) return rc; }
     }
@@ -2301,7 +2301,7 @@ static int lzss_encode_stream(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32
             RSN_LAUNCH("lzss_chain_verify", k_chain_verify, dim3((uint32_t)ceil_div(n_pt, 256)), dim3(256), 0, s, d_tchain, n_pt, E, (uint32_t)PT, (uint32_t *)(d_ttot + 1), d_redo_list, redo_cap,
                        d_redo_start, (const uint32_t *)(with_pred ? d_pred : nullptr), list_gave ? 1u : 0u);
             rc = scan_u64(c, s, "lzss_scan", d_tbytes, d_toff, n_pt, d_ttot); if (rc) return rc;
-            RSN_HIP(hipMemcpyAsync(h64, d_ttot, 32, hipMemcpyDeviceToHost, s));
+            RSN_HIP(copy_async(h64, d_ttot, 32, hipMemcpyDeviceToHost, s));
             RSN_HIP(hipStreamSynchronize(s));
             return RSN_OK;
         };
@@ -2313,7 +2313,7 @@ static int lzss_encode_stream(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32
             // such visits from the window's stretches.  (A heavy tile gives up at its first such visit: the first walk was short.)
             RSN_HIP(hipMemsetAsync(d_ttot + 3, 0, 8, s));
             RSN_LAUNCH("lzss_scan", k_count_flags, dim3((uint32_t)ceil_div(n_strips, 256)), dim3(256), 0, s, (const uint32_t *)d_heavy, n_strips, (unsigned long long *)(d_ttot + 3));
-            RSN_HIP(hipMemcpyAsync(h64 + 3, d_ttot + 3, 8, hipMemcpyDeviceToHost, s));
+            RSN_HIP(copy_async(h64 + 3, d_ttot + 3, 8, hipMemcpyDeviceToHost, s));
             RSN_HIP(hipStreamSynchronize(s));
             if (h64[3]) {
                 if (dbg) fprintf(stderr, "lzss chain walk: %u tiles gave up, heavy ones in %llu strips: once more with the instance for repeated stretches\n", (uint32_t)h64[1], (unsigned long long)h64[3]);
@@ -2328,7 +2328,7 @@ static int lzss_encode_stream(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32
         if (dbg) fprintf(stderr, "lzss chain walk: %u tiles, %u gave up, %u chains that do not join, %u periodic tiles not placed\n", n_pt, (uint32_t)h64[1], (uint32_t)(h64[1] >> 32), (uint32_t)h64[2]);
         if (dbg && (uint32_t)h64[1]) {                                    // which strips, and why (heavy: the long candidates of a visit did not decide; dense: steps of one and two bytes)
             std::vector<uint32_t> fl((size_t)n_strips * 3);
-            RSN_HIP(hipMemcpyAsync(fl.data(), d_heavy, fl.size() * 4, hipMemcpyDeviceToHost, s));
+            RSN_HIP(copy_async(fl.data(), d_heavy, fl.size() * 4, hipMemcpyDeviceToHost, s));
             RSN_HIP(hipStreamSynchronize(s));
             std::string line;
             for (uint32_t k = 0, shown = 0; k < n_strips && shown < 12; k++)
@@ -2417,7 +2417,7 @@ static int lzss_encode_stream(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32
         RSN_LAUNCH("lzss_parse_fill", k_parse_fill, dim3((uint32_t)ceil_div(n_groups, 64)), dim3(64), 0, s, d_exit, d_gentry, n_groups, n_pt, d_entry);
         RSN_LAUNCH("lzss_parse_mark", k_parse_mark, dim3(n_pt), dim3(LB), mark_sh, s, d_fc, d_keys, E, W, d_entry, d_flags, d_tbytes, d_redo, d_ttot + 1);
         rc = scan_u64(c, s, "lzss_scan", d_tbytes, d_toff, n_pt, d_ttot); if (rc) return rc;
-        RSN_HIP(hipMemcpyAsync(h64, d_ttot, 16, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(h64, d_ttot, 16, hipMemcpyDeviceToHost, s));
         RSN_HIP(hipStreamSynchronize(s));
         if (h64[1] == 0) break;
         if (!chain_mode || round > n_strips) return c.fail(RSN_ERR_DEVICE, "lzss: internal error: the parse met an unevaluated position outside chain mode");
@@ -2431,9 +2431,9 @@ static int lzss_encode_stream(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32
     size_t total = (size_t)h64[0];
     if (stop_tile && stop_tile < n_pt) {
         // the section ends in front of stop_tile: what the items before it emit, and where the chain goes on
-        RSN_HIP(hipMemcpyAsync(h64, d_toff + stop_tile, 8, hipMemcpyDeviceToHost, s));
-        if (parsed_by_walk) RSN_HIP(hipMemcpyAsync(h64 + 1, &d_tchain[stop_tile].entry, 4, hipMemcpyDeviceToHost, s));
-        else RSN_HIP(hipMemcpyAsync(h64 + 1, d_entry + stop_tile, 4, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(h64, d_toff + stop_tile, 8, hipMemcpyDeviceToHost, s));
+        if (parsed_by_walk) RSN_HIP(copy_async(h64 + 1, &d_tchain[stop_tile].entry, 4, hipMemcpyDeviceToHost, s));
+        else RSN_HIP(copy_async(h64 + 1, d_entry + stop_tile, 4, hipMemcpyDeviceToHost, s));
         RSN_HIP(hipStreamSynchronize(s));
         total = (size_t)h64[0];
         const uint32_t ent = (uint32_t)h64[1];
@@ -2548,7 +2548,7 @@ static int lzss_encode_admitted(Ctx &c, hipStream_t s, const uint8_t *d_in, size
     const uint32_t n_psamp = (uint32_t)std::min<size_t>(64, std::max<size_t>(1, n / (4 * PSAMPLE_CHUNK)));
     if (tail_cand) RSN_LAUNCH("lzss_last_unlike", k_last_unlike, dim3(std::max((uint32_t)ceil_div(n_eb, 4096), n_psamp)), dim3(256), 0, s, (const uint8_t *)d_same, n_eb, d_etot + 2, d_in, n, n_psamp, d_etot + 1);
     else RSN_LAUNCH("lzss_esc_check", k_period_sample, dim3(n_psamp), dim3(256), 0, s, d_in, n, n_psamp, d_etot + 1);
-    RSN_HIP(hipMemcpyAsync(h64, d_etot + 1, 16, hipMemcpyDeviceToHost, s));
+    RSN_HIP(copy_async(h64, d_etot + 1, 16, hipMemcpyDeviceToHost, s));
     RSN_HIP(hipStreamSynchronize(s));
     copied = (h64[0] & 1ull) == 0;
     c.lz_runs = (h64[0] & 4ull) != 0;                                 // (lzss_encode_stream's choice of walk)
@@ -2557,7 +2557,7 @@ static int lzss_encode_admitted(Ctx &c, hipStream_t s, const uint8_t *d_in, size
     if (!copied) {
         RSN_LAUNCH("lzss_esc_count", k_esc_count, dim3(n_eb), dim3(LB), 0, s, d_in, n, d_extra);
         rc = scan_u64(c, s, "lzss_scan", d_extra, d_eoff, n_eb, d_etot); if (rc) return rc;
-        RSN_HIP(hipMemcpyAsync(h64, d_etot, 8, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(h64, d_etot, 8, hipMemcpyDeviceToHost, s));
         RSN_HIP(hipStreamSynchronize(s));
     }
     const size_t E64 = n + (size_t)h64[0];
@@ -2640,7 +2640,7 @@ static int lzss_encode_admitted(Ctx &c, hipStream_t s, const uint8_t *d_in, size
         // an aligned copy of its own with zeroed padding behind it, like a whole stream's (the kernels load 16 bytes at a time from the
         // base, and what lies behind the last position must not look like data): 1 GiB device to device, 0.4 ms of a 30 ms section
         rc = dev_buf(c, 36, (size_t)Es + 64, &sp); if (rc) return rc;
-        RSN_HIP(hipMemcpyAsync(sp, d_fc + a0, Es, hipMemcpyDeviceToDevice, s));
+        RSN_HIP(copy_async(sp, d_fc + a0, Es, hipMemcpyDeviceToDevice, s));
         RSN_HIP(hipMemsetAsync((uint8_t *)sp + Es, 0, 64, s));
         const uint8_t *fc_s = (const uint8_t *)sp;
         size_t got = 0; uint32_t exit_local = 0;
@@ -2711,7 +2711,7 @@ int lzss_encode_sliced(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, int
             const uint32_t n_eb = (uint32_t)ceil_div(m, ESC_TILE);
             RSN_LAUNCH("lzss_esc_check", k_esc_try, dim3((uint32_t)ceil_div(n_eb, ESC_RUN)), dim3(LB), 0, s, d_in + checked, m, (uint8_t *)nullptr, d_flag, 0u, (uint8_t *)nullptr, n_eb);
             { const uint32_t ns = (uint32_t)std::min<size_t>(64, std::max<size_t>(1, m / (4 * PSAMPLE_CHUNK))); RSN_LAUNCH("lzss_esc_check", k_period_sample, dim3(ns), dim3(256), 0, s, d_in + checked, m, ns, d_flag); }
-            RSN_HIP(hipMemcpyAsync(h64, d_flag, 8, hipMemcpyDeviceToHost, s));
+            RSN_HIP(copy_async(h64, d_flag, 8, hipMemcpyDeviceToHost, s));
             RSN_HIP(hipStreamSynchronize(s));
             if (h64[0] & 1ull) { if (dbg) fprintf(stderr, "lzss sliced: a byte that needs an escape below position %zu: encoded whole instead\n", upto); return 1; }
             if (h64[0] & 4ull) c.lz_runs = true;
@@ -2721,7 +2721,7 @@ int lzss_encode_sliced(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, int
         const uint32_t Es = (uint32_t)(b0 - a0);
         const uint32_t stop_tile = last ? 0u : (uint32_t)((entry - a0 + sec) / PT);
         rc = dev_buf(c, 36, (size_t)Es + 64, &sp); if (rc) return rc;
-        RSN_HIP(hipMemcpyAsync(sp, d_in + a0, Es, hipMemcpyDeviceToDevice, s));
+        RSN_HIP(copy_async(sp, d_in + a0, Es, hipMemcpyDeviceToDevice, s));
         RSN_HIP(hipMemsetAsync((uint8_t *)sp + Es, 0, 64, s));
         size_t got = 0; uint32_t exit_local = 0;
         rc = lzss_encode_stream(c, s, (const uint8_t *)sp, Es, std::min(W, Es), nullptr, 0, true, halo, stop_tile, d_out + written, out_cap > written ? out_cap - written : 0, &got, &exit_local,

@@ -374,14 +374,14 @@ struct PinGuard { PinHold h; ~PinGuard() { pin_release(h); } };         // a ser
 // copy command per stretch that lies wholly inside one registered range or wholly outside all of them -- a single command over memory of
 // two kinds is decided by how its first byte is mapped
 hipError_t copy_up(void *dst, const void *src, size_t len, hipStream_t st, const PinHold &h) {
-    if (h.registered || h.held.empty()) return len ? hipMemcpyAsync(dst, src, len, hipMemcpyHostToDevice, st) : hipSuccess;
+    if (h.registered || h.held.empty()) return len ? copy_async(dst, src, len, hipMemcpyHostToDevice, st) : hipSuccess;
     const uintptr_t a = (uintptr_t)src, b = a + len;
     std::vector<uintptr_t> cuts{a, b};
     for (const auto &pr : h.held) { if (pr.first > a && pr.first < b) cuts.push_back(pr.first); if (pr.second > a && pr.second < b) cuts.push_back(pr.second); }
     std::sort(cuts.begin(), cuts.end());
     for (size_t i = 0; i + 1 < cuts.size(); i++) {
         if (cuts[i + 1] == cuts[i]) continue;
-        const hipError_t e = hipMemcpyAsync((uint8_t *)dst + (cuts[i] - a), (const void *)cuts[i], cuts[i + 1] - cuts[i], hipMemcpyHostToDevice, st);
+        const hipError_t e = copy_async((uint8_t *)dst + (cuts[i] - a), (const void *)cuts[i], cuts[i + 1] - cuts[i], hipMemcpyHostToDevice, st);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -433,7 +433,7 @@ int host_call(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n, size_t 
     if (!res) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", got);
     const double t_alloc = timing ? stamp() : 0;
     if (got) {
-        RSN_HIP(hipMemcpyAsync(res, d_out, got, hipMemcpyDeviceToHost, s));
+        RSN_HIP(copy_async(res, d_out, got, hipMemcpyDeviceToHost, s));
         RSN_HIP(hipStreamSynchronize(s));
     }
     if (timing)
@@ -538,7 +538,7 @@ static int piped_call(const uint8_t *in, size_t n, size_t out_cap, size_t codec_
                 while (cut(res, total_out, k + 1) <= at) k++;
                 while (k > 0 && cut(res, total_out, k) > at) k--;
                 const size_t stop = std::min(end, cut(res, total_out, k + 1));
-                e = hipMemcpyAsync(res + at, (const uint8_t *)d_out + at, stop - at, hipMemcpyDeviceToHost, sd);
+                e = copy_async(res + at, (const uint8_t *)d_out + at, stop - at, hipMemcpyDeviceToHost, sd);
                 at = stop;
             }
             if (e == hipSuccess) pin_below(r.first + 2 * r.second);            // under these copies: where the next range will land
@@ -973,7 +973,7 @@ static int batch_on_device(Ctx &c, const std::vector<size_t> &idx, const uint8_t
             uint8_t *res = (uint8_t *)result_alloc(got);
             if (!res) { P.fail(RSN_ERR_NOMEM, "allocating a result block failed"); return; }
             outs[i] = res; out_lens[i] = got;
-            hipError_t e = hipMemcpyAsync(res, P.d_tmp[r] ? P.d_tmp[r] : P.d_out[r], got, hipMemcpyDeviceToHost, s);
+            hipError_t e = copy_async(res, P.d_tmp[r] ? P.d_tmp[r] : P.d_out[r], got, hipMemcpyDeviceToHost, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
             if (P.d_tmp[r]) { (void)hipFree(P.d_tmp[r]); P.d_tmp[r] = nullptr; }
             if (e != hipSuccess) { P.fail(RSN_ERR_DEVICE, hipGetErrorString(e)); return; }
@@ -1337,11 +1337,11 @@ static int rsn_huffman_compress_sharded_impl(const uint8_t *in, size_t n, int sh
         const uint8_t *dl = (const uint8_t *)d_out - origin;                // dl[k] = byte k of the stream
         e = hipSuccess;
         if (x.has) {
-            e = hipMemcpyAsync(&x.edge[0], dl + x.first, 1, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(&x.edge[1], dl + x.last, 1, hipMemcpyDeviceToHost, s);
-            if (w == 0 && x.first > 0 && e == hipSuccess) e = hipMemcpyAsync(res, dl, x.first, hipMemcpyDeviceToHost, s);   // the header
-            if (x.last > x.first + 1 && e == hipSuccess) e = hipMemcpyAsync(res + x.first + 1, dl + x.first + 1, x.last - x.first - 1, hipMemcpyDeviceToHost, s);
-        } else e = hipMemcpyAsync(res, dl, hi + 1 - lo, hipMemcpyDeviceToHost, s);   // one distinct symbol: the header is the stream
+            e = copy_async(&x.edge[0], dl + x.first, 1, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = copy_async(&x.edge[1], dl + x.last, 1, hipMemcpyDeviceToHost, s);
+            if (w == 0 && x.first > 0 && e == hipSuccess) e = copy_async(res, dl, x.first, hipMemcpyDeviceToHost, s);   // the header
+            if (x.last > x.first + 1 && e == hipSuccess) e = copy_async(res + x.first + 1, dl + x.first + 1, x.last - x.first - 1, hipMemcpyDeviceToHost, s);
+        } else e = copy_async(res, dl, hi + 1 - lo, hipMemcpyDeviceToHost, s);   // one distinct symbol: the header is the stream
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) sync.fail(RSN_ERR_DEVICE, hipGetErrorString(e));
     };
@@ -1364,9 +1364,258 @@ static int rsn_huffman_compress_sharded_impl(const uint8_t *in, size_t n, int sh
     return RSN_OK;
 }
 
-static void rsn_prof_enable_impl(int on) { ctx().prof = on != 0; }
+// ---- layered calls (rsn.h): a list of layers over one buffer, the stream kept on the device between the layers.
+// host_call's shape -- an input slot, an output slot, fn(c, s, d_in, d_out, cap, &got) with one retry on RSN_ERR_CAPACITY -- with the
+// two slots swapped per layer.  Slots of their own: 39 the uploaded input (the round trip keeps it to the end), 40 / 41 the stream,
+// taking turns, 42 the round trip's counts and its first-difference word.
+namespace {
+constexpr int L_IN = 39, L_A = 40, L_B = 41, L_STAT = 42;
+constexpr unsigned long long CALL_SLOTS = (3ull << 20) | (0xFFFull << 8) | (0x3Full << 22) | (3ull << 35) | (0xFull << 39);   // host_call's and these
+struct Admitted { Ctx &c; size_t held; ~Admitted() { scratch_release(c, held, CALL_SLOTS); } };
+struct HostBlock { uint8_t *p = nullptr; ~HostBlock() { if (p) result_free(p); } uint8_t *release() { uint8_t *r = p; p = nullptr; return r; } };
+// host buffers up to this size run the chain of single host calls (RSN_LAYERS_CHAIN_MAX: the A/B of scripts/layers_bench.py)
+size_t layers_chain_max() {
+    static const size_t v = getenv("RSN_LAYERS_CHAIN_MAX") ? (size_t)atoll(getenv("RSN_LAYERS_CHAIN_MAX")) : (size_t)65536;
+    return v;
+}
+const char *layer_name(int id) { return id == RSN_LAYER_LZSS ? "lzss" : "huffman"; }
+int layers_check(Ctx &c, const int *layers, size_t n_layers) {
+    if (n_layers > RSN_LAYERS_MAX) return c.fail(RSN_ERR_ARG, "%zu layers: at most %d in one call", n_layers, RSN_LAYERS_MAX);
+    if (n_layers && !layers) return c.fail(RSN_ERR_ARG, "null layer list");
+    for (size_t k = 0; k < n_layers; k++)
+        if (layers[k] != RSN_LAYER_LZSS && layers[k] != RSN_LAYER_HUFFMAN) return c.fail(RSN_ERR_ARG, "layer %zu: unknown layer id %d", k, layers[k]);
+    return RSN_OK;
+}
+int layer_fail(Ctx &c, int rc, size_t k, int id) { const std::string m = c.err; return c.fail(rc, "layer %zu (%s): %s", k, layer_name(id), m.c_str()); }
+// what host_call gives the single calls: the output buffer's first size, and the codec's own scratch
+size_t layer_cap(bool enc, int id, size_t n) {
+    if (id == RSN_LAYER_LZSS) return enc ? lzss_compress_bound(n) : 8 * n + (1 << 16);
+    return enc ? n + n / 8 + (1 << 16) : 4 * n + (1 << 16);
+}
+size_t layer_scratch(bool enc, int id, size_t n) {
+    if (id == RSN_LAYER_LZSS) return n < ((size_t)32 << 20) ? 0 : (enc ? 13 * std::min(n, (size_t)3 << 29) + 2 * n : 8 * n);
+    return enc ? n / 32 : n / 8;
+}
+// the SUM of what is live at once, over the chain's steps: a step's input, its output buffer (dev_buf rounds up by an eighth) and its
+// codec's scratch.  A step's input is not known before the step before it has run: compress takes its bound, decompress twice its input.
+size_t layers_need(bool enc, const int *layers, size_t n_layers, size_t n) {
+    size_t live = 0, cur = n;
+    for (size_t k = 0; k < n_layers; k++) {
+        const int id = layers[enc ? k : n_layers - 1 - k];
+        const size_t cap = layer_cap(enc, id, cur);
+        live = std::max(live, round_up(cur, 16) + 64 + cap + cap / 8 + layer_scratch(enc, id, cur));
+        cur = enc ? cap : std::min(cap, 2 * cur);
+    }
+    return live;
+}
+int layer_dev(Ctx &c, hipStream_t s, bool enc, int id, const uint8_t *di, size_t n, uint8_t *dout, size_t cap, size_t *got) {
+    if (id == RSN_LAYER_LZSS) return enc ? lzss_encode_dev(c, s, di, n, RSN_LZSS_DEFAULT_WINDOW, dout, cap, got) : lzss_decode_dev(c, s, di, n, dout, cap, got);
+    return enc ? huff_encode_dev(c, s, di, n, dout, cap, got, nullptr, nullptr) : huff_decode_dev(c, s, di, n, dout, cap, got);
+}
+}  // namespace
+
+static int layer_host(bool enc, int id, const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
+    if (id == RSN_LAYER_LZSS) return enc ? rsn_lzss_compress_impl(in, n, RSN_LZSS_DEFAULT_WINDOW, out, out_n) : rsn_lzss_decompress_impl(in, n, out, out_n);
+    return enc ? rsn_huffman_compress_impl(in, n, out, out_n) : rsn_huffman_decompress_impl(in, n, out, out_n);
+}
+
+// the chain of single host calls: one layer (the call IS the single call), and host buffers below the cutoff
+static int layers_host_chain(Ctx &c, bool enc, const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n) {
+    HostBlock held;
+    const uint8_t *cur = in; size_t cur_n = n;
+    for (size_t k = 0; k < n_layers; k++) {
+        const size_t li = enc ? k : n_layers - 1 - k;
+        HostBlock next; size_t next_n = 0;
+        const int rc = layer_host(enc, layers[li], cur, cur_n, &next.p, &next_n);
+        if (rc) return layer_fail(c, rc, li, layers[li]);
+        if (held.p) result_free(held.p);
+        held.p = next.release(); cur = held.p; cur_n = next_n;
+    }
+    *out = held.release(); *out_n = cur_n;
+    return RSN_OK;
+}
+
+static int upload_input(Ctx &c, hipStream_t s, const uint8_t *in, size_t n, uint8_t **d_in) {
+    void *p;
+    int rc = dev_buf(c, L_IN, round_up(n, 16) + 64, &p); if (rc) return rc;
+    RSN_HIP(hipMemsetAsync((uint8_t *)p + (n & ~(size_t)15), 0, 64, s));
+    PinGuard g;                                                           // (another call may have these bytes registered: not released under this copy)
+    pin_acquire(in, n, false, g.h);
+    RSN_HIP(copy_up(p, in, n, s, g.h));
+    if (n && !g.h.held.empty()) RSN_HIP(hipStreamSynchronize(s));
+    *d_in = (uint8_t *)p;
+    return RSN_OK;
+}
+
+// The layers over a stream that is on the device: step k reads what step k - 1 wrote, the slots L_A / L_B taking turns from `slot` on.
+// The last step writes to `last_out` (the caller's buffer, no retry: RSN_ERR_CAPACITY and the need in *res_n) when there is one, else
+// into a slot too.  Every codec synchronises `s` before it returns.  *res / *res_n: where the result is, and its size.
+static int run_chain(Ctx &c, hipStream_t s, bool enc, const int *layers, size_t n_layers, const uint8_t *d_src, size_t n, int slot,
+                     uint8_t *last_out, size_t last_cap, const uint8_t **res, size_t *res_n) {
+    const uint8_t *cur = d_src; size_t cur_n = n;
+    *res_n = 0;
+    for (size_t k = 0; k < n_layers; k++) {
+        const size_t li = enc ? k : n_layers - 1 - k;
+        const int id = layers[li];
+        const bool to_caller = last_out && k + 1 == n_layers;
+        size_t cap = to_caller ? last_cap : layer_cap(enc, id, cur_n), got = 0;
+        uint8_t *dst = last_out;
+        int rc;
+        for (int attempt = 0;; attempt++) {
+            if (!to_caller) { void *p; rc = dev_buf(c, slot, cap + 80, &p); if (rc) return rc; dst = (uint8_t *)p; }
+            rc = layer_dev(c, s, enc, id, cur, cur_n, dst, cap, &got);
+            if (rc == RSN_ERR_CAPACITY && !to_caller && attempt == 0 && got > cap) { cap = got; continue; }   // (both decoders: the size is known after a pass)
+            break;
+        }
+        if (rc) { if (rc == RSN_ERR_CAPACITY) *res_n = got; return layer_fail(c, rc, li, id); }
+        if (!to_caller) RSN_HIP(hipMemsetAsync(dst + got, 0, round_up(got, 16) + 64 - got, s));   // zero behind the stream, as behind an uploaded input
+        cur = dst; cur_n = got;
+        slot = slot == L_A ? L_B : L_A;
+    }
+    *res = cur; *res_n = cur_n;
+    return RSN_OK;
+}
+
+static int layers_host(bool enc, const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n) {
+    Ctx &c = ctx();
+    if (!out || !out_n || (!in && n)) return c.fail(RSN_ERR_ARG, "null argument");
+    *out = nullptr; *out_n = 0;
+    int rc = layers_check(c, layers, n_layers); if (rc) return rc;
+    rc = ctx_init(c); if (rc) return rc;
+    if (n_layers == 0) {                                                  // the reference's loops do nothing: the input
+        uint8_t *r = (uint8_t *)result_alloc(n);
+        if (!r) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", n);
+        if (n) memcpy(r, in, n);
+        *out = r; *out_n = n;
+        return RSN_OK;
+    }
+    if (n_layers == 1 || n <= layers_chain_max()) return layers_host_chain(c, enc, in, n, layers, n_layers, out, out_n);
+    hipStream_t s = c.own_stream;
+    const size_t need = round_up(n, 16) + 64 + layers_need(enc, layers, n_layers, n);
+    Admitted gate{c, need >= ((size_t)64 << 20) ? scratch_admit(c, need) : 0};
+    uint8_t *d_in;
+    rc = upload_input(c, s, in, n, &d_in); if (rc) return rc;
+    const uint8_t *d_res; size_t got = 0;
+    rc = run_chain(c, s, enc, layers, n_layers, d_in, n, L_A, nullptr, 0, &d_res, &got); if (rc) return rc;
+    HostBlock r;
+    r.p = (uint8_t *)result_alloc(got);
+    if (!r.p) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", got);
+    if (got) {
+        RSN_HIP(copy_async(r.p, d_res, got, hipMemcpyDeviceToHost, s));
+        RSN_HIP(hipStreamSynchronize(s));
+    }
+    *out = r.release(); *out_n = got;
+    return RSN_OK;
+}
+
+static int layers_dev(bool enc, const void *d_in, size_t n, const int *layers, size_t n_layers, void *d_out, size_t out_cap, size_t *out_n, void *stream) {
+    Ctx &c = ctx(); hipStream_t s;
+    if ((!d_in && n) || !out_n) return c.fail(RSN_ERR_ARG, "null argument");
+    *out_n = 0;
+    int rc = layers_check(c, layers, n_layers); if (rc) return rc;
+    if (((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 15)) return c.fail(RSN_ERR_ARG, "layers: device buffers must be 16-byte aligned");
+    if (!d_out) out_cap = 0;
+    if (ranges_overlap(d_in, n, d_out, out_cap)) return c.fail(RSN_ERR_ARG, "input and output ranges overlap");
+    rc = dev_prologue(c, stream, &s); if (rc) return rc;
+    if (n_layers == 0) {
+        if (out_cap < n) { *out_n = round_up(n, 16) + 16; return c.fail(RSN_ERR_CAPACITY, "layers: output needs %zu bytes, buffer holds %zu", n, out_cap); }
+        if (n) RSN_HIP(copy_async(d_out, d_in, n, hipMemcpyDeviceToDevice, s));
+        RSN_HIP(hipStreamSynchronize(s));
+        *out_n = n;
+        return RSN_OK;
+    }
+    if (n_layers == 1 && (out_cap || !enc)) {                            // the single call, its own size query included (the decoders answer it)
+        const int id = layers[0];
+        if (id == RSN_LAYER_LZSS) rc = enc ? rsn_lzss_compress_dev_impl(d_in, n, RSN_LZSS_DEFAULT_WINDOW, d_out, out_cap, out_n, stream) : rsn_lzss_decompress_dev_impl(d_in, n, d_out, out_cap, out_n, stream);
+        else rc = enc ? rsn_huffman_compress_dev_impl(d_in, n, d_out, out_cap, out_n, stream) : rsn_huffman_decompress_dev_impl(d_in, n, d_out, out_cap, out_n, stream);
+        return rc ? layer_fail(c, rc, 0, id) : RSN_OK;
+    }
+    const size_t need = layers_need(enc, layers, n_layers, n);
+    Admitted gate{c, need >= ((size_t)64 << 20) ? scratch_admit(c, need) : 0};
+    const uint8_t *d_res; size_t got = 0;
+    rc = run_chain(c, s, enc, layers, n_layers, (const uint8_t *)d_in, n, L_A, out_cap ? (uint8_t *)d_out : nullptr, out_cap, &d_res, &got);
+    if (rc) { if (rc == RSN_ERR_CAPACITY) *out_n = got; return rc; }
+    if (!out_cap) {                                                       // the size query: the chain has run, its last layer into scratch
+        *out_n = round_up(got, 16) + 32;                                  // (what every last layer takes: the Huffman encoder asks for its size rounded up to 16, plus 32)
+        return c.fail(RSN_ERR_CAPACITY, "layers: output needs %zu bytes", got);
+    }
+    *out_n = got;
+    return RSN_OK;
+}
+
+static int layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size_t n_layers, rsn_roundtrip_result *res, uint8_t **compressed, size_t *compressed_n) {
+    Ctx &c = ctx();
+    if (!res || (!in && n) || (compressed && !compressed_n)) return c.fail(RSN_ERR_ARG, "null argument");
+    memset(res, 0, sizeof *res);
+    if (compressed) { *compressed = nullptr; *compressed_n = 0; }
+    int rc = layers_check(c, layers, n_layers); if (rc) return rc;
+    rc = ctx_init(c); if (rc) return rc;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    rsn_roundtrip_result r;
+    memset(&r, 0, sizeof r);
+    r.original_n = n;
+    HostBlock comp;
+    const auto t0 = now();
+    if (n <= layers_chain_max()) {                                        // a call of this size is its launches: the single host calls, and the host counts
+        size_t cn = 0, dn = 0;
+        HostBlock dec;
+        rc = layers_host(true, in, n, layers, n_layers, &comp.p, &cn); if (rc) return rc;
+        const auto t1 = now();
+        rc = layers_host(false, comp.p, cn, layers, n_layers, &dec.p, &dn); if (rc) return rc;
+        for (size_t i = 0; i < n; i++) r.hist_original[in[i]]++;
+        for (size_t i = 0; i < dn; i++) r.hist_decompressed[dec.p[i]]++;
+        const size_t m = std::min(n, dn);
+        size_t at = 0;
+        while (at < m && in[at] == dec.p[at]) at++;
+        r.first_difference = at == m && n == dn ? UINT64_MAX : at;
+        r.compressed_n = cn; r.decompressed_n = dn;
+        r.compress_ms = ms(t0, t1); r.decompress_ms = ms(t1, now());
+    } else {
+        hipStream_t s = c.own_stream;
+        const size_t need = round_up(n, 16) + 64 + layers_need(true, layers, n_layers, n) + 2 * n;
+        Admitted gate{c, need >= ((size_t)64 << 20) ? scratch_admit(c, need) : 0};
+        uint8_t *d_in;
+        rc = upload_input(c, s, in, n, &d_in); if (rc) return rc;
+        const uint8_t *d_c; size_t cn = 0;
+        rc = run_chain(c, s, true, layers, n_layers, d_in, n, L_A, nullptr, 0, &d_c, &cn); if (rc) return rc;
+        if (compressed) {
+            comp.p = (uint8_t *)result_alloc(cn);
+            if (!comp.p) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", cn);
+            if (cn) { RSN_HIP(copy_async(comp.p, d_c, cn, hipMemcpyDeviceToHost, s)); RSN_HIP(hipStreamSynchronize(s)); }
+        }
+        const auto t1 = now();
+        const uint8_t *d_d; size_t dn = 0;
+        rc = run_chain(c, s, false, layers, n_layers, d_c, cn, d_c == (const uint8_t *)c.bufs[L_A].p ? L_B : L_A, nullptr, 0, &d_d, &dn); if (rc) return rc;
+        void *p, *hp;
+        rc = dev_buf(c, L_STAT, 513 * 8 + 64, &p); if (rc) return rc;
+        unsigned long long *d_stat = (unsigned long long *)p;
+        rc = byte_hist256_dev(c, s, d_in, n, d_stat); if (rc) return rc;
+        rc = byte_hist256_dev(c, s, d_d, dn, d_stat + 256); if (rc) return rc;
+        rc = bytes_differ_dev(c, s, d_in, d_d, std::min(n, dn), d_stat + 512); if (rc) return rc;
+        rc = pinned_buf(c, 513 * 8, &hp); if (rc) return rc;
+        RSN_HIP(copy_async(hp, d_stat, 513 * 8, hipMemcpyDeviceToHost, s));
+        RSN_HIP(hipStreamSynchronize(s));
+        const unsigned long long *h = (const unsigned long long *)hp;
+        for (int b = 0; b < 256; b++) { r.hist_original[b] = h[b]; r.hist_decompressed[b] = h[256 + b]; }
+        r.first_difference = h[512] != ~0ull ? h[512] : (n == dn ? UINT64_MAX : (uint64_t)std::min(n, dn));
+        r.compressed_n = cn; r.decompressed_n = dn;
+        r.compress_ms = ms(t0, t1); r.decompress_ms = ms(t1, now());
+    }
+    r.lossless = r.first_difference == UINT64_MAX;
+    *res = r;
+    if (compressed) { *compressed = comp.release(); *compressed_n = (size_t)r.compressed_n; }
+    return RSN_OK;
+}
+
+static void rsn_prof_enable_impl(int on) { ctx().prof = on != 0; g_copy_count.on.store(on != 0); }
+static void rsn_prof_copied_impl(uint64_t *h2d_bytes, uint64_t *d2h_bytes) {
+    if (h2d_bytes) *h2d_bytes = g_copy_count.h2d.load();
+    if (d2h_bytes) *d2h_bytes = g_copy_count.d2h.load();
+}
 static void rsn_prof_reset_impl(void) {
     Ctx &c = ctx();
+    g_copy_count.h2d.store(0); g_copy_count.d2h.store(0);
     prof_collect(c);
     for (auto &s : c.slots) { s.launches = 0; s.total_ms = 0; }
 }
@@ -1508,6 +1757,23 @@ int rsn_lzss_decompress_batch(size_t n, const uint8_t *const *ins, const size_t 
 int rsn_huffman_compress_sharded(const uint8_t *in, size_t n, int shards, uint8_t **out, size_t *out_n) {
     return guarded_call<int>([&] { return rsn_huffman_compress_sharded_impl(in, n, shards, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
 }
+int rsn_layers_compress(const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n) {
+    return guarded_call<int>([&] { return layers_host(true, in, n, layers, n_layers, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
+}
+int rsn_layers_decompress(const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n) {
+    return guarded_call<int>([&] { return layers_host(false, in, n, layers, n_layers, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
+}
+int rsn_layers_compress_dev(const void *d_in, size_t n, const int *layers, size_t n_layers, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded_call<int>([&] { return layers_dev(true, d_in, n, layers, n_layers, d_out, out_cap, out_n, stream); }, boundary_error); }
+int rsn_layers_decompress_dev(const void *d_in, size_t n, const int *layers, size_t n_layers, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded_call<int>([&] { return layers_dev(false, d_in, n, layers, n_layers, d_out, out_cap, out_n, stream); }, boundary_error); }
+int rsn_layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size_t n_layers, rsn_roundtrip_result *res, uint8_t **compressed, size_t *compressed_n) {
+    return guarded_call<int>([&] { return layers_roundtrip(in, n, layers, n_layers, res, compressed, compressed_n); }, [&](int code, const char *m) {
+        if (res) memset(res, 0, sizeof *res);
+        if (compressed && *compressed) { result_free(*compressed); *compressed = nullptr; }
+        if (compressed_n) *compressed_n = 0;
+        return boundary_error(code, m);
+    });
+}
+void rsn_prof_copied(uint64_t *h2d_bytes, uint64_t *d2h_bytes) { guarded_call<int>([&] { rsn_prof_copied_impl(h2d_bytes, d2h_bytes); return 0; }, boundary_error); }
 void rsn_prof_enable(int on) { guarded_call<int>([&] { rsn_prof_enable_impl(on); return 0; }, boundary_error); }
 void rsn_prof_reset(void) { guarded_call<int>([&] { rsn_prof_reset_impl(); return 0; }, boundary_error); }
 int rsn_prof_get(rsn_prof_entry *entries, int cap) { return guarded_call<int>([&] { return rsn_prof_get_impl(entries, cap); }, boundary_error); }

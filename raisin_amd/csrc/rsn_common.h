@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <atomic>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -38,7 +39,7 @@ struct Ctx {
     std::vector<hipEvent_t> free_events;
 
     struct Buf { void *p = nullptr; size_t cap = 0; unsigned long long gen = 0; };   // gen: process-unique number of this allocation (dev_buf) -- an address can come back with other contents
-    enum { N_BUFS = 39 };   // 28..33: the batch pipeline's ring; 34: the one-pass Huffman decoder's tile words; 35: k_esc_try's block flags; 36: an LZSS section's stream (encoder: the aligned copy; decoder: the escaped bytes in front + the section's tokens); 37, 38: the small-input Huffman path's device copy / its decoder's block maps
+    enum { N_BUFS = 43 };   // 39..42: the layered calls' input, the stream's two turns, the round trip's counts (rsn_api.hip); 28..33: the batch pipeline's ring; 34: the one-pass Huffman decoder's tile words; 35: k_esc_try's block flags; 36: an LZSS section's stream (encoder: the aligned copy; decoder: the escaped bytes in front + the section's tokens); 37, 38: the small-input Huffman path's device copy / its decoder's block maps
     Buf bufs[N_BUFS];
     void *pinned = nullptr; size_t pinned_cap = 0;
     bool lz_runs = false;           // the LZSS input in hand holds runs of a byte (k_esc_try's flag): lzss_encode_stream walks it with k_match_chain<RUNS>
@@ -101,6 +102,18 @@ inline int persistent_grid(Ctx &c, const void *fn, int block, size_t work, dim3 
     }
     *grid = dim3((uint32_t)std::min<size_t>(work, blocks));
     return RSN_OK;
+}
+
+// Every copy command between host and device goes through here: rsn_prof_copied's process-wide byte counts (rsn.h), kept while
+// profiling is on.  Device-to-device copies are not counted.
+struct CopyCount { std::atomic<int> on{0}; std::atomic<unsigned long long> h2d{0}, d2h{0}; };
+inline CopyCount g_copy_count;
+inline hipError_t copy_async(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    if (g_copy_count.on.load(std::memory_order_relaxed)) {
+        if (kind == hipMemcpyHostToDevice) g_copy_count.h2d.fetch_add(bytes, std::memory_order_relaxed);
+        else if (kind == hipMemcpyDeviceToHost) g_copy_count.d2h.fetch_add(bytes, std::memory_order_relaxed);
+    }
+    return hipMemcpyAsync(dst, src, bytes, kind, s);
 }
 
 // Brackets a kernel launch with events when profiling is on.

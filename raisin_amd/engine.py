@@ -8,7 +8,7 @@ import os
 import time
 from dataclasses import dataclass
 
-from . import huffman, lz
+from . import huffman, layers as _layers, lz
 
 # engine.go:32 lists 11 engines; the MI355X build carries the two this path names
 # (the others -- arithmetic, dmc, mcc, stdlib bindings -- are out of scope).
@@ -52,8 +52,19 @@ class CompressedFile:
         return chunk, eof
 
 
+def _on_device(algorithms):
+    """every layer is one the layered calls carry (rsn_layers_*: the stream stays on the device between the layers)"""
+    return all(a in _layers.IDS for a in algorithms)
+
+
 def compress(content, algorithms):
-    """engine.go:443-452: layers applied in order."""
+    """engine.go:443-452: layers applied in order.  Two or more layers of lzss / huffman go through the layered call, in runs of at
+    most RSN_LAYERS_MAX."""
+    algorithms = list(algorithms)
+    if len(algorithms) >= 2 and _on_device(algorithms):
+        for i in range(0, len(algorithms), _layers.LAYERS_MAX):
+            content = _layers.Compress(content, algorithms[i:i + _layers.LAYERS_MAX])
+        return content
     for algorithm in algorithms:
         f = CompressedFile(MaxSearchBufferLength=4096)
         f.CompressionEngine = algorithm
@@ -63,7 +74,14 @@ def compress(content, algorithms):
 
 
 def decompress(content, algorithms):
-    """engine.go:454-479: layers undone in reverse order, read through a 512-byte buffer."""
+    """engine.go:454-479: layers undone in reverse order, read through a 512-byte buffer (the layered call for two or more layers of
+    lzss / huffman, the runs of compress() last to first)."""
+    algorithms = list(algorithms)
+    if len(algorithms) >= 2 and _on_device(algorithms):
+        runs = [algorithms[i:i + _layers.LAYERS_MAX] for i in range(0, len(algorithms), _layers.LAYERS_MAX)]
+        for run in reversed(runs):
+            content = _layers.Decompress(content, run)
+        return content
     for algorithm in reversed(algorithms):
         f = CompressedFile(CompressionEngine=algorithm, Compressed=content)
         while True:
@@ -316,21 +334,32 @@ def BenchmarkFile(algorithms, fileString, PrintStats=False):
     compressed length."""
     data = open(fileString, "rb").read()
     name = ",".join(algorithms)
-    entropy = _entropy(_byte_counts(data), len(data)) if data else 0.0
-    start = time.perf_counter()
-    compressed = compress(data, algorithms)
-    decompressed = decompress(compressed, algorithms)
-    dur = time.perf_counter() - start
-    lossless = decompressed == data
-    ratio = len(compressed) / len(data) * 100 if data else float("nan")
-    actual = _entropy(_byte_counts(decompressed), len(compressed)) if compressed else 0.0
+    algorithms = list(algorithms)
+    if 1 <= len(algorithms) <= _layers.LAYERS_MAX and _on_device(algorithms):
+        # one call: upload once, both directions, the comparison and both byte counts on the device; the entropies from the 256 counts here
+        start = time.perf_counter()
+        rt, _ = _layers.RoundTrip(data, algorithms)
+        dur = time.perf_counter() - start
+        n_compressed, n_decompressed, lossless = int(rt.compressed_n), int(rt.decompressed_n), bool(rt.lossless)
+        entropy = _entropy(list(rt.hist_original), len(data)) if data else 0.0
+        actual = _entropy(list(rt.hist_decompressed), n_compressed) if n_compressed else 0.0
+    else:
+        entropy = _entropy(_byte_counts(data), len(data)) if data else 0.0
+        start = time.perf_counter()
+        compressed = compress(data, algorithms)
+        decompressed = decompress(compressed, algorithms)
+        dur = time.perf_counter() - start
+        lossless = decompressed == data
+        n_compressed, n_decompressed = len(compressed), len(decompressed)
+        actual = _entropy(_byte_counts(decompressed), n_compressed) if compressed else 0.0
+    ratio = n_compressed / len(data) * 100 if data else float("nan")
     res = Result(name, _time_taken(dur), ratio, actual, entropy, lossless, False)
     if PrintStats:
         print("Lossless: %s" % str(lossless).lower())
         print("Original bytes: %d" % len(data))
-        print("Compressed bytes: %d" % len(compressed))
+        print("Compressed bytes: %d" % n_compressed)
         if not lossless:
-            print("Decompressed bytes: %d" % len(decompressed))
+            print("Decompressed bytes: %d" % n_decompressed)
         print("Compression ratio: %.2f%%" % ratio)
         print("Time taken: %s" % res.TimeTaken)
     return res

@@ -101,37 +101,44 @@ static Bytes take(Call call) {
 }
 
 namespace engine {
-// engine.go:101-111 Writers / :48-58 Readers, restricted to the engines on this path
-using Codec = std::function<Bytes(const Bytes &)>;
-static const std::map<std::string, Codec> Writers = {
-    {"lzss", [](const Bytes &in) { return take([&](uint8_t **o, size_t *n) { return rsn_lzss_compress(in.data(), in.size(), RSN_LZSS_DEFAULT_WINDOW, o, n); }); }},
-    {"huffman", [](const Bytes &in) { return take([&](uint8_t **o, size_t *n) { return rsn_huffman_compress(in.data(), in.size(), o, n); }); }},
-};
-static const std::map<std::string, Codec> Readers = {
-    {"lzss", [](const Bytes &in) { return take([&](uint8_t **o, size_t *n) { return rsn_lzss_decompress(in.data(), in.size(), o, n); }); }},
-    {"huffman", [](const Bytes &in) { return take([&](uint8_t **o, size_t *n) { return rsn_huffman_decompress(in.data(), in.size(), o, n); }); }},
-};
-static const Codec &lookup(const std::map<std::string, Codec> &m, const std::string &name) {
-    auto it = m.find(name);
-    if (it == m.end()) throw std::runtime_error("unknown compression engine '" + name + "' (this build carries: lzss, huffman)");
-    return it->second;
+// engine.go:101-111 Writers / :48-58 Readers, restricted to the engines on this path: the layer ids of rsn_layers_* (rsn.h)
+static std::vector<int> layer_ids(const std::vector<std::string> &algorithms) {
+    std::vector<int> ids;
+    for (auto &name : algorithms) {
+        if (name == "lzss") ids.push_back(RSN_LAYER_LZSS);
+        else if (name == "huffman") ids.push_back(RSN_LAYER_HUFFMAN);
+        else throw std::runtime_error("unknown compression engine '" + name + "' (this build carries: lzss, huffman)");
+    }
+    return ids;
 }
-// engine.go:443-452
+// engine.go:443-452: the layers in order, through the layered call -- the stream stays on the device between them -- in runs of at
+// most RSN_LAYERS_MAX
 static Bytes compress(Bytes content, const std::vector<std::string> &algorithms) {
-    for (auto &a : algorithms) content = lookup(Writers, a)(content);
+    const std::vector<int> ids = layer_ids(algorithms);
+    for (size_t i = 0; i < ids.size(); i += RSN_LAYERS_MAX) {
+        const size_t k = std::min<size_t>(RSN_LAYERS_MAX, ids.size() - i);
+        content = take([&](uint8_t **o, size_t *n) { return rsn_layers_compress(content.data(), content.size(), ids.data() + i, k, o, n); });
+    }
     return content;
 }
-// engine.go:454-479 (reverse order)
+// engine.go:454-479 (reverse order: the runs last to first, each undone last to first by the call)
 static Bytes decompress(Bytes content, const std::vector<std::string> &algorithms) {
-    for (size_t i = algorithms.size(); i-- > 0;) content = lookup(Readers, algorithms[i])(content);
+    const std::vector<int> ids = layer_ids(algorithms);
+    for (size_t r = (ids.size() + RSN_LAYERS_MAX - 1) / RSN_LAYERS_MAX; r-- > 0;) {
+        const size_t i = r * RSN_LAYERS_MAX, k = std::min<size_t>(RSN_LAYERS_MAX, ids.size() - i);
+        content = take([&](uint8_t **o, size_t *n) { return rsn_layers_decompress(content.data(), content.size(), ids.data() + i, k, o, n); });
+    }
     return content;
 }
-static double entropy(const Bytes &sym, size_t total) {   // goent Entropy(p, math.Log), engine.go:410,423
-    size_t cnt[256] = {0};
-    for (uint8_t c : sym) cnt[c]++;
+static double entropy(const uint64_t *cnt, size_t total) {   // goent Entropy(p, math.Log), engine.go:410,423
     double h = 0;
-    for (size_t c : cnt) if (c) { const double p = (double)c / (double)total; h -= p * std::log(p); }
+    for (int b = 0; b < 256; b++) if (cnt[b]) { const double p = (double)cnt[b] / (double)total; h -= p * std::log(p); }
     return h;
+}
+static double entropy(const Bytes &sym, size_t total) {
+    uint64_t cnt[256] = {0};
+    for (uint8_t c : sym) cnt[c]++;
+    return entropy(cnt, total);
 }
 struct Result { std::string engine, timeTaken; float ratio; float actualEntropy; double entropy; bool lossless, failed; };
 // engine.go:357-441
@@ -139,6 +146,16 @@ static Result BenchmarkFile(const std::vector<std::string> &algorithms, const st
     std::string name;
     for (size_t i = 0; i < algorithms.size(); i++) name += (i ? "," : "") + algorithms[i];
     const Bytes data = read_file(path);
+    const std::vector<int> ids = layer_ids(algorithms);
+    if (!ids.empty() && ids.size() <= RSN_LAYERS_MAX) {
+        // one call: upload once, both directions, the comparison and both byte counts on the device (rsn_layers_roundtrip)
+        rsn_roundtrip_result r;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (rsn_layers_roundtrip(data.data(), data.size(), ids.data(), ids.size(), &r, nullptr, nullptr) != RSN_OK) throw std::runtime_error(rsn_last_error());
+        const long long ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        return {name, go_duration_ns(go_round_ns(ns, 10000)), (float)r.compressed_n / (float)data.size() * 100.f,
+                (float)entropy(r.hist_decompressed, (size_t)r.compressed_n), entropy(r.hist_original, data.size()), r.lossless != 0, false};
+    }
     const auto t0 = std::chrono::steady_clock::now();
     const Bytes c = compress(data, algorithms);
     const Bytes d = decompress(c, algorithms);
