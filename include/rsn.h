@@ -134,17 +134,26 @@ RSN_API int rsn_huffman_compress_sharded(const uint8_t *in, size_t n, int shards
  * is a hipStream_t (NULL = the thread's own stream).  The call returns after
  * the result size is known on the host; d_out is complete once `stream` has
  * been synchronised (the calls below synchronise it before returning).
- * d_out must be 16-byte aligned and hold rsn_*_bound() bytes; [d_in, d_in+n)
- * and [d_out, d_out+out_cap) must not overlap (RSN_ERR_ARG).                */
+ * d_in and d_out must both be 16-byte aligned (RSN_ERR_ARG otherwise: the
+ * kernels load and store 16 bytes at a time from both bases); [d_in, d_in+n)
+ * and [d_out, d_out+out_cap) must not overlap (RSN_ERR_ARG).  Only the n bytes
+ * of the input are read as data: the result never depends on what lies before
+ * d_in or behind d_in + n.  A d_out of rsn_*_bound(n) bytes always suffices
+ * for the two compress calls.                                                */
 RSN_API size_t rsn_huffman_compress_bound(size_t n);
 RSN_API size_t rsn_lzss_compress_bound(size_t n);
 RSN_API int rsn_huffman_compress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream);
 /* The decoded size is only known after the header is parsed.  When the buffer is too small -- or
  * d_out is NULL / out_cap 0, the size query -- the call returns RSN_ERR_CAPACITY, sets the error
  * string, and stores in *out_n a capacity that WOULD suffice (the exact size rounded up to 16, plus
- * 16: not the exact size); call again with a buffer of at least that many bytes, the second call
- * returns RSN_OK and the exact size.  rsn_lzss_decompress_dev and the two compress_dev calls follow
- * the same contract.  On RSN_ERR_FORMAT and on RSN_ERR_CAPACITY the contents of d_out are unspecified (the decoders
+ * 16 -- plus 32 from rsn_huffman_compress_dev: not the exact size); call again with a buffer of at least
+ * that many bytes, the second call returns RSN_OK and the exact size.  rsn_lzss_decompress_dev and the two
+ * compress_dev calls follow the same contract, with that one figure apart.  An empty input (n == 0) has nothing
+ * to size: the two LZSS calls return RSN_OK and size 0 for it, the query included (rsn_huffman_compress_dev
+ * returns RSN_ERR_EMPTY, rsn_huffman_decompress_dev RSN_ERR_FORMAT).  How small a buffer may be: rsn_huffman_decompress_dev, rsn_lzss_compress_dev and rsn_lzss_decompress_dev
+ * take out_cap == the exact result size, whatever its remainder mod 16.  rsn_huffman_compress_dev needs the result size rounded
+ * up to 16, plus 32 (its emit kernels clear and fill whole words up to there); with less -- the exact size included -- it returns
+ * RSN_ERR_CAPACITY and stores that figure.  On RSN_ERR_FORMAT and on RSN_ERR_CAPACITY the contents of d_out are unspecified (the decoders
  * write while they validate, and what fits a too-small buffer may have been written before the total is known; nothing
  * is ever written outside [d_out, d_out + out_cap)).  (The Huffman query with d_out NULL is answered from the header's counts alone,
  * without touching the payload: a foreign stream whose payload decodes to more than its header
@@ -176,7 +185,8 @@ RSN_API int rsn_layers_decompress(const uint8_t *in, size_t n, const int *layers
  * RSN_ERR_CAPACITY and stores in *out_n a capacity that would suffice.  The size of a layered result is only known once the chain has
  * run: the query of two or more layers (and of one compress layer) costs the whole chain, its last layer writing into scratch, and a
  * buffer that turns out too small costs the chain up to its last layer; a caller that can bound the result (the compress bounds
- * applied in turn, or the original's size when decompressing) should pass a buffer of that size.                                  */
+ * applied in turn, or the original's size when decompressing) should pass a buffer of that size.  The smallest out_cap that is
+ * taken is the last step's own: the exact size, except behind a last Huffman compress layer (rounded up to 16, plus 32).          */
 RSN_API int rsn_layers_compress_dev(const void *d_in, size_t n, const int *layers, size_t n_layers, void *d_out, size_t out_cap, size_t *out_n, void *stream);
 RSN_API int rsn_layers_decompress_dev(const void *d_in, size_t n, const int *layers, size_t n_layers, void *d_out, size_t out_cap, size_t *out_n, void *stream);
 

@@ -1199,7 +1199,7 @@ int huff_encode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
                              ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4), tree.n_leaves);
     if (tree_out) *tree_out = tree;
     if (codes_out) *codes_out = codes;
-    if (!d_out) return RSN_OK;   // table introspection only
+    if (!d_out && (tree_out || codes_out)) return RSN_OK;   // table introspection only (without either: the size query, answered below)
 
     const unsigned pad = (unsigned)((8 - codes.total_bits % 8) % 8);            // huffman.go:245-249
     hdr.append("\\\n");

@@ -661,7 +661,8 @@ size_t rsn_lzss_compress_bound(size_t n) { return lzss_compress_bound(n); }
 
 static int rsn_huffman_compress_dev_impl(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) {
     Ctx &c = ctx(); hipStream_t s;
-    if (!d_in || !d_out || !out_n) return c.fail(RSN_ERR_ARG, "null argument");
+    if (!d_in || !out_n) return c.fail(RSN_ERR_ARG, "null argument");
+    if (!d_out) out_cap = 0;                                              // the size query (rsn.h): the encoder answers it before it writes a byte
     if (ranges_overlap(d_in, n, d_out, out_cap)) return c.fail(RSN_ERR_ARG, "input and output ranges overlap");
     int rc = dev_prologue(c, stream, &s); if (rc) return rc;
     return huff_encode_dev(c, s, (const uint8_t *)d_in, n, (uint8_t *)d_out, out_cap, out_n, nullptr, nullptr);
@@ -677,7 +678,8 @@ static int rsn_huffman_decompress_dev_impl(const void *d_in, size_t n, void *d_o
 
 static int rsn_lzss_compress_dev_impl(const void *d_in, size_t n, int64_t window, void *d_out, size_t out_cap, size_t *out_n, void *stream) {
     Ctx &c = ctx(); hipStream_t s;
-    if ((!d_in && n) || !d_out || !out_n) return c.fail(RSN_ERR_ARG, "null argument");
+    if ((!d_in && n) || !out_n) return c.fail(RSN_ERR_ARG, "null argument");
+    if (!d_out) out_cap = 0;                                              // the size query (rsn.h): every emit pass runs behind the capacity check
     if (ranges_overlap(d_in, n, d_out, out_cap)) return c.fail(RSN_ERR_ARG, "input and output ranges overlap");
     int rc = dev_prologue(c, stream, &s); if (rc) return rc;
     return lzss_encode_dev(c, s, (const uint8_t *)d_in, n, window, (uint8_t *)d_out, out_cap, out_n);
@@ -1535,7 +1537,7 @@ static int layers_dev(bool enc, const void *d_in, size_t n, const int *layers, s
     const uint8_t *d_res; size_t got = 0;
     rc = run_chain(c, s, enc, layers, n_layers, (const uint8_t *)d_in, n, L_A, out_cap ? (uint8_t *)d_out : nullptr, out_cap, &d_res, &got);
     if (rc) { if (rc == RSN_ERR_CAPACITY) *out_n = got; return rc; }
-    if (!out_cap) {                                                       // the size query: the chain has run, its last layer into scratch
+    if (!out_cap && got) {                                                // the size query: the chain has run, its last layer into scratch (an empty result has nothing to size: RSN_OK, as from the single calls)
         *out_n = round_up(got, 16) + 32;                                  // (what every last layer takes: the Huffman encoder asks for its size rounded up to 16, plus 32)
         return c.fail(RSN_ERR_CAPACITY, "layers: output needs %zu bytes", got);
     }
