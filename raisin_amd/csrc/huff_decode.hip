@@ -1002,7 +1002,7 @@ int huff_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
     if (host_timing) fprintf(stderr, "huffman decode host: first level + child array %.2f ms, second level %.2f ms (%zu entries), bit-reversal %.2f ms\n", ms(t3, t4), ms(t4, t5), lut2.size(), ms(t5, now()));
     static const bool dbg = getenv("RSN_DEBUG") != nullptr;
     if (dbg) fprintf(stderr, "huffman decode tables: K %d, longest code %u, %zu tree nodes, second level %zu entries (%s)\n", K, codes.max_len, child.size() / 2, lut2.size(), lut2.size() <= (size_t)LUT2_LDS ? "LDS" : "L2");
-    rc = dev_buf(c, 5, (lut.size() + child.size() + lut2.size()) * 4 + 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::HD_TABLES, (lut.size() + child.size() + lut2.size()) * 4 + 64, &p); if (rc) return rc;
     uint32_t *d_lut = (uint32_t *)p;
     int32_t *d_child = (int32_t *)(d_lut + lut.size());
     uint32_t *d_lut2 = (uint32_t *)(d_child + child.size());
@@ -1039,9 +1039,9 @@ int huff_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
     a.flat_guess = codes.min_len == codes.max_len;
     a.warm = std::min(std::max(warm_env, 0), ORG - 32);
     const uint32_t n_blk = (uint32_t)ceil_div(a.n_sub, DB);
-    rc = dev_buf(c, 6, (size_t)a.n_sub * 6 + 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::H_RUNES_SUBSEQ, (size_t)a.n_sub * 6 + 64, &p); if (rc) return rc;
     a.exit_rel = (uint16_t *)p; a.entry_rel = a.exit_rel + a.n_sub; a.nbyte = a.entry_rel + a.n_sub;
-    rc = dev_buf(c, 7, ((size_t)n_blk * 2 + 4) * 8 + (size_t)n_blk * 4 + 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::HD_BLOCKS, ((size_t)n_blk * 2 + 4) * 8 + (size_t)n_blk * 4 + 64, &p); if (rc) return rc;
     a.blk_bytes = (unsigned long long *)p;
     unsigned long long *d_blk_off = a.blk_bytes + n_blk;
     unsigned long long *d_total = d_blk_off + n_blk;
@@ -1099,7 +1099,7 @@ int huff_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
         const auto ph_t0 = std::chrono::steady_clock::now();
         auto ph_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ph_t0).count(); };
         const size_t nbk = n_blk;
-        void *pp2; int r2 = dev_buf(c, 34, nbk * (PH_CAND * 8 + 1) + 256, &pp2); if (r2) return r2;
+        void *pp2; int r2 = dev_buf(c, Slot::HD_TILE_WORDS, nbk * (PH_CAND * 8 + 1) + 256, &pp2); if (r2) return r2;
         PhaseArgs ph{};
         ph.blk_map = (uint2 *)pp2;
         uint8_t *d_true = (uint8_t *)(ph.blk_map + PH_CAND * nbk);

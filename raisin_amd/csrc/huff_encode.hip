@@ -502,7 +502,7 @@ int scan_u64(Ctx &c, hipStream_t s, const char *name, const unsigned long long *
         return RSN_OK;
     }
     const uint32_t nb = (uint32_t)ceil_div(n, SCAN_BLK);
-    void *p; int rc = dev_buf(c, 24, (size_t)nb * 8, &p); if (rc) return rc;
+    void *p; int rc = dev_buf(c, Slot::SCAN_PARTIALS, (size_t)nb * 8, &p); if (rc) return rc;
     unsigned long long *part = (unsigned long long *)p;
     RSN_LAUNCH(name, k_scan_local, dim3(nb), dim3(1024), 0, s, in, out, n, part);
     RSN_LAUNCH(name, k_scan_add, dim3(nb), dim3(1024), 0, s, out, n, (const unsigned long long *)part, total);
@@ -971,7 +971,7 @@ __global__ void k_rune_table(const RuneCode *__restrict__ list, uint32_t k, unsi
 int hist_ascii_or_rune(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint32_t n_tiles, uint32_t tile, uint32_t *d_tile_hist,
                        std::vector<HuffSym> &syms, bool &ascii, uint16_t **smask_out) {
     void *p;
-    int rc = dev_buf(c, 1, 256 * 8, &p); if (rc) return rc;
+    int rc = dev_buf(c, Slot::HE_BYTE_HIST, 256 * 8, &p); if (rc) return rc;
     unsigned long long *d_gh = (unsigned long long *)p;
     RSN_HIP(hipMemsetAsync(d_gh, 0, 256 * 8, s));
     dim3 grid;                                                           // persistent blocks (8 loads in flight: within noise, r01d A/B)
@@ -993,17 +993,17 @@ int hist_ascii_or_rune(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uin
         return RSN_OK;
     }
     // rune path: Go UTF-8 semantics (huffman.go:309)
-    rc = dev_buf(c, 2, (size_t)kMaxRune * 8, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::HE_RUNE_HIST, (size_t)kMaxRune * 8, &p); if (rc) return rc;
     unsigned long long *d_rh = (unsigned long long *)p;
     RSN_HIP(hipMemsetAsync(d_rh, 0, (size_t)kMaxRune * 8, s));
     const size_t rounds = ceil_div(n, ROUND);
     uint16_t *d_smask = nullptr;
-    { rc = dev_buf(c, 26, (ceil_div(n, 16) + 2) * 2 + 64, &p); if (rc) return rc; d_smask = (uint16_t *)p; }
+    { rc = dev_buf(c, Slot::RUNES_REDO, (ceil_div(n, 16) + 2) * 2 + 64, &p); if (rc) return rc; d_smask = (uint16_t *)p; }
     *smask_out = d_smask;
     RSN_LAUNCH("huff_rune_hist", k_rune_hist, dim3((uint32_t)std::min<size_t>(rounds, 4096)), dim3(HB), 0, s, d_in, n, d_rh, d_smask);
     // the present runes, compacted in rune order (see k_rune_flags)
     const size_t bound = std::min<size_t>(n, kMaxRune);                // distinct runes never exceed the input's bytes
-    rc = dev_buf(c, 6, (size_t)kMaxRune * 16 + 16 + bound * sizeof(HuffSym) + 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::H_RUNES_SUBSEQ, (size_t)kMaxRune * 16 + 16 + bound * sizeof(HuffSym) + 64, &p); if (rc) return rc;
     unsigned long long *d_flag = (unsigned long long *)p, *d_off = d_flag + kMaxRune, *d_cnt = d_off + kMaxRune;
     HuffSym *d_pairs = (HuffSym *)(d_cnt + 2);
     const dim3 rg((kMaxRune + 255) / 256);
@@ -1043,7 +1043,7 @@ int huff_slice_hist(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, HuffSl
     sl.tile = n <= SMALL_INPUT ? SMALL_TILE : TILE;
     sl.n_tiles = (uint32_t)ceil_div(n, sl.tile);
     void *p;
-    int rc = dev_buf(c, 0, (size_t)sl.n_tiles * 128 * 4, &p); if (rc) return rc;
+    int rc = dev_buf(c, Slot::HE_TILE_HIST, (size_t)sl.n_tiles * 128 * 4, &p); if (rc) return rc;
     sl.d_tile_hist = (uint32_t *)p;
     sl.d_smask = nullptr;                                                 // rune path: which positions start a rune (k_rune_hist's classification, kept)
     rc = hist_ascii_or_rune(c, s, d_in, n, sl.n_tiles, sl.tile, sl.d_tile_hist, sl.syms, sl.ascii, &sl.d_smask); if (rc) return rc;
@@ -1082,7 +1082,7 @@ int huff_slice_emit(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, const 
         for (uint32_t i = 0; i < tree.n_leaves; i++) hcodes[tree.rune[i]] = (uint8_t)codes.code[i];
         memcpy(hcodes + 128, hdr.data(), H);
         if (hcodes != fa.inl) {
-            rc = dev_buf(c, 3, 128 + H + 16, &p); if (rc) return rc;
+            rc = dev_buf(c, Slot::HE_CODES, 128 + H + 16, &p); if (rc) return rc;
             RSN_HIP(copy_async(p, hcodes, 128 + H, hipMemcpyHostToDevice, s));
             fa.codes = (const uint8_t *)p;
         }
@@ -1109,7 +1109,7 @@ int huff_slice_emit(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, const 
         void *hp; rc = pinned_buf(c, (size_t)k * sizeof(RuneCode), &hp); if (rc) return rc;
         RuneCode *hl = (RuneCode *)hp;
         for (uint32_t i = 0; i < k; i++) hl[i] = RuneCode{tree.rune[i], codes.len[i], codes.code[i]};
-        rc = dev_buf(c, 3, (size_t)kMaxRune * 9 + 64 + (size_t)k * sizeof(RuneCode), &p); if (rc) return rc;
+        rc = dev_buf(c, Slot::HE_CODES, (size_t)kMaxRune * 9 + 64 + (size_t)k * sizeof(RuneCode), &p); if (rc) return rc;
         RuneCode *d_list = (RuneCode *)((uint8_t *)p + round_up((size_t)kMaxRune * 9, 64));
         RSN_HIP(copy_async(d_list, hl, (size_t)k * sizeof(RuneCode), hipMemcpyHostToDevice, s));
         a.code64 = (const unsigned long long *)p;
@@ -1126,7 +1126,7 @@ int huff_slice_emit(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, const 
             ht->c64[r] = codes.code[i]; ht->l8[r] = codes.len[i];
             if (codes.max_len <= (unsigned)TAB_LEN_SHIFT) ht->t32[r] = ((uint32_t)codes.len[i] << TAB_LEN_SHIFT) | (uint32_t)codes.code[i];
         }
-        rc = dev_buf(c, 3, sizeof(Tab), &p); if (rc) return rc;
+        rc = dev_buf(c, Slot::HE_CODES, sizeof(Tab), &p); if (rc) return rc;
         RSN_HIP(copy_async(p, ht, sizeof(Tab), hipMemcpyHostToDevice, s));
         Tab *dt = (Tab *)p;
         a.tab32 = dt->t32; a.code64 = dt->c64;
@@ -1135,7 +1135,7 @@ int huff_slice_emit(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, const 
     a.len8 = d_len8;
 
     // ---- tile bit offsets
-    rc = dev_buf(c, 4, ((size_t)n_tiles * 2 + 2) * 8, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::HE_TILE_BITS, ((size_t)n_tiles * 2 + 2) * 8, &p); if (rc) return rc;
     unsigned long long *d_tile_bits = (unsigned long long *)p;
     unsigned long long *d_tile_off = d_tile_bits + n_tiles;
     if (mode == MODE_RUNE) {

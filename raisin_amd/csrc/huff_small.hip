@@ -718,7 +718,7 @@ int huff_small_compress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **out
     hipStream_t s = c.own_stream;
     void *pp; rc = pinned_buf(c, PIN_BYTES, &pp); if (rc) return rc;
     uint8_t *pin = (uint8_t *)pp;
-    void *dp; rc = dev_buf(c, 37, SMALL_MAX + 64, &dp); if (rc) return rc;
+    void *dp; rc = dev_buf(c, Slot::HS_INPUT, SMALL_MAX + 64, &dp); if (rc) return rc;
     memcpy(pin + PIN_IN, in, n);
     memset(pin + PIN_IN + n, 0, 16);
     const uint32_t n_tiles = (uint32_t)ceil_div(n, ST);
@@ -819,13 +819,13 @@ int huff_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **o
     hipStream_t s = c.own_stream;
     void *pp; rc = pinned_buf(c, PIN_BYTES, &pp); if (rc) return rc;
     uint8_t *pin = (uint8_t *)pp;
-    void *dp; rc = dev_buf(c, 38, (DEC_BLOCKS * 32 + DEC_BLOCKS) * 4, &dp); if (rc) return rc;      // the blocks' maps and flags
+    void *dp; rc = dev_buf(c, Slot::HS_DEC_MAPS, (DEC_BLOCKS * 32 + DEC_BLOCKS) * 4, &dp); if (rc) return rc;      // the blocks' maps and flags
     // A flag holds the number of the call that set it: nothing to clear between calls on the same ALLOCATION.  Keyed on the allocation's
     // process-unique number, not its address (rsn_device_set / rsn_trim / the admission gate free the slot, and a later
     // hipMalloc can hand the same address back with other contents -- a stale flag equal to the current number would pass for this call's).
     static thread_local uint32_t seq = 0;
     static thread_local unsigned long long seq_of = 0;
-    if (seq_of != c.bufs[38].gen || ++seq == 0) { seq = 1; seq_of = c.bufs[38].gen; RSN_HIP(hipMemsetAsync(dp, 0, (DEC_BLOCKS * 32 + DEC_BLOCKS) * 4, s)); }
+    if (seq_of != c.buf(Slot::HS_DEC_MAPS).gen || ++seq == 0) { seq = 1; seq_of = c.buf(Slot::HS_DEC_MAPS).gen; RSN_HIP(hipMemsetAsync(dp, 0, (DEC_BLOCKS * 32 + DEC_BLOCKS) * 4, s)); }
     memcpy(pin + PIN_IN, in + A0, n - A0);
     memset(pin + PIN_IN + (n - A0), 0, 64);
     uint32_t *status = (uint32_t *)(pin + PIN_CNT);

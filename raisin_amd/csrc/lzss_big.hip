@@ -135,13 +135,13 @@ __global__ __launch_bounds__(BT) void k_big_emit(const uint8_t *__restrict__ fc,
 
 int lzss_encode_big(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32_t E, uint32_t W, uint8_t *d_out, size_t out_cap, size_t *out_n) {
     void *p; int rc;
-    rc = dev_buf(c, 10, (size_t)E * 8 + 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::LE_KEYS, (size_t)E * 8 + 64, &p); if (rc) return rc;
     unsigned long long *d_keys = (unsigned long long *)p;
-    rc = dev_buf(c, 11, ((size_t)E + 1) * 8 + 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::LE_LISTS_EXITS, ((size_t)E + 1) * 8 + 64, &p); if (rc) return rc;
     uint32_t *d_nxt0 = (uint32_t *)p, *d_nxt1 = d_nxt0 + ((size_t)E + 1);
     const size_t on_words = (size_t)E / 32 + 2;
     const uint32_t n_blk = (uint32_t)ceil_div(E, BT);
-    rc = dev_buf(c, 12, on_words * 4 + ((size_t)n_blk * 2 + 2) * 8 + 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::LE_TILES, on_words * 4 + ((size_t)n_blk * 2 + 2) * 8 + 64, &p); if (rc) return rc;
     unsigned long long *d_bbytes = (unsigned long long *)p, *d_boff = d_bbytes + n_blk, *d_btot = d_boff + n_blk;
     uint32_t *d_on = (uint32_t *)(d_btot + 2);
     uint32_t *d_give_up = (uint32_t *)(d_btot + 1);

@@ -1250,23 +1250,13 @@ __global__ __launch_bounds__(ZB) void k_une_write(const uint8_t *__restrict__ es
 // ======================================================================= host side
 namespace {
 
-// The decoder's large scratch -- 2 bytes of descriptors per escaped byte, the escaped stream itself, the tail maps -- goes through the
-// same admission gate as the encoder's (rsn_api.hip: a goroutine storm of gigabyte calls queues instead of running the device out of
-// memory); released, with the buffers when others wait, on every way out.  Slots 13 .. 16, 19, 22, 23, 25, 27, 36.
-struct DecGate {
-    Ctx &c; size_t held = 0; bool asked = false;
-    explicit DecGate(Ctx &cc) : c(cc) {}
-    void admit(size_t escaped) { if (!asked && escaped >= ((size_t)64 << 20)) { asked = true; held = scratch_admit(c, 4 * escaped); } }   // (0 inside a host-buffer call: covered there)
-    ~DecGate() { scratch_release(c, held, (0xFull << 13) | (1ull << 19) | (3ull << 22) | (1ull << 25) | (1ull << 27) | (1ull << 36)); }
-};
-
 // L4 over an escaped stream of any length: d_esc[0, E) -> d_out.  have_summ: the per-block summaries are in place already (the tile
-// path's emit kernel writes them on its way out).  Scratch slot 16.
+// path's emit kernel writes them on its way out).  Scratch: Slot::LD_UNESCAPE (16).
 int lzss_unescape(Ctx &c, hipStream_t s, const uint8_t *d_esc, size_t E, bool have_summ, uint8_t *d_out, size_t out_cap, size_t *out_n) {
     void *p; int rc;
     if (ceil_div(E, (size_t)ZTILE) > 0xFFFFFF00ull) return c.fail(RSN_ERR_LIMIT, "lzss: decoded stream too large for one call");
     const uint32_t n_ub = (uint32_t)ceil_div(E, (size_t)ZTILE);          // unescape blocks
-    rc = dev_buf(c, 16, ((size_t)n_ub * 2 + 2) * 8 + (size_t)round_up(n_ub, 16) * 2 + 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::LD_UNESCAPE, ((size_t)n_ub * 2 + 2) * 8 + (size_t)round_up(n_ub, 16) * 2 + 64, &p); if (rc) return rc;
     unsigned long long *d_ulen = (unsigned long long *)p, *d_uoff = d_ulen + n_ub, *d_utot = d_uoff + n_ub;
     uint8_t *d_summ = (uint8_t *)(d_utot + 2), *d_inpar = d_summ + round_up(n_ub, 16);   // both 16-byte aligned
     void *hp; rc = pinned_buf(c, 64, &hp); if (rc) return rc;
@@ -1408,7 +1398,7 @@ int lzss_decode_impl(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8
     if (n >= (1ull << 32) - 65536) return c.fail(RSN_ERR_LIMIT, "lzss: compressed input too large for one call");
     void *p; int rc;
     const uint32_t n_cb = (uint32_t)ceil_div(n, ZTILE);
-    rc = dev_buf(c, 13, ((size_t)n_cb * 2 + 5) * 8, &p); if (rc) return rc;   // ... + flags: [0] error, [1] changed, [2] largest back-pointer, [3] tile path gave up
+    rc = dev_buf(c, Slot::LD_BLOCKS, ((size_t)n_cb * 2 + 5) * 8, &p); if (rc) return rc;   // ... + flags: [0] error, [1] changed, [2] largest back-pointer, [3] tile path gave up
     unsigned long long *d_blen = (unsigned long long *)p, *d_boff = d_blen + n_cb, *d_btot = d_boff + n_cb;
     int *d_flag = (int *)(d_btot + 1);
     unsigned long long *d_brk = d_btot + 4;                             // (k_lzd_run_start's word)
@@ -1418,7 +1408,7 @@ int lzss_decode_impl(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8
     volatile int *hflag = (volatile int *)(h64 + 1);
     RSN_HIP(hipMemsetAsync(d_flag, 0, 24, s));                          // ... [4] the stream holds a 5C byte, [5] a span produces 65535 bytes or more
     uint16_t *d_span = nullptr; unsigned long long *d_need = nullptr;
-    rc = dev_buf(c, 27, (size_t)n_cb * ZB * 2 + (size_t)n_cb * 8 + 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::LZ_COUNTS, (size_t)n_cb * ZB * 2 + (size_t)n_cb * 8 + 64, &p); if (rc) return rc;
     d_need = (unsigned long long *)p; d_span = (uint16_t *)(d_need + n_cb);
     RSN_LAUNCH("lzss_dec_count", k_lzd_count2, dim3(n_cb), dim3(ZB), 0, s, d_in, n, d_blen, d_span, d_need, (uint32_t *)(d_flag + 2), d_flag);
     rc = scan_u64(c, s, "lzss_dec_scan", d_blen, d_boff, n_cb, d_btot); if (rc) return rc;
@@ -1442,21 +1432,23 @@ int lzss_decode_impl(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8
         if (rc != 1) return rc;
         *out_n = 0;
     }
-    DecGate gate(c);
-    if (!esc_dst && d_out) gate.admit(E);                               // (a section is admitted by lzss_decode_sections; the size query allocates nothing)
+    // The decoder's large scratch -- 2 bytes of descriptors per escaped byte, the escaped stream itself, the tail maps -- goes through the
+    // same admission gate as the encoder's: four bytes per escaped byte, asked for from 64 MiB of them (inside a host-buffer call: covered there)
+    Admission gate(c, slotset::LZSS_DEC);
+    if (!esc_dst && d_out) gate.admit(4 * E, 4 * ADMIT_FROM);                            // (a section is admitted by lzss_decode_sections; the size query allocates nothing)
     if (!d_out && !esc_dst) {   // the size query: the escaped length is known here, and unescaping only ever shortens it -- a capacity that suffices, one pass over the tokens
         *out_n = round_up((size_t)E, 16) + 16;
         return c.fail(RSN_ERR_CAPACITY, "lzss: output needs at most %u bytes", E);
     }
     const bool plain = hflag[4] == 0 && !esc_dst;          // no 5C anywhere: unescaping is FF -> '<', done by k_lzd_emit on its way out
     uint8_t *d_esc = esc_dst;
-    if (!d_esc) { rc = dev_buf(c, 15, (size_t)E + 64, &p); if (rc) return rc; d_esc = (uint8_t *)p; }
+    if (!d_esc) { rc = dev_buf(c, Slot::LD_ESCAPED, (size_t)E + 64, &p); if (rc) return rc; d_esc = (uint8_t *)p; }
     const uint32_t n_ub = (uint32_t)ceil_div(E, ZTILE);                 // unescape blocks
-    rc = dev_buf(c, 16, ((size_t)n_ub * 2 + 2) * 8 + (size_t)round_up(n_ub, 16) * 2 + 64, &p); if (rc) return rc;
-    uint8_t *d_summ = (uint8_t *)((unsigned long long *)p + (size_t)n_ub * 2 + 2);   // (lzss_unescape's layout of slot 16: k_lzd_emit leaves the block summaries where it looks for them)
+    rc = dev_buf(c, Slot::LD_UNESCAPE, ((size_t)n_ub * 2 + 2) * 8 + (size_t)round_up(n_ub, 16) * 2 + 64, &p); if (rc) return rc;
+    uint8_t *d_summ = (uint8_t *)((unsigned long long *)p + (size_t)n_ub * 2 + 2);   // (lzss_unescape's layout of LD_UNESCAPE: k_lzd_emit leaves the block summaries where it looks for them)
     // ---- L2
     const uint32_t n_tiles = (uint32_t)ceil_div(E, DT), dgrp = group_tiles(n_tiles), n_groups = (uint32_t)ceil_div(n_tiles, dgrp);
-    rc = dev_buf(c, 19, (size_t)n_tiles * 8 + 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::LZ_DUMP_TILES, (size_t)n_tiles * 8 + 64, &p); if (rc) return rc;
     uint2 *d_tinfo = (uint2 *)p;
     uint32_t *d_maxptr = (uint32_t *)(d_flag + 2);
     int *d_fallback = d_flag + 3;
@@ -1478,15 +1470,15 @@ int lzss_decode_impl(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8
     if (tile_path) {
         uint32_t TL = 256;
         while (TL < hmax[0]) TL <<= 1;
-        rc = dev_buf(c, 14, ((size_t)n_tiles * DT + 64) * 2, &p); if (rc) return rc;
+        rc = dev_buf(c, Slot::LD_DESC, ((size_t)n_tiles * DT + 64) * 2, &p); if (rc) return rc;
         uint16_t *d_desc = (uint16_t *)p;
-        rc = dev_buf(c, 22, (size_t)n_groups * TL * 5 + 64, &p); if (rc) return rc;
+        rc = dev_buf(c, Slot::LD_MAPS, (size_t)n_groups * TL * 5 + 64, &p); if (rc) return rc;
         uint16_t *d_comp = (uint16_t *)p, *d_comp2 = d_comp + (size_t)n_groups * TL;   // (two map arrays: the scan below ping-pongs)
         uint8_t *d_gtail = (uint8_t *)(d_comp2 + (size_t)n_groups * TL);
         static const bool no_runs = getenv("RSN_LZSS_DEC_NO_RUNS") != nullptr;   // A/B switch: descriptors for every tile (no run tiles)
         uint32_t *d_rt_cnt = nullptr, *d_rt_runs = nullptr;
         if (!no_runs) {
-            rc = dev_buf(c, 23, (size_t)n_tiles * (RT_RUNS + 1) * 4 + 128, &p); if (rc) return rc;
+            rc = dev_buf(c, Slot::LD_RUNS, (size_t)n_tiles * (RT_RUNS + 1) * 4 + 128, &p); if (rc) return rc;
             d_rt_runs = (uint32_t *)p; d_rt_cnt = d_rt_runs + (size_t)n_tiles * RT_RUNS;
         }
         ResolveArgs ra{d_in, n, d_tinfo, n_tiles, E, TL, d_desc, d_fallback, d_rt_cnt, d_rt_runs};
@@ -1532,7 +1524,7 @@ int lzss_decode_impl(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8
         if (hflag[0] & 2) return c.fail(RSN_ERR_FORMAT, "lzss: back-reference outside the decoded data (reference: slice bounds out of range, lzss.go:350)");
     }
     if (!tile_path) {
-        rc = dev_buf(c, 14, (size_t)E * 4 + 64, &p); if (rc) return rc;
+        rc = dev_buf(c, Slot::LD_DESC, (size_t)E * 4 + 64, &p); if (rc) return rc;
         uint32_t *d_src = (uint32_t *)p;
         RSN_LAUNCH("lzss_dec_expand", k_lzd_expand, dim3(n_cb), dim3(ZB), 0, s, d_in, n, d_boff, d_src, d_esc, d_flag);
         const uint32_t grid = (uint32_t)std::min<size_t>(ceil_div(E, ZB), 8192);
@@ -1547,7 +1539,7 @@ int lzss_decode_impl(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8
         RSN_LAUNCH("lzss_dec_gather", k_lzd_gather, dim3(grid), dim3(ZB), 0, s, d_src, d_esc, E);
     }
     if (esc_dst) { RSN_HIP(hipStreamSynchronize(s)); *out_n = E; return RSN_OK; }
-    // ---- unescape (the tile path's emit kernel has left the block summaries in slot 16, where lzss_unescape expects them)
+    // ---- unescape (the tile path's emit kernel has left the block summaries in LD_UNESCAPE, where lzss_unescape expects them)
     return lzss_unescape(c, s, d_esc, (size_t)E, tile_path, d_out, out_cap, out_n);
 }
 
@@ -1569,11 +1561,11 @@ int lzss_decode_sections(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, u
     std::vector<unsigned long long> boff((size_t)n_cb + 1);
     int hflag[6];
     {   // the counting pass over the whole stream (its per-span outputs are not kept: every section counts its own)
-        rc = dev_buf(c, 13, ((size_t)n_cb * 2 + 4) * 8, &p); if (rc) return rc;
+        rc = dev_buf(c, Slot::LD_BLOCKS, ((size_t)n_cb * 2 + 4) * 8, &p); if (rc) return rc;
         unsigned long long *d_blen = (unsigned long long *)p, *d_boff = d_blen + n_cb, *d_btot = d_boff + n_cb;
         int *d_flag = (int *)(d_btot + 1);
         RSN_HIP(hipMemsetAsync(d_flag, 0, 24, s));
-        rc = dev_buf(c, 27, (size_t)n_cb * ZB * 2 + (size_t)n_cb * 8 + 64, &p); if (rc) return rc;
+        rc = dev_buf(c, Slot::LZ_COUNTS, (size_t)n_cb * ZB * 2 + (size_t)n_cb * 8 + 64, &p); if (rc) return rc;
         unsigned long long *d_need = (unsigned long long *)p; uint16_t *d_span = (uint16_t *)(d_need + n_cb);
         RSN_LAUNCH("lzss_dec_count", k_lzd_count2, dim3(n_cb), dim3(ZB), 0, s, d_in, n, d_blen, d_span, d_need, (uint32_t *)(d_flag + 2), d_flag);
         rc = scan_u64(c, s, "lzss_dec_scan", d_blen, d_boff, n_cb, d_btot); if (rc) return rc;
@@ -1590,9 +1582,9 @@ int lzss_decode_sections(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, u
     if (E == 0) return RSN_OK;
     if (!d_out) { *out_n = round_up(E, 16) + 16; return c.fail(RSN_ERR_CAPACITY, "lzss: output needs at most %zu bytes", E); }
     if (hmax + 16 > SEC && hmax + 16 > ((size_t)1 << 30)) return c.fail(RSN_ERR_LIMIT, "lzss: a stream of 4 GiB and more with back-pointers beyond 1 GiB");
-    DecGate gate(c);
-    gate.admit(E / 4 + std::min(E, SEC + ((size_t)1 << 28)));          // (admit() charges four times its argument: the whole escaped stream + four bytes per escaped byte of a section)
-    rc = dev_buf(c, 15, E + 64, &p); if (rc) return rc;
+    Admission gate(c, slotset::LZSS_DEC);
+    gate.admit(4 * (E / 4 + std::min(E, SEC + ((size_t)1 << 28))), 4 * ADMIT_FROM);   // (the whole escaped stream + four bytes per escaped byte of a section)
+    rc = dev_buf(c, Slot::LD_ESCAPED, E + 64, &p); if (rc) return rc;
     uint8_t *d_esc = (uint8_t *)p;
     // the first item that STARTS at or after compressed position q (a block start): the tokens are known to be well-formed
     auto item_start = [&](size_t q, size_t *out) -> int {
@@ -1630,7 +1622,7 @@ int lzss_decode_sections(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, u
         // the escaped bytes in front: the largest back-pointer's worth, a little more so that the destination is 16-byte aligned
         const size_t W = e0 <= hmax ? e0 : hmax + ((e0 - hmax) & 15);
         const size_t vn = W + (c1 - c0);
-        if (vn + 64 > sec_buf) { sec_buf = vn + 64 + (vn >> 3); rc = dev_buf(c, 36, sec_buf, &p); if (rc) return rc; d_v = (uint8_t *)p; }
+        if (vn + 64 > sec_buf) { sec_buf = vn + 64 + (vn >> 3); rc = dev_buf(c, Slot::LZ_SECTION, sec_buf, &p); if (rc) return rc; d_v = (uint8_t *)p; }
         if (W) RSN_HIP(copy_async(d_v, d_esc + (e0 - W), W, hipMemcpyDeviceToDevice, s));
         if (c1 > c0) RSN_HIP(copy_async(d_v + W, d_in + c0, c1 - c0, hipMemcpyDeviceToDevice, s));
         size_t got = 0;
@@ -1679,7 +1671,7 @@ int lzss_decode_sliced(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uin
     void *p; int rc;
     const uint32_t n_cb = (uint32_t)ceil_div(n, (size_t)ZTILE);
     const size_t SL = std::max<size_t>(st.slice_bytes / ZTILE, 16) * ZTILE;
-    rc = dev_buf(c, 15, out_cap + 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::LD_ESCAPED, out_cap + 64, &p); if (rc) return rc;
     uint8_t *d_esc = (uint8_t *)p;
     void *hp; rc = pinned_buf(c, 256, &hp); if (rc) return rc;
     size_t c0 = 0, e0 = 0, hmax = 0, sec_buf = 0;
@@ -1690,10 +1682,10 @@ int lzss_decode_sliced(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uin
         const size_t q1 = b1 == n_cb ? n : (size_t)b1 * ZTILE, avail = std::min(n, q1 + 64);   // (a token that begins in front of q1 ends before q1 + 24)
         if (!st.need_in(avail)) return c.fail(RSN_ERR_DEVICE, "lzss: the upload of a sliced call failed");
         // ---- the slice's counts: its escaped length, its largest back-pointer, is there a 5C (the decoder below validates the tokens itself)
-        rc = dev_buf(c, 13, ((size_t)n_cb * 2 + 5) * 8, &p); if (rc) return rc;
+        rc = dev_buf(c, Slot::LD_BLOCKS, ((size_t)n_cb * 2 + 5) * 8, &p); if (rc) return rc;
         unsigned long long *d_blen = (unsigned long long *)p, *d_boff = d_blen + n_cb, *d_btot = d_boff + n_cb;
         int *d_flag = (int *)(d_btot + 1);
-        rc = dev_buf(c, 27, (size_t)n_cb * ZB * 2 + (size_t)n_cb * 8 + 64, &p); if (rc) return rc;
+        rc = dev_buf(c, Slot::LZ_COUNTS, (size_t)n_cb * ZB * 2 + (size_t)n_cb * 8 + 64, &p); if (rc) return rc;
         unsigned long long *d_need = (unsigned long long *)p; uint16_t *d_span = (uint16_t *)(d_need + n_cb);
         RSN_HIP(hipMemsetAsync(d_flag, 0, 24, s));
         RSN_LAUNCH("lzss_dec_count", k_lzd_count2, dim3(b1 - b0), dim3(ZB), 0, s, d_in, avail, d_blen, d_span, d_need, (uint32_t *)(d_flag + 2), d_flag, b0);
@@ -1730,7 +1722,7 @@ int lzss_decode_sliced(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uin
         // ---- the slice as a stream of its own: the escaped bytes in front (16-byte aligned destination), then its items
         const size_t W = e0 <= hmax ? e0 : hmax + ((e0 - hmax) & 15);
         const size_t vn = W + (c1 - c0);
-        if (vn + 64 > sec_buf) { sec_buf = vn + 64 + (vn >> 3); rc = dev_buf(c, 36, sec_buf, &p); if (rc) return rc; d_v = (uint8_t *)p; }
+        if (vn + 64 > sec_buf) { sec_buf = vn + 64 + (vn >> 3); rc = dev_buf(c, Slot::LZ_SECTION, sec_buf, &p); if (rc) return rc; d_v = (uint8_t *)p; }
         if (W) RSN_HIP(copy_async(d_v, d_esc + (e0 - W), W, hipMemcpyDeviceToDevice, s));
         if (c1 > c0) RSN_HIP(copy_async(d_v + W, d_in + c0, c1 - c0, hipMemcpyDeviceToDevice, s));
         RSN_HIP(hipMemsetAsync(d_v + vn, 0, 64, s));

@@ -2151,10 +2151,10 @@ static int lzss_encode_stream(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32
     // ---- E2 + E3.  Chain mode (default, W <= 4096): keys only where greedy chains land, everything else
     //      KEY_UNKNOWN; if the parse finds the true chain on an unknown position, those strips are
     //      searched at every position and the parse runs again (never more rounds than strips).
-    rc = dev_buf(c, 10, (size_t)E * 4 + 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::LE_KEYS, (size_t)E * 4 + 64, &p); if (rc) return rc;
     uint32_t *d_keys = (uint32_t *)p;
     const uint32_t n_strips = (uint32_t)ceil_div(E, MATCH_STRIP);
-    rc = dev_buf(c, 18, (size_t)n_strips * 12 + 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::LE_STRIPS, (size_t)n_strips * 12 + 64, &p); if (rc) return rc;
     uint32_t *d_heavy = (uint32_t *)p, *d_redo = d_heavy + n_strips, *d_dense = d_redo + n_strips;
     static const bool allpos = getenv("RSN_LZSS_ALLPOS") != nullptr;                                            // A/B switch: bucket search at every position
     const bool hashed = W <= HWMAX;
@@ -2163,7 +2163,7 @@ static int lzss_encode_stream(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32
     if (!chain_mode) { rc = need_copy(); if (rc) return rc; }
     // E3 buffers (the chain walk fills flags and tile bytes itself when its per-tile chains join up)
     const uint32_t n_pt = (uint32_t)ceil_div(E, PT);
-    rc = dev_buf(c, 12, (size_t)n_pt * 8 + (size_t)n_pt * (PT / 32) * 4 + ((size_t)n_pt * 2 + 4) * 8 + (size_t)n_pt * sizeof(TileChain) + 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::LE_TILES, (size_t)n_pt * 8 + (size_t)n_pt * (PT / 32) * 4 + ((size_t)n_pt * 2 + 4) * 8 + (size_t)n_pt * sizeof(TileChain) + 64, &p); if (rc) return rc;
     unsigned long long *d_tbytes = (unsigned long long *)p, *d_toff = d_tbytes + n_pt, *d_ttot = d_toff + n_pt;   // d_ttot[1..2]: strips to redo / the chain walk's three failure counts
     uint32_t *d_entry = (uint32_t *)(d_ttot + 4);                       // (also k_prev_walked's output: the two are never live together)
     uint32_t *d_flags = d_entry + n_pt;
@@ -2215,9 +2215,9 @@ static int lzss_encode_stream(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32
     const uint32_t redo_cap = n_pt + 64;                              // the list of a second look: every tile can be on it (and room for the sample below)
     const uint32_t gave_cap = std::max(64u, n_pt / 64);               // ... which is worth it while this many tiles at most gave up as dense / heavy: beyond, the bucket search is the tool
     if (chain_mode) {
-        void *dp; rc = dev_buf(c, 19, (size_t)n_pt * CC::DUMP_BYTES + 64, &dp); if (rc) return rc;   // (slot 19 is the decoder's too: never live at the same time)
+        void *dp; rc = dev_buf(c, Slot::LZ_DUMP_TILES, (size_t)n_pt * CC::DUMP_BYTES + 64, &dp); if (rc) return rc;
         d_dump = (uint8_t *)dp;
-        void *rl; rc = dev_buf(c, 26, (size_t)redo_cap * 8 + (size_t)n_pt * 16 + 64, &rl); if (rc) return rc;
+        void *rl; rc = dev_buf(c, Slot::RUNES_REDO, (size_t)redo_cap * 8 + (size_t)n_pt * 16 + 64, &rl); if (rc) return rc;
         d_redo_list = (uint32_t *)rl;
         d_redo_start = d_redo_list + redo_cap;                           // the entry each listed tile is walked from
         d_step = d_redo_start + redo_cap;                                 // per tile: its whole-distance step (k_match_chain), then k_stretch_*'s scratch
@@ -2254,9 +2254,9 @@ static int lzss_encode_stream(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32
         static const bool no_ckeys = getenv("RSN_LZSS_NO_CKEYS") != nullptr, tail_serial = getenv("RSN_LZSS_TAIL_SERIAL") != nullptr;
         uint32_t *d_ckn = nullptr;
         {
-            void *lp; rc = dev_buf(c, 11, std::max((size_t)E * 2, (size_t)n_pt * PT * 4) + 64, &lp); if (rc) return rc;
+            void *lp; rc = dev_buf(c, Slot::LE_LISTS_EXITS, std::max((size_t)E * 2, (size_t)n_pt * PT * 4) + 64, &lp); if (rc) return rc;
             d_clist = (uint32_t *)lp;
-            rc = dev_buf(c, 27, (size_t)n_pt * 8 + 64, &lp); if (rc) return rc;
+            rc = dev_buf(c, Slot::LZ_COUNTS, (size_t)n_pt * 8 + 64, &lp); if (rc) return rc;
             d_ccnt = (uint32_t *)lp;
             RSN_HIP(hipMemsetAsync(d_ccnt, 0xFF, (size_t)n_pt * 8, s));
             if (!no_ckeys && (n_pt >= 32768 || tail_serial)) d_ckn = d_ccnt + n_pt;
@@ -2266,7 +2266,7 @@ static int lzss_encode_stream(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32
         static_assert(CC::CT == PT, "the chain walk's tiles are the parse tiles");
         static const bool no_fused = getenv("RSN_LZSS_NO_FUSED_PARSE") != nullptr;   // A/B switch: always the general parse
         const uint32_t n_prev = (uint32_t)ceil_div(n_pt, PREV_BLK);
-        void *pp; rc = dev_buf(c, 25, (size_t)n_prev * 4 + 64, &pp); if (rc) return rc;
+        void *pp; rc = dev_buf(c, Slot::LE_PREV, (size_t)n_prev * 4 + 64, &pp); if (rc) return rc;
         uint32_t *d_prev_part = (uint32_t *)pp;
         bool list_gave = true;                                                    // tiles that gave up are on the look's list (until there are too many of them)
         auto resolve = [&](bool second, bool with_pred) -> int {                  // in-tile chains, periodic stretches, the joints, the offsets; one host sync
@@ -2401,10 +2401,10 @@ static int lzss_encode_stream(Ctx &c, hipStream_t s, const uint8_t *d_fc, uint32
         rc = sweep(nullptr); if (rc) return rc;
     }
     // ---- E3: the general parse (skipped when the chain walk's own per-tile parse was accepted)
-    rc = dev_buf(c, 11, (size_t)E * 2 + 64, &p); if (rc) return rc;      // (grow-only: the lists' larger block stays where it is)
+    rc = dev_buf(c, Slot::LE_LISTS_EXITS, (size_t)E * 2 + 64, &p); if (rc) return rc;
     uint16_t *d_exit = (uint16_t *)p;
     const uint32_t n_groups = (uint32_t)ceil_div(n_pt, SUPER);
-    void *q; rc = dev_buf(c, 17, (size_t)n_groups * PT * 4 + (size_t)n_groups * 8 + 64, &q); if (rc) return rc;
+    void *q; rc = dev_buf(c, Slot::LE_SUPER, (size_t)n_groups * PT * 4 + (size_t)n_groups * 8 + 64, &q); if (rc) return rc;
     uint32_t *d_super = (uint32_t *)q;
     unsigned long long *d_gentry = (unsigned long long *)(d_super + (size_t)n_groups * PT);
     const size_t mark_sh = std::max<size_t>((size_t)PT + 2 * (size_t)W + 48, (size_t)PT * 2);
@@ -2517,18 +2517,17 @@ int lzss_encode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, int64_
     // ~12 bytes of scratch per position of a pass (keys 4, compact lists 4, chain records, the escaped stream, a section's copy) + the
     // escaped stream itself: small calls pass straight through, large ones are admitted one device-full at a time (rsn_api.hip)
     const size_t need = n < ((size_t)32 << 20) ? 0 : 13 * std::min(n, (size_t)3 << 29) + 2 * n;
-    const size_t held = scratch_admit(c, need);                        // (0 inside a host-buffer call: that one's admission covers this need)
-    const int rc = lzss_encode_admitted(c, s, d_in, n, window, d_out, out_cap, out_n);
-    // (the encoder's scratch: slots 8..19, 22..27, 35, 36 -- not 20 / 21, the host-buffer entry points' staging, still in use by the caller)
-    scratch_release(c, held, (0xFFFull << 8) | (0x3Full << 22) | (3ull << 35));
-    return rc;
+    // (released: the encoder's set -- not the host-buffer entry points' staging, still in use by the caller; inside a host-buffer call that
+    //  one's admission covers this need, and nothing is released here)
+    Admission gate(c, slotset::LZSS_ENC); gate.admit(need);
+    return lzss_encode_admitted(c, s, d_in, n, window, d_out, out_cap, out_n);
 }
 
 static int lzss_encode_admitted(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, int64_t window, uint8_t *d_out, size_t out_cap, size_t *out_n) {
     void *p; int rc;
     // ---- E1
     const uint32_t n_eb = (uint32_t)ceil_div(n, ESC_TILE);
-    rc = dev_buf(c, 8, ((size_t)n_eb * 2 + 3) * 8, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::LE_ESC_BLOCKS, ((size_t)n_eb * 2 + 3) * 8, &p); if (rc) return rc;
     unsigned long long *d_extra = (unsigned long long *)p, *d_eoff = d_extra + n_eb, *d_etot = d_eoff + n_eb;   // d_etot[1]: the check's flags; [2]: 1 + the last chunk that does not repeat
     void *hp; rc = pinned_buf(c, 64, &hp); if (rc) return rc;
     unsigned long long *h64 = (unsigned long long *)hp;
@@ -2540,7 +2539,7 @@ static int lzss_encode_admitted(Ctx &c, hipStream_t s, const uint8_t *d_in, size
     // before them): most inputs hold no 5C and no FF, and then the escaped stream is the input with '<' mapped to FF (lzss.go:373-377),
     // which the chain walk and the token emitter can do where they load it.  The copy (r04 wrote it here, N bytes out and N back in for
     // one byte value in 254: half of config 3's traffic) is written only if a kernel that wants the stream in memory has to run.
-    if (Wp) { void *sp; rc = dev_buf(c, 35, (size_t)n_eb + 64, &sp); if (rc) return rc; d_same = (uint8_t *)sp; }
+    if (Wp) { void *sp; rc = dev_buf(c, Slot::LE_SAME, (size_t)n_eb + 64, &sp); if (rc) return rc; d_same = (uint8_t *)sp; }
     RSN_HIP(hipMemsetAsync(d_etot + 1, 0, 16, s));
     RSN_LAUNCH("lzss_esc_check", k_esc_try, dim3((uint32_t)ceil_div(n_eb, ESC_RUN)), dim3(LB), 0, s, d_in, n, (uint8_t *)nullptr, d_etot + 1, d_same ? Wp : 0u, d_same, n_eb);
     static const bool no_tail = getenv("RSN_LZSS_NO_PERIODIC_TAIL") != nullptr;   // A/B switch (tests): a W-periodic stream through the whole pipeline
@@ -2562,9 +2561,9 @@ static int lzss_encode_admitted(Ctx &c, hipStream_t s, const uint8_t *d_in, size
     }
     const size_t E64 = n + (size_t)h64[0];
     uint8_t *d_fc = nullptr;
-    auto write_stream = [&](size_t upto = 0) -> int {                 // the escaped stream in memory (slot 9), zeroed padding behind it (upto: a prefix of a stream that needs no escape)
+    auto write_stream = [&](size_t upto = 0) -> int {                 // the escaped stream in memory (LE_ESCAPED), zeroed padding behind it (upto: a prefix of a stream that needs no escape)
         const size_t len = upto ? upto : E64;
-        void *q; int r2 = dev_buf(c, 9, len + 64, &q); if (r2) return r2;
+        void *q; int r2 = dev_buf(c, Slot::LE_ESCAPED, len + 64, &q); if (r2) return r2;
         d_fc = (uint8_t *)q;
         RSN_HIP(hipMemsetAsync(d_fc + len, 0, 64, s));
         const uint32_t n_b = (uint32_t)ceil_div(len, ESC_TILE);
@@ -2639,7 +2638,7 @@ static int lzss_encode_admitted(Ctx &c, hipStream_t s, const uint8_t *d_in, size
         const uint32_t stop_tile = last ? 0u : (uint32_t)((entry - a0 + sec) / PT);
         // an aligned copy of its own with zeroed padding behind it, like a whole stream's (the kernels load 16 bytes at a time from the
         // base, and what lies behind the last position must not look like data): 1 GiB device to device, 0.4 ms of a 30 ms section
-        rc = dev_buf(c, 36, (size_t)Es + 64, &sp); if (rc) return rc;
+        rc = dev_buf(c, Slot::LZ_SECTION, (size_t)Es + 64, &sp); if (rc) return rc;
         RSN_HIP(copy_async(sp, d_fc + a0, Es, hipMemcpyDeviceToDevice, s));
         RSN_HIP(hipMemsetAsync((uint8_t *)sp + Es, 0, 64, s));
         const uint8_t *fc_s = (const uint8_t *)sp;
@@ -2688,7 +2687,7 @@ int lzss_encode_sliced(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, int
     std::vector<std::pair<size_t, size_t>> held;
     auto announce = [&](bool all_checked) -> bool { if (!all_checked) return true; for (auto &r : held) if (!st.have_out(r.first, r.second)) return false; held.clear(); return true; };
     void *p; int rc;
-    rc = dev_buf(c, 8, 64, &p); if (rc) return rc;
+    rc = dev_buf(c, Slot::LE_ESC_BLOCKS, 64, &p); if (rc) return rc;
     unsigned long long *d_flag = (unsigned long long *)p;
     void *hp; rc = pinned_buf(c, 64, &hp); if (rc) return rc;
     unsigned long long *h64 = (unsigned long long *)hp;
@@ -2720,7 +2719,7 @@ int lzss_encode_sliced(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, int
         }
         const uint32_t Es = (uint32_t)(b0 - a0);
         const uint32_t stop_tile = last ? 0u : (uint32_t)((entry - a0 + sec) / PT);
-        rc = dev_buf(c, 36, (size_t)Es + 64, &sp); if (rc) return rc;
+        rc = dev_buf(c, Slot::LZ_SECTION, (size_t)Es + 64, &sp); if (rc) return rc;
         RSN_HIP(copy_async(sp, d_in + a0, Es, hipMemcpyDeviceToDevice, s));
         RSN_HIP(hipMemsetAsync((uint8_t *)sp + Es, 0, 64, s));
         size_t got = 0; uint32_t exit_local = 0;

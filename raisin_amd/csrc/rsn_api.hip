@@ -198,8 +198,8 @@ static void trim_own_context() {
     }
 }
 
-int dev_buf(Ctx &c, int slot, size_t bytes, void **out) {
-    Ctx::Buf &b = c.bufs[slot];
+int dev_buf(Ctx &c, Slot slot, size_t bytes, void **out) {
+    Ctx::Buf &b = c.buf(slot);
     if (bytes > b.cap) {
         if (b.p) { RSN_HIP(hipFree(b.p)); g_arena_bytes[c.device & 63] -= b.cap; b.p = nullptr; b.cap = 0; }
         const size_t want = round_up(bytes + bytes / 8, 4096);
@@ -386,6 +386,24 @@ hipError_t copy_up(void *dst, const void *src, size_t len, hipStream_t st, const
     }
     return hipSuccess;
 }
+
+// A host buffer onto the device, the way every kernel expects its input.  stage_buf: `slot` grown to round_up(n, 16) + 64 bytes, the 64
+// bytes from the last 16-byte boundary at or before n zeroed (the kernels' vector loads see zeros behind the data, not an earlier call's
+// bytes).  stage_input: that, then the copy -- bytes another call has registered stay registered under it (PinGuard), and the stream is
+// synchronised before they can be released.  Both fail with the message in c.err.
+int stage_buf(Ctx &c, hipStream_t s, Slot slot, size_t n, void **d_in) {
+    int rc = dev_buf(c, slot, round_up(n, 16) + 64, d_in); if (rc) return rc;
+    RSN_HIP(hipMemsetAsync((uint8_t *)*d_in + (n & ~(size_t)15), 0, 64, s));
+    return RSN_OK;
+}
+int stage_input(Ctx &c, hipStream_t s, Slot slot, const uint8_t *in, size_t n, void **d_in) {
+    int rc = stage_buf(c, s, slot, n, d_in); if (rc) return rc;
+    PinGuard g;
+    pin_acquire(in, n, false, g.h);
+    RSN_HIP(copy_up(*d_in, in, n, s, g.h));
+    if (!g.h.held.empty()) RSN_HIP(hipStreamSynchronize(s));
+    return RSN_OK;
+}
 }  // namespace
 
 // Host-buffer wrapper: H2D, run `fn` on device buffers, D2H into a library-owned result.
@@ -399,29 +417,17 @@ int host_call(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n, size_t 
     *out = nullptr; *out_n = 0;
     int rc = ctx_init(c); if (rc) return rc;
     hipStream_t s = c.own_stream;
-    struct Admitted {                                                  // released, with the large buffers when others wait, on every way out
-        Ctx &c; size_t held;
-        ~Admitted() { scratch_release(c, held, (3ull << 20) | (0xFFFull << 8) | (0x3Full << 22) | (3ull << 35)); }   // staging + the codecs' slots (8..19, 22..27, 35, 36)
-    };
-    const size_t total_need = round_up(n, 16) + 64 + bound + bound / 8 + codec_need;
-    Admitted gate{c, total_need >= ((size_t)64 << 20) ? scratch_admit(c, total_need) : 0};
+    Admission gate(c, slotset::HOST_CALL); gate.admit(round_up(n, 16) + 64 + bound + bound / 8 + codec_need, ADMIT_FROM);
     static const bool timing = getenv("RSN_HOST_TIMING") != nullptr;
     auto stamp = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_in = timing ? stamp() : 0;
     void *d_in, *d_out;
-    rc = dev_buf(c, 20, round_up(n, 16) + 64, &d_in); if (rc) return rc;
-    RSN_HIP(hipMemsetAsync((uint8_t *)d_in + (n & ~(size_t)15), 0, 64, s));
-    {
-        PinGuard g;                                                       // (another call may have these bytes registered: not released under this copy)
-        pin_acquire(in, n, false, g.h);
-        RSN_HIP(copy_up(d_in, in, n, s, g.h));
-        if (n && !g.h.held.empty()) RSN_HIP(hipStreamSynchronize(s));
-    }
+    rc = stage_input(c, s, Slot::STAGE_IN, in, n, &d_in); if (rc) return rc;
     if (timing) RSN_HIP(hipStreamSynchronize(s));
     const double t_up = timing ? stamp() : 0;
     size_t cap = bound, got = 0;
     for (int attempt = 0;; attempt++) {
-        rc = dev_buf(c, 21, cap, &d_out); if (rc) return rc;
+        rc = dev_buf(c, Slot::STAGE_OUT, cap, &d_out); if (rc) return rc;
         rc = fn(c, s, (const uint8_t *)d_in, (uint8_t *)d_out, cap, &got);
         if (rc == RSN_ERR_CAPACITY && attempt == 0 && got > cap) { cap = got; continue; }
         break;
@@ -465,15 +471,13 @@ static int piped_call(const uint8_t *in, size_t n, size_t out_cap, size_t codec_
     Ctx &c = ctx();
     int rc = ctx_init(c); if (rc) return rc;
     hipStream_t s = c.own_stream;
-    struct Admitted { Ctx &c; size_t held; ~Admitted() { scratch_release(c, held, (3ull << 20) | (0xFFFull << 8) | (0x3Full << 22) | (3ull << 35)); } };
-    Admitted gate{c, scratch_admit(c, round_up(n, 16) + 64 + out_cap + codec_need)};
+    Admission gate(c, slotset::HOST_CALL); gate.admit(round_up(n, 16) + 64 + out_cap + codec_need);
     void *d_in, *d_out;
-    rc = dev_buf(c, 20, round_up(n, 16) + 64, &d_in); if (rc) return rc;
-    rc = dev_buf(c, 21, round_up(out_cap, 16) + 64, &d_out); if (rc) return rc;
+    rc = stage_buf(c, s, Slot::STAGE_IN, n, &d_in); if (rc) return rc;               // (the uploader below sends the bytes)
+    rc = dev_buf(c, Slot::STAGE_OUT, round_up(out_cap, 16) + 64, &d_out); if (rc) return rc;
     uint8_t *res = (uint8_t *)result_alloc(out_cap);
     if (!res) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", out_cap);
-    RSN_HIP(hipMemsetAsync((uint8_t *)d_in + (n & ~(size_t)15), 0, 64, s));
-    RSN_HIP(hipStreamSynchronize(s));                                     // (before the uploader's first piece lands on the same bytes)
+    RSN_HIP(hipStreamSynchronize(s));                                     // (the zeroed tail, before the uploader's first piece lands on the same bytes)
 
     struct Pipe {
         std::mutex mu; std::condition_variable cv;
@@ -903,7 +907,6 @@ static int rsn_lzss_decompress_impl(const uint8_t *in, size_t n, uint8_t **out, 
 //                          staying with the worker's (parked) context for the next batch
 namespace {
 struct BatchPipe {
-    enum { RING = 3 };
     std::mutex mu; std::condition_variable cv;
     size_t uploaded = 0, encoded = 0, downloaded = 0;      // chunks that have left each stage
     int rc = RSN_OK; std::string msg;
@@ -934,9 +937,9 @@ static int batch_on_device(Ctx &c, const std::vector<size_t> &idx, const uint8_t
     for (size_t i : idx) max_len = std::max(max_len, lens[i]);
     BatchPipe P;
     const size_t in_cap = round_up(max_len, 16) + 64, out_cap = max_len + max_len / 8 + (1 << 16);   // typical outputs are < n; a chunk that needs more gets its own block
-    for (int r = 0; r < BatchPipe::RING; r++) {
-        int rc = dev_buf(c, 28 + r, in_cap, &P.d_in[r]); if (rc) return rc;
-        rc = dev_buf(c, 28 + BatchPipe::RING + r, out_cap, &P.d_out[r]); if (rc) return rc;
+    for (int r = 0; r < RING; r++) {
+        int rc = dev_buf(c, ring_in(r), in_cap, &P.d_in[r]); if (rc) return rc;
+        rc = dev_buf(c, ring_out(r), out_cap, &P.d_out[r]); if (rc) return rc;
     }
     const int device = c.device;
     static const bool timing = getenv("RSN_HOST_TIMING") != nullptr;
@@ -949,7 +952,7 @@ static int batch_on_device(Ctx &c, const std::vector<size_t> &idx, const uint8_t
         for (size_t j = 0; j < m; j++) {
             if (!P.wait(P.uploaded, j + 1)) return;
             const size_t i = idx[j];
-            const int r = (int)(j % BatchPipe::RING);
+            const int r = (int)(j % RING);
             size_t got = 0;
             int rc = huff_encode_dev(ce, s, (const uint8_t *)P.d_in[r], lens[i], (uint8_t *)P.d_out[r], out_cap, &got, nullptr, nullptr);
             if (rc == RSN_ERR_CAPACITY && got > out_cap) {
@@ -970,7 +973,7 @@ static int batch_on_device(Ctx &c, const std::vector<size_t> &idx, const uint8_t
         for (size_t j = 0; j < m; j++) {
             if (!P.wait(P.encoded, j + 1)) return;
             const size_t i = idx[j];
-            const int r = (int)(j % BatchPipe::RING);
+            const int r = (int)(j % RING);
             const size_t got = P.got[r];
             uint8_t *res = (uint8_t *)result_alloc(got);
             if (!res) { P.fail(RSN_ERR_NOMEM, "allocating a result block failed"); return; }
@@ -990,24 +993,22 @@ static int batch_on_device(Ctx &c, const std::vector<size_t> &idx, const uint8_t
     }
     // this thread uploads
     for (size_t j = 0; j < m; j++) {
-        if (j >= BatchPipe::RING && !P.wait(P.downloaded, j + 1 - BatchPipe::RING)) break;   // the ring slot is free once its segment is down
+        if (j >= RING && !P.wait(P.downloaded, j + 1 - RING)) break;   // the ring slot is free once its segment is down
         const size_t i = idx[j];
-        const int r = (int)(j % BatchPipe::RING);
+        const int r = (int)(j % RING);
         hipStream_t s = c.own_stream;
-        hipError_t e = hipMemsetAsync((uint8_t *)P.d_in[r] + (lens[i] & ~(size_t)15), 0, 64, s);
-        PinGuard g;                                                       // (bytes another call has registered stay registered under this copy)
-        pin_acquire(ins[i], lens[i], false, g.h);
-        if (e == hipSuccess) e = copy_up(P.d_in[r], ins[i], lens[i], s, g.h);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { P.fail(RSN_ERR_DEVICE, hipGetErrorString(e)); break; }
+        int rc = stage_input(c, s, ring_in(r), ins[i], lens[i], &P.d_in[r]);   // (in_cap holds every chunk: the slot does not move)
+        if (rc == RSN_OK && hipStreamSynchronize(s) != hipSuccess) rc = c.fail(RSN_ERR_DEVICE, "hipStreamSynchronize after an upload failed");
+        if (rc != RSN_OK) { P.fail(rc, c.err.c_str()); break; }
         if (timing) fprintf(stderr, "batch dev %d chunk %zu up at %.2f ms\n", device, i, stamp());
         P.done(P.uploaded);
     }
     HelperPool::wait(encoder);
     HelperPool::wait(downloader);
-    for (int r = 0; r < BatchPipe::RING; r++) if (P.d_tmp[r]) (void)hipFree(P.d_tmp[r]);
-    if ((in_cap + out_cap) * BatchPipe::RING > ((size_t)std::max(0, env_int("RSN_BATCH_KEEP_MIB", 1024)) << 20))
-        for (int k = 28; k < 28 + 2 * BatchPipe::RING; k++) { if (c.bufs[k].p) { (void)hipFree(c.bufs[k].p); scratch_forget(c, c.bufs[k].cap); } c.bufs[k].p = nullptr; c.bufs[k].cap = 0; }
+    for (int r = 0; r < RING; r++) if (P.d_tmp[r]) (void)hipFree(P.d_tmp[r]);
+    if ((in_cap + out_cap) * RING > ((size_t)std::max(0, env_int("RSN_BATCH_KEEP_MIB", 1024)) << 20))
+        for (int r = 0; r < RING; r++)
+            for (Slot k : {ring_in(r), ring_out(r)}) { Ctx::Buf &b = c.buf(k); if (b.p) { (void)hipFree(b.p); scratch_forget(c, b.cap); } b.p = nullptr; b.cap = 0; }
     if (P.rc != RSN_OK) return c.fail(P.rc, "%s", P.msg.c_str());
     return RSN_OK;
 }
@@ -1311,15 +1312,7 @@ static int rsn_huffman_compress_sharded_impl(const uint8_t *in, size_t n, int sh
         auto bail = [&](int rc) { sync.fail(rc, cw.err.c_str()); };
         const size_t n_w = cut[w + 1] - cut[w];
         void *d_in = nullptr, *d_out = nullptr;
-        int rc = dev_buf(cw, 20, round_up(n_w, 16) + 64, &d_in); if (rc) return bail(rc);
-        hipError_t e = hipMemsetAsync((uint8_t *)d_in + (n_w & ~(size_t)15), 0, 64, s);
-        {
-            PinGuard g;
-            pin_acquire(in + cut[w], n_w, false, g.h);
-            if (e == hipSuccess) e = copy_up(d_in, in + cut[w], n_w, s, g.h);
-            if (e == hipSuccess && !g.h.held.empty()) e = hipStreamSynchronize(s);
-        }
-        if (e != hipSuccess) { sync.fail(RSN_ERR_DEVICE, hipGetErrorString(e)); return; }
+        int rc = stage_input(cw, s, Slot::STAGE_IN, in + cut[w], n_w, &d_in); if (rc) return bail(rc);
         rc = huff_slice_hist(cw, s, (const uint8_t *)d_in, n_w, sl[w].hs); if (rc) return bail(rc);
         if (!sync.meet(plan)) return;
         Slice &x = sl[w];
@@ -1327,7 +1320,7 @@ static int rsn_huffman_compress_sharded_impl(const uint8_t *in, size_t n, int sh
         const size_t origin = w == 0 ? 0 : (size_t)(x.start / 8) & ~(size_t)15;
         const unsigned long long base = x.start - 8ull * origin;
         const size_t local = (size_t)((base + x.bits + 7) / 8);
-        rc = dev_buf(cw, 21, round_up(local, 16) + 64, &d_out); if (rc) return bail(rc);
+        rc = dev_buf(cw, Slot::STAGE_OUT, round_up(local, 16) + 64, &d_out); if (rc) return bail(rc);
         rc = huff_slice_emit(cw, s, (const uint8_t *)d_in, n_w, x.hs, tree, codes, flat, w == 0 ? hdr : std::string(), base, x.bits, (uint8_t *)d_out);
         if (rc) return bail(rc);
         // down: the bytes that are this slice's alone straight into the result, its first and last payload byte (which a neighbour
@@ -1337,7 +1330,7 @@ static int rsn_huffman_compress_sharded_impl(const uint8_t *in, size_t n, int sh
         x.has = x.bits != 0;
         x.first = (size_t)(x.start / 8); x.last = hi;
         const uint8_t *dl = (const uint8_t *)d_out - origin;                // dl[k] = byte k of the stream
-        e = hipSuccess;
+        hipError_t e = hipSuccess;
         if (x.has) {
             e = copy_async(&x.edge[0], dl + x.first, 1, hipMemcpyDeviceToHost, s);
             if (e == hipSuccess) e = copy_async(&x.edge[1], dl + x.last, 1, hipMemcpyDeviceToHost, s);
@@ -1368,12 +1361,8 @@ static int rsn_huffman_compress_sharded_impl(const uint8_t *in, size_t n, int sh
 
 // ---- layered calls (rsn.h): a list of layers over one buffer, the stream kept on the device between the layers.
 // host_call's shape -- an input slot, an output slot, fn(c, s, d_in, d_out, cap, &got) with one retry on RSN_ERR_CAPACITY -- with the
-// two slots swapped per layer.  Slots of their own: 39 the uploaded input (the round trip keeps it to the end), 40 / 41 the stream,
-// taking turns, 42 the round trip's counts and its first-difference word.
+// two slots swapped per layer.  Slots of their own (Slot::L_IN, L_A, L_B, L_STAT); the gate releases host_call's and these.
 namespace {
-constexpr int L_IN = 39, L_A = 40, L_B = 41, L_STAT = 42;
-constexpr unsigned long long CALL_SLOTS = (3ull << 20) | (0xFFFull << 8) | (0x3Full << 22) | (3ull << 35) | (0xFull << 39);   // host_call's and these
-struct Admitted { Ctx &c; size_t held; ~Admitted() { scratch_release(c, held, CALL_SLOTS); } };
 struct HostBlock { uint8_t *p = nullptr; ~HostBlock() { if (p) result_free(p); } uint8_t *release() { uint8_t *r = p; p = nullptr; return r; } };
 // host buffers up to this size run the chain of single host calls (RSN_LAYERS_CHAIN_MAX: the A/B of scripts/layers_bench.py)
 size_t layers_chain_max() {
@@ -1437,22 +1426,10 @@ static int layers_host_chain(Ctx &c, bool enc, const uint8_t *in, size_t n, cons
     return RSN_OK;
 }
 
-static int upload_input(Ctx &c, hipStream_t s, const uint8_t *in, size_t n, uint8_t **d_in) {
-    void *p;
-    int rc = dev_buf(c, L_IN, round_up(n, 16) + 64, &p); if (rc) return rc;
-    RSN_HIP(hipMemsetAsync((uint8_t *)p + (n & ~(size_t)15), 0, 64, s));
-    PinGuard g;                                                           // (another call may have these bytes registered: not released under this copy)
-    pin_acquire(in, n, false, g.h);
-    RSN_HIP(copy_up(p, in, n, s, g.h));
-    if (n && !g.h.held.empty()) RSN_HIP(hipStreamSynchronize(s));
-    *d_in = (uint8_t *)p;
-    return RSN_OK;
-}
-
 // The layers over a stream that is on the device: step k reads what step k - 1 wrote, the slots L_A / L_B taking turns from `slot` on.
 // The last step writes to `last_out` (the caller's buffer, no retry: RSN_ERR_CAPACITY and the need in *res_n) when there is one, else
 // into a slot too.  Every codec synchronises `s` before it returns.  *res / *res_n: where the result is, and its size.
-static int run_chain(Ctx &c, hipStream_t s, bool enc, const int *layers, size_t n_layers, const uint8_t *d_src, size_t n, int slot,
+static int run_chain(Ctx &c, hipStream_t s, bool enc, const int *layers, size_t n_layers, const uint8_t *d_src, size_t n, Slot slot,
                      uint8_t *last_out, size_t last_cap, const uint8_t **res, size_t *res_n) {
     const uint8_t *cur = d_src; size_t cur_n = n;
     *res_n = 0;
@@ -1472,7 +1449,7 @@ static int run_chain(Ctx &c, hipStream_t s, bool enc, const int *layers, size_t 
         if (rc) { if (rc == RSN_ERR_CAPACITY) *res_n = got; return layer_fail(c, rc, li, id); }
         if (!to_caller) RSN_HIP(hipMemsetAsync(dst + got, 0, round_up(got, 16) + 64 - got, s));   // zero behind the stream, as behind an uploaded input
         cur = dst; cur_n = got;
-        slot = slot == L_A ? L_B : L_A;
+        slot = slot == Slot::L_A ? Slot::L_B : Slot::L_A;
     }
     *res = cur; *res_n = cur_n;
     return RSN_OK;
@@ -1494,11 +1471,11 @@ static int layers_host(bool enc, const uint8_t *in, size_t n, const int *layers,
     if (n_layers == 1 || n <= layers_chain_max()) return layers_host_chain(c, enc, in, n, layers, n_layers, out, out_n);
     hipStream_t s = c.own_stream;
     const size_t need = round_up(n, 16) + 64 + layers_need(enc, layers, n_layers, n);
-    Admitted gate{c, need >= ((size_t)64 << 20) ? scratch_admit(c, need) : 0};
-    uint8_t *d_in;
-    rc = upload_input(c, s, in, n, &d_in); if (rc) return rc;
+    Admission gate(c, slotset::LAYERED_CALL); gate.admit(need, ADMIT_FROM);
+    void *d_in;
+    rc = stage_input(c, s, Slot::L_IN, in, n, &d_in); if (rc) return rc;
     const uint8_t *d_res; size_t got = 0;
-    rc = run_chain(c, s, enc, layers, n_layers, d_in, n, L_A, nullptr, 0, &d_res, &got); if (rc) return rc;
+    rc = run_chain(c, s, enc, layers, n_layers, (const uint8_t *)d_in, n, Slot::L_A, nullptr, 0, &d_res, &got); if (rc) return rc;
     HostBlock r;
     r.p = (uint8_t *)result_alloc(got);
     if (!r.p) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", got);
@@ -1533,9 +1510,9 @@ static int layers_dev(bool enc, const void *d_in, size_t n, const int *layers, s
         return rc ? layer_fail(c, rc, 0, id) : RSN_OK;
     }
     const size_t need = layers_need(enc, layers, n_layers, n);
-    Admitted gate{c, need >= ((size_t)64 << 20) ? scratch_admit(c, need) : 0};
+    Admission gate(c, slotset::LAYERED_CALL); gate.admit(need, ADMIT_FROM);
     const uint8_t *d_res; size_t got = 0;
-    rc = run_chain(c, s, enc, layers, n_layers, (const uint8_t *)d_in, n, L_A, out_cap ? (uint8_t *)d_out : nullptr, out_cap, &d_res, &got);
+    rc = run_chain(c, s, enc, layers, n_layers, (const uint8_t *)d_in, n, Slot::L_A, out_cap ? (uint8_t *)d_out : nullptr, out_cap, &d_res, &got);
     if (rc) { if (rc == RSN_ERR_CAPACITY) *out_n = got; return rc; }
     if (!out_cap && got) {                                                // the size query: the chain has run, its last layer into scratch (an empty result has nothing to size: RSN_OK, as from the single calls)
         *out_n = round_up(got, 16) + 32;                                  // (what every last layer takes: the Huffman encoder asks for its size rounded up to 16, plus 32)
@@ -1576,11 +1553,11 @@ static int layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size
     } else {
         hipStream_t s = c.own_stream;
         const size_t need = round_up(n, 16) + 64 + layers_need(true, layers, n_layers, n) + 2 * n;
-        Admitted gate{c, need >= ((size_t)64 << 20) ? scratch_admit(c, need) : 0};
-        uint8_t *d_in;
-        rc = upload_input(c, s, in, n, &d_in); if (rc) return rc;
+        Admission gate(c, slotset::LAYERED_CALL); gate.admit(need, ADMIT_FROM);
+        void *d_up; rc = stage_input(c, s, Slot::L_IN, in, n, &d_up); if (rc) return rc;
+        const uint8_t *d_in = (const uint8_t *)d_up;
         const uint8_t *d_c; size_t cn = 0;
-        rc = run_chain(c, s, true, layers, n_layers, d_in, n, L_A, nullptr, 0, &d_c, &cn); if (rc) return rc;
+        rc = run_chain(c, s, true, layers, n_layers, d_in, n, Slot::L_A, nullptr, 0, &d_c, &cn); if (rc) return rc;
         if (compressed) {
             comp.p = (uint8_t *)result_alloc(cn);
             if (!comp.p) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", cn);
@@ -1588,9 +1565,9 @@ static int layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size
         }
         const auto t1 = now();
         const uint8_t *d_d; size_t dn = 0;
-        rc = run_chain(c, s, false, layers, n_layers, d_c, cn, d_c == (const uint8_t *)c.bufs[L_A].p ? L_B : L_A, nullptr, 0, &d_d, &dn); if (rc) return rc;
+        rc = run_chain(c, s, false, layers, n_layers, d_c, cn, d_c == (const uint8_t *)c.buf(Slot::L_A).p ? Slot::L_B : Slot::L_A, nullptr, 0, &d_d, &dn); if (rc) return rc;
         void *p, *hp;
-        rc = dev_buf(c, L_STAT, 513 * 8 + 64, &p); if (rc) return rc;
+        rc = dev_buf(c, Slot::L_STAT, 513 * 8 + 64, &p); if (rc) return rc;
         unsigned long long *d_stat = (unsigned long long *)p;
         rc = byte_hist256_dev(c, s, d_in, n, d_stat); if (rc) return rc;
         rc = byte_hist256_dev(c, s, d_d, dn, d_stat + 256); if (rc) return rc;
@@ -1643,13 +1620,7 @@ static int64_t rsn_huffman_table_impl(const uint8_t *in, size_t n, uint32_t *run
     int rc = ctx_init(c); if (rc) return rc;
     hipStream_t s = c.own_stream;
     void *d_in;
-    rc = dev_buf(c, 20, round_up(n, 16) + 64, &d_in); if (rc) return rc;
-    {
-        PinGuard g;
-        pin_acquire(in, n, false, g.h);
-        RSN_HIP(copy_up(d_in, in, n, s, g.h));
-        if (!g.h.held.empty()) RSN_HIP(hipStreamSynchronize(s));
-    }
+    rc = stage_input(c, s, Slot::STAGE_IN, in, n, &d_in); if (rc) return rc;
     HuffTree t; HuffCodes hc; size_t dummy = 0;
     rc = huff_encode_dev(c, s, (const uint8_t *)d_in, n, nullptr, 0, &dummy, &t, &hc);
     if (rc) return rc;

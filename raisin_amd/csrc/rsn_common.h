@@ -26,6 +26,84 @@ struct ProfSlot {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
+// The scratch slots of a thread's arena (Ctx::bufs, dev_buf): one row per slot -- who allocates it, what it holds, and in [..] the
+// codec gates that give its block back (E: the LZSS encoder's, D: the LZSS decoder's; X*: released by X's gate though X never allocates
+// it; the masks are below the table).  The gates of the host-buffer calls release what E releases plus the staging pair; the layered
+// calls' gate releases those and its own four slots.
+// A slot with two users is shared by convention: every codec call synchronises its stream before it returns, and the calls of one
+// thread -- the layers of a layered call included -- run one after the other, so the two users are never live together.
+// The numbers are fixed: DESIGN 4.8 and comments cite them, and a parked arena is adopted by index.
+enum class Slot : int {
+    HE_TILE_HIST = 0,   // Huffman encoder: per-tile histograms
+    HE_BYTE_HIST = 1,   // Huffman encoder: the 256 byte counts
+    HE_RUNE_HIST = 2,   // Huffman encoder, rune path: a count per rune
+    HE_CODES = 3,       // Huffman encoder: the code table in the form its emit kernel wants (flat / rune list / Tab)
+    HE_TILE_BITS = 4,   // Huffman encoder: the tiles' bit counts and offsets
+    HD_TABLES = 5,      // Huffman decoder: first-level table, tree children, second level
+    H_RUNES_SUBSEQ = 6, // SHARED -- Huffman encoder, rune path: rune flags, offsets and (rune, count) pairs; Huffman decoder: the subsequences' exit / entry / byte records
+    HD_BLOCKS = 7,      // Huffman decoder: the blocks' byte counts and offsets
+    LE_ESC_BLOCKS = 8,  // LZSS encoder: the escape pass's per-block counts, offsets and flags (a sectioned call: its flag word) [E]
+    LE_ESCAPED = 9,     // LZSS encoder: the escaped stream [E]
+    LE_KEYS = 10,       // LZSS encoder: the positions' hash keys (4 bytes each; lzss_big: 8) [E]
+    LE_LISTS_EXITS = 11,// LZSS encoder: the chain walk's compact lists, later the general parse's exits (2 bytes a position), lzss_big's two next-arrays
+                        //   -- grow-only: the lists' larger block stays when the exits ask for less [E]
+    LE_TILES = 12,      // LZSS encoder: the parse tiles' bytes, offsets, entry bits and chains (lzss_big: its blocks' and the on-bits) [E]
+    LD_BLOCKS = 13,     // LZSS decoder: the count pass's per-block lengths, offsets and flags [D, E*]
+    LD_DESC = 14,       // LZSS decoder: the tiles' descriptors (tile path) or a source index per escaped byte [D, E*]
+    LD_ESCAPED = 15,    // LZSS decoder: the escaped stream [D, E*]
+    LD_UNESCAPE = 16,   // LZSS decoder: the unescape blocks' lengths, offsets, summaries (lzss_unescape's layout) [D, E*]
+    LE_SUPER = 17,      // LZSS encoder: the general parse's super-tiles and group entries [E]
+    LE_STRIPS = 18,     // LZSS encoder: the strips' heavy / redo / dense marks [E]
+    LZ_DUMP_TILES = 19, // SHARED -- LZSS encoder: the chain walk's dump; LZSS decoder: the tile list [E, D]
+    STAGE_IN = 20,      // host-buffer calls: the uploaded input (stage_input, rsn_api.hip)
+    STAGE_OUT = 21,     // host-buffer calls: the codec's output before it goes down
+    LD_MAPS = 22,       // LZSS decoder, tile path: the groups' two map arrays and tails [D, E*]
+    LD_RUNS = 23,       // LZSS decoder, tile path: the tiles' runs and their counts [D, E*]
+    SCAN_PARTIALS = 24, // SHARED by all four directions -- scan_u64's block partials (huff_encode.hip): both Huffman directions, the LZSS encoder (lzss_big too) and
+                        //   the LZSS decoder call it, each scan finished before the next begins [E; not D, though the decoder allocates it too]
+    LE_PREV = 25,       // LZSS encoder: the chain walk's n_prev partials [E, D*]
+    RUNES_REDO = 26,    // SHARED -- Huffman encoder, rune path: the rune start map; LZSS encoder: the chain walk's redo list [E]
+    LZ_COUNTS = 27,     // SHARED -- LZSS encoder: the compact lists' counts; LZSS decoder: the count pass's needs and spans [E, D]
+    RING_IN0 = 28, RING_IN1 = 29, RING_IN2 = 30,        // the batch pipeline's ring (ring_in / ring_out below): the chunks' inputs ...
+    RING_OUT0 = 31, RING_OUT1 = 32, RING_OUT2 = 33,     // ... and their segments; freed by the batch itself above RSN_BATCH_KEEP_MIB
+    HD_TILE_WORDS = 34, // Huffman decoder, one-pass path: the tile words and block map
+    LE_SAME = 35,       // LZSS encoder: k_esc_try's block flags [E]
+    LZ_SECTION = 36,    // SHARED -- a section's stream.  LZSS encoder: the aligned copy; LZSS decoder: the escaped bytes in front + the section's tokens [E, D]
+    HS_INPUT = 37,      // small-input Huffman path: the device copy
+    HS_DEC_MAPS = 38,   // small-input Huffman decoder: the blocks' maps and flags (keyed on Buf::gen)
+    L_IN = 39,          // layered calls: the uploaded input (the round trip keeps it to the end) [layered]
+    L_A = 40,           // layered calls: the stream between the layers ... [layered]
+    L_B = 41,           // ... the two taking turns [layered]
+    L_STAT = 42,        // layered round trip: the two histograms and the first-difference word [layered]
+};
+constexpr int RING = 3;                                                  // the batch pipeline's depth: RING inputs, RING segments
+constexpr Slot ring_in(int r) { return (Slot)((int)Slot::RING_IN0 + r); }
+constexpr Slot ring_out(int r) { return (Slot)((int)Slot::RING_OUT0 + r); }
+template <class... S> constexpr unsigned long long slot_mask(S... s) { return ((1ull << (int)s) | ... | 0ull); }
+
+namespace slotset {   // bit k = slot k (scratch_release)
+using S = Slot;
+// what each codec allocates (the structural checks below; the rows above say what for)
+constexpr unsigned long long HUFF_OWN = slot_mask(S::HE_TILE_HIST, S::HE_BYTE_HIST, S::HE_RUNE_HIST, S::HE_CODES, S::HE_TILE_BITS, S::HD_TABLES, S::H_RUNES_SUBSEQ, S::HD_BLOCKS, S::SCAN_PARTIALS, S::RUNES_REDO, S::HD_TILE_WORDS, S::HS_INPUT, S::HS_DEC_MAPS);
+constexpr unsigned long long LZSS_ENC_OWN = slot_mask(S::LE_ESC_BLOCKS, S::LE_ESCAPED, S::LE_KEYS, S::LE_LISTS_EXITS, S::LE_TILES, S::LE_SUPER, S::LE_STRIPS, S::LZ_DUMP_TILES, S::SCAN_PARTIALS, S::LE_PREV, S::RUNES_REDO, S::LZ_COUNTS, S::LE_SAME, S::LZ_SECTION);
+constexpr unsigned long long LZSS_DEC_OWN = slot_mask(S::LD_BLOCKS, S::LD_DESC, S::LD_ESCAPED, S::LD_UNESCAPE, S::LZ_DUMP_TILES, S::LD_MAPS, S::LD_RUNS, S::SCAN_PARTIALS, S::LZ_COUNTS, S::LZ_SECTION);
+// what the gates give back: kept bit for bit as they have been (whether the oddities are meant is a question of behaviour, not of naming).
+// The encoder's set is its own slots plus six that only the decoder allocates; the decoder's is its own WITHOUT the scan's partials,
+// which it allocates but has never released, plus one slot of the encoder's
+constexpr unsigned long long LZSS_ENC = LZSS_ENC_OWN | slot_mask(S::LD_BLOCKS, S::LD_DESC, S::LD_ESCAPED, S::LD_UNESCAPE, S::LD_MAPS, S::LD_RUNS);
+constexpr unsigned long long LZSS_DEC = (LZSS_DEC_OWN & ~slot_mask(S::SCAN_PARTIALS)) | slot_mask(S::LE_PREV);
+constexpr unsigned long long STAGING = slot_mask(S::STAGE_IN, S::STAGE_OUT);
+constexpr unsigned long long LAYERED = slot_mask(S::L_IN, S::L_A, S::L_B, S::L_STAT);
+constexpr unsigned long long RINGS = slot_mask(ring_in(0), ring_in(1), ring_in(2), ring_out(0), ring_out(1), ring_out(2));
+constexpr unsigned long long HOST_CALL = STAGING | LZSS_ENC;              // (the decoder's set lies inside the encoder's)
+constexpr unsigned long long LAYERED_CALL = HOST_CALL | LAYERED;
+// (RING is written out three times: the enumerators, RINGS and this check change together)
+static_assert(ring_in(RING) == Slot::RING_OUT0 && ring_out(RING - 1) == Slot::RING_OUT2, "the ring's slots are RING inputs, then RING segments");
+static_assert(((STAGING | RINGS | LAYERED) & (LZSS_ENC | LZSS_DEC)) == 0, "a codec's gate releases no staging, ring or layered slot: their callers still use them");
+static_assert(((STAGING | LAYERED) & (HUFF_OWN | LZSS_ENC_OWN | LZSS_DEC_OWN)) == 0, "no codec allocates a staging or a layered slot");
+static_assert((LZSS_DEC & ~LZSS_ENC) == 0, "HOST_CALL covers both LZSS directions");
+}  // namespace slotset
+
 // One per host thread (thread_local): device, stream, reusable device scratch
 // buffers and pinned staging.  Nothing here is shared between threads.
 struct Ctx {
@@ -39,8 +117,9 @@ struct Ctx {
     std::vector<hipEvent_t> free_events;
 
     struct Buf { void *p = nullptr; size_t cap = 0; unsigned long long gen = 0; };   // gen: process-unique number of this allocation (dev_buf) -- an address can come back with other contents
-    enum { N_BUFS = 43 };   // 39..42: the layered calls' input, the stream's two turns, the round trip's counts (rsn_api.hip); 28..33: the batch pipeline's ring; 34: the one-pass Huffman decoder's tile words; 35: k_esc_try's block flags; 36: an LZSS section's stream (encoder: the aligned copy; decoder: the escaped bytes in front + the section's tokens); 37, 38: the small-input Huffman path's device copy / its decoder's block maps
+    enum { N_BUFS = (int)Slot::L_STAT + 1 };   // (the table above)
     Buf bufs[N_BUFS];
+    Buf &buf(Slot k) { return bufs[(int)k]; }
     void *pinned = nullptr; size_t pinned_cap = 0;
     bool lz_runs = false;           // the LZSS input in hand holds runs of a byte (k_esc_try's flag): lzss_encode_stream walks it with k_match_chain<RUNS>
     size_t gate_held = 0;           // scratch this thread's call in progress has been admitted with (rsn_api.hip: a nested admission is covered by it)
@@ -57,11 +136,24 @@ struct Ctx {
 
 Ctx &ctx();
 int ctx_init(Ctx &c);                       // lazy: picks device, creates stream
-int dev_buf(Ctx &c, int slot, size_t bytes, void **out);   // grow-only scratch
+int dev_buf(Ctx &c, Slot slot, size_t bytes, void **out);  // grow-only scratch
 int pinned_buf(Ctx &c, size_t bytes, void **out);
 // admission of calls with gigabytes of scratch (rsn_api.hip): waits while the device's calls in flight need more than it holds
 size_t scratch_admit(Ctx &c, size_t need);                                   // returns what to hand to scratch_release: `need`, or 0 inside a call that has been admitted already
 void scratch_release(Ctx &c, size_t held, unsigned long long slots);         // ... and gives those slots' large buffers back when others wait (bit k = slot k); held == 0: nothing to do
+// A call's place behind that gate: admitted at most once, released -- with the large buffers of `slots` when others wait -- on every way
+// out.  from: needs below it pass without asking (ADMIT_FROM: the calls whose small sizes are not worth the lock).  The sites' four rules:
+// admit(need) always asks (piped_call); the same with a need that may be 0 asks only when it is not, because scratch_admit(0) admits
+// nothing (lzss_encode_dev); admit(need, ADMIT_FROM) asks from 64 MiB (host_call, the layered calls); the decoder calls admit late, once
+// the escaped size is known.  Not copyable: a copy would release one admission twice.
+constexpr size_t ADMIT_FROM = (size_t)64 << 20;
+struct Admission {
+    Ctx &c; unsigned long long slots; size_t held = 0; bool asked = false;
+    Admission(Ctx &c_, unsigned long long slots_) : c(c_), slots(slots_) {}
+    Admission(const Admission &) = delete; Admission &operator=(const Admission &) = delete;
+    void admit(size_t need, size_t from = 0) { if (!asked && need >= from) { asked = true; held = scratch_admit(c, need); } }
+    ~Admission() { scratch_release(c, held, slots); }
+};
 void scratch_forget(Ctx &c, size_t bytes);
 unsigned long long scratch_queued(int device);                               // calls that have had to wait so far (tests)
 void prof_collect(Ctx &c);

@@ -142,3 +142,15 @@ def test_rune_start_map_at_every_lane_and_stream_edge(huff, oracle):
     cases.append(bytes(range(256)) * 40)
     got = [huff.Compress(c) for c in cases]
     assert got == [oracle.huffman_compress(c) for c in cases]
+
+
+def test_table_ignores_what_an_earlier_call_left_behind_its_input(huff, oracle, samiam):
+    """rsn_huffman_table stages its input in the slot every host-buffer call stages in.  After a call that left that slot full of bytes
+    >= 0x80, the table of ASCII text of every length 1..48 (every residue mod 16, three times over) is the oracle's: a stale byte counted
+    past n would switch the call to the rune path or add a rune."""
+    dirt = b"\xc3\xa9" * (40 << 10)                                        # 80 KiB: above the small-input path, so it goes through the staging slot
+    text = samiam[:48]
+    assert max(text) < 0x80
+    assert huff.Compress(dirt) == oracle.huffman_compress(dirt)
+    for k in range(1, 49):
+        assert huff.table(text[:k]) == oracle.huffman_table(text[:k]), k
