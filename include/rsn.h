@@ -1,7 +1,7 @@
 /*
  * rsn.h -- C ABI of librsn: the MI355X (gfx950) implementation of raisin's
- * Huffman and LZSS codecs (go-compression/raisin compressor/huffman,
- * compressor/lz).  This is the drop-in boundary: a Go host binds these entry
+ * Huffman, LZSS and arithmetic codecs (go-compression/raisin compressor/huffman,
+ * compressor/lz, compressor/arithmetic).  This is the drop-in boundary: a Go host binds these entry
  * points with cgo in place of the per-package Compress/Decompress functions
  * (binding shown in INTEGRATION.md).  Plain pointers and sizes only.
  *
@@ -203,6 +203,35 @@ typedef struct {
 } rsn_roundtrip_result;
 RSN_API int rsn_layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size_t n_layers, rsn_roundtrip_result *res,
                                  uint8_t **compressed, size_t *compressed_n);
+
+/* ---- the adaptive arithmetic codec ---------------------------------------
+ * replaces arithmetic.Compress([]byte) []byte / arithmetic.Decompress([]byte) []byte (compressor/arithmetic/arithmetic.go:15,27):
+ * an adaptive 16-bit arithmetic coder over a 257-symbol model (bytes and an end symbol) that freezes once its total reaches 16383;
+ * streams are byte for byte the reference's.  An empty input compresses to 01 ff (which, as in the reference, does not decompress).
+ * One stream is SERIAL work: each member runs on one wavefront, and the device is used by running many members at once -- the batch
+ * calls are the fast path.  A member above RSN_ARITH_MAX_BYTES (input of a compress call, output of a decompress call;
+ * for a stream handed to decompress, rsn_arithmetic_compress_bound of it) returns RSN_ERR_LIMIT.
+ * Decompress returns RSN_ERR_FORMAT where the reference panics -- no 1 bit in the stream, or fewer than 14 bits behind the first --
+ * and, the one deliberate deviation, where the reference would decode for ever: a stream that has not reached its end symbol after
+ * more than RSN_ARITH_TAIL_BITS bits have been shifted in from behind its end (the 1, 0 the decoder appends and the zeros that follow;
+ * a stream the reference's encoder wrote needs at most 16 plus the pending bits it dropped).
+ * The host-buffer and batch calls follow the contracts of their neighbours above: results released with rsn_free; n == 0 members
+ * return RSN_OK; outs[i] is byte for byte the single call's (the single call IS a batch of one: every member goes through the same
+ * two kernels); if any member fails every outs[i] is NULL, the code is the lowest failing member's and rsn_last_error() reads
+ * "member <i>: ..."; null arrays or a null member of non-zero length are RSN_ERR_ARG before a device is looked for; without a device
+ * RSN_ERR_DEVICE.  The _dev calls follow the device-resident contract above (16-byte alignment, no overlap, synchronised before
+ * returning); on RSN_ERR_CAPACITY -- or the size query, d_out NULL / out_cap 0 -- *out_n is the EXACT result size, and out_cap equal
+ * to it is accepted; nothing is ever written outside [d_out, d_out + out_cap).  A buffer of rsn_arithmetic_compress_bound(n) bytes
+ * always suffices for rsn_arithmetic_compress_dev (a symbol causes at most 16 shifts: 2 * n + 4).                                  */
+#define RSN_ARITH_TAIL_BITS 4096
+#define RSN_ARITH_MAX_BYTES ((size_t)64 << 20)
+RSN_API size_t rsn_arithmetic_compress_bound(size_t n);
+RSN_API int rsn_arithmetic_compress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n);
+RSN_API int rsn_arithmetic_decompress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n);
+RSN_API int rsn_arithmetic_compress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens);
+RSN_API int rsn_arithmetic_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens);
+RSN_API int rsn_arithmetic_compress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream);
+RSN_API int rsn_arithmetic_decompress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream);
 
 /* ---- measurement --------------------------------------------------------
  * When enabled, every kernel launch of the calling thread is bracketed by HIP

@@ -51,6 +51,8 @@ SYMBOLS = [
     "rsn_huffman_plan", "rsn_huffman_parse_header", "rsn_huffman_slice_cuts",
     "rsn_layers_compress", "rsn_layers_decompress", "rsn_layers_compress_dev", "rsn_layers_decompress_dev", "rsn_layers_roundtrip",
     "rsn_prof_copied",
+    "rsn_arithmetic_compress_bound", "rsn_arithmetic_compress", "rsn_arithmetic_decompress",
+    "rsn_arithmetic_compress_batch", "rsn_arithmetic_decompress_batch", "rsn_arithmetic_compress_dev", "rsn_arithmetic_decompress_dev",
 ]
 
 
@@ -84,7 +86,7 @@ def lib():
     L.rsn_free.argtypes = [vp]
     L.rsn_free.restype = None
     L.rsn_device_set.argtypes = [ctypes.c_int]
-    for name in ("rsn_huffman_compress", "rsn_huffman_decompress", "rsn_lzss_decompress"):
+    for name in ("rsn_huffman_compress", "rsn_huffman_decompress", "rsn_lzss_decompress", "rsn_arithmetic_compress", "rsn_arithmetic_decompress"):
         getattr(L, name).argtypes = [ctypes.c_char_p, sz, ctypes.POINTER(u8p), szp]
     L.rsn_lzss_compress.argtypes = [ctypes.c_char_p, sz, ctypes.c_int64, ctypes.POINTER(u8p), szp]
     L.rsn_lzss_compress_legacy.argtypes = [ctypes.c_char_p, sz, ctypes.c_int64, ctypes.POINTER(u8p), szp]
@@ -92,7 +94,9 @@ def lib():
     L.rsn_huffman_compress_bound.restype = sz
     L.rsn_lzss_compress_bound.argtypes = [sz]
     L.rsn_lzss_compress_bound.restype = sz
-    for name in ("rsn_huffman_compress_dev", "rsn_huffman_decompress_dev", "rsn_lzss_decompress_dev"):
+    L.rsn_arithmetic_compress_bound.argtypes = [sz]
+    L.rsn_arithmetic_compress_bound.restype = sz
+    for name in ("rsn_huffman_compress_dev", "rsn_huffman_decompress_dev", "rsn_lzss_decompress_dev", "rsn_arithmetic_compress_dev", "rsn_arithmetic_decompress_dev"):
         getattr(L, name).argtypes = [vp, sz, vp, sz, szp, vp]
     L.rsn_lzss_compress_dev.argtypes = [vp, sz, ctypes.c_int64, vp, sz, szp, vp]
     L.rsn_prof_enable.argtypes = [ctypes.c_int]
@@ -110,6 +114,8 @@ def lib():
     L.rsn_huffman_compress_sharded.argtypes = [ctypes.c_char_p, sz, ctypes.c_int, ctypes.POINTER(u8p), szp]
     L.rsn_huffman_compress_batch.argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.POINTER(u8p), szp]
     L.rsn_huffman_decompress_batch.argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.POINTER(u8p), szp]
+    for name in ("rsn_arithmetic_compress_batch", "rsn_arithmetic_decompress_batch"):
+        getattr(L, name).argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.POINTER(u8p), szp]
     L.rsn_lzss_compress_batch.argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.c_int64, ctypes.POINTER(u8p), szp]
     L.rsn_lzss_decompress_batch.argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ctypes.POINTER(u8p), szp]
     ip = ctypes.POINTER(ctypes.c_int)

@@ -81,6 +81,20 @@ int lzss_decode_sliced(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uin
 int byte_hist256_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, unsigned long long *d_hist);
 int bytes_differ_dev(Ctx &c, hipStream_t s, const uint8_t *d_a, const uint8_t *d_b, size_t n, unsigned long long *d_first);
 
+// ---- the adaptive arithmetic codec (arith.hip): one wave per member, in slices of at most ARITH_SLICE_SYMBOLS symbols a launch
+// (mirrored as raisin_amd.arithmetic.SLICE_SYMBOLS).  One member is one wave's serial work, so its size is limited:
+// ARITH_MAX_BYTES of input to the encoder and of output from the decoder, RSN_ERR_LIMIT beyond.
+constexpr uint32_t ARITH_SLICE_SYMBOLS = 65536;
+constexpr size_t ARITH_MAX_BYTES = RSN_ARITH_MAX_BYTES;
+size_t arith_compress_bound(size_t n);
+// the members `idx` of a batch (the single call: a batch of one) through the two kernels, in groups, on the thread's own stream; take(i, p,
+// len) receives member i's result.  A failure returns the lowest failing member's code with *failed = that member.
+int arith_compress_members(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, const SmallTake &take, size_t *failed);
+int arith_decompress_members(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, const SmallTake &take, size_t *failed);
+// device buffers, under the contract of the four at the top; out_cap == the exact size is taken, and *out_n on RSN_ERR_CAPACITY is it
+int arith_encode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t out_cap, size_t *out_n);
+int arith_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t out_cap, size_t *out_n);
+
 // exclusive scan of n counts on the stream (huff_encode.hip); *total (may be null) receives the sum; in and out must not overlap
 int scan_u64(Ctx &c, hipStream_t s, const char *name, const unsigned long long *in, unsigned long long *out, uint32_t n, unsigned long long *total);
 

@@ -1241,6 +1241,52 @@ static int rsn_lzss_decompress_batch_impl(size_t n, const uint8_t *const *ins, c
                        [&](size_t i, bool small) { return rsn_lzss_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small); });
 }
 
+// ---- the arithmetic codec (arith.hip): the single call is a batch of one -- every member goes through the same two kernels
+static int arithmetic_batch(bool enc, size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
+    Ctx &c = ctx();
+    if (n == 0) return RSN_OK;
+    if (!ins || !lens || !outs || !out_lens) return c.fail(RSN_ERR_ARG, "null argument");
+    for (size_t i = 0; i < n; i++) { outs[i] = nullptr; out_lens[i] = 0; }
+    for (size_t i = 0; i < n; i++) if (!ins[i] && lens[i]) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
+    int rc = ctx_init(c); if (rc) return rc;                              // (no device: RSN_ERR_DEVICE -- there is no CPU path)
+    std::vector<size_t> idx(n);
+    for (size_t i = 0; i < n; i++) idx[i] = i;
+    const SmallTake take = [&](size_t i, const uint8_t *p, size_t len) -> int {
+        uint8_t *r = (uint8_t *)result_alloc(len);
+        if (!r) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", len);
+        memcpy(r, p, len);
+        outs[i] = r; out_lens[i] = len;
+        return RSN_OK;
+    };
+    size_t failed = 0;
+    rc = enc ? arith_compress_members(c, idx, ins, lens, take, &failed) : arith_decompress_members(c, idx, ins, lens, take, &failed);
+    if (rc == RSN_OK) return RSN_OK;
+    for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
+    const std::string m = c.err;
+    return c.fail(rc, "member %zu: %s", failed, m.c_str());
+}
+static int arithmetic_single(bool enc, const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
+    Ctx &c = ctx();
+    if (!out || !out_n || (!in && n)) return c.fail(RSN_ERR_ARG, "null argument");
+    *out = nullptr; *out_n = 0;
+    static const uint8_t none = 0;
+    const uint8_t *ins[1] = {in ? in : &none};
+    const int rc = arithmetic_batch(enc, 1, ins, &n, out, out_n);
+    if (rc != RSN_OK && !c.err.compare(0, 10, "member 0: ")) c.err.erase(0, 10);
+    return rc;
+}
+static int arithmetic_dev(bool enc, const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) {
+    Ctx &c = ctx(); hipStream_t s;
+    if ((!d_in && n) || !out_n) return c.fail(RSN_ERR_ARG, "null argument");
+    if (!d_out) out_cap = 0;                                              // the size query (rsn.h)
+    if (ranges_overlap(d_in, n, d_out, out_cap)) return c.fail(RSN_ERR_ARG, "input and output ranges overlap");
+    if (((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 15)) return c.fail(RSN_ERR_ARG, "arithmetic: device buffers must be 16-byte aligned");
+    int rc = dev_prologue(c, stream, &s); if (rc) return rc;
+    return enc ? arith_encode_dev(c, s, (const uint8_t *)d_in, n, (uint8_t *)d_out, out_cap, out_n)
+               : arith_decode_dev(c, s, (const uint8_t *)d_in, n, (uint8_t *)d_out, out_cap, out_n);
+}
+size_t rsn_arithmetic_compress_bound(size_t n) { return arith_compress_bound(n); }
+
 static int rsn_huffman_compress_sharded_impl(const uint8_t *in, size_t n, int shards, uint8_t **out, size_t *out_n) {
     Ctx &c = ctx();
     if (!out || !out_n || (!in && n)) return c.fail(RSN_ERR_ARG, "null argument");
@@ -1727,6 +1773,26 @@ int rsn_lzss_decompress_batch(size_t n, const uint8_t *const *ins, const size_t 
         return boundary_error(code, m);
     });
 }
+int rsn_arithmetic_compress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
+    return guarded_call<int>([&] { return arithmetic_single(true, in, n, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
+}
+int rsn_arithmetic_decompress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
+    return guarded_call<int>([&] { return arithmetic_single(false, in, n, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
+}
+int rsn_arithmetic_compress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
+    return guarded_call<int>([&] { return arithmetic_batch(true, n, ins, lens, outs, out_lens); }, [&](int code, const char *m) {
+        if (outs && out_lens) for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
+        return boundary_error(code, m);
+    });
+}
+int rsn_arithmetic_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
+    return guarded_call<int>([&] { return arithmetic_batch(false, n, ins, lens, outs, out_lens); }, [&](int code, const char *m) {
+        if (outs && out_lens) for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
+        return boundary_error(code, m);
+    });
+}
+int rsn_arithmetic_compress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded_call<int>([&] { return arithmetic_dev(true, d_in, n, d_out, out_cap, out_n, stream); }, boundary_error); }
+int rsn_arithmetic_decompress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded_call<int>([&] { return arithmetic_dev(false, d_in, n, d_out, out_cap, out_n, stream); }, boundary_error); }
 int rsn_huffman_compress_sharded(const uint8_t *in, size_t n, int shards, uint8_t **out, size_t *out_n) {
     return guarded_call<int>([&] { return rsn_huffman_compress_sharded_impl(in, n, shards, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
 }

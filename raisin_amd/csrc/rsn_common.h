@@ -75,6 +75,9 @@ enum class Slot : int {
     L_A = 40,           // layered calls: the stream between the layers ... [layered]
     L_B = 41,           // ... the two taking turns [layered]
     L_STAT = 42,        // layered round trip: the two histograms and the first-difference word [layered]
+    AR_STATE = 43,      // arithmetic codec: the members' state records (table, coder state, cursors), their summaries, sizes and offsets [arith]
+    AR_RAW = 44,        // arithmetic codec: the encoder's raw bits before the front pad (a device-buffer call: its descriptor in front);
+                        //   the decoder's descriptors [arith]
 };
 constexpr int RING = 3;                                                  // the batch pipeline's depth: RING inputs, RING segments
 constexpr Slot ring_in(int r) { return (Slot)((int)Slot::RING_IN0 + r); }
@@ -97,11 +100,14 @@ constexpr unsigned long long LAYERED = slot_mask(S::L_IN, S::L_A, S::L_B, S::L_S
 constexpr unsigned long long RINGS = slot_mask(ring_in(0), ring_in(1), ring_in(2), ring_out(0), ring_out(1), ring_out(2));
 constexpr unsigned long long HOST_CALL = STAGING | LZSS_ENC;              // (the decoder's set lies inside the encoder's)
 constexpr unsigned long long LAYERED_CALL = HOST_CALL | LAYERED;
+constexpr unsigned long long ARITH = slot_mask(S::AR_STATE, S::AR_RAW);   // the arithmetic codec's own: what its device-buffer calls' gate gives back
+constexpr unsigned long long ARITH_HOST = STAGING | ARITH;                // ... and its host-buffer calls', which stage through the staging pair
 // (RING is written out three times: the enumerators, RINGS and this check change together)
 static_assert(ring_in(RING) == Slot::RING_OUT0 && ring_out(RING - 1) == Slot::RING_OUT2, "the ring's slots are RING inputs, then RING segments");
 static_assert(((STAGING | RINGS | LAYERED) & (LZSS_ENC | LZSS_DEC)) == 0, "a codec's gate releases no staging, ring or layered slot: their callers still use them");
 static_assert(((STAGING | LAYERED) & (HUFF_OWN | LZSS_ENC_OWN | LZSS_DEC_OWN)) == 0, "no codec allocates a staging or a layered slot");
 static_assert((LZSS_DEC & ~LZSS_ENC) == 0, "HOST_CALL covers both LZSS directions");
+static_assert((ARITH & (HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED)) == 0, "the arithmetic codec shares no slot of its own with another codec or a caller");
 }  // namespace slotset
 
 // One per host thread (thread_local): device, stream, reusable device scratch
@@ -117,7 +123,7 @@ struct Ctx {
     std::vector<hipEvent_t> free_events;
 
     struct Buf { void *p = nullptr; size_t cap = 0; unsigned long long gen = 0; };   // gen: process-unique number of this allocation (dev_buf) -- an address can come back with other contents
-    enum { N_BUFS = (int)Slot::L_STAT + 1 };   // (the table above)
+    enum { N_BUFS = (int)Slot::AR_RAW + 1 };   // (the table above)
     Buf bufs[N_BUFS];
     Buf &buf(Slot k) { return bufs[(int)k]; }
     void *pinned = nullptr; size_t pinned_cap = 0;
