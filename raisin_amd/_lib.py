@@ -177,6 +177,47 @@ def call_dev(fn, d_in, n, d_out, cap, stream, *extra):
     return got.value
 
 
+class Writer:
+    """The reference's whole-buffer io.WriteCloser: Write compresses the buffer once with `compress` and returns len(compressed)."""
+
+    def __init__(self, w, compress):
+        self.w = w
+        self._compress = compress
+
+    def Write(self, data):
+        compressed = self._compress(data)
+        self.w.write(compressed)
+        return len(compressed)
+
+    write = Write
+
+    def Close(self):
+        return None
+
+    close = Close
+
+
+class Reader:
+    """The reference's io.Reader: the first Read drains the source and decompresses everything with `decompress`."""
+
+    def __init__(self, r, decompress):
+        self.r = r
+        self._decompress = decompress
+        self.decompressed = None
+        self.pos = 0
+
+    def Read(self, size=-1):
+        if self.decompressed is None:
+            self.decompressed = self._decompress(self.r.read())
+        if size is None or size < 0:
+            size = len(self.decompressed) - self.pos
+        chunk = self.decompressed[self.pos:self.pos + size]
+        self.pos += len(chunk)
+        return chunk
+
+    read = Read
+
+
 _hip = None
 
 
@@ -257,6 +298,43 @@ def prof_copied():
     up, down = ctypes.c_uint64(0), ctypes.c_uint64(0)
     lib().rsn_prof_copied(ctypes.byref(up), ctypes.byref(down))
     return int(up.value), int(down.value)
+
+
+def dev_tensor(fn, src, out, stream, guess, *extra, retry=True, floor=0):
+    """`fn` (rsn_*_dev) over the uint8 CUDA tensor src -> a view of `out` when it was large enough, otherwise (RSN_ERR_CAPACITY: .needed is
+    a size that suffices) a view of a fresh tensor of that size, at least `floor` bytes; retry=False raises instead.  Without `out`: a
+    tensor of `guess` bytes, or with guess None the size query first (d_out NULL) -- a guess of the expansion would be a buffer of many
+    times the input, held by the view returned."""
+    import torch
+    n = src.numel()
+    st = own_stream(src, stream)
+
+    def run(to):
+        if to is None:
+            return call_dev(fn, src.data_ptr(), n, None, 0, st, *extra)
+        return call_dev(fn, src.data_ptr(), n, to.data_ptr(), to.numel(), st, *extra)
+
+    def fresh(size):
+        return torch.empty(size, dtype=torch.uint8, device=src.device)
+
+    if out is None and guess is not None:
+        out = fresh(guess)
+    if out is None:
+        try:
+            need = run(None)
+        except RsnError as e:
+            if e.code != RSN_ERR_CAPACITY:
+                raise
+            need = e.needed
+        out = fresh(max(need, 16))
+    try:
+        got = run(out)
+    except RsnError as e:
+        if e.code != RSN_ERR_CAPACITY or not retry:
+            raise
+        out = fresh(max(e.needed, floor))
+        got = run(out)
+    return out[:got]
 
 
 def own_stream(tensor, stream=None):

@@ -35,43 +35,18 @@ def DecompressBatch(streams):
     return _lib.call_batch(_lib.lib().rsn_arithmetic_decompress_batch, streams)
 
 
-class Writer:
+class Writer(_lib.Writer):
     """arithmetic.go:312-332: Write compresses the whole buffer once and returns len(compressed)."""
 
     def __init__(self, w):
-        self.w = w
-
-    def Write(self, data):
-        compressed = Compress(data)
-        self.w.write(compressed)
-        return len(compressed)
-
-    write = Write
-
-    def Close(self):
-        return None
-
-    close = Close
+        super().__init__(w, lambda data: Compress(data))
 
 
-class Reader:
+class Reader(_lib.Reader):
     """arithmetic.go:335-370: the first Read drains the source and decompresses everything."""
 
     def __init__(self, r):
-        self.r = r
-        self.decompressed = None
-        self.pos = 0
-
-    def Read(self, size=-1):
-        if self.decompressed is None:
-            self.decompressed = Decompress(self.r.read())
-        if size is None or size < 0:
-            size = len(self.decompressed) - self.pos
-        chunk = self.decompressed[self.pos:self.pos + size]
-        self.pos += len(chunk)
-        return chunk
-
-    read = Read
+        super().__init__(r, lambda data: Decompress(data))
 
 
 def NewWriter(w):
@@ -87,37 +62,16 @@ def NewReader(r):
 
 
 # ---- device-resident form (torch tensors as plain device memory) -----------
-from ._lib import own_stream as _own_stream  # noqa: E402
-
-
 def compress_bound(n):
     return int(_lib.lib().rsn_arithmetic_compress_bound(n))
 
 
-def _dev_tensor(fn, src, out, stream, guess):
-    """`fn` over src -> a view of `out` when it was large enough, otherwise (RSN_ERR_CAPACITY: .needed is the exact size) a view of a
-    fresh tensor of that size."""
-    import torch
-    n = src.numel()
-    st = _own_stream(src, stream)
-    if out is None:
-        out = torch.empty(guess, dtype=torch.uint8, device=src.device)
-    try:
-        got = _lib.call_dev(fn, src.data_ptr(), n, out.data_ptr(), out.numel(), st)
-    except _lib.RsnError as e:
-        if e.code != _lib.RSN_ERR_CAPACITY:
-            raise
-        out = torch.empty(max(e.needed, 16), dtype=torch.uint8, device=src.device)
-        got = _lib.call_dev(fn, src.data_ptr(), n, out.data_ptr(), out.numel(), st)
-    return out[:got]
-
-
 def compress_tensor(src, out=None, stream=None):
     """src: uint8 CUDA tensor.  Returns a uint8 tensor holding the stream."""
-    return _dev_tensor(_lib.lib().rsn_arithmetic_compress_dev, src, out, stream, compress_bound(src.numel()))
+    return _lib.dev_tensor(_lib.lib().rsn_arithmetic_compress_dev, src, out, stream, compress_bound(src.numel()), floor=16)
 
 
 def decompress_tensor(src, out=None, stream=None):
     """The decoded size is not in the stream: a guess of eight times the stream first, the exact size on the second call if that was
     too small."""
-    return _dev_tensor(_lib.lib().rsn_arithmetic_decompress_dev, src, out, stream, 8 * src.numel() + 4096)
+    return _lib.dev_tensor(_lib.lib().rsn_arithmetic_decompress_dev, src, out, stream, 8 * src.numel() + 4096, floor=16)

@@ -279,11 +279,9 @@ constexpr unsigned long long RES_MAGIC = 0x52534E5F52455330ull;
 std::mutex g_pool_mu;
 std::vector<std::pair<size_t, void *>> g_pool;                    // (capacity, base)
 
-bool pool_enabled() { return true; }
-
 void *result_alloc(size_t n) {
     const size_t need = n ? n : 1;
-    if (need >= POOL_MIN && pool_enabled()) {
+    if (need >= POOL_MIN) {
         std::lock_guard<std::mutex> lk(g_pool_mu);
         size_t best = g_pool.size();
         for (size_t i = 0; i < g_pool.size(); i++)
@@ -309,7 +307,7 @@ void result_free(void *p) {
     void *base = (uint8_t *)p - RES_HDR;
     const ResHdr *h = (const ResHdr *)base;
     if (h->magic != RES_MAGIC) { fprintf(stderr, "librsn: rsn_free() of a pointer librsn did not return\n"); return; }
-    if (h->cap >= POOL_MIN && pool_enabled()) {
+    if (h->cap >= POOL_MIN) {
         std::lock_guard<std::mutex> lk(g_pool_mu);
         if (g_pool.size() < POOL_BLOCKS) { g_pool.emplace_back((size_t)h->cap, base); return; }
         size_t small = 0;                                              // keep the largest blocks
@@ -318,6 +316,73 @@ void result_free(void *p) {
     }
     ((ResHdr *)base)->magic = 0;
     free(base);
+}
+
+// ---- how a result reaches the caller.  HostBlock owns a block across the ways out of a call that can still fail; result_from_host /
+// result_from_dev are the two deliveries -- a fresh block, the bytes into it (from the device: copied down and the stream synchronised),
+// then *out / *out_n; t_alloc: the RSN_HOST_TIMING stamp between the allocation and the copy.  drop_results undoes a batch's.
+struct HostBlock { uint8_t *p = nullptr; ~HostBlock() { if (p) result_free(p); } uint8_t *release() { uint8_t *r = p; p = nullptr; return r; } };
+double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+int result_block(Ctx &c, size_t len, HostBlock &b) {
+    b.p = (uint8_t *)result_alloc(len);
+    return b.p ? RSN_OK : c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", len);
+}
+int result_from_host(Ctx &c, const void *p, size_t len, uint8_t **out, size_t *out_n) {
+    HostBlock b;
+    int rc = result_block(c, len, b); if (rc) return rc;
+    if (len) memcpy(b.p, p, len);
+    *out = b.release(); *out_n = len;
+    return RSN_OK;
+}
+int result_from_dev(Ctx &c, hipStream_t s, const void *d_src, size_t len, uint8_t **out, size_t *out_n, double *t_alloc = nullptr) {
+    HostBlock b;
+    int rc = result_block(c, len, b); if (rc) return rc;
+    if (t_alloc) *t_alloc = now_ms();
+    if (len) {
+        RSN_HIP(copy_async(b.p, d_src, len, hipMemcpyDeviceToHost, s));
+        RSN_HIP(hipStreamSynchronize(s));
+    }
+    *out = b.release(); *out_n = len;
+    return RSN_OK;
+}
+SmallTake take_into(Ctx &c, uint8_t **outs, size_t *out_lens) {
+    return [&c, outs, out_lens](size_t i, const uint8_t *p, size_t len) { return result_from_host(c, p, len, &outs[i], &out_lens[i]); };
+}
+void drop_results(size_t n, uint8_t **outs, size_t *out_lens) {
+    for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
+}
+
+// ---- the argument checks of the host-buffer forms, before a device is looked for.  host_args: one buffer, *out / *out_n zeroed once the
+// pointers are known to be there.  batch_args: the arrays, outs[] / out_lens[] zeroed, then the members in index order -- member_word:
+// the message names the member; empty_first: a batch of none is answered (RSN_OK, the caller returns too) before the arrays are looked
+// at; empty_member: what a member of length 0 fails with (RSN_ERR_EMPTY), or nullptr where it is a member like any other.
+int host_args(Ctx &c, const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
+    if (!out || !out_n || (!in && n)) return c.fail(RSN_ERR_ARG, "null argument");
+    *out = nullptr; *out_n = 0;
+    return RSN_OK;
+}
+int batch_args(Ctx &c, size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens, bool member_word, bool empty_first,
+               const char *empty_member = nullptr) {
+    if (empty_first && n == 0) return RSN_OK;
+    if (!ins || !lens || !outs || !out_lens) return c.fail(RSN_ERR_ARG, "null argument");
+    for (size_t i = 0; i < n; i++) { outs[i] = nullptr; out_lens[i] = 0; }
+    for (size_t i = 0; i < n; i++) {
+        if (!ins[i] && lens[i]) return member_word ? c.fail(RSN_ERR_ARG, "member %zu: null argument", i) : c.fail(RSN_ERR_ARG, "null argument");
+        if (empty_member && lens[i] == 0) return c.fail(RSN_ERR_EMPTY, "%s", empty_member);
+    }
+    return RSN_OK;
+}
+
+// ---- what a helper thread leaves for the thread that waits for it: the FIRST failure's code and text.  The pipes and the barrier below
+// hold their shared state under `mu` and wake their waiters through `cv`.  on_helper: what runs ON a helper -- an exception there (a
+// vector that cannot grow) fails P at once, and the other stages, which wait on P, end.
+struct FirstFailure {
+    std::mutex mu; std::condition_variable cv;
+    int rc = RSN_OK; std::string msg;
+    void fail(int code, const char *m) noexcept { try { std::lock_guard<std::mutex> lk(mu); if (rc == RSN_OK) { rc = code; try { msg = m; } catch (...) {} } } catch (...) {} cv.notify_all(); }
+};
+template <class Body> auto on_helper(FirstFailure &P, Body body) {
+    return [&P, body] { guarded_call<int>([&] { body(); return 0; }, [&](int code, const char *m) { P.fail(code, m); return 0; }); };
 }
 
 // ---- the caller's INPUT memory, registered in place for the pipelined calls, under a process-wide table (r06).  The input is borrowed and
@@ -413,18 +478,16 @@ int stage_input(Ctx &c, hipStream_t s, Slot slot, const uint8_t *in, size_t n, v
 template <class Fn>
 int host_call(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n, size_t bound, size_t codec_need, Fn fn) {
     Ctx &c = ctx();
-    if (!out || !out_n || (!in && n)) return c.fail(RSN_ERR_ARG, "null argument");
-    *out = nullptr; *out_n = 0;
-    int rc = ctx_init(c); if (rc) return rc;
+    int rc = host_args(c, in, n, out, out_n); if (rc) return rc;
+    rc = ctx_init(c); if (rc) return rc;
     hipStream_t s = c.own_stream;
     Admission gate(c, slotset::HOST_CALL); gate.admit(round_up(n, 16) + 64 + bound + bound / 8 + codec_need, ADMIT_FROM);
     static const bool timing = getenv("RSN_HOST_TIMING") != nullptr;
-    auto stamp = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_in = timing ? stamp() : 0;
+    const double t_in = timing ? now_ms() : 0;
     void *d_in, *d_out;
     rc = stage_input(c, s, Slot::STAGE_IN, in, n, &d_in); if (rc) return rc;
     if (timing) RSN_HIP(hipStreamSynchronize(s));
-    const double t_up = timing ? stamp() : 0;
+    const double t_up = timing ? now_ms() : 0;
     size_t cap = bound, got = 0;
     for (int attempt = 0;; attempt++) {
         rc = dev_buf(c, Slot::STAGE_OUT, cap, &d_out); if (rc) return rc;
@@ -434,18 +497,12 @@ int host_call(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n, size_t 
     }
     if (rc) return rc;
     if (timing) RSN_HIP(hipStreamSynchronize(s));
-    const double t_codec = timing ? stamp() : 0;
-    uint8_t *res = (uint8_t *)result_alloc(got);
-    if (!res) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", got);
-    const double t_alloc = timing ? stamp() : 0;
-    if (got) {
-        RSN_HIP(copy_async(res, d_out, got, hipMemcpyDeviceToHost, s));
-        RSN_HIP(hipStreamSynchronize(s));
-    }
+    const double t_codec = timing ? now_ms() : 0;
+    double t_alloc = 0;
+    rc = result_from_dev(c, s, d_out, got, out, out_n, timing ? &t_alloc : nullptr); if (rc) return rc;
     if (timing)
         fprintf(stderr, "host call %p: in at %.2f ms, %zu B up by +%.2f, codec +%.2f, result block +%.2f, %zu B down +%.2f\n", (void *)&c,
-                fmod(t_in, 100000.0), n, t_up - t_in, t_codec - t_up, t_alloc - t_codec, got, stamp() - t_alloc);
-    *out = res; *out_n = got;
+                fmod(t_in, 100000.0), n, t_up - t_in, t_codec - t_up, t_alloc - t_codec, got, now_ms() - t_alloc);
     return RSN_OK;
 }
 
@@ -475,19 +532,17 @@ static int piped_call(const uint8_t *in, size_t n, size_t out_cap, size_t codec_
     void *d_in, *d_out;
     rc = stage_buf(c, s, Slot::STAGE_IN, n, &d_in); if (rc) return rc;               // (the uploader below sends the bytes)
     rc = dev_buf(c, Slot::STAGE_OUT, round_up(out_cap, 16) + 64, &d_out); if (rc) return rc;
-    uint8_t *res = (uint8_t *)result_alloc(out_cap);
-    if (!res) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", out_cap);
+    HostBlock block;                                                      // (allocated here, not by a result helper: it must exist before the codec runs)
+    rc = result_block(c, out_cap, block); if (rc) return rc;
+    uint8_t *const res = block.p;
     RSN_HIP(hipStreamSynchronize(s));                                     // (the zeroed tail, before the uploader's first piece lands on the same bytes)
 
-    struct Pipe {
-        std::mutex mu; std::condition_variable cv;
+    struct Pipe : FirstFailure {                                          // (rc: a failed transfer is RSN_ERR_DEVICE, a failed codec its own code)
         size_t uploaded = 0;                                              // bytes of the stream on the device
         std::vector<std::pair<size_t, size_t>> ready;                     // decoded ranges not yet asked for by the downloader
-        size_t taken = 0; bool decoded_all = false, failed = false; std::string msg;
-        void fail(const char *m) noexcept { try { std::lock_guard<std::mutex> lk(mu); if (!failed) { failed = true; try { msg = m; } catch (...) {} } } catch (...) {} cv.notify_all(); }
+        size_t taken = 0; bool decoded_all = false;
+        bool failed() const { return rc != RSN_OK; }                      // (under mu, or once the helpers have ended)
     } P;
-    // what runs on a helper: an exception there (a vector that cannot grow) fails the pipe at once -- the other stages wait on P
-    auto stage = [&P](auto body) { return [&P, body] { guarded_call<int>([&] { body(); return 0; }, [&](int, const char *m) { P.fail(m); return 0; }); }; };
     const int device = c.device;
     static const bool timing = getenv("RSN_HOST_TIMING") != nullptr;
     const auto t_start = std::chrono::steady_clock::now();
@@ -495,8 +550,8 @@ static int piped_call(const uint8_t *in, size_t n, size_t out_cap, size_t codec_
     std::vector<PinHold> in_pinned((n + PIECE - 1) / PIECE + 2);         // the input's pieces: registered or shared through the table above (released below)
     // Both helpers come from the pool (rsn_helpers.h): no thread and no stream is created once a first call has run, and "no thread to be
     // had" is an answer, not an exception -- the caller then takes the serial call.
-    HelperPool::Handle uploader = HelperPool::run(device, stage([&] {
-        if (rsn_device_set(device) != RSN_OK) { P.fail(rsn_last_error()); return; }
+    HelperPool::Handle uploader = HelperPool::run(device, on_helper(P, [&] {
+        if (rsn_device_set(device) != RSN_OK) { P.fail(RSN_ERR_DEVICE, rsn_last_error()); return; }
         hipStream_t su = ctx().own_stream;
         std::vector<PinHold> &pinned = in_pinned;
         auto pin = [&](size_t k) { const size_t lo = cut(in, n, k), hi = cut(in, n, k + 1); if (hi > lo) pin_acquire(in + lo, hi - lo, true, pinned[k]); };
@@ -506,15 +561,15 @@ static int piped_call(const uint8_t *in, size_t n, size_t out_cap, size_t codec_
             hipError_t e = copy_up((uint8_t *)d_in + lo, in + lo, hi - lo, su, pinned[k]);
             if (e == hipSuccess && hi < n) pin(k + 1);                        // (under this piece's copy)
             if (e == hipSuccess) e = hipStreamSynchronize(su);
-            if (e != hipSuccess) { P.fail(hipGetErrorString(e)); return; }
-            { std::lock_guard<std::mutex> lk(P.mu); if (P.failed) return; P.uploaded = hi; }
+            if (e != hipSuccess) { P.fail(RSN_ERR_DEVICE, hipGetErrorString(e)); return; }
+            { std::lock_guard<std::mutex> lk(P.mu); if (P.failed()) return; P.uploaded = hi; }
             P.cv.notify_all();
         }
         if (timing) { size_t np_ = 0; for (const PinHold &x : pinned) np_ += x.registered; fprintf(stderr, "piped call: %zu B up by +%.2f ms (%zu pieces registered)\n", n, since(), np_); }
     }));
-    if (!uploader) { result_free(res); return 1; }
-    HelperPool::Handle downloader = HelperPool::run(device, stage([&] {
-        if (rsn_device_set(device) != RSN_OK) { P.fail(rsn_last_error()); return; }
+    if (!uploader) return 1;
+    HelperPool::Handle downloader = HelperPool::run(device, on_helper(P, [&] {
+        if (rsn_device_set(device) != RSN_OK) { P.fail(RSN_ERR_DEVICE, rsn_last_error()); return; }
         hipStream_t sd = ctx().own_stream;
         const size_t total_out = out_cap;
         std::vector<char> pinned((total_out + PIECE - 1) / PIECE + 1, 0);
@@ -523,8 +578,8 @@ static int piped_call(const uint8_t *in, size_t n, size_t out_cap, size_t codec_
             std::pair<size_t, size_t> r;
             {
                 std::unique_lock<std::mutex> lk(P.mu);
-                P.cv.wait(lk, [&] { return P.failed || P.taken < P.ready.size() || P.decoded_all; });
-                if (P.failed || P.taken >= P.ready.size()) break;
+                P.cv.wait(lk, [&] { return P.failed() || P.taken < P.ready.size() || P.decoded_all; });
+                if (P.failed() || P.taken >= P.ready.size()) break;
                 r = P.ready[P.taken++];
             }
             if (!r.second) continue;
@@ -547,27 +602,26 @@ static int piped_call(const uint8_t *in, size_t n, size_t out_cap, size_t codec_
             }
             if (e == hipSuccess) pin_below(r.first + 2 * r.second);            // under these copies: where the next range will land
             if (e == hipSuccess) e = hipStreamSynchronize(sd);
-            if (e != hipSuccess) { P.fail(hipGetErrorString(e)); break; }
+            if (e != hipSuccess) { P.fail(RSN_ERR_DEVICE, hipGetErrorString(e)); break; }
             if (timing) fprintf(stderr, "piped call: [%zu, +%zu) down by +%.2f ms\n", r.first, r.second, since());
         }
         if (timing) { size_t np_ = 0; for (size_t k = 0; k < next_pin; k++) np_ += pinned[k] != 0; fprintf(stderr, "piped call: %zu of %zu pieces of the result registered\n", np_, next_pin); }
         for (size_t k = 0; k < next_pin; k++) if (pinned[k]) (void)hipHostUnregister(res + cut(res, total_out, k));
     }));
     if (!downloader) {                                                    // (the uploader is at work on P and d_in: it ends before they do)
-        P.fail("no helper thread for the downloads");
+        P.fail(RSN_ERR_NOMEM, "no helper thread for the downloads");
         HelperPool::wait(uploader);
         (void)hipSetDevice(c.device);
         for (PinHold &x : in_pinned) pin_release(x);
-        result_free(res);
         return 1;
     }
     SliceStream st;
     st.slice_bytes = (size_t)64 << 20;
-    st.need_in = [&](size_t bytes) { std::unique_lock<std::mutex> lk(P.mu); P.cv.wait(lk, [&] { return P.failed || P.uploaded >= std::min(bytes, n); }); return !P.failed; };
+    st.need_in = [&](size_t bytes) { std::unique_lock<std::mutex> lk(P.mu); P.cv.wait(lk, [&] { return P.failed() || P.uploaded >= std::min(bytes, n); }); return !P.failed(); };
     st.in_so_far = [&] { std::lock_guard<std::mutex> lk(P.mu); return P.uploaded; };
     st.have_out = [&](size_t off, size_t len) {
         if (timing) fprintf(stderr, "piped call: [%zu, +%zu) decoded by +%.2f ms\n", off, len, since());
-        { std::lock_guard<std::mutex> lk(P.mu); if (P.failed) return false; P.ready.emplace_back(off, len); }
+        { std::lock_guard<std::mutex> lk(P.mu); if (P.failed()) return false; P.ready.emplace_back(off, len); }
         P.cv.notify_all();
         return true;
     };
@@ -575,7 +629,7 @@ static int piped_call(const uint8_t *in, size_t n, size_t out_cap, size_t codec_
     // (an exception out of the codec -- a vector that cannot grow -- must not unwind this frame while the helpers work on it)
     rc = guarded_call<int>([&] { return run(c, s, (const uint8_t *)d_in, (uint8_t *)d_out, out_cap, &got, &st); },
                            [&](int code, const char *m) { try { c.err = m; } catch (...) {} return code; });
-    if (rc != RSN_OK) P.fail(c.err.c_str());                              // (stops both helpers)
+    if (rc != RSN_OK) P.fail(rc, c.err.c_str());                          // (stops both helpers)
     { std::lock_guard<std::mutex> lk(P.mu); P.decoded_all = true; }
     P.cv.notify_all();
     HelperPool::wait(uploader);
@@ -583,11 +637,11 @@ static int piped_call(const uint8_t *in, size_t n, size_t out_cap, size_t codec_
     (void)hipSetDevice(c.device);
     for (PinHold &x : in_pinned) pin_release(x);
     if (timing) fprintf(stderr, "piped call: the codec returned %d (%s) at +%.2f ms\n", rc, rc > 0 || rc == RSN_OK ? "" : c.err.c_str(), since());
-    if (rc == RSN_ERR_CAPACITY || rc == 1) { result_free(res); return 1; }   // more output than the caller allowed for, or not a stream for slices: the serial call
-    if (rc != RSN_OK && P.failed && P.msg != c.err) { result_free(res); return c.fail(rc, "%s (%s)", std::string(c.err).c_str(), P.msg.c_str()); }
-    if (rc != RSN_OK) { result_free(res); return rc; }
-    if (P.failed) { result_free(res); return c.fail(RSN_ERR_DEVICE, "a transfer of the pipelined call failed: %s", P.msg.c_str()); }
-    *out = res; *out_n = got;
+    if (rc == RSN_ERR_CAPACITY || rc == 1) return 1;                      // more output than the caller allowed for, or not a stream for slices: the serial call
+    if (rc != RSN_OK && P.msg != c.err) return c.fail(rc, "%s (%s)", std::string(c.err).c_str(), P.msg.c_str());
+    if (rc != RSN_OK) return rc;
+    if (P.failed()) return c.fail(RSN_ERR_DEVICE, "a transfer of the pipelined call failed: %s", P.msg.c_str());
+    *out = block.release(); *out_n = got;
     return RSN_OK;
 }
 
@@ -602,6 +656,45 @@ int dev_prologue(Ctx &c, void *stream, hipStream_t *s) {
     int rc = ctx_init(c); if (rc) return rc;
     *s = stream ? (hipStream_t)stream : c.own_stream;
     return RSN_OK;
+}
+
+// The argument checks of the device-buffer form, then the context and the stream.  The calls differ in three rules, each as rsn.h states it:
+// null_empty: a NULL d_in is an argument error only with a length (the Huffman calls refuse it with none, too); size_query: a NULL d_out
+// makes out_cap count as 0 (the codec answers the size before it writes a byte); align: both buffers on 16-byte boundaries, the word in
+// front of the message.
+struct DevRules { bool null_empty, size_query; const char *align; };
+int dev_args(Ctx &c, const DevRules &r, const void *d_in, size_t n, void *d_out, size_t *out_cap, size_t *out_n, void *stream, hipStream_t *s) {
+    if ((!d_in && (n || !r.null_empty)) || !out_n) return c.fail(RSN_ERR_ARG, "null argument");
+    if (r.size_query && !d_out) *out_cap = 0;
+    if (ranges_overlap(d_in, n, d_out, *out_cap)) return c.fail(RSN_ERR_ARG, "input and output ranges overlap");
+    if (r.align && (((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 15))) return c.fail(RSN_ERR_ARG, "%s: device buffers must be 16-byte aligned", r.align);
+    return dev_prologue(c, stream, s);
+}
+
+// ---- the layers' codecs, one row per (RSN_LAYER_*, direction): what the serial host call gives the codec -- the output buffer's first
+// size (typical outputs are smaller; the exact need comes back on RSN_ERR_CAPACITY) and the codec's own statement of scratch for the
+// admission -- the codec on device buffers (window: the LZSS encoder's, ignored by the rest), the device-buffer call's argument rules, and
+// the whole host-buffer call at the layers' window.  The single calls, the batch pipeline and the layered calls all read these rows, so a
+// layered call admits and allocates what the chain of single calls does.  (The arithmetic codec is not a layer: arith.hip sizes itself.)
+struct Codec {
+    size_t (*cap)(size_t n);
+    size_t (*scratch)(size_t n);
+    int (*dev)(Ctx &c, hipStream_t s, const uint8_t *di, size_t n, int64_t window, uint8_t *dout, size_t cap, size_t *got);
+    DevRules rules;
+    int (*host)(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n);
+};
+const Codec &codec(int id, bool enc);
+
+// the serial host-buffer call of a row: host_call around its codec
+int host_codec(const Codec &k, const uint8_t *in, size_t n, int64_t window, uint8_t **out, size_t *out_n) {
+    return host_call(in, n, out, out_n, k.cap(n), k.scratch(n),
+                     [&k, n, window](Ctx &c, hipStream_t s, const uint8_t *di, uint8_t *dout, size_t cap, size_t *got) { return k.dev(c, s, di, n, window, dout, cap, got); });
+}
+// ... and its device-buffer call
+int dev_codec(const Codec &k, const void *d_in, size_t n, int64_t window, void *d_out, size_t out_cap, size_t *out_n, void *stream) {
+    Ctx &c = ctx(); hipStream_t s;
+    int rc = dev_args(c, k.rules, d_in, n, d_out, &out_cap, out_n, stream, &s); if (rc) return rc;
+    return k.dev(c, s, (const uint8_t *)d_in, n, window, (uint8_t *)d_out, out_cap, out_n);
 }
 
 }  // namespace
@@ -658,65 +751,19 @@ static void rsn_trim_impl(void) {
     }
     for (auto &pr : pool) { ((ResHdr *)pr.second)->magic = 0; free(pr.second); }
 }
-static void rsn_free_impl(void *p) { result_free(p); }
-
 size_t rsn_huffman_compress_bound(size_t n) { return huff_compress_bound(n); }
 size_t rsn_lzss_compress_bound(size_t n) { return lzss_compress_bound(n); }
 
-static int rsn_huffman_compress_dev_impl(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) {
-    Ctx &c = ctx(); hipStream_t s;
-    if (!d_in || !out_n) return c.fail(RSN_ERR_ARG, "null argument");
-    if (!d_out) out_cap = 0;                                              // the size query (rsn.h): the encoder answers it before it writes a byte
-    if (ranges_overlap(d_in, n, d_out, out_cap)) return c.fail(RSN_ERR_ARG, "input and output ranges overlap");
-    int rc = dev_prologue(c, stream, &s); if (rc) return rc;
-    return huff_encode_dev(c, s, (const uint8_t *)d_in, n, (uint8_t *)d_out, out_cap, out_n, nullptr, nullptr);
-}
-
-static int rsn_huffman_decompress_dev_impl(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) {
-    Ctx &c = ctx(); hipStream_t s;
-    if (!d_in || !out_n) return c.fail(RSN_ERR_ARG, "null argument");
-    if (ranges_overlap(d_in, n, d_out, out_cap)) return c.fail(RSN_ERR_ARG, "input and output ranges overlap");
-    int rc = dev_prologue(c, stream, &s); if (rc) return rc;
-    return huff_decode_dev(c, s, (const uint8_t *)d_in, n, (uint8_t *)d_out, out_cap, out_n);
-}
-
-static int rsn_lzss_compress_dev_impl(const void *d_in, size_t n, int64_t window, void *d_out, size_t out_cap, size_t *out_n, void *stream) {
-    Ctx &c = ctx(); hipStream_t s;
-    if ((!d_in && n) || !out_n) return c.fail(RSN_ERR_ARG, "null argument");
-    if (!d_out) out_cap = 0;                                              // the size query (rsn.h): every emit pass runs behind the capacity check
-    if (ranges_overlap(d_in, n, d_out, out_cap)) return c.fail(RSN_ERR_ARG, "input and output ranges overlap");
-    int rc = dev_prologue(c, stream, &s); if (rc) return rc;
-    return lzss_encode_dev(c, s, (const uint8_t *)d_in, n, window, (uint8_t *)d_out, out_cap, out_n);
-}
-
-static int rsn_lzss_decompress_dev_impl(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) {
-    Ctx &c = ctx(); hipStream_t s;
-    if ((!d_in && n) || !out_n) return c.fail(RSN_ERR_ARG, "null argument");
-    if (ranges_overlap(d_in, n, d_out, out_cap)) return c.fail(RSN_ERR_ARG, "input and output ranges overlap");
-    int rc = dev_prologue(c, stream, &s); if (rc) return rc;
-    return lzss_decode_dev(c, s, (const uint8_t *)d_in, n, (uint8_t *)d_out, out_cap, out_n);
-}
-
-static int huffman_compress_single(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
-    // typical outputs are < n; the exact need is reported back on RSN_ERR_CAPACITY
-    return host_call(in, n, out, out_n, n + n / 8 + (1 << 16), n / 32,
-                     [n](Ctx &c, hipStream_t s, const uint8_t *di, uint8_t *dout, size_t cap, size_t *got) {
-                         return huff_encode_dev(c, s, di, n, dout, cap, got, nullptr, nullptr);
-                     });
-}
+static const char *const HUFF_EMPTY = "huffman: empty input (reference panics in heap.Pop, huffman.go:102)";
+static int huffman_compress_single(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) { return host_codec(codec(RSN_LAYER_HUFFMAN, true), in, n, 0, out, out_n); }
 
 // the small-input codec's result (in pinned staging) into a block of the caller's; 1 stays 1
 static int small_result(Ctx &c, int rc, const uint8_t *p, size_t got, uint8_t **out, size_t *out_n) {
-    if (rc != RSN_OK) return rc;
-    uint8_t *res = (uint8_t *)result_alloc(got);
-    if (!res) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", got);
-    memcpy(res, p, got);
-    *out = res; *out_n = got;
-    return RSN_OK;
+    return rc != RSN_OK ? rc : result_from_host(c, p, got, out, out_n);
 }
 
 static int rsn_huffman_compress_impl(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
-    if (n == 0) return ctx().fail(RSN_ERR_EMPTY, "huffman: empty input (reference panics in heap.Pop, huffman.go:102)");
+    if (n == 0) return ctx().fail(RSN_ERR_EMPTY, "%s", HUFF_EMPTY);
     if (in && out && out_n && n <= 65536) {                              // (the general path for the same bytes: the device-pointer entry points, tests/test_gpu_huffman_small.py)
         Ctx &c = ctx(); const uint8_t *p = nullptr; size_t got = 0;
         const int rc = small_result(c, huff_small_compress(c, in, n, &p, &got), p, got, out, out_n);
@@ -726,13 +773,6 @@ static int rsn_huffman_compress_impl(const uint8_t *in, size_t n, uint8_t **out,
     static const int env_shards = env_int("RSN_HUFF_SHARDS", 0);
     if (env_shards > 1 && n >= ((size_t)1 << 16)) return rsn_huffman_compress_sharded(in, n, env_shards, out, out_n);
     return huffman_compress_single(in, n, out, out_n);
-}
-
-static int huffman_decompress_serial(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
-    return host_call(in, n, out, out_n, 4 * n + (1 << 16), n / 8,
-                     [n](Ctx &c, hipStream_t s, const uint8_t *di, uint8_t *dout, size_t cap, size_t *got) {
-                         return huff_decode_dev(c, s, di, n, dout, cap, got);
-                     });
 }
 
 // A large host-buffer decode as a PIPELINE (what the cgo shim binds was upload, then codec, then download -- 16 + 0.5 + 19 ms
@@ -764,7 +804,7 @@ static int huffman_decompress_piped(const uint8_t *in, size_t n, uint8_t **out, 
         expect += sy.freq * (unsigned long long)utf8_len(sy.rune);
     }
     if (expect == 0) return 1;
-    return piped_call(in, n, (size_t)expect, n / 8, out, out_n,
+    return piped_call(in, n, (size_t)expect, codec(RSN_LAYER_HUFFMAN, false).scratch(n), out, out_n,
                       [n](Ctx &c, hipStream_t s, const uint8_t *di, uint8_t *dout, size_t cap, size_t *got, const SliceStream *st) {
                           return huff_decode_dev(c, s, di, n, dout, cap, got, st);
                       });
@@ -773,8 +813,7 @@ static int huffman_decompress_piped(const uint8_t *in, size_t n, uint8_t **out, 
 // (small = false: a member the batch's grouped kernel has handed back -- the single call's small-input kernel would hand it back too)
 static int rsn_huffman_decompress_impl(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n, bool small = true) {
     Ctx &c = ctx();
-    if (!out || !out_n || (!in && n)) return c.fail(RSN_ERR_ARG, "null argument");
-    *out = nullptr; *out_n = 0;
+    int rc0 = host_args(c, in, n, out, out_n); if (rc0) return rc0;
     static const bool serial = getenv("RSN_HOST_SERIAL") != nullptr;     // A/B switch (tests): upload, decode, download, one after the other
     if (small && n <= 65536 + 2048) {
         const uint8_t *p = nullptr; size_t got = 0;
@@ -785,7 +824,7 @@ static int rsn_huffman_decompress_impl(const uint8_t *in, size_t n, uint8_t **ou
         const int rc = huffman_decompress_piped(in, n, out, out_n);
         if (rc != 1) return rc;
     }
-    return huffman_decompress_serial(in, n, out, out_n);
+    return host_codec(codec(RSN_LAYER_HUFFMAN, false), in, n, 0, out, out_n);
 }
 
 static int rsn_lzss_compress_impl(const uint8_t *in, size_t n, int64_t window, uint8_t **out, size_t *out_n, bool small = true) {
@@ -812,17 +851,12 @@ static int rsn_lzss_compress_impl(const uint8_t *in, size_t n, int64_t window, u
                                   });
         if (rc != 1) return rc;
     }
-    // (the encoder's own statement of need, lzss_encode_dev: ~13 bytes of scratch per position of a pass + the escaped stream)
-    return host_call(in, n, out, out_n, lzss_compress_bound(n), n < ((size_t)32 << 20) ? 0 : 13 * std::min(n, (size_t)3 << 29) + 2 * n,
-                     [n, window](Ctx &c, hipStream_t s, const uint8_t *di, uint8_t *dout, size_t cap, size_t *got) {
-                         return lzss_encode_dev(c, s, di, n, window, dout, cap, got);
-                     });
+    return host_codec(codec(RSN_LAYER_LZSS, true), in, n, window, out, out_n);
 }
 
 static int rsn_lzss_compress_legacy_impl(const uint8_t *in, size_t n, int64_t window, uint8_t **out, size_t *out_n) {
     Ctx &c = ctx();
-    if (!out || !out_n || (!in && n)) return c.fail(RSN_ERR_ARG, "null argument");
-    *out = nullptr; *out_n = 0;
+    int rc = host_args(c, in, n, out, out_n); if (rc) return rc;
     {   // an O(n * W) serial loop that cannot be interrupted from Go: refuse what would run for hours (rsn.h)
         static const bool no_limit = getenv("RSN_LEGACY_NO_LIMIT") != nullptr;
         const size_t bound = (window <= 0 || window > 65536) ? ((size_t)1 << 20) : ((size_t)64 << 20);
@@ -832,11 +866,7 @@ static int rsn_lzss_compress_legacy_impl(const uint8_t *in, size_t n, int64_t wi
     }
     std::string res;
     lzss_compress_legacy_host(in, n, window, res);
-    uint8_t *buf = (uint8_t *)result_alloc(res.size());
-    if (!buf) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", res.size());
-    memcpy(buf, res.data(), res.size());
-    *out = buf; *out_n = res.size();
-    return RSN_OK;
+    return result_from_host(c, res.data(), res.size(), out, out_n);
 }
 
 static int rsn_lzss_decompress_impl(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n, bool small = true) {
@@ -883,12 +913,7 @@ static int rsn_lzss_decompress_impl(const uint8_t *in, size_t n, uint8_t **out, 
             }
         }
     }
-    // (the decoder asks for 4 bytes per escaped byte from 64 MiB of them up, lzss_decode.hip: stated for an expansion of two -- text is 1.5;
-    //  a stream that expands further decodes inside this admission all the same)
-    return host_call(in, n, out, out_n, 8 * n + (1 << 16), n < ((size_t)32 << 20) ? 0 : 8 * n,
-                     [n](Ctx &c, hipStream_t s, const uint8_t *di, uint8_t *dout, size_t cap, size_t *got) {
-                         return lzss_decode_dev(c, s, di, n, dout, cap, got);
-                     });
+    return host_codec(codec(RSN_LAYER_LZSS, false), in, n, 0, out, out_n);
 }
 
 // Independent chunks, one complete .rsn segment each (engine.CompressFiles: one file per input,
@@ -906,13 +931,10 @@ static int rsn_lzss_decompress_impl(const uint8_t *in, size_t n, uint8_t **out, 
 //   RSN_BATCH_KEEP_MIB=<m> ring buffers above m MiB per worker (default 1024) are released when the batch ends instead of
 //                          staying with the worker's (parked) context for the next batch
 namespace {
-struct BatchPipe {
-    std::mutex mu; std::condition_variable cv;
+struct BatchPipe : FirstFailure {
     size_t uploaded = 0, encoded = 0, downloaded = 0;      // chunks that have left each stage
-    int rc = RSN_OK; std::string msg;
     void *d_in[RING] = {}, *d_out[RING] = {}, *d_tmp[RING] = {};
     size_t got[RING] = {};
-    void fail(int code, const char *m) noexcept { try { std::lock_guard<std::mutex> lk(mu); if (rc == RSN_OK) { rc = code; try { msg = m; } catch (...) {} } } catch (...) {} cv.notify_all(); }
     // waits until `counter` has passed `want` chunks; false when another stage failed
     bool wait(const size_t &counter, size_t want) { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return rc != RSN_OK || counter >= want; }); return rc == RSN_OK; }
     void done(size_t &counter) { { std::lock_guard<std::mutex> lk(mu); counter++; } cv.notify_all(); }
@@ -926,7 +948,7 @@ static int batch_on_device(Ctx &c, const std::vector<size_t> &idx, const uint8_t
     auto one_by_one = [&] {                                              // no pipeline: a single chunk, or no helper threads to be had
         for (size_t j = 0; j < m; j++) {
             const size_t i = idx[j];
-            if (outs[i]) { rsn_free(outs[i]); outs[i] = nullptr; out_lens[i] = 0; }
+            drop_results(1, &outs[i], &out_lens[i]);
             const int rc = rsn_huffman_compress(ins[i], lens[i], &outs[i], &out_lens[i]);
             if (rc != RSN_OK) return rc;
         }
@@ -936,17 +958,16 @@ static int batch_on_device(Ctx &c, const std::vector<size_t> &idx, const uint8_t
     size_t max_len = 0;
     for (size_t i : idx) max_len = std::max(max_len, lens[i]);
     BatchPipe P;
-    const size_t in_cap = round_up(max_len, 16) + 64, out_cap = max_len + max_len / 8 + (1 << 16);   // typical outputs are < n; a chunk that needs more gets its own block
+    const size_t in_cap = round_up(max_len, 16) + 64, out_cap = codec(RSN_LAYER_HUFFMAN, true).cap(max_len);   // (a chunk that needs more gets its own block)
     for (int r = 0; r < RING; r++) {
         int rc = dev_buf(c, ring_in(r), in_cap, &P.d_in[r]); if (rc) return rc;
         rc = dev_buf(c, ring_out(r), out_cap, &P.d_out[r]); if (rc) return rc;
     }
     const int device = c.device;
     static const bool timing = getenv("RSN_HOST_TIMING") != nullptr;
-    auto stamp = [] { return fmod(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(), 100000.0); };
+    auto stamp = [] { return fmod(now_ms(), 100000.0); };
 
-    auto stage = [&P](auto body) { return [&P, body] { guarded_call<int>([&] { body(); return 0; }, [&](int code, const char *msg) { P.fail(code, msg); return 0; }); }; };
-    HelperPool::Handle encoder = HelperPool::run(device, stage([&] {
+    HelperPool::Handle encoder = HelperPool::run(device, on_helper(P, [&] {
         if (rsn_device_set(device) != RSN_OK) { P.fail(RSN_ERR_DEVICE, rsn_last_error()); return; }
         Ctx &ce = ctx(); hipStream_t s = ce.own_stream;
         for (size_t j = 0; j < m; j++) {
@@ -967,21 +988,16 @@ static int batch_on_device(Ctx &c, const std::vector<size_t> &idx, const uint8_t
         }
     }));
     if (!encoder) return one_by_one();
-    HelperPool::Handle downloader = HelperPool::run(device, stage([&] {
+    HelperPool::Handle downloader = HelperPool::run(device, on_helper(P, [&] {
         if (rsn_device_set(device) != RSN_OK) { P.fail(RSN_ERR_DEVICE, rsn_last_error()); return; }
-        hipStream_t s = ctx().own_stream;
+        Ctx &cd = ctx(); hipStream_t s = cd.own_stream;
         for (size_t j = 0; j < m; j++) {
             if (!P.wait(P.encoded, j + 1)) return;
             const size_t i = idx[j];
             const int r = (int)(j % RING);
-            const size_t got = P.got[r];
-            uint8_t *res = (uint8_t *)result_alloc(got);
-            if (!res) { P.fail(RSN_ERR_NOMEM, "allocating a result block failed"); return; }
-            outs[i] = res; out_lens[i] = got;
-            hipError_t e = copy_async(res, P.d_tmp[r] ? P.d_tmp[r] : P.d_out[r], got, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            const int rc = result_from_dev(cd, s, P.d_tmp[r] ? P.d_tmp[r] : P.d_out[r], P.got[r], &outs[i], &out_lens[i]);
             if (P.d_tmp[r]) { (void)hipFree(P.d_tmp[r]); P.d_tmp[r] = nullptr; }
-            if (e != hipSuccess) { P.fail(RSN_ERR_DEVICE, hipGetErrorString(e)); return; }
+            if (rc != RSN_OK) { P.fail(rc, rc == RSN_ERR_NOMEM ? "allocating a result block failed" : cd.err.c_str()); return; }
             if (timing) fprintf(stderr, "batch dev %d chunk %zu down at %.2f ms\n", device, i, stamp());
             P.done(P.downloaded);
         }
@@ -1030,10 +1046,10 @@ static DealPlan deal_plan(size_t n_items) {
     d.n_workers = std::min<size_t>((size_t)std::max(1, env_int("RSN_BATCH_WORKERS", d.n_dev)), std::max<size_t>(n_items, 1));
     return d;
 }
+static int worker_device(const DealPlan &d, int base, size_t w) { return (base + (int)(w % (size_t)d.n_dev)) % d.visible; }
 template <class Work>
 static void deal_items(Ctx &c, size_t n_items, Work work, std::vector<int> &rcs, std::vector<std::string> &msgs) {
     const DealPlan d = deal_plan(n_items);
-    const int visible = d.visible, n_dev = d.n_dev;
     const size_t n_workers = d.n_workers;
     rcs.assign(n_workers, RSN_OK);
     msgs.assign(n_workers, std::string());
@@ -1048,7 +1064,7 @@ static void deal_items(Ctx &c, size_t n_items, Work work, std::vector<int> &rcs,
     const int base = c.device;
     auto share = [&](size_t w, bool own_thread) {                         // worker w's items; on the caller's thread they stay on the caller's device
         guarded_call<int>([&] {
-            int rc = own_thread ? rsn_device_set((base + (int)(w % (size_t)n_dev)) % visible) : RSN_OK;
+            int rc = own_thread ? rsn_device_set(worker_device(d, base, w)) : RSN_OK;
             if (rc == RSN_OK) {
                 std::vector<size_t> idx;
                 for (size_t k = w; k < n_items; k += n_workers) idx.push_back(k);
@@ -1059,7 +1075,7 @@ static void deal_items(Ctx &c, size_t n_items, Work work, std::vector<int> &rcs,
             return 0;
         }, [&](int code, const char *m) { rcs[w] = code; try { msgs[w] = m; } catch (...) {} return 0; });
     };
-    for (size_t w = 0; w < n_workers; w++) workers[w] = HelperPool::run((base + (int)(w % (size_t)n_dev)) % visible, [&share, w] { share(w, true); });
+    for (size_t w = 0; w < n_workers; w++) workers[w] = HelperPool::run(worker_device(d, base, w), [&share, w] { share(w, true); });
     for (size_t w = 0; w < n_workers; w++) if (!workers[w]) share(w, false);   // no thread to be had for that worker: its items on this one
     for (auto &t : workers) HelperPool::wait(t);
     (void)hipSetDevice(c.device);
@@ -1070,15 +1086,10 @@ constexpr size_t HUFF_GROUP_MIN = 2;
 
 static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
     Ctx &c = ctx();
-    if (!ins || !lens || !outs || !out_lens) return c.fail(RSN_ERR_ARG, "null argument");
-    for (size_t i = 0; i < n_chunks; i++) { outs[i] = nullptr; out_lens[i] = 0; }
-    for (size_t i = 0; i < n_chunks; i++) {
-        if (!ins[i] && lens[i]) return c.fail(RSN_ERR_ARG, "null argument");
-        if (lens[i] == 0) return c.fail(RSN_ERR_EMPTY, "huffman: empty input (reference panics in heap.Pop, huffman.go:102)");
-    }
-    int rc0 = ctx_init(c); if (rc0) return rc0;
+    int rc0 = batch_args(c, n_chunks, ins, lens, outs, out_lens, false, false, HUFF_EMPTY); if (rc0) return rc0;
+    rc0 = ctx_init(c); if (rc0) return rc0;
     auto undo = [&](int rc, const char *msg) {
-        for (size_t k = 0; k < n_chunks; k++) { if (outs[k]) rsn_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
+        drop_results(n_chunks, outs, out_lens);
         return c.fail(rc, "%s", msg);
     };
     // Members of 2 B to 16 KiB run grouped on this thread (huff_batch_compress_group: one launch of k_huff_batch_enc per group, every member
@@ -1090,13 +1101,7 @@ static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const
     if (!grouped.empty()) {
         std::vector<size_t> back;
         size_t failed = 0;
-        const SmallTake take = [&](size_t i, const uint8_t *p, size_t len) -> int {
-            uint8_t *r = (uint8_t *)result_alloc(len);
-            if (!r) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", len);
-            memcpy(r, p, len);
-            outs[i] = r; out_lens[i] = len;
-            return RSN_OK;
-        };
+        const SmallTake take = take_into(c, outs, out_lens);
         const int rc = huff_batch_compress_group(c, grouped, ins, lens, take, back, &failed);
         if (rc != RSN_OK) { const std::string msg = c.err; return undo(rc, msg.c_str()); }
         rest.insert(rest.end(), back.begin(), back.end());
@@ -1124,12 +1129,9 @@ static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const
 // split is exercised on a one-GPU box); on a node with several GPUs each slice has its own PCIe link, histogram and emit.
 // Cuts fall on rune starts (a UTF-8 sequence is never split: huffman.go:309 decodes the whole string).
 namespace {
-struct ShardSync {
-    std::mutex mu; std::condition_variable cv;
+struct ShardSync : FirstFailure {
     size_t arrived = 0, generation = 0, parties;
-    int rc = RSN_OK; std::string msg;
     explicit ShardSync(size_t p) : parties(p) {}
-    void fail(int code, const char *m) noexcept { try { std::lock_guard<std::mutex> lk(mu); if (rc == RSN_OK) { rc = code; try { msg = m; } catch (...) {} } } catch (...) {} cv.notify_all(); }
     // all parties meet; `last` runs on the last one to arrive, before the others go on.  false: somebody failed
     bool meet(const std::function<void()> &last) {
         std::unique_lock<std::mutex> lk(mu);
@@ -1154,11 +1156,8 @@ template <class Takes, class Group, class Single>
 static int small_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens, bool back_skips_small,
                        Takes takes, Group group, Single single) {
     Ctx &c = ctx();
-    if (n == 0) return RSN_OK;
-    if (!ins || !lens || !outs || !out_lens) return c.fail(RSN_ERR_ARG, "null argument");
-    for (size_t i = 0; i < n; i++) { outs[i] = nullptr; out_lens[i] = 0; }
-    for (size_t i = 0; i < n; i++) if (!ins[i] && lens[i]) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
-    int rc = ctx_init(c); if (rc) return rc;                              // (no device: RSN_ERR_DEVICE -- there is no CPU path)
+    int rc = batch_args(c, n, ins, lens, outs, out_lens, true, true); if (rc || n == 0) return rc;
+    rc = ctx_init(c); if (rc) return rc;                                  // (no device: RSN_ERR_DEVICE -- there is no CPU path)
     constexpr size_t NONE = (size_t)-1;
     struct Fail { size_t at = NONE; int rc = RSN_OK; std::string msg; };
     Fail f;
@@ -1167,13 +1166,7 @@ static int small_batch(size_t n, const uint8_t *const *ins, const size_t *lens, 
     for (size_t i = 0; i < n; i++) (takes(i) ? grouped : rest).push_back(i);
     if (!grouped.empty()) {
         size_t failed = NONE;
-        const SmallTake take = [&](size_t i, const uint8_t *p, size_t len) -> int {
-            uint8_t *r = (uint8_t *)result_alloc(len);
-            if (!r) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", len);
-            memcpy(r, p, len);
-            outs[i] = r; out_lens[i] = len;
-            return RSN_OK;
-        };
+        const SmallTake take = take_into(c, outs, out_lens);
         rc = group(c, grouped, take, back, &failed);
         if (rc != RSN_OK) note(f, failed, rc, c.err);
     }
@@ -1210,7 +1203,7 @@ static int small_batch(size_t n, const uint8_t *const *ins, const size_t *lens, 
         }
     }
     if (f.at == NONE) return RSN_OK;
-    for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
+    drop_results(n, outs, out_lens);
     return c.fail(f.rc, "member %zu: %s", f.at, f.msg.c_str());
 }
 
@@ -1244,44 +1237,30 @@ static int rsn_lzss_decompress_batch_impl(size_t n, const uint8_t *const *ins, c
 // ---- the arithmetic codec (arith.hip): the single call is a batch of one -- every member goes through the same two kernels
 static int arithmetic_batch(bool enc, size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
     Ctx &c = ctx();
-    if (n == 0) return RSN_OK;
-    if (!ins || !lens || !outs || !out_lens) return c.fail(RSN_ERR_ARG, "null argument");
-    for (size_t i = 0; i < n; i++) { outs[i] = nullptr; out_lens[i] = 0; }
-    for (size_t i = 0; i < n; i++) if (!ins[i] && lens[i]) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
-    int rc = ctx_init(c); if (rc) return rc;                              // (no device: RSN_ERR_DEVICE -- there is no CPU path)
+    int rc = batch_args(c, n, ins, lens, outs, out_lens, true, true); if (rc || n == 0) return rc;
+    rc = ctx_init(c); if (rc) return rc;                                  // (no device: RSN_ERR_DEVICE -- there is no CPU path)
     std::vector<size_t> idx(n);
     for (size_t i = 0; i < n; i++) idx[i] = i;
-    const SmallTake take = [&](size_t i, const uint8_t *p, size_t len) -> int {
-        uint8_t *r = (uint8_t *)result_alloc(len);
-        if (!r) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", len);
-        memcpy(r, p, len);
-        outs[i] = r; out_lens[i] = len;
-        return RSN_OK;
-    };
+    const SmallTake take = take_into(c, outs, out_lens);
     size_t failed = 0;
     rc = enc ? arith_compress_members(c, idx, ins, lens, take, &failed) : arith_decompress_members(c, idx, ins, lens, take, &failed);
     if (rc == RSN_OK) return RSN_OK;
-    for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
+    drop_results(n, outs, out_lens);
     const std::string m = c.err;
     return c.fail(rc, "member %zu: %s", failed, m.c_str());
 }
 static int arithmetic_single(bool enc, const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
     Ctx &c = ctx();
-    if (!out || !out_n || (!in && n)) return c.fail(RSN_ERR_ARG, "null argument");
-    *out = nullptr; *out_n = 0;
+    int rc = host_args(c, in, n, out, out_n); if (rc) return rc;
     static const uint8_t none = 0;
     const uint8_t *ins[1] = {in ? in : &none};
-    const int rc = arithmetic_batch(enc, 1, ins, &n, out, out_n);
+    rc = arithmetic_batch(enc, 1, ins, &n, out, out_n);
     if (rc != RSN_OK && !c.err.compare(0, 10, "member 0: ")) c.err.erase(0, 10);
     return rc;
 }
 static int arithmetic_dev(bool enc, const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) {
     Ctx &c = ctx(); hipStream_t s;
-    if ((!d_in && n) || !out_n) return c.fail(RSN_ERR_ARG, "null argument");
-    if (!d_out) out_cap = 0;                                              // the size query (rsn.h)
-    if (ranges_overlap(d_in, n, d_out, out_cap)) return c.fail(RSN_ERR_ARG, "input and output ranges overlap");
-    if (((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 15)) return c.fail(RSN_ERR_ARG, "arithmetic: device buffers must be 16-byte aligned");
-    int rc = dev_prologue(c, stream, &s); if (rc) return rc;
+    int rc = dev_args(c, DevRules{true, true, "arithmetic"}, d_in, n, d_out, &out_cap, out_n, stream, &s); if (rc) return rc;
     return enc ? arith_encode_dev(c, s, (const uint8_t *)d_in, n, (uint8_t *)d_out, out_cap, out_n)
                : arith_decode_dev(c, s, (const uint8_t *)d_in, n, (uint8_t *)d_out, out_cap, out_n);
 }
@@ -1289,15 +1268,12 @@ size_t rsn_arithmetic_compress_bound(size_t n) { return arith_compress_bound(n);
 
 static int rsn_huffman_compress_sharded_impl(const uint8_t *in, size_t n, int shards, uint8_t **out, size_t *out_n) {
     Ctx &c = ctx();
-    if (!out || !out_n || (!in && n)) return c.fail(RSN_ERR_ARG, "null argument");
-    *out = nullptr; *out_n = 0;
-    if (n == 0) return c.fail(RSN_ERR_EMPTY, "huffman: empty input (reference panics in heap.Pop, huffman.go:102)");
-    int rc0 = ctx_init(c); if (rc0) return rc0;
+    int rc0 = host_args(c, in, n, out, out_n); if (rc0) return rc0;
+    if (n == 0) return c.fail(RSN_ERR_EMPTY, "%s", HUFF_EMPTY);
+    rc0 = ctx_init(c); if (rc0) return rc0;
     int G = shards > 0 ? shards : env_int("RSN_HUFF_SHARDS", 0);
-    int visible = 1;
-    if (hipGetDeviceCount(&visible) != hipSuccess || visible < 1) visible = 1;
-    const char *bd = getenv("RSN_BATCH_DEVICES");
-    const int n_dev = std::max(1, std::min(visible, !bd || !*bd ? 1 : (!strcmp(bd, "all") ? visible : atoi(bd))));
+    const DealPlan dp = deal_plan(1);                                     // (the devices of the batch workers: RSN_BATCH_DEVICES)
+    const int n_dev = dp.n_dev;
     if (G <= 0) G = n_dev;
     // (every slice is a thread with a stream and an arena of its own that meets the others at a barrier -- a few per device
     //  is all that can overlap anything; 64 or 255 of them only left that many parked contexts behind)
@@ -1311,7 +1287,7 @@ static int rsn_huffman_compress_sharded_impl(const uint8_t *in, size_t n, int sh
     std::vector<Slice> sl(S);
     HuffTree tree; HuffCodes codes; std::string hdr;
     bool flat = false;
-    uint8_t *res = nullptr; size_t total = 0;
+    HostBlock block; uint8_t *res = nullptr; size_t total = 0;
     ShardSync sync(S);
     const int base_dev = c.device;
 
@@ -1347,13 +1323,12 @@ static int rsn_huffman_compress_sharded_impl(const uint8_t *in, size_t n, int sh
         for (auto &x : sl) { x.start = at; at += x.bits; }
         total = hdr.size() + (size_t)((codes.total_bits + pad) / 8);
         flat = ascii && huff_flat_code(tree, codes);
-        res = (uint8_t *)result_alloc(total);
+        block.p = res = (uint8_t *)result_alloc(total);
         if (!res) sync.fail(RSN_ERR_NOMEM, "allocating the result block failed");
     };
 
     auto worker = [&](size_t w) {
-        const int dev = (base_dev + (int)(w % (size_t)n_dev)) % visible;
-        if (rsn_device_set(dev) != RSN_OK) { sync.fail(RSN_ERR_DEVICE, rsn_last_error()); return; }
+        if (rsn_device_set(worker_device(dp, base_dev, w)) != RSN_OK) { sync.fail(RSN_ERR_DEVICE, rsn_last_error()); return; }
         Ctx &cw = ctx(); hipStream_t s = cw.own_stream;
         auto bail = [&](int rc) { sync.fail(rc, cw.err.c_str()); };
         const size_t n_w = cut[w + 1] - cut[w];
@@ -1388,28 +1363,60 @@ static int rsn_huffman_compress_sharded_impl(const uint8_t *in, size_t n, int sh
     };
 
     // a slice whose thread cannot be had, or whose worker throws, fails the call: the workers that did start stop at the barrier
-    auto safely = [&](size_t w) { guarded_call<int>([&] { worker(w); return 0; }, [&](int code, const char *m) { sync.fail(code, m); return 0; }); };
+    auto safely = [&](size_t w) { on_helper(sync, [&] { worker(w); })(); };
     std::vector<HelperPool::Handle> threads;
     threads.reserve(S);
     for (size_t w = 1; w < S; w++) {
-        threads.push_back(HelperPool::run((base_dev + (int)(w % (size_t)n_dev)) % visible, [&safely, w] { safely(w); }));
+        threads.push_back(HelperPool::run(worker_device(dp, base_dev, w), [&safely, w] { safely(w); }));
         if (!threads.back()) { sync.fail(RSN_ERR_NOMEM, "huffman: no helper thread for a slice of the sharded stream"); break; }
     }
     safely(0);                                                            // the caller is worker 0, on its own context
     for (auto &t : threads) HelperPool::wait(t);
     (void)hipSetDevice(c.device);
-    if (sync.rc != RSN_OK) { if (res) result_free(res); return c.fail(sync.rc, "%s", sync.msg.c_str()); }
+    if (sync.rc != RSN_OK) return c.fail(sync.rc, "%s", sync.msg.c_str());
     for (auto &x : sl) if (x.has) { res[x.first] = 0; res[x.last] = 0; }
     for (auto &x : sl) if (x.has) { res[x.first] |= x.edge[0]; if (x.last != x.first) res[x.last] |= x.edge[1]; }
-    *out = res; *out_n = total;
+    *out = block.release(); *out_n = total;
     return RSN_OK;
 }
+
+// ---- the codec rows (declared above host_codec)
+namespace rsn {
+namespace {
+const Codec &codec(int id, bool enc) {
+    using u8 = uint8_t;
+    constexpr int64_t W = RSN_LZSS_DEFAULT_WINDOW;
+    constexpr size_t BIG = (size_t)32 << 20;                              // from here up the LZSS codecs state scratch (below it: not worth the gate)
+    static const Codec rows[2][2] = {
+        {   // RSN_LAYER_LZSS: decompress, compress
+            // (the decoder asks for 4 bytes per escaped byte from 64 MiB of them up, lzss_decode.hip: stated for an expansion of two -- text is
+            //  1.5; a stream that expands further decodes inside this admission all the same)
+            {[](size_t n) { return 8 * n + (1 << 16); }, [](size_t n) { return n < BIG ? 0 : 8 * n; },
+             [](Ctx &c, hipStream_t s, const u8 *di, size_t n, int64_t, u8 *dout, size_t cap, size_t *got) { return lzss_decode_dev(c, s, di, n, dout, cap, got); },
+             {true, false, nullptr}, [](const u8 *in, size_t n, u8 **out, size_t *out_n) { return rsn_lzss_decompress_impl(in, n, out, out_n); }},
+            // (the encoder's own statement of need, lzss_encode_dev: ~13 bytes of scratch per position of a pass + the escaped stream)
+            {[](size_t n) { return lzss_compress_bound(n); }, [](size_t n) { return n < BIG ? 0 : 13 * std::min(n, (size_t)3 << 29) + 2 * n; },
+             [](Ctx &c, hipStream_t s, const u8 *di, size_t n, int64_t w, u8 *dout, size_t cap, size_t *got) { return lzss_encode_dev(c, s, di, n, w, dout, cap, got); },
+             {true, true, nullptr}, [](const u8 *in, size_t n, u8 **out, size_t *out_n) { return rsn_lzss_compress_impl(in, n, W, out, out_n); }},
+        },
+        {   // RSN_LAYER_HUFFMAN
+            {[](size_t n) { return 4 * n + (1 << 16); }, [](size_t n) { return n / 8; },
+             [](Ctx &c, hipStream_t s, const u8 *di, size_t n, int64_t, u8 *dout, size_t cap, size_t *got) { return huff_decode_dev(c, s, di, n, dout, cap, got); },
+             {false, false, nullptr}, [](const u8 *in, size_t n, u8 **out, size_t *out_n) { return rsn_huffman_decompress_impl(in, n, out, out_n); }},
+            {[](size_t n) { return n + n / 8 + (1 << 16); }, [](size_t n) { return n / 32; },
+             [](Ctx &c, hipStream_t s, const u8 *di, size_t n, int64_t, u8 *dout, size_t cap, size_t *got) { return huff_encode_dev(c, s, di, n, dout, cap, got, nullptr, nullptr); },
+             {false, true, nullptr}, [](const u8 *in, size_t n, u8 **out, size_t *out_n) { return rsn_huffman_compress_impl(in, n, out, out_n); }},
+        },
+    };
+    return rows[id == RSN_LAYER_HUFFMAN][enc];
+}
+}  // namespace
+}  // namespace rsn
 
 // ---- layered calls (rsn.h): a list of layers over one buffer, the stream kept on the device between the layers.
 // host_call's shape -- an input slot, an output slot, fn(c, s, d_in, d_out, cap, &got) with one retry on RSN_ERR_CAPACITY -- with the
 // two slots swapped per layer.  Slots of their own (Slot::L_IN, L_A, L_B, L_STAT); the gate releases host_call's and these.
 namespace {
-struct HostBlock { uint8_t *p = nullptr; ~HostBlock() { if (p) result_free(p); } uint8_t *release() { uint8_t *r = p; p = nullptr; return r; } };
 // host buffers up to this size run the chain of single host calls (RSN_LAYERS_CHAIN_MAX: the A/B of scripts/layers_bench.py)
 size_t layers_chain_max() {
     static const size_t v = getenv("RSN_LAYERS_CHAIN_MAX") ? (size_t)atoll(getenv("RSN_LAYERS_CHAIN_MAX")) : (size_t)65536;
@@ -1424,37 +1431,19 @@ int layers_check(Ctx &c, const int *layers, size_t n_layers) {
     return RSN_OK;
 }
 int layer_fail(Ctx &c, int rc, size_t k, int id) { const std::string m = c.err; return c.fail(rc, "layer %zu (%s): %s", k, layer_name(id), m.c_str()); }
-// what host_call gives the single calls: the output buffer's first size, and the codec's own scratch
-size_t layer_cap(bool enc, int id, size_t n) {
-    if (id == RSN_LAYER_LZSS) return enc ? lzss_compress_bound(n) : 8 * n + (1 << 16);
-    return enc ? n + n / 8 + (1 << 16) : 4 * n + (1 << 16);
-}
-size_t layer_scratch(bool enc, int id, size_t n) {
-    if (id == RSN_LAYER_LZSS) return n < ((size_t)32 << 20) ? 0 : (enc ? 13 * std::min(n, (size_t)3 << 29) + 2 * n : 8 * n);
-    return enc ? n / 32 : n / 8;
-}
 // the SUM of what is live at once, over the chain's steps: a step's input, its output buffer (dev_buf rounds up by an eighth) and its
 // codec's scratch.  A step's input is not known before the step before it has run: compress takes its bound, decompress twice its input.
 size_t layers_need(bool enc, const int *layers, size_t n_layers, size_t n) {
     size_t live = 0, cur = n;
     for (size_t k = 0; k < n_layers; k++) {
         const int id = layers[enc ? k : n_layers - 1 - k];
-        const size_t cap = layer_cap(enc, id, cur);
-        live = std::max(live, round_up(cur, 16) + 64 + cap + cap / 8 + layer_scratch(enc, id, cur));
+        const size_t cap = codec(id, enc).cap(cur);
+        live = std::max(live, round_up(cur, 16) + 64 + cap + cap / 8 + codec(id, enc).scratch(cur));
         cur = enc ? cap : std::min(cap, 2 * cur);
     }
     return live;
 }
-int layer_dev(Ctx &c, hipStream_t s, bool enc, int id, const uint8_t *di, size_t n, uint8_t *dout, size_t cap, size_t *got) {
-    if (id == RSN_LAYER_LZSS) return enc ? lzss_encode_dev(c, s, di, n, RSN_LZSS_DEFAULT_WINDOW, dout, cap, got) : lzss_decode_dev(c, s, di, n, dout, cap, got);
-    return enc ? huff_encode_dev(c, s, di, n, dout, cap, got, nullptr, nullptr) : huff_decode_dev(c, s, di, n, dout, cap, got);
-}
 }  // namespace
-
-static int layer_host(bool enc, int id, const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
-    if (id == RSN_LAYER_LZSS) return enc ? rsn_lzss_compress_impl(in, n, RSN_LZSS_DEFAULT_WINDOW, out, out_n) : rsn_lzss_decompress_impl(in, n, out, out_n);
-    return enc ? rsn_huffman_compress_impl(in, n, out, out_n) : rsn_huffman_decompress_impl(in, n, out, out_n);
-}
 
 // the chain of single host calls: one layer (the call IS the single call), and host buffers below the cutoff
 static int layers_host_chain(Ctx &c, bool enc, const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n) {
@@ -1463,7 +1452,7 @@ static int layers_host_chain(Ctx &c, bool enc, const uint8_t *in, size_t n, cons
     for (size_t k = 0; k < n_layers; k++) {
         const size_t li = enc ? k : n_layers - 1 - k;
         HostBlock next; size_t next_n = 0;
-        const int rc = layer_host(enc, layers[li], cur, cur_n, &next.p, &next_n);
+        const int rc = codec(layers[li], enc).host(cur, cur_n, &next.p, &next_n);
         if (rc) return layer_fail(c, rc, li, layers[li]);
         if (held.p) result_free(held.p);
         held.p = next.release(); cur = held.p; cur_n = next_n;
@@ -1483,12 +1472,12 @@ static int run_chain(Ctx &c, hipStream_t s, bool enc, const int *layers, size_t 
         const size_t li = enc ? k : n_layers - 1 - k;
         const int id = layers[li];
         const bool to_caller = last_out && k + 1 == n_layers;
-        size_t cap = to_caller ? last_cap : layer_cap(enc, id, cur_n), got = 0;
+        size_t cap = to_caller ? last_cap : codec(id, enc).cap(cur_n), got = 0;
         uint8_t *dst = last_out;
         int rc;
         for (int attempt = 0;; attempt++) {
             if (!to_caller) { void *p; rc = dev_buf(c, slot, cap + 80, &p); if (rc) return rc; dst = (uint8_t *)p; }
-            rc = layer_dev(c, s, enc, id, cur, cur_n, dst, cap, &got);
+            rc = codec(id, enc).dev(c, s, cur, cur_n, RSN_LZSS_DEFAULT_WINDOW, dst, cap, &got);
             if (rc == RSN_ERR_CAPACITY && !to_caller && attempt == 0 && got > cap) { cap = got; continue; }   // (both decoders: the size is known after a pass)
             break;
         }
@@ -1503,17 +1492,10 @@ static int run_chain(Ctx &c, hipStream_t s, bool enc, const int *layers, size_t 
 
 static int layers_host(bool enc, const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n) {
     Ctx &c = ctx();
-    if (!out || !out_n || (!in && n)) return c.fail(RSN_ERR_ARG, "null argument");
-    *out = nullptr; *out_n = 0;
-    int rc = layers_check(c, layers, n_layers); if (rc) return rc;
+    int rc = host_args(c, in, n, out, out_n); if (rc) return rc;
+    rc = layers_check(c, layers, n_layers); if (rc) return rc;
     rc = ctx_init(c); if (rc) return rc;
-    if (n_layers == 0) {                                                  // the reference's loops do nothing: the input
-        uint8_t *r = (uint8_t *)result_alloc(n);
-        if (!r) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", n);
-        if (n) memcpy(r, in, n);
-        *out = r; *out_n = n;
-        return RSN_OK;
-    }
+    if (n_layers == 0) return result_from_host(c, in, n, out, out_n);     // the reference's loops do nothing: the input
     if (n_layers == 1 || n <= layers_chain_max()) return layers_host_chain(c, enc, in, n, layers, n_layers, out, out_n);
     hipStream_t s = c.own_stream;
     const size_t need = round_up(n, 16) + 64 + layers_need(enc, layers, n_layers, n);
@@ -1522,15 +1504,7 @@ static int layers_host(bool enc, const uint8_t *in, size_t n, const int *layers,
     rc = stage_input(c, s, Slot::L_IN, in, n, &d_in); if (rc) return rc;
     const uint8_t *d_res; size_t got = 0;
     rc = run_chain(c, s, enc, layers, n_layers, (const uint8_t *)d_in, n, Slot::L_A, nullptr, 0, &d_res, &got); if (rc) return rc;
-    HostBlock r;
-    r.p = (uint8_t *)result_alloc(got);
-    if (!r.p) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", got);
-    if (got) {
-        RSN_HIP(copy_async(r.p, d_res, got, hipMemcpyDeviceToHost, s));
-        RSN_HIP(hipStreamSynchronize(s));
-    }
-    *out = r.release(); *out_n = got;
-    return RSN_OK;
+    return result_from_dev(c, s, d_res, got, out, out_n);
 }
 
 static int layers_dev(bool enc, const void *d_in, size_t n, const int *layers, size_t n_layers, void *d_out, size_t out_cap, size_t *out_n, void *stream) {
@@ -1538,10 +1512,8 @@ static int layers_dev(bool enc, const void *d_in, size_t n, const int *layers, s
     if ((!d_in && n) || !out_n) return c.fail(RSN_ERR_ARG, "null argument");
     *out_n = 0;
     int rc = layers_check(c, layers, n_layers); if (rc) return rc;
-    if (((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 15)) return c.fail(RSN_ERR_ARG, "layers: device buffers must be 16-byte aligned");
-    if (!d_out) out_cap = 0;
-    if (ranges_overlap(d_in, n, d_out, out_cap)) return c.fail(RSN_ERR_ARG, "input and output ranges overlap");
-    rc = dev_prologue(c, stream, &s); if (rc) return rc;
+    if (((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 15)) return c.fail(RSN_ERR_ARG, "layers: device buffers must be 16-byte aligned");   // (before the overlap: its own line)
+    rc = dev_args(c, DevRules{true, true, nullptr}, d_in, n, d_out, &out_cap, out_n, stream, &s); if (rc) return rc;
     if (n_layers == 0) {
         if (out_cap < n) { *out_n = round_up(n, 16) + 16; return c.fail(RSN_ERR_CAPACITY, "layers: output needs %zu bytes, buffer holds %zu", n, out_cap); }
         if (n) RSN_HIP(copy_async(d_out, d_in, n, hipMemcpyDeviceToDevice, s));
@@ -1551,8 +1523,7 @@ static int layers_dev(bool enc, const void *d_in, size_t n, const int *layers, s
     }
     if (n_layers == 1 && (out_cap || !enc)) {                            // the single call, its own size query included (the decoders answer it)
         const int id = layers[0];
-        if (id == RSN_LAYER_LZSS) rc = enc ? rsn_lzss_compress_dev_impl(d_in, n, RSN_LZSS_DEFAULT_WINDOW, d_out, out_cap, out_n, stream) : rsn_lzss_decompress_dev_impl(d_in, n, d_out, out_cap, out_n, stream);
-        else rc = enc ? rsn_huffman_compress_dev_impl(d_in, n, d_out, out_cap, out_n, stream) : rsn_huffman_decompress_dev_impl(d_in, n, d_out, out_cap, out_n, stream);
+        rc = dev_codec(codec(id, enc), d_in, n, RSN_LZSS_DEFAULT_WINDOW, d_out, out_cap, out_n, stream);
         return rc ? layer_fail(c, rc, 0, id) : RSN_OK;
     }
     const size_t need = layers_need(enc, layers, n_layers, n);
@@ -1604,11 +1575,7 @@ static int layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size
         const uint8_t *d_in = (const uint8_t *)d_up;
         const uint8_t *d_c; size_t cn = 0;
         rc = run_chain(c, s, true, layers, n_layers, d_in, n, Slot::L_A, nullptr, 0, &d_c, &cn); if (rc) return rc;
-        if (compressed) {
-            comp.p = (uint8_t *)result_alloc(cn);
-            if (!comp.p) return c.fail(RSN_ERR_NOMEM, "allocating %zu result bytes failed", cn);
-            if (cn) { RSN_HIP(copy_async(comp.p, d_c, cn, hipMemcpyDeviceToHost, s)); RSN_HIP(hipStreamSynchronize(s)); }
-        }
+        if (compressed) { size_t down = 0; rc = result_from_dev(c, s, d_c, cn, &comp.p, &down); if (rc) return rc; }
         const auto t1 = now();
         const uint8_t *d_d; size_t dn = 0;
         rc = run_chain(c, s, false, layers, n_layers, d_c, cn, d_c == (const uint8_t *)c.buf(Slot::L_A).p ? Slot::L_B : Slot::L_A, nullptr, 0, &d_d, &dn); if (rc) return rc;
@@ -1633,11 +1600,6 @@ static int layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size
     return RSN_OK;
 }
 
-static void rsn_prof_enable_impl(int on) { ctx().prof = on != 0; g_copy_count.on.store(on != 0); }
-static void rsn_prof_copied_impl(uint64_t *h2d_bytes, uint64_t *d2h_bytes) {
-    if (h2d_bytes) *h2d_bytes = g_copy_count.h2d.load();
-    if (d2h_bytes) *d2h_bytes = g_copy_count.d2h.load();
-}
 static void rsn_prof_reset_impl(void) {
     Ctx &c = ctx();
     g_copy_count.h2d.store(0); g_copy_count.d2h.store(0);
@@ -1723,87 +1685,46 @@ static int64_t rsn_huffman_parse_header_impl(const uint8_t *header, size_t n, ui
 // ends that way hands out nothing: *out stays NULL.
 namespace {
 int boundary_error(int code, const char *m) noexcept { try { ctx().err = m; } catch (...) {} return code; }
+// the three forms: a call that hands out nothing; one with (out, out_n); one with (n, outs, out_lens) -- what was handed out before the throw goes back
+template <class F> auto guarded(F f) noexcept { return guarded_call<decltype(f())>(f, boundary_error); }
+template <class F> int guarded_out(uint8_t **out, size_t *out_n, F f) noexcept {
+    return guarded_call<int>(f, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
+}
+template <class F> int guarded_outs(size_t n, uint8_t **outs, size_t *out_lens, F f) noexcept {
+    return guarded_call<int>(f, [&](int code, const char *m) { if (outs && out_lens) drop_results(n, outs, out_lens); return boundary_error(code, m); });
+}
+const Codec &HUFF_ENC = codec(RSN_LAYER_HUFFMAN, true), &HUFF_DEC = codec(RSN_LAYER_HUFFMAN, false), &LZSS_ENC = codec(RSN_LAYER_LZSS, true), &LZSS_DEC = codec(RSN_LAYER_LZSS, false);
 }  // namespace
 
 extern "C" {
-int rsn_device_set(int device) { return guarded_call<int>([&] { return rsn_device_set_impl(device); }, boundary_error); }
-int rsn_device_count(void) { return guarded_call<int>([&] { return rsn_device_count_impl(); }, boundary_error); }
-void rsn_trim(void) { guarded_call<int>([&] { rsn_trim_impl(); return 0; }, boundary_error); }
-void rsn_free(void *p) { guarded_call<int>([&] { rsn_free_impl(p); return 0; }, boundary_error); }
-int rsn_huffman_compress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded_call<int>([&] { return rsn_huffman_compress_dev_impl(d_in, n, d_out, out_cap, out_n, stream); }, boundary_error); }
-int rsn_huffman_decompress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded_call<int>([&] { return rsn_huffman_decompress_dev_impl(d_in, n, d_out, out_cap, out_n, stream); }, boundary_error); }
-int rsn_lzss_compress_dev(const void *d_in, size_t n, int64_t window, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded_call<int>([&] { return rsn_lzss_compress_dev_impl(d_in, n, window, d_out, out_cap, out_n, stream); }, boundary_error); }
-int rsn_lzss_decompress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded_call<int>([&] { return rsn_lzss_decompress_dev_impl(d_in, n, d_out, out_cap, out_n, stream); }, boundary_error); }
-int rsn_huffman_compress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
-    return guarded_call<int>([&] { return rsn_huffman_compress_impl(in, n, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
-}
-int rsn_huffman_decompress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
-    return guarded_call<int>([&] { return rsn_huffman_decompress_impl(in, n, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
-}
-int rsn_lzss_compress(const uint8_t *in, size_t n, int64_t window, uint8_t **out, size_t *out_n) {
-    return guarded_call<int>([&] { return rsn_lzss_compress_impl(in, n, window, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
-}
-int rsn_lzss_compress_legacy(const uint8_t *in, size_t n, int64_t window, uint8_t **out, size_t *out_n) {
-    return guarded_call<int>([&] { return rsn_lzss_compress_legacy_impl(in, n, window, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
-}
-int rsn_lzss_decompress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
-    return guarded_call<int>([&] { return rsn_lzss_decompress_impl(in, n, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
-}
-int rsn_huffman_compress_batch(size_t n_chunks, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
-    return guarded_call<int>([&] { return rsn_huffman_compress_batch_impl(n_chunks, ins, lens, outs, out_lens); }, [&](int code, const char *m) {
-        if (outs && out_lens) for (size_t k = 0; k < n_chunks; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
-        return boundary_error(code, m);
-    });
-}
-int rsn_huffman_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
-    return guarded_call<int>([&] { return rsn_huffman_decompress_batch_impl(n, ins, lens, outs, out_lens); }, [&](int code, const char *m) {
-        if (outs && out_lens) for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
-        return boundary_error(code, m);
-    });
-}
-int rsn_lzss_compress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, int64_t window, uint8_t **outs, size_t *out_lens) {
-    return guarded_call<int>([&] { return rsn_lzss_compress_batch_impl(n, ins, lens, window, outs, out_lens); }, [&](int code, const char *m) {
-        if (outs && out_lens) for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
-        return boundary_error(code, m);
-    });
-}
-int rsn_lzss_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
-    return guarded_call<int>([&] { return rsn_lzss_decompress_batch_impl(n, ins, lens, outs, out_lens); }, [&](int code, const char *m) {
-        if (outs && out_lens) for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
-        return boundary_error(code, m);
-    });
-}
-int rsn_arithmetic_compress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
-    return guarded_call<int>([&] { return arithmetic_single(true, in, n, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
-}
-int rsn_arithmetic_decompress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) {
-    return guarded_call<int>([&] { return arithmetic_single(false, in, n, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
-}
-int rsn_arithmetic_compress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
-    return guarded_call<int>([&] { return arithmetic_batch(true, n, ins, lens, outs, out_lens); }, [&](int code, const char *m) {
-        if (outs && out_lens) for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
-        return boundary_error(code, m);
-    });
-}
-int rsn_arithmetic_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
-    return guarded_call<int>([&] { return arithmetic_batch(false, n, ins, lens, outs, out_lens); }, [&](int code, const char *m) {
-        if (outs && out_lens) for (size_t k = 0; k < n; k++) { if (outs[k]) result_free(outs[k]); outs[k] = nullptr; out_lens[k] = 0; }
-        return boundary_error(code, m);
-    });
-}
-int rsn_arithmetic_compress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded_call<int>([&] { return arithmetic_dev(true, d_in, n, d_out, out_cap, out_n, stream); }, boundary_error); }
-int rsn_arithmetic_decompress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded_call<int>([&] { return arithmetic_dev(false, d_in, n, d_out, out_cap, out_n, stream); }, boundary_error); }
-int rsn_huffman_compress_sharded(const uint8_t *in, size_t n, int shards, uint8_t **out, size_t *out_n) {
-    return guarded_call<int>([&] { return rsn_huffman_compress_sharded_impl(in, n, shards, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
-}
-int rsn_layers_compress(const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n) {
-    return guarded_call<int>([&] { return layers_host(true, in, n, layers, n_layers, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
-}
-int rsn_layers_decompress(const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n) {
-    return guarded_call<int>([&] { return layers_host(false, in, n, layers, n_layers, out, out_n); }, [&](int code, const char *m) { if (out && *out) { result_free(*out); *out = nullptr; } if (out_n) *out_n = 0; return boundary_error(code, m); });
-}
-int rsn_layers_compress_dev(const void *d_in, size_t n, const int *layers, size_t n_layers, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded_call<int>([&] { return layers_dev(true, d_in, n, layers, n_layers, d_out, out_cap, out_n, stream); }, boundary_error); }
-int rsn_layers_decompress_dev(const void *d_in, size_t n, const int *layers, size_t n_layers, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded_call<int>([&] { return layers_dev(false, d_in, n, layers, n_layers, d_out, out_cap, out_n, stream); }, boundary_error); }
+int rsn_device_set(int device) { return guarded([&] { return rsn_device_set_impl(device); }); }
+int rsn_device_count(void) { return guarded([&] { return rsn_device_count_impl(); }); }
+void rsn_trim(void) { guarded([&] { rsn_trim_impl(); return 0; }); }
+void rsn_free(void *p) { guarded([&] { result_free(p); return 0; }); }
+int rsn_huffman_compress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded([&] { return dev_codec(HUFF_ENC, d_in, n, 0, d_out, out_cap, out_n, stream); }); }
+int rsn_huffman_decompress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded([&] { return dev_codec(HUFF_DEC, d_in, n, 0, d_out, out_cap, out_n, stream); }); }
+int rsn_lzss_compress_dev(const void *d_in, size_t n, int64_t window, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded([&] { return dev_codec(LZSS_ENC, d_in, n, window, d_out, out_cap, out_n, stream); }); }
+int rsn_lzss_decompress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded([&] { return dev_codec(LZSS_DEC, d_in, n, 0, d_out, out_cap, out_n, stream); }); }
+int rsn_huffman_compress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return rsn_huffman_compress_impl(in, n, out, out_n); }); }
+int rsn_huffman_decompress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return rsn_huffman_decompress_impl(in, n, out, out_n); }); }
+int rsn_lzss_compress(const uint8_t *in, size_t n, int64_t window, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return rsn_lzss_compress_impl(in, n, window, out, out_n); }); }
+int rsn_lzss_compress_legacy(const uint8_t *in, size_t n, int64_t window, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return rsn_lzss_compress_legacy_impl(in, n, window, out, out_n); }); }
+int rsn_lzss_decompress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return rsn_lzss_decompress_impl(in, n, out, out_n); }); }
+int rsn_huffman_compress_batch(size_t n_chunks, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) { return guarded_outs(n_chunks, outs, out_lens, [&] { return rsn_huffman_compress_batch_impl(n_chunks, ins, lens, outs, out_lens); }); }
+int rsn_huffman_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) { return guarded_outs(n, outs, out_lens, [&] { return rsn_huffman_decompress_batch_impl(n, ins, lens, outs, out_lens); }); }
+int rsn_lzss_compress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, int64_t window, uint8_t **outs, size_t *out_lens) { return guarded_outs(n, outs, out_lens, [&] { return rsn_lzss_compress_batch_impl(n, ins, lens, window, outs, out_lens); }); }
+int rsn_lzss_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) { return guarded_outs(n, outs, out_lens, [&] { return rsn_lzss_decompress_batch_impl(n, ins, lens, outs, out_lens); }); }
+int rsn_arithmetic_compress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return arithmetic_single(true, in, n, out, out_n); }); }
+int rsn_arithmetic_decompress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return arithmetic_single(false, in, n, out, out_n); }); }
+int rsn_arithmetic_compress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) { return guarded_outs(n, outs, out_lens, [&] { return arithmetic_batch(true, n, ins, lens, outs, out_lens); }); }
+int rsn_arithmetic_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) { return guarded_outs(n, outs, out_lens, [&] { return arithmetic_batch(false, n, ins, lens, outs, out_lens); }); }
+int rsn_arithmetic_compress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded([&] { return arithmetic_dev(true, d_in, n, d_out, out_cap, out_n, stream); }); }
+int rsn_arithmetic_decompress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded([&] { return arithmetic_dev(false, d_in, n, d_out, out_cap, out_n, stream); }); }
+int rsn_huffman_compress_sharded(const uint8_t *in, size_t n, int shards, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return rsn_huffman_compress_sharded_impl(in, n, shards, out, out_n); }); }
+int rsn_layers_compress(const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return layers_host(true, in, n, layers, n_layers, out, out_n); }); }
+int rsn_layers_decompress(const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return layers_host(false, in, n, layers, n_layers, out, out_n); }); }
+int rsn_layers_compress_dev(const void *d_in, size_t n, const int *layers, size_t n_layers, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded([&] { return layers_dev(true, d_in, n, layers, n_layers, d_out, out_cap, out_n, stream); }); }
+int rsn_layers_decompress_dev(const void *d_in, size_t n, const int *layers, size_t n_layers, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded([&] { return layers_dev(false, d_in, n, layers, n_layers, d_out, out_cap, out_n, stream); }); }
 int rsn_layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size_t n_layers, rsn_roundtrip_result *res, uint8_t **compressed, size_t *compressed_n) {
     return guarded_call<int>([&] { return layers_roundtrip(in, n, layers, n_layers, res, compressed, compressed_n); }, [&](int code, const char *m) {
         if (res) memset(res, 0, sizeof *res);
@@ -1812,13 +1733,13 @@ int rsn_layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size_t 
         return boundary_error(code, m);
     });
 }
-void rsn_prof_copied(uint64_t *h2d_bytes, uint64_t *d2h_bytes) { guarded_call<int>([&] { rsn_prof_copied_impl(h2d_bytes, d2h_bytes); return 0; }, boundary_error); }
-void rsn_prof_enable(int on) { guarded_call<int>([&] { rsn_prof_enable_impl(on); return 0; }, boundary_error); }
-void rsn_prof_reset(void) { guarded_call<int>([&] { rsn_prof_reset_impl(); return 0; }, boundary_error); }
-int rsn_prof_get(rsn_prof_entry *entries, int cap) { return guarded_call<int>([&] { return rsn_prof_get_impl(entries, cap); }, boundary_error); }
-int64_t rsn_huffman_table(const uint8_t *in, size_t n, uint32_t *runes, uint64_t *freqs, uint64_t *codes, uint8_t *lens, size_t cap) { return guarded_call<int64_t>([&] { return rsn_huffman_table_impl(in, n, runes, freqs, codes, lens, cap); }, boundary_error); }
-int64_t rsn_huffman_plan(const uint32_t *runes, const uint64_t *counts, size_t n_syms, uint32_t *out_runes, uint64_t *out_codes, uint8_t *out_lens, uint8_t *header, size_t header_cap, size_t *header_len) { return guarded_call<int64_t>([&] { return rsn_huffman_plan_impl(runes, counts, n_syms, out_runes, out_codes, out_lens, header, header_cap, header_len); }, boundary_error); }
-int64_t rsn_huffman_slice_cuts(const uint8_t *in, size_t n, int shards, size_t *cuts, size_t cap) { return guarded_call<int64_t>([&] { return rsn_huffman_slice_cuts_impl(in, n, shards, cuts, cap); }, boundary_error); }
-int64_t rsn_huffman_parse_header(const uint8_t *header, size_t n, uint32_t *runes, uint64_t *counts, size_t cap) { return guarded_call<int64_t>([&] { return rsn_huffman_parse_header_impl(header, n, runes, counts, cap); }, boundary_error); }
+void rsn_prof_copied(uint64_t *h2d_bytes, uint64_t *d2h_bytes) { guarded([&] { if (h2d_bytes) *h2d_bytes = g_copy_count.h2d.load(); if (d2h_bytes) *d2h_bytes = g_copy_count.d2h.load(); return 0; }); }
+void rsn_prof_enable(int on) { guarded([&] { ctx().prof = on != 0; g_copy_count.on.store(on != 0); return 0; }); }
+void rsn_prof_reset(void) { guarded([&] { rsn_prof_reset_impl(); return 0; }); }
+int rsn_prof_get(rsn_prof_entry *entries, int cap) { return guarded([&] { return rsn_prof_get_impl(entries, cap); }); }
+int64_t rsn_huffman_table(const uint8_t *in, size_t n, uint32_t *runes, uint64_t *freqs, uint64_t *codes, uint8_t *lens, size_t cap) { return guarded([&] { return rsn_huffman_table_impl(in, n, runes, freqs, codes, lens, cap); }); }
+int64_t rsn_huffman_plan(const uint32_t *runes, const uint64_t *counts, size_t n_syms, uint32_t *out_runes, uint64_t *out_codes, uint8_t *out_lens, uint8_t *header, size_t header_cap, size_t *header_len) { return guarded([&] { return rsn_huffman_plan_impl(runes, counts, n_syms, out_runes, out_codes, out_lens, header, header_cap, header_len); }); }
+int64_t rsn_huffman_slice_cuts(const uint8_t *in, size_t n, int shards, size_t *cuts, size_t cap) { return guarded([&] { return rsn_huffman_slice_cuts_impl(in, n, shards, cuts, cap); }); }
+int64_t rsn_huffman_parse_header(const uint8_t *header, size_t n, uint32_t *runes, uint64_t *counts, size_t cap) { return guarded([&] { return rsn_huffman_parse_header_impl(header, n, runes, counts, cap); }); }
 
 }  // extern "C"

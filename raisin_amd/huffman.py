@@ -26,20 +26,7 @@ def CompressBatch(chunks):
     chunk's own tree on the device (byte alphabets; a chunk with a byte >= 0x80 or a single distinct byte is handed back), when at least
     two chunks are of that size.  The other chunks are dealt out over the batch workers (chunk k -> device k mod G) and go through a
     pipeline of upload / encode / download per device.  Each result equals Compress(chunk)."""
-    import ctypes
-    L = _lib.lib()
-    chunks = [bytes(c) for c in chunks]
-    k = len(chunks)
-    ins = (ctypes.c_char_p * k)(*chunks)
-    lens = (ctypes.c_size_t * k)(*[len(c) for c in chunks])
-    outs = (ctypes.POINTER(ctypes.c_uint8) * k)()
-    olens = (ctypes.c_size_t * k)()
-    _lib.check(L.rsn_huffman_compress_batch(k, ins, lens, outs, olens))
-    try:
-        return [ctypes.string_at(outs[i], olens[i]) for i in range(k)]
-    finally:
-        for i in range(k):
-            L.rsn_free(outs[i])
+    return _lib.call_batch(_lib.lib().rsn_huffman_compress_batch, chunks)
 
 
 # The largest chunk the batch encoder's grouped kernel takes (csrc/huff_small.hip HE_IN_MAX; DESIGN 4.7): its output -- at most 7 bits
@@ -59,43 +46,18 @@ def DecompressBatch(streams):
     return _lib.call_batch(_lib.lib().rsn_huffman_decompress_batch, streams)
 
 
-class Writer:
+class Writer(_lib.Writer):
     """huffman.go:368-386: Write compresses the whole buffer once and returns len(compressed)."""
 
     def __init__(self, w):
-        self.w = w
-
-    def Write(self, data):
-        compressed = Compress(data)
-        self.w.write(compressed)
-        return len(compressed)
-
-    write = Write
-
-    def Close(self):
-        return None
-
-    close = Close
+        super().__init__(w, lambda data: Compress(data))
 
 
-class Reader:
+class Reader(_lib.Reader):
     """huffman.go:388-422: the first Read drains the source and decompresses everything."""
 
     def __init__(self, r):
-        self.r = r
-        self.decompressed = None
-        self.pos = 0
-
-    def Read(self, size=-1):
-        if self.decompressed is None:
-            self.decompressed = Decompress(self.r.read())
-        if size is None or size < 0:
-            size = len(self.decompressed) - self.pos
-        chunk = self.decompressed[self.pos:self.pos + size]
-        self.pos += len(chunk)
-        return chunk
-
-    read = Read
+        super().__init__(r, lambda data: Decompress(data))
 
 
 def NewWriter(w):
@@ -166,8 +128,6 @@ def parse_header(header):
 
 
 # ---- device-resident form (torch tensors as plain device memory) -----------
-from ._lib import own_stream as _own_stream  # noqa: E402
-
 def compress_bound(n):
     return int(_lib.lib().rsn_huffman_compress_bound(n))
 
@@ -175,41 +135,11 @@ def compress_bound(n):
 def compress_tensor(src, out=None, stream=None):
     """src: uint8 CUDA tensor.  Returns a uint8 tensor holding the .rsn bytes: a view of `out` when it was large
     enough, otherwise (RSN_ERR_CAPACITY) a view of a fresh tensor of the capacity the library asked for."""
-    import torch
     n = src.numel()
-    if out is None:
-        out = torch.empty(n + n // 8 + (1 << 16), dtype=torch.uint8, device=src.device)
-    st = _own_stream(src, stream)
-    try:
-        got = _lib.call_dev(_lib.lib().rsn_huffman_compress_dev, src.data_ptr(), n, out.data_ptr(), out.numel(), st)
-    except _lib.RsnError as e:
-        if e.code != _lib.RSN_ERR_CAPACITY:
-            raise
-        out = torch.empty(e.needed, dtype=torch.uint8, device=src.device)
-        got = _lib.call_dev(_lib.lib().rsn_huffman_compress_dev, src.data_ptr(), n, out.data_ptr(), out.numel(), st)
-    return out[:got]
+    return _lib.dev_tensor(_lib.lib().rsn_huffman_compress_dev, src, out, stream, n + n // 8 + (1 << 16))
 
 
 def decompress_tensor(src, out=None, stream=None):
-    import torch
+    """below 1 MiB of stream a generous guess costs less than a second call; from there the size query first"""
     n = src.numel()
-    st = _own_stream(src, stream)
-    if out is None and n < (1 << 20):
-        out = torch.empty(8 * n + (1 << 16), dtype=torch.uint8, device=src.device)   # small: a generous guess costs less than a second call
-    if out is None:
-        # the size query first (d_out NULL): a guess of the expansion would be a buffer of many times the input, held by the view returned
-        try:
-            need = _lib.call_dev(_lib.lib().rsn_huffman_decompress_dev, src.data_ptr(), n, None, 0, st)
-        except _lib.RsnError as e:
-            if e.code != _lib.RSN_ERR_CAPACITY:
-                raise
-            need = e.needed
-        out = torch.empty(max(need, 16), dtype=torch.uint8, device=src.device)
-    try:
-        got = _lib.call_dev(_lib.lib().rsn_huffman_decompress_dev, src.data_ptr(), n, out.data_ptr(), out.numel(), st)
-    except _lib.RsnError as e:
-        if e.code != _lib.RSN_ERR_CAPACITY:
-            raise
-        out = torch.empty(e.needed, dtype=torch.uint8, device=src.device)
-        got = _lib.call_dev(_lib.lib().rsn_huffman_decompress_dev, src.data_ptr(), n, out.data_ptr(), out.numel(), st)
-    return out[:got]
+    return _lib.dev_tensor(_lib.lib().rsn_huffman_decompress_dev, src, out, stream, 8 * n + (1 << 16) if n < (1 << 20) else None)

@@ -3,7 +3,6 @@ between the layers (rsn_layers_*, include/rsn.h).  Layers are given by the engin
 import ctypes
 
 from . import _lib
-from ._lib import own_stream as _own_stream
 
 LZSS, HUFFMAN = 1, 2          # RSN_LAYER_LZSS, RSN_LAYER_HUFFMAN
 LAYERS_MAX = 8                # RSN_LAYERS_MAX
@@ -31,35 +30,16 @@ def Decompress(data, layers):
     return _lib.call_host(_lib.lib().rsn_layers_decompress, data, arr, k)
 
 
-def _tensor(fn, src, layers, out, stream, guess):
-    import torch
-    arr, k = ids(layers)
-    n = src.numel()
-    st = _own_stream(src, stream)
-    if out is None and guess is not None:
-        out = torch.empty(guess, dtype=torch.uint8, device=src.device)
-    try:
-        if out is None:                                       # the size query (d_out NULL): runs the chain once, rsn.h
-            got = _lib.call_dev(fn, src.data_ptr(), n, None, 0, st, arr, k)
-        else:
-            got = _lib.call_dev(fn, src.data_ptr(), n, out.data_ptr(), out.numel(), st, arr, k)
-    except _lib.RsnError as e:
-        if e.code != _lib.RSN_ERR_CAPACITY:
-            raise
-        out = torch.empty(max(e.needed, 16), dtype=torch.uint8, device=src.device)
-        got = _lib.call_dev(fn, src.data_ptr(), n, out.data_ptr(), out.numel(), st, arr, k)
-    return out[:got]
-
-
 def compress_tensor(src, layers, out=None, stream=None):
     """src: uint8 CUDA tensor -> a uint8 tensor holding the layered stream (a view of `out` when it was large enough)."""
     n = src.numel()
-    return _tensor(_lib.lib().rsn_layers_compress_dev, src, layers, out, stream, n + n // 4 + (1 << 16))
+    return _lib.dev_tensor(_lib.lib().rsn_layers_compress_dev, src, out, stream, n + n // 4 + (1 << 16), *ids(layers), floor=16)
 
 
 def decompress_tensor(src, layers, out=None, stream=None):
+    """from 1 MiB of stream up the size query first (d_out NULL): it runs the chain once, rsn.h"""
     n = src.numel()
-    return _tensor(_lib.lib().rsn_layers_decompress_dev, src, layers, out, stream, 8 * n + (1 << 16) if n < (1 << 20) else None)
+    return _lib.dev_tensor(_lib.lib().rsn_layers_decompress_dev, src, out, stream, 8 * n + (1 << 16) if n < (1 << 20) else None, *ids(layers), floor=16)
 
 
 def RoundTrip(data, layers, keep_compressed=False):

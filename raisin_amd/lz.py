@@ -35,45 +35,20 @@ def DecompressBatch(streams):
     return _lib.call_batch(_lib.lib().rsn_lzss_decompress_batch, streams)
 
 
-class Writer:
+class Writer(_lib.Writer):
     """lzss.go:29-61"""
 
     def __init__(self, w, windowSize):
-        self.w = w
+        super().__init__(w, lambda data: CompressAsync(data, self.useProgressBar, self.windowSize))
         self.windowSize = windowSize
         self.useProgressBar = True
 
-    def Write(self, data):
-        compressed = CompressAsync(data, self.useProgressBar, self.windowSize)
-        self.w.write(compressed)
-        return len(compressed)
 
-    write = Write
-
-    def Close(self):
-        return None
-
-    close = Close
-
-
-class Reader:
+class Reader(_lib.Reader):
     """lzss.go:63-106"""
 
     def __init__(self, r):
-        self.r = r
-        self.decompressed = None
-        self.pos = 0
-
-    def Read(self, size=-1):
-        if self.decompressed is None:
-            self.decompressed = Decompress(self.r.read(), True)
-        if size is None or size < 0:
-            size = len(self.decompressed) - self.pos
-        chunk = self.decompressed[self.pos:self.pos + size]
-        self.pos += len(chunk)
-        return chunk
-
-    read = Read
+        super().__init__(r, lambda data: Decompress(data, True))
 
     def Close(self):
         return None
@@ -98,43 +73,16 @@ def NewReader(r):
     return Reader(r)
 
 
-from ._lib import own_stream as _own_stream  # noqa: E402
-
-
 def compress_bound(n):
     return int(_lib.lib().rsn_lzss_compress_bound(n))
 
 
 def compress_tensor(src, window=DefaultWindowSize, out=None, stream=None):
-    import torch
-    n = src.numel()
-    if out is None:
-        out = torch.empty(compress_bound(n), dtype=torch.uint8, device=src.device)
-    st = _own_stream(src, stream)
-    got = _lib.call_dev(_lib.lib().rsn_lzss_compress_dev, src.data_ptr(), n, out.data_ptr(), out.numel(), st, int(window))
-    return out[:got]
+    """no second call here: an `out` that is too small raises (RsnError.needed: the size that suffices)"""
+    return _lib.dev_tensor(_lib.lib().rsn_lzss_compress_dev, src, out, stream, compress_bound(src.numel()), int(window), retry=False)
 
 
 def decompress_tensor(src, out=None, stream=None):
-    import torch
+    """below 1 MiB of stream a generous guess costs less than a second call; from there the size query first"""
     n = src.numel()
-    st = _own_stream(src, stream)
-    if out is None and n < (1 << 20):
-        out = torch.empty(16 * n + (1 << 16), dtype=torch.uint8, device=src.device)   # small: a generous guess costs less than a second call
-    if out is None:
-        # the size query first (d_out NULL): a guess of the expansion would be a buffer of many times the input, held by the view returned
-        try:
-            need = _lib.call_dev(_lib.lib().rsn_lzss_decompress_dev, src.data_ptr(), n, None, 0, st)
-        except _lib.RsnError as e:
-            if e.code != _lib.RSN_ERR_CAPACITY:
-                raise
-            need = e.needed
-        out = torch.empty(max(need, 16), dtype=torch.uint8, device=src.device)
-    try:
-        got = _lib.call_dev(_lib.lib().rsn_lzss_decompress_dev, src.data_ptr(), n, out.data_ptr(), out.numel(), st)
-    except _lib.RsnError as e:
-        if e.code != _lib.RSN_ERR_CAPACITY:
-            raise
-        out = torch.empty(e.needed, dtype=torch.uint8, device=src.device)
-        got = _lib.call_dev(_lib.lib().rsn_lzss_decompress_dev, src.data_ptr(), n, out.data_ptr(), out.numel(), st)
-    return out[:got]
+    return _lib.dev_tensor(_lib.lib().rsn_lzss_decompress_dev, src, out, stream, 16 * n + (1 << 16) if n < (1 << 20) else None)
