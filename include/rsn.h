@@ -112,7 +112,9 @@ RSN_API int rsn_huffman_compress_batch(size_t n_chunks, const uint8_t *const *in
  * is that of the lowest-index failing member and rsn_last_error() reads "member <i>: " followed by the single call's message.
  * Null arrays, or a null ins[i] with a non-zero length, return RSN_ERR_ARG; without a device every call returns RSN_ERR_DEVICE.
  * Small members run many to a launch, a workgroup each, on the calling thread: LZSS compress inputs of at most
- * 1 KiB (window <= 0xFFFF), LZSS streams of at most 2 KiB that expand to at most 8 KiB, Huffman streams of a byte alphabet
+ * 1 KiB (window <= 0xFFFF) and, through a kernel of their own, of at most 64 KiB (window 1 to 4096) that escape to at most 68 KiB;
+ * LZSS streams of at most 2 KiB that expand to at most 8 KiB and, likewise, of at most 68 KiB that expand to at most 68 KiB
+ * (the mid-size classes only when the call holds at least 64 such members); Huffman streams of a byte alphabet
  * (2 to 128 symbols, codes of at most 32 bits) with at most 16 KiB of payload and 32 KiB of output.  Every other member -- and
  * one a kernel hands back -- takes the single call's path, in index order; RSN_BATCH_WORKERS / RSN_BATCH_DEVICES deal those
  * over workers as rsn_huffman_compress_batch deals its chunks.  The same input bytes may be passed to several calls at once. */

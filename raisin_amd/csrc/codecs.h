@@ -68,6 +68,22 @@ int huff_batch_decompress_group(Ctx &c, const std::vector<size_t> &idx, const ui
                                 const SmallTake &take, std::vector<size_t> &back, size_t *failed);
 int huff_batch_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
                               const SmallTake &take, std::vector<size_t> &back, size_t *failed);
+// ---- LZSS members above those cutoffs (lzss_mid.hip): the same contract, a workgroup per member that keeps the member's whole
+// escaped stream in LDS.  The encoder takes LZSS_MID_IN_MAX bytes with a window of 1 to 4096 and hands back what escapes to more than
+// LZSS_MID_E_MAX bytes (what LDS holds beside the search structure); the decoder takes a stream of at most LZSS_MID_E_MAX bytes that
+// expands to at most as many -- so every stream the encoder writes is one the decoder takes.  Fewer than LZSS_MID_GROUP_MIN such members
+// in a call are not grouped: one workgroup each against the whole device a single call has -- a group takes as long as its largest
+// member, 6.7 ms for 64 KiB of text, and from 64 members on it is no slower than the loop at every size (measured).
+// Mirrored as raisin_amd.lz.MID_IN_MAX / MID_E_MAX / MID_GROUP_MIN.
+constexpr uint32_t LZSS_MID_IN_MAX = 65536;
+constexpr uint32_t LZSS_MID_E_MAX = 69632;
+constexpr size_t LZSS_MID_GROUP_MIN = 64;
+bool lzss_mid_compress_takes(size_t n, int64_t window);            // asked after lzss_small_compress_takes: what that one does not take, up to LZSS_MID_IN_MAX, window 1 to 4096
+bool lzss_mid_decompress_takes(size_t n);                          // ... after lzss_small_decompress_takes: up to LZSS_MID_E_MAX of stream
+int lzss_mid_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
+                            const SmallTake &take, std::vector<size_t> &back, size_t *failed);
+int lzss_mid_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
+                              const SmallTake &take, std::vector<size_t> &back, size_t *failed);
 // until every member's status word (base + off[k]) differs from `pending`: polled for 5 ms, then the stream is queried until a time limit --
 // a kernel that never answers is RSN_ERR_DEVICE, the host never spins for ever
 int group_wait(Ctx &c, hipStream_t s, const uint8_t *base, const std::vector<uint32_t> &off, uint32_t pending, const char *what);

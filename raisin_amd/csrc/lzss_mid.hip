@@ -1,0 +1,425 @@
+// lzss_mid.hip -- the LZSS codec for the mid-size members of a batch: above lzss_small.hip's cutoffs, up to LZSS_MID_IN_MAX bytes to
+// compress and LZSS_MID_E_MAX bytes of stream to decompress.
+//
+// A directory of source files, configs, JSON documents or log slices is mostly 1 to 64 KiB a file.  The single call's general path was
+// built for gigabytes -- a dozen launches and three host round trips, 0.23 ms however few the bytes -- and the brute-force search of
+// lzss_small.hip looks at every distance for every position.  Here a member is ONE workgroup of a launch that holds many members, the
+// whole escaped stream of the member lies in LDS, and the search walks hash chains keyed on a position's first two bytes.
+//
+//   compress    EncodeOpeningSymbols (lzss.go:369-389) by a block-wide scan into LDS.  Then tile by tile (MID_TILE positions): the tile's
+//               positions join the chains of their two-byte keys (a ring of links that covers the window and the tile); every position
+//               walks its chain over the window -- the longest match that lies entirely inside the window, at its largest distance
+//               (lzss.go:166-184,418-421); the greedy chain (lzss.go:134-151) enters the tile where the tile before it left, and is marked by
+//               pointer doubling inside the tile; item sizes, a scan, the bytes (lzss.go:143,318-320), flushed in 16-byte units.
+//               A match of length 1 and no match give the same bytes and the same step, so a position without a two-byte candidate is a
+//               literal.  Runs and short periods (every candidate matches as far as it may) exceed MID_STEP_CAP and are handed back.
+//   decompress  the stream in chunks of MID_TILE bytes: every '<' parses its token (lzss.go:323-364), a scan gives the output offsets; the
+//               chunk's output in tiles of MID_TILE bytes in output order -- a source in an earlier tile is final, chains inside the tile
+//               are settled by pointer jumping; DecodeOpeningSymbols (lzss.go:391-406) as lzss_small.hip does it.
+// What the kernels do not take is handed back (MID_NOT_MINE) and goes through the single call, which also words the errors.
+// No loop waits for another workgroup, and every loop is bounded: the chain walk by the ring's size, the extensions by MID_STEP_CAP.
+#include "codecs.h"
+#include "lzss_match.h"
+
+namespace rsn {
+namespace {
+
+constexpr int MT = 1024;                          // threads of a workgroup
+constexpr uint32_t MID_TILE = 2048;               // positions of a tile (two per thread)
+constexpr uint32_t MID_W_MAX = 4096;              // the largest window (what the pipelined host call takes, too)
+constexpr uint32_t MID_RING = 8192;               // links kept: the window, rounded down to a sub-tile, and the tile in hand
+constexpr uint32_t MID_HEADS = 4096;              // chains (a 12-bit hash of the two-byte key)
+constexpr uint32_t MID_NONE = 0xFFFFFFFFu;
+constexpr uint32_t MID_PENDING = 0xFFFFFFFFu, MID_NOT_MINE = 0xFFFFFFFEu;
+constexpr uint32_t MID_STEP_CAP = 4096;           // eight-byte extension steps a thread spends on a tile (its two positions) before the member is handed back -- lzss_small.hip's SL_STEP_CAP, for the same two positions
+constexpr uint32_t E_PAD = 64;                    // zeros behind the escaped stream (an eight-byte load may start at its last byte)
+constexpr uint32_t E_MAX = LZSS_MID_E_MAX;
+
+// ---- LDS of the encoder (dynamic; offsets in bytes)
+constexpr uint32_t EL_FC = 0;                                   // the escaped stream
+constexpr uint32_t EL_RING = EL_FC + E_MAX + E_PAD;             // uint32[MID_RING]: the position that was the chain's head when this one joined
+constexpr uint32_t EL_HEAD = EL_RING + MID_RING * 4;            // uint32[MID_HEADS]
+constexpr uint32_t EL_KEY = EL_HEAD + MID_HEADS * 4;            // uint32[MID_TILE]: L << 16 | distance
+constexpr uint32_t EL_JMP = EL_KEY + MID_TILE * 4;              // uint16[2][MID_TILE + 8]
+constexpr uint32_t EL_ON = EL_JMP + 2 * (MID_TILE + 8) * 2;     // uint8[MID_TILE + 16]
+constexpr uint32_t EL_OUT = EL_ON + MID_TILE + 16;              // uint8[MID_TILE + 64]: at most 15 bytes carried over, the tile's items
+constexpr uint32_t EL_WAVE = EL_OUT + MID_TILE + 64;            // uint32[MT / 64 + 1 (+ 3)]
+constexpr uint32_t EL_MISC = EL_WAVE + (MT / 64 + 4) * 4;       // uint32[4]
+constexpr uint32_t EL_BYTES = EL_MISC + 16;
+constexpr uint32_t EL_IN = EL_RING;                             // the member as it came, until it is escaped: over the tile's arrays
+static_assert(EL_IN + LZSS_MID_IN_MAX + 16 <= EL_WAVE, "the raw member lies over the tile arrays, not over the scan's words");
+static_assert(EL_BYTES <= 160 * 1024 && EL_RING % 16 == 0 && EL_OUT % 16 == 0 && EL_WAVE % 4 == 0, "LDS of k_lzss_mid_enc");
+static_assert(MID_RING >= MID_W_MAX + MID_TILE + MT, "a link is never overwritten while a walk may still read it");
+
+// ---- LDS of the decoder
+constexpr uint32_t DL_IN = 0;                                   // the stream; in the end the result
+constexpr uint32_t DL_VAL = DL_IN + E_MAX + E_PAD;              // the escaped bytes
+constexpr uint32_t DL_SRC = DL_VAL + E_MAX + E_PAD;             // uint32[2][MID_TILE]: where a byte of the tile comes from
+constexpr uint32_t DL_COV = DL_SRC + 2 * MID_TILE * 4;          // uint8[MID_TILE + 64]: the byte of the chunk belongs to a token's text
+constexpr uint32_t DL_WAVE = DL_COV + MID_TILE + 64;
+constexpr uint32_t DL_BYTES = DL_WAVE + (MT / 64 + 4) * 4;
+static_assert(DL_BYTES <= 160 * 1024 && DL_VAL % 16 == 0 && DL_SRC % 16 == 0 && DL_WAVE % 4 == 0, "LDS of k_lzss_mid_dec");
+constexpr uint32_t MID_TOKEN_TEXT = 23;                         // '<' ten digits ',' ten digits '>'
+static_assert(MID_TOKEN_TEXT <= 32, "a token's text spills at most 32 bytes into the next chunk");
+
+__device__ __forceinline__ void mid_done(uint32_t *flag, uint32_t value) {
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// exclusive scan of one value per thread over the workgroup; *total: the sum
+__device__ __forceinline__ uint32_t mid_scan(uint32_t v, uint32_t *s_wave /*[MT / 64 + 1]*/, uint32_t *total) {
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += o; }
+    __syncthreads();                                                      // (the previous scan's readers are done with s_wave)
+    if (lane == 63) s_wave[wave] = inc;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        uint32_t w = threadIdx.x < MT / 64 ? s_wave[threadIdx.x] : 0u, wi = w;
+#pragma unroll
+        for (int d = 1; d < MT / 64; d <<= 1) { const uint32_t o = __shfl_up(wi, d, 64); if (lane >= (uint32_t)d) wi += o; }
+        if (threadIdx.x < MT / 64) s_wave[threadIdx.x] = wi - w;
+        if (threadIdx.x == MT / 64 - 1) s_wave[MT / 64] = wi;
+    }
+    __syncthreads();
+    *total = s_wave[MT / 64];
+    return s_wave[wave] + inc - v;
+}
+
+__device__ __forceinline__ uint32_t mid_digits(uint32_t v) { return v < 10 ? 1u : v < 100 ? 2u : v < 1000 ? 3u : v < 10000 ? 4u : 5u; }
+__device__ __forceinline__ uint32_t mid_hash(uint32_t b0, uint32_t b1) { return ((b0 | (b1 << 8)) * 0x9E3779B1u) >> 20; }
+
+// ---------------------------------------------------------------- compress
+__global__ __launch_bounds__(MT) void k_lzss_mid_enc(const SmallMember *__restrict__ tab, uint8_t *__restrict__ base, uint32_t W) {
+    extern __shared__ uint4 mid_lds[];
+    uint8_t *sm = reinterpret_cast<uint8_t *>(mid_lds);
+    uint8_t *s_fc = sm + EL_FC;
+    uint32_t *s_ring = reinterpret_cast<uint32_t *>(sm + EL_RING);
+    uint32_t *s_head = reinterpret_cast<uint32_t *>(sm + EL_HEAD);
+    uint32_t *s_key = reinterpret_cast<uint32_t *>(sm + EL_KEY);
+    uint16_t *s_jmp = reinterpret_cast<uint16_t *>(sm + EL_JMP);                  // [2][MID_TILE + 8]
+    uint8_t *s_on = sm + EL_ON;
+    uint8_t *s_out = sm + EL_OUT;
+    uint32_t *s_wave = reinterpret_cast<uint32_t *>(sm + EL_WAVE);
+    uint32_t *s_misc = reinterpret_cast<uint32_t *>(sm + EL_MISC);                // [0]: where the chain enters the next tile
+    const uint8_t *s_in = sm + EL_IN;
+    const SmallMember m = tab[blockIdx.x];
+    const uint8_t *hin = base + m.in_off;
+    uint8_t *hout = base + m.out_off;
+    uint32_t *flag = reinterpret_cast<uint32_t *>(base + m.status_off);
+    const uint32_t tid = threadIdx.x, n = m.n;
+    if (n > LZSS_MID_IN_MAX || W == 0 || W > MID_W_MAX) { mid_done(flag, MID_NOT_MINE); return; }   // (the host does not send these)
+    for (uint32_t u = tid; u * 16 < n; u += MT) reinterpret_cast<uint4 *>(sm + EL_IN)[u] = reinterpret_cast<const uint4 *>(hin)[u];   // (pinned host memory, zero behind n)
+    for (uint32_t i = tid; i < (E_MAX + E_PAD) / 4; i += MT) reinterpret_cast<uint32_t *>(s_fc)[i] = 0;
+    __syncthreads();
+    // ---- EncodeOpeningSymbols: 3C -> FF; FF -> 5C FF; 5C -> 5C 5C.  A run of ceil(n / MT) input bytes per thread.
+    uint32_t E;
+    {
+        const uint32_t per = (n + MT - 1) / MT, i0 = min(n, tid * per), i1 = min(n, i0 + per);
+        uint32_t cnt = 0;
+        for (uint32_t i = i0; i < i1; i++) { const uint32_t b = s_in[i]; cnt += (b == 0x5C || b == 0xFF) ? 2u : 1u; }
+        uint32_t at = mid_scan(cnt, s_wave, &E);
+        if (E > E_MAX) { mid_done(flag, MID_NOT_MINE); return; }                  // (uniform)
+        for (uint32_t i = i0; i < i1; i++) {
+            const uint32_t b = s_in[i];
+            if (b == 0x5C || b == 0xFF) { s_fc[at++] = 0x5C; s_fc[at++] = (uint8_t)b; } else s_fc[at++] = b == 0x3C ? (uint8_t)0xFF : (uint8_t)b;
+        }
+    }
+    __syncthreads();                                                              // (the raw member is no longer read: its LDS is the tile's now)
+    for (uint32_t i = tid; i < MID_HEADS; i += MT) s_head[i] = MID_NONE;
+    __syncthreads();
+    const uint32_t *fw = reinterpret_cast<const uint32_t *>(s_fc);
+    uint32_t entry = 0;                                                           // the greedy chain's first position in the tile, from the tile's start
+    uint32_t flushed = 0, carry = 0;                                              // bytes of the result in hout; bytes waiting at the front of s_out (< 16)
+    for (uint32_t t0 = 0; t0 < E; t0 += MID_TILE) {
+        const bool live = entry < MID_TILE;                                       // (a match may step over a whole tile: nothing to search or emit in it)
+        uint32_t steps = 0;
+        for (uint32_t sub = 0; sub < MID_TILE; sub += MT) {
+            // ---- the sub-tile's positions join their chains.  Between sub-tiles a chain is in descending order; inside one, in any order.
+            const uint32_t i = t0 + sub + tid;
+            const uint32_t h = i < E ? mid_hash(s_fc[i], s_fc[i + 1]) : 0u;
+            if (i < E) s_ring[i & (MID_RING - 1)] = atomicExch(&s_head[h], i);
+            __syncthreads();
+            // ---- the longest L >= 2 with fc[i, i + L) inside the window (L <= distance, L <= E - i), at its largest distance
+            if (live && i < E) {
+                const uint32_t cap = E - i;
+                uint32_t best = 0;
+                if (cap >= 2 && i >= 2) {
+                    const uint32_t jlo = i - min(i, W), floor_ = jlo & ~(uint32_t)(MT - 1);   // (a chain entry below floor_: everything behind it is older still)
+                    const unsigned long long pat = lds_load8(fw, i);
+                    uint32_t j = s_head[h];
+                    for (uint32_t visits = 0; j < E && j >= floor_ && visits < MID_RING && steps <= MID_STEP_CAP; visits++) {
+                        const uint32_t nxt = s_ring[j & (MID_RING - 1)];
+                        if (j + 2 <= i && j >= jlo) {
+                            const uint32_t d = i - j, lim = min(d, cap), bl = best >> 16;
+                            // (a candidate counts if it is at least as long as the best so far: the byte at that length decides for most)
+                            if (lim >= bl && (bl == 0 || s_fc[j + bl - 1] == s_fc[i + bl - 1])) {
+                                unsigned long long x = lds_load8(fw, j) ^ pat;
+                                uint32_t L = x ? (uint32_t)__builtin_ctzll(x) >> 3 : 8u;
+                                if (!x) {
+                                    uint32_t off = 8;
+                                    while (off < lim) {
+                                        x = lds_load8(fw, j + off) ^ lds_load8(fw, i + off);
+                                        steps++;
+                                        if (x) { off += (uint32_t)__builtin_ctzll(x) >> 3; break; }
+                                        off += 8;
+                                    }
+                                    L = off;
+                                }
+                                best = max(best, (min(L, lim) << 16) | d);        // longest, then farthest back (bytes.Index finds the leftmost, lzss.go:419)
+                            }
+                        }
+                        j = nxt;
+                    }
+                }
+                s_key[sub + tid] = best;
+            }
+            __syncthreads();                                                      // (the next sub-tile's links are written behind this)
+        }
+        if (!live) { entry -= MID_TILE; continue; }
+        if (__syncthreads_or(steps > MID_STEP_CAP)) { mid_done(flag, MID_NOT_MINE); return; }
+        // ---- the greedy chain inside the tile: r -> r + max(1, L) (lzss.go:139-142), MID_TILE: beyond the tile
+        const uint32_t R = min(MID_TILE, E - t0);
+        for (uint32_t r = tid; r <= MID_TILE; r += MT) {
+            s_jmp[r] = (uint16_t)(r < R ? min(MID_TILE, r + max(1u, s_key[r] >> 16)) : MID_TILE);
+            s_on[r] = r == entry;
+        }
+        __syncthreads();
+        int cur = 0;
+        for (uint32_t reach = 1; reach < MID_TILE + 1; reach <<= 1) {              // after the round: everything within 2 * reach - 1 steps of the entry
+            const uint16_t *ja = s_jmp + cur * (MID_TILE + 8);
+            uint16_t *jb = s_jmp + (cur ^ 1) * (MID_TILE + 8);
+            for (uint32_t r = tid; r < MID_TILE; r += MT) if (s_on[r]) s_on[ja[r]] = 1;
+            for (uint32_t r = tid; r <= MID_TILE; r += MT) jb[r] = ja[ja[r]];
+            cur ^= 1;
+            __syncthreads();
+        }
+        // ---- what every chain position puts out: a token iff it is shorter than what it stands for (lzss.go:143), else the bytes
+        uint32_t total = 0;
+        {
+            const uint32_t r0 = 2 * tid;
+            uint32_t sz[2] = {0, 0}, el[2] = {0, 0};
+            for (int k = 0; k < 2; k++) {
+                const uint32_t r = r0 + k;
+                if (r < R && s_on[r]) {
+                    const uint32_t key = s_key[r], L = key >> 16, d = key & 0xFFFFu;
+                    el[k] = L ? 3 + mid_digits(d) + mid_digits(L) : 0u;
+                    sz[k] = L == 0 ? 1u : (el[k] < L ? el[k] : L);
+                    if (r + max(1u, L) >= MID_TILE) s_misc[0] = r + max(1u, L) - MID_TILE;   // (one position of the tile: the chain's last in it)
+                }
+            }
+            uint32_t at = carry + mid_scan(sz[0] + sz[1], s_wave, &total);
+            for (int k = 0; k < 2; k++) {
+                const uint32_t r = r0 + k;
+                if (!sz[k]) continue;
+                const uint32_t key = s_key[r], L = key >> 16, d = key & 0xFFFFu;
+                if (L && el[k] < L) {                                              // "<" + itoa(d) + "," + itoa(L) + ">" (lzss.go:318-320)
+                    uint32_t p = at + el[k];
+                    s_out[--p] = '>';
+                    for (uint32_t v = L; ; v /= 10) { s_out[--p] = (uint8_t)('0' + v % 10); if (v < 10) break; }
+                    s_out[--p] = ',';
+                    for (uint32_t v = d; ; v /= 10) { s_out[--p] = (uint8_t)('0' + v % 10); if (v < 10) break; }
+                    s_out[--p] = '<';
+                } else for (uint32_t q = 0; q < sz[k]; q++) s_out[at + q] = s_fc[t0 + r + q];
+                at += sz[k];
+            }
+        }
+        __syncthreads();
+        // ---- whole 16-byte units go out; what is left waits at the front for the next tile's
+        const uint32_t avail = carry + total, units = avail >> 4, rem = avail & 15u;
+        if (tid < units) reinterpret_cast<uint4 *>(hout + flushed)[tid] = reinterpret_cast<const uint4 *>(s_out)[tid];
+        const uint32_t keep = tid < rem ? s_out[units * 16 + tid] : 0u;
+        entry = s_misc[0];
+        __syncthreads();
+        if (tid < rem) s_out[tid] = (uint8_t)keep;
+        flushed += units * 16; carry = rem;
+        __syncthreads();
+    }
+    if (tid == 0 && carry) reinterpret_cast<uint4 *>(hout + flushed)[0] = reinterpret_cast<const uint4 *>(s_out)[0];   // (the slot ends on a whole unit)
+    mid_done(flag, flushed + carry);
+}
+
+// ---------------------------------------------------------------- decompress
+__global__ __launch_bounds__(MT) void k_lzss_mid_dec(const SmallMember *__restrict__ tab, uint8_t *__restrict__ base) {
+    extern __shared__ uint4 mid_lds[];
+    uint8_t *sm = reinterpret_cast<uint8_t *>(mid_lds);
+    uint8_t *s_in = sm + DL_IN;
+    uint8_t *s_val = sm + DL_VAL;
+    uint32_t *s_src = reinterpret_cast<uint32_t *>(sm + DL_SRC);                   // [2][MID_TILE]
+    uint8_t *s_cov = sm + DL_COV;
+    uint32_t *s_wave = reinterpret_cast<uint32_t *>(sm + DL_WAVE);
+    const SmallMember m = tab[blockIdx.x];
+    const uint8_t *hin = base + m.in_off;
+    uint8_t *hout = base + m.out_off;
+    uint32_t *flag = reinterpret_cast<uint32_t *>(base + m.status_off);
+    const uint32_t tid = threadIdx.x, n = m.n;
+    if (n > E_MAX) { mid_done(flag, MID_NOT_MINE); return; }                       // (the host does not send these)
+    for (uint32_t u = tid; u * 16 < n + 32; u += MT) reinterpret_cast<uint4 *>(s_in)[u] = u * 16 < n ? reinterpret_cast<const uint4 *>(hin)[u] : make_uint4(0, 0, 0, 0);
+    for (uint32_t i = tid; i < MID_TILE + 64; i += MT) s_cov[i] = 0;
+    __syncthreads();
+    uint32_t E = 0;                                                                // escaped bytes so far
+    for (uint32_t c0 = 0; c0 < n; c0 += MID_TILE) {
+        if (c0) {                                                                  // a token's text that began in the chunk before covers this one's first bytes
+            const uint32_t spill = tid < 32 ? s_cov[MID_TILE + tid] : 0u;
+            __syncthreads();
+            for (uint32_t i = tid; i < MID_TILE + 64; i += MT) s_cov[i] = i < 32 ? (uint8_t)spill : (uint8_t)0;
+            __syncthreads();
+        }
+        // ---- two bytes of the chunk per thread: a '<' parses its token (lzss.go:331-352) and covers its text
+        const uint32_t k0 = c0 + 2 * tid;
+        uint32_t tptr[2] = {0, 0}, tlen[2] = {0, 0}, ttl[2] = {0, 0};
+        bool bad = false;
+        for (int k = 0; k < 2; k++) {
+            const uint32_t p = k0 + k;
+            if (p >= n || s_in[p] != '<') continue;
+            uint32_t q = p + 1; unsigned long long v = 0; int nd = 0;
+            while (q < n && nd < 10 && s_in[q] >= '0' && s_in[q] <= '9') { v = v * 10 + (s_in[q] - '0'); q++; nd++; }
+            bool ok = nd && q < n && s_in[q] == ',' && v <= (unsigned long long)E_MAX;
+            tptr[k] = (uint32_t)v; q++; v = 0; nd = 0;
+            while (ok && q < n && nd < 10 && s_in[q] >= '0' && s_in[q] <= '9') { v = v * 10 + (s_in[q] - '0'); q++; nd++; }
+            ok = ok && nd && q < n && s_in[q] == '>' && v <= (unsigned long long)E_MAX && (uint32_t)v <= tptr[k];   // (len <= ptr: lzss.go:350's slice stays inside the data)
+            if (!ok) { bad = true; continue; }
+            tlen[k] = (uint32_t)v; ttl[k] = q + 1 - p;
+            for (uint32_t t = 0; t < ttl[k]; t++) s_cov[p - c0 + t] = 1;
+        }
+        if (__syncthreads_or(bad)) { mid_done(flag, MID_NOT_MINE); return; }       // (malformed: the single call words the error)
+        uint32_t outl[2] = {0, 0};
+        for (int k = 0; k < 2; k++) { const uint32_t p = k0 + k; if (p < n) outl[k] = ttl[k] ? tlen[k] : (s_cov[p - c0] ? 0u : 1u); }
+        uint32_t tot;
+        const uint32_t at0 = E + mid_scan(outl[0] + outl[1], s_wave, &tot);
+        if (tot > E_MAX - E) { mid_done(flag, MID_NOT_MINE); return; }             // expands beyond the limit (uniform; every outl <= E_MAX, 2048 of them: no overflow)
+        bad = (ttl[0] && tptr[0] > at0) || (ttl[1] && tptr[1] > at0 + outl[0]);   // the slice starts before the data (lzss.go:349)
+        if (__syncthreads_or(bad)) { mid_done(flag, MID_NOT_MINE); return; }
+        // ---- the chunk's output, a tile at a time in output order
+        for (uint32_t s0 = E; s0 < E + tot; s0 += MID_TILE) {
+            const uint32_t s1 = min(s0 + MID_TILE, E + tot);
+            uint32_t a = at0;
+            for (int k = 0; k < 2; k++) {
+                if (!outl[k]) continue;
+                const uint32_t lo = max(a, s0), hi = min(a + outl[k], s1);
+                if (ttl[k]) for (uint32_t q = lo; q < hi; q++) s_src[q - s0] = q - tptr[k];
+                else if (lo < hi) { s_src[a - s0] = a; s_val[a] = s_in[k0 + k]; }
+                a += outl[k];
+            }
+            __syncthreads();
+            // every byte's source: src <- src[src] while it lies in the tile and is not a literal (a copied byte lies before the byte that copies it)
+            int cur = 0;
+            for (int round = 0; round < 13; round++) {
+                bool moved = false;
+                const uint32_t *sa = s_src + cur * MID_TILE;
+                uint32_t *sb = s_src + (cur ^ 1) * MID_TILE;
+                for (uint32_t r = tid; r < s1 - s0; r += MT) {
+                    const uint32_t x = sa[r], y = x >= s0 ? sa[x - s0] : x;
+                    sb[r] = y; moved = moved || x != y;
+                }
+                cur ^= 1;
+                if (!__syncthreads_or(moved)) break;
+            }
+            for (uint32_t r = tid; r < s1 - s0; r += MT) { const uint32_t x = s_src[cur * MID_TILE + r]; if (x != s0 + r) s_val[s0 + r] = s_val[x]; }   // (x: a literal of the tile, or final in an earlier one)
+            __syncthreads();
+        }
+        E += tot;
+    }
+    if (E == 0) { mid_done(flag, MID_NOT_MINE); return; }                          // (an empty result is the single call's to word)
+    // ---- DecodeOpeningSymbols (lzss.go:391-406): a byte is escaped iff the run of 5C right in front of it has odd length, counted from the
+    //      last byte that is not 5C (as lzss_small.hip).  A run of ceil(E / MT) bytes per thread.
+    const uint32_t per = (E + MT - 1) / MT, q0 = min(E, tid * per), q1 = min(E, q0 + per);
+    uint32_t mine = 0;                                                            // 1 + the last of this thread's positions whose byte is not 5C; 0: none
+    for (uint32_t q = q0; q < q1; q++) if (s_val[q] != 0x5C) mine = q + 1;
+    uint32_t inc = mine, before = 0;                                              // before: the same for every position in front of q0
+    {
+        const uint32_t lane = tid & 63, wave = tid >> 6;
+        for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc = max(inc, o); }
+        __syncthreads();
+        if (lane == 63) s_wave[wave] = inc;
+        __syncthreads();
+        for (uint32_t w = 0; w < wave; w++) before = max(before, s_wave[w]);
+        uint32_t prev = __shfl_up(inc, 1, 64);
+        if (lane == 0) prev = 0;
+        before = max(before, prev);
+    }
+    uint32_t cnt = 0;
+    for (uint32_t q = q0, bq = before; q < q1; q++) {
+        const uint32_t b = s_val[q];
+        cnt += (((q - bq) & 1u) || b != 0x5C) ? 1u : 0u;
+        if (b != 0x5C) bq = q + 1;
+    }
+    uint32_t total;
+    uint32_t o = mid_scan(cnt, s_wave, &total);
+    uint8_t *s_res = s_in;                                                         // (the stream is parsed: its LDS takes the result)
+    for (uint32_t q = q0, bq = before; q < q1; q++) {
+        const uint32_t b = s_val[q];
+        const bool esc = (q - bq) & 1u;
+        if (esc || b != 0x5C) s_res[o++] = (uint8_t)(esc ? b : (b == 0xFF ? 0x3Cu : b));
+        if (b != 0x5C) bq = q + 1;
+    }
+    __syncthreads();
+    for (uint32_t u = tid; u * 16 < total; u += MT) reinterpret_cast<uint4 *>(hout)[u] = reinterpret_cast<const uint4 *>(s_res)[u];
+    mid_done(flag, total);
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------- the host side: groups in pinned staging, as lzss_small.hip's
+bool lzss_mid_compress_takes(size_t n, int64_t window) { return n != 0 && n <= LZSS_MID_IN_MAX && window >= 1 && window <= (int64_t)MID_W_MAX; }
+bool lzss_mid_decompress_takes(size_t n) { return n != 0 && n <= LZSS_MID_E_MAX; }
+
+namespace {
+// The members idx in groups: staging = the table, then per member its bytes (zero behind them), its output slot and its status word.
+int lzss_mid_groups(Ctx &c, bool enc, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
+                    const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    int rc = ctx_init(c); if (rc) return rc;
+    hipStream_t s = c.own_stream;
+    const char *what = enc ? "lzss batch compress" : "lzss batch decompress";
+    const size_t lds = enc ? EL_BYTES : DL_BYTES;
+    rc = func_dyn_lds(c, enc ? reinterpret_cast<const void *>(k_lzss_mid_enc) : reinterpret_cast<const void *>(k_lzss_mid_dec), lds);
+    if (rc) { *failed = idx.empty() ? 0 : idx[0]; return rc; }
+    auto in_bytes = [](size_t n) { return round_up(n, 16) + 32; };
+    auto out_bytes = [&](size_t n) { return enc ? round_up(std::min(2 * n, (size_t)LZSS_MID_E_MAX), 16) + 16 : (size_t)LZSS_MID_E_MAX + 16; };
+    auto need = [&](size_t n) { return sizeof(SmallMember) + in_bytes(n) + out_bytes(n) + 16; };
+    std::vector<uint32_t> st;
+    for (size_t j = 0; j < idx.size();) {
+        size_t k = j, bytes = 0;
+        while (k < idx.size() && k - j < SMALL_GROUP_MAX && (k == j || bytes + need(lens[idx[k]]) <= SMALL_GROUP_BYTES)) bytes += need(lens[idx[k++]]);
+        const size_t g = k - j;
+        void *pp; rc = pinned_buf(c, bytes + 64, &pp); if (rc) { *failed = idx[j]; return rc; }
+        uint8_t *base = (uint8_t *)pp;
+        SmallMember *tab = (SmallMember *)base;
+        size_t at = round_up(g * sizeof(SmallMember), 16);
+        st.assign(g, 0);
+        for (size_t q = 0; q < g; q++) {
+            const size_t i = idx[j + q], n = lens[i];
+            SmallMember &m = tab[q];
+            m.n = (uint32_t)n;
+            m.in_off = (uint32_t)at; memcpy(base + at, ins[i], n); memset(base + at + n, 0, in_bytes(n) - n); at += in_bytes(n);
+            m.out_off = (uint32_t)at; at += out_bytes(n);
+            m.status_off = st[q] = (uint32_t)at; *(uint32_t *)(base + at) = MID_PENDING; at += 16;
+        }
+        if (enc) RSN_LAUNCH("lzss_batch_mid_enc", k_lzss_mid_enc, dim3((uint32_t)g), dim3(MT), lds, s, (const SmallMember *)tab, base, (uint32_t)window);
+        else RSN_LAUNCH("lzss_batch_mid_dec", k_lzss_mid_dec, dim3((uint32_t)g), dim3(MT), lds, s, (const SmallMember *)tab, base);
+        rc = group_wait(c, s, base, st, MID_PENDING, what); if (rc) { *failed = idx[j]; return rc; }
+        for (size_t q = 0; q < g; q++) {
+            const size_t i = idx[j + q];
+            const uint32_t v = *(const uint32_t *)(base + st[q]);
+            if (v == MID_NOT_MINE) { back.push_back(i); continue; }
+            rc = take(i, base + tab[q].out_off, v); if (rc) { *failed = i; return rc; }
+        }
+        j = k;
+    }
+    return RSN_OK;
+}
+}  // namespace
+
+int lzss_mid_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
+                            const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    return lzss_mid_groups(c, true, idx, ins, lens, window, take, back, failed);
+}
+int lzss_mid_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
+                              const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    return lzss_mid_groups(c, false, idx, ins, lens, 0, take, back, failed);
+}
+
+}  // namespace rsn

@@ -1150,11 +1150,13 @@ struct ShardSync : FirstFailure {
 // rest -- a member a kernel handed back, larger ones, another alphabet -- goes through the single call's implementation, in index order,
 // dealt over the batch workers like the compress batch's chunks (deal_items).  Every outs[i] is what the single call returns for ins[i]; on
 // any failure every outs[i] is NULL and the answer is the lowest-index failing member's code, its message prefixed "member <i>: ".
-// `takes(i)`: member i is for the grouped kernel; `group`: runs those; `single(i, small)`: the single call for member i (small = false:
-// the member was handed back by a grouped kernel whose body the single call's small path shares).
+// `takes(i)`: the grouped class of member i -- 0: none (the single call), 1: the small kernel's, 2: the mid-size kernel's (LZSS only,
+// lzss_mid.hip), which is used when at least `mid_min` members of the call are of it; `group(c, cls, ...)`: runs the members of one class;
+// `single(i, small)`: the single call for member i (small = false: the member was handed back by a grouped kernel whose body the single
+// call's small path shares).
 template <class Takes, class Group, class Single>
 static int small_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens, bool back_skips_small,
-                       Takes takes, Group group, Single single) {
+                       size_t mid_min, Takes takes, Group group, Single single) {
     Ctx &c = ctx();
     int rc = batch_args(c, n, ins, lens, outs, out_lens, true, true); if (rc || n == 0) return rc;
     rc = ctx_init(c); if (rc) return rc;                                  // (no device: RSN_ERR_DEVICE -- there is no CPU path)
@@ -1162,12 +1164,18 @@ static int small_batch(size_t n, const uint8_t *const *ins, const size_t *lens, 
     struct Fail { size_t at = NONE; int rc = RSN_OK; std::string msg; };
     Fail f;
     auto note = [](Fail &x, size_t i, int code, const std::string &m) { if (i < x.at) { x.at = i; x.rc = code; x.msg = m; } };
-    std::vector<size_t> grouped, rest, back;
-    for (size_t i = 0; i < n; i++) (takes(i) ? grouped : rest).push_back(i);
+    std::vector<size_t> grouped, mid, rest, back;
+    for (size_t i = 0; i < n; i++) { const int cls = takes(i); (cls == 1 ? grouped : cls == 2 ? mid : rest).push_back(i); }
+    if (mid.size() < mid_min) { rest.insert(rest.end(), mid.begin(), mid.end()); mid.clear(); }   // (rest is sorted below)
+    const SmallTake take = take_into(c, outs, out_lens);
     if (!grouped.empty()) {
         size_t failed = NONE;
-        const SmallTake take = take_into(c, outs, out_lens);
-        rc = group(c, grouped, take, back, &failed);
+        rc = group(c, 1, grouped, take, back, &failed);
+        if (rc != RSN_OK) note(f, failed, rc, c.err);
+    }
+    if (!mid.empty() && f.at == NONE) {                                   // (a device failure above: nothing more is launched)
+        size_t failed = NONE;
+        rc = group(c, 2, mid, take, back, &failed);
         if (rc != RSN_OK) note(f, failed, rc, c.err);
     }
     std::vector<char> handed(back_skips_small ? n : 0, 0);
@@ -1208,28 +1216,30 @@ static int small_batch(size_t n, const uint8_t *const *ins, const size_t *lens, 
 }
 
 static int rsn_huffman_decompress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
-    return small_batch(n, ins, lens, outs, out_lens, false,
-                       [&](size_t i) { return huff_batch_decompress_may_take(lens[i]); },
-                       [&](Ctx &c, const std::vector<size_t> &idx, const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    return small_batch(n, ins, lens, outs, out_lens, false, 0,
+                       [&](size_t i) { return huff_batch_decompress_may_take(lens[i]) ? 1 : 0; },
+                       [&](Ctx &c, int, const std::vector<size_t> &idx, const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
                            return huff_batch_decompress_group(c, idx, ins, lens, take, back, failed);
                        },
                        [&](size_t i, bool small) { return rsn_huffman_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small); });
 }
 
 static int rsn_lzss_compress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, int64_t window, uint8_t **outs, size_t *out_lens) {
-    return small_batch(n, ins, lens, outs, out_lens, true,
-                       [&](size_t i) { return lzss_small_compress_takes(lens[i], window); },
-                       [&](Ctx &c, const std::vector<size_t> &idx, const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-                           return lzss_small_compress_group(c, idx, ins, lens, window, take, back, failed);
+    return small_batch(n, ins, lens, outs, out_lens, true, LZSS_MID_GROUP_MIN,
+                       [&](size_t i) { return lzss_small_compress_takes(lens[i], window) ? 1 : lzss_mid_compress_takes(lens[i], window) ? 2 : 0; },
+                       [&](Ctx &c, int cls, const std::vector<size_t> &idx, const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+                           return cls == 1 ? lzss_small_compress_group(c, idx, ins, lens, window, take, back, failed)
+                                           : lzss_mid_compress_group(c, idx, ins, lens, window, take, back, failed);
                        },
                        [&](size_t i, bool small) { return rsn_lzss_compress_impl(ins[i], lens[i], window, &outs[i], &out_lens[i], small); });
 }
 
 static int rsn_lzss_decompress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
-    return small_batch(n, ins, lens, outs, out_lens, true,
-                       [&](size_t i) { return lzss_small_decompress_takes(lens[i]); },
-                       [&](Ctx &c, const std::vector<size_t> &idx, const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-                           return lzss_small_decompress_group(c, idx, ins, lens, take, back, failed);
+    return small_batch(n, ins, lens, outs, out_lens, true, LZSS_MID_GROUP_MIN,
+                       [&](size_t i) { return lzss_small_decompress_takes(lens[i]) ? 1 : lzss_mid_decompress_takes(lens[i]) ? 2 : 0; },
+                       [&](Ctx &c, int cls, const std::vector<size_t> &idx, const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+                           return cls == 1 ? lzss_small_decompress_group(c, idx, ins, lens, take, back, failed)
+                                           : lzss_mid_decompress_group(c, idx, ins, lens, take, back, failed);
                        },
                        [&](size_t i, bool small) { return rsn_lzss_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small); });
 }

@@ -4,6 +4,12 @@ import io
 from . import _lib
 
 DefaultWindowSize = 4096  # lzss.go:35
+# The mid-size members of a batch (csrc/codecs.h: LZSS_MID_IN_MAX, LZSS_MID_E_MAX, LZSS_MID_GROUP_MIN; tests/test_lzss_mid_host.py holds
+# the two together): inputs above 1 KiB and up to MID_IN_MAX bytes (window 1 to 4096) and streams above 2 KiB and up to MID_E_MAX bytes
+# go many to a launch, a workgroup each, when a call holds at least MID_GROUP_MIN of them.
+MID_IN_MAX = 65536
+MID_E_MAX = 69632
+MID_GROUP_MIN = 64
 
 
 def CompressAsync(fileContents, useProgressBar=False, maxSearchBufferLength=DefaultWindowSize):
@@ -25,12 +31,15 @@ def Decompress(fileContents, useProgressBar=False):
 
 def CompressAsyncBatch(files, maxSearchBufferLength=DefaultWindowSize):
     """CompressAsync(f, False, maxSearchBufferLength) for every buffer of the list in one call (rsn_lzss_compress_batch): inputs of at most
-    1 KiB many to a launch, a workgroup each; the rest through the single call's path.  Each result equals CompressAsync(f)."""
+    1 KiB many to a launch, a workgroup each; inputs up to MID_IN_MAX bytes likewise, through a kernel of their own, when the window is 1 to
+    4096 and the list holds at least MID_GROUP_MIN of them; the rest through the single call's path.  Each result equals CompressAsync(f)."""
     return _lib.call_batch(_lib.lib().rsn_lzss_compress_batch, files, int(maxSearchBufferLength))
 
 
 def DecompressBatch(streams):
-    """Decompress(s) for every stream of the list in one call (rsn_lzss_decompress_batch); each result equals Decompress(s).  A failing
+    """Decompress(s) for every stream of the list in one call (rsn_lzss_decompress_batch); each result equals Decompress(s): streams of
+    at most 2 KiB many to a launch, streams up to MID_E_MAX bytes likewise (at least MID_GROUP_MIN of them), the rest through the single
+    call's path.  A failing
     stream raises for the whole list (the message names the lowest failing index: "member <i>: ...")."""
     return _lib.call_batch(_lib.lib().rsn_lzss_decompress_batch, streams)
 

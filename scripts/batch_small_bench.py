@@ -5,12 +5,19 @@ Huffman compress of those and of 16 KiB of text, Huffman decompress of those and
 (lzss,huffman: the two batch calls one after the other against a loop of two single calls per member).  Every time is the median of REPS
 runs of the whole list; both sides go through ctypes the same way.  `--single` first prints the single calls' own times per call (the
 small-input paths the batch shares its kernels with).  `--only` runs the rows whose call name contains one of its comma-separated words.
-Usage: python scripts/batch_small_bench.py [--single] [--reps R] [--k 16,256,4096] [--only huffman compress,lzss,huffman]"""
+
+`--mid` runs the rows of the mid-size LZSS class instead (csrc/lzss_mid.hip): LZSS compress and decompress of 4, 16 and 64 KiB of text and
+lzss,huffman of 4 and 16 KiB, for K in {2, 4, 16, 64, 256, 4096} (64 KiB: 1024 in place of 4096 -- result blocks of 256 MiB are a host
+cost of their own); with `--single` also the single calls at those sizes.  `--parent LIB` first runs the same rows in a child process on
+another build of the library (RSN_LIB_PATH: the parent commit's), so that one job on one box gives the three legs the cutoffs rest on:
+the parent's batch call and loop, this build's loop, this build's batch call.
+Usage: python scripts/batch_small_bench.py [--single] [--mid] [--parent LIB] [--reps R] [--k 16,256,4096] [--only huffman compress,lzss,huffman]"""
 import argparse
 import ctypes
 import os
 import random
 import statistics
+import subprocess
 import sys
 import time
 
@@ -34,7 +41,7 @@ def members(kind, k):
         return [README[0]] * k
     if kind == "25B":
         return [README[1]] * k
-    distinct = [text(i, {"1KiB": 1024, "16KiB": 16 << 10, "64KiB": 64 << 10}[kind]) for i in range(min(k, 64))]
+    distinct = [text(i, {"1KiB": 1024, "4KiB": 4 << 10, "16KiB": 16 << 10, "64KiB": 64 << 10}[kind]) for i in range(min(k, 64))]
     return [distinct[i % len(distinct)] for i in range(k)]
 
 
@@ -94,8 +101,14 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--k", default="16,256,4096")
     ap.add_argument("--only", default="")
+    ap.add_argument("--mid", action="store_true")
+    ap.add_argument("--parent", default="")
     a = ap.parse_args()
     only = [w for w in a.only.split(",") if w]
+    if a.parent:                                                          # the same rows on another build, in a process of its own
+        argv = [x for i, x in enumerate(sys.argv[1:]) if x != "--parent" and (i == 0 or sys.argv[i] != "--parent")]
+        sys.stdout.flush()
+        subprocess.run([sys.executable, os.path.abspath(__file__)] + argv, check=True, env=dict(os.environ, RSN_LIB_PATH=os.path.abspath(a.parent)))
     L = _lib.lib()
     print("library: %s" % os.path.basename(_lib.LIB_PATH))
     if a.single:
@@ -109,6 +122,9 @@ def main():
                  ("huffman compress", "rsn_huffman_compress", text(0, 1024), ()), ("huffman compress", "rsn_huffman_compress", text(0, 64 << 10), ()),
                  ("huffman decompress", "rsn_huffman_decompress", huffman.Compress(text(0, 16 << 10)), ()),
                  ("huffman decompress", "rsn_huffman_decompress", huffman.Compress(text(0, 64 << 10)), ())]
+        if a.mid:
+            cases = [("lzss compress", "rsn_lzss_compress", text(0, n << 10), (4096,)) for n in (4, 16, 64)]
+            cases += [("lzss decompress", "rsn_lzss_decompress", lz.CompressAsync(text(0, n << 10)), ()) for n in (4, 16, 64)]
         for label, name, data, extra in cases:
             run = loop_fn(L, name, [data] * 200, extra)
             run()
@@ -119,11 +135,20 @@ def main():
             ("huffman decompress", "rsn_huffman_decompress_batch", "rsn_huffman_decompress", ("13B", "25B", "1KiB", "16KiB", "64KiB"), ()),
             ("huffman compress", "rsn_huffman_compress_batch", "rsn_huffman_compress", ("13B", "25B", "1KiB", "16KiB"), ()),
             ("lzss,huffman", None, None, ("13B", "25B", "1KiB"), ())]
+    ks = [int(x) for x in a.k.split(",")]
+    if a.mid:
+        plan = [("lzss compress", "rsn_lzss_compress_batch", "rsn_lzss_compress", ("4KiB", "16KiB", "64KiB"), (4096,)),
+                ("lzss decompress", "rsn_lzss_decompress_batch", "rsn_lzss_decompress", ("4KiB", "16KiB", "64KiB"), ()),
+                ("lzss,huffman", None, None, ("4KiB", "16KiB"), ())]
+        if a.k == ap.get_default("k"):
+            ks = [2, 4, 16, 64, 256, 4096]
     for label, bname, sname, kinds, extra in plan:
         if only and not any(w == label or w in label.replace(",", " ").split() for w in only):
             continue
         for kind in kinds:
-            for k in [int(x) for x in a.k.split(",")]:
+            for k in ks:
+                if kind == "64KiB" and k > 1024:
+                    k = 1024
                 src = members(kind, k)
                 if label == "lzss decompress":
                     bufs = lz.CompressAsyncBatch(src)
