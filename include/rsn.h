@@ -100,7 +100,8 @@ RSN_API int rsn_lzss_decompress(const uint8_t *in, size_t n, uint8_t **out, size
  * rsn_huffman_compress() returns for ins[i]; on any error every outs[i] is NULL.
  * When at least two chunks are of 2 B to 16 KiB, those run grouped first, on the calling thread:
  * one launch per group, a workgroup per chunk that builds the chunk's own tree.
- * A grouped chunk with a byte >= 0x80 or a single distinct byte is handed back to the pipeline.
+ * Chunks above 16 KiB and up to 64 KiB run grouped the same way through a kernel of their own when the call holds at least
+ * four of them.  A grouped chunk with a byte >= 0x80 or a single distinct byte is handed back to the pipeline.
  * (RSN_BATCH_WORKERS, RSN_BATCH_KEEP_MIB: see rsn_api.hip / INTEGRATION.md.) */
 RSN_API int rsn_huffman_compress_batch(size_t n_chunks, const uint8_t *const *ins, const size_t *lens,
                                uint8_t **outs, size_t *out_lens);
@@ -115,7 +116,8 @@ RSN_API int rsn_huffman_compress_batch(size_t n_chunks, const uint8_t *const *in
  * 1 KiB (window <= 0xFFFF) and, through a kernel of their own, of at most 64 KiB (window 1 to 4096) that escape to at most 68 KiB;
  * LZSS streams of at most 2 KiB that expand to at most 8 KiB and, likewise, of at most 68 KiB that expand to at most 68 KiB
  * (the mid-size classes only when the call holds at least 64 such members); Huffman streams of a byte alphabet
- * (2 to 128 symbols, codes of at most 32 bits) with at most 16 KiB of payload and 32 KiB of output.  Every other member -- and
+ * (2 to 128 symbols, codes of at most 32 bits) with at most 16 KiB of payload and 32 KiB of output and, through a kernel of
+ * their own when the call holds at least four such streams, with at most 56 KiB of payload and 64 KiB of output.  Every other member -- and
  * one a kernel hands back -- takes the single call's path, in index order; RSN_BATCH_WORKERS / RSN_BATCH_DEVICES deal those
  * over workers as rsn_huffman_compress_batch deals its chunks.  The same input bytes may be passed to several calls at once. */
 RSN_API int rsn_huffman_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens);

@@ -84,6 +84,27 @@ int lzss_mid_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_
                             const SmallTake &take, std::vector<size_t> &back, size_t *failed);
 int lzss_mid_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
                               const SmallTake &take, std::vector<size_t> &back, size_t *failed);
+// ---- Huffman members above the cutoffs of huff_small.hip's batch kernels (huff_mid.hip): the same contract, a workgroup of 1024
+// threads per member that keeps the whole member and the whole image of its stream in LDS, one workgroup to a CU.  The encoder takes more
+// than 16 KiB and at most HUFF_MID_IN_MAX bytes of a byte alphabet (every byte < 0x80, two distinct bytes at least) and hands the rest
+// back; a byte of such an alphabet codes in at most 7 bits, so its payload is at most 7/8 of the input: HUFF_MID_PAY_MAX.  The decoder
+// takes a stream whose header promises at most HUFF_MID_OUT_MAX bytes from at most HUFF_MID_PAY_MAX bytes of payload, and that
+// k_huff_batch_dec's workgroup does not hold -- so every stream the encoder writes is one a grouped decoder takes.  Fewer than
+// HUFF_MID_GROUP_MIN such members in a call are not grouped: a workgroup each against the whole device a single call has -- two members
+// lose to the loop of single calls (0.6x to compress), from four on no size does in either direction (measured).
+// Mirrored as raisin_amd.huffman.MID_IN_MAX / MID_PAY_MAX / MID_OUT_MAX / MID_GROUP_MIN.
+constexpr uint32_t HUFF_MID_IN_MAX = 65536;
+constexpr uint32_t HUFF_MID_PAY_MAX = 57344;
+constexpr uint32_t HUFF_MID_OUT_MAX = 65536;
+constexpr size_t HUFF_MID_GROUP_MIN = 4;
+static_assert((unsigned long long)HUFF_MID_PAY_MAX * 8 >= (unsigned long long)HUFF_MID_IN_MAX * 7 && HUFF_MID_OUT_MAX >= HUFF_MID_IN_MAX,
+              "the decoder takes every stream the encoder writes");
+bool huff_mid_compress_takes(size_t n);                            // asked after huff_batch_compress_takes: above it, up to HUFF_MID_IN_MAX
+bool huff_mid_decompress_takes(const uint8_t *in, size_t n);       // by the stream's header: payload and promised output within the limits above, one of them beyond k_huff_batch_dec's
+int huff_mid_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
+                            const SmallTake &take, std::vector<size_t> &back, size_t *failed);
+int huff_mid_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
+                              const SmallTake &take, std::vector<size_t> &back, size_t *failed);
 // until every member's status word (base + off[k]) differs from `pending`: polled for 5 ms, then the stream is queried until a time limit --
 // a kernel that never answers is RSN_ERR_DEVICE, the host never spins for ever
 int group_wait(Ctx &c, hipStream_t s, const uint8_t *base, const std::vector<uint32_t> &off, uint32_t pending, const char *what);

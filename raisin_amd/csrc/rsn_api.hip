@@ -1095,14 +1095,21 @@ static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const
     // Members of 2 B to 16 KiB run grouped on this thread (huff_batch_compress_group: one launch of k_huff_batch_enc per group, every member
     // its own workgroup and its own tree) when there are at least HUFF_GROUP_MIN of them.  The rest -- larger members, and the members the
     // kernel hands back (runes, a single symbol) -- take the pipeline below, as every member did before, dealt over the batch workers.
-    std::vector<size_t> grouped, rest;
-    for (size_t i = 0; i < n_chunks; i++) (huff_batch_compress_takes(lens[i]) ? grouped : rest).push_back(i);
-    if (grouped.size() < HUFF_GROUP_MIN) { rest.insert(rest.end(), grouped.begin(), grouped.end()); grouped.clear(); std::sort(rest.begin(), rest.end()); }
-    if (!grouped.empty()) {
+    // Members above 16 KiB and up to HUFF_MID_IN_MAX are the mid class (huff_mid.hip: k_huff_mid_enc, one launch per group), grouped from
+    // HUFF_MID_GROUP_MIN of them.
+    std::vector<size_t> grouped, mid, rest;
+    for (size_t i = 0; i < n_chunks; i++) (huff_batch_compress_takes(lens[i]) ? grouped : huff_mid_compress_takes(lens[i]) ? mid : rest).push_back(i);
+    if (grouped.size() < HUFF_GROUP_MIN) { rest.insert(rest.end(), grouped.begin(), grouped.end()); grouped.clear(); }
+    if (mid.size() < HUFF_MID_GROUP_MIN) { rest.insert(rest.end(), mid.begin(), mid.end()); mid.clear(); }
+    std::sort(rest.begin(), rest.end());
+    for (int cls = 1; cls <= 2; cls++) {
+        const std::vector<size_t> &members = cls == 1 ? grouped : mid;
+        if (members.empty()) continue;
         std::vector<size_t> back;
         size_t failed = 0;
         const SmallTake take = take_into(c, outs, out_lens);
-        const int rc = huff_batch_compress_group(c, grouped, ins, lens, take, back, &failed);
+        const int rc = cls == 1 ? huff_batch_compress_group(c, members, ins, lens, take, back, &failed)
+                                : huff_mid_compress_group(c, members, ins, lens, take, back, &failed);
         if (rc != RSN_OK) { const std::string msg = c.err; return undo(rc, msg.c_str()); }
         rest.insert(rest.end(), back.begin(), back.end());
         std::sort(rest.begin(), rest.end());
@@ -1150,8 +1157,8 @@ struct ShardSync : FirstFailure {
 // rest -- a member a kernel handed back, larger ones, another alphabet -- goes through the single call's implementation, in index order,
 // dealt over the batch workers like the compress batch's chunks (deal_items).  Every outs[i] is what the single call returns for ins[i]; on
 // any failure every outs[i] is NULL and the answer is the lowest-index failing member's code, its message prefixed "member <i>: ".
-// `takes(i)`: the grouped class of member i -- 0: none (the single call), 1: the small kernel's, 2: the mid-size kernel's (LZSS only,
-// lzss_mid.hip), which is used when at least `mid_min` members of the call are of it; `group(c, cls, ...)`: runs the members of one class;
+// `takes(i)`: the grouped class of member i -- 0: none (the single call), 1: the small kernel's, 2: the mid-size kernel's (lzss_mid.hip,
+// huff_mid.hip), which is used when at least `mid_min` members of the call are of it; `group(c, cls, ...)`: runs the members of one class;
 // `single(i, small)`: the single call for member i (small = false: the member was handed back by a grouped kernel whose body the single
 // call's small path shares).
 template <class Takes, class Group, class Single>
@@ -1216,10 +1223,11 @@ static int small_batch(size_t n, const uint8_t *const *ins, const size_t *lens, 
 }
 
 static int rsn_huffman_decompress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
-    return small_batch(n, ins, lens, outs, out_lens, false, 0,
-                       [&](size_t i) { return huff_batch_decompress_may_take(lens[i]) ? 1 : 0; },
-                       [&](Ctx &c, int, const std::vector<size_t> &idx, const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-                           return huff_batch_decompress_group(c, idx, ins, lens, take, back, failed);
+    return small_batch(n, ins, lens, outs, out_lens, false, HUFF_MID_GROUP_MIN,
+                       [&](size_t i) { return huff_mid_decompress_takes(ins[i], lens[i]) ? 2 : huff_batch_decompress_may_take(lens[i]) ? 1 : 0; },
+                       [&](Ctx &c, int cls, const std::vector<size_t> &idx, const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+                           return cls == 1 ? huff_batch_decompress_group(c, idx, ins, lens, take, back, failed)
+                                           : huff_mid_decompress_group(c, idx, ins, lens, take, back, failed);
                        },
                        [&](size_t i, bool small) { return rsn_huffman_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small); });
 }

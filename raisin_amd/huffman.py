@@ -24,7 +24,8 @@ def CompressBatch(chunks):
     """One complete .rsn segment per chunk, as engine.CompressFiles writes one file per input (engine.go:150-154).
     rsn_huffman_compress_batch runs chunks of 2 to BATCH_COMPRESS_INPUT_MAX bytes many to a launch, a workgroup each that builds the
     chunk's own tree on the device (byte alphabets; a chunk with a byte >= 0x80 or a single distinct byte is handed back), when at least
-    two chunks are of that size.  The other chunks are dealt out over the batch workers (chunk k -> device k mod G) and go through a
+    two chunks are of that size.  Chunks above that and up to MID_IN_MAX bytes are the mid class (csrc/huff_mid.hip: the same kernel body at
+    1024 threads, the whole chunk in LDS), grouped the same way when the call holds at least MID_GROUP_MIN of them.  The other chunks are dealt out over the batch workers (chunk k -> device k mod G) and go through a
     pipeline of upload / encode / download per device.  Each result equals Compress(chunk)."""
     return _lib.call_batch(_lib.lib().rsn_huffman_compress_batch, chunks)
 
@@ -39,9 +40,20 @@ BATCH_GROUP_PAYLOAD_MAX = 16384
 BATCH_GROUP_OUTPUT_MAX = 32768
 
 
+# The mid class of the two batch calls (csrc/codecs.h HUFF_MID_IN_MAX / HUFF_MID_PAY_MAX / HUFF_MID_OUT_MAX / HUFF_MID_GROUP_MIN):
+# chunks above BATCH_COMPRESS_INPUT_MAX and up to MID_IN_MAX bytes, and streams beyond the two limits above whose header promises at most
+# MID_OUT_MAX bytes from at most MID_PAY_MAX bytes of payload -- 7/8 of MID_IN_MAX, what a byte alphabet codes to at most -- go a workgroup
+# each through one launch per group when a call holds at least MID_GROUP_MIN of them.
+MID_IN_MAX = 65536
+MID_PAY_MAX = 57344
+MID_OUT_MAX = 65536
+MID_GROUP_MIN = 4
+
+
 def DecompressBatch(streams):
     """Decompress(stream) for every stream of the list in one call (rsn_huffman_decompress_batch): small streams many to a launch, a
-    workgroup each; the rest through the single call's path.  Each result equals Decompress(stream); a failing stream raises for the
+    workgroup each; streams of up to MID_PAY_MAX bytes of payload that decode to at most MID_OUT_MAX bytes likewise (csrc/huff_mid.hip)
+    when the call holds at least MID_GROUP_MIN of them; the rest through the single call's path.  Each result equals Decompress(stream); a failing stream raises for the
     whole list (the message names the lowest failing index: "member <i>: ...")."""
     return _lib.call_batch(_lib.lib().rsn_huffman_decompress_batch, streams)
 

@@ -11,7 +11,9 @@ lzss,huffman of 4 and 16 KiB, for K in {2, 4, 16, 64, 256, 4096} (64 KiB: 1024 i
 cost of their own); with `--single` also the single calls at those sizes.  `--parent LIB` first runs the same rows in a child process on
 another build of the library (RSN_LIB_PATH: the parent commit's), so that one job on one box gives the three legs the cutoffs rest on:
 the parent's batch call and loop, this build's loop, this build's batch call.
-Usage: python scripts/batch_small_bench.py [--single] [--mid] [--parent LIB] [--reps R] [--k 16,256,4096] [--only huffman compress,lzss,huffman]"""
+`--huff-mid` runs the rows of the mid-size Huffman class (csrc/huff_mid.hip) the same way: Huffman compress and decompress of 20, 32 and
+64 KiB of text and lzss,huffman of 64 KiB, for K in {2, 4, 16, 64, 256} and 1024 at 64 KiB; with `--single` also the single calls.
+Usage: python scripts/batch_small_bench.py [--single] [--mid | --huff-mid] [--parent LIB] [--reps R] [--k 16,256,4096] [--only huffman compress,lzss,huffman]"""
 import argparse
 import ctypes
 import os
@@ -41,7 +43,7 @@ def members(kind, k):
         return [README[0]] * k
     if kind == "25B":
         return [README[1]] * k
-    distinct = [text(i, {"1KiB": 1024, "4KiB": 4 << 10, "16KiB": 16 << 10, "64KiB": 64 << 10}[kind]) for i in range(min(k, 64))]
+    distinct = [text(i, {"1KiB": 1024, "4KiB": 4 << 10, "16KiB": 16 << 10, "20KiB": 20 << 10, "32KiB": 32 << 10, "64KiB": 64 << 10}[kind]) for i in range(min(k, 64))]
     return [distinct[i % len(distinct)] for i in range(k)]
 
 
@@ -102,6 +104,7 @@ def main():
     ap.add_argument("--k", default="16,256,4096")
     ap.add_argument("--only", default="")
     ap.add_argument("--mid", action="store_true")
+    ap.add_argument("--huff-mid", action="store_true")
     ap.add_argument("--parent", default="")
     a = ap.parse_args()
     only = [w for w in a.only.split(",") if w]
@@ -125,6 +128,9 @@ def main():
         if a.mid:
             cases = [("lzss compress", "rsn_lzss_compress", text(0, n << 10), (4096,)) for n in (4, 16, 64)]
             cases += [("lzss decompress", "rsn_lzss_decompress", lz.CompressAsync(text(0, n << 10)), ()) for n in (4, 16, 64)]
+        if a.huff_mid:
+            cases = [("huffman compress", "rsn_huffman_compress", text(0, n << 10), ()) for n in (20, 32, 64)]
+            cases += [("huffman decompress", "rsn_huffman_decompress", huffman.Compress(text(0, n << 10)), ()) for n in (20, 32, 64)]
         for label, name, data, extra in cases:
             run = loop_fn(L, name, [data] * 200, extra)
             run()
@@ -142,6 +148,12 @@ def main():
                 ("lzss,huffman", None, None, ("4KiB", "16KiB"), ())]
         if a.k == ap.get_default("k"):
             ks = [2, 4, 16, 64, 256, 4096]
+    if a.huff_mid:
+        plan = [("huffman compress", "rsn_huffman_compress_batch", "rsn_huffman_compress", ("20KiB", "32KiB", "64KiB"), ()),
+                ("huffman decompress", "rsn_huffman_decompress_batch", "rsn_huffman_decompress", ("20KiB", "32KiB", "64KiB"), ()),
+                ("lzss,huffman", None, None, ("64KiB",), ())]
+        if a.k == ap.get_default("k"):
+            ks = [2, 4, 16, 64, 256, 1024]
     for label, bname, sname, kinds, extra in plan:
         if only and not any(w == label or w in label.replace(",", " ").split() for w in only):
             continue
@@ -149,6 +161,8 @@ def main():
             for k in ks:
                 if kind == "64KiB" and k > 1024:
                     k = 1024
+                if a.huff_mid and kind != "64KiB" and k > 256:
+                    continue
                 src = members(kind, k)
                 if label == "lzss decompress":
                     bufs = lz.CompressAsyncBatch(src)
