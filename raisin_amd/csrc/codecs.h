@@ -47,51 +47,47 @@ int lzss_small_compress(Ctx &c, const uint8_t *in, size_t n, int64_t window, con
 int lzss_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **out, size_t *out_n);
 int lzss_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t out_cap, size_t *out_n);
 
-// ---- many small members in one launch (the batch calls, rsn_api.hip).  The members `idx` (indexes into ins / lens) are packed
-// into the calling thread's pinned staging in groups of at most SMALL_GROUP_BYTES, and each group is ONE launch of a kernel that gives every
-// member a workgroup of its own.  take(i, p, len) receives member i's result (p: in the staging, valid during the call; a non-zero return
-// stops the call with that code); a member the kernel hands back -- or, for Huffman, one the grouped kernel does not take -- is appended to
-// `back`, in index order, for the caller's single call.  A device failure returns its code with *failed = the group's first member.
+// ---- many members in one launch (the batch calls, rsn_api.hip).  A CLASS of members is what one grouped kernel takes, a
+// workgroup per member: the small and the mid-size members of each layer and direction, eight rows.  The contract of every row:
+//   takes(in, n, window)   whether the member is of the class, asked in the order of batch_classes' rows (a later row need not exclude
+//                          what an earlier one takes).  Fewer than group_min members of a class in a call are not grouped: a workgroup each
+//                          against the whole device a single call has (the minimums are measured).
+//   run(...)               the members `idx` (indexes into ins / lens, all of the class) are packed into the calling thread's pinned
+//                          staging in groups of at most SMALL_GROUP_MAX members and SMALL_GROUP_BYTES, and each group is ONE launch
+//                          (run_groups, group_run.h).  take(i, p, len) receives member i's result (p: in the staging, valid during the
+//                          call; a non-zero return stops the call with that code); a member the kernel hands back -- or, for the Huffman
+//                          decoders, one whose header the host's plan refuses -- is appended to `back`, in index order, for the caller's
+//                          single call.  A failure returns its code with *failed = the group's first member (staging, launch, wait) or
+//                          the member itself (take).
 struct SmallMember { uint32_t in_off, n, out_off, status_off; };   // byte offsets into the group's staging
 constexpr size_t SMALL_GROUP_BYTES = (size_t)16 << 20;             // staging of one group (a member larger than that is a group of its own)
 constexpr size_t SMALL_GROUP_MAX = 4096;                           // members of one group
 using SmallTake = std::function<int(size_t i, const uint8_t *p, size_t len)>;
-bool lzss_small_compress_takes(size_t n, int64_t window);          // what lzss_small_compress takes (1 KiB, window <= 0xFFFF)
-bool lzss_small_decompress_takes(size_t n);                        // ... lzss_small_decompress (2 KiB of stream)
-bool huff_batch_decompress_may_take(size_t n);                     // a stream short enough to be looked at by huff_batch_decompress_group
-bool huff_batch_compress_takes(size_t n);                          // an input huff_batch_compress_group looks at (2 B to 16 KiB)
-int lzss_small_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
-                              const SmallTake &take, std::vector<size_t> &back, size_t *failed);
-int lzss_small_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                                const SmallTake &take, std::vector<size_t> &back, size_t *failed);
-int huff_batch_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                                const SmallTake &take, std::vector<size_t> &back, size_t *failed);
-int huff_batch_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                              const SmallTake &take, std::vector<size_t> &back, size_t *failed);
-// ---- LZSS members above those cutoffs (lzss_mid.hip): the same contract, a workgroup per member that keeps the member's whole
-// escaped stream in LDS.  The encoder takes LZSS_MID_IN_MAX bytes with a window of 1 to 4096 and hands back what escapes to more than
-// LZSS_MID_E_MAX bytes (what LDS holds beside the search structure); the decoder takes a stream of at most LZSS_MID_E_MAX bytes that
-// expands to at most as many -- so every stream the encoder writes is one the decoder takes.  Fewer than LZSS_MID_GROUP_MIN such members
-// in a call are not grouped: one workgroup each against the whole device a single call has -- a group takes as long as its largest
-// member, 6.7 ms for 64 KiB of text, and from 64 members on it is no slower than the loop at every size (measured).
-// Mirrored as raisin_amd.lz.MID_IN_MAX / MID_E_MAX / MID_GROUP_MIN.
+struct BatchClass {
+    const char *name;
+    size_t group_min;
+    bool (*takes)(const uint8_t *in, size_t n, int64_t window);
+    int (*run)(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
+               const SmallTake &take, std::vector<size_t> &back, size_t *failed);
+};
+// lzss_small.hip: what lzss_small_compress / _decompress take (1 KiB with a window <= 0xFFFF; 2 KiB of stream).
+// lzss_mid.hip: a workgroup keeps the member's whole escaped stream in LDS.  The encoder takes LZSS_MID_IN_MAX bytes with a window of 1 to
+// 4096 and hands back what escapes to more than LZSS_MID_E_MAX bytes (what LDS holds beside the search structure); the decoder takes a
+// stream of at most LZSS_MID_E_MAX bytes that expands to at most as many -- so every stream the encoder writes is one the decoder takes.
+// A group takes as long as its largest member, 6.7 ms for 64 KiB of text; from LZSS_MID_GROUP_MIN members on it is no slower than the
+// loop of single calls at every size.  Mirrored as raisin_amd.lz.MID_IN_MAX / MID_E_MAX / MID_GROUP_MIN.
 constexpr uint32_t LZSS_MID_IN_MAX = 65536;
 constexpr uint32_t LZSS_MID_E_MAX = 69632;
 constexpr size_t LZSS_MID_GROUP_MIN = 64;
-bool lzss_mid_compress_takes(size_t n, int64_t window);            // asked after lzss_small_compress_takes: what that one does not take, up to LZSS_MID_IN_MAX, window 1 to 4096
-bool lzss_mid_decompress_takes(size_t n);                          // ... after lzss_small_decompress_takes: up to LZSS_MID_E_MAX of stream
-int lzss_mid_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
-                            const SmallTake &take, std::vector<size_t> &back, size_t *failed);
-int lzss_mid_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                              const SmallTake &take, std::vector<size_t> &back, size_t *failed);
-// ---- Huffman members above the cutoffs of huff_small.hip's batch kernels (huff_mid.hip): the same contract, a workgroup of 1024
-// threads per member that keeps the whole member and the whole image of its stream in LDS, one workgroup to a CU.  The encoder takes more
-// than 16 KiB and at most HUFF_MID_IN_MAX bytes of a byte alphabet (every byte < 0x80, two distinct bytes at least) and hands the rest
-// back; a byte of such an alphabet codes in at most 7 bits, so its payload is at most 7/8 of the input: HUFF_MID_PAY_MAX.  The decoder
-// takes a stream whose header promises at most HUFF_MID_OUT_MAX bytes from at most HUFF_MID_PAY_MAX bytes of payload, and that
-// k_huff_batch_dec's workgroup does not hold -- so every stream the encoder writes is one a grouped decoder takes.  Fewer than
-// HUFF_MID_GROUP_MIN such members in a call are not grouped: a workgroup each against the whole device a single call has -- two members
-// lose to the loop of single calls (0.6x to compress), from four on no size does in either direction (measured).
+const BatchClass &lzss_small_class(bool compress), &lzss_mid_class(bool compress);
+// huff_small.hip: inputs of 2 B to 16 KiB (two members at least: a group's one serial tree against the host's); streams short enough for
+// k_huff_batch_dec's workgroup.
+// huff_mid.hip: a workgroup of 1024 threads keeps the whole member and the whole image of its stream in LDS, one workgroup to a CU.  The
+// encoder takes more than 16 KiB and at most HUFF_MID_IN_MAX bytes of a byte alphabet (every byte < 0x80, two distinct bytes at least) and
+// hands the rest back; a byte of such an alphabet codes in at most 7 bits, so its payload is at most 7/8 of the input: HUFF_MID_PAY_MAX.
+// The decoder takes, by its header, a stream that promises at most HUFF_MID_OUT_MAX bytes from at most HUFF_MID_PAY_MAX bytes of payload,
+// and that k_huff_batch_dec's workgroup does not hold -- so every stream the encoder writes is one a grouped decoder takes.  Two such
+// members lose to the loop of single calls (0.6x to compress), from HUFF_MID_GROUP_MIN on no size does in either direction.
 // Mirrored as raisin_amd.huffman.MID_IN_MAX / MID_PAY_MAX / MID_OUT_MAX / MID_GROUP_MIN.
 constexpr uint32_t HUFF_MID_IN_MAX = 65536;
 constexpr uint32_t HUFF_MID_PAY_MAX = 57344;
@@ -99,12 +95,23 @@ constexpr uint32_t HUFF_MID_OUT_MAX = 65536;
 constexpr size_t HUFF_MID_GROUP_MIN = 4;
 static_assert((unsigned long long)HUFF_MID_PAY_MAX * 8 >= (unsigned long long)HUFF_MID_IN_MAX * 7 && HUFF_MID_OUT_MAX >= HUFF_MID_IN_MAX,
               "the decoder takes every stream the encoder writes");
-bool huff_mid_compress_takes(size_t n);                            // asked after huff_batch_compress_takes: above it, up to HUFF_MID_IN_MAX
-bool huff_mid_decompress_takes(const uint8_t *in, size_t n);       // by the stream's header: payload and promised output within the limits above, one of them beyond k_huff_batch_dec's
-int huff_mid_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                            const SmallTake &take, std::vector<size_t> &back, size_t *failed);
-int huff_mid_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                              const SmallTake &take, std::vector<size_t> &back, size_t *failed);
+const BatchClass &huff_small_class(bool compress), &huff_mid_class(bool compress);
+// the rows of a layer and direction in order of precedence: LZSS asks its small class first, Huffman decompress its mid class (a short
+// stream may promise more output than k_huff_batch_dec's workgroup holds)
+enum class BatchLayer { HUFFMAN, LZSS };
+struct BatchRows {
+    const BatchClass *const *first; size_t n;
+    template <size_t N> BatchRows(const BatchClass *const (&rows)[N]) : first(rows), n(N) {}
+};
+inline BatchRows batch_classes(BatchLayer layer, bool compress) {
+    static const BatchClass *const huff_enc[] = {&huff_small_class(true), &huff_mid_class(true)}, *const huff_dec[] = {&huff_mid_class(false), &huff_small_class(false)};
+    static const BatchClass *const lzss_enc[] = {&lzss_small_class(true), &lzss_mid_class(true)}, *const lzss_dec[] = {&lzss_small_class(false), &lzss_mid_class(false)};
+    if (layer == BatchLayer::HUFFMAN) return compress ? BatchRows(huff_enc) : BatchRows(huff_dec);
+    return compress ? BatchRows(lzss_enc) : BatchRows(lzss_dec);
+}
+// until none of flags[0 .. n) is GROUP_PENDING (group_layout.h; the single small calls): polled for 5 ms, then the stream is waited for the
+// ordinary way -- a kernel that has not answered by then is RSN_ERR_DEVICE
+int flags_wait(Ctx &c, hipStream_t s, const uint32_t *flags, uint32_t n, const char *what);
 // until every member's status word (base + off[k]) differs from `pending`: polled for 5 ms, then the stream is queried until a time limit --
 // a kernel that never answers is RSN_ERR_DEVICE, the host never spins for ever
 int group_wait(Ctx &c, hipStream_t s, const uint8_t *base, const std::vector<uint32_t> &off, uint32_t pending, const char *what);

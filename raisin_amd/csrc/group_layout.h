@@ -1,0 +1,66 @@
+// group_layout.h -- the arithmetic of a group of batch members in pinned staging, as plain host code: no HIP include, so a CPU
+// test (tests/group_layout_test.cpp) checks what keeps a grouped kernel inside its buffers -- slots that do not overlap, zero padding
+// behind every input, 16-byte aligned offsets.  group_run.h's run_groups is the one user.
+//
+// Staging of a group of g members: a table of g entries of E bytes (E a multiple of 16), then per member its input slot (the member's
+// bytes, zeros behind them), its output slot and 16 bytes of status.  Input and output slots are whole 16-byte units.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+namespace rsn {
+
+// a member's status word until its workgroup answers / the answer "not mine": the member goes back to the caller's single call.  Every
+// other value is the length of the result.
+constexpr uint32_t GROUP_PENDING = 0xFFFFFFFFu, GROUP_BACK = 0xFFFFFFFEu;
+constexpr size_t GROUP_STATUS_BYTES = 16;
+
+constexpr size_t group_round16(size_t v) { return (v + 15) & ~(size_t)15; }
+// staging one member adds to its group
+constexpr size_t group_need(size_t entry_bytes, size_t in_bytes, size_t out_bytes) { return entry_bytes + in_bytes + out_bytes + GROUP_STATUS_BYTES; }
+
+// The group that starts at member lo of count: at most max_members members; the first always enters, a further one only while the group's
+// bytes stay within max_bytes (a member larger than that is a group of its own).  need(k): the staging of member k.
+struct GroupCut { size_t hi, bytes; };   // the group is [lo, hi)
+template <class Need>
+GroupCut next_group(size_t lo, size_t count, size_t max_members, size_t max_bytes, Need need) {
+    size_t k = lo, bytes = 0;
+    while (k < count && k - lo < max_members) {
+        const size_t b = need(k);
+        if (k != lo && bytes + b > max_bytes) break;
+        bytes += b; k++;
+    }
+    return {k, bytes};
+}
+
+// Hands out the offsets of a group's members in order; end(): the group's bytes so far -- after the last member the sum of group_need.
+struct MemberSlots { uint32_t in, out, status; };
+class GroupLayout {
+    size_t at_;
+public:
+    GroupLayout(size_t members, size_t entry_bytes) : at_(group_round16(members * entry_bytes)) {}
+    MemberSlots member(size_t in_bytes, size_t out_bytes) {
+        MemberSlots m{};
+        m.in = (uint32_t)at_; at_ += in_bytes;
+        m.out = (uint32_t)at_; at_ += out_bytes;
+        m.status = (uint32_t)at_; at_ += GROUP_STATUS_BYTES;
+        return m;
+    }
+    size_t end() const { return at_; }
+};
+
+// ---- the slots of the four classes.  An input slot leaves behind the member's n bytes the zeros its kernel's loads rely on: 32 bytes for
+// the LZSS kernels, 16 for the Huffman encoders, 64 for the Huffman decoders.
+constexpr size_t lzss_in_slot(size_t n) { return group_round16(n) + 32; }
+// e_max: the escaped bytes the class's kernel holds (an input escapes to at most twice its length)
+constexpr size_t lzss_enc_out_slot(size_t n, size_t e_max) { return group_round16(2 * n < e_max ? 2 * n : e_max) + 16; }
+constexpr size_t lzss_dec_out_slot(size_t e_max) { return e_max + 16; }               // whatever the stream's length
+constexpr size_t huff_enc_in_slot(size_t n) { return group_round16(n) + 16; }
+constexpr uint32_t HUFF_HDR_MAX = 1100;         // 128 entries of at most 5 digits + '|' + 2 bytes, + "\\\n" + pad
+constexpr uint32_t huff_small_enc_out_slot(uint32_t n) { return (HUFF_HDR_MAX + n + 15) & ~15u; }                    // holds header + 7n/8 + pad
+constexpr uint32_t huff_mid_enc_out_slot(uint32_t n) { return (HUFF_HDR_MAX + (7 * n + 7) / 8 + 3 + 15) & ~15u; }    // header + payload in whole words
+constexpr size_t huff_dec_in_slot(size_t sn) { return group_round16(sn) + 64; }       // sn: the stream from the 4-byte boundary the kernel reads from
+constexpr size_t huff_dec_out_slot(size_t expect) { return group_round16(expect) + 16; }   // expect: the bytes the header promises
+
+}  // namespace rsn

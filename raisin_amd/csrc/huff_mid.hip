@@ -11,7 +11,7 @@
 //   decompress  small_dec_body, one block alone, at 960 lanes of at most 480 bits (and the wavefront of the first lane's entry): the payload
 //               in LDS (56 KiB), the lanes' maps of up to four phases, a wavefront scan, the output image in LDS (64 KiB).
 // Both take about 130 KiB of the CU's 160 KiB of LDS, so a CU holds one workgroup, and 1024 threads are what fills its four SIMDs.
-// What a kernel does not take it hands back (HE_BACK / status 1), and that member goes through the single call, which words the errors.
+// What a kernel does not take it hands back (GROUP_BACK / status 1), and that member goes through the single call, which words the errors.
 // No workgroup waits for another; every loop is bounded by the member's size or a constant; the status word is a member's last store.
 #include "huff_small_body.h"
 
@@ -29,9 +29,8 @@ constexpr unsigned long long hm_fib(int k) { unsigned long long a = 0, b = 1; fo
 static_assert(hm_fib(24) <= HUFF_MID_IN_MAX && hm_fib(25) > HUFF_MID_IN_MAX, "the deepest code of a member is 22 bits: inside the 24 of the emit table");
 // the flat 7-bit code is a prefix code of a byte alphabet, and Huffman's is no longer than any: the payload is at most 7 n / 8 bytes
 static_assert((unsigned long long)HUFF_MID_IN_MAX * 7 <= (unsigned long long)HUFF_MID_PAY_MAX * 8, "the payload of the largest member");
-__host__ __device__ constexpr uint32_t hm_out_slot(uint32_t n) { return (HDR_MAX + (7 * n + 7) / 8 + 3 + 15) & ~15u; }   // bytes: header + payload in whole words, whole 16-byte units
 constexpr uint32_t HM_IMG_WORDS = ((HDR_MAX + HUFF_MID_PAY_MAX + 64) / 4 + 3) & ~3u;
-static_assert(hm_out_slot(HUFF_MID_IN_MAX) / 4 <= HM_IMG_WORDS && HM_IMG_WORDS % 4 == 0, "the image holds the largest member's slot, in 16-byte units");
+static_assert(huff_mid_enc_out_slot(HUFF_MID_IN_MAX) / 4 <= HM_IMG_WORDS && HM_IMG_WORDS % 4 == 0, "the image holds the largest member's slot, in 16-byte units");
 // ---- LDS of the encoder (dynamic; offsets in bytes).  Beside it huff_enc_body's own: 16 x 128 counts, the tables, the scan's words
 constexpr uint32_t EL_IN = 0;                                    // the member
 constexpr uint32_t EL_IMG = EL_IN + HUFF_MID_IN_MAX;             // the image of the stream
@@ -53,7 +52,7 @@ __global__ __launch_bounds__(HM_T) void k_huff_mid_enc(const SmallMember *__rest
     extern __shared__ uint4 hm_lds[];
     uint8_t *sm = reinterpret_cast<uint8_t *>(hm_lds);
     huff_enc_body<HM_T, HUFF_MID_IN_MAX, HM_IMG_WORDS, true>(tab, base, reinterpret_cast<uint4 *>(sm + EL_IN), reinterpret_cast<uint32_t *>(sm + EL_IMG),
-                                                             [](uint32_t n) { return hm_out_slot(n); });
+                                                             [](uint32_t n) { return huff_mid_enc_out_slot(n); });
 }
 
 __global__ __launch_bounds__(HM_T) void k_huff_mid_dec(const SmallDecArgs *__restrict__ tab) {
@@ -66,20 +65,11 @@ __global__ __launch_bounds__(HM_T) void k_huff_mid_dec(const SmallDecArgs *__res
     small_dec_body<HM_PAY_WORDS, HUFF_MID_OUT_MAX, false, HM_DL>(s_a, reinterpret_cast<uint32_t *>(sm + DL_PAY), sm + DL_OUT);
 }
 
-int launch_mid_enc(Ctx &c, hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
-    const int rc = func_dyn_lds(c, reinterpret_cast<const void *>(k_huff_mid_enc), EL_BYTES); if (rc) return rc;
-    RSN_LAUNCH("huff_batch_mid_enc", k_huff_mid_enc, dim3(g), dim3(HM_T), EL_BYTES, s, tab, base);
-    return RSN_OK;
-}
 int launch_mid_dec(Ctx &c, hipStream_t s, uint32_t g, const SmallDecArgs *tab) {
     const int rc = func_dyn_lds(c, reinterpret_cast<const void *>(k_huff_mid_dec), DL_BYTES); if (rc) return rc;
     RSN_LAUNCH("huff_batch_mid_dec", k_huff_mid_dec, dim3(g), dim3(HM_T), DL_BYTES, s, tab);
     return RSN_OK;
 }
-
-}  // namespace
-
-bool huff_mid_compress_takes(size_t n) { return n > HE_IN_MAX && n <= HUFF_MID_IN_MAX; }
 
 // The header alone decides (huffman.go:196-227,261): the payload is what lies behind "\\\n" and the pad byte, the output is the sum of the
 // counts.  This runs for every member of a decompress batch, the small kernel's thousands included, so it allocates nothing and looks at
@@ -87,7 +77,7 @@ bool huff_mid_compress_takes(size_t n) { return n > HE_IN_MAX && n <= HUFF_MID_I
 // than huff_batch_dec holds.  The sum is parse_header's scan of the counts without its table: an entry that occurs twice counts twice,
 // and runes are not looked at -- an upper bound that is exact for every header an encoder writes.  The group's own plan
 // (small_dec_plan) is exact and hands back what it refuses.
-bool huff_mid_decompress_takes(const uint8_t *in, size_t n) {
+bool mid_dec_takes(const uint8_t *in, size_t n, int64_t) {
     if (n < 8 || n > HDR_MAX + 8 + HUFF_MID_PAY_MAX || 8 * n <= HB_OUT_MAX) return false;
     size_t sep = (size_t)-1;
     for (size_t i = 0; i + 1 < std::min<size_t>(n, HDR_MAX + 8); i++) if (in[i] == 0x5C && in[i + 1] == 0x0A) { sep = i; break; }
@@ -106,13 +96,24 @@ bool huff_mid_decompress_takes(const uint8_t *in, size_t n) {
     return pay > HB_PAY_MAX || expect > HB_OUT_MAX;                    // (the rest is k_huff_batch_dec's)
 }
 
-int huff_mid_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                            const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return huff_enc_groups(c, HuffEncClass{hm_out_slot, launch_mid_enc}, idx, ins, lens, take, back, failed);
+bool mid_enc_takes(const uint8_t *, size_t n, int64_t) { return n > HE_IN_MAX && n <= HUFF_MID_IN_MAX; }   // (asked after the small class)
+int mid_enc_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t,
+                const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    return run_member_groups(c, "huffman batch compress", idx, ins, lens, huff_enc_in_slot, huff_mid_enc_out_slot,
+        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
+            const int rc = func_dyn_lds(c, reinterpret_cast<const void *>(k_huff_mid_enc), EL_BYTES); if (rc) return rc;
+            RSN_LAUNCH("huff_batch_mid_enc", k_huff_mid_enc, dim3(g), dim3(HM_T), EL_BYTES, s, tab, base);
+            return RSN_OK;
+        }, take, back, failed);
 }
-int huff_mid_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                              const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return huff_dec_groups(c, HuffDecClass{HM_DL, HM_S_MAX, HUFF_MID_PAY_MAX, HUFF_MID_OUT_MAX, launch_mid_dec}, idx, ins, lens, take, back, failed);
+int mid_dec_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t,
+                const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    return huff_dec_run(c, HuffDecShape{HM_DL, HM_S_MAX, HUFF_MID_PAY_MAX, HUFF_MID_OUT_MAX}, launch_mid_dec, idx, ins, lens, take, back, failed);
+}
+}  // namespace
+const BatchClass &huff_mid_class(bool compress) {
+    static const BatchClass enc = {"huffman mid compress", HUFF_MID_GROUP_MIN, mid_enc_takes, mid_enc_run}, dec = {"huffman mid decompress", HUFF_MID_GROUP_MIN, mid_dec_takes, mid_dec_run};
+    return compress ? enc : dec;
 }
 
 }  // namespace rsn

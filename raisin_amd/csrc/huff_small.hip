@@ -16,9 +16,6 @@
 // Many inputs at once (rsn_huffman_compress_batch): k_huff_batch_enc, ONE block per input of 2 B to 16 KiB that builds its own tree.
 // For byte alphabets (every symbol < 0x80); everything else -- runes, a single symbol,
 // foreign headers, malformed streams and their error texts -- returns 1 and takes the general path, which words the errors.
-#include <atomic>
-#include <chrono>
-
 #include "huff_small_body.h"
 #include "huff_plan_small.h"
 
@@ -172,29 +169,10 @@ __global__ __launch_bounds__(DT) void k_huff_batch_dec(const SmallDecArgs *__res
 __global__ __launch_bounds__(HE_T) void k_huff_batch_enc(const SmallMember *__restrict__ tab, uint8_t *__restrict__ base) {
     __shared__ uint4 s_in[HE_IN_MAX / 16];
     __shared__ uint32_t s_img[HE_IMG_WORDS];
-    huff_enc_body<HE_T, HE_IN_MAX, HE_IMG_WORDS, false>(tab, base, s_in, s_img, [](uint32_t n) { return he_out_slot(n); });
+    huff_enc_body<HE_T, HE_IN_MAX, HE_IMG_WORDS, false>(tab, base, s_in, s_img, [](uint32_t n) { return huff_small_enc_out_slot(n); });
 }
 
 
-}  // namespace
-
-namespace {
-// until none of f[0 .. n) is FLAG_PENDING; a kernel that has not answered within 5 ms is waited for the ordinary way
-int wait_flags(Ctx &c, hipStream_t s, const uint32_t *f, uint32_t n) {
-    const volatile uint32_t *vf = f;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t spins = 1;; spins++) {
-        uint32_t pending = 0;
-        for (uint32_t i = 0; i < n; i++) pending |= vf[i] == FLAG_PENDING;
-        if (!pending) { std::atomic_thread_fence(std::memory_order_acquire); return RSN_OK; }
-        if ((spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) {
-            RSN_HIP(hipStreamSynchronize(s));
-            for (uint32_t i = 0; i < n; i++) if (vf[i] == FLAG_PENDING) return c.fail(RSN_ERR_DEVICE, "huffman: a small-input kernel finished without its answer");
-            return RSN_OK;
-        }
-        __builtin_ia32_pause();
-    }
-}
 }  // namespace
 
 // 1: not an input for this path (the caller takes the general one)
@@ -213,7 +191,7 @@ int huff_small_compress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **out
     uint32_t *done = hi + ST_MAX;
     for (uint32_t t = 0; t < n_tiles; t++) { hi[t] = FLAG_PENDING; done[t] = FLAG_PENDING; }
     RSN_LAUNCH("huff_small_hist", k_small_hist, dim3(n_tiles), dim3(128), 0, s, (const uint4 *)(pin + PIN_IN), (uint32_t)n, (uint4 *)dp, th, hi);
-    rc = wait_flags(c, s, hi, n_tiles); if (rc) return rc;
+    rc = flags_wait(c, s, hi, n_tiles, "huffman"); if (rc) return rc;
     uint32_t cnt[128] = {0};
     for (uint32_t t = 0; t < n_tiles; t++) {
         if (hi[t]) return 1;                                                    // a byte >= 0x80: runes (huffman.go:309)
@@ -246,7 +224,7 @@ int huff_small_compress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **out
     }
     memcpy(a.hdr, hdr.data(), H);
     RSN_LAUNCH("huff_small_emit", k_small_emit, dim3(n_tiles), dim3(256), 0, s, a);
-    rc = wait_flags(c, s, done, n_tiles); if (rc) return rc;
+    rc = flags_wait(c, s, done, n_tiles, "huffman"); if (rc) return rc;
     *out = pin + PIN_OUT; *out_n = total;
     return RSN_OK;
 }
@@ -321,65 +299,40 @@ int huff_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **o
     a.g_maps = (uint32_t *)dp; a.g_flags = a.g_maps + DEC_BLOCKS * 32;
     for (uint32_t b = 0; b <= DEC_BLOCKS; b++) status[b] = FLAG_PENDING;
     RSN_LAUNCH("huff_small_dec", k_small_dec, dim3(n_blk), dim3(DT), 0, s, a);
-    rc = wait_flags(c, s, status, n_blk); if (rc) return rc;
+    rc = flags_wait(c, s, status, n_blk, "huffman"); if (rc) return rc;
     for (uint32_t b = 0; b < n_blk; b++) if (status[b] != 0) return 1;
     *out = pin + PIN_OUT; *out_n = status[DEC_BLOCKS];
     return RSN_OK;
 }
 
-bool huff_batch_decompress_may_take(size_t n) { return n >= 8 && n <= HDR_MAX + 8 + HB_PAY_MAX; }
-
-// Members in groups of at most SMALL_GROUP_BYTES of staging: the table (a SmallDecArgs per member), then per member its stream from the
-// 4-byte boundary the kernel reads from (zero behind it), its output slot and two status words (done / handed back, decoded bytes).
-// A stream the one-block decoder cannot take -- runes, over the cutoff, anything small_dec_plan refuses -- goes to `back` untouched.
-int huff_dec_groups(Ctx &c, const HuffDecClass &cls, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                    const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+// The members of a decoding class: a stream the one-workgroup decoder cannot take -- runes, over the cutoff, anything small_dec_plan
+// refuses -- goes to `back` untouched; the rest in groups (run_groups): the table entry is the plan's SmallDecArgs with its pointers into
+// the staging, the input the stream from the 4-byte boundary the kernel reads from, and two status words (done / handed back, decoded bytes).
+int huff_dec_run(Ctx &c, const HuffDecShape &shape, HuffDecLaunch launch, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
+                 const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
     struct Plan { size_t i, A0; unsigned long long expect; SmallDecArgs a; };
     std::vector<Plan> plans;
     plans.reserve(idx.size());
     for (size_t i : idx) {
         Plan p; p.i = i;
-        if (lens[i] < 8 || lens[i] > HDR_MAX + 8 + cls.pay_max || small_dec_plan(ins[i], lens[i], cls.lanes, cls.s_max, p.a, &p.A0, &p.expect) != RSN_OK ||
-            p.expect > cls.out_max) { back.push_back(i); continue; }
+        if (lens[i] < 8 || lens[i] > HDR_MAX + 8 + shape.pay_max || small_dec_plan(ins[i], lens[i], shape.lanes, shape.s_max, p.a, &p.A0, &p.expect) != RSN_OK ||
+            p.expect > shape.out_max) { back.push_back(i); continue; }
         plans.push_back(p);
     }
-    if (plans.empty()) return RSN_OK;
-    int rc = ctx_init(c); if (rc) { *failed = plans[0].i; return rc; }
-    hipStream_t s = c.own_stream;
-    auto need = [&](const Plan &p) { return sizeof(SmallDecArgs) + round_up(lens[p.i] - p.A0, 16) + 64 + round_up(p.expect, 16) + 16 + 16; };
-    std::vector<uint32_t> st;
-    std::vector<size_t> taken_back;
-    for (size_t j = 0; j < plans.size();) {
-        size_t k = j, bytes = 0;
-        while (k < plans.size() && k - j < SMALL_GROUP_MAX && (k == j || bytes + need(plans[k]) <= SMALL_GROUP_BYTES)) bytes += need(plans[k++]);
-        const size_t g = k - j;
-        void *pp; rc = pinned_buf(c, bytes + 64, &pp); if (rc) { *failed = plans[j].i; return rc; }
-        uint8_t *base = (uint8_t *)pp;
-        SmallDecArgs *tab = (SmallDecArgs *)base;
-        size_t at = round_up(g * sizeof(SmallDecArgs), 16);
-        st.assign(g, 0);
-        for (size_t q = 0; q < g; q++) {
-            Plan &p = plans[j + q];
-            const size_t n = lens[p.i], sn = n - p.A0;
-            SmallDecArgs &a = tab[q];
-            a = p.a;
-            memcpy(base + at, ins[p.i] + p.A0, sn); memset(base + at + sn, 0, round_up(sn, 16) + 64 - sn);
-            a.pay = (const uint32_t *)(base + at); at += round_up(sn, 16) + 64;
-            a.hout = base + at; a.out_max = (uint32_t)p.expect; at += round_up(p.expect, 16) + 16;
-            a.status = (uint32_t *)(base + at); a.status[0] = FLAG_PENDING; a.status[1] = 0; st[q] = (uint32_t)at; at += 16;
-        }
-        rc = cls.launch(c, s, (uint32_t)g, tab); if (rc) { *failed = plans[j].i; return rc; }
-        rc = group_wait(c, s, base, st, FLAG_PENDING, "huffman batch decompress"); if (rc) { *failed = plans[j].i; return rc; }
-        for (size_t q = 0; q < g; q++) {
-            const size_t i = plans[j + q].i;
-            const uint32_t *w = (const uint32_t *)(base + st[q]);
-            if (w[0] != 0) { taken_back.push_back(i); continue; }
-            rc = take(i, tab[q].hout, w[1]); if (rc) { *failed = i; return rc; }
-        }
-        j = k;
-    }
+    std::vector<size_t> handed;
+    const int rc = run_groups<SmallDecArgs>(c, "huffman batch decompress", plans.size(),
+        [&](size_t k) { const Plan &p = plans[k]; const size_t sn = lens[p.i] - p.A0; return GroupItem{p.i, ins[p.i] + p.A0, sn, huff_dec_in_slot(sn), huff_dec_out_slot(p.expect)}; },
+        [&](SmallDecArgs &a, size_t k, uint8_t *base, const MemberSlots &o) {
+            a = plans[k].a;
+            a.pay = (const uint32_t *)(base + o.in);
+            a.hout = base + o.out; a.out_max = (uint32_t)plans[k].expect;
+            a.status = (uint32_t *)(base + o.status); a.status[1] = 0;
+        },
+        [&](hipStream_t s, uint32_t g, const SmallDecArgs *tab, uint8_t *) { return launch(c, s, g, tab); },
+        [](const uint32_t *w) { return w[0] != 0 ? GROUP_BACK : w[1]; }, take, handed, failed);
+    if (rc) return rc;
     // (members refused up front and members handed back, in index order)
-    back.insert(back.end(), taken_back.begin(), taken_back.end());
+    back.insert(back.end(), handed.begin(), handed.end());
     std::sort(back.begin(), back.end());
     return RSN_OK;
 }
@@ -389,62 +342,26 @@ int launch_batch_dec(Ctx &c, hipStream_t s, uint32_t g, const SmallDecArgs *tab)
     RSN_LAUNCH("huff_batch_dec", k_huff_batch_dec, dim3(g), dim3(DT), 0, s, tab);
     return RSN_OK;
 }
-int launch_batch_enc(Ctx &c, hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
-    RSN_LAUNCH("huff_batch_enc", k_huff_batch_enc, dim3(g), dim3(HE_T), 0, s, tab, base);
-    return RSN_OK;
+bool batch_dec_takes(const uint8_t *, size_t n, int64_t) { return n >= 8 && n <= HDR_MAX + 8 + HB_PAY_MAX; }
+int batch_dec_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t,
+                  const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    return huff_dec_run(c, HuffDecShape{DL, HB_S_MAX, HB_PAY_MAX, HB_OUT_MAX}, launch_batch_dec, idx, ins, lens, take, back, failed);
+}
+bool batch_enc_takes(const uint8_t *, size_t n, int64_t) { return n >= 2 && n <= HE_IN_MAX; }
+// (the kernel hands back runes and a single symbol)
+int batch_enc_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t,
+                  const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    return run_member_groups(c, "huffman batch compress", idx, ins, lens, huff_enc_in_slot, huff_small_enc_out_slot,
+        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
+            RSN_LAUNCH("huff_batch_enc", k_huff_batch_enc, dim3(g), dim3(HE_T), 0, s, tab, base);
+            return RSN_OK;
+        }, take, back, failed);
 }
 }  // namespace
-
-int huff_batch_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                                const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return huff_dec_groups(c, HuffDecClass{DL, HB_S_MAX, HB_PAY_MAX, HB_OUT_MAX, launch_batch_dec}, idx, ins, lens, take, back, failed);
-}
-
-bool huff_batch_compress_takes(size_t n) { return n >= 2 && n <= HE_IN_MAX; }
-
-// Members in groups of at most SMALL_GROUP_BYTES of staging: the table (a SmallMember per member), then per member its bytes (zero behind
-// them), its output slot and its status word.  Every member of idx must be one huff_batch_compress_takes; the kernel hands back the
-// rest (runes, a single symbol), and those go to `back` in index order.
-int huff_enc_groups(Ctx &c, const HuffEncClass &cls, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                    const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    if (idx.empty()) return RSN_OK;
-    int rc = ctx_init(c); if (rc) { *failed = idx[0]; return rc; }
-    hipStream_t s = c.own_stream;
-    auto need = [&](size_t n) { return sizeof(SmallMember) + round_up(n, 16) + 16 + cls.slot((uint32_t)n) + 16; };
-    std::vector<uint32_t> st;
-    for (size_t j = 0; j < idx.size();) {
-        size_t k = j, bytes = 0;
-        while (k < idx.size() && k - j < SMALL_GROUP_MAX && (k == j || bytes + need(lens[idx[k]]) <= SMALL_GROUP_BYTES)) bytes += need(lens[idx[k++]]);
-        const size_t g = k - j;
-        void *pp; rc = pinned_buf(c, bytes + 64, &pp); if (rc) { *failed = idx[j]; return rc; }
-        uint8_t *base = (uint8_t *)pp;
-        SmallMember *tab = (SmallMember *)base;
-        size_t at = round_up(g * sizeof(SmallMember), 16);
-        st.assign(g, 0);
-        for (size_t q = 0; q < g; q++) {
-            const size_t i = idx[j + q], n = lens[i];
-            SmallMember &m = tab[q];
-            m.n = (uint32_t)n;
-            m.in_off = (uint32_t)at; memcpy(base + at, ins[i], n); memset(base + at + n, 0, round_up(n, 16) + 16 - n); at += round_up(n, 16) + 16;
-            m.out_off = (uint32_t)at; at += cls.slot((uint32_t)n);
-            m.status_off = st[q] = (uint32_t)at; *(uint32_t *)(base + at) = HE_PENDING; at += 16;
-        }
-        rc = cls.launch(c, s, (uint32_t)g, tab, base); if (rc) { *failed = idx[j]; return rc; }
-        rc = group_wait(c, s, base, st, HE_PENDING, "huffman batch compress"); if (rc) { *failed = idx[j]; return rc; }
-        for (size_t q = 0; q < g; q++) {
-            const size_t i = idx[j + q];
-            const uint32_t v = *(const uint32_t *)(base + st[q]);
-            if (v == HE_BACK) { back.push_back(i); continue; }
-            rc = take(i, base + tab[q].out_off, v); if (rc) { *failed = i; return rc; }
-        }
-        j = k;
-    }
-    return RSN_OK;
-}
-
-int huff_batch_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                              const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return huff_enc_groups(c, HuffEncClass{he_out_slot, launch_batch_enc}, idx, ins, lens, take, back, failed);
+// fewer than two members for the grouped encoder: every member takes the pipeline (a group's one serial tree against the host's)
+const BatchClass &huff_small_class(bool compress) {
+    static const BatchClass enc = {"huffman small compress", 2, batch_enc_takes, batch_enc_run}, dec = {"huffman small decompress", 1, batch_dec_takes, batch_dec_run};
+    return compress ? enc : dec;
 }
 
 }  // namespace rsn

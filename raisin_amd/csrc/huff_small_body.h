@@ -4,7 +4,7 @@
 // -- lanes, LDS sizes, where the large LDS arrays live -- as template parameters and arguments; DESIGN 4.7.
 #pragma once
 
-#include "codecs.h"
+#include "group_run.h"
 #include "huff_host.h"
 #include "huff_pathmap.h"
 #include "huff_plan_small.h"
@@ -31,25 +31,19 @@ static_assert(sizeof(SmallDecArgs) % 16 == 0, "a batch table entry is copied in 
 // at most s_max bits.  1 = not for the lane-map decoder (the caller takes the general one, which also words the errors).
 int small_dec_plan(const uint8_t *in, size_t n, uint32_t lanes, uint32_t s_max, SmallDecArgs &a, size_t *A0, unsigned long long *expect_out);
 
-// ---- the packing of a batch's members into groups of pinned staging, one launch a group (huff_small.hip), for a class of members: the
-// kernels of huff_small.hip and of huff_mid.hip differ in what one workgroup holds and in the launch.
-struct HuffDecClass {
+// ---- the decoding classes (huff_small.hip's k_huff_batch_dec, huff_mid.hip's k_huff_mid_dec) differ in what one workgroup holds and in the
+// launch: the plan in front of the packer and the packing itself are huff_dec_run's (huff_small.hip; run_groups, group_run.h).
+struct HuffDecShape {
     uint32_t lanes, s_max;                         // subsequences of one workgroup; bits of one at most
     uint32_t pay_max, out_max;                     // payload bytes / decoded bytes of a member at most
-    int (*launch)(Ctx &c, hipStream_t s, uint32_t members, const SmallDecArgs *tab);
 };
-struct HuffEncClass {
-    uint32_t (*slot)(uint32_t n);                  // bytes of the output slot of a member of n bytes (whole 16-byte units)
-    int (*launch)(Ctx &c, hipStream_t s, uint32_t members, const SmallMember *tab, uint8_t *base);
-};
-int huff_dec_groups(Ctx &c, const HuffDecClass &cls, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                    const SmallTake &take, std::vector<size_t> &back, size_t *failed);
-int huff_enc_groups(Ctx &c, const HuffEncClass &cls, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                    const SmallTake &take, std::vector<size_t> &back, size_t *failed);
+using HuffDecLaunch = int (*)(Ctx &c, hipStream_t s, uint32_t members, const SmallDecArgs *tab);
+int huff_dec_run(Ctx &c, const HuffDecShape &shape, HuffDecLaunch launch, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
+                 const SmallTake &take, std::vector<size_t> &back, size_t *failed);
 
 namespace {
 
-constexpr uint32_t HDR_MAX = 1100;              // 128 entries of at most 5 digits + '|' + 2 bytes, + "\\\n" + pad
+constexpr uint32_t HDR_MAX = HUFF_HDR_MAX;
 constexpr uint32_t DEC_STREAM_MAX = 65536 + 2048;   // bytes of a stream the decoder takes
 constexpr int DEC_K = 9;                        // index bits of the decoder's table, at most (every block builds the table: 11 bits cost 2 us more than they save on 64 KiB)
 constexpr int DEC_ROUNDS = 64;                  // rounds of the synchronisation before the general decoder is asked instead
@@ -57,6 +51,7 @@ constexpr int DEC_ROUNDS = 64;                  // rounds of the synchronisation
 // A block's last act: its stores to host memory made visible, then ONE word the host is polling (the host does not wait for the stream: a
 // hipStreamSynchronize is 5-10 us of wake-up, the kernel is as long).
 constexpr uint32_t FLAG_PENDING = 0xFFFFFFFFu;
+static_assert(FLAG_PENDING == GROUP_PENDING, "flags_wait and group_wait poll the decoder's words too");
 __device__ __forceinline__ void block_done(uint32_t *flag, uint32_t value) {
     __threadfence_system();
     __syncthreads();
@@ -420,14 +415,12 @@ __device__ __forceinline__ void small_dec_body(const SmallDecArgs &a, uint32_t *
 // build_tree / assign_codes) with the heap, the children and the codes held in VGPRs, a slot per lane: a read is a readlane, a write a select in
 // the one lane, both at a wave-uniform index.  The other wavefronts wait; the header's entries are already in place (a scan of their lengths).  Then every
 // byte's first bit is a block scan of the code lengths and the codes are ORed into an LDS image of the output words, as k_small_emit does.
-// Status word: the stream's length, or HE_BACK -- a byte >= 0x80 (runes, huffman.go:309), fewer than two distinct bytes, a code beyond
+// Status word: the stream's length, or GROUP_BACK -- a byte >= 0x80 (runes, huffman.go:309), fewer than two distinct bytes, a code beyond
 // 24 bits or a header beyond HDR_MAX (none of the last two below the member cutoff: counts below 2^15 give codes of at most 20 bits).
 constexpr uint32_t HE_IN_MAX = 16384;            // member cutoff: 128 symbols code at most 7 bits a byte, so at most 14 KiB of payload
 constexpr uint32_t HE_T = 256;
-constexpr uint32_t HE_PENDING = 0xFFFFFFFFu, HE_BACK = 0xFFFFFFFEu;
-__host__ __device__ constexpr uint32_t he_out_slot(uint32_t n) { return (HDR_MAX + n + 15) & ~15u; }   // bytes; holds header + 7n/8 + pad
 constexpr uint32_t HE_IMG_WORDS = (HDR_MAX + HE_IN_MAX * 7 / 8 + 64) / 4;
-static_assert(he_out_slot(HE_IN_MAX) / 4 >= HE_IMG_WORDS, "the image fits the largest member's slot");
+static_assert(huff_small_enc_out_slot(HE_IN_MAX) / 4 >= HE_IMG_WORDS, "the image fits the largest member's slot");
 
 // `R` VGPRs of a wavefront as 64 R slots (slot i: register i / 64 of lane i % 64); every index wave-uniform
 template <int R>
@@ -460,7 +453,7 @@ __device__ __forceinline__ void huff_enc_body(const SmallMember *__restrict__ ta
     const SmallMember m = tab[blockIdx.x];
     uint32_t *status = reinterpret_cast<uint32_t *>(base + m.status_off);
     const uint32_t n = m.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (n < 2 || n > IN_MAX) { block_done(status, HE_BACK); return; }    // (the host never sends one)
+    if (n < 2 || n > IN_MAX) { block_done(status, GROUP_BACK); return; }    // (the host never sends one)
     for (uint32_t i = tid; i < T / 64 * 128; i += T) (&s_cnt[0][0])[i] = 0;
     for (uint32_t i = tid; i < IMG_WORDS; i += T) s_img[i] = 0;
     __syncthreads();
@@ -485,7 +478,7 @@ __device__ __forceinline__ void huff_enc_body(const SmallMember *__restrict__ ta
         s_tot[tid] = c;
     }
     const uint32_t a = (uint32_t)__syncthreads_count(tid < 128 && c != 0);
-    if (high || a < 2) { block_done(status, HE_BACK); return; }
+    if (high || a < 2) { block_done(status, GROUP_BACK); return; }
     // ---- leaves in (count asc, byte asc) order; the header's entries ascending by byte, '\\' first when it would be last (huffman.go:312-318)
     const bool above_bs = __syncthreads_or(tid > 0x5C && tid < 128 && c != 0);
     const bool bs_first = s_tot[0x5C] != 0 && !above_bs;
@@ -519,7 +512,7 @@ __device__ __forceinline__ void huff_enc_body(const SmallMember *__restrict__ ta
     const uint32_t max_len = s_plan[0], pay_bits = s_plan[1];
     const uint32_t H = E + 3, pad = (8 - pay_bits % 8) % 8;              // huffman.go:245-249
     const uint32_t total = H + (pay_bits + pad) / 8, out_words = (total + 3) / 4;
-    if (max_len > 24 || H > HDR_MAX || out_words > IMG_WORDS || 4 * out_words > slot(n)) { block_done(status, HE_BACK); return; }
+    if (max_len > 24 || H > HDR_MAX || out_words > IMG_WORDS || 4 * out_words > slot(n)) { block_done(status, GROUP_BACK); return; }
     if (tid == 0) {
         uint8_t *h = reinterpret_cast<uint8_t *>(s_img);
         h[E] = '\\'; h[E + 1] = '\n'; h[E + 2] = (uint8_t)pad;

@@ -16,9 +16,9 @@
 //   decompress  the stream in chunks of MID_TILE bytes: every '<' parses its token (lzss.go:323-364), a scan gives the output offsets; the
 //               chunk's output in tiles of MID_TILE bytes in output order -- a source in an earlier tile is final, chains inside the tile
 //               are settled by pointer jumping; DecodeOpeningSymbols (lzss.go:391-406) as lzss_small.hip does it.
-// What the kernels do not take is handed back (MID_NOT_MINE) and goes through the single call, which also words the errors.
+// What the kernels do not take is handed back (GROUP_BACK) and goes through the single call, which also words the errors.
 // No loop waits for another workgroup, and every loop is bounded: the chain walk by the ring's size, the extensions by MID_STEP_CAP.
-#include "codecs.h"
+#include "group_run.h"
 #include "lzss_match.h"
 
 namespace rsn {
@@ -30,7 +30,6 @@ constexpr uint32_t MID_W_MAX = 4096;              // the largest window (what th
 constexpr uint32_t MID_RING = 8192;               // links kept: the window, rounded down to a sub-tile, and the tile in hand
 constexpr uint32_t MID_HEADS = 4096;              // chains (a 12-bit hash of the two-byte key)
 constexpr uint32_t MID_NONE = 0xFFFFFFFFu;
-constexpr uint32_t MID_PENDING = 0xFFFFFFFFu, MID_NOT_MINE = 0xFFFFFFFEu;
 constexpr uint32_t MID_STEP_CAP = 4096;           // eight-byte extension steps a thread spends on a tile (its two positions) before the member is handed back -- lzss_small.hip's SL_STEP_CAP, for the same two positions
 constexpr uint32_t E_PAD = 64;                    // zeros behind the escaped stream (an eight-byte load may start at its last byte)
 constexpr uint32_t E_MAX = LZSS_MID_E_MAX;
@@ -111,7 +110,7 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_enc(const SmallMember *__restri
     uint8_t *hout = base + m.out_off;
     uint32_t *flag = reinterpret_cast<uint32_t *>(base + m.status_off);
     const uint32_t tid = threadIdx.x, n = m.n;
-    if (n > LZSS_MID_IN_MAX || W == 0 || W > MID_W_MAX) { mid_done(flag, MID_NOT_MINE); return; }   // (the host does not send these)
+    if (n > LZSS_MID_IN_MAX || W == 0 || W > MID_W_MAX) { mid_done(flag, GROUP_BACK); return; }   // (the host does not send these)
     for (uint32_t u = tid; u * 16 < n; u += MT) reinterpret_cast<uint4 *>(sm + EL_IN)[u] = reinterpret_cast<const uint4 *>(hin)[u];   // (pinned host memory, zero behind n)
     for (uint32_t i = tid; i < (E_MAX + E_PAD) / 4; i += MT) reinterpret_cast<uint32_t *>(s_fc)[i] = 0;
     __syncthreads();
@@ -122,7 +121,7 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_enc(const SmallMember *__restri
         uint32_t cnt = 0;
         for (uint32_t i = i0; i < i1; i++) { const uint32_t b = s_in[i]; cnt += (b == 0x5C || b == 0xFF) ? 2u : 1u; }
         uint32_t at = mid_scan(cnt, s_wave, &E);
-        if (E > E_MAX) { mid_done(flag, MID_NOT_MINE); return; }                  // (uniform)
+        if (E > E_MAX) { mid_done(flag, GROUP_BACK); return; }                  // (uniform)
         for (uint32_t i = i0; i < i1; i++) {
             const uint32_t b = s_in[i];
             if (b == 0x5C || b == 0xFF) { s_fc[at++] = 0x5C; s_fc[at++] = (uint8_t)b; } else s_fc[at++] = b == 0x3C ? (uint8_t)0xFF : (uint8_t)b;
@@ -180,7 +179,7 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_enc(const SmallMember *__restri
             __syncthreads();                                                      // (the next sub-tile's links are written behind this)
         }
         if (!live) { entry -= MID_TILE; continue; }
-        if (__syncthreads_or(steps > MID_STEP_CAP)) { mid_done(flag, MID_NOT_MINE); return; }
+        if (__syncthreads_or(steps > MID_STEP_CAP)) { mid_done(flag, GROUP_BACK); return; }
         // ---- the greedy chain inside the tile: r -> r + max(1, L) (lzss.go:139-142), MID_TILE: beyond the tile
         const uint32_t R = min(MID_TILE, E - t0);
         for (uint32_t r = tid; r <= MID_TILE; r += MT) {
@@ -256,7 +255,7 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_dec(const SmallMember *__restri
     uint8_t *hout = base + m.out_off;
     uint32_t *flag = reinterpret_cast<uint32_t *>(base + m.status_off);
     const uint32_t tid = threadIdx.x, n = m.n;
-    if (n > E_MAX) { mid_done(flag, MID_NOT_MINE); return; }                       // (the host does not send these)
+    if (n > E_MAX) { mid_done(flag, GROUP_BACK); return; }                       // (the host does not send these)
     for (uint32_t u = tid; u * 16 < n + 32; u += MT) reinterpret_cast<uint4 *>(s_in)[u] = u * 16 < n ? reinterpret_cast<const uint4 *>(hin)[u] : make_uint4(0, 0, 0, 0);
     for (uint32_t i = tid; i < MID_TILE + 64; i += MT) s_cov[i] = 0;
     __syncthreads();
@@ -285,14 +284,14 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_dec(const SmallMember *__restri
             tlen[k] = (uint32_t)v; ttl[k] = q + 1 - p;
             for (uint32_t t = 0; t < ttl[k]; t++) s_cov[p - c0 + t] = 1;
         }
-        if (__syncthreads_or(bad)) { mid_done(flag, MID_NOT_MINE); return; }       // (malformed: the single call words the error)
+        if (__syncthreads_or(bad)) { mid_done(flag, GROUP_BACK); return; }       // (malformed: the single call words the error)
         uint32_t outl[2] = {0, 0};
         for (int k = 0; k < 2; k++) { const uint32_t p = k0 + k; if (p < n) outl[k] = ttl[k] ? tlen[k] : (s_cov[p - c0] ? 0u : 1u); }
         uint32_t tot;
         const uint32_t at0 = E + mid_scan(outl[0] + outl[1], s_wave, &tot);
-        if (tot > E_MAX - E) { mid_done(flag, MID_NOT_MINE); return; }             // expands beyond the limit (uniform; every outl <= E_MAX, 2048 of them: no overflow)
+        if (tot > E_MAX - E) { mid_done(flag, GROUP_BACK); return; }             // expands beyond the limit (uniform; every outl <= E_MAX, 2048 of them: no overflow)
         bad = (ttl[0] && tptr[0] > at0) || (ttl[1] && tptr[1] > at0 + outl[0]);   // the slice starts before the data (lzss.go:349)
-        if (__syncthreads_or(bad)) { mid_done(flag, MID_NOT_MINE); return; }
+        if (__syncthreads_or(bad)) { mid_done(flag, GROUP_BACK); return; }
         // ---- the chunk's output, a tile at a time in output order
         for (uint32_t s0 = E; s0 < E + tot; s0 += MID_TILE) {
             const uint32_t s1 = min(s0 + MID_TILE, E + tot);
@@ -323,7 +322,7 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_dec(const SmallMember *__restri
         }
         E += tot;
     }
-    if (E == 0) { mid_done(flag, MID_NOT_MINE); return; }                          // (an empty result is the single call's to word)
+    if (E == 0) { mid_done(flag, GROUP_BACK); return; }                          // (an empty result is the single call's to word)
     // ---- DecodeOpeningSymbols (lzss.go:391-406): a byte is escaped iff the run of 5C right in front of it has odd length, counted from the
     //      last byte that is not 5C (as lzss_small.hip).  A run of ceil(E / MT) bytes per thread.
     const uint32_t per = (E + MT - 1) / MT, q0 = min(E, tid * per), q1 = min(E, q0 + per);
@@ -363,63 +362,32 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_dec(const SmallMember *__restri
 
 }  // namespace
 
-// ---------------------------------------------------------------- the host side: groups in pinned staging, as lzss_small.hip's
-bool lzss_mid_compress_takes(size_t n, int64_t window) { return n != 0 && n <= LZSS_MID_IN_MAX && window >= 1 && window <= (int64_t)MID_W_MAX; }
-bool lzss_mid_decompress_takes(size_t n) { return n != 0 && n <= LZSS_MID_E_MAX; }
-
+// ---------------------------------------------------------------- the host side: groups in pinned staging (group_run.h)
 namespace {
-// The members idx in groups: staging = the table, then per member its bytes (zero behind them), its output slot and its status word.
-int lzss_mid_groups(Ctx &c, bool enc, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
-                    const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    int rc = ctx_init(c); if (rc) return rc;
-    hipStream_t s = c.own_stream;
-    const char *what = enc ? "lzss batch compress" : "lzss batch decompress";
-    const size_t lds = enc ? EL_BYTES : DL_BYTES;
-    rc = func_dyn_lds(c, enc ? reinterpret_cast<const void *>(k_lzss_mid_enc) : reinterpret_cast<const void *>(k_lzss_mid_dec), lds);
-    if (rc) { *failed = idx.empty() ? 0 : idx[0]; return rc; }
-    auto in_bytes = [](size_t n) { return round_up(n, 16) + 32; };
-    auto out_bytes = [&](size_t n) { return enc ? round_up(std::min(2 * n, (size_t)LZSS_MID_E_MAX), 16) + 16 : (size_t)LZSS_MID_E_MAX + 16; };
-    auto need = [&](size_t n) { return sizeof(SmallMember) + in_bytes(n) + out_bytes(n) + 16; };
-    std::vector<uint32_t> st;
-    for (size_t j = 0; j < idx.size();) {
-        size_t k = j, bytes = 0;
-        while (k < idx.size() && k - j < SMALL_GROUP_MAX && (k == j || bytes + need(lens[idx[k]]) <= SMALL_GROUP_BYTES)) bytes += need(lens[idx[k++]]);
-        const size_t g = k - j;
-        void *pp; rc = pinned_buf(c, bytes + 64, &pp); if (rc) { *failed = idx[j]; return rc; }
-        uint8_t *base = (uint8_t *)pp;
-        SmallMember *tab = (SmallMember *)base;
-        size_t at = round_up(g * sizeof(SmallMember), 16);
-        st.assign(g, 0);
-        for (size_t q = 0; q < g; q++) {
-            const size_t i = idx[j + q], n = lens[i];
-            SmallMember &m = tab[q];
-            m.n = (uint32_t)n;
-            m.in_off = (uint32_t)at; memcpy(base + at, ins[i], n); memset(base + at + n, 0, in_bytes(n) - n); at += in_bytes(n);
-            m.out_off = (uint32_t)at; at += out_bytes(n);
-            m.status_off = st[q] = (uint32_t)at; *(uint32_t *)(base + at) = MID_PENDING; at += 16;
-        }
-        if (enc) RSN_LAUNCH("lzss_batch_mid_enc", k_lzss_mid_enc, dim3((uint32_t)g), dim3(MT), lds, s, (const SmallMember *)tab, base, (uint32_t)window);
-        else RSN_LAUNCH("lzss_batch_mid_dec", k_lzss_mid_dec, dim3((uint32_t)g), dim3(MT), lds, s, (const SmallMember *)tab, base);
-        rc = group_wait(c, s, base, st, MID_PENDING, what); if (rc) { *failed = idx[j]; return rc; }
-        for (size_t q = 0; q < g; q++) {
-            const size_t i = idx[j + q];
-            const uint32_t v = *(const uint32_t *)(base + st[q]);
-            if (v == MID_NOT_MINE) { back.push_back(i); continue; }
-            rc = take(i, base + tab[q].out_off, v); if (rc) { *failed = i; return rc; }
-        }
-        j = k;
-    }
-    return RSN_OK;
+bool mid_enc_takes(const uint8_t *, size_t n, int64_t window) { return n != 0 && n <= LZSS_MID_IN_MAX && window >= 1 && window <= (int64_t)MID_W_MAX; }
+bool mid_dec_takes(const uint8_t *, size_t n, int64_t) { return n != 0 && n <= LZSS_MID_E_MAX; }
+int mid_enc_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
+                const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    return run_member_groups(c, "lzss batch compress", idx, ins, lens, lzss_in_slot, [](size_t n) { return lzss_enc_out_slot(n, LZSS_MID_E_MAX); },
+        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
+            const int rc = func_dyn_lds(c, reinterpret_cast<const void *>(k_lzss_mid_enc), EL_BYTES); if (rc) return rc;
+            RSN_LAUNCH("lzss_batch_mid_enc", k_lzss_mid_enc, dim3(g), dim3(MT), EL_BYTES, s, tab, base, (uint32_t)window);
+            return RSN_OK;
+        }, take, back, failed);
+}
+int mid_dec_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t,
+                const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    return run_member_groups(c, "lzss batch decompress", idx, ins, lens, lzss_in_slot, [](size_t) { return lzss_dec_out_slot(LZSS_MID_E_MAX); },
+        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
+            const int rc = func_dyn_lds(c, reinterpret_cast<const void *>(k_lzss_mid_dec), DL_BYTES); if (rc) return rc;
+            RSN_LAUNCH("lzss_batch_mid_dec", k_lzss_mid_dec, dim3(g), dim3(MT), DL_BYTES, s, tab, base);
+            return RSN_OK;
+        }, take, back, failed);
 }
 }  // namespace
-
-int lzss_mid_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
-                            const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return lzss_mid_groups(c, true, idx, ins, lens, window, take, back, failed);
-}
-int lzss_mid_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                              const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return lzss_mid_groups(c, false, idx, ins, lens, 0, take, back, failed);
+const BatchClass &lzss_mid_class(bool compress) {
+    static const BatchClass enc = {"lzss mid compress", LZSS_MID_GROUP_MIN, mid_enc_takes, mid_enc_run}, dec = {"lzss mid decompress", LZSS_MID_GROUP_MIN, mid_dec_takes, mid_dec_run};
+    return compress ? enc : dec;
 }
 
 }  // namespace rsn

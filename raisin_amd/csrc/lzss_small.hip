@@ -21,7 +21,7 @@
 #include <chrono>
 #include <thread>
 
-#include "codecs.h"
+#include "group_run.h"
 #include "lzss_match.h"
 
 namespace rsn {
@@ -32,7 +32,6 @@ constexpr uint32_t SL_E_MAX = 2048;             // escaped positions (every byte
 constexpr uint32_t SL_DEC_IN_MAX = 2048;        // bytes of a compressed stream the decoder takes
 constexpr uint32_t SL_DEC_E_MAX = 8192;         // bytes of the escaped stream it expands to, at most
 constexpr int SLT = 1024;                       // threads of the one block
-constexpr uint32_t SL_PENDING = 0xFFFFFFFFu, SL_NOT_MINE = 0xFFFFFFFEu;
 
 // pinned staging of one call: offsets into Ctx::pinned
 constexpr size_t SP_IN = 0, SP_OUT = 4096, SP_FLAG = SP_OUT + SL_DEC_E_MAX + 64, SP_BYTES = SP_FLAG + 64;
@@ -100,7 +99,7 @@ __device__ __forceinline__ void lzss_small_enc_body(const uint8_t *__restrict__ 
         const uint32_t b0 = i0 < n ? s_in[i0] : 0u, b1 = i0 + 1 < n ? s_in[i0 + 1] : 0u;
         const uint32_t c0 = i0 < n ? ((b0 == 0x5C || b0 == 0xFF) ? 2u : 1u) : 0u, c1 = i0 + 1 < n ? ((b1 == 0x5C || b1 == 0xFF) ? 2u : 1u) : 0u;
         uint32_t at = sl_scan(c0 + c1, s_wave, &E);
-        if (E > SL_E_MAX) { sl_done(flag, SL_NOT_MINE); return; }                 // (block-uniform)
+        if (E > SL_E_MAX) { sl_done(flag, GROUP_BACK); return; }                 // (block-uniform)
         if (c0 == 2) { s_fc[at++] = 0x5C; s_fc[at++] = (uint8_t)b0; } else if (c0 == 1) s_fc[at++] = b0 == 0x3C ? (uint8_t)0xFF : (uint8_t)b0;
         if (c1 == 2) { s_fc[at++] = 0x5C; s_fc[at++] = (uint8_t)b1; } else if (c1 == 1) s_fc[at++] = b1 == 0x3C ? (uint8_t)0xFF : (uint8_t)b1;
     }
@@ -150,7 +149,7 @@ __device__ __forceinline__ void lzss_small_enc_body(const uint8_t *__restrict__ 
     }
     if (steps > SL_STEP_CAP) s_bail = 1;
     __syncthreads();
-    if (s_bail) { sl_done(flag, SL_NOT_MINE); return; }
+    if (s_bail) { sl_done(flag, GROUP_BACK); return; }
     // ---- the greedy chain from 0: i -> i + max(1, L) (lzss.go:139-142), marked by pointer doubling
     for (uint32_t i = tid; i <= E; i += SLT) {
         s_jmp[0][i] = (uint16_t)(i < E ? min(E, i + max(1u, s_key[i] >> 16)) : E);
@@ -228,13 +227,13 @@ __device__ __forceinline__ void lzss_small_dec_body(const uint8_t *__restrict__ 
         for (uint32_t t = 0; t < ttl[k]; t++) s_cov[p + t] = 1;
     }
     __syncthreads();
-    if (s_bad) { sl_done(flag, SL_NOT_MINE); return; }                             // (a '<' inside a token's text is a malformed token too: it set s_bad itself or parses as one -- checked below)
+    if (s_bad) { sl_done(flag, GROUP_BACK); return; }                             // (a '<' inside a token's text is a malformed token too: it set s_bad itself or parses as one -- checked below)
     // a '<' inside another token's text: the outer token's digits would have stopped at it, so it cannot happen once every token parsed
     uint32_t outl[2] = {0, 0};
     for (int k = 0; k < 2; k++) { const uint32_t p = k0 + k; if (p < n) outl[k] = ttl[k] ? tlen[k] : (s_cov[p] ? 0u : 1u); }
     uint32_t E;
     uint32_t at = sl_scan(outl[0] + outl[1], s_wave, &E);
-    if (E > SL_DEC_E_MAX || E == 0) { sl_done(flag, E == 0 ? 0u : SL_NOT_MINE); return; }
+    if (E > SL_DEC_E_MAX || E == 0) { sl_done(flag, E == 0 ? 0u : GROUP_BACK); return; }
     for (int k = 0; k < 2; k++) {
         const uint32_t p = k0 + k;
         if (!outl[k]) continue;
@@ -245,7 +244,7 @@ __device__ __forceinline__ void lzss_small_dec_body(const uint8_t *__restrict__ 
         at += outl[k];
     }
     __syncthreads();
-    if (s_bad) { sl_done(flag, SL_NOT_MINE); return; }
+    if (s_bad) { sl_done(flag, GROUP_BACK); return; }
     // ---- every byte's literal: src <- src[src] until nothing moves (a copied byte always lies before the byte that copies it)
     int cur = 0;
     for (int round = 0; round < 14; round++) {
@@ -325,25 +324,15 @@ __global__ __launch_bounds__(SLT) void k_lzss_batch_dec(const SmallMember *__res
     lzss_small_dec_body(base + m.in_off, m.n, base + m.out_off, reinterpret_cast<uint32_t *>(base + m.status_off));
 }
 
-int sl_wait(Ctx &c, hipStream_t s, const uint32_t *f) {
-    const volatile uint32_t *vf = f;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t spins = 1;; spins++) {
-        if (*vf != SL_PENDING) { std::atomic_thread_fence(std::memory_order_acquire); return RSN_OK; }
-        if ((spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) {
-            RSN_HIP(hipStreamSynchronize(s));
-            if (*vf == SL_PENDING) return c.fail(RSN_ERR_DEVICE, "lzss: the small-input kernel finished without its answer");
-            return RSN_OK;
-        }
-        __builtin_ia32_pause();
-    }
-}
+// what the single calls and the batch classes below take
+bool small_enc_takes(const uint8_t *, size_t n, int64_t window) { return n != 0 && n <= SL_IN_MAX && window <= 0xFFFF; }
+bool small_dec_takes(const uint8_t *, size_t n, int64_t) { return n != 0 && n <= SL_DEC_IN_MAX; }
 
 }  // namespace
 
 // 1: not an input for this path (the caller takes the general one).  *out: the result in the context's pinned staging.
 int lzss_small_compress(Ctx &c, const uint8_t *in, size_t n, int64_t window, const uint8_t **out, size_t *out_n) {
-    if (n == 0 || n > SL_IN_MAX || window > 0xFFFF) return 1;
+    if (!small_enc_takes(in, n, window)) return 1;
     int rc = ctx_init(c); if (rc) return rc;
     hipStream_t s = c.own_stream;
     void *pp; rc = pinned_buf(c, SP_BYTES, &pp); if (rc) return rc;
@@ -351,16 +340,28 @@ int lzss_small_compress(Ctx &c, const uint8_t *in, size_t n, int64_t window, con
     memcpy(pin + SP_IN, in, n);
     memset(pin + SP_IN + n, 0, 16);
     uint32_t *flag = (uint32_t *)(pin + SP_FLAG);
-    *flag = SL_PENDING;
+    *flag = GROUP_PENDING;
     RSN_LAUNCH("lzss_small_enc", k_lzss_small_enc, dim3(1), dim3(SLT), 0, s, (const uint8_t *)(pin + SP_IN), (uint32_t)n, (uint32_t)(window <= 0 ? 0 : window), pin + SP_OUT, flag);
-    rc = sl_wait(c, s, flag); if (rc) return rc;
-    if (*flag == SL_NOT_MINE) return 1;
+    rc = flags_wait(c, s, flag, 1, "lzss"); if (rc) return rc;
+    if (*flag == GROUP_BACK) return 1;
     *out = pin + SP_OUT; *out_n = *flag;
     return RSN_OK;
 }
 
-bool lzss_small_compress_takes(size_t n, int64_t window) { return n != 0 && n <= SL_IN_MAX && window <= 0xFFFF; }
-bool lzss_small_decompress_takes(size_t n) { return n != 0 && n <= SL_DEC_IN_MAX; }
+int flags_wait(Ctx &c, hipStream_t s, const uint32_t *flags, uint32_t n, const char *what) {
+    const volatile uint32_t *vf = flags;
+    auto pending = [&] { uint32_t p = 0; for (uint32_t i = 0; i < n; i++) p |= vf[i] == GROUP_PENDING; return p != 0; };
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t spins = 1;; spins++) {
+        if (!pending()) { std::atomic_thread_fence(std::memory_order_acquire); return RSN_OK; }
+        if ((spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) {
+            RSN_HIP(hipStreamSynchronize(s));
+            if (pending()) return c.fail(RSN_ERR_DEVICE, "%s: a small-input kernel finished without its answer", what);
+            return RSN_OK;
+        }
+        __builtin_ia32_pause();
+    }
+}
 
 int group_wait(Ctx &c, hipStream_t s, const uint8_t *base, const std::vector<uint32_t> &off, uint32_t pending, const char *what) {
     auto at = [&](size_t k) { return *reinterpret_cast<const volatile uint32_t *>(base + off[k]); };
@@ -384,58 +385,32 @@ int group_wait(Ctx &c, hipStream_t s, const uint8_t *base, const std::vector<uin
     return RSN_OK;
 }
 
+// ---------------------------------------------------------------- the two classes of the batch calls (codecs.h; the packer: group_run.h)
 namespace {
-// The members idx in groups: staging = the table, then per member its bytes (zero behind them), its output slot and its status word.
-int lzss_groups(Ctx &c, bool enc, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
-                const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    int rc = ctx_init(c); if (rc) return rc;
-    hipStream_t s = c.own_stream;
-    const char *what = enc ? "lzss batch compress" : "lzss batch decompress";
-    auto need = [&](size_t n) { return sizeof(SmallMember) + round_up(n, 16) + 32 + (enc ? round_up(2 * n, 16) + 16 : SL_DEC_E_MAX + 16) + 16; };
-    std::vector<uint32_t> st;
-    for (size_t j = 0; j < idx.size();) {
-        size_t k = j, bytes = 0;
-        while (k < idx.size() && k - j < SMALL_GROUP_MAX && (k == j || bytes + need(lens[idx[k]]) <= SMALL_GROUP_BYTES)) bytes += need(lens[idx[k++]]);
-        const size_t g = k - j;
-        void *pp; rc = pinned_buf(c, bytes + 64, &pp); if (rc) { *failed = idx[j]; return rc; }
-        uint8_t *base = (uint8_t *)pp;
-        SmallMember *tab = (SmallMember *)base;
-        size_t at = round_up(g * sizeof(SmallMember), 16);
-        st.assign(g, 0);
-        for (size_t q = 0; q < g; q++) {
-            const size_t i = idx[j + q], n = lens[i];
-            SmallMember &m = tab[q];
-            m.n = (uint32_t)n;
-            m.in_off = (uint32_t)at; memcpy(base + at, ins[i], n); memset(base + at + n, 0, round_up(n, 16) + 32 - n); at += round_up(n, 16) + 32;
-            m.out_off = (uint32_t)at; at += enc ? round_up(2 * n, 16) + 16 : SL_DEC_E_MAX + 16;
-            m.status_off = st[q] = (uint32_t)at; *(uint32_t *)(base + at) = SL_PENDING; at += 16;
-        }
-        if (enc) RSN_LAUNCH("lzss_batch_enc", k_lzss_batch_enc, dim3((uint32_t)g), dim3(SLT), 0, s, (const SmallMember *)tab, base, (uint32_t)(window <= 0 ? 0 : window));
-        else RSN_LAUNCH("lzss_batch_dec", k_lzss_batch_dec, dim3((uint32_t)g), dim3(SLT), 0, s, (const SmallMember *)tab, base);
-        rc = group_wait(c, s, base, st, SL_PENDING, what); if (rc) { *failed = idx[j]; return rc; }
-        for (size_t q = 0; q < g; q++) {
-            const size_t i = idx[j + q];
-            const uint32_t v = *(const uint32_t *)(base + st[q]);
-            if (v == SL_NOT_MINE) { back.push_back(i); continue; }
-            rc = take(i, base + tab[q].out_off, v); if (rc) { *failed = i; return rc; }
-        }
-        j = k;
-    }
-    return RSN_OK;
+int small_enc_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
+                  const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    return run_member_groups(c, "lzss batch compress", idx, ins, lens, lzss_in_slot, [](size_t n) { return lzss_enc_out_slot(n, SL_E_MAX); },
+        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
+            RSN_LAUNCH("lzss_batch_enc", k_lzss_batch_enc, dim3(g), dim3(SLT), 0, s, tab, base, (uint32_t)(window <= 0 ? 0 : window));
+            return RSN_OK;
+        }, take, back, failed);
+}
+int small_dec_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t,
+                  const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    return run_member_groups(c, "lzss batch decompress", idx, ins, lens, lzss_in_slot, [](size_t) { return lzss_dec_out_slot(SL_DEC_E_MAX); },
+        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
+            RSN_LAUNCH("lzss_batch_dec", k_lzss_batch_dec, dim3(g), dim3(SLT), 0, s, tab, base);
+            return RSN_OK;
+        }, take, back, failed);
 }
 }  // namespace
-
-int lzss_small_compress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
-                              const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return lzss_groups(c, true, idx, ins, lens, window, take, back, failed);
-}
-int lzss_small_decompress_group(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
-                                const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return lzss_groups(c, false, idx, ins, lens, 0, take, back, failed);
+const BatchClass &lzss_small_class(bool compress) {
+    static const BatchClass enc = {"lzss small compress", 1, small_enc_takes, small_enc_run}, dec = {"lzss small decompress", 1, small_dec_takes, small_dec_run};
+    return compress ? enc : dec;
 }
 
 int lzss_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **out, size_t *out_n) {
-    if (n == 0 || n > SL_DEC_IN_MAX) return 1;
+    if (!small_dec_takes(in, n, 0)) return 1;
     int rc = ctx_init(c); if (rc) return rc;
     hipStream_t s = c.own_stream;
     void *pp; rc = pinned_buf(c, SP_BYTES, &pp); if (rc) return rc;
@@ -443,10 +418,10 @@ int lzss_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **o
     memcpy(pin + SP_IN, in, n);
     memset(pin + SP_IN + n, 0, 32);
     uint32_t *flag = (uint32_t *)(pin + SP_FLAG);
-    *flag = SL_PENDING;
+    *flag = GROUP_PENDING;
     RSN_LAUNCH("lzss_small_dec", k_lzss_small_dec, dim3(1), dim3(SLT), 0, s, (const uint8_t *)(pin + SP_IN), (uint32_t)n, pin + SP_OUT, flag);
-    rc = sl_wait(c, s, flag); if (rc) return rc;
-    if (*flag == SL_NOT_MINE) return 1;
+    rc = flags_wait(c, s, flag, 1, "lzss"); if (rc) return rc;
+    if (*flag == GROUP_BACK) return 1;
     *out = pin + SP_OUT; *out_n = *flag;
     return RSN_OK;
 }

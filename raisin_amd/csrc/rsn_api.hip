@@ -1081,8 +1081,19 @@ static void deal_items(Ctx &c, size_t n_items, Work work, std::vector<int> &rcs,
     (void)hipSetDevice(c.device);
 }
 
-// fewer grouped members than this: every member takes the pipeline (a group's one serial tree against the host's)
-constexpr size_t HUFF_GROUP_MIN = 2;
+// The members of a batch by class: per[r] = the members rows' r-th class takes and no earlier one does, in index order; a class with fewer
+// members than its group_min is not grouped.  Those, and what no class takes, go to `rest` (not sorted).
+static void classify(BatchRows rows, size_t n, const uint8_t *const *ins, const size_t *lens, int64_t window,
+                     std::vector<std::vector<size_t>> &per, std::vector<size_t> &rest) {
+    per.assign(rows.n, {});
+    for (size_t i = 0; i < n; i++) {
+        size_t r = 0;
+        while (r < rows.n && !rows.first[r]->takes(ins[i], lens[i], window)) r++;
+        (r < rows.n ? per[r] : rest).push_back(i);
+    }
+    for (size_t r = 0; r < rows.n; r++)
+        if (per[r].size() < rows.first[r]->group_min) { rest.insert(rest.end(), per[r].begin(), per[r].end()); per[r].clear(); }
+}
 
 static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
     Ctx &c = ctx();
@@ -1092,24 +1103,21 @@ static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const
         drop_results(n_chunks, outs, out_lens);
         return c.fail(rc, "%s", msg);
     };
-    // Members of 2 B to 16 KiB run grouped on this thread (huff_batch_compress_group: one launch of k_huff_batch_enc per group, every member
-    // its own workgroup and its own tree) when there are at least HUFF_GROUP_MIN of them.  The rest -- larger members, and the members the
-    // kernel hands back (runes, a single symbol) -- take the pipeline below, as every member did before, dealt over the batch workers.
-    // Members above 16 KiB and up to HUFF_MID_IN_MAX are the mid class (huff_mid.hip: k_huff_mid_enc, one launch per group), grouped from
-    // HUFF_MID_GROUP_MIN of them.
-    std::vector<size_t> grouped, mid, rest;
-    for (size_t i = 0; i < n_chunks; i++) (huff_batch_compress_takes(lens[i]) ? grouped : huff_mid_compress_takes(lens[i]) ? mid : rest).push_back(i);
-    if (grouped.size() < HUFF_GROUP_MIN) { rest.insert(rest.end(), grouped.begin(), grouped.end()); grouped.clear(); }
-    if (mid.size() < HUFF_MID_GROUP_MIN) { rest.insert(rest.end(), mid.begin(), mid.end()); mid.clear(); }
+    // Members of 2 B to 16 KiB (k_huff_batch_enc) and above that up to HUFF_MID_IN_MAX (k_huff_mid_enc) run grouped on this thread, one
+    // launch per group, every member its own workgroup and its own tree (codecs.h: the rows and their minimums).  The rest -- larger
+    // members, and the members a kernel hands back (runes, a single symbol) -- take the pipeline below, as every member did before, dealt
+    // over the batch workers.
+    const BatchRows rows = batch_classes(BatchLayer::HUFFMAN, true);
+    std::vector<std::vector<size_t>> per;
+    std::vector<size_t> rest;
+    classify(rows, n_chunks, ins, lens, 0, per, rest);
     std::sort(rest.begin(), rest.end());
-    for (int cls = 1; cls <= 2; cls++) {
-        const std::vector<size_t> &members = cls == 1 ? grouped : mid;
-        if (members.empty()) continue;
+    const SmallTake take = take_into(c, outs, out_lens);
+    for (size_t r = 0; r < rows.n; r++) {
+        if (per[r].empty()) continue;
         std::vector<size_t> back;
         size_t failed = 0;
-        const SmallTake take = take_into(c, outs, out_lens);
-        const int rc = cls == 1 ? huff_batch_compress_group(c, members, ins, lens, take, back, &failed)
-                                : huff_mid_compress_group(c, members, ins, lens, take, back, &failed);
+        const int rc = rows.first[r]->run(c, per[r], ins, lens, 0, take, back, &failed);
         if (rc != RSN_OK) { const std::string msg = c.err; return undo(rc, msg.c_str()); }
         rest.insert(rest.end(), back.begin(), back.end());
         std::sort(rest.begin(), rest.end());
@@ -1157,13 +1165,11 @@ struct ShardSync : FirstFailure {
 // rest -- a member a kernel handed back, larger ones, another alphabet -- goes through the single call's implementation, in index order,
 // dealt over the batch workers like the compress batch's chunks (deal_items).  Every outs[i] is what the single call returns for ins[i]; on
 // any failure every outs[i] is NULL and the answer is the lowest-index failing member's code, its message prefixed "member <i>: ".
-// `takes(i)`: the grouped class of member i -- 0: none (the single call), 1: the small kernel's, 2: the mid-size kernel's (lzss_mid.hip,
-// huff_mid.hip), which is used when at least `mid_min` members of the call are of it; `group(c, cls, ...)`: runs the members of one class;
-// `single(i, small)`: the single call for member i (small = false: the member was handed back by a grouped kernel whose body the single
-// call's small path shares).
-template <class Takes, class Group, class Single>
-static int small_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens, bool back_skips_small,
-                       size_t mid_min, Takes takes, Group group, Single single) {
+// `rows`: the layer's and direction's classes (codecs.h), run in their order; `single(i, small)`: the single call for member i (small =
+// false: the member was handed back by a grouped kernel whose body the single call's small path shares).
+template <class Single>
+static int small_batch(BatchRows rows, int64_t window, size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens,
+                       bool back_skips_small, Single single) {
     Ctx &c = ctx();
     int rc = batch_args(c, n, ins, lens, outs, out_lens, true, true); if (rc || n == 0) return rc;
     rc = ctx_init(c); if (rc) return rc;                                  // (no device: RSN_ERR_DEVICE -- there is no CPU path)
@@ -1171,18 +1177,14 @@ static int small_batch(size_t n, const uint8_t *const *ins, const size_t *lens, 
     struct Fail { size_t at = NONE; int rc = RSN_OK; std::string msg; };
     Fail f;
     auto note = [](Fail &x, size_t i, int code, const std::string &m) { if (i < x.at) { x.at = i; x.rc = code; x.msg = m; } };
-    std::vector<size_t> grouped, mid, rest, back;
-    for (size_t i = 0; i < n; i++) { const int cls = takes(i); (cls == 1 ? grouped : cls == 2 ? mid : rest).push_back(i); }
-    if (mid.size() < mid_min) { rest.insert(rest.end(), mid.begin(), mid.end()); mid.clear(); }   // (rest is sorted below)
+    std::vector<std::vector<size_t>> per;
+    std::vector<size_t> rest, back;
+    classify(rows, n, ins, lens, window, per, rest);                      // (rest is sorted below)
     const SmallTake take = take_into(c, outs, out_lens);
-    if (!grouped.empty()) {
+    for (size_t r = 0; r < rows.n && f.at == NONE; r++) {                 // (a device failure: nothing more is launched)
+        if (per[r].empty()) continue;
         size_t failed = NONE;
-        rc = group(c, 1, grouped, take, back, &failed);
-        if (rc != RSN_OK) note(f, failed, rc, c.err);
-    }
-    if (!mid.empty() && f.at == NONE) {                                   // (a device failure above: nothing more is launched)
-        size_t failed = NONE;
-        rc = group(c, 2, mid, take, back, &failed);
+        rc = rows.first[r]->run(c, per[r], ins, lens, window, take, back, &failed);
         if (rc != RSN_OK) note(f, failed, rc, c.err);
     }
     std::vector<char> handed(back_skips_small ? n : 0, 0);
@@ -1223,32 +1225,17 @@ static int small_batch(size_t n, const uint8_t *const *ins, const size_t *lens, 
 }
 
 static int rsn_huffman_decompress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
-    return small_batch(n, ins, lens, outs, out_lens, false, HUFF_MID_GROUP_MIN,
-                       [&](size_t i) { return huff_mid_decompress_takes(ins[i], lens[i]) ? 2 : huff_batch_decompress_may_take(lens[i]) ? 1 : 0; },
-                       [&](Ctx &c, int cls, const std::vector<size_t> &idx, const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-                           return cls == 1 ? huff_batch_decompress_group(c, idx, ins, lens, take, back, failed)
-                                           : huff_mid_decompress_group(c, idx, ins, lens, take, back, failed);
-                       },
+    return small_batch(batch_classes(BatchLayer::HUFFMAN, false), 0, n, ins, lens, outs, out_lens, false,
                        [&](size_t i, bool small) { return rsn_huffman_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small); });
 }
 
 static int rsn_lzss_compress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, int64_t window, uint8_t **outs, size_t *out_lens) {
-    return small_batch(n, ins, lens, outs, out_lens, true, LZSS_MID_GROUP_MIN,
-                       [&](size_t i) { return lzss_small_compress_takes(lens[i], window) ? 1 : lzss_mid_compress_takes(lens[i], window) ? 2 : 0; },
-                       [&](Ctx &c, int cls, const std::vector<size_t> &idx, const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-                           return cls == 1 ? lzss_small_compress_group(c, idx, ins, lens, window, take, back, failed)
-                                           : lzss_mid_compress_group(c, idx, ins, lens, window, take, back, failed);
-                       },
+    return small_batch(batch_classes(BatchLayer::LZSS, true), window, n, ins, lens, outs, out_lens, true,
                        [&](size_t i, bool small) { return rsn_lzss_compress_impl(ins[i], lens[i], window, &outs[i], &out_lens[i], small); });
 }
 
 static int rsn_lzss_decompress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
-    return small_batch(n, ins, lens, outs, out_lens, true, LZSS_MID_GROUP_MIN,
-                       [&](size_t i) { return lzss_small_decompress_takes(lens[i]) ? 1 : lzss_mid_decompress_takes(lens[i]) ? 2 : 0; },
-                       [&](Ctx &c, int cls, const std::vector<size_t> &idx, const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-                           return cls == 1 ? lzss_small_decompress_group(c, idx, ins, lens, take, back, failed)
-                                           : lzss_mid_decompress_group(c, idx, ins, lens, take, back, failed);
-                       },
+    return small_batch(batch_classes(BatchLayer::LZSS, false), 0, n, ins, lens, outs, out_lens, true,
                        [&](size_t i, bool small) { return rsn_lzss_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small); });
 }
 

@@ -109,6 +109,23 @@ def test_a_thousand_small_members_are_one_launch(mods, oracle):
     assert hdec[:50] == [oracle.huffman_decompress(s) for s in hstreams[:50]]
 
 
+def test_small_lzss_decoder_group_ends_on_the_byte_limit(mods, oracle):
+    """The small LZSS decoder's output slot is the full 8 KiB + 16 whatever the stream's length, so a stream of at most 16 bytes takes
+    16 (entry) + 16 + 32 (input) + 8192 + 16 (output) + 16 (status) = 8288 bytes of a group's 16 MiB of staging: 2024 such members are
+    one launch, and the 2025th starts the next."""
+    _lib, _, lz = mods
+    stream = oracle.lzss_compress(README[0])
+    assert len(stream) <= 16
+    need = 16 + 16 + 32 + 8192 + 16 + 16
+    assert (need, (16 << 20) // need) == (8288, 2024)
+    want = oracle.lzss_decompress(stream)
+    assert want == README[0]
+    for members, launches in ((2024, 1), (2025, 2)):
+        dec, p = _prof(_lib, lambda: lz.DecompressBatch([stream] * members))
+        assert p == {"lzss_batch_dec": launches}, p
+        assert dec == [want] * members
+
+
 def _payload(stream):
     return len(stream) - stream.index(b"\\\n") - 3
 
