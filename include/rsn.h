@@ -237,6 +237,40 @@ RSN_API int rsn_arithmetic_decompress_batch(size_t n, const uint8_t *const *ins,
 RSN_API int rsn_arithmetic_compress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream);
 RSN_API int rsn_arithmetic_decompress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream);
 
+/* ---- batch calls on device buffers ---------------------------------------
+ * Many independent members that already lie in device memory, in one call: `members` is a HOST array of n descriptors, each under
+ * the contract of the device-resident entry points above -- d_in / d_out device pointers on the calling thread's device, both
+ * 16-byte aligned (RSN_ERR_ARG otherwise), only the n bytes of a member's input read as data: nothing in front of d_in or behind
+ * d_in + n reaches a result, so members may be packed back to back in one allocation at 16-byte offsets.  Member i's result is byte
+ * for byte what the single call (rsn_lzss_compress_dev(..., window, ...), rsn_lzss_decompress_dev, rsn_arithmetic_compress_dev,
+ * rsn_arithmetic_decompress_dev) writes for the same input -- which is the host batch call's and the reference's -- and lies at
+ * members[i].d_out[0 .. out_lens[i]); empty members behave as in the single call.  The work is queued on `stream` (NULL = the
+ * thread's own), which is synchronised before the call returns.  The members' bytes never cross to the host: LZSS members of the
+ * host batch calls' classes (same sizes, same window rules, same minimum counts) are gathered on the device into the grouped
+ * kernels' staging, run one launch a group and are scattered to their buffers; arithmetic members are coded where they lie, a
+ * wavefront each; every other LZSS member -- and one a grouped kernel hands back -- runs the single call on the same stream, in
+ * index order.
+ * Arguments, all checked before a device is looked for (RSN_ERR_ARG): n == 0 returns RSN_OK; null `members` or `out_lens`; a null
+ * d_in with n > 0; a d_in or d_out that is not 16-byte aligned; a null d_out with out_cap != 0 (a null d_out with out_cap == 0 is a
+ * size query for that member); an output range that overlaps ANY member's input range, or another member's output range (empty
+ * ranges overlap nothing; inputs may overlap each other).  `window` is rsn_lzss_compress_dev's.  Without a device: RSN_ERR_DEVICE.
+ * Failures: if a member fails with a code other than RSN_ERR_CAPACITY the call returns the lowest-index such member's code,
+ * rsn_last_error() reads "member <i>: " followed by the single call's message, and every out_lens[i] is 0.  Otherwise, if some
+ * members did not fit their buffers, the call returns RSN_ERR_CAPACITY and names the lowest such member; every member has still
+ * been processed: out_lens[i] <= out_cap marks a member that fits -- its bytes are complete and out_lens[i] is exact -- and
+ * out_lens[i] > out_cap one that did not, the value being a capacity that suffices, as the single call reports it (LZSS: the exact
+ * size rounded up to 16, plus 16; arithmetic: the exact size).  A buffer of rsn_lzss_compress_bound(n) / rsn_arithmetic_compress_bound(n)
+ * bytes always suffices for a compress member, and an out_cap equal to the exact result size is accepted whatever its remainder
+ * mod 16.  Nothing is ever written outside [d_out, d_out + out_cap) of any member; what a member that did not fit, or the members of
+ * a failed call, hold is unspecified.
+ * Huffman is not offered in this form: its decoder's header parse and its general encoder's tree are host work on the stream's own
+ * bytes, so a member's bytes would have to come down -- the follow-up is a device-side header parse for byte alphabets. */
+typedef struct { const void *d_in; size_t n; void *d_out; size_t out_cap; } rsn_dev_member;
+RSN_API int rsn_lzss_compress_batch_dev(size_t n, const rsn_dev_member *members, int64_t window, size_t *out_lens, void *stream);
+RSN_API int rsn_lzss_decompress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream);
+RSN_API int rsn_arithmetic_compress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream);
+RSN_API int rsn_arithmetic_decompress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream);
+
 /* ---- measurement --------------------------------------------------------
  * When enabled, every kernel launch of the calling thread is bracketed by HIP
  * events on the launch stream; rsn_prof_get() reports per-kernel totals since

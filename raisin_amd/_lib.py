@@ -38,6 +38,11 @@ class RoundTripResult(ctypes.Structure):
                 ("compress_ms", ctypes.c_double), ("decompress_ms", ctypes.c_double)]
 
 
+class DevMember(ctypes.Structure):
+    """rsn_dev_member (include/rsn.h): one member of a batch call on device buffers"""
+    _fields_ = [("d_in", ctypes.c_void_p), ("n", ctypes.c_size_t), ("d_out", ctypes.c_void_p), ("out_cap", ctypes.c_size_t)]
+
+
 _lib = None
 
 SYMBOLS = [
@@ -53,6 +58,7 @@ SYMBOLS = [
     "rsn_prof_copied",
     "rsn_arithmetic_compress_bound", "rsn_arithmetic_compress", "rsn_arithmetic_decompress",
     "rsn_arithmetic_compress_batch", "rsn_arithmetic_decompress_batch", "rsn_arithmetic_compress_dev", "rsn_arithmetic_decompress_dev",
+    "rsn_lzss_compress_batch_dev", "rsn_lzss_decompress_batch_dev", "rsn_arithmetic_compress_batch_dev", "rsn_arithmetic_decompress_batch_dev",
 ]
 
 
@@ -99,6 +105,10 @@ def lib():
     for name in ("rsn_huffman_compress_dev", "rsn_huffman_decompress_dev", "rsn_lzss_decompress_dev", "rsn_arithmetic_compress_dev", "rsn_arithmetic_decompress_dev"):
         getattr(L, name).argtypes = [vp, sz, vp, sz, szp, vp]
     L.rsn_lzss_compress_dev.argtypes = [vp, sz, ctypes.c_int64, vp, sz, szp, vp]
+    mp = ctypes.POINTER(DevMember)
+    L.rsn_lzss_compress_batch_dev.argtypes = [sz, mp, ctypes.c_int64, szp, vp]
+    for name in ("rsn_lzss_decompress_batch_dev", "rsn_arithmetic_compress_batch_dev", "rsn_arithmetic_decompress_batch_dev"):
+        getattr(L, name).argtypes = [sz, mp, szp, vp]
     L.rsn_prof_enable.argtypes = [ctypes.c_int]
     L.rsn_prof_enable.restype = None
     L.rsn_prof_reset.restype = None
@@ -175,6 +185,22 @@ def call_dev(fn, d_in, n, d_out, cap, stream, *extra):
         err.needed = got.value
         raise err
     return got.value
+
+
+def call_batch_dev(fn, members, stream, *extra):
+    """(d_in, n, d_out, out_cap) per member -> the list of out_lens through a batch entry point on device buffers (rsn_*_batch_dev: n,
+    members, [extra,] out_lens, stream).  On RSN_ERR_CAPACITY raises RsnError whose .out_lens holds the list: out_lens[i] > out_cap marks
+    a member that did not fit, the value is a capacity that suffices; every other member is complete."""
+    k = len(members)
+    arr = (DevMember * max(k, 1))(*[DevMember(a or None, n, b or None, cap) for a, n, b, cap in members])
+    olens = (ctypes.c_size_t * max(k, 1))()
+    rc = fn(k, arr, *extra, olens, stream)
+    got = [int(olens[i]) for i in range(k)]
+    if rc != RSN_OK:
+        err = RsnError(rc, lib().rsn_last_error().decode("utf-8", "replace"))
+        err.out_lens = got
+        raise err
+    return got
 
 
 class Writer:
@@ -335,6 +361,53 @@ def dev_tensor(fn, src, out, stream, guess, *extra, retry=True, floor=0):
         out = fresh(max(e.needed, floor))
         got = run(out)
     return out[:got]
+
+
+def _ru16(x):
+    return (x + 15) // 16 * 16
+
+
+def dev_tensors(fn, srcs, outs, stream, guess, *extra, retry=True):
+    """`fn` (rsn_*_batch_dev) over a list of 1-D uint8 CUDA tensors -> a list of tensors trimmed to the result sizes.  Every tensor's
+    data_ptr must be 16-byte aligned (slices of one allocation at 16-byte offsets are).  Without `outs` the results are views of ONE
+    allocation, member i's slot guess(n_i) bytes; a member whose slot or `out` turns out too small (RSN_ERR_CAPACITY: out_lens[i] is a size
+    that suffices) is run once more, alone with the others of its kind, into a fresh allocation -- the way dev_tensor treats a single;
+    retry=False raises instead."""
+    import torch
+    srcs = list(srcs)
+    if not srcs:
+        return []
+    st = own_stream(srcs[0], stream)
+    dev = srcs[0].device
+
+    def slots(sizes):
+        offs, at = [], 0
+        for b in sizes:
+            offs.append(at)
+            at += _ru16(max(b, 16))
+        whole = torch.empty(at, dtype=torch.uint8, device=dev)
+        return [whole[o:o + b] for o, b in zip(offs, sizes)]
+
+    def run(which, to):
+        return call_batch_dev(fn, [(srcs[i].data_ptr() if srcs[i].numel() else None, srcs[i].numel(),
+                                    to[i].data_ptr() if to[i].numel() else None, to[i].numel()) for i in which], st, *extra)
+
+    if outs is None:
+        outs = slots([guess(t.numel()) for t in srcs])
+    outs = list(outs)
+    every = list(range(len(srcs)))
+    try:
+        got = run(every, outs)
+    except RsnError as e:
+        if e.code != RSN_ERR_CAPACITY or not retry:
+            raise
+        got = e.out_lens
+        again = [i for i in every if got[i] > outs[i].numel()]
+        for i, t in zip(again, slots([got[i] for i in again])):
+            outs[i] = t
+        for i, v in zip(again, run(again, outs)):
+            got[i] = v
+    return [outs[i][:got[i]] for i in every]
 
 
 def own_stream(tensor, stream=None):

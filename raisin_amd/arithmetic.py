@@ -75,3 +75,17 @@ def decompress_tensor(src, out=None, stream=None):
     """The decoded size is not in the stream: a guess of eight times the stream first, the exact size on the second call if that was
     too small."""
     return _lib.dev_tensor(_lib.lib().rsn_arithmetic_decompress_dev, src, out, stream, 8 * src.numel() + 4096, floor=16)
+
+
+def compress_tensors(srcs, outs=None, stream=None):
+    """compress_tensor for a list of 1-D uint8 CUDA tensors in ONE call (rsn_arithmetic_compress_batch_dev): a wavefront per member, the
+    members coded where they lie -- the fast path for data that is on the device already.  Each tensor's data_ptr must be 16-byte aligned
+    (slices of one allocation at 16-byte offsets are).  Returns the streams, trimmed; without `outs` they are views of one allocation of
+    bound-sized slots."""
+    return _lib.dev_tensors(_lib.lib().rsn_arithmetic_compress_batch_dev, srcs, outs, stream, compress_bound)
+
+
+def decompress_tensors(srcs, outs=None, stream=None):
+    """decompress_tensor for a list of streams in ONE call (rsn_arithmetic_decompress_batch_dev).  Without `outs`: a guess of eight times
+    the stream plus 4 KiB per member; the members that decode to more are run once more with the exact sizes the call reports."""
+    return _lib.dev_tensors(_lib.lib().rsn_arithmetic_decompress_batch_dev, srcs, outs, stream, lambda n: 8 * n + 4096)

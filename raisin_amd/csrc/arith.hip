@@ -222,9 +222,13 @@ __global__ __launch_bounds__(64 * AR_WAVES) void k_arith_enc(const ArithMember *
 // The raw bits into place behind the front pad -- p = 8 - nbits % 8 bits, all zero but the last -- and the members' streams side by side:
 // member k's at out + offs[k] (offs: the exclusive scan of the 16-byte rounded sizes).  A thread makes 16 bytes of one member's stream:
 // byte j is the last p bits of raw byte j - 1 and the first 8 - p of raw byte j.  Only the stream's own bytes are stored.
+// OWN (the batch call on device buffers): member k's stream goes to its own buffer, dests[k].dst, instead of out + offs[k] -- the scan only
+// deals the threads out -- and only when the whole of it fits dests[k].cap.
+struct ArithDest { uint8_t *dst; unsigned long long cap; };
+template <bool OWN>
 __global__ __launch_bounds__(256) void k_arith_pack(const ArithMember *__restrict__ mem, const ArithState *__restrict__ states,
                                                     const unsigned long long *__restrict__ offs, const unsigned long long *__restrict__ total,
-                                                    uint32_t n_members, uint8_t *__restrict__ out) {
+                                                    uint32_t n_members, uint8_t *__restrict__ out, const ArithDest *__restrict__ dests) {
     const unsigned long long units = *total / 16;
     for (unsigned long long u = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; u < units; u += (unsigned long long)gridDim.x * blockDim.x) {
         const unsigned long long at = u * 16;
@@ -233,6 +237,12 @@ __global__ __launch_bounds__(256) void k_arith_pack(const ArithMember *__restric
         const ArithMember me = mem[a];
         const unsigned long long nbits = states[me.state].out_pos, len = nbits / 8 + 1, j0 = at - offs[a];
         if (j0 >= len) continue;
+        uint8_t *dst = out + at;
+        if constexpr (OWN) {
+            const ArithDest d = dests[a];
+            if (len > d.cap) continue;
+            dst = d.dst + j0;
+        }
         const uint32_t p = 8 - (uint32_t)(nbits & 7);
         const uint4 r4 = *reinterpret_cast<const uint4 *>(me.out + j0);
         const uint32_t r[4] = {r4.x, r4.y, r4.z, r4.w};
@@ -249,7 +259,6 @@ __global__ __launch_bounds__(256) void k_arith_pack(const ArithMember *__restric
             }
         }
         if (j0 == 0) f[0] |= 1u << (8 - p);
-        uint8_t *dst = out + at;
         if (j0 + 16 <= len) *reinterpret_cast<uint4 *>(dst) = make_uint4(f[0], f[1], f[2], f[3]);
         else for (uint32_t i = 0; j0 + i < len; i++) dst[i] = (uint8_t)(f[i >> 2] >> (8 * (i & 3)));
     }
@@ -431,7 +440,12 @@ int encode_run(Ctx &c, hipStream_t s, const ArithMember *d_mem, const StateArea 
 }
 int pack_run(Ctx &c, hipStream_t s, const ArithMember *d_mem, const StateArea &a, size_t m, unsigned long long total, uint8_t *d_out) {
     const uint32_t blocks = (uint32_t)std::min<size_t>(ceil_div((size_t)total / 16, 256), 4096);
-    if (blocks) RSN_LAUNCH("k_arith_pack", k_arith_pack, dim3(blocks), dim3(256), 0, s, d_mem, (const ArithState *)a.st, (const unsigned long long *)a.offs, (const unsigned long long *)a.total, (uint32_t)m, d_out);
+    if (blocks) RSN_LAUNCH("k_arith_pack", k_arith_pack<false>, dim3(blocks), dim3(256), 0, s, d_mem, (const ArithState *)a.st, (const unsigned long long *)a.offs, (const unsigned long long *)a.total, (uint32_t)m, d_out, (const ArithDest *)nullptr);
+    return RSN_OK;
+}
+int pack_own_run(Ctx &c, hipStream_t s, const ArithMember *d_mem, const StateArea &a, size_t m, unsigned long long total, const ArithDest *d_dests) {
+    const uint32_t blocks = (uint32_t)std::min<size_t>(ceil_div((size_t)total / 16, 256), 4096);
+    if (blocks) RSN_LAUNCH("k_arith_pack_own", k_arith_pack<true>, dim3(blocks), dim3(256), 0, s, d_mem, (const ArithState *)a.st, (const unsigned long long *)a.offs, (const unsigned long long *)a.total, (uint32_t)m, (uint8_t *)nullptr, d_dests);
     return RSN_OK;
 }
 
@@ -577,9 +591,97 @@ int members_in_groups(Ctx &c, const std::vector<size_t> &idx, const size_t *lens
     return RSN_OK;
 }
 
+// ---- the batch calls on device buffers (rsn.h): the members where they lie.  Members [lo, hi) of `mem` in one go; sizes[i]:
+// the exact size of member i's result.  A member's failure: its code, *failed = the lowest such member.
+int compress_group_dev(Ctx &c, hipStream_t s, const rsn_dev_member *mem, size_t lo, size_t hi, size_t *sizes, size_t *failed) {
+    const size_t m = hi - lo;
+    const size_t desc_b = round_up(m * sizeof(ArithMember), 16), dest_b = round_up(m * sizeof(ArithDest), 16), summ_b = round_up(m * sizeof(ArithSummary), 16) + 16;
+    size_t raw_b = 0, max_n = 0;
+    for (size_t k = lo; k < hi; k++) { raw_b += raw_bytes(mem[k].n); max_n = std::max(max_n, mem[k].n); }
+    Admission gate(c, slotset::ARITH); gate.admit(desc_b + dest_b + raw_b, ADMIT_FROM);
+    *failed = lo;
+    void *p_up, *d_raw; StateArea a;
+    int rc = pinned_buf(c, desc_b + dest_b + summ_b, &p_up); if (rc) return rc;
+    rc = dev_buf(c, Slot::AR_RAW, desc_b + dest_b + raw_b, &d_raw); if (rc) return rc;      // (the descriptors and destinations in front)
+    rc = state_area(c, m, a); if (rc) return rc;
+    ArithMember *hm = (ArithMember *)p_up;
+    ArithDest *hd = (ArithDest *)((uint8_t *)p_up + desc_b);
+    size_t ro = desc_b + dest_b;
+    for (size_t k = 0; k < m; k++) {
+        const rsn_dev_member &x = mem[lo + k];
+        ArithMember &me = hm[k];
+        me.in = (const uint8_t *)x.d_in; me.n = x.n; me.out = (uint8_t *)d_raw + ro; me.cap = raw_bytes(x.n); me.origin = 0; me.state = (uint32_t)k; me.pad_ = 0;
+        hd[k] = ArithDest{(uint8_t *)x.d_out, x.d_out ? (unsigned long long)x.out_cap : 0ull};
+        ro += raw_bytes(x.n);
+    }
+    RSN_HIP(copy_async(d_raw, p_up, desc_b + dest_b, hipMemcpyHostToDevice, s));
+    ArithSummary *hs = (ArithSummary *)((uint8_t *)p_up + desc_b + dest_b);
+    unsigned long long *h_total = (unsigned long long *)((uint8_t *)hs + summ_b - 16);
+    rc = encode_run(c, s, (const ArithMember *)d_raw, a, m, max_n, hs, h_total); if (rc) return rc;
+    for (size_t k = 0; k < m; k++) if (hs[k].status != AR_DONE) { *failed = lo + k; return member_fail(c, hs[k]); }
+    for (size_t k = 0; k < m; k++) sizes[lo + k] = (size_t)hs[k].total;
+    return pack_own_run(c, s, (const ArithMember *)d_raw, a, m, *h_total, (const ArithDest *)((const uint8_t *)d_raw + desc_b));
+}
+
+// the decoder writes while it fits and keeps counting beyond: a member whose buffer is too small reports its exact need all the same
+int decompress_group_dev(Ctx &c, hipStream_t s, const rsn_dev_member *mem, size_t lo, size_t hi, size_t *sizes, size_t *failed) {
+    const size_t m = hi - lo;
+    const size_t desc_b = round_up(m * sizeof(ArithMember), 16), summ_b = round_up(m * sizeof(ArithSummary), 16);
+    *failed = lo;
+    void *p_pin, *d_desc; StateArea a;
+    int rc = pinned_buf(c, desc_b + summ_b, &p_pin); if (rc) return rc;
+    rc = dev_buf(c, Slot::AR_RAW, desc_b, &d_desc); if (rc) return rc;
+    rc = state_area(c, m, a); if (rc) return rc;
+    ArithMember *hm = (ArithMember *)p_pin;
+    ArithSummary *hs = (ArithSummary *)((uint8_t *)p_pin + desc_b);
+    for (size_t k = 0; k < m; k++) {
+        const rsn_dev_member &x = mem[lo + k];
+        ArithMember &me = hm[k];
+        me.in = (const uint8_t *)x.d_in; me.n = x.n; me.out = (uint8_t *)x.d_out; me.cap = x.d_out ? x.out_cap : 0; me.origin = 0; me.state = (uint32_t)k; me.pad_ = 0;
+    }
+    RSN_HIP(copy_async(d_desc, hm, m * sizeof(ArithMember), hipMemcpyHostToDevice, s));
+    // the summaries are looked at after one launch, then after every eight (arith_decode_dev), until no member is running
+    for (uint32_t round = 0;; round++) {
+        for (int k = 0; k < (round ? 8 : 1); k++)
+            RSN_LAUNCH("k_arith_dec", k_arith_dec, member_grid(m), dim3(64 * AR_WAVES), 0, s, (const ArithMember *)d_desc, a.st, a.summ, (uint32_t)m, ARITH_SLICE_SYMBOLS,
+                       round == 0 && k == 0 ? 1 : 0, (unsigned long long)ARITH_MAX_BYTES);
+        RSN_HIP(copy_async(hs, a.summ, m * sizeof(ArithSummary), hipMemcpyDeviceToHost, s));
+        RSN_HIP(hipStreamSynchronize(s));
+        bool running = false;
+        for (size_t k = 0; k < m && !running; k++) running = hs[k].status == AR_RUN || hs[k].status == AR_SCAN;
+        if (!running) break;
+    }
+    for (size_t k = 0; k < m; k++) if (hs[k].status != AR_DONE) { *failed = lo + k; return member_fail(c, hs[k]); }
+    for (size_t k = 0; k < m; k++) sizes[lo + k] = (size_t)hs[k].total;
+    return RSN_OK;
+}
+
 }  // namespace
 
 size_t arith_compress_bound(size_t n) { return 2 * n + 4; }
+
+int arith_members_dev(Ctx &c, hipStream_t s, bool enc, size_t n, const rsn_dev_member *mem, size_t *out_lens, size_t *failed) {
+    // the host form's groups (members_in_groups), the single calls' limits and words: a member above the limit fails when its turn comes
+    const size_t limit = enc ? (size_t)ARITH_MAX_BYTES : arith_compress_bound(ARITH_MAX_BYTES);
+    for (size_t lo = 0; lo < n;) {
+        if (mem[lo].n > limit) {
+            *failed = lo;
+            return enc ? c.fail(RSN_ERR_LIMIT, "arithmetic: %zu bytes are more than the %zu of one stream (one wave's serial work: DESIGN 7)", mem[lo].n, limit)
+                       : c.fail(RSN_ERR_LIMIT, "arithmetic: a stream of %zu bytes is more than the %zu of one stream (DESIGN 7)", mem[lo].n, limit);
+        }
+        size_t hi = lo, bytes = 0;
+        while (hi < n && hi - lo < AR_GROUP_MAX && mem[hi].n <= limit && (hi == lo || bytes + raw_bytes(mem[hi].n) <= AR_GROUP_BYTES)) bytes += raw_bytes(mem[hi++].n);
+        const int rc = enc ? compress_group_dev(c, s, mem, lo, hi, out_lens, failed) : decompress_group_dev(c, s, mem, lo, hi, out_lens, failed);
+        if (rc) return rc;
+        lo = hi;
+    }
+    RSN_HIP(hipStreamSynchronize(s));
+    for (size_t i = 0; i < n; i++) {
+        const size_t cap = mem[i].d_out ? mem[i].out_cap : 0;
+        if (out_lens[i] > cap) { *failed = i; return c.fail(RSN_ERR_CAPACITY, "arithmetic: output needs %zu bytes, buffer holds %zu", out_lens[i], cap); }
+    }
+    return RSN_OK;
+}
 
 int arith_compress_members(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, const SmallTake &take, size_t *failed) {
     hipStream_t s = c.own_stream;

@@ -69,6 +69,10 @@ struct BatchClass {
     bool (*takes)(const uint8_t *in, size_t n, int64_t window);
     int (*run)(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
                const SmallTake &take, std::vector<size_t> &back, size_t *failed);
+    // the device-buffer form (the batch calls on device buffers; group_run.h: run_groups_dev): the members `idx` of `mem` through the same
+    // groups and the same kernel on `s`, the staging in device scratch; answers[k]: GROUP_BACK, or member idx[k]'s length -- its bytes are in
+    // its d_out when that is at most its out_cap.  Null where the class has none (the Huffman rows: their plans are host work on the bytes).
+    int (*run_dev)(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const rsn_dev_member *mem, int64_t window, std::vector<uint32_t> &answers);
 };
 // lzss_small.hip: what lzss_small_compress / _decompress take (1 KiB with a window <= 0xFFFF; 2 KiB of stream).
 // lzss_mid.hip: a workgroup keeps the member's whole escaped stream in LDS.  The encoder takes LZSS_MID_IN_MAX bytes with a window of 1 to
@@ -138,6 +142,11 @@ int arith_decompress_members(Ctx &c, const std::vector<size_t> &idx, const uint8
 // device buffers, under the contract of the four at the top; out_cap == the exact size is taken, and *out_n on RSN_ERR_CAPACITY is it
 int arith_encode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t out_cap, size_t *out_n);
 int arith_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t out_cap, size_t *out_n);
+// the batch calls on device buffers (rsn.h): the n members where they lie, a wave each, in the host form's groups, on `s`,
+// which is synchronised.  out_lens[i]: the exact size of member i's result, complete in its d_out when that is at most its out_cap (a null
+// d_out counts as none).  RSN_ERR_CAPACITY: some member did not fit, *failed the lowest of them, every member has run; any other code:
+// the lowest failing member's, *failed that member (out_lens is then the caller's to clear).  The messages are the single calls'.
+int arith_members_dev(Ctx &c, hipStream_t s, bool enc, size_t n, const rsn_dev_member *mem, size_t *out_lens, size_t *failed);
 
 // exclusive scan of n counts on the stream (huff_encode.hip); *total (may be null) receives the sum; in and out must not overlap
 int scan_u64(Ctx &c, hipStream_t s, const char *name, const unsigned long long *in, unsigned long long *out, uint32_t n, unsigned long long *total);

@@ -1,0 +1,120 @@
+// group_dev.hip -- the grouped batch kernels on members that lie in device memory (the batch calls on device buffers, rsn.h).
+// The host form (group_run.h: run_groups) packs a group's members into pinned staging with memcpy and reads the results out of it; here the
+// staging is device scratch and two kernels stand where the host's copies stood: k_group_gather in front of the class's kernel,
+// k_group_scatter behind it.  The class's kernel is the host form's, launched unchanged with the device staging as `base`.  What crosses
+// PCIe per group is its tables (64 bytes a member, one copy up) and per class its answers (4 bytes a member, one copy down).
+#include "group_run.h"
+
+namespace rsn {
+
+namespace {
+
+constexpr int GD_THREADS = 256;
+
+// a member of a group: where it comes from, where its result goes, and its slots in the staging (the SmallMember beside it says the same to
+// the class's kernel)
+struct GatherEntry {
+    const uint8_t *src; uint8_t *dst;
+    unsigned long long cap;                       // bytes of dst (0: a size query, dst may be null)
+    uint32_t n, in_off, in_bytes, out_off, out_bytes, status_off;
+};
+static_assert(sizeof(GatherEntry) == 48 && (sizeof(SmallMember) + sizeof(GatherEntry)) % 16 == 0, "a group's two tables are whole 16-byte units");
+constexpr size_t GD_ENTRY = sizeof(SmallMember) + sizeof(GatherEntry);
+
+// A workgroup per member: the member's n bytes into its input slot, 16 at a time, zeros from byte n to the slot's end -- the class kernels
+// rely on those zeros, so what lies behind the member in the caller's memory never takes their place: the one unit that reaches beyond
+// src + n is masked, and nothing is loaded at or behind src + n rounded up to 16.  Then the status word: GROUP_PENDING.
+__global__ __launch_bounds__(GD_THREADS) void k_group_gather(const GatherEntry *__restrict__ tab, uint8_t *__restrict__ base) {
+    const GatherEntry e = tab[blockIdx.x];
+    const uint4 *src = reinterpret_cast<const uint4 *>(e.src);
+    uint4 *dst = reinterpret_cast<uint4 *>(base + e.in_off);
+    const uint32_t units = e.in_bytes / 16, full = e.n / 16, rest = e.n & 15;
+    for (uint32_t u = threadIdx.x; u < units; u += GD_THREADS) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (u < full) v = src[u];
+        else if (u == full && rest) {
+            v = src[u];
+            uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) {
+                const uint32_t keep = rest > 4 * k ? min(rest - 4 * k, 4u) : 0u;   // bytes of word k that are the member's
+                w[k] = keep == 4 ? w[k] : keep == 0 ? 0u : w[k] & ((1u << (8 * keep)) - 1);
+            }
+            v = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        dst[u] = v;
+    }
+    if (threadIdx.x == 0) *reinterpret_cast<uint32_t *>(base + e.status_off) = GROUP_PENDING;
+}
+
+// A workgroup per member, behind the class's kernel on the stream: the status word into the class's compact array -- GROUP_BACK, or the
+// length of the result -- and, when the result fits the member's buffer, the output slot into it: whole 16-byte units, then the tail byte
+// by byte, never a byte at or behind dst + len.  A word no kernel of the class can have written (still GROUP_PENDING, or a length beyond
+// the output slot) goes down as GROUP_PENDING: the host words it as the device failure it is, and nothing is copied.
+__global__ __launch_bounds__(GD_THREADS) void k_group_scatter(const GatherEntry *__restrict__ tab, const uint8_t *__restrict__ base, uint32_t *__restrict__ answers) {
+    const GatherEntry e = tab[blockIdx.x];
+    uint32_t v = *reinterpret_cast<const uint32_t *>(base + e.status_off);
+    if (v != GROUP_BACK && v > e.out_bytes) v = GROUP_PENDING;
+    if (threadIdx.x == 0) answers[blockIdx.x] = v;
+    if (v >= GROUP_BACK || v > e.cap) return;
+    const uint4 *src = reinterpret_cast<const uint4 *>(base + e.out_off);
+    uint4 *dst = reinterpret_cast<uint4 *>(e.dst);
+    const uint32_t full = v / 16;
+    for (uint32_t u = threadIdx.x; u < full; u += GD_THREADS) dst[u] = src[u];
+    const uint32_t i = full * 16 + threadIdx.x;
+    if (threadIdx.x < 16 && i < v) e.dst[i] = base[e.out_off + i];
+}
+
+}  // namespace
+
+int run_groups_dev(Ctx &c, hipStream_t s, const char *what, const std::vector<size_t> &idx, const rsn_dev_member *mem,
+                   size_t (*in_bytes)(size_t n), size_t (*out_bytes)(size_t n), const GroupLaunch &launch, std::vector<uint32_t> &answers) {
+    const size_t count = idx.size();
+    answers.assign(count, GROUP_PENDING);
+    if (count == 0) return RSN_OK;
+    auto need = [&](size_t k) { const size_t n = mem[idx[k]].n; return group_need(GD_ENTRY, in_bytes(n), out_bytes(n)); };
+    // the groups first: the largest one sizes the staging, and every group's tables have a pinned region of their own -- no group waits
+    // for the copy of the one before it
+    std::vector<GroupCut> cuts;
+    size_t stage = 0;
+    for (size_t j = 0; j < count;) { const GroupCut cut = next_group(j, count, SMALL_GROUP_MAX, SMALL_GROUP_BYTES, need); stage = std::max(stage, cut.bytes); cuts.push_back(cut); j = cut.hi; }
+    const size_t tables = count * GD_ENTRY, down = round_up(count * sizeof(uint32_t), 16);
+    Admission gate(c, slotset::GROUP_DEV); gate.admit(stage + down, ADMIT_FROM);
+    void *pp, *d_stage, *d_ans;
+    int rc = pinned_buf(c, tables + down, &pp); if (rc) return rc;
+    rc = dev_buf(c, Slot::GD_STAGE, stage + 64, &d_stage); if (rc) return rc;
+    rc = dev_buf(c, Slot::GD_LENS, down, &d_ans); if (rc) return rc;
+    uint8_t *pin = (uint8_t *)pp, *base = (uint8_t *)d_stage;
+    size_t j = 0;
+    for (const GroupCut &cut : cuts) {
+        const size_t g = cut.hi - j;
+        SmallMember *tab = (SmallMember *)(pin + j * GD_ENTRY);
+        GatherEntry *gat = (GatherEntry *)(tab + g);
+        GroupLayout lay(g, GD_ENTRY);
+        for (size_t q = 0; q < g; q++) {
+            const rsn_dev_member &m = mem[idx[j + q]];
+            const size_t ib = in_bytes(m.n), ob = out_bytes(m.n);
+            const MemberSlots o = lay.member(ib, ob);
+            tab[q] = SmallMember{o.in, (uint32_t)m.n, o.out, o.status};
+            gat[q] = GatherEntry{(const uint8_t *)m.d_in, (uint8_t *)m.d_out, m.d_out ? (unsigned long long)m.out_cap : 0ull,
+                                 (uint32_t)m.n, o.in, (uint32_t)ib, o.out, (uint32_t)ob, o.status};
+        }
+        if (lay.end() != cut.bytes || lay.end() > 0xFFFFFFFFull) return c.fail(RSN_ERR_DEVICE, "%s: internal error: a group of %zu members lays out to %zu bytes, cut at %zu", what, g, lay.end(), cut.bytes);
+        RSN_HIP(copy_async(base, tab, g * GD_ENTRY, hipMemcpyHostToDevice, s));
+        const GatherEntry *d_gat = (const GatherEntry *)(base + g * sizeof(SmallMember));
+        RSN_LAUNCH("group_gather", k_group_gather, dim3((uint32_t)g), dim3(GD_THREADS), 0, s, d_gat, base);
+        rc = launch(s, (uint32_t)g, (const SmallMember *)base, base); if (rc) return rc;
+        RSN_LAUNCH("group_scatter", k_group_scatter, dim3((uint32_t)g), dim3(GD_THREADS), 0, s, d_gat, (const uint8_t *)base, (uint32_t *)d_ans + j);
+        j = cut.hi;
+    }
+    uint32_t *h_ans = (uint32_t *)(pin + tables);
+    RSN_HIP(copy_async(h_ans, d_ans, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    RSN_HIP(hipStreamSynchronize(s));
+    for (size_t k = 0; k < count; k++) {
+        if (h_ans[k] == GROUP_PENDING) return c.fail(RSN_ERR_DEVICE, "%s: the grouped kernel finished without an answer for one of its members", what);
+        answers[k] = h_ans[k];
+    }
+    return RSN_OK;
+}
+
+}  // namespace rsn

@@ -1,6 +1,6 @@
 // group_layout.h -- the arithmetic of a group of batch members in pinned staging, as plain host code: no HIP include, so a CPU
 // test (tests/group_layout_test.cpp) checks what keeps a grouped kernel inside its buffers -- slots that do not overlap, zero padding
-// behind every input, 16-byte aligned offsets.  group_run.h's run_groups is the one user.
+// behind every input, 16-byte aligned offsets.  group_run.h's run_groups and group_dev.hip's run_groups_dev (the same groups on device staging) are the users.
 //
 // Staging of a group of g members: a table of g entries of E bytes (E a multiple of 16), then per member its input slot (the member's
 // bytes, zeros behind them), its output slot and 16 bytes of status.  Input and output slots are whole 16-byte units.

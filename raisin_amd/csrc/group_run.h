@@ -66,4 +66,30 @@ int run_member_groups(Ctx &c, const char *what, const std::vector<size_t> &idx, 
         launch, [](const uint32_t *w) { return w[0]; }, take, back, failed);
 }
 
+// The same classes on device buffers (the batch calls on device buffers, rsn.h; group_dev.hip): the members idx[k] of `mem`
+// in the same groups (next_group, GroupLayout), the staging in device scratch (Slot::GD_STAGE) -- per group one small copy up, the member
+// table and a gather table from a pinned region of the group's own, then k_group_gather (the members into their input slots, zeros behind
+// them, the status words GROUP_PENDING), the class's kernel through `launch` as above, and k_group_scatter (what fits the member's buffer
+// out of the output slot, the status into a word per member).  No host wait between the groups -- the stream orders the staging's reuse --
+// and one at the end, when the words come down: answers[k] is GROUP_BACK or the length of member idx[k]'s result, which is complete in
+// mem[idx[k]].d_out when it is at most its out_cap.
+using GroupLaunch = std::function<int(hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base)>;
+int run_groups_dev(Ctx &c, hipStream_t s, const char *what, const std::vector<size_t> &idx, const rsn_dev_member *mem,
+                   size_t (*in_bytes)(size_t n), size_t (*out_bytes)(size_t n), const GroupLaunch &launch, std::vector<uint32_t> &answers);
+
+// A class of SmallMember entries is stated ONCE, as a type K -- K::what (the name in messages), K::in_bytes(n) / K::out_bytes(n) (the slots of
+// a member of n bytes, group_layout.h) and K::launch(c, s, g, tab, base, window) (the group's kernel) -- and both of its runners, the
+// host-buffer form and the device-buffer form (BatchClass::run / run_dev, codecs.h), are these two.
+template <class K>
+int class_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
+              const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+    return run_member_groups(c, K::what, idx, ins, lens, K::in_bytes, K::out_bytes,
+        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) { return K::launch(c, s, g, tab, base, window); }, take, back, failed);
+}
+template <class K>
+int class_run_dev(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const rsn_dev_member *mem, int64_t window, std::vector<uint32_t> &answers) {
+    return run_groups_dev(c, s, K::what, idx, mem, K::in_bytes, K::out_bytes,
+        [&](hipStream_t s2, uint32_t g, const SmallMember *tab, uint8_t *base) { return K::launch(c, s2, g, tab, base, window); }, answers);
+}
+
 }  // namespace rsn

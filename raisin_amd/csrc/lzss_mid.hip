@@ -366,27 +366,30 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_dec(const SmallMember *__restri
 namespace {
 bool mid_enc_takes(const uint8_t *, size_t n, int64_t window) { return n != 0 && n <= LZSS_MID_IN_MAX && window >= 1 && window <= (int64_t)MID_W_MAX; }
 bool mid_dec_takes(const uint8_t *, size_t n, int64_t) { return n != 0 && n <= LZSS_MID_E_MAX; }
-int mid_enc_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
-                const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return run_member_groups(c, "lzss batch compress", idx, ins, lens, lzss_in_slot, [](size_t n) { return lzss_enc_out_slot(n, LZSS_MID_E_MAX); },
-        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
-            const int rc = func_dyn_lds(c, reinterpret_cast<const void *>(k_lzss_mid_enc), EL_BYTES); if (rc) return rc;
-            RSN_LAUNCH("lzss_batch_mid_enc", k_lzss_mid_enc, dim3(g), dim3(MT), EL_BYTES, s, tab, base, (uint32_t)window);
-            return RSN_OK;
-        }, take, back, failed);
-}
-int mid_dec_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t,
-                const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return run_member_groups(c, "lzss batch decompress", idx, ins, lens, lzss_in_slot, [](size_t) { return lzss_dec_out_slot(LZSS_MID_E_MAX); },
-        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
-            const int rc = func_dyn_lds(c, reinterpret_cast<const void *>(k_lzss_mid_dec), DL_BYTES); if (rc) return rc;
-            RSN_LAUNCH("lzss_batch_mid_dec", k_lzss_mid_dec, dim3(g), dim3(MT), DL_BYTES, s, tab, base);
-            return RSN_OK;
-        }, take, back, failed);
-}
+struct MidEncClass {
+    static constexpr const char *what = "lzss batch compress";
+    static size_t in_bytes(size_t n) { return lzss_in_slot(n); }
+    static size_t out_bytes(size_t n) { return lzss_enc_out_slot(n, LZSS_MID_E_MAX); }
+    static int launch(Ctx &c, hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base, int64_t window) {
+        const int rc = func_dyn_lds(c, reinterpret_cast<const void *>(k_lzss_mid_enc), EL_BYTES); if (rc) return rc;
+        RSN_LAUNCH("lzss_batch_mid_enc", k_lzss_mid_enc, dim3(g), dim3(MT), EL_BYTES, s, tab, base, (uint32_t)window);
+        return RSN_OK;
+    }
+};
+struct MidDecClass {
+    static constexpr const char *what = "lzss batch decompress";
+    static size_t in_bytes(size_t n) { return lzss_in_slot(n); }
+    static size_t out_bytes(size_t) { return lzss_dec_out_slot(LZSS_MID_E_MAX); }
+    static int launch(Ctx &c, hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base, int64_t) {
+        const int rc = func_dyn_lds(c, reinterpret_cast<const void *>(k_lzss_mid_dec), DL_BYTES); if (rc) return rc;
+        RSN_LAUNCH("lzss_batch_mid_dec", k_lzss_mid_dec, dim3(g), dim3(MT), DL_BYTES, s, tab, base);
+        return RSN_OK;
+    }
+};
 }  // namespace
 const BatchClass &lzss_mid_class(bool compress) {
-    static const BatchClass enc = {"lzss mid compress", LZSS_MID_GROUP_MIN, mid_enc_takes, mid_enc_run}, dec = {"lzss mid decompress", LZSS_MID_GROUP_MIN, mid_dec_takes, mid_dec_run};
+    static const BatchClass enc = {"lzss mid compress", LZSS_MID_GROUP_MIN, mid_enc_takes, class_run<MidEncClass>, class_run_dev<MidEncClass>},
+                            dec = {"lzss mid decompress", LZSS_MID_GROUP_MIN, mid_dec_takes, class_run<MidDecClass>, class_run_dev<MidDecClass>};
     return compress ? enc : dec;
 }
 

@@ -385,27 +385,30 @@ int group_wait(Ctx &c, hipStream_t s, const uint8_t *base, const std::vector<uin
     return RSN_OK;
 }
 
-// ---------------------------------------------------------------- the two classes of the batch calls (codecs.h; the packer: group_run.h)
+// ---------------------------------------------------------------- the two classes of the batch calls (codecs.h; the packers: group_run.h)
 namespace {
-int small_enc_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
-                  const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return run_member_groups(c, "lzss batch compress", idx, ins, lens, lzss_in_slot, [](size_t n) { return lzss_enc_out_slot(n, SL_E_MAX); },
-        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
-            RSN_LAUNCH("lzss_batch_enc", k_lzss_batch_enc, dim3(g), dim3(SLT), 0, s, tab, base, (uint32_t)(window <= 0 ? 0 : window));
-            return RSN_OK;
-        }, take, back, failed);
-}
-int small_dec_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t,
-                  const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return run_member_groups(c, "lzss batch decompress", idx, ins, lens, lzss_in_slot, [](size_t) { return lzss_dec_out_slot(SL_DEC_E_MAX); },
-        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
-            RSN_LAUNCH("lzss_batch_dec", k_lzss_batch_dec, dim3(g), dim3(SLT), 0, s, tab, base);
-            return RSN_OK;
-        }, take, back, failed);
-}
+struct SmallEncClass {
+    static constexpr const char *what = "lzss batch compress";
+    static size_t in_bytes(size_t n) { return lzss_in_slot(n); }
+    static size_t out_bytes(size_t n) { return lzss_enc_out_slot(n, SL_E_MAX); }
+    static int launch(Ctx &c, hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base, int64_t window) {
+        RSN_LAUNCH("lzss_batch_enc", k_lzss_batch_enc, dim3(g), dim3(SLT), 0, s, tab, base, (uint32_t)(window <= 0 ? 0 : window));
+        return RSN_OK;
+    }
+};
+struct SmallDecClass {
+    static constexpr const char *what = "lzss batch decompress";
+    static size_t in_bytes(size_t n) { return lzss_in_slot(n); }
+    static size_t out_bytes(size_t) { return lzss_dec_out_slot(SL_DEC_E_MAX); }
+    static int launch(Ctx &c, hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base, int64_t) {
+        RSN_LAUNCH("lzss_batch_dec", k_lzss_batch_dec, dim3(g), dim3(SLT), 0, s, tab, base);
+        return RSN_OK;
+    }
+};
 }  // namespace
 const BatchClass &lzss_small_class(bool compress) {
-    static const BatchClass enc = {"lzss small compress", 1, small_enc_takes, small_enc_run}, dec = {"lzss small decompress", 1, small_dec_takes, small_dec_run};
+    static const BatchClass enc = {"lzss small compress", 1, small_enc_takes, class_run<SmallEncClass>, class_run_dev<SmallEncClass>},
+                            dec = {"lzss small decompress", 1, small_dec_takes, class_run<SmallDecClass>, class_run_dev<SmallDecClass>};
     return compress ? enc : dec;
 }
 

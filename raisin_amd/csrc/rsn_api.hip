@@ -2,6 +2,8 @@
 // context.  Host-buffer entry points stage through device memory and call the
 // device-resident codecs; there is no CPU compute path.
 #include "codecs.h"
+#include "dev_ranges.h"
+#include "group_layout.h"
 #include "rsn_common.h"
 #include "rsn_helpers.h"
 
@@ -1271,6 +1273,90 @@ static int arithmetic_dev(bool enc, const void *d_in, size_t n, void *d_out, siz
 }
 size_t rsn_arithmetic_compress_bound(size_t n) { return arith_compress_bound(n); }
 
+// ---- the batch calls on device buffers (rsn.h)
+// The argument checks, before a device is looked for: the arrays, then the members in index order, then the ranges (dev_ranges.h).
+// word: the codec's name in front of the alignment message, as the single calls word it.  RSN_OK with n == 0: the caller returns, too.
+static int batch_dev_args(Ctx &c, size_t n, const rsn_dev_member *mem, size_t *out_lens, const char *word) {
+    if (n == 0) return RSN_OK;
+    if (!mem || !out_lens) return c.fail(RSN_ERR_ARG, "null argument");
+    for (size_t i = 0; i < n; i++) out_lens[i] = 0;
+    std::vector<DevRange> ins, outs;
+    for (size_t i = 0; i < n; i++) {
+        const rsn_dev_member &m = mem[i];
+        if (!m.d_in && m.n) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
+        if (!m.d_out && m.out_cap) return c.fail(RSN_ERR_ARG, "member %zu: a null d_out with an out_cap of %zu (the size query is out_cap 0)", i, m.out_cap);
+        if (((uintptr_t)m.d_in & 15) || ((uintptr_t)m.d_out & 15)) return c.fail(RSN_ERR_ARG, "member %zu: %s: device buffers must be 16-byte aligned", i, word);
+        add_dev_range(ins, m.d_in, m.n, i);
+        add_dev_range(outs, m.d_out, m.out_cap, i);
+    }
+    size_t a = 0, b = 0;
+    const int clash = dev_ranges_clash(ins, outs, &a, &b);
+    if (clash == 1) return c.fail(RSN_ERR_ARG, "member %zu: its output range and member %zu's output range overlap", a, b);
+    if (clash == 2) return c.fail(RSN_ERR_ARG, "member %zu: its output range and member %zu's input range overlap", a, b);
+    return RSN_OK;
+}
+// what the call answers once every member has run: a failure other than RSN_ERR_CAPACITY clears out_lens
+static int batch_dev_answer(Ctx &c, int rc, size_t failed, size_t n, size_t *out_lens) {
+    if (rc == RSN_OK) return RSN_OK;
+    if (rc != RSN_ERR_CAPACITY) for (size_t i = 0; i < n; i++) out_lens[i] = 0;
+    const std::string m = c.err;
+    return c.fail(rc, "member %zu: %s", failed, m.c_str());
+}
+
+// LZSS: the members by class as in the host form (classify: the same rows, the same takes(), the same minimums), each class through its
+// device-form runner; what no class takes, what a class below its minimum holds and what a kernel hands back run the single call's codec
+// on the same stream, in index order, straight into the member's buffer.  No worker threads: one stream, device buffers.
+static int lzss_batch_dev(bool enc, size_t n, const rsn_dev_member *mem, int64_t window, size_t *out_lens, void *stream) {
+    Ctx &c = ctx(); hipStream_t s;
+    int rc = batch_dev_args(c, n, mem, out_lens, "lzss"); if (rc || n == 0) return rc;
+    rc = dev_prologue(c, stream, &s); if (rc) return rc;
+    constexpr size_t NONE = (size_t)-1;
+    const BatchRows rows = batch_classes(BatchLayer::LZSS, enc);
+    std::vector<const uint8_t *> ins(n);
+    std::vector<size_t> lens(n);
+    for (size_t i = 0; i < n; i++) { ins[i] = (const uint8_t *)mem[i].d_in; lens[i] = mem[i].n; }   // (takes() looks at no byte of an LZSS member)
+    std::vector<std::vector<size_t>> per;
+    std::vector<size_t> rest;
+    classify(rows, n, ins.data(), lens.data(), window, per, rest);
+    size_t tight = NONE; std::string tight_msg;                           // the lowest member that did not fit, and what the single call says of it
+    auto cap_of = [&](size_t i) { return mem[i].d_out ? mem[i].out_cap : (size_t)0; };
+    std::vector<uint32_t> answers;
+    for (size_t r = 0; r < rows.n; r++) {
+        if (per[r].empty()) continue;
+        rc = rows.first[r]->run_dev(c, s, per[r], mem, window, answers);
+        if (rc) return batch_dev_answer(c, rc, per[r][0], n, out_lens);   // (a device failure: nothing more is launched)
+        for (size_t k = 0; k < per[r].size(); k++) {
+            const size_t i = per[r][k], got = answers[k];
+            if (answers[k] == GROUP_BACK) { rest.push_back(i); continue; }
+            if (got <= cap_of(i)) { out_lens[i] = got; continue; }
+            out_lens[i] = round_up(got, 16) + 16;                         // (as lzss_encode_dev / lzss_decode_dev report it)
+            if (i < tight) { tight = i; c.fail(RSN_ERR_CAPACITY, "lzss: output needs %zu bytes, buffer holds %zu", got, cap_of(i)); tight_msg = c.err; }
+        }
+    }
+    std::sort(rest.begin(), rest.end());
+    for (size_t i : rest) {
+        size_t got = 0;
+        rc = enc ? lzss_encode_dev(c, s, ins[i], lens[i], window, (uint8_t *)mem[i].d_out, cap_of(i), &got)
+                 : lzss_decode_dev(c, s, ins[i], lens[i], (uint8_t *)mem[i].d_out, cap_of(i), &got);
+        if (rc != RSN_OK && rc != RSN_ERR_CAPACITY) return batch_dev_answer(c, rc, i, n, out_lens);
+        out_lens[i] = got;
+        if (rc == RSN_ERR_CAPACITY && i < tight) { tight = i; tight_msg = c.err; }
+    }
+    RSN_HIP(hipStreamSynchronize(s));
+    if (tight == NONE) return RSN_OK;
+    c.err = tight_msg;
+    return batch_dev_answer(c, RSN_ERR_CAPACITY, tight, n, out_lens);
+}
+
+static int arithmetic_batch_dev(bool enc, size_t n, const rsn_dev_member *mem, size_t *out_lens, void *stream) {
+    Ctx &c = ctx(); hipStream_t s;
+    int rc = batch_dev_args(c, n, mem, out_lens, "arithmetic"); if (rc || n == 0) return rc;
+    rc = dev_prologue(c, stream, &s); if (rc) return rc;
+    size_t failed = 0;
+    rc = arith_members_dev(c, s, enc, n, mem, out_lens, &failed);
+    return batch_dev_answer(c, rc, failed, n, out_lens);
+}
+
 static int rsn_huffman_compress_sharded_impl(const uint8_t *in, size_t n, int shards, uint8_t **out, size_t *out_n) {
     Ctx &c = ctx();
     int rc0 = host_args(c, in, n, out, out_n); if (rc0) return rc0;
@@ -1698,6 +1784,10 @@ template <class F> int guarded_out(uint8_t **out, size_t *out_n, F f) noexcept {
 template <class F> int guarded_outs(size_t n, uint8_t **outs, size_t *out_lens, F f) noexcept {
     return guarded_call<int>(f, [&](int code, const char *m) { if (outs && out_lens) drop_results(n, outs, out_lens); return boundary_error(code, m); });
 }
+// ... and the batch calls on device buffers: something thrown leaves every out_lens[i] 0, as every failure but RSN_ERR_CAPACITY does
+template <class F> int guarded_lens(size_t n, const rsn_dev_member *members, size_t *out_lens, F f) noexcept {
+    return guarded_call<int>(f, [&](int code, const char *m) { if (members && out_lens) for (size_t i = 0; i < n; i++) out_lens[i] = 0; return boundary_error(code, m); });
+}
 const Codec &HUFF_ENC = codec(RSN_LAYER_HUFFMAN, true), &HUFF_DEC = codec(RSN_LAYER_HUFFMAN, false), &LZSS_ENC = codec(RSN_LAYER_LZSS, true), &LZSS_DEC = codec(RSN_LAYER_LZSS, false);
 }  // namespace
 
@@ -1725,6 +1815,10 @@ int rsn_arithmetic_compress_batch(size_t n, const uint8_t *const *ins, const siz
 int rsn_arithmetic_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) { return guarded_outs(n, outs, out_lens, [&] { return arithmetic_batch(false, n, ins, lens, outs, out_lens); }); }
 int rsn_arithmetic_compress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded([&] { return arithmetic_dev(true, d_in, n, d_out, out_cap, out_n, stream); }); }
 int rsn_arithmetic_decompress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded([&] { return arithmetic_dev(false, d_in, n, d_out, out_cap, out_n, stream); }); }
+int rsn_lzss_compress_batch_dev(size_t n, const rsn_dev_member *members, int64_t window, size_t *out_lens, void *stream) { return guarded_lens(n, members, out_lens, [&] { return lzss_batch_dev(true, n, members, window, out_lens, stream); }); }
+int rsn_lzss_decompress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream) { return guarded_lens(n, members, out_lens, [&] { return lzss_batch_dev(false, n, members, 0, out_lens, stream); }); }
+int rsn_arithmetic_compress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream) { return guarded_lens(n, members, out_lens, [&] { return arithmetic_batch_dev(true, n, members, out_lens, stream); }); }
+int rsn_arithmetic_decompress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream) { return guarded_lens(n, members, out_lens, [&] { return arithmetic_batch_dev(false, n, members, out_lens, stream); }); }
 int rsn_huffman_compress_sharded(const uint8_t *in, size_t n, int shards, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return rsn_huffman_compress_sharded_impl(in, n, shards, out, out_n); }); }
 int rsn_layers_compress(const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return layers_host(true, in, n, layers, n_layers, out, out_n); }); }
 int rsn_layers_decompress(const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return layers_host(false, in, n, layers, n_layers, out, out_n); }); }

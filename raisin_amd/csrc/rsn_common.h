@@ -77,7 +77,9 @@ enum class Slot : int {
     L_STAT = 42,        // layered round trip: the two histograms and the first-difference word [layered]
     AR_STATE = 43,      // arithmetic codec: the members' state records (table, coder state, cursors), their summaries, sizes and offsets [arith]
     AR_RAW = 44,        // arithmetic codec: the encoder's raw bits before the front pad (a device-buffer call: its descriptor in front);
-                        //   the decoder's descriptors [arith]
+                        //   the decoder's descriptors (the batch call on device buffers: both directions' descriptors in front) [arith]
+    GD_STAGE = 45,      // batch calls on device buffers (group_dev.hip): a group's staging -- the member and gather tables, then the members' slots [group_dev]
+    GD_LENS = 46,       // batch calls on device buffers: a class's answers, a word per member [group_dev]
 };
 constexpr int RING = 3;                                                  // the batch pipeline's depth: RING inputs, RING segments
 constexpr Slot ring_in(int r) { return (Slot)((int)Slot::RING_IN0 + r); }
@@ -102,11 +104,13 @@ constexpr unsigned long long HOST_CALL = STAGING | LZSS_ENC;              // (th
 constexpr unsigned long long LAYERED_CALL = HOST_CALL | LAYERED;
 constexpr unsigned long long ARITH = slot_mask(S::AR_STATE, S::AR_RAW);   // the arithmetic codec's own: what its device-buffer calls' gate gives back
 constexpr unsigned long long ARITH_HOST = STAGING | ARITH;                // ... and its host-buffer calls', which stage through the staging pair
+constexpr unsigned long long GROUP_DEV = slot_mask(S::GD_STAGE, S::GD_LENS);   // the grouped kernels' staging on the device: what a class's run of the batch calls on device buffers gives back
 // (RING is written out three times: the enumerators, RINGS and this check change together)
 static_assert(ring_in(RING) == Slot::RING_OUT0 && ring_out(RING - 1) == Slot::RING_OUT2, "the ring's slots are RING inputs, then RING segments");
 static_assert(((STAGING | RINGS | LAYERED) & (LZSS_ENC | LZSS_DEC)) == 0, "a codec's gate releases no staging, ring or layered slot: their callers still use them");
 static_assert(((STAGING | LAYERED) & (HUFF_OWN | LZSS_ENC_OWN | LZSS_DEC_OWN)) == 0, "no codec allocates a staging or a layered slot");
 static_assert((LZSS_DEC & ~LZSS_ENC) == 0, "HOST_CALL covers both LZSS directions");
+static_assert((GROUP_DEV & (HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED | ARITH)) == 0, "the device staging is released by its own gate only: the single calls that follow a class never hold it");
 static_assert((ARITH & (HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED)) == 0, "the arithmetic codec shares no slot of its own with another codec or a caller");
 }  // namespace slotset
 
@@ -123,7 +127,7 @@ struct Ctx {
     std::vector<hipEvent_t> free_events;
 
     struct Buf { void *p = nullptr; size_t cap = 0; unsigned long long gen = 0; };   // gen: process-unique number of this allocation (dev_buf) -- an address can come back with other contents
-    enum { N_BUFS = (int)Slot::AR_RAW + 1 };   // (the table above)
+    enum { N_BUFS = (int)Slot::GD_LENS + 1 };   // (the table above)
     Buf bufs[N_BUFS];
     Buf &buf(Slot k) { return bufs[(int)k]; }
     void *pinned = nullptr; size_t pinned_cap = 0;

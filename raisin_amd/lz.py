@@ -95,3 +95,17 @@ def decompress_tensor(src, out=None, stream=None):
     """below 1 MiB of stream a generous guess costs less than a second call; from there the size query first"""
     n = src.numel()
     return _lib.dev_tensor(_lib.lib().rsn_lzss_decompress_dev, src, out, stream, 16 * n + (1 << 16) if n < (1 << 20) else None)
+
+
+def compress_tensors(srcs, window=DefaultWindowSize, outs=None, stream=None):
+    """compress_tensor for a list of 1-D uint8 CUDA tensors in ONE call (rsn_lzss_compress_batch_dev): the members of CompressAsyncBatch's
+    classes many to a launch without leaving the device, the rest through the single call's path.  Each tensor's data_ptr must be 16-byte
+    aligned (slices of one allocation at 16-byte offsets are).  Returns the streams, trimmed; without `outs` they are views of one
+    allocation of bound-sized slots.  An `out` that is too small raises (RsnError.out_lens: sizes that suffice)."""
+    return _lib.dev_tensors(_lib.lib().rsn_lzss_compress_batch_dev, srcs, outs, stream, compress_bound, int(window), retry=False)
+
+
+def decompress_tensors(srcs, outs=None, stream=None):
+    """decompress_tensor for a list of streams in ONE call (rsn_lzss_decompress_batch_dev).  Without `outs`: a guess of sixteen times the
+    stream plus 4 KiB per member, and the members that expand further are run once more with the capacities the call reports."""
+    return _lib.dev_tensors(_lib.lib().rsn_lzss_decompress_batch_dev, srcs, outs, stream, lambda n: 16 * n + 4096)
