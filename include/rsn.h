@@ -263,9 +263,24 @@ RSN_API int rsn_arithmetic_decompress_dev(const void *d_in, size_t n, void *d_ou
  * bytes always suffices for a compress member, and an out_cap equal to the exact result size is accepted whatever its remainder
  * mod 16.  Nothing is ever written outside [d_out, d_out + out_cap) of any member; what a member that did not fit, or the members of
  * a failed call, hold is unspecified.
- * Huffman is not offered in this form: its decoder's header parse and its general encoder's tree are host work on the stream's own
- * bytes, so a member's bytes would have to come down -- the follow-up is a device-side header parse for byte alphabets. */
+ * Huffman (rsn_huffman_compress_batch_dev, rsn_huffman_decompress_batch_dev; the single calls are rsn_huffman_compress_dev /
+ * rsn_huffman_decompress_dev) runs the host batch calls' classes the same way.  To compress, members of 2 bytes to 64 KiB of a byte
+ * alphabet (every byte below 0x80, two distinct bytes at least) are gathered and coded by the grouped encoders, which build their
+ * trees themselves.  To decompress, one more kernel in front reads every candidate stream's header WHERE IT LIES -- separator, counts,
+ * the reference's tree and the stream's bit bounds, a workgroup a member -- and 16 bytes a member come down for the host to size the
+ * slots; streams of a byte alphabet that promise at most 64 KiB from at most 56 KiB of payload then run the grouped decoders.  What
+ * still takes the single call on the same stream, in index order: rune alphabets (a byte >= 0x80 in the input or among the header's
+ * symbols), a single distinct byte, headers the device-side plan refuses (a count of 65536 or more, foreign or malformed headers --
+ * the single call decodes them or words their error), members above 64 KiB, and classes below their minimum count.  An empty member
+ * fails rsn_huffman_compress_batch_dev with RSN_ERR_EMPTY, as in the single call, before a device is looked for.
+ * Huffman capacities: a buffer of rsn_huffman_compress_bound(n) always suffices.  A member that takes the single call needs what
+ * rsn_huffman_compress_dev / rsn_huffman_decompress_dev need (compress: the exact size rounded up to 16, plus 32); a grouped member is
+ * written by the scatter kernel, and an out_cap equal to its exact size is accepted.  On RSN_ERR_CAPACITY out_lens[i] of a member
+ * that did not fit is the single call's figure whichever path it took -- compress: the exact size rounded up to 16, plus 32;
+ * decompress: rounded up to 16, plus 16 -- so a second call with the reported figures always succeeds. */
 typedef struct { const void *d_in; size_t n; void *d_out; size_t out_cap; } rsn_dev_member;
+RSN_API int rsn_huffman_compress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream);
+RSN_API int rsn_huffman_decompress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream);
 RSN_API int rsn_lzss_compress_batch_dev(size_t n, const rsn_dev_member *members, int64_t window, size_t *out_lens, void *stream);
 RSN_API int rsn_lzss_decompress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream);
 RSN_API int rsn_arithmetic_compress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream);

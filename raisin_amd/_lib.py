@@ -59,6 +59,7 @@ SYMBOLS = [
     "rsn_arithmetic_compress_bound", "rsn_arithmetic_compress", "rsn_arithmetic_decompress",
     "rsn_arithmetic_compress_batch", "rsn_arithmetic_decompress_batch", "rsn_arithmetic_compress_dev", "rsn_arithmetic_decompress_dev",
     "rsn_lzss_compress_batch_dev", "rsn_lzss_decompress_batch_dev", "rsn_arithmetic_compress_batch_dev", "rsn_arithmetic_decompress_batch_dev",
+    "rsn_huffman_compress_batch_dev", "rsn_huffman_decompress_batch_dev",
 ]
 
 
@@ -107,7 +108,8 @@ def lib():
     L.rsn_lzss_compress_dev.argtypes = [vp, sz, ctypes.c_int64, vp, sz, szp, vp]
     mp = ctypes.POINTER(DevMember)
     L.rsn_lzss_compress_batch_dev.argtypes = [sz, mp, ctypes.c_int64, szp, vp]
-    for name in ("rsn_lzss_decompress_batch_dev", "rsn_arithmetic_compress_batch_dev", "rsn_arithmetic_decompress_batch_dev"):
+    for name in ("rsn_lzss_decompress_batch_dev", "rsn_arithmetic_compress_batch_dev", "rsn_arithmetic_decompress_batch_dev",
+                 "rsn_huffman_compress_batch_dev", "rsn_huffman_decompress_batch_dev"):
         getattr(L, name).argtypes = [sz, mp, szp, vp]
     L.rsn_prof_enable.argtypes = [ctypes.c_int]
     L.rsn_prof_enable.restype = None

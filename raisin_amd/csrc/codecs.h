@@ -6,6 +6,7 @@
 #include "huff_host.h"
 #include "lzss_legacy.h"
 #include "rsn_common.h"
+#include "huff_parse_small.h"   // (behind the HIP runtime: its functions are __host__ __device__ under hipcc)
 
 namespace rsn {
 
@@ -63,6 +64,16 @@ struct SmallMember { uint32_t in_off, n, out_off, status_off; };   // byte offse
 constexpr size_t SMALL_GROUP_BYTES = (size_t)16 << 20;             // staging of one group (a member larger than that is a group of its own)
 constexpr size_t SMALL_GROUP_MAX = 4096;                           // members of one group
 using SmallTake = std::function<int(size_t i, const uint8_t *p, size_t len)>;
+// what the Huffman decompress batch on device buffers knows of its members before it classifies them (huff_dev.hip: huff_dev_plan): the
+// candidates' summaries as k_huff_dev_plan wrote them and the device table of their plans.  at[i]: member i's entry in both, DEV_PLAN_NONE
+// where the member is no candidate.
+constexpr uint32_t DEV_PLAN_NONE = 0xFFFFFFFFu;
+struct DevPlans {
+    std::vector<uint32_t> at;
+    std::vector<HuffDevSummary> sum;
+    const HuffDevPlan *d_table = nullptr;
+    const HuffDevSummary *of(size_t i) const { return at[i] == DEV_PLAN_NONE ? nullptr : &sum[at[i]]; }
+};
 struct BatchClass {
     const char *name;
     size_t group_min;
@@ -71,8 +82,12 @@ struct BatchClass {
                const SmallTake &take, std::vector<size_t> &back, size_t *failed);
     // the device-buffer form (the batch calls on device buffers; group_run.h: run_groups_dev): the members `idx` of `mem` through the same
     // groups and the same kernel on `s`, the staging in device scratch; answers[k]: GROUP_BACK, or member idx[k]'s length -- its bytes are in
-    // its d_out when that is at most its out_cap.  Null where the class has none (the Huffman rows: their plans are host work on the bytes).
-    int (*run_dev)(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const rsn_dev_member *mem, int64_t window, std::vector<uint32_t> &answers);
+    // its d_out when that is at most its out_cap.  plans: null but for the Huffman decoders, whose table entries are completed on the device
+    // from the plans.
+    int (*run_dev)(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const rsn_dev_member *mem, int64_t window, const DevPlans *plans, std::vector<uint32_t> &answers);
+    // takes() for a member whose bytes lie in device memory, from its length and its plan's summary (a planned one): the same cutoffs.
+    // Null where takes() looks at no byte of the member and serves both forms.
+    bool (*takes_plan)(size_t n, const HuffDevSummary &sum) = nullptr;
 };
 // lzss_small.hip: what lzss_small_compress / _decompress take (1 KiB with a window <= 0xFFFF; 2 KiB of stream).
 // lzss_mid.hip: a workgroup keeps the member's whole escaped stream in LDS.  The encoder takes LZSS_MID_IN_MAX bytes with a window of 1 to
@@ -147,6 +162,11 @@ int arith_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8
 // d_out counts as none).  RSN_ERR_CAPACITY: some member did not fit, *failed the lowest of them, every member has run; any other code:
 // the lowest failing member's, *failed that member (out_lens is then the caller's to clear).  The messages are the single calls'.
 int arith_members_dev(Ctx &c, hipStream_t s, bool enc, size_t n, const rsn_dev_member *mem, size_t *out_lens, size_t *failed);
+
+// the Huffman decompress batch on device buffers (rsn.h; huff_dev.hip): ONE launch of k_huff_dev_plan over the members a grouped
+// decoder could take (8 <= n <= HUFF_HDR_MAX + 8 + HUFF_MID_PAY_MAX), a workgroup each -- the header parsed, the tree built and the stream's
+// bounds computed where the stream lies -- then ONE copy down, 16 bytes a candidate, and the one host wait the classes' slots need.
+int huff_dev_plan(Ctx &c, hipStream_t s, size_t n, const rsn_dev_member *mem, DevPlans &plans);
 
 // exclusive scan of n counts on the stream (huff_encode.hip); *total (may be null) receives the sum; in and out must not overlap
 int scan_u64(Ctx &c, hipStream_t s, const char *name, const unsigned long long *in, unsigned long long *out, uint32_t n, unsigned long long *total);

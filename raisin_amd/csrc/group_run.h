@@ -87,7 +87,7 @@ int class_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins,
         [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) { return K::launch(c, s, g, tab, base, window); }, take, back, failed);
 }
 template <class K>
-int class_run_dev(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const rsn_dev_member *mem, int64_t window, std::vector<uint32_t> &answers) {
+int class_run_dev(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const rsn_dev_member *mem, int64_t window, const DevPlans *, std::vector<uint32_t> &answers) {
     return run_groups_dev(c, s, K::what, idx, mem, K::in_bytes, K::out_bytes,
         [&](hipStream_t s2, uint32_t g, const SmallMember *tab, uint8_t *base) { return K::launch(c, s2, g, tab, base, window); }, answers);
 }

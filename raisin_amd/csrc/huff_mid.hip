@@ -77,6 +77,12 @@ int launch_mid_dec(Ctx &c, hipStream_t s, uint32_t g, const SmallDecArgs *tab) {
 // than huff_batch_dec holds.  The sum is parse_header's scan of the counts without its table: an entry that occurs twice counts twice,
 // and runes are not looked at -- an upper bound that is exact for every header an encoder writes.  The group's own plan
 // (small_dec_plan) is exact and hands back what it refuses.
+constexpr HuffDecShape MID_DEC_SHAPE = {HM_DL, HM_S_MAX, HUFF_MID_PAY_MAX, HUFF_MID_OUT_MAX};
+// the class's cutoffs, stated once for both forms of takes: within what one workgroup holds here, and beyond what k_huff_batch_dec's does
+bool mid_dec_wants(size_t pay, unsigned long long expect) {
+    if (pay > MID_DEC_SHAPE.pay_max || expect > MID_DEC_SHAPE.out_max) return false;
+    return pay > HB_PAY_MAX || expect > HB_OUT_MAX;                    // (the rest is k_huff_batch_dec's)
+}
 bool mid_dec_takes(const uint8_t *in, size_t n, int64_t) {
     if (n < 8 || n > HDR_MAX + 8 + HUFF_MID_PAY_MAX || 8 * n <= HB_OUT_MAX) return false;
     size_t sep = (size_t)-1;
@@ -92,27 +98,36 @@ bool mid_dec_takes(const uint8_t *in, size_t n, int64_t) {
         expect += acc; acc = 0;
         i += (i + 2 < sep && in[i + 1] == 0x5C && in[i + 2] == 'n') ? 2 : 1;      // the entry's byte is not a count's digit
     }
-    if (expect > HUFF_MID_OUT_MAX) return false;
-    return pay > HB_PAY_MAX || expect > HB_OUT_MAX;                    // (the rest is k_huff_batch_dec's)
+    return mid_dec_wants(pay, expect);
+}
+// ... and from the plan's figures, once k_huff_dev_plan has read the header where it lies: the code bits in whole bytes stand for the payload
+// (the same number for every stream whose pad byte is below 8, as an encoder writes it)
+bool mid_dec_takes_plan(size_t n, const HuffDevSummary &sum) {
+    return n >= 8 && n <= HDR_MAX + 8 + HUFF_MID_PAY_MAX && mid_dec_wants((sum.span + 7) / 8, sum.expect) && huff_dec_shape_takes(MID_DEC_SHAPE, sum);
 }
 
 bool mid_enc_takes(const uint8_t *, size_t n, int64_t) { return n > HE_IN_MAX && n <= HUFF_MID_IN_MAX; }   // (asked after the small class)
-int mid_enc_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t,
-                const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return run_member_groups(c, "huffman batch compress", idx, ins, lens, huff_enc_in_slot, huff_mid_enc_out_slot,
-        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
-            const int rc = func_dyn_lds(c, reinterpret_cast<const void *>(k_huff_mid_enc), EL_BYTES); if (rc) return rc;
-            RSN_LAUNCH("huff_batch_mid_enc", k_huff_mid_enc, dim3(g), dim3(HM_T), EL_BYTES, s, tab, base);
-            return RSN_OK;
-        }, take, back, failed);
-}
+struct MidEncClass {
+    static constexpr const char *what = "huffman batch compress";
+    static size_t in_bytes(size_t n) { return huff_enc_in_slot(n); }
+    static size_t out_bytes(size_t n) { return huff_mid_enc_out_slot((uint32_t)n); }
+    static int launch(Ctx &c, hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base, int64_t) {
+        const int rc = func_dyn_lds(c, reinterpret_cast<const void *>(k_huff_mid_enc), EL_BYTES); if (rc) return rc;
+        RSN_LAUNCH("huff_batch_mid_enc", k_huff_mid_enc, dim3(g), dim3(HM_T), EL_BYTES, s, tab, base);
+        return RSN_OK;
+    }
+};
 int mid_dec_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t,
                 const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return huff_dec_run(c, HuffDecShape{HM_DL, HM_S_MAX, HUFF_MID_PAY_MAX, HUFF_MID_OUT_MAX}, launch_mid_dec, idx, ins, lens, take, back, failed);
+    return huff_dec_run(c, MID_DEC_SHAPE, launch_mid_dec, idx, ins, lens, take, back, failed);
+}
+int mid_dec_run_dev(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const rsn_dev_member *mem, int64_t, const DevPlans *plans, std::vector<uint32_t> &answers) {
+    return huff_dec_run_dev(c, s, MID_DEC_SHAPE, launch_mid_dec, idx, mem, *plans, answers);
 }
 }  // namespace
 const BatchClass &huff_mid_class(bool compress) {
-    static const BatchClass enc = {"huffman mid compress", HUFF_MID_GROUP_MIN, mid_enc_takes, mid_enc_run}, dec = {"huffman mid decompress", HUFF_MID_GROUP_MIN, mid_dec_takes, mid_dec_run};
+    static const BatchClass enc = {"huffman mid compress", HUFF_MID_GROUP_MIN, mid_enc_takes, class_run<MidEncClass>, class_run_dev<MidEncClass>},
+                            dec = {"huffman mid decompress", HUFF_MID_GROUP_MIN, mid_dec_takes, mid_dec_run, mid_dec_run_dev, mid_dec_takes_plan};
     return compress ? enc : dec;
 }
 

@@ -342,25 +342,33 @@ int launch_batch_dec(Ctx &c, hipStream_t s, uint32_t g, const SmallDecArgs *tab)
     RSN_LAUNCH("huff_batch_dec", k_huff_batch_dec, dim3(g), dim3(DT), 0, s, tab);
     return RSN_OK;
 }
-bool batch_dec_takes(const uint8_t *, size_t n, int64_t) { return n >= 8 && n <= HDR_MAX + 8 + HB_PAY_MAX; }
+constexpr HuffDecShape BATCH_DEC_SHAPE = {DL, HB_S_MAX, HB_PAY_MAX, HB_OUT_MAX};
+bool batch_dec_takes(const uint8_t *, size_t n, int64_t) { return n >= 8 && n <= HDR_MAX + 8 + BATCH_DEC_SHAPE.pay_max; }
+// (the plan has been made: what huff_dec_run refuses behind it, asked here)
+bool batch_dec_takes_plan(size_t n, const HuffDevSummary &sum) { return batch_dec_takes(nullptr, n, 0) && huff_dec_shape_takes(BATCH_DEC_SHAPE, sum); }
 int batch_dec_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t,
                   const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return huff_dec_run(c, HuffDecShape{DL, HB_S_MAX, HB_PAY_MAX, HB_OUT_MAX}, launch_batch_dec, idx, ins, lens, take, back, failed);
+    return huff_dec_run(c, BATCH_DEC_SHAPE, launch_batch_dec, idx, ins, lens, take, back, failed);
+}
+int batch_dec_run_dev(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const rsn_dev_member *mem, int64_t, const DevPlans *plans, std::vector<uint32_t> &answers) {
+    return huff_dec_run_dev(c, s, BATCH_DEC_SHAPE, launch_batch_dec, idx, mem, *plans, answers);
 }
 bool batch_enc_takes(const uint8_t *, size_t n, int64_t) { return n >= 2 && n <= HE_IN_MAX; }
 // (the kernel hands back runes and a single symbol)
-int batch_enc_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t,
-                  const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
-    return run_member_groups(c, "huffman batch compress", idx, ins, lens, huff_enc_in_slot, huff_small_enc_out_slot,
-        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
-            RSN_LAUNCH("huff_batch_enc", k_huff_batch_enc, dim3(g), dim3(HE_T), 0, s, tab, base);
-            return RSN_OK;
-        }, take, back, failed);
-}
+struct SmallEncClass {
+    static constexpr const char *what = "huffman batch compress";
+    static size_t in_bytes(size_t n) { return huff_enc_in_slot(n); }
+    static size_t out_bytes(size_t n) { return huff_small_enc_out_slot((uint32_t)n); }
+    static int launch(Ctx &c, hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base, int64_t) {
+        RSN_LAUNCH("huff_batch_enc", k_huff_batch_enc, dim3(g), dim3(HE_T), 0, s, tab, base);
+        return RSN_OK;
+    }
+};
 }  // namespace
 // fewer than two members for the grouped encoder: every member takes the pipeline (a group's one serial tree against the host's)
 const BatchClass &huff_small_class(bool compress) {
-    static const BatchClass enc = {"huffman small compress", 2, batch_enc_takes, batch_enc_run}, dec = {"huffman small decompress", 1, batch_dec_takes, batch_dec_run};
+    static const BatchClass enc = {"huffman small compress", 2, batch_enc_takes, class_run<SmallEncClass>, class_run_dev<SmallEncClass>},
+                            dec = {"huffman small decompress", 1, batch_dec_takes, batch_dec_run, batch_dec_run_dev, batch_dec_takes_plan};
     return compress ? enc : dec;
 }
 

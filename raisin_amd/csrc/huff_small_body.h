@@ -40,6 +40,17 @@ struct HuffDecShape {
 using HuffDecLaunch = int (*)(Ctx &c, hipStream_t s, uint32_t members, const SmallDecArgs *tab);
 int huff_dec_run(Ctx &c, const HuffDecShape &shape, HuffDecLaunch launch, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
                  const SmallTake &take, std::vector<size_t> &back, size_t *failed);
+// The same classes on device buffers (huff_dev.hip): the members idx[k] of `mem`, every one with a planned summary that the class's
+// takes_plan has accepted, in run_groups_dev's groups on device staging -- a gather kernel copies each stream from its 4-byte boundary into
+// its input slot and completes its SmallDecArgs from the plan table, the decoder is launched unchanged, and a scatter kernel copies what
+// fits to d_out and turns the decoder's two status words into the answer: GROUP_BACK, or the decoded length.
+int huff_dec_run_dev(Ctx &c, hipStream_t s, const HuffDecShape &shape, HuffDecLaunch launch, const std::vector<size_t> &idx, const rsn_dev_member *mem,
+                     const DevPlans &plans, std::vector<uint32_t> &answers);
+// what a decoding class asks of a planned stream beside its own cutoffs: its lanes hold the code bits
+inline bool huff_dec_shape_takes(const HuffDecShape &shape, const HuffDevSummary &sum) {
+    uint32_t S, T;
+    return sum.expect <= shape.out_max && (sum.span + 7) / 8 <= shape.pay_max && parse_lanes(sum.span, shape.lanes, shape.s_max, &S, &T);
+}
 
 namespace {
 

@@ -1085,16 +1085,21 @@ static void deal_items(Ctx &c, size_t n_items, Work work, std::vector<int> &rcs,
 
 // The members of a batch by class: per[r] = the members rows' r-th class takes and no earlier one does, in index order; a class with fewer
 // members than its group_min is not grouped.  Those, and what no class takes, go to `rest` (not sorted).
-static void classify(BatchRows rows, size_t n, const uint8_t *const *ins, const size_t *lens, int64_t window,
-                     std::vector<std::vector<size_t>> &per, std::vector<size_t> &rest) {
+// takes(row, i): whether the class takes member i -- the host form asks the bytes, the device form the plan's summary
+template <class Takes>
+static void classify_by(BatchRows rows, size_t n, Takes takes, std::vector<std::vector<size_t>> &per, std::vector<size_t> &rest) {
     per.assign(rows.n, {});
     for (size_t i = 0; i < n; i++) {
         size_t r = 0;
-        while (r < rows.n && !rows.first[r]->takes(ins[i], lens[i], window)) r++;
+        while (r < rows.n && !takes(*rows.first[r], i)) r++;
         (r < rows.n ? per[r] : rest).push_back(i);
     }
     for (size_t r = 0; r < rows.n; r++)
         if (per[r].size() < rows.first[r]->group_min) { rest.insert(rest.end(), per[r].begin(), per[r].end()); per[r].clear(); }
+}
+static void classify(BatchRows rows, size_t n, const uint8_t *const *ins, const size_t *lens, int64_t window,
+                     std::vector<std::vector<size_t>> &per, std::vector<size_t> &rest) {
+    classify_by(rows, n, [&](const BatchClass &k, size_t i) { return k.takes(ins[i], lens[i], window); }, per, rest);
 }
 
 static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
@@ -1303,41 +1308,57 @@ static int batch_dev_answer(Ctx &c, int rc, size_t failed, size_t n, size_t *out
     return c.fail(rc, "member %zu: %s", failed, m.c_str());
 }
 
-// LZSS: the members by class as in the host form (classify: the same rows, the same takes(), the same minimums), each class through its
-// device-form runner; what no class takes, what a class below its minimum holds and what a kernel hands back run the single call's codec
-// on the same stream, in index order, straight into the member's buffer.  No worker threads: one stream, device buffers.
-static int lzss_batch_dev(bool enc, size_t n, const rsn_dev_member *mem, int64_t window, size_t *out_lens, void *stream) {
+// LZSS and Huffman: the members by class as in the host form (classify_by: the same rows, the same cutoffs, the same minimums), each class
+// through its device-form runner; what no class takes, what a class below its minimum holds and what a kernel hands back run the single
+// call's codec (the layer's row of codec()) on the same stream, in index order, straight into the member's buffer.  No worker threads: one
+// stream, device buffers.  A class that states takes_plan is asked through it with the member's planned summary -- the Huffman decoders,
+// whose members' headers k_huff_dev_plan has read where they lie (huff_dev.hip); a member without one is not theirs.  slack: what the single
+// call adds to a size rounded up to 16 when it reports a capacity (rsn.h), which a grouped member that did not fit reports too.
+struct BatchDevLayer { BatchLayer rows; int codec_id; const char *word; size_t slack; const char *empty_member; };
+static int layer_batch_dev(const BatchDevLayer &layer, bool enc, size_t n, const rsn_dev_member *mem, int64_t window, size_t *out_lens, void *stream) {
     Ctx &c = ctx(); hipStream_t s;
-    int rc = batch_dev_args(c, n, mem, out_lens, "lzss"); if (rc || n == 0) return rc;
+    int rc = batch_dev_args(c, n, mem, out_lens, layer.word); if (rc || n == 0) return rc;
+    if (enc && layer.empty_member)
+        for (size_t i = 0; i < n; i++) if (mem[i].n == 0) return c.fail(RSN_ERR_EMPTY, "member %zu: %s", i, layer.empty_member);
     rc = dev_prologue(c, stream, &s); if (rc) return rc;
     constexpr size_t NONE = (size_t)-1;
-    const BatchRows rows = batch_classes(BatchLayer::LZSS, enc);
-    std::vector<const uint8_t *> ins(n);
-    std::vector<size_t> lens(n);
-    for (size_t i = 0; i < n; i++) { ins[i] = (const uint8_t *)mem[i].d_in; lens[i] = mem[i].n; }   // (takes() looks at no byte of an LZSS member)
+    const BatchRows rows = batch_classes(layer.rows, enc);
+    const Codec &single = codec(layer.codec_id, enc);
+    bool planned = false;
+    for (size_t r = 0; r < rows.n; r++) planned = planned || rows.first[r]->takes_plan;
+    DevPlans plans;
+    Admission plan_gate(c, slotset::HUFF_DEV_PLANS);                      // (the plan table is the call's: no class's gate gives it back)
+    if (planned) {
+        plan_gate.admit(n * sizeof(HuffDevPlan), ADMIT_FROM);
+        rc = huff_dev_plan(c, s, n, mem, plans);
+        if (rc) return batch_dev_answer(c, rc, 0, n, out_lens);
+    }
     std::vector<std::vector<size_t>> per;
     std::vector<size_t> rest;
-    classify(rows, n, ins.data(), lens.data(), window, per, rest);
+    classify_by(rows, n, [&](const BatchClass &k, size_t i) {
+        if (!k.takes_plan) return k.takes((const uint8_t *)mem[i].d_in, mem[i].n, window);   // (such a takes() looks at no byte of the member)
+        const HuffDevSummary *v = plans.of(i);
+        return v && v->verdict == PARSE_PLANNED && k.takes_plan(mem[i].n, *v);
+    }, per, rest);
     size_t tight = NONE; std::string tight_msg;                           // the lowest member that did not fit, and what the single call says of it
     auto cap_of = [&](size_t i) { return mem[i].d_out ? mem[i].out_cap : (size_t)0; };
     std::vector<uint32_t> answers;
     for (size_t r = 0; r < rows.n; r++) {
         if (per[r].empty()) continue;
-        rc = rows.first[r]->run_dev(c, s, per[r], mem, window, answers);
+        rc = rows.first[r]->run_dev(c, s, per[r], mem, window, planned ? &plans : nullptr, answers);
         if (rc) return batch_dev_answer(c, rc, per[r][0], n, out_lens);   // (a device failure: nothing more is launched)
         for (size_t k = 0; k < per[r].size(); k++) {
             const size_t i = per[r][k], got = answers[k];
             if (answers[k] == GROUP_BACK) { rest.push_back(i); continue; }
             if (got <= cap_of(i)) { out_lens[i] = got; continue; }
-            out_lens[i] = round_up(got, 16) + 16;                         // (as lzss_encode_dev / lzss_decode_dev report it)
-            if (i < tight) { tight = i; c.fail(RSN_ERR_CAPACITY, "lzss: output needs %zu bytes, buffer holds %zu", got, cap_of(i)); tight_msg = c.err; }
+            out_lens[i] = round_up(got, 16) + layer.slack;                // (as the single call reports it)
+            if (i < tight) { tight = i; c.fail(RSN_ERR_CAPACITY, "%s: output needs %zu bytes, buffer holds %zu", layer.word, got, cap_of(i)); tight_msg = c.err; }
         }
     }
     std::sort(rest.begin(), rest.end());
     for (size_t i : rest) {
         size_t got = 0;
-        rc = enc ? lzss_encode_dev(c, s, ins[i], lens[i], window, (uint8_t *)mem[i].d_out, cap_of(i), &got)
-                 : lzss_decode_dev(c, s, ins[i], lens[i], (uint8_t *)mem[i].d_out, cap_of(i), &got);
+        rc = single.dev(c, s, (const uint8_t *)mem[i].d_in, mem[i].n, window, (uint8_t *)mem[i].d_out, cap_of(i), &got);
         if (rc != RSN_OK && rc != RSN_ERR_CAPACITY) return batch_dev_answer(c, rc, i, n, out_lens);
         out_lens[i] = got;
         if (rc == RSN_ERR_CAPACITY && i < tight) { tight = i; tight_msg = c.err; }
@@ -1346,6 +1367,12 @@ static int lzss_batch_dev(bool enc, size_t n, const rsn_dev_member *mem, int64_t
     if (tight == NONE) return RSN_OK;
     c.err = tight_msg;
     return batch_dev_answer(c, RSN_ERR_CAPACITY, tight, n, out_lens);
+}
+static int lzss_batch_dev(bool enc, size_t n, const rsn_dev_member *mem, int64_t window, size_t *out_lens, void *stream) {
+    return layer_batch_dev(BatchDevLayer{BatchLayer::LZSS, RSN_LAYER_LZSS, "lzss", 16, nullptr}, enc, n, mem, window, out_lens, stream);
+}
+static int huffman_batch_dev(bool enc, size_t n, const rsn_dev_member *mem, size_t *out_lens, void *stream) {
+    return layer_batch_dev(BatchDevLayer{BatchLayer::HUFFMAN, RSN_LAYER_HUFFMAN, "huffman", enc ? (size_t)32 : (size_t)16, HUFF_EMPTY}, enc, n, mem, 0, out_lens, stream);
 }
 
 static int arithmetic_batch_dev(bool enc, size_t n, const rsn_dev_member *mem, size_t *out_lens, void *stream) {
@@ -1817,6 +1844,8 @@ int rsn_arithmetic_compress_dev(const void *d_in, size_t n, void *d_out, size_t 
 int rsn_arithmetic_decompress_dev(const void *d_in, size_t n, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded([&] { return arithmetic_dev(false, d_in, n, d_out, out_cap, out_n, stream); }); }
 int rsn_lzss_compress_batch_dev(size_t n, const rsn_dev_member *members, int64_t window, size_t *out_lens, void *stream) { return guarded_lens(n, members, out_lens, [&] { return lzss_batch_dev(true, n, members, window, out_lens, stream); }); }
 int rsn_lzss_decompress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream) { return guarded_lens(n, members, out_lens, [&] { return lzss_batch_dev(false, n, members, 0, out_lens, stream); }); }
+int rsn_huffman_compress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream) { return guarded_lens(n, members, out_lens, [&] { return huffman_batch_dev(true, n, members, out_lens, stream); }); }
+int rsn_huffman_decompress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream) { return guarded_lens(n, members, out_lens, [&] { return huffman_batch_dev(false, n, members, out_lens, stream); }); }
 int rsn_arithmetic_compress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream) { return guarded_lens(n, members, out_lens, [&] { return arithmetic_batch_dev(true, n, members, out_lens, stream); }); }
 int rsn_arithmetic_decompress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream) { return guarded_lens(n, members, out_lens, [&] { return arithmetic_batch_dev(false, n, members, out_lens, stream); }); }
 int rsn_huffman_compress_sharded(const uint8_t *in, size_t n, int shards, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return rsn_huffman_compress_sharded_impl(in, n, shards, out, out_n); }); }

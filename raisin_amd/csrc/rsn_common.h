@@ -80,6 +80,8 @@ enum class Slot : int {
                         //   the decoder's descriptors (the batch call on device buffers: both directions' descriptors in front) [arith]
     GD_STAGE = 45,      // batch calls on device buffers (group_dev.hip): a group's staging -- the member and gather tables, then the members' slots [group_dev]
     GD_LENS = 46,       // batch calls on device buffers: a class's answers, a word per member [group_dev]
+    GD_PLANS = 47,      // Huffman decompress batch on device buffers (huff_dev.hip): the candidates' plans (a HuffDevPlan each), then their table entries
+                        //   and their summaries -- written by k_huff_dev_plan, read by every class's groups until the call ends [huff_dev]
 };
 constexpr int RING = 3;                                                  // the batch pipeline's depth: RING inputs, RING segments
 constexpr Slot ring_in(int r) { return (Slot)((int)Slot::RING_IN0 + r); }
@@ -105,12 +107,14 @@ constexpr unsigned long long LAYERED_CALL = HOST_CALL | LAYERED;
 constexpr unsigned long long ARITH = slot_mask(S::AR_STATE, S::AR_RAW);   // the arithmetic codec's own: what its device-buffer calls' gate gives back
 constexpr unsigned long long ARITH_HOST = STAGING | ARITH;                // ... and its host-buffer calls', which stage through the staging pair
 constexpr unsigned long long GROUP_DEV = slot_mask(S::GD_STAGE, S::GD_LENS);   // the grouped kernels' staging on the device: what a class's run of the batch calls on device buffers gives back
+constexpr unsigned long long HUFF_DEV_PLANS = slot_mask(S::GD_PLANS);          // the plan table outlives the classes' runs: the call's own gate gives it back, never a class's
 // (RING is written out three times: the enumerators, RINGS and this check change together)
 static_assert(ring_in(RING) == Slot::RING_OUT0 && ring_out(RING - 1) == Slot::RING_OUT2, "the ring's slots are RING inputs, then RING segments");
 static_assert(((STAGING | RINGS | LAYERED) & (LZSS_ENC | LZSS_DEC)) == 0, "a codec's gate releases no staging, ring or layered slot: their callers still use them");
 static_assert(((STAGING | LAYERED) & (HUFF_OWN | LZSS_ENC_OWN | LZSS_DEC_OWN)) == 0, "no codec allocates a staging or a layered slot");
 static_assert((LZSS_DEC & ~LZSS_ENC) == 0, "HOST_CALL covers both LZSS directions");
 static_assert((GROUP_DEV & (HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED | ARITH)) == 0, "the device staging is released by its own gate only: the single calls that follow a class never hold it");
+static_assert((HUFF_DEV_PLANS & (GROUP_DEV | HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED | ARITH)) == 0, "no class run and no single call gives the plan table back while the call still reads it");
 static_assert((ARITH & (HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED)) == 0, "the arithmetic codec shares no slot of its own with another codec or a caller");
 }  // namespace slotset
 
@@ -127,7 +131,7 @@ struct Ctx {
     std::vector<hipEvent_t> free_events;
 
     struct Buf { void *p = nullptr; size_t cap = 0; unsigned long long gen = 0; };   // gen: process-unique number of this allocation (dev_buf) -- an address can come back with other contents
-    enum { N_BUFS = (int)Slot::GD_LENS + 1 };   // (the table above)
+    enum { N_BUFS = (int)Slot::GD_PLANS + 1 };   // (the table above)
     Buf bufs[N_BUFS];
     Buf &buf(Slot k) { return bufs[(int)k]; }
     void *pinned = nullptr; size_t pinned_cap = 0;

@@ -155,3 +155,17 @@ def decompress_tensor(src, out=None, stream=None):
     """below 1 MiB of stream a generous guess costs less than a second call; from there the size query first"""
     n = src.numel()
     return _lib.dev_tensor(_lib.lib().rsn_huffman_decompress_dev, src, out, stream, 8 * n + (1 << 16) if n < (1 << 20) else None)
+
+
+def compress_tensors(srcs, outs=None, stream=None):
+    """compress_tensor for a list of 1-D uint8 CUDA tensors in ONE call (rsn_huffman_compress_batch_dev): the members of CompressBatch's
+    classes run grouped on the device, the others the single call's codec; nothing of a member crosses to the host.  -> a list of
+    tensors; without `outs`, views of one allocation of compress_bound(n) bytes a member.  An empty member raises, as Compress does."""
+    return _lib.dev_tensors(_lib.lib().rsn_huffman_compress_batch_dev, srcs, outs, stream, compress_bound, retry=False)
+
+
+def decompress_tensors(srcs, outs=None, stream=None):
+    """decompress_tensor for a list of streams in ONE call (rsn_huffman_decompress_batch_dev): the headers are read on the device.  Without
+    `outs`: a guess of eight times the stream plus 4 KiB a member (a two-symbol stream expands eightfold at most per payload byte); the
+    members it does not hold are run once more."""
+    return _lib.dev_tensors(_lib.lib().rsn_huffman_decompress_batch_dev, srcs, outs, stream, lambda n: 8 * n + 4096)

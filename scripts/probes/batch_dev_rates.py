@@ -4,7 +4,9 @@
     (b) the host-buffer batch call            the same members starting from, and ending in, host memory
     (c) the batch call on device buffers      rsn_*_batch_dev
 
-    python scripts/probes/batch_dev_rates.py [out_file]          (default profiles/batch_dev_rates.txt)
+    python scripts/probes/batch_dev_rates.py [out_file [codec ...]]     (default profiles/batch_dev_rates.txt, every codec)
+
+With codecs named (lzss, arithmetic, huffman) only their rows are run, and they are APPENDED to the file under a heading of their own.
 
 Host wall clock around calls that synchronise before they return; every leg is warmed up once, then the median of five runs, with the
 five runs' least and greatest beside it.  All three legs go through ctypes with their argument arrays built beforehand, so what is
@@ -21,7 +23,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 
-from raisin_amd import _lib, arithmetic as A, lz  # noqa: E402
+from raisin_amd import _lib, arithmetic as A, huffman as H, lz  # noqa: E402
 
 U8P = ctypes.POINTER(ctypes.c_uint8)
 VOCAB = None
@@ -134,10 +136,20 @@ def main():
     say()
     say("%-11s %-14s %-10s %26s %26s %26s %7s %7s  %s" % ("codec", "members", "direction", "(a) ms", "(b) ms", "(c) ms", "a/c", "b/c", "c < a - spread(a)"))
     ok = True
-    shapes = [("lzss", 4096, 25), ("lzss", 4096, 1024), ("lzss", 256, 16 << 10), ("lzss", 256, 64 << 10), ("arithmetic", 4096, 25), ("arithmetic", 4096, 1024)]
+    shapes = [("lzss", 4096, 25), ("lzss", 4096, 1024), ("lzss", 256, 16 << 10), ("lzss", 256, 64 << 10), ("arithmetic", 4096, 25), ("arithmetic", 4096, 1024),
+              ("huffman", 4096, 25), ("huffman", 4096, 1024), ("huffman", 256, 16 << 10), ("huffman", 256, 64 << 10)]
+    only = sys.argv[2:]
     for codec, count, size in shapes:
+        if only and codec not in only:
+            continue
         datas = [text(size, 1000 * size + i) for i in range(count)]
-        if codec == "lzss":
+        if codec == "huffman":
+            streams = H.CompressBatch(datas)
+            assert H.DecompressBatch(streams) == datas
+            bound = L.rsn_huffman_compress_bound
+            rows = (("compress", L.rsn_huffman_compress_dev, L.rsn_huffman_compress_batch, L.rsn_huffman_compress_batch_dev, (), datas, streams),
+                    ("decompress", L.rsn_huffman_decompress_dev, L.rsn_huffman_decompress_batch, L.rsn_huffman_decompress_batch_dev, (), streams, datas))
+        elif codec == "lzss":
             streams = lz.CompressAsyncBatch(datas, 4096)
             assert lz.DecompressBatch(streams) == datas
             bound = L.rsn_lzss_compress_bound
@@ -161,8 +173,8 @@ def main():
     say()
     say("the condition (4096-member shapes): %s" % ("holds at every shape" if ok else "DOES NOT HOLD at a shape above"))
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
-    with open(out_path, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    with open(out_path, "a" if only else "w") as f:
+        f.write(("\n" if only else "") + "\n".join(lines) + "\n")
     return 0 if ok else 1
 
 
