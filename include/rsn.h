@@ -286,6 +286,39 @@ RSN_API int rsn_lzss_decompress_batch_dev(size_t n, const rsn_dev_member *member
 RSN_API int rsn_arithmetic_compress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream);
 RSN_API int rsn_arithmetic_decompress_batch_dev(size_t n, const rsn_dev_member *members, size_t *out_lens, void *stream);
 
+/* ---- layered batch calls -------------------------------------------------
+ * The engine's whole unit of work: a LIST of layers over MANY members (engine.CompressFiles / DecompressFiles; the CLI's default is
+ * lzss,huffman), in one call.  Member i's result is byte for byte what rsn_layers_compress(ins[i], ...) / rsn_layers_compress_dev returns
+ * for the same layer list -- the chain of the single calls at RSN_LZSS_DEFAULT_WINDOW, the Huffman codec's lossy treatment of bytes that
+ * are not UTF-8 included; decompress undoes the layers last to first.  `layers` is in compress order, holds RSN_LAYER_LZSS /
+ * RSN_LAYER_HUFFMAN only and at most RSN_LAYERS_MAX entries.  The layers run LAYER-MAJOR: every member through one layer -- the batch
+ * calls' grouped kernels, thousands of small members to a launch -- before the next, and between the layers every member stays on the
+ * device, in slots of the calling thread's scratch.  Members are taken in runs of consecutive members whose slots fit a
+ * budget (1 GiB; RSN_LAYERS_BATCH_BUDGET=<bytes>, read at every call); a member above the budget is a run of its own.
+ * Arguments, all checked before a device is looked for (RSN_ERR_ARG): n == 0 returns RSN_OK before anything else is looked at; then the
+ * arrays and members as in the neighbouring batch calls -- host form: null arrays, a null ins[i] of non-zero length; device form: null
+ * arrays, a null d_in with n > 0, alignment, a null d_out with an out_cap, the overlap rule over the CALLER's ranges; then the layer list as
+ * in rsn_layers_compress.  Without a device: RSN_ERR_DEVICE.
+ * Failures: the first layer, in run order, at which some member fails with a code other than RSN_ERR_CAPACITY ends the call with that
+ * layer's lowest failing member's code; rsn_last_error() reads "member <i>: layer <k> (<name>): " followed by the single call's message, k
+ * counting in compress order; every outs[i] is then NULL and every out_lens[i] 0.  [lzss, huffman] with an empty member fails as
+ * "member <i>: layer 1 (huffman): ..." with RSN_ERR_EMPTY; a list without Huffman takes empty members, and their result is empty.
+ * Host form: runs on the calling thread's device; a run's inputs go up in ONE copy, its results are packed on the device and come down
+ * in ONE copy; each outs[i] is released with rsn_free.
+ * Device form: under the contract of the batch calls on device buffers above; intermediates never cross to the host.  Only the last step
+ * writes caller memory, and its contract holds: a size query per member (d_out NULL with out_cap 0); on RSN_ERR_CAPACITY -- the message
+ * names the lowest member that did not fit -- every member has been processed, out_lens[i] <= out_cap marks a member that fits, complete
+ * and exact, out_lens[i] > out_cap one that did not, the value being a capacity that suffices on a second call (the last step's figure:
+ * the exact size rounded up to 16, plus 16 -- plus 32 behind a last Huffman compress layer); the smallest out_cap taken is the last
+ * step's own (the exact size; a member the last Huffman compress layer runs through the single call: rounded up to 16, plus 32).
+ * Nothing is ever written outside [d_out, d_out + out_cap).  n_layers == 1 IS the codec's batch call on device buffers at window
+ * RSN_LZSS_DEFAULT_WINDOW -- the same launches -- with the layer named in the message.  n_layers == 0 copies each member; a member that
+ * does not fit reports its size rounded up to 16, plus 16.  The stream is synchronised before the call returns. */
+RSN_API int rsn_layers_compress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, const int *layers, size_t n_layers, uint8_t **outs, size_t *out_lens);
+RSN_API int rsn_layers_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, const int *layers, size_t n_layers, uint8_t **outs, size_t *out_lens);
+RSN_API int rsn_layers_compress_batch_dev(size_t n, const rsn_dev_member *members, const int *layers, size_t n_layers, size_t *out_lens, void *stream);
+RSN_API int rsn_layers_decompress_batch_dev(size_t n, const rsn_dev_member *members, const int *layers, size_t n_layers, size_t *out_lens, void *stream);
+
 /* ---- measurement --------------------------------------------------------
  * When enabled, every kernel launch of the calling thread is bracketed by HIP
  * events on the launch stream; rsn_prof_get() reports per-kernel totals since

@@ -60,6 +60,7 @@ SYMBOLS = [
     "rsn_arithmetic_compress_batch", "rsn_arithmetic_decompress_batch", "rsn_arithmetic_compress_dev", "rsn_arithmetic_decompress_dev",
     "rsn_lzss_compress_batch_dev", "rsn_lzss_decompress_batch_dev", "rsn_arithmetic_compress_batch_dev", "rsn_arithmetic_decompress_batch_dev",
     "rsn_huffman_compress_batch_dev", "rsn_huffman_decompress_batch_dev",
+    "rsn_layers_compress_batch", "rsn_layers_decompress_batch", "rsn_layers_compress_batch_dev", "rsn_layers_decompress_batch_dev",
 ]
 
 
@@ -135,6 +136,10 @@ def lib():
         getattr(L, name).argtypes = [ctypes.c_char_p, sz, ip, sz, ctypes.POINTER(u8p), szp]
     for name in ("rsn_layers_compress_dev", "rsn_layers_decompress_dev"):
         getattr(L, name).argtypes = [vp, sz, ip, sz, vp, sz, szp, vp]
+    for name in ("rsn_layers_compress_batch", "rsn_layers_decompress_batch"):
+        getattr(L, name).argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ip, sz, ctypes.POINTER(u8p), szp]
+    for name in ("rsn_layers_compress_batch_dev", "rsn_layers_decompress_batch_dev"):
+        getattr(L, name).argtypes = [sz, mp, ip, sz, szp, vp]
     L.rsn_layers_roundtrip.argtypes = [ctypes.c_char_p, sz, ip, sz, ctypes.POINTER(RoundTripResult), ctypes.POINTER(u8p), szp]
     L.rsn_prof_copied.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.rsn_prof_copied.restype = None

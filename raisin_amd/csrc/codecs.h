@@ -168,6 +168,12 @@ int arith_members_dev(Ctx &c, hipStream_t s, bool enc, size_t n, const rsn_dev_m
 // bounds computed where the stream lies -- then ONE copy down, 16 bytes a candidate, and the one host wait the classes' slots need.
 int huff_dev_plan(Ctx &c, hipStream_t s, size_t n, const rsn_dev_member *mem, DevPlans &plans);
 
+// the layered batch calls' mover (rsn.h; layers_batch.hip): `tiles` entries of at most LB_TILE bytes each (layers_batch_layout.h),
+// src and dst 16-byte aligned device pointers -- h_tab (pinned) goes up to d_tab in one copy and ONE launch of k_members_move, a workgroup
+// an entry, moves them.  Only queues work on `s`: h_tab is the caller's until the stream has been synchronised.
+struct MoveEntry { const uint8_t *src; uint8_t *dst; unsigned long long len; };
+int members_move(Ctx &c, hipStream_t s, const MoveEntry *h_tab, MoveEntry *d_tab, size_t tiles);
+
 // exclusive scan of n counts on the stream (huff_encode.hip); *total (may be null) receives the sum; in and out must not overlap
 int scan_u64(Ctx &c, hipStream_t s, const char *name, const unsigned long long *in, unsigned long long *out, uint32_t n, unsigned long long *total);
 

@@ -3,6 +3,7 @@
 // device-resident codecs; there is no CPU compute path.
 #include "codecs.h"
 #include "dev_ranges.h"
+#include "layers_batch_layout.h"
 #include "group_layout.h"
 #include "rsn_common.h"
 #include "rsn_helpers.h"
@@ -1315,13 +1316,27 @@ static int batch_dev_answer(Ctx &c, int rc, size_t failed, size_t n, size_t *out
 // whose members' headers k_huff_dev_plan has read where they lie (huff_dev.hip); a member without one is not theirs.  slack: what the single
 // call adds to a size rounded up to 16 when it reports a capacity (rsn.h), which a grouped member that did not fit reports too.
 struct BatchDevLayer { BatchLayer rows; int codec_id; const char *word; size_t slack; const char *empty_member; };
-static int layer_batch_dev(const BatchDevLayer &layer, bool enc, size_t n, const rsn_dev_member *mem, int64_t window, size_t *out_lens, void *stream) {
-    Ctx &c = ctx(); hipStream_t s;
-    int rc = batch_dev_args(c, n, mem, out_lens, layer.word); if (rc || n == 0) return rc;
+static const BatchDevLayer &batch_dev_layer(int id, bool enc) {
+    static const BatchDevLayer rows[2][2] = {
+        {{BatchLayer::LZSS, RSN_LAYER_LZSS, "lzss", 16, nullptr}, {BatchLayer::LZSS, RSN_LAYER_LZSS, "lzss", 16, nullptr}},
+        {{BatchLayer::HUFFMAN, RSN_LAYER_HUFFMAN, "huffman", 16, HUFF_EMPTY}, {BatchLayer::HUFFMAN, RSN_LAYER_HUFFMAN, "huffman", 32, HUFF_EMPTY}},
+    };
+    return rows[id == RSN_LAYER_HUFFMAN][enc];
+}
+// a member the layer does not take empty (Huffman compress, as the single call): RSN_ERR_EMPTY, the single call's message, *failed the lowest
+static int layer_empty_member(Ctx &c, const BatchDevLayer &layer, bool enc, size_t n, const rsn_dev_member *mem, size_t *failed) {
     if (enc && layer.empty_member)
-        for (size_t i = 0; i < n; i++) if (mem[i].n == 0) return c.fail(RSN_ERR_EMPTY, "member %zu: %s", i, layer.empty_member);
-    rc = dev_prologue(c, stream, &s); if (rc) return rc;
+        for (size_t i = 0; i < n; i++) if (mem[i].n == 0) { *failed = i; return c.fail(RSN_ERR_EMPTY, "%s", layer.empty_member); }
+    return RSN_OK;
+}
+// The flow on a table whose arguments are known to be good -- the caller's after batch_dev_args, or one the layered batch calls built over
+// their arenas -- on a stream that is there.  Returns the code with the single call's message in c.err and the member it is
+// about in *failed -- (size_t)-1 where it is about none: the stream's own failure; a failure other than RSN_ERR_CAPACITY clears out_lens.
+static int layer_batch_run(Ctx &c, hipStream_t s, const BatchDevLayer &layer, bool enc, size_t n, const rsn_dev_member *mem, int64_t window, size_t *out_lens, size_t *failed) {
     constexpr size_t NONE = (size_t)-1;
+    auto fails = [&](int rc, size_t i) { *failed = i; if (rc != RSN_ERR_CAPACITY) for (size_t k = 0; k < n; k++) out_lens[k] = 0; return rc; };
+    int rc;
+    *failed = NONE;
     const BatchRows rows = batch_classes(layer.rows, enc);
     const Codec &single = codec(layer.codec_id, enc);
     bool planned = false;
@@ -1331,7 +1346,7 @@ static int layer_batch_dev(const BatchDevLayer &layer, bool enc, size_t n, const
     if (planned) {
         plan_gate.admit(n * sizeof(HuffDevPlan), ADMIT_FROM);
         rc = huff_dev_plan(c, s, n, mem, plans);
-        if (rc) return batch_dev_answer(c, rc, 0, n, out_lens);
+        if (rc) return fails(rc, 0);
     }
     std::vector<std::vector<size_t>> per;
     std::vector<size_t> rest;
@@ -1346,7 +1361,7 @@ static int layer_batch_dev(const BatchDevLayer &layer, bool enc, size_t n, const
     for (size_t r = 0; r < rows.n; r++) {
         if (per[r].empty()) continue;
         rc = rows.first[r]->run_dev(c, s, per[r], mem, window, planned ? &plans : nullptr, answers);
-        if (rc) return batch_dev_answer(c, rc, per[r][0], n, out_lens);   // (a device failure: nothing more is launched)
+        if (rc) return fails(rc, per[r][0]);                              // (a device failure: nothing more is launched)
         for (size_t k = 0; k < per[r].size(); k++) {
             const size_t i = per[r][k], got = answers[k];
             if (answers[k] == GROUP_BACK) { rest.push_back(i); continue; }
@@ -1359,20 +1374,30 @@ static int layer_batch_dev(const BatchDevLayer &layer, bool enc, size_t n, const
     for (size_t i : rest) {
         size_t got = 0;
         rc = single.dev(c, s, (const uint8_t *)mem[i].d_in, mem[i].n, window, (uint8_t *)mem[i].d_out, cap_of(i), &got);
-        if (rc != RSN_OK && rc != RSN_ERR_CAPACITY) return batch_dev_answer(c, rc, i, n, out_lens);
+        if (rc != RSN_OK && rc != RSN_ERR_CAPACITY) return fails(rc, i);
         out_lens[i] = got;
         if (rc == RSN_ERR_CAPACITY && i < tight) { tight = i; tight_msg = c.err; }
     }
     RSN_HIP(hipStreamSynchronize(s));
     if (tight == NONE) return RSN_OK;
     c.err = tight_msg;
-    return batch_dev_answer(c, RSN_ERR_CAPACITY, tight, n, out_lens);
+    return fails(RSN_ERR_CAPACITY, tight);
+}
+// the call on the caller's table: the argument checks and an empty member's answer before a device is looked for, then the flow
+static int layer_batch_dev(const BatchDevLayer &layer, bool enc, size_t n, const rsn_dev_member *mem, int64_t window, size_t *out_lens, void *stream) {
+    Ctx &c = ctx(); hipStream_t s;
+    size_t failed = 0;
+    int rc = batch_dev_args(c, n, mem, out_lens, layer.word); if (rc || n == 0) return rc;
+    rc = layer_empty_member(c, layer, enc, n, mem, &failed); if (rc) return batch_dev_answer(c, rc, failed, n, out_lens);
+    rc = dev_prologue(c, stream, &s); if (rc) return rc;
+    rc = layer_batch_run(c, s, layer, enc, n, mem, window, out_lens, &failed);
+    return failed == (size_t)-1 ? rc : batch_dev_answer(c, rc, failed, n, out_lens);
 }
 static int lzss_batch_dev(bool enc, size_t n, const rsn_dev_member *mem, int64_t window, size_t *out_lens, void *stream) {
-    return layer_batch_dev(BatchDevLayer{BatchLayer::LZSS, RSN_LAYER_LZSS, "lzss", 16, nullptr}, enc, n, mem, window, out_lens, stream);
+    return layer_batch_dev(batch_dev_layer(RSN_LAYER_LZSS, enc), enc, n, mem, window, out_lens, stream);
 }
 static int huffman_batch_dev(bool enc, size_t n, const rsn_dev_member *mem, size_t *out_lens, void *stream) {
-    return layer_batch_dev(BatchDevLayer{BatchLayer::HUFFMAN, RSN_LAYER_HUFFMAN, "huffman", enc ? (size_t)32 : (size_t)16, HUFF_EMPTY}, enc, n, mem, 0, out_lens, stream);
+    return layer_batch_dev(batch_dev_layer(RSN_LAYER_HUFFMAN, enc), enc, n, mem, 0, out_lens, stream);
 }
 
 static int arithmetic_batch_dev(bool enc, size_t n, const rsn_dev_member *mem, size_t *out_lens, void *stream) {
@@ -1657,6 +1682,217 @@ static int layers_dev(bool enc, const void *d_in, size_t n, const int *layers, s
     return RSN_OK;
 }
 
+// ---- layered batch calls (rsn.h): many members through a list of layers, layer-major, every member on the device from the
+// first step to the last.  The members are cut into runs (layers_batch_layout.h); a run's step k is layer_batch_run over a member table
+// built here: d_in where step k - 1 left the member, d_out a slot of the arena whose turn it is (LB_A / LB_B) -- or, behind the last step
+// of the device form, the caller's buffer.  A slot holds the codec's bound (compress) or the single chain's first guess (decompress); the
+// members that report more are run again alone, with the reported figures, into LB_XA / LB_XB, the others being complete.
+namespace {
+constexpr size_t LB_NONE = (size_t)-1;
+size_t layers_batch_budget() {                                            // (read at every call: a test cuts runs at small sizes)
+    const char *e = getenv("RSN_LAYERS_BATCH_BUDGET");
+    return e && atoll(e) > 0 ? (size_t)atoll(e) : LB_BUDGET;
+}
+size_t layer_slot_cap(int id, bool enc, size_t n) {
+    if (!enc) return codec(id, false).cap(n);
+    return id == RSN_LAYER_HUFFMAN ? huff_compress_bound(n) : lzss_compress_bound(n);
+}
+// the largest slot a member of n bytes is expected to take over the chain, for the run cuts: compress bounds applied in turn are exact
+// upper bounds; a decompress step's result is taken as layers_need takes it
+size_t layers_batch_slot(bool enc, const int *layers, size_t n_layers, size_t n) {
+    size_t most = 0, cur = n;
+    for (size_t k = 0; k < n_layers; k++) {
+        const size_t cap = layer_slot_cap(layers[enc ? k : n_layers - 1 - k], enc, cur);
+        most = std::max(most, cap);
+        cur = enc ? cap : std::min(cap, 2 * cur);
+    }
+    return most;
+}
+// what ended a call: the step (in run order) and the member (the call's numbering) of a failure other than RSN_ERR_CAPACITY
+struct LbFailure { size_t step = LB_NONE, member = 0; int rc = RSN_OK; std::string msg; };
+// where a run's members are and how long, step by step; tight: the lowest member that did not fit the caller's buffer behind the last step
+struct LbRunState { std::vector<const uint8_t *> at; std::vector<size_t> len; size_t tight = LB_NONE; std::string tight_msg; };
+}  // namespace
+
+// The steps [0, steps) of the run [lo, lo + m) of a call's members; st.at / st.len: where they lie going in, and coming out.  `last`: the
+// m members' d_out / out_cap behind the last step (the device form), or null: an arena slot, as behind every other step.  A step's failure
+// is noted in `f` (and returned); a failure of the flow itself is returned with f.step untouched.
+static int layers_batch_steps(Ctx &c, hipStream_t s, bool enc, const int *layers, size_t n_layers, size_t steps, size_t lo, size_t m, const rsn_dev_member *last,
+                              LbRunState &st, size_t *got, LbFailure &f) {
+    std::vector<rsn_dev_member> tab(m);
+    std::vector<size_t> caps(m), offs;
+    for (size_t k = 0; k < steps; k++) {
+        const size_t li = enc ? k : n_layers - 1 - k;
+        const int id = layers[li];
+        const BatchDevLayer &layer = batch_dev_layer(id, enc);
+        const bool to_caller = last && k + 1 == n_layers;
+        auto fails = [&](int rc, size_t member) { f.step = k; f.member = member; f.rc = rc; f.msg = c.err; return rc; };
+        if (to_caller) {
+            for (size_t i = 0; i < m; i++) tab[i] = rsn_dev_member{st.at[i], st.len[i], last[i].d_out, last[i].d_out ? last[i].out_cap : 0};
+        } else {
+            for (size_t i = 0; i < m; i++) caps[i] = layer_slot_cap(id, enc, st.len[i]);
+            void *p;
+            int rc = dev_buf(c, k & 1 ? Slot::LB_B : Slot::LB_A, lb_arena(caps.data(), m, offs), &p); if (rc) return rc;
+            for (size_t i = 0; i < m; i++) tab[i] = rsn_dev_member{st.at[i], st.len[i], (uint8_t *)p + offs[i], caps[i]};
+        }
+        size_t failed = 0;
+        int rc = layer_empty_member(c, layer, enc, m, tab.data(), &failed); if (rc) return fails(rc, lo + failed);
+        rc = layer_batch_run(c, s, layer, enc, m, tab.data(), RSN_LZSS_DEFAULT_WINDOW, got, &failed);
+        if (failed == LB_NONE && rc) return rc;
+        if (rc && rc != RSN_ERR_CAPACITY) return fails(rc, lo + failed);
+        if (rc == RSN_ERR_CAPACITY && to_caller) { st.tight = lo + failed; st.tight_msg = c.err; }
+        if (rc == RSN_ERR_CAPACITY && !to_caller) {                       // the members that outgrew their slots, alone, with the reported figures
+            std::vector<size_t> again, caps2, got2;
+            for (size_t i = 0; i < m; i++) if (got[i] > caps[i]) { again.push_back(i); caps2.push_back(got[i]); }
+            std::vector<rsn_dev_member> tab2(again.size());
+            got2.assign(again.size(), 0);
+            void *p;
+            rc = dev_buf(c, k & 1 ? Slot::LB_XB : Slot::LB_XA, lb_arena(caps2.data(), again.size(), offs), &p); if (rc) return rc;
+            for (size_t q = 0; q < again.size(); q++) tab2[q] = rsn_dev_member{st.at[again[q]], st.len[again[q]], (uint8_t *)p + offs[q], caps2[q]};
+            rc = layer_batch_run(c, s, layer, enc, again.size(), tab2.data(), RSN_LZSS_DEFAULT_WINDOW, got2.data(), &failed);
+            if (failed == LB_NONE && rc) return rc;
+            if (rc) return fails(rc, lo + again[failed]);                 // (a figure that did not suffice after all: the codec's own error, worded as it words it)
+            for (size_t q = 0; q < again.size(); q++) { tab[again[q]].d_out = tab2[q].d_out; got[again[q]] = got2[q]; }
+        }
+        for (size_t i = 0; i < m; i++) { st.at[i] = (const uint8_t *)tab[i].d_out; st.len[i] = got[i]; }
+    }
+    return RSN_OK;
+}
+
+// what the call answers once its runs are through: a step's failure in the words of rsn.h, k counting in compress order
+static int layers_batch_failure(Ctx &c, bool enc, const int *layers, size_t n_layers, const LbFailure &f) {
+    const size_t li = enc ? f.step : n_layers - 1 - f.step;
+    return c.fail(f.rc, "member %zu: layer %zu (%s): %s", f.member, li, layer_name(layers[li]), f.msg.c_str());
+}
+// the runs of a call: the form's staged bytes of member i (0: it lies in the caller's device memory) and its largest slot, twice
+template <class Len>
+static std::vector<LbRun> layers_batch_runs(bool enc, const int *layers, size_t n_layers, size_t n, bool staged, Len len) {
+    return lb_runs(n, layers_batch_budget(), [&](size_t i) { return lb_member_need(staged ? len(i) : 0, layers_batch_slot(enc, layers, n_layers, len(i))); });
+}
+// the members' bytes as tiles of the move table; returns the entries written
+static size_t move_tiles(MoveEntry *tab, const uint8_t *src, uint8_t *dst, size_t len) {
+    size_t t = 0;
+    for (size_t at = 0; at < len; at += LB_TILE) tab[t++] = MoveEntry{src + at, dst + at, (unsigned long long)std::min(LB_TILE, len - at)};
+    return t;
+}
+
+static int layers_batch_dev(bool enc, size_t n, const rsn_dev_member *mem, const int *layers, size_t n_layers, size_t *out_lens, void *stream) {
+    Ctx &c = ctx(); hipStream_t s;
+    int rc = batch_dev_args(c, n, mem, out_lens, "layers"); if (rc || n == 0) return rc;
+    rc = layers_check(c, layers, n_layers); if (rc) return rc;
+    rc = dev_prologue(c, stream, &s); if (rc) return rc;
+    auto cleared = [&](int code) { for (size_t i = 0; i < n; i++) out_lens[i] = 0; return code; };
+    if (n_layers == 0) {                                                  // a copy of every member: one table up, one launch
+        size_t tiles = 0, tight = LB_NONE;
+        for (size_t i = 0; i < n; i++) tiles += lb_tiles(mem[i].n);
+        Admission gate(c, slotset::LAYERS_BATCH_CALL); gate.admit(tiles * sizeof(MoveEntry), ADMIT_FROM);
+        void *hp, *dp;
+        rc = pinned_buf(c, tiles * sizeof(MoveEntry) + 16, &hp); if (rc) return cleared(rc);
+        rc = dev_buf(c, Slot::LB_STAGE, tiles * sizeof(MoveEntry) + 16, &dp); if (rc) return cleared(rc);
+        MoveEntry *tab = (MoveEntry *)hp;
+        tiles = 0;
+        for (size_t i = 0; i < n; i++) {
+            const size_t cap = mem[i].d_out ? mem[i].out_cap : 0;
+            if (mem[i].n <= cap) { out_lens[i] = mem[i].n; tiles += move_tiles(tab + tiles, (const uint8_t *)mem[i].d_in, (uint8_t *)mem[i].d_out, mem[i].n); continue; }
+            out_lens[i] = round_up(mem[i].n, 16) + 16;                    // (layers_dev's figure)
+            if (tight == LB_NONE) tight = i;
+        }
+        rc = members_move(c, s, tab, (MoveEntry *)dp, tiles); if (rc) return cleared(rc);
+        { const hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) return cleared(c.fail(RSN_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e))); }
+        if (tight == LB_NONE) return RSN_OK;
+        return c.fail(RSN_ERR_CAPACITY, "member %zu: layers: output needs %zu bytes, buffer holds %zu", tight, (size_t)mem[tight].n, mem[tight].d_out ? (size_t)mem[tight].out_cap : (size_t)0);
+    }
+    const std::vector<LbRun> runs = layers_batch_runs(enc, layers, n_layers, n, false, [&](size_t i) { return (size_t)mem[i].n; });
+    size_t most = 0;
+    for (const LbRun &r : runs) most = std::max(most, r.bytes);
+    Admission gate(c, slotset::LAYERS_BATCH_CALL); gate.admit(most, ADMIT_FROM);
+    LbFailure f;
+    size_t tight = LB_NONE; std::string tight_msg;
+    size_t steps = n_layers;                                              // (behind a failure the later runs go as far as the steps in front of it: an earlier layer's failure there is the call's)
+    for (const LbRun &r : runs) {
+        if (steps == 0) break;
+        const size_t m = r.hi - r.lo;
+        LbRunState st;
+        st.at.resize(m); st.len.resize(m);
+        for (size_t i = 0; i < m; i++) { st.at[i] = (const uint8_t *)mem[r.lo + i].d_in; st.len[i] = mem[r.lo + i].n; }
+        const size_t before = f.step;
+        rc = layers_batch_steps(c, s, enc, layers, n_layers, steps, r.lo, m, mem + r.lo, st, out_lens + r.lo, f);
+        if (rc && f.step == before) return cleared(rc);
+        if (rc) { steps = f.step; continue; }
+        if (st.tight != LB_NONE && tight == LB_NONE) { tight = st.tight; tight_msg = st.tight_msg; }
+    }
+    if (f.step != LB_NONE) return cleared(layers_batch_failure(c, enc, layers, n_layers, f));
+    if (tight == LB_NONE) return RSN_OK;
+    const size_t li = enc ? n_layers - 1 : 0;
+    return c.fail(RSN_ERR_CAPACITY, "member %zu: layer %zu (%s): %s", tight, li, layer_name(layers[li]), tight_msg.c_str());
+}
+
+static int layers_batch_host(bool enc, size_t n, const uint8_t *const *ins, const size_t *lens, const int *layers, size_t n_layers, uint8_t **outs, size_t *out_lens) {
+    Ctx &c = ctx();
+    int rc = batch_args(c, n, ins, lens, outs, out_lens, true, true); if (rc || n == 0) return rc;
+    rc = layers_check(c, layers, n_layers); if (rc) return rc;
+    rc = ctx_init(c); if (rc) return rc;                                  // (no device: RSN_ERR_DEVICE -- there is no CPU path)
+    auto dropped = [&](int code) { drop_results(n, outs, out_lens); return code; };
+    if (n_layers == 0) {                                                  // the reference's loops do nothing: the inputs
+        for (size_t i = 0; i < n; i++) { rc = result_from_host(c, ins[i], lens[i], &outs[i], &out_lens[i]); if (rc) return dropped(rc); }
+        return RSN_OK;
+    }
+    hipStream_t s = c.own_stream;
+    const std::vector<LbRun> runs = layers_batch_runs(enc, layers, n_layers, n, true, [&](size_t i) { return lens[i]; });
+    size_t most = 0;
+    for (const LbRun &r : runs) most = std::max(most, r.bytes);
+    Admission gate(c, slotset::LAYERS_BATCH_CALL); gate.admit(most, ADMIT_FROM);
+    LbFailure f;
+    size_t steps = n_layers;
+    std::vector<size_t> offs, got;
+    for (const LbRun &r : runs) {
+        if (steps == 0) break;
+        const size_t m = r.hi - r.lo;
+        // up: the run's inputs packed at 16-byte offsets in pinned staging, ONE copy
+        const size_t up = lb_packed(lens + r.lo, m, offs);
+        void *hp, *dp;
+        rc = pinned_buf(c, up + 16, &hp); if (rc) return dropped(rc);
+        rc = dev_buf(c, Slot::LB_STAGE, up + LB_SLACK, &dp); if (rc) return dropped(rc);
+        LbRunState st;
+        st.at.resize(m); st.len.resize(m);
+        for (size_t i = 0; i < m; i++) {
+            const size_t len = lens[r.lo + i];
+            if (len) memcpy((uint8_t *)hp + offs[i], ins[r.lo + i], len);
+            memset((uint8_t *)hp + offs[i] + len, 0, lb_round16(len) - len);
+            st.at[i] = (const uint8_t *)dp + offs[i]; st.len[i] = len;
+        }
+        if (up) {
+            const hipError_t e = copy_async(dp, hp, up, hipMemcpyHostToDevice, s);
+            if (e != hipSuccess) return dropped(c.fail(RSN_ERR_DEVICE, "the upload of %zu bytes failed: %s", up, hipGetErrorString(e)));
+        }
+        { const hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) return dropped(c.fail(RSN_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e))); }   // (the steps stage their tables through the same pinned block)
+        got.assign(m, 0);
+        const size_t before = f.step;
+        rc = layers_batch_steps(c, s, enc, layers, n_layers, steps, r.lo, m, nullptr, st, got.data(), f);
+        if (rc && f.step == before) return dropped(rc);
+        if (rc) { steps = f.step; continue; }
+        if (steps < n_layers) continue;                                   // (the call has failed: this run only looked for an earlier layer's failure)
+        // down: the move table up, the members packed at 16-byte offsets by ONE launch, ONE copy, carved into the results
+        size_t tiles = 0;
+        for (size_t i = 0; i < m; i++) tiles += lb_tiles(st.len[i]);
+        const size_t tb = round_up(tiles * sizeof(MoveEntry), 16), down = lb_packed(st.len.data(), m, offs);
+        rc = pinned_buf(c, tb + down + 16, &hp); if (rc) return dropped(rc);
+        rc = dev_buf(c, Slot::LB_STAGE, tb + down + LB_SLACK, &dp); if (rc) return dropped(rc);
+        MoveEntry *tab = (MoveEntry *)hp;
+        tiles = 0;
+        for (size_t i = 0; i < m; i++) tiles += move_tiles(tab + tiles, st.at[i], (uint8_t *)dp + tb + offs[i], st.len[i]);
+        rc = members_move(c, s, tab, (MoveEntry *)dp, tiles); if (rc) return dropped(rc);
+        if (down) {
+            const hipError_t e = copy_async((uint8_t *)hp + tb, (const uint8_t *)dp + tb, down, hipMemcpyDeviceToHost, s);
+            if (e != hipSuccess) return dropped(c.fail(RSN_ERR_DEVICE, "the download of %zu bytes failed: %s", down, hipGetErrorString(e)));
+        }
+        { const hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) return dropped(c.fail(RSN_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e))); }
+        for (size_t i = 0; i < m; i++) { rc = result_from_host(c, (const uint8_t *)hp + tb + offs[i], st.len[i], &outs[r.lo + i], &out_lens[r.lo + i]); if (rc) return dropped(rc); }
+    }
+    if (f.step != LB_NONE) return dropped(layers_batch_failure(c, enc, layers, n_layers, f));
+    return RSN_OK;
+}
+
 static int layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size_t n_layers, rsn_roundtrip_result *res, uint8_t **compressed, size_t *compressed_n) {
     Ctx &c = ctx();
     if (!res || (!in && n) || (compressed && !compressed_n)) return c.fail(RSN_ERR_ARG, "null argument");
@@ -1853,6 +2089,10 @@ int rsn_layers_compress(const uint8_t *in, size_t n, const int *layers, size_t n
 int rsn_layers_decompress(const uint8_t *in, size_t n, const int *layers, size_t n_layers, uint8_t **out, size_t *out_n) { return guarded_out(out, out_n, [&] { return layers_host(false, in, n, layers, n_layers, out, out_n); }); }
 int rsn_layers_compress_dev(const void *d_in, size_t n, const int *layers, size_t n_layers, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded([&] { return layers_dev(true, d_in, n, layers, n_layers, d_out, out_cap, out_n, stream); }); }
 int rsn_layers_decompress_dev(const void *d_in, size_t n, const int *layers, size_t n_layers, void *d_out, size_t out_cap, size_t *out_n, void *stream) { return guarded([&] { return layers_dev(false, d_in, n, layers, n_layers, d_out, out_cap, out_n, stream); }); }
+int rsn_layers_compress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, const int *layers, size_t n_layers, uint8_t **outs, size_t *out_lens) { return guarded_outs(n, outs, out_lens, [&] { return layers_batch_host(true, n, ins, lens, layers, n_layers, outs, out_lens); }); }
+int rsn_layers_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, const int *layers, size_t n_layers, uint8_t **outs, size_t *out_lens) { return guarded_outs(n, outs, out_lens, [&] { return layers_batch_host(false, n, ins, lens, layers, n_layers, outs, out_lens); }); }
+int rsn_layers_compress_batch_dev(size_t n, const rsn_dev_member *members, const int *layers, size_t n_layers, size_t *out_lens, void *stream) { return guarded_lens(n, members, out_lens, [&] { return layers_batch_dev(true, n, members, layers, n_layers, out_lens, stream); }); }
+int rsn_layers_decompress_batch_dev(size_t n, const rsn_dev_member *members, const int *layers, size_t n_layers, size_t *out_lens, void *stream) { return guarded_lens(n, members, out_lens, [&] { return layers_batch_dev(false, n, members, layers, n_layers, out_lens, stream); }); }
 int rsn_layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size_t n_layers, rsn_roundtrip_result *res, uint8_t **compressed, size_t *compressed_n) {
     return guarded_call<int>([&] { return layers_roundtrip(in, n, layers, n_layers, res, compressed, compressed_n); }, [&](int code, const char *m) {
         if (res) memset(res, 0, sizeof *res);

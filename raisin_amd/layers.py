@@ -1,5 +1,6 @@
 """The engine's unit of work over librsn: a LIST of layers applied to one buffer (engine.go:443-479), with the stream kept on the device
-between the layers (rsn_layers_*, include/rsn.h).  Layers are given by the engine's names, in compress order."""
+between the layers (rsn_layers_*, include/rsn.h), and the same over MANY buffers in one call, layer-major, every member on the device from
+the first layer to the last (rsn_layers_*_batch, rsn_layers_*_batch_dev).  Layers are given by the engine's names, in compress order."""
 import ctypes
 
 from . import _lib
@@ -40,6 +41,40 @@ def decompress_tensor(src, layers, out=None, stream=None):
     """from 1 MiB of stream up the size query first (d_out NULL): it runs the chain once, rsn.h"""
     n = src.numel()
     return _lib.dev_tensor(_lib.lib().rsn_layers_decompress_dev, src, out, stream, 8 * n + (1 << 16) if n < (1 << 20) else None, *ids(layers), floor=16)
+
+
+def CompressBatch(datas, layers):
+    """engine.CompressFiles' work on a list of buffers: element i is byte for byte Compress(datas[i], layers)."""
+    arr, k = ids(layers)
+    return _lib.call_batch(_lib.lib().rsn_layers_compress_batch, datas, arr, k)
+
+
+def DecompressBatch(datas, layers):
+    """engine.DecompressFiles' work on a list of streams: element i is byte for byte Decompress(datas[i], layers)."""
+    arr, k = ids(layers)
+    return _lib.call_batch(_lib.lib().rsn_layers_decompress_batch, datas, arr, k)
+
+
+def compress_bound(n, layers):
+    """a capacity that always suffices for the layered stream of n bytes: the codecs' bounds applied in turn"""
+    L = _lib.lib()
+    for a in layers:
+        n = L.rsn_huffman_compress_bound(n) if IDS[a] == HUFFMAN else L.rsn_lzss_compress_bound(n)
+    return n
+
+
+def compress_tensors(srcs, layers, outs=None, stream=None):
+    """a list of uint8 CUDA tensors (16-byte aligned) -> the list of their layered streams, in one call (rsn_layers_compress_batch_dev);
+    without `outs`, views of one allocation with a slot of compress_bound bytes a member."""
+    arr, k = ids(layers)
+    return _lib.dev_tensors(_lib.lib().rsn_layers_compress_batch_dev, srcs, outs, stream, lambda n: compress_bound(n, layers), arr, k)
+
+
+def decompress_tensors(srcs, layers, outs=None, stream=None):
+    """the list of layered streams -> the list of what they hold (rsn_layers_decompress_batch_dev); a member that outgrows its slot of
+    8 * n + 64 KiB -- or its `out` -- is run once more, with the others of its kind, into an allocation of the size the call reported."""
+    arr, k = ids(layers)
+    return _lib.dev_tensors(_lib.lib().rsn_layers_decompress_batch_dev, srcs, outs, stream, lambda n: 8 * n + (1 << 16), arr, k)
 
 
 def RoundTrip(data, layers, keep_compressed=False):
