@@ -319,6 +319,42 @@ RSN_API int rsn_layers_decompress_batch(size_t n, const uint8_t *const *ins, con
 RSN_API int rsn_layers_compress_batch_dev(size_t n, const rsn_dev_member *members, const int *layers, size_t n_layers, size_t *out_lens, void *stream);
 RSN_API int rsn_layers_decompress_batch_dev(size_t n, const rsn_dev_member *members, const int *layers, size_t n_layers, size_t *out_lens, void *stream);
 
+/* ---- batch round trip ----------------------------------------------------
+ * engine.BenchmarkFile's body over MANY members in one call (the reference's benchmark loop, ai/helpers/compressor.py:89-108 over
+ * engine.go:213-309): every member is compressed under the layer list, decompressed again, compared with its original and its bytes
+ * counted, all on the device.  res[i] holds, field for field, what rsn_layers_roundtrip(ins[i], lens[i], layers, n_layers,
+ * ...) reports for member i alone; `hists` is NULL or n * 512 counters: hists[512 * i .. + 256) the byte counts of member i's input,
+ * hists[512 * i + 256 .. + 512) of what came back -- that call's two histograms as 32-bit counts.  No compressed bytes are handed out
+ * (rsn_layers_compress_batch does that), and there are no per-member times: the caller times the call.
+ * The layer list follows rsn_layers_compress_batch's rules: compress order, RSN_LAYER_LZSS / RSN_LAYER_HUFFMAN only, at most
+ * RSN_LAYERS_MAX entries, LZSS at RSN_LZSS_DEFAULT_WINDOW.  n_layers == 0: compressed and decompressed both equal the input.  An empty
+ * member under a list without Huffman: all sizes 0, lossless, first_difference UINT64_MAX.  The members run layer-major in the layered
+ * batch calls' runs (RSN_LAYERS_BATCH_BUDGET applies) -- the compress pass, the decompress pass from where the first left every member,
+ * then ONE launch that compares and counts all members of the run; per run one table goes up and one block of answers comes down (8 bytes
+ * a member, plus 2 KiB a member when `hists` is given).  Nothing else of a member crosses to the host; in the host form a run's inputs go
+ * up in one copy, in the device form the members are read where they lie and never written.
+ * Arguments, all checked before a device is looked for (RSN_ERR_ARG): n == 0 returns RSN_OK before anything else is looked at.  Host form:
+ * null `ins`, `lens` or `res`, a null ins[i] with a non-zero length.  Device form: null `members` or `res`; a null d_in with n > 0; a d_in
+ * that is not 16-byte aligned; every member's d_out must be NULL and its out_cap 0 -- both are RESERVED in this call, which writes no
+ * caller memory on the device.  Then the layer list as in rsn_layers_compress.  Without a device: RSN_ERR_DEVICE.
+ * Failures are all or nothing.  A round trip is 2 * n_layers steps: compress layers 0 .. L-1, then decompress layers L-1 .. 0.  The call
+ * ends with the EARLIEST step in that order at which some member fails, and with that step's lowest failing member, however the members
+ * were cut into runs; rsn_last_error() reads "member <i>: layer <k> (<name>): " followed by the single call's message, k counting in
+ * compress order.  Every res[i] is then zeroed and `hists` unspecified.  Behind the passes, a member whose original or decompressed
+ * length exceeds UINT32_MAX (the counters are 32 bits) fails the call with RSN_ERR_LIMIT and "member <i>: ...": one large buffer is
+ * rsn_layers_roundtrip's job.  Anything thrown leaves every res[i] zeroed.
+ * The device form queues its work on `stream` (NULL = the thread's own), which is synchronised before the call returns. */
+typedef struct {
+    uint64_t original_n, compressed_n, decompressed_n;
+    uint64_t first_difference;   /* as rsn_roundtrip_result: lowest differing offset; min(original_n, decompressed_n) if one is a
+                                    prefix of the other; UINT64_MAX if lossless */
+    int lossless;
+} rsn_roundtrip_member;
+RSN_API int rsn_layers_roundtrip_batch(size_t n, const uint8_t *const *ins, const size_t *lens, const int *layers, size_t n_layers,
+                                       rsn_roundtrip_member *res, uint32_t *hists);
+RSN_API int rsn_layers_roundtrip_batch_dev(size_t n, const rsn_dev_member *members, const int *layers, size_t n_layers,
+                                           rsn_roundtrip_member *res, uint32_t *hists, void *stream);
+
 /* ---- measurement --------------------------------------------------------
  * When enabled, every kernel launch of the calling thread is bracketed by HIP
  * events on the launch stream; rsn_prof_get() reports per-kernel totals since

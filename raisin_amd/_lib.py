@@ -38,6 +38,12 @@ class RoundTripResult(ctypes.Structure):
                 ("compress_ms", ctypes.c_double), ("decompress_ms", ctypes.c_double)]
 
 
+class RoundTripMember(ctypes.Structure):
+    """rsn_roundtrip_member (include/rsn.h): one member's answer of the batch round trip"""
+    _fields_ = [("original_n", ctypes.c_uint64), ("compressed_n", ctypes.c_uint64), ("decompressed_n", ctypes.c_uint64),
+                ("first_difference", ctypes.c_uint64), ("lossless", ctypes.c_int)]
+
+
 class DevMember(ctypes.Structure):
     """rsn_dev_member (include/rsn.h): one member of a batch call on device buffers"""
     _fields_ = [("d_in", ctypes.c_void_p), ("n", ctypes.c_size_t), ("d_out", ctypes.c_void_p), ("out_cap", ctypes.c_size_t)]
@@ -61,6 +67,7 @@ SYMBOLS = [
     "rsn_lzss_compress_batch_dev", "rsn_lzss_decompress_batch_dev", "rsn_arithmetic_compress_batch_dev", "rsn_arithmetic_decompress_batch_dev",
     "rsn_huffman_compress_batch_dev", "rsn_huffman_decompress_batch_dev",
     "rsn_layers_compress_batch", "rsn_layers_decompress_batch", "rsn_layers_compress_batch_dev", "rsn_layers_decompress_batch_dev",
+    "rsn_layers_roundtrip_batch", "rsn_layers_roundtrip_batch_dev",
 ]
 
 
@@ -141,6 +148,9 @@ def lib():
     for name in ("rsn_layers_compress_batch_dev", "rsn_layers_decompress_batch_dev"):
         getattr(L, name).argtypes = [sz, mp, ip, sz, szp, vp]
     L.rsn_layers_roundtrip.argtypes = [ctypes.c_char_p, sz, ip, sz, ctypes.POINTER(RoundTripResult), ctypes.POINTER(u8p), szp]
+    rmp, u32p = ctypes.POINTER(RoundTripMember), ctypes.POINTER(ctypes.c_uint32)
+    L.rsn_layers_roundtrip_batch.argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ip, sz, rmp, u32p]
+    L.rsn_layers_roundtrip_batch_dev.argtypes = [sz, mp, ip, sz, rmp, u32p, vp]
     L.rsn_prof_copied.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.rsn_prof_copied.restype = None
     _lib = L

@@ -4,6 +4,7 @@
 #include "codecs.h"
 #include "dev_ranges.h"
 #include "layers_batch_layout.h"
+#include "roundtrip_batch_layout.h"
 #include "group_layout.h"
 #include "rsn_common.h"
 #include "rsn_helpers.h"
@@ -1716,8 +1717,9 @@ struct LbRunState { std::vector<const uint8_t *> at; std::vector<size_t> len; si
 
 // The steps [0, steps) of the run [lo, lo + m) of a call's members; st.at / st.len: where they lie going in, and coming out.  `last`: the
 // m members' d_out / out_cap behind the last step (the device form), or null: an arena slot, as behind every other step.  A step's failure
-// is noted in `f` (and returned); a failure of the flow itself is returned with f.step untouched.
-static int layers_batch_steps(Ctx &c, hipStream_t s, bool enc, const int *layers, size_t n_layers, size_t steps, size_t lo, size_t m, const rsn_dev_member *last,
+// is noted in `f` (and returned); a failure of the flow itself is returned with f.step untouched.  start: the arena of step 0 (0: LB_A and
+// LB_XA, 1: LB_B and LB_XB) -- the batch round trip's second pass begins in the arena its first did not end in.
+static int layers_batch_steps(Ctx &c, hipStream_t s, bool enc, const int *layers, size_t n_layers, size_t steps, size_t start, size_t lo, size_t m, const rsn_dev_member *last,
                               LbRunState &st, size_t *got, LbFailure &f) {
     std::vector<rsn_dev_member> tab(m);
     std::vector<size_t> caps(m), offs;
@@ -1732,7 +1734,7 @@ static int layers_batch_steps(Ctx &c, hipStream_t s, bool enc, const int *layers
         } else {
             for (size_t i = 0; i < m; i++) caps[i] = layer_slot_cap(id, enc, st.len[i]);
             void *p;
-            int rc = dev_buf(c, k & 1 ? Slot::LB_B : Slot::LB_A, lb_arena(caps.data(), m, offs), &p); if (rc) return rc;
+            int rc = dev_buf(c, (k + start) & 1 ? Slot::LB_B : Slot::LB_A, lb_arena(caps.data(), m, offs), &p); if (rc) return rc;
             for (size_t i = 0; i < m; i++) tab[i] = rsn_dev_member{st.at[i], st.len[i], (uint8_t *)p + offs[i], caps[i]};
         }
         size_t failed = 0;
@@ -1747,7 +1749,7 @@ static int layers_batch_steps(Ctx &c, hipStream_t s, bool enc, const int *layers
             std::vector<rsn_dev_member> tab2(again.size());
             got2.assign(again.size(), 0);
             void *p;
-            rc = dev_buf(c, k & 1 ? Slot::LB_XB : Slot::LB_XA, lb_arena(caps2.data(), again.size(), offs), &p); if (rc) return rc;
+            rc = dev_buf(c, (k + start) & 1 ? Slot::LB_XB : Slot::LB_XA, lb_arena(caps2.data(), again.size(), offs), &p); if (rc) return rc;
             for (size_t q = 0; q < again.size(); q++) tab2[q] = rsn_dev_member{st.at[again[q]], st.len[again[q]], (uint8_t *)p + offs[q], caps2[q]};
             rc = layer_batch_run(c, s, layer, enc, again.size(), tab2.data(), RSN_LZSS_DEFAULT_WINDOW, got2.data(), &failed);
             if (failed == LB_NONE && rc) return rc;
@@ -1768,6 +1770,26 @@ static int layers_batch_failure(Ctx &c, bool enc, const int *layers, size_t n_la
 template <class Len>
 static std::vector<LbRun> layers_batch_runs(bool enc, const int *layers, size_t n_layers, size_t n, bool staged, Len len) {
     return lb_runs(n, layers_batch_budget(), [&](size_t i) { return lb_member_need(staged ? len(i) : 0, layers_batch_slot(enc, layers, n_layers, len(i))); });
+}
+// A host-form run on the way up: the m inputs packed at 16-byte offsets (lb_packed) in pinned staging, ONE copy into LB_STAGE, and the
+// stream synchronised (the steps stage their tables through the same pinned block).  st: where the members lie and how long.
+static int layers_batch_stage(Ctx &c, hipStream_t s, const uint8_t *const *ins, const size_t *lens, size_t m, std::vector<size_t> &offs, LbRunState &st) {
+    const size_t up = lb_packed(lens, m, offs);
+    void *hp, *dp;
+    int rc = pinned_buf(c, up + 16, &hp); if (rc) return rc;
+    rc = dev_buf(c, Slot::LB_STAGE, up + LB_SLACK, &dp); if (rc) return rc;
+    st.at.resize(m); st.len.resize(m);
+    for (size_t i = 0; i < m; i++) {
+        if (lens[i]) memcpy((uint8_t *)hp + offs[i], ins[i], lens[i]);
+        memset((uint8_t *)hp + offs[i] + lens[i], 0, lb_round16(lens[i]) - lens[i]);
+        st.at[i] = (const uint8_t *)dp + offs[i]; st.len[i] = lens[i];
+    }
+    if (up) {
+        const hipError_t e = copy_async(dp, hp, up, hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) return c.fail(RSN_ERR_DEVICE, "the upload of %zu bytes failed: %s", up, hipGetErrorString(e));
+    }
+    const hipError_t e = hipStreamSynchronize(s);
+    return e == hipSuccess ? RSN_OK : c.fail(RSN_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
 }
 // the members' bytes as tiles of the move table; returns the entries written
 static size_t move_tiles(MoveEntry *tab, const uint8_t *src, uint8_t *dst, size_t len) {
@@ -1816,7 +1838,7 @@ static int layers_batch_dev(bool enc, size_t n, const rsn_dev_member *mem, const
         st.at.resize(m); st.len.resize(m);
         for (size_t i = 0; i < m; i++) { st.at[i] = (const uint8_t *)mem[r.lo + i].d_in; st.len[i] = mem[r.lo + i].n; }
         const size_t before = f.step;
-        rc = layers_batch_steps(c, s, enc, layers, n_layers, steps, r.lo, m, mem + r.lo, st, out_lens + r.lo, f);
+        rc = layers_batch_steps(c, s, enc, layers, n_layers, steps, 0, r.lo, m, mem + r.lo, st, out_lens + r.lo, f);
         if (rc && f.step == before) return cleared(rc);
         if (rc) { steps = f.step; continue; }
         if (st.tight != LB_NONE && tight == LB_NONE) { tight = st.tight; tight_msg = st.tight_msg; }
@@ -1849,26 +1871,12 @@ static int layers_batch_host(bool enc, size_t n, const uint8_t *const *ins, cons
         if (steps == 0) break;
         const size_t m = r.hi - r.lo;
         // up: the run's inputs packed at 16-byte offsets in pinned staging, ONE copy
-        const size_t up = lb_packed(lens + r.lo, m, offs);
         void *hp, *dp;
-        rc = pinned_buf(c, up + 16, &hp); if (rc) return dropped(rc);
-        rc = dev_buf(c, Slot::LB_STAGE, up + LB_SLACK, &dp); if (rc) return dropped(rc);
         LbRunState st;
-        st.at.resize(m); st.len.resize(m);
-        for (size_t i = 0; i < m; i++) {
-            const size_t len = lens[r.lo + i];
-            if (len) memcpy((uint8_t *)hp + offs[i], ins[r.lo + i], len);
-            memset((uint8_t *)hp + offs[i] + len, 0, lb_round16(len) - len);
-            st.at[i] = (const uint8_t *)dp + offs[i]; st.len[i] = len;
-        }
-        if (up) {
-            const hipError_t e = copy_async(dp, hp, up, hipMemcpyHostToDevice, s);
-            if (e != hipSuccess) return dropped(c.fail(RSN_ERR_DEVICE, "the upload of %zu bytes failed: %s", up, hipGetErrorString(e)));
-        }
-        { const hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) return dropped(c.fail(RSN_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e))); }   // (the steps stage their tables through the same pinned block)
+        rc = layers_batch_stage(c, s, ins + r.lo, lens + r.lo, m, offs, st); if (rc) return dropped(rc);
         got.assign(m, 0);
         const size_t before = f.step;
-        rc = layers_batch_steps(c, s, enc, layers, n_layers, steps, r.lo, m, nullptr, st, got.data(), f);
+        rc = layers_batch_steps(c, s, enc, layers, n_layers, steps, 0, r.lo, m, nullptr, st, got.data(), f);
         if (rc && f.step == before) return dropped(rc);
         if (rc) { steps = f.step; continue; }
         if (steps < n_layers) continue;                                   // (the call has failed: this run only looked for an earlier layer's failure)
@@ -1891,6 +1899,135 @@ static int layers_batch_host(bool enc, size_t n, const uint8_t *const *ins, cons
     }
     if (f.step != LB_NONE) return dropped(layers_batch_failure(c, enc, layers, n_layers, f));
     return RSN_OK;
+}
+
+// ---- batch round trip (rsn.h): engine.BenchmarkFile's body over many members.  The layered batch calls' runs and steps, twice
+// -- the compress pass, then the decompress pass from where the first left every member, beginning in the other arena -- and behind them ONE
+// launch of k_members_verify (roundtrip_batch.hip) over a table of the run's tiles; the run's stats block is all that comes down.  A round
+// trip is 2 L steps; `limit` is how far the runs still go: behind a failure the later runs go as far as the steps in front of it.
+namespace {
+// the largest slot of the decompress pass of a member of n bytes, for the run cuts: the stream behind compress layer k is at most its bound
+// and taken as at most twice the member and a header -- an estimate, as layers_batch_slot's is for a decompress call
+size_t roundtrip_dec_slot(const int *layers, size_t n_layers, size_t n) {
+    size_t most = 0, cur = n;
+    for (size_t k = 0; k < n_layers; k++) {
+        cur = layer_slot_cap(layers[k], true, cur);
+        most = std::max(most, layer_slot_cap(layers[k], false, std::min(cur, 2 * n + 4096)));
+    }
+    return most;
+}
+}  // namespace
+
+// ins / lens: the host form (a run's inputs are staged in LB_STAGE and stay there to the end of the run); mem: the device form (read where
+// they lie).  The arguments have been checked and res zeroed.
+static int roundtrip_batch_flow(Ctx &c, hipStream_t s, size_t n, const uint8_t *const *ins, const size_t *lens, const rsn_dev_member *mem, const int *layers, size_t n_layers,
+                                rsn_roundtrip_member *res, uint32_t *hists) {
+    const bool staged = mem == nullptr;
+    auto len_of = [&](size_t i) { return staged ? lens[i] : (size_t)mem[i].n; };
+    auto zeroed = [&](int code) { memset(res, 0, n * sizeof *res); return code; };
+    const std::vector<LbRun> runs = lb_runs(n, layers_batch_budget(), [&](size_t i) {
+        const size_t len = len_of(i);
+        // (what comes back is taken as long as what went in: a member that comes back longer -- the Huffman codec's treatment of bytes that are
+        //  not UTF-8 -- may take a table entry of 32 bytes more than the run was cut for)
+        return rb_member_need(staged ? len : 0, layers_batch_slot(true, layers, n_layers, len), roundtrip_dec_slot(layers, n_layers, len), len, len, hists != nullptr);
+    });
+    size_t most = 0;
+    for (const LbRun &r : runs) most = std::max(most, r.bytes);
+    Admission gate(c, slotset::ROUNDTRIP_BATCH_CALL); gate.admit(most, ADMIT_FROM);
+    LbFailure fc, fd;                                                     // the compress pass's and the decompress pass's
+    size_t limit = 2 * n_layers, big = LB_NONE;                           // big: the lowest member the 32-bit counters do not hold
+    std::vector<size_t> offs, got, comp;
+    std::vector<const uint8_t *> orig;
+    int rc;
+    auto synced = [&]() { const hipError_t e = hipStreamSynchronize(s); return e == hipSuccess ? RSN_OK : c.fail(RSN_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e)); };
+    for (const LbRun &r : runs) {
+        if (n_layers && limit == 0) break;
+        const size_t m = r.hi - r.lo;
+        LbRunState st;
+        st.at.resize(m); st.len.resize(m); orig.resize(m);
+        void *hp, *dp;
+        if (staged) {                                                     // up: as layers_batch_host; the inputs stay in LB_STAGE to the end of the run
+            rc = layers_batch_stage(c, s, ins + r.lo, lens + r.lo, m, offs, st); if (rc) return zeroed(rc);
+        } else {
+            for (size_t i = 0; i < m; i++) { st.at[i] = (const uint8_t *)mem[r.lo + i].d_in; st.len[i] = mem[r.lo + i].n; }
+        }
+        for (size_t i = 0; i < m; i++) orig[i] = st.at[i];
+        got.assign(m, 0);
+        // the compress pass: steps 0 .. L - 1 of the round trip
+        size_t before = fc.step;
+        rc = layers_batch_steps(c, s, true, layers, n_layers, std::min(limit, n_layers), 0, r.lo, m, nullptr, st, got.data(), fc);
+        if (rc && fc.step == before) return zeroed(rc);
+        if (rc) { limit = fc.step; continue; }
+        if (n_layers && limit <= n_layers) continue;                      // (the call has failed in or right behind this pass: the run only looked for an earlier failure)
+        comp = st.len;
+        // the decompress pass: steps L .. 2 L - 1, from the arena the compress pass did not end in
+        before = fd.step;
+        rc = layers_batch_steps(c, s, false, layers, n_layers, limit - n_layers, n_layers & 1, r.lo, m, nullptr, st, got.data(), fd);
+        if (rc && fd.step == before) return zeroed(rc);
+        if (rc) { limit = n_layers + fd.step; continue; }
+        if (limit < 2 * n_layers || big != LB_NONE) continue;
+        // verify: the table up, ONE launch, the stats block down
+        size_t tiles = 0;
+        for (size_t i = 0; i < m; i++) {
+            if (!rb_fits(len_of(r.lo + i)) || !rb_fits(st.len[i])) { big = r.lo + i; break; }
+            tiles += rb_tiles(len_of(r.lo + i), st.len[i]);
+        }
+        if (big != LB_NONE) continue;
+        const bool counting = hists != nullptr;
+        const RbLayout lay = rb_layout(tiles, m, counting);
+        rc = pinned_buf(c, lay.bytes + 16, &hp); if (rc) return zeroed(rc);
+        rc = dev_buf(c, Slot::LB_VERIFY, lay.bytes + 16, &dp); if (rc) return zeroed(rc);
+        RbEntry *tab = (RbEntry *)((uint8_t *)hp + lay.table);
+        tiles = 0;
+        for (size_t i = 0; i < m; i++)
+            for (size_t t = 0, k = rb_tiles(len_of(r.lo + i), st.len[i]); t < k; t++)
+                tab[tiles++] = RbEntry{orig[i], st.at[i], (uint32_t)len_of(r.lo + i), (uint32_t)st.len[i], (uint32_t)i, (uint32_t)t};
+        rc = members_verify(c, s, tab, tiles, m, counting, dp); if (rc) return zeroed(rc);
+        {
+            const size_t down = rb_stats_bytes(lay);
+            const hipError_t e = copy_async((uint8_t *)hp + lay.words, (const uint8_t *)dp + lay.words, down, hipMemcpyDeviceToHost, s);
+            if (e != hipSuccess) return zeroed(c.fail(RSN_ERR_DEVICE, "the download of %zu bytes failed: %s", down, hipGetErrorString(e)));
+        }
+        rc = synced(); if (rc) return zeroed(rc);
+        const unsigned long long *words = (const unsigned long long *)((const uint8_t *)hp + lay.words);
+        for (size_t i = 0; i < m; i++) {
+            rsn_roundtrip_member &o = res[r.lo + i];
+            o.original_n = len_of(r.lo + i); o.compressed_n = comp[i]; o.decompressed_n = st.len[i];
+            o.first_difference = words[i] ? ~words[i] : (o.original_n == o.decompressed_n ? UINT64_MAX : std::min(o.original_n, o.decompressed_n));
+            o.lossless = o.first_difference == UINT64_MAX;
+        }
+        if (counting) memcpy(hists + r.lo * RB_HIST_WORDS, (const uint8_t *)hp + lay.hists, m * RB_HIST_BYTES);
+    }
+    if (fc.step != LB_NONE) return zeroed(layers_batch_failure(c, true, layers, n_layers, fc));
+    if (fd.step != LB_NONE) return zeroed(layers_batch_failure(c, false, layers, n_layers, fd));
+    if (big != LB_NONE) return zeroed(c.fail(RSN_ERR_LIMIT, "member %zu: a round trip of %zu bytes or more in a batch: the counters are 32 bits (rsn_layers_roundtrip takes one large buffer)", big, (size_t)1 << 32));
+    return RSN_OK;
+}
+
+static int layers_roundtrip_batch_host(size_t n, const uint8_t *const *ins, const size_t *lens, const int *layers, size_t n_layers, rsn_roundtrip_member *res, uint32_t *hists) {
+    Ctx &c = ctx();
+    if (n == 0) return RSN_OK;
+    if (!ins || !lens || !res) return c.fail(RSN_ERR_ARG, "null argument");
+    memset(res, 0, n * sizeof *res);
+    for (size_t i = 0; i < n; i++) if (!ins[i] && lens[i]) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
+    int rc = layers_check(c, layers, n_layers); if (rc) return rc;
+    rc = ctx_init(c); if (rc) return rc;                                  // (no device: RSN_ERR_DEVICE -- there is no CPU path)
+    return roundtrip_batch_flow(c, c.own_stream, n, ins, lens, nullptr, layers, n_layers, res, hists);
+}
+
+static int layers_roundtrip_batch_dev(size_t n, const rsn_dev_member *mem, const int *layers, size_t n_layers, rsn_roundtrip_member *res, uint32_t *hists, void *stream) {
+    Ctx &c = ctx(); hipStream_t s;
+    if (n == 0) return RSN_OK;
+    if (!mem || !res) return c.fail(RSN_ERR_ARG, "null argument");
+    memset(res, 0, n * sizeof *res);
+    for (size_t i = 0; i < n; i++) {                                      // (batch_dev_args' rules on d_in; this call writes no caller memory on the device)
+        if (!mem[i].d_in && mem[i].n) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
+        if (mem[i].d_out || mem[i].out_cap) return c.fail(RSN_ERR_ARG, "member %zu: d_out and out_cap are reserved in a round trip: NULL and 0", i);
+        if ((uintptr_t)mem[i].d_in & 15) return c.fail(RSN_ERR_ARG, "member %zu: layers: device buffers must be 16-byte aligned", i);
+    }
+    int rc = layers_check(c, layers, n_layers); if (rc) return rc;
+    rc = dev_prologue(c, stream, &s); if (rc) return rc;
+    return roundtrip_batch_flow(c, s, n, nullptr, nullptr, mem, layers, n_layers, res, hists);
 }
 
 static int layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size_t n_layers, rsn_roundtrip_result *res, uint8_t **compressed, size_t *compressed_n) {
@@ -2100,6 +2237,14 @@ int rsn_layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size_t 
         if (compressed_n) *compressed_n = 0;
         return boundary_error(code, m);
     });
+}
+int rsn_layers_roundtrip_batch(size_t n, const uint8_t *const *ins, const size_t *lens, const int *layers, size_t n_layers, rsn_roundtrip_member *res, uint32_t *hists) {
+    return guarded_call<int>([&] { return layers_roundtrip_batch_host(n, ins, lens, layers, n_layers, res, hists); },
+                             [&](int code, const char *m) { if (res) memset(res, 0, n * sizeof *res); return boundary_error(code, m); });
+}
+int rsn_layers_roundtrip_batch_dev(size_t n, const rsn_dev_member *members, const int *layers, size_t n_layers, rsn_roundtrip_member *res, uint32_t *hists, void *stream) {
+    return guarded_call<int>([&] { return layers_roundtrip_batch_dev(n, members, layers, n_layers, res, hists, stream); },
+                             [&](int code, const char *m) { if (res) memset(res, 0, n * sizeof *res); return boundary_error(code, m); });
 }
 void rsn_prof_copied(uint64_t *h2d_bytes, uint64_t *d2h_bytes) { guarded([&] { if (h2d_bytes) *h2d_bytes = g_copy_count.h2d.load(); if (d2h_bytes) *d2h_bytes = g_copy_count.d2h.load(); return 0; }); }
 void rsn_prof_enable(int on) { guarded([&] { ctx().prof = on != 0; g_copy_count.on.store(on != 0); return 0; }); }

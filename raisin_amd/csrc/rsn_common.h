@@ -29,7 +29,8 @@ struct ProfSlot {
 // The scratch slots of a thread's arena (Ctx::bufs, dev_buf): one row per slot -- who allocates it, what it holds, and in [..] the
 // codec gates that give its block back (E: the LZSS encoder's, D: the LZSS decoder's; X*: released by X's gate though X never allocates
 // it; the masks are below the table).  The gates of the host-buffer calls release what E releases plus the staging pair; the layered
-// calls' gate releases those and its own four slots; the layered batch calls' gate what E releases and its own five.
+// calls' gate releases those and its own four slots; the layered batch calls' gate what E releases and its own five; the batch round
+// trip's gate those and its verify slot.
 // A slot with two users is shared by convention: every codec call synchronises its stream before it returns, and the calls of one
 // thread -- the layers of a layered call included -- run one after the other, so the two users are never live together.
 // The numbers are fixed: DESIGN 4.8 and comments cite them, and a parked arena is adopted by index.
@@ -88,6 +89,8 @@ enum class Slot : int {
     LB_B = 50,          // ... the two arenas taking turns [layers_batch]
     LB_XA = 51,         // layered batch calls: the slots of the members that outgrew their first slot in LB_A and were run again alone ... [layers_batch]
     LB_XB = 52,         // ... and of those that outgrew theirs in LB_B [layers_batch]
+    LB_VERIFY = 53,     // batch round trip (rsn_api.hip: roundtrip_batch_flow): a run's verify table, behind it the stats block -- the members'
+                        //   first-difference words and histograms (roundtrip_batch_layout.h) [roundtrip_batch]
 };
 constexpr int RING = 3;                                                  // the batch pipeline's depth: RING inputs, RING segments
 constexpr Slot ring_in(int r) { return (Slot)((int)Slot::RING_IN0 + r); }
@@ -116,6 +119,8 @@ constexpr unsigned long long GROUP_DEV = slot_mask(S::GD_STAGE, S::GD_LENS);   /
 constexpr unsigned long long HUFF_DEV_PLANS = slot_mask(S::GD_PLANS);          // the plan table outlives the classes' runs: the call's own gate gives it back, never a class's
 constexpr unsigned long long LAYERS_BATCH = slot_mask(S::LB_STAGE, S::LB_A, S::LB_B, S::LB_XA, S::LB_XB);   // the layered batch calls' own
 constexpr unsigned long long LAYERS_BATCH_CALL = LZSS_ENC | LAYERS_BATCH;      // ... and what their gate gives back: the single calls that run inside a step leave the LZSS codecs' scratch
+constexpr unsigned long long ROUNDTRIP_BATCH = slot_mask(S::LB_VERIFY);        // the batch round trip's own: the verify table and the stats block
+constexpr unsigned long long ROUNDTRIP_BATCH_CALL = LAYERS_BATCH_CALL | ROUNDTRIP_BATCH;   // ... and what its gate gives back: both passes are the layered batch calls' steps
 // (RING is written out three times: the enumerators, RINGS and this check change together)
 static_assert(ring_in(RING) == Slot::RING_OUT0 && ring_out(RING - 1) == Slot::RING_OUT2, "the ring's slots are RING inputs, then RING segments");
 static_assert(((STAGING | RINGS | LAYERED) & (LZSS_ENC | LZSS_DEC)) == 0, "a codec's gate releases no staging, ring or layered slot: their callers still use them");
@@ -124,6 +129,7 @@ static_assert((LZSS_DEC & ~LZSS_ENC) == 0, "HOST_CALL covers both LZSS direction
 static_assert((GROUP_DEV & (HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED | ARITH)) == 0, "the device staging is released by its own gate only: the single calls that follow a class never hold it");
 static_assert((HUFF_DEV_PLANS & (GROUP_DEV | HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED | ARITH)) == 0, "no class run and no single call gives the plan table back while the call still reads it");
 static_assert((LAYERS_BATCH & (GROUP_DEV | HUFF_DEV_PLANS | HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED | ARITH)) == 0, "no step of a layered batch call gives an arena back: the next step reads it");
+static_assert((ROUNDTRIP_BATCH & (LAYERS_BATCH | GROUP_DEV | HUFF_DEV_PLANS | HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED | ARITH)) == 0, "no step of either pass gives the verify slot back, and the verify pass regrows no arena it reads");
 static_assert((ARITH & (HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED)) == 0, "the arithmetic codec shares no slot of its own with another codec or a caller");
 }  // namespace slotset
 
@@ -140,7 +146,7 @@ struct Ctx {
     std::vector<hipEvent_t> free_events;
 
     struct Buf { void *p = nullptr; size_t cap = 0; unsigned long long gen = 0; };   // gen: process-unique number of this allocation (dev_buf) -- an address can come back with other contents
-    enum { N_BUFS = (int)Slot::LB_XB + 1 };   // (the table above)
+    enum { N_BUFS = (int)Slot::LB_VERIFY + 1 };   // (the table above)
     Buf bufs[N_BUFS];
     Buf &buf(Slot k) { return bufs[(int)k]; }
     void *pinned = nullptr; size_t pinned_cap = 0;

@@ -8,7 +8,7 @@ import os
 import time
 from dataclasses import dataclass
 
-from . import huffman, layers as _layers, lz
+from . import _lib, huffman, layers as _layers, lz
 
 # engine.go:32 lists 11 engines; the MI355X build carries the two this path names
 # (the others -- arithmetic, dmc, mcc, stdlib bindings -- are out of scope).
@@ -371,6 +371,40 @@ def AsyncBenchmarkFile(algorithms, fileString):
         return BenchmarkFile(algorithms, fileString)
     except Exception:  # noqa: BLE001 -- mirrors recover()
         return Result(",".join(algorithms), "failed", 0.0, 0.0, 0.0, False, True)
+
+
+def BenchmarkFiles(algorithms, files):
+    """The benchmark loop for ONE layer list over many files (ai/helpers/compressor.py:89-108 over engine.BenchmarkFile): one Result per
+    file, in order, with BenchmarkFile's Ratio, Entropy, ActualEntropy (the quirk included, from the same counts) and Lossless.  The files
+    are taken in groups of at most BATCH_BYTES; a group of two or more files under layers that are all on the device is ONE call
+    (layers.RoundTripBatch: compressed, undone, compared and counted on the device, only the answers come down).  There is one timer around
+    a group's call: TimeTaken is that wall time divided by the group's file count.  A group whose call fails in the library -- one empty
+    file under Huffman -- is done again file by file through AsyncBenchmarkFile, so that file becomes a `failed` row and the others get
+    theirs; anything else that is raised is the caller's to see."""
+    algorithms, files = list(algorithms), list(files)
+    name = ",".join(algorithms)
+    batched = 1 <= len(algorithms) <= _layers.LAYERS_MAX and _on_device(algorithms)
+    results = []
+    for group, datas, bad in _groups(files, take_empty=True):
+        rows = None
+        if batched and len(group) > 1:
+            try:
+                start = time.perf_counter()
+                rows = _layers.RoundTripBatch(datas, algorithms)
+                dur = (time.perf_counter() - start) / len(group)
+            except _lib.RsnError:                               # a member's failure ends the call: the per-file loop finds the file
+                rows = None
+        if rows is None:
+            results.extend(AsyncBenchmarkFile(algorithms, f) for f in group)
+        else:
+            for data, rt in zip(datas, rows):
+                entropy = _entropy(rt.hist_original, len(data)) if data else 0.0
+                actual = _entropy(rt.hist_decompressed, rt.compressed_n) if rt.compressed_n else 0.0
+                ratio = rt.compressed_n / len(data) * 100 if data else float("nan")
+                results.append(Result(name, _time_taken(dur), ratio, actual, entropy, rt.lossless, False))
+        if bad is not None:
+            results.append(AsyncBenchmarkFile(algorithms, bad))  # a file that cannot be read: a failed row, in order
+    return results
 
 
 def _suite_order(results):

@@ -1,7 +1,10 @@
 """The engine's unit of work over librsn: a LIST of layers applied to one buffer (engine.go:443-479), with the stream kept on the device
 between the layers (rsn_layers_*, include/rsn.h), and the same over MANY buffers in one call, layer-major, every member on the device from
-the first layer to the last (rsn_layers_*_batch, rsn_layers_*_batch_dev).  Layers are given by the engine's names, in compress order."""
+the first layer to the last (rsn_layers_*_batch, rsn_layers_*_batch_dev) -- and the benchmark's whole body over many buffers, compressed,
+undone, compared and counted on the device (rsn_layers_roundtrip_batch, rsn_layers_roundtrip_batch_dev).  Layers are given by the engine's
+names, in compress order."""
 import ctypes
+from dataclasses import dataclass
 
 from . import _lib
 
@@ -93,3 +96,59 @@ def RoundTrip(data, layers, keep_compressed=False):
         return res, ctypes.string_at(out, n.value)
     finally:
         L.rsn_free(out)
+
+
+@dataclass
+class RoundTripMember:
+    """rsn_roundtrip_member, and the member's two histograms (lists of 256 counts) when they were asked for"""
+    original_n: int
+    compressed_n: int
+    decompressed_n: int
+    first_difference: int
+    lossless: bool
+    hist_original: list = None
+    hist_decompressed: list = None
+
+
+def _roundtrip_batch(k, hists, call):
+    """call(res, counts) over k members -> the list of RoundTripMember"""
+    import numpy as np
+    res = (_lib.RoundTripMember * max(k, 1))()
+    counts = np.zeros(512 * max(k, 1), dtype=np.uint32) if hists else None
+    _lib.check(call(res, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if hists else None))
+    out = []
+    for i in range(k):
+        r = res[i]
+        m = RoundTripMember(int(r.original_n), int(r.compressed_n), int(r.decompressed_n), int(r.first_difference), bool(r.lossless))
+        if hists:
+            m.hist_original = counts[512 * i:512 * i + 256].tolist()
+            m.hist_decompressed = counts[512 * i + 256:512 * i + 512].tolist()
+        out.append(m)
+    return out
+
+
+def RoundTripBatch(datas, layers, hists=True):
+    """engine.BenchmarkFile's body over a list of buffers in one call (rsn_layers_roundtrip_batch): element i holds what
+    RoundTrip(datas[i], layers) reports -- the sizes, lossless or not, where the buffers first differ -- and, with `hists`, both byte
+    histograms.  If any member fails the call raises, naming the member and the layer."""
+    arr, k = ids(layers)
+    L = _lib.lib()
+    datas = [bytes(d) for d in datas]
+    n = len(datas)
+    ins = (ctypes.c_char_p * max(n, 1))(*datas)
+    lens = (ctypes.c_size_t * max(n, 1))(*[len(d) for d in datas])
+    return _roundtrip_batch(n, hists, lambda res, counts: L.rsn_layers_roundtrip_batch(n, ins, lens, arr, k, res, counts))
+
+
+def roundtrip_tensors(srcs, layers, hists=True, stream=None):
+    """the same for a list of uint8 CUDA tensors (16-byte aligned), read where they lie and never written (rsn_layers_roundtrip_batch_dev);
+    only the answers come down."""
+    arr, k = ids(layers)
+    srcs = list(srcs)
+    if not srcs:
+        return []
+    L = _lib.lib()
+    st = _lib.own_stream(srcs[0], stream)
+    n = len(srcs)
+    mem = (_lib.DevMember * n)(*[_lib.DevMember(t.data_ptr() if t.numel() else None, t.numel(), None, 0) for t in srcs])
+    return _roundtrip_batch(n, hists, lambda res, counts: L.rsn_layers_roundtrip_batch_dev(n, mem, arr, k, res, counts, st))
