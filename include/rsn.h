@@ -101,7 +101,10 @@ RSN_API int rsn_lzss_decompress(const uint8_t *in, size_t n, uint8_t **out, size
  * When at least two chunks are of 2 B to 16 KiB, those run grouped first, on the calling thread:
  * one launch per group, a workgroup per chunk that builds the chunk's own tree.
  * Chunks above 16 KiB and up to 64 KiB run grouped the same way through a kernel of their own when the call holds at least
- * four of them.  A grouped chunk with a byte >= 0x80 or a single distinct byte is handed back to the pipeline.
+ * four of them.  A grouped chunk with a single distinct byte is handed back to the pipeline.  Chunks of at most 16 KiB with a
+ * byte >= 0x80 -- UTF-8 text, or no UTF-8 at all -- run grouped too, through an encoder of their own that counts runes as Go's
+ * `range string` yields them, when the call holds at least 16 of them; one with more than 256 distinct runes, or with a single
+ * one, is handed back to the pipeline, as every such chunk is in a call with fewer, and as chunks above 16 KiB are.
  * (RSN_BATCH_WORKERS, RSN_BATCH_KEEP_MIB: see rsn_api.hip / INTEGRATION.md.) */
 RSN_API int rsn_huffman_compress_batch(size_t n_chunks, const uint8_t *const *ins, const size_t *lens,
                                uint8_t **outs, size_t *out_lens);
@@ -269,8 +272,10 @@ RSN_API int rsn_arithmetic_decompress_dev(const void *d_in, size_t n, void *d_ou
  * trees themselves.  To decompress, one more kernel in front reads every candidate stream's header WHERE IT LIES -- separator, counts,
  * the reference's tree and the stream's bit bounds, a workgroup a member -- and 16 bytes a member come down for the host to size the
  * slots; streams of a byte alphabet that promise at most 64 KiB from at most 56 KiB of payload then run the grouped decoders.  What
- * still takes the single call on the same stream, in index order: rune alphabets (a byte >= 0x80 in the input or among the header's
- * symbols), a single distinct byte, headers the device-side plan refuses (a count of 65536 or more, foreign or malformed headers --
+ * still takes the single call on the same stream, in index order: to decompress, rune alphabets (a symbol >= 0x80 among the header's);
+ * to compress, members with a byte >= 0x80 unless the call holds at least 16 of them of at most 16 KiB -- those run grouped as well,
+ * through an encoder of their own that counts runes as Go's `range string` yields them (2 to 256 distinct runes; more, or one, take
+ * the single call); in both directions a single distinct byte, headers the device-side plan refuses (a count of 65536 or more, foreign or malformed headers --
  * the single call decodes them or words their error), members above 64 KiB, and classes below their minimum count.  An empty member
  * fails rsn_huffman_compress_batch_dev with RSN_ERR_EMPTY, as in the single call, before a device is looked for.
  * Huffman capacities: a buffer of rsn_huffman_compress_bound(n) always suffices.  A member that takes the single call needs what

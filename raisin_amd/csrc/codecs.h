@@ -10,7 +10,8 @@
 
 namespace rsn {
 
-size_t huff_compress_bound(size_t n);
+// an optimal prefix code never costs more than the fixed-length code: <= 21 bits per rune
+constexpr size_t huff_compress_bound(size_t n) { return n * 21 / 8 + (n < kMaxRune ? n : (size_t)kMaxRune) * 26 + 96; }
 size_t lzss_compress_bound(size_t n);
 
 // All four: buffers are device pointers (16-byte aligned), the call synchronises
@@ -59,7 +60,8 @@ int lzss_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
 //                          call; a non-zero return stops the call with that code); a member the kernel hands back -- or, for the Huffman
 //                          decoders, one whose header the host's plan refuses -- is appended to `back`, in index order, for the caller's
 //                          single call.  A failure returns its code with *failed = the group's first member (staging, launch, wait) or
-//                          the member itself (take).
+//                          the member itself (take).  back_runes (may be null): receives, instead of `back`, the members a kernel hands
+//                          back as GROUP_BACK_RUNES (group_layout.h) -- the Huffman byte encoders' "a byte >= 0x80 and nothing else".
 struct SmallMember { uint32_t in_off, n, out_off, status_off; };   // byte offsets into the group's staging
 constexpr size_t SMALL_GROUP_BYTES = (size_t)16 << 20;             // staging of one group (a member larger than that is a group of its own)
 constexpr size_t SMALL_GROUP_MAX = 4096;                           // members of one group
@@ -79,7 +81,7 @@ struct BatchClass {
     size_t group_min;
     bool (*takes)(const uint8_t *in, size_t n, int64_t window);
     int (*run)(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
-               const SmallTake &take, std::vector<size_t> &back, size_t *failed);
+               const SmallTake &take, std::vector<size_t> &back, size_t *failed, std::vector<size_t> *back_runes);
     // the device-buffer form (the batch calls on device buffers; group_run.h: run_groups_dev): the members `idx` of `mem` through the same
     // groups and the same kernel on `s`, the staging in device scratch; answers[k]: GROUP_BACK, or member idx[k]'s length -- its bytes are in
     // its d_out when that is at most its out_cap.  plans: null but for the Huffman decoders, whose table entries are completed on the device
@@ -115,6 +117,20 @@ constexpr size_t HUFF_MID_GROUP_MIN = 4;
 static_assert((unsigned long long)HUFF_MID_PAY_MAX * 8 >= (unsigned long long)HUFF_MID_IN_MAX * 7 && HUFF_MID_OUT_MAX >= HUFF_MID_IN_MAX,
               "the decoder takes every stream the encoder writes");
 const BatchClass &huff_small_class(bool compress), &huff_mid_class(bool compress);
+// huff_rune.hip: the members of at most HUFF_RUNE_IN_MAX bytes that k_huff_batch_enc hands back as GROUP_BACK_RUNES -- UTF-8 text, bytes
+// that are no UTF-8 at all -- a workgroup each in k_huff_batch_rune_enc: the runes as Go's `range string(b)` yields them counted in an
+// LDS table, the Go-exact tree of 2 to HUFF_RUNE_SYMS_MAX leaves in one wavefront (huff_plan_rune.h), header and code bits as the byte
+// encoder writes them.  It hands back more distinct runes than that, and a single one.  No row of batch_classes: no member is asked
+// whether it is of the class -- the byte encoder's answer says so -- and both batch flows (rsn_api.hip) run it behind the rows when a
+// call holds at least HUFF_RUNE_GROUP_MIN such members; fewer take the single call, as every one did before.
+// HUFF_RUNE_GROUP_MIN = 16 is the floor, not a crossover: calls with up to 12 such members keep their launches as they were, and at 16
+// members the grouped route already is 8 to 27 times as fast as the single calls it replaces, at 25 B, 1 KiB and 16 KiB, from host and
+// from device buffers -- no count tried (16 to 4096) loses at any size (profiles/huff_rune_batch.txt).
+// Mirrored as raisin_amd.huffman.RUNE_SYMS_MAX / RUNE_GROUP_MIN.
+constexpr uint32_t HUFF_RUNE_IN_MAX = 16384;
+constexpr uint32_t HUFF_RUNE_SYMS_MAX = 256;
+constexpr size_t HUFF_RUNE_GROUP_MIN = 16;
+const BatchClass &huff_rune_class();
 // the rows of a layer and direction in order of precedence: LZSS asks its small class first, Huffman decompress its mid class (a short
 // stream may promise more output than k_huff_batch_dec's workgroup holds)
 enum class BatchLayer { HUFFMAN, LZSS };

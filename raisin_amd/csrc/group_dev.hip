@@ -47,16 +47,16 @@ __global__ __launch_bounds__(GD_THREADS) void k_group_gather(const GatherEntry *
     if (threadIdx.x == 0) *reinterpret_cast<uint32_t *>(base + e.status_off) = GROUP_PENDING;
 }
 
-// A workgroup per member, behind the class's kernel on the stream: the status word into the class's compact array -- GROUP_BACK, or the
+// A workgroup per member, behind the class's kernel on the stream: the status word into the class's compact array -- GROUP_BACK, GROUP_BACK_RUNES, or the
 // length of the result -- and, when the result fits the member's buffer, the output slot into it: whole 16-byte units, then the tail byte
 // by byte, never a byte at or behind dst + len.  A word no kernel of the class can have written (still GROUP_PENDING, or a length beyond
 // the output slot) goes down as GROUP_PENDING: the host words it as the device failure it is, and nothing is copied.
 __global__ __launch_bounds__(GD_THREADS) void k_group_scatter(const GatherEntry *__restrict__ tab, const uint8_t *__restrict__ base, uint32_t *__restrict__ answers) {
     const GatherEntry e = tab[blockIdx.x];
     uint32_t v = *reinterpret_cast<const uint32_t *>(base + e.status_off);
-    if (v != GROUP_BACK && v > e.out_bytes) v = GROUP_PENDING;
+    if (!group_is_back(v) && v > e.out_bytes) v = GROUP_PENDING;
     if (threadIdx.x == 0) answers[blockIdx.x] = v;
-    if (v >= GROUP_BACK || v > e.cap) return;
+    if (v >= GROUP_BACK_RUNES || v > e.cap) return;                          // (a hand-back of either kind, or no answer)
     const uint4 *src = reinterpret_cast<const uint4 *>(base + e.out_off);
     uint4 *dst = reinterpret_cast<uint4 *>(e.dst);
     const uint32_t full = v / 16;

@@ -12,8 +12,10 @@
 namespace rsn {
 
 // a member's status word until its workgroup answers / the answer "not mine": the member goes back to the caller's single call.  Every
-// other value is the length of the result.
-constexpr uint32_t GROUP_PENDING = 0xFFFFFFFFu, GROUP_BACK = 0xFFFFFFFEu;
+// other value is the length of the result.  GROUP_BACK_RUNES is a hand-back too, with its reason: the Huffman byte encoders answer it
+// where the only obstacle was a byte >= 0x80, and the batch flows offer such members to the rune encoder (huff_rune.hip) first.
+constexpr uint32_t GROUP_PENDING = 0xFFFFFFFFu, GROUP_BACK = 0xFFFFFFFEu, GROUP_BACK_RUNES = 0xFFFFFFFDu;
+constexpr bool group_is_back(uint32_t v) { return v == GROUP_BACK || v == GROUP_BACK_RUNES; }
 constexpr size_t GROUP_STATUS_BYTES = 16;
 
 constexpr size_t group_round16(size_t v) { return (v + 15) & ~(size_t)15; }
@@ -60,6 +62,12 @@ constexpr size_t huff_enc_in_slot(size_t n) { return group_round16(n) + 16; }
 constexpr uint32_t HUFF_HDR_MAX = 1100;         // 128 entries of at most 5 digits + '|' + 2 bytes, + "\\\n" + pad
 constexpr uint32_t huff_small_enc_out_slot(uint32_t n) { return (HUFF_HDR_MAX + n + 15) & ~15u; }                    // holds header + 7n/8 + pad
 constexpr uint32_t huff_mid_enc_out_slot(uint32_t n) { return (HUFF_HDR_MAX + (7 * n + 7) / 8 + 3 + 15) & ~15u; }    // header + payload in whole words
+// the rune encoder (huff_rune.hip): at most 256 entries of 5 digits + '|' + 4 bytes of UTF-8, + "\\\n" + pad -- a header maximum of its
+// own, the decoders and huff_parse_small.h keep HUFF_HDR_MAX; fewer than 9 bits a rune (a Huffman code's average is below the entropy + 1,
+// and 256 symbols have at most 8 bits of it) and at most a rune a byte.  huff_rune_stream_max(n): the longest stream of a member of n bytes.
+constexpr uint32_t HUFF_RUNE_HDR_MAX = 256 * (5 + 1 + 4) + 3;
+constexpr uint32_t huff_rune_stream_max(uint32_t n) { return (n < 256 ? n : 256u) * 10 + 3 + (9 * n + 7) / 8; }
+constexpr uint32_t huff_rune_enc_out_slot(uint32_t n) { return (HUFF_RUNE_HDR_MAX + (9 * n + 7) / 8 + 64 + 15) & ~15u; }   // header + payload in whole words, and the image's slack
 constexpr size_t huff_dec_in_slot(size_t sn) { return group_round16(sn) + 64; }       // sn: the stream from the 4-byte boundary the kernel reads from
 constexpr size_t huff_dec_out_slot(size_t expect) { return group_round16(expect) + 16; }   // expect: the bytes the header promises
 

@@ -188,7 +188,7 @@ __global__ __launch_bounds__(GD_THREADS) void k_huff_dev_scatter(const DecEntry 
     uint32_t v = w0 == GROUP_PENDING ? GROUP_PENDING : w0 != 0 ? GROUP_BACK : w[1];
     if (v < GROUP_BACK && v > e.out_bytes) v = GROUP_PENDING;
     if (threadIdx.x == 0) answers[blockIdx.x] = v;
-    if (v >= GROUP_BACK || v > e.cap) return;
+    if (v >= GROUP_BACK_RUNES || v > e.cap) return;
     const uint4 *src = reinterpret_cast<const uint4 *>(base + e.out_off);
     uint4 *dst = reinterpret_cast<uint4 *>(e.dst);
     const uint32_t full = v / 16;

@@ -118,7 +118,7 @@ struct MidEncClass {
     }
 };
 int mid_dec_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t,
-                const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+                const SmallTake &take, std::vector<size_t> &back, size_t *failed, std::vector<size_t> *) {
     return huff_dec_run(c, MID_DEC_SHAPE, launch_mid_dec, idx, ins, lens, take, back, failed);
 }
 int mid_dec_run_dev(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const rsn_dev_member *mem, int64_t, const DevPlans *plans, std::vector<uint32_t> &answers) {

@@ -28,10 +28,12 @@ constexpr uint32_t PLAN_NODES_MAX = 2 * PLAN_SYMS_MAX - 1;
 constexpr uint32_t PLAN_COUNT_LIMIT = 1u << 16;   // every count below this
 
 // A heap item / a node's code: one word each.
-//   item   count << 8 | node id           (sums of counts < 2^23, ids < 255)
+//   item   count << IDB | node id         (sums of counts < 2^23, ids < 255)
 //   code   len << 24 | code (low 24 bits)  (k_small_emit's table entry; only meaningful while len <= 24)
-RSN_PLAN_FN uint32_t plan_item(uint32_t count, uint32_t id) { return count << 8 | id; }
-RSN_PLAN_FN uint32_t plan_count(uint32_t item) { return item >> 8; }
+// IDB: bits of a node id -- 8 for this alphabet; 9 for the rune alphabet of up to 256 leaves (huff_plan_rune.h: ids reach 510), which
+// shares the tree and the codes below.
+template <uint32_t IDB = 8> RSN_PLAN_FN uint32_t plan_item(uint32_t count, uint32_t id) { return count << IDB | id; }
+template <uint32_t IDB = 8> RSN_PLAN_FN uint32_t plan_count(uint32_t item) { return item >> IDB; }
 
 // position of byte b among the present bytes in (count asc, byte asc) order; cnt[128], cnt[b] > 0
 RSN_PLAN_FN uint32_t plan_leaf_rank(const uint32_t *cnt, uint32_t b) {
@@ -44,22 +46,23 @@ RSN_PLAN_FN uint32_t plan_leaf_rank(const uint32_t *cnt, uint32_t b) {
     return r;
 }
 
-// The Go heap over heap slots [0, a), filled with plan_item(count of leaf i, i) for the leaves in rank order (ascending: a heap already,
-// so heap.Init moves nothing, huffman.go:93).  Internal node a + k gets kids.set(k, left | right << 8).  Returns the root's id.
+// The Go heap over heap slots [0, a), filled with plan_item<IDB>(count of leaf i, i) for the leaves in rank order (ascending: a heap already,
+// so heap.Init moves nothing, huffman.go:93).  Internal node a + k gets kids.set(k, left | right << IDB).  Returns the root's id.
 // Pop and push carry the moving item and shift the others past it: heap.go's swaps give the same final layout.
-template <class Heap, class Kids>
+template <uint32_t IDB = 8, class Heap, class Kids>
 RSN_PLAN_FN uint32_t plan_tree(uint32_t a, Heap &h, Kids &kids) {
+    constexpr uint32_t IDM = (1u << IDB) - 1;
     uint32_t n = a, next = a;
     auto pop = [&]() -> uint32_t {                                    // heap.Pop: swap(0, n-1), down(0, n-1), take the last
-        const uint32_t m = n - 1, top = h.get(0), x = h.get(m), fx = plan_count(x);
+        const uint32_t m = n - 1, top = h.get(0), x = h.get(m), fx = plan_count<IDB>(x);
         n = m;
         uint32_t i = 0;
         for (;;) {
             const uint32_t l = 2 * i + 1;
             if (l >= m) break;
             uint32_t j = l, hj = h.get(l);
-            if (l + 1 < m) { const uint32_t hr = h.get(l + 1); if (plan_count(hr) < plan_count(hj)) { j = l + 1; hj = hr; } }
-            if (!(plan_count(hj) < fx)) break;
+            if (l + 1 < m) { const uint32_t hr = h.get(l + 1); if (plan_count<IDB>(hr) < plan_count<IDB>(hj)) { j = l + 1; hj = hr; } }
+            if (!(plan_count<IDB>(hj) < fx)) break;
             h.set(i, hj);
             i = j;
         }
@@ -68,14 +71,14 @@ RSN_PLAN_FN uint32_t plan_tree(uint32_t a, Heap &h, Kids &kids) {
     };
     while (n > 1) {                                                   // huffman.go:96-101
         const uint32_t x = pop(), y = pop();
-        const uint32_t f = plan_count(x) + plan_count(y), it = plan_item(f, next);
-        kids.set(next - a, (x & 0xFFu) | (y & 0xFFu) << 8);
+        const uint32_t f = plan_count<IDB>(x) + plan_count<IDB>(y), it = plan_item<IDB>(f, next);
+        kids.set(next - a, (x & IDM) | (y & IDM) << IDB);
         uint32_t j = n++;                                             // heap.Push: up(n)
         for (;;) {
             const uint32_t i = j ? (j - 1) / 2 : 0;
             if (i == j) break;
             const uint32_t hi = h.get(i);
-            if (!(f < plan_count(hi))) break;
+            if (!(f < plan_count<IDB>(hi))) break;
             h.set(j, hi);
             j = i;
         }
@@ -86,13 +89,13 @@ RSN_PLAN_FN uint32_t plan_tree(uint32_t a, Heap &h, Kids &kids) {
 }
 
 // Codes of every node [0, 2a - 1), parents before children: code.set(id, len << 24 | code).  Slots must start at 0 (the root's code).
-template <class Kids, class Codes>
+template <uint32_t IDB = 8, class Kids, class Codes>
 RSN_PLAN_FN void plan_codes(uint32_t a, uint32_t root, const Kids &kids, Codes &code) {
     for (uint32_t id = root + 1; id-- > a;) {
         const uint32_t p = code.get(id), l = (p >> 24) + 1, base = (p << 1) & 0xFFFFFEu;
         const uint32_t k = kids.get(id - a);
-        code.set(k & 0xFFu, l << 24 | base);
-        code.set(k >> 8, l << 24 | base | 1u);
+        code.set(k & ((1u << IDB) - 1), l << 24 | base);
+        code.set(k >> IDB, l << 24 | base | 1u);
     }
 }
 

@@ -347,7 +347,7 @@ bool batch_dec_takes(const uint8_t *, size_t n, int64_t) { return n >= 8 && n <=
 // (the plan has been made: what huff_dec_run refuses behind it, asked here)
 bool batch_dec_takes_plan(size_t n, const HuffDevSummary &sum) { return batch_dec_takes(nullptr, n, 0) && huff_dec_shape_takes(BATCH_DEC_SHAPE, sum); }
 int batch_dec_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t,
-                  const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
+                  const SmallTake &take, std::vector<size_t> &back, size_t *failed, std::vector<size_t> *) {
     return huff_dec_run(c, BATCH_DEC_SHAPE, launch_batch_dec, idx, ins, lens, take, back, failed);
 }
 int batch_dec_run_dev(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const rsn_dev_member *mem, int64_t, const DevPlans *plans, std::vector<uint32_t> &answers) {

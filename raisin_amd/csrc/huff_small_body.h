@@ -426,7 +426,7 @@ __device__ __forceinline__ void small_dec_body(const SmallDecArgs &a, uint32_t *
 // build_tree / assign_codes) with the heap, the children and the codes held in VGPRs, a slot per lane: a read is a readlane, a write a select in
 // the one lane, both at a wave-uniform index.  The other wavefronts wait; the header's entries are already in place (a scan of their lengths).  Then every
 // byte's first bit is a block scan of the code lengths and the codes are ORed into an LDS image of the output words, as k_small_emit does.
-// Status word: the stream's length, or GROUP_BACK -- a byte >= 0x80 (runes, huffman.go:309), fewer than two distinct bytes, a code beyond
+// Status word: the stream's length, GROUP_BACK_RUNES -- a byte >= 0x80 (runes, huffman.go:309) -- or GROUP_BACK: fewer than two distinct bytes, a code beyond
 // 24 bits or a header beyond HDR_MAX (none of the last two below the member cutoff: counts below 2^15 give codes of at most 20 bits).
 constexpr uint32_t HE_IN_MAX = 16384;            // member cutoff: 128 symbols code at most 7 bits a byte, so at most 14 KiB of payload
 constexpr uint32_t HE_T = 256;
@@ -450,6 +450,27 @@ struct LaneStore {
         for (int k = 0; k < R; k++) if (q == (uint32_t)k && me == l) r[k] = v;
     }
 };
+
+// A lane's up to 16 codes (len << 24 | code, len <= 24; 0: none) into the image from bit pos0 on: MSB first, words byte-swapped; the
+// lane's first and last words may be shared with its neighbours (LDS atomics), the words between are its own.
+__device__ __forceinline__ void pack_codes16(const uint32_t e[16], uint32_t pos0, uint32_t *s_img) {
+    uint32_t w = pos0 >> 5, nacc = pos0 & 31;
+    unsigned long long acc = 0;
+    bool first = true;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+        const uint32_t l = e[j] >> 24;
+        if (l) acc |= (unsigned long long)(e[j] & 0xFFFFFFu) << (64 - nacc - l);
+        nacc += l;
+        if (nacc >= 32) {
+            const uint32_t be = __builtin_bswap32((uint32_t)(acc >> 32));
+            if (first) atomicOr(&s_img[w], be); else s_img[w] = be;
+            first = false;
+            w++; acc <<= 32; nacc -= 32;
+        }
+    }
+    if (nacc) atomicOr(&s_img[w], __builtin_bswap32((uint32_t)(acc >> 32)));
+}
 
 // The encoder of one workgroup of T threads.  s_in: the member, IN_MAX bytes; s_img: the output, IMG_WORDS words -- header bytes, then the
 // code bits (MSB first, words byte-swapped); slot(n): bytes of the output slot of a member of n bytes.  WIDE: the image leaves in 16-byte
@@ -489,7 +510,7 @@ __device__ __forceinline__ void huff_enc_body(const SmallMember *__restrict__ ta
         s_tot[tid] = c;
     }
     const uint32_t a = (uint32_t)__syncthreads_count(tid < 128 && c != 0);
-    if (high || a < 2) { block_done(status, GROUP_BACK); return; }
+    if (high || a < 2) { block_done(status, high ? GROUP_BACK_RUNES : GROUP_BACK); return; }   // (runes: the rune encoder's, huff_rune.hip, when the call holds enough of them)
     // ---- leaves in (count asc, byte asc) order; the header's entries ascending by byte, '\\' first when it would be last (huffman.go:312-318)
     const bool above_bs = __syncthreads_or(tid > 0x5C && tid < 128 && c != 0);
     const bool bs_first = s_tot[0x5C] != 0 && !above_bs;
@@ -543,24 +564,7 @@ __device__ __forceinline__ void huff_enc_body(const SmallMember *__restrict__ ta
         }
         const uint32_t pos0 = at0 + block_excl_scan<T / 64>(bits, s_wave);
         at0 += s_wave[T / 64];
-        if (bits) {
-            uint32_t w = pos0 >> 5, nacc = pos0 & 31;
-            unsigned long long acc = 0;
-            bool first = true;
-#pragma unroll
-            for (int j = 0; j < 16; j++) {
-                const uint32_t l = e[j] >> 24;
-                if (l) acc |= (unsigned long long)(e[j] & 0xFFFFFFu) << (64 - nacc - l);
-                nacc += l;
-                if (nacc >= 32) {
-                    const uint32_t be = __builtin_bswap32((uint32_t)(acc >> 32));
-                    if (first) atomicOr(&s_img[w], be); else s_img[w] = be;
-                    first = false;
-                    w++; acc <<= 32; nacc -= 32;
-                }
-            }
-            if (nacc) atomicOr(&s_img[w], __builtin_bswap32((uint32_t)(acc >> 32)));
-        }
+        if (bits) pack_codes16(e, pos0, s_img);
     }
     __syncthreads();
     if constexpr (WIDE) {

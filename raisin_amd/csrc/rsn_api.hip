@@ -1104,6 +1104,19 @@ static void classify(BatchRows rows, size_t n, const uint8_t *const *ins, const 
     classify_by(rows, n, [&](const BatchClass &k, size_t i) { return k.takes(ins[i], lens[i], window); }, per, rest);
 }
 
+// The members the Huffman byte encoders handed back as GROUP_BACK_RUNES, sorted: those the rune class takes (huff_rune.hip: at most 16 KiB)
+// move to the front of `runes` and their number is returned, when there are at least its minimum of them; the others -- all of them
+// when there are fewer -- join `rest`, and go where they went before there was such a class.  len(i): member i's length.
+template <class Len>
+static size_t rune_class_members(std::vector<size_t> &runes, std::vector<size_t> &rest, Len len) {
+    const BatchClass &k = huff_rune_class();
+    std::sort(runes.begin(), runes.end());
+    auto mid = std::stable_partition(runes.begin(), runes.end(), [&](size_t i) { return k.takes(nullptr, len(i), 0); });
+    if ((size_t)(mid - runes.begin()) < k.group_min) mid = runes.begin();
+    rest.insert(rest.end(), mid, runes.end());
+    return (size_t)(mid - runes.begin());
+}
+
 static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
     Ctx &c = ctx();
     int rc0 = batch_args(c, n_chunks, ins, lens, outs, out_lens, false, false, HUFF_EMPTY); if (rc0) return rc0;
@@ -1113,24 +1126,31 @@ static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const
         return c.fail(rc, "%s", msg);
     };
     // Members of 2 B to 16 KiB (k_huff_batch_enc) and above that up to HUFF_MID_IN_MAX (k_huff_mid_enc) run grouped on this thread, one
-    // launch per group, every member its own workgroup and its own tree (codecs.h: the rows and their minimums).  The rest -- larger
-    // members, and the members a kernel hands back (runes, a single symbol) -- take the pipeline below, as every member did before, dealt
-    // over the batch workers.
+    // launch per group, every member its own workgroup and its own tree (codecs.h: the rows and their minimums).  The members those
+    // kernels hand back because of a byte >= 0x80 run grouped as well, through the rune class behind the rows (huff_rune.hip), when the call
+    // holds enough of them that it takes.  The rest -- larger members, and the members a kernel hands back (a single symbol, more runes
+    // than the rune class takes) -- take the pipeline below, as every member did before, dealt over the batch workers.
     const BatchRows rows = batch_classes(BatchLayer::HUFFMAN, true);
     std::vector<std::vector<size_t>> per;
-    std::vector<size_t> rest;
+    std::vector<size_t> rest, runes;
     classify(rows, n_chunks, ins, lens, 0, per, rest);
-    std::sort(rest.begin(), rest.end());
     const SmallTake take = take_into(c, outs, out_lens);
+    auto run_class = [&](const BatchClass &k, const std::vector<size_t> &idx, std::vector<size_t> *back_runes) {
+        size_t failed = 0;
+        return k.run(c, idx, ins, lens, 0, take, rest, &failed, back_runes);
+    };
     for (size_t r = 0; r < rows.n; r++) {
         if (per[r].empty()) continue;
-        std::vector<size_t> back;
-        size_t failed = 0;
-        const int rc = rows.first[r]->run(c, per[r], ins, lens, 0, take, back, &failed);
+        const int rc = run_class(*rows.first[r], per[r], &runes);
         if (rc != RSN_OK) { const std::string msg = c.err; return undo(rc, msg.c_str()); }
-        rest.insert(rest.end(), back.begin(), back.end());
-        std::sort(rest.begin(), rest.end());
     }
+    const size_t n_rune = rune_class_members(runes, rest, [&](size_t i) { return lens[i]; });
+    if (n_rune) {
+        runes.resize(n_rune);
+        const int rc = run_class(huff_rune_class(), runes, nullptr);
+        if (rc != RSN_OK) { const std::string msg = c.err; return undo(rc, msg.c_str()); }
+    }
+    std::sort(rest.begin(), rest.end());
     if (rest.empty()) return RSN_OK;
     std::vector<int> rcs;
     std::vector<std::string> msgs;
@@ -1193,7 +1213,7 @@ static int small_batch(BatchRows rows, int64_t window, size_t n, const uint8_t *
     for (size_t r = 0; r < rows.n && f.at == NONE; r++) {                 // (a device failure: nothing more is launched)
         if (per[r].empty()) continue;
         size_t failed = NONE;
-        rc = rows.first[r]->run(c, per[r], ins, lens, window, take, back, &failed);
+        rc = rows.first[r]->run(c, per[r], ins, lens, window, take, back, &failed, nullptr);
         if (rc != RSN_OK) note(f, failed, rc, c.err);
     }
     std::vector<char> handed(back_skips_small ? n : 0, 0);
@@ -1359,17 +1379,29 @@ static int layer_batch_run(Ctx &c, hipStream_t s, const BatchDevLayer &layer, bo
     size_t tight = NONE; std::string tight_msg;                           // the lowest member that did not fit, and what the single call says of it
     auto cap_of = [&](size_t i) { return mem[i].d_out ? mem[i].out_cap : (size_t)0; };
     std::vector<uint32_t> answers;
-    for (size_t r = 0; r < rows.n; r++) {
-        if (per[r].empty()) continue;
-        rc = rows.first[r]->run_dev(c, s, per[r], mem, window, planned ? &plans : nullptr, answers);
-        if (rc) return fails(rc, per[r][0]);                              // (a device failure: nothing more is launched)
-        for (size_t k = 0; k < per[r].size(); k++) {
-            const size_t i = per[r][k], got = answers[k];
-            if (answers[k] == GROUP_BACK) { rest.push_back(i); continue; }
+    std::vector<size_t> runes;                                            // handed back as GROUP_BACK_RUNES (the Huffman byte encoders alone answer that)
+    auto settle = [&](const std::vector<size_t> &idx) {                   // a class's answers for its members idx
+        for (size_t q = 0; q < idx.size(); q++) {
+            const size_t i = idx[q], got = answers[q];
+            if (group_is_back(answers[q])) { (answers[q] == GROUP_BACK_RUNES ? runes : rest).push_back(i); continue; }
             if (got <= cap_of(i)) { out_lens[i] = got; continue; }
             out_lens[i] = round_up(got, 16) + layer.slack;                // (as the single call reports it)
             if (i < tight) { tight = i; c.fail(RSN_ERR_CAPACITY, "%s: output needs %zu bytes, buffer holds %zu", layer.word, got, cap_of(i)); tight_msg = c.err; }
         }
+    };
+    for (size_t r = 0; r < rows.n; r++) {
+        if (per[r].empty()) continue;
+        rc = rows.first[r]->run_dev(c, s, per[r], mem, window, planned ? &plans : nullptr, answers);
+        if (rc) return fails(rc, per[r][0]);                              // (a device failure: nothing more is launched)
+        settle(per[r]);
+    }
+    if (const size_t n_rune = rune_class_members(runes, rest, [&](size_t i) { return mem[i].n; })) {   // (huff_rune.hip: the rune class behind the rows)
+        const std::vector<size_t> idx(runes.begin(), runes.begin() + (long)n_rune);
+        runes.clear();                                                    // (the class answers GROUP_BACK alone)
+        rc = huff_rune_class().run_dev(c, s, idx, mem, window, nullptr, answers);
+        if (rc) return fails(rc, idx[0]);
+        settle(idx);
+        rest.insert(rest.end(), runes.begin(), runes.end());
     }
     std::sort(rest.begin(), rest.end());
     for (size_t i : rest) {

@@ -23,8 +23,8 @@ def CompressSharded(fileContents, shards=0):
 def CompressBatch(chunks):
     """One complete .rsn segment per chunk, as engine.CompressFiles writes one file per input (engine.go:150-154).
     rsn_huffman_compress_batch runs chunks of 2 to BATCH_COMPRESS_INPUT_MAX bytes many to a launch, a workgroup each that builds the
-    chunk's own tree on the device (byte alphabets; a chunk with a byte >= 0x80 or a single distinct byte is handed back), when at least
-    two chunks are of that size.  Chunks above that and up to MID_IN_MAX bytes are the mid class (csrc/huff_mid.hip: the same kernel body at
+    chunk's own tree on the device (byte alphabets; a chunk with a single distinct byte is handed back, one with a byte >= 0x80 goes to
+    the rune class below, RUNE_GROUP_MIN), when at least two chunks are of that size.  Chunks above that and up to MID_IN_MAX bytes are the mid class (csrc/huff_mid.hip: the same kernel body at
     1024 threads, the whole chunk in LDS), grouped the same way when the call holds at least MID_GROUP_MIN of them.  The other chunks are dealt out over the batch workers (chunk k -> device k mod G) and go through a
     pipeline of upload / encode / download per device.  Each result equals Compress(chunk)."""
     return _lib.call_batch(_lib.lib().rsn_huffman_compress_batch, chunks)
@@ -48,6 +48,13 @@ MID_IN_MAX = 65536
 MID_PAY_MAX = 57344
 MID_OUT_MAX = 65536
 MID_GROUP_MIN = 4
+
+# The rune class of the compress batch calls (csrc/codecs.h HUFF_RUNE_SYMS_MAX / HUFF_RUNE_GROUP_MIN; csrc/huff_rune.hip): chunks
+# of at most BATCH_COMPRESS_INPUT_MAX bytes that hold a byte >= 0x80 -- UTF-8 text, or no UTF-8 at all -- go a workgroup each through one
+# launch per group when a call holds at least RUNE_GROUP_MIN of them; a chunk with more than RUNE_SYMS_MAX distinct runes, or with one, takes
+# the single call's path inside the batch, as every such chunk does in a call with fewer.  Decompress has no such class yet.
+RUNE_SYMS_MAX = 256
+RUNE_GROUP_MIN = 16
 
 
 def DecompressBatch(streams):
