@@ -120,7 +120,9 @@ RSN_API int rsn_huffman_compress_batch(size_t n_chunks, const uint8_t *const *in
  * LZSS streams of at most 2 KiB that expand to at most 8 KiB and, likewise, of at most 68 KiB that expand to at most 68 KiB
  * (the mid-size classes only when the call holds at least 64 such members); Huffman streams of a byte alphabet
  * (2 to 128 symbols, codes of at most 32 bits) with at most 16 KiB of payload and 32 KiB of output and, through a kernel of
- * their own when the call holds at least four such streams, with at most 56 KiB of payload and 64 KiB of output.  Every other member -- and
+ * their own when the call holds at least four such streams, with at most 56 KiB of payload and 64 KiB of output; Huffman streams of
+ * a rune alphabet (a symbol >= 0x80 among the header's 2 to 256; what the encoders write for UTF-8 text) that promise at most 16 KiB
+ * from at most 18 KiB of payload, through a decoder of their own when the call holds at least 16 such streams.  Every other member -- and
  * one a kernel hands back -- takes the single call's path, in index order; RSN_BATCH_WORKERS / RSN_BATCH_DEVICES deal those
  * over workers as rsn_huffman_compress_batch deals its chunks.  The same input bytes may be passed to several calls at once. */
 RSN_API int rsn_huffman_decompress_batch(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens);
@@ -272,7 +274,10 @@ RSN_API int rsn_arithmetic_decompress_dev(const void *d_in, size_t n, void *d_ou
  * trees themselves.  To decompress, one more kernel in front reads every candidate stream's header WHERE IT LIES -- separator, counts,
  * the reference's tree and the stream's bit bounds, a workgroup a member -- and 16 bytes a member come down for the host to size the
  * slots; streams of a byte alphabet that promise at most 64 KiB from at most 56 KiB of payload then run the grouped decoders.  What
- * still takes the single call on the same stream, in index order: to decompress, rune alphabets (a symbol >= 0x80 among the header's);
+ * still takes the single call on the same stream, in index order: to decompress, rune alphabets (a symbol >= 0x80 among the header's)
+ * unless the call holds at least 16 such streams that promise at most 16 KiB from at most 18 KiB of payload with 2 to 256 distinct
+ * runes -- ONE more plan kernel reads those headers where they lie (16 more bytes a member come down, one more host wait, only in calls
+ * that hold such members), and they run grouped through a decoder of their own that parses its header and builds its tree itself;
  * to compress, members with a byte >= 0x80 unless the call holds at least 16 of them of at most 16 KiB -- those run grouped as well,
  * through an encoder of their own that counts runes as Go's `range string` yields them (2 to 256 distinct runes; more, or one, take
  * the single call); in both directions a single distinct byte, headers the device-side plan refuses (a count of 65536 or more, foreign or malformed headers --

@@ -3,6 +3,7 @@
 
 #include <functional>
 
+#include "group_layout.h"
 #include "huff_host.h"
 #include "lzss_legacy.h"
 #include "rsn_common.h"
@@ -131,6 +132,37 @@ constexpr uint32_t HUFF_RUNE_IN_MAX = 16384;
 constexpr uint32_t HUFF_RUNE_SYMS_MAX = 256;
 constexpr size_t HUFF_RUNE_GROUP_MIN = 16;
 const BatchClass &huff_rune_class();
+// huff_rune_dec.hip: the way back.  A stream whose header names a rune >= 0x80 -- what the byte decoders' plans refuse -- a workgroup each
+// in k_huff_batch_rune_dec: the workgroup parses the header itself (huff_parse_rune.h: at most HUFF_RUNE_SYMS_MAX distinct runes, the
+// Go-exact tree in one wavefront), decodes the payload with the byte decoders' lane maps (huff_small_body.h: lane_dec_body) to a leaf rank
+// per symbol, and writes every rune as string(rune).  It takes a stream of at most HUFF_RUNE_STREAM_MAX bytes that promises at most
+// HUFF_RUNE_OUT_MAX bytes from at most HUFF_RUNE_PAY_MAX bytes of payload (group_layout.h) -- so every stream the rune encoder writes for a
+// member of valid UTF-8 is one this decoder takes; a byte that is no UTF-8 comes back as the three bytes of U+FFFD, so a lossy member's
+// stream may promise up to three times the member's size and goes to the single call when that passes HUFF_RUNE_OUT_MAX -- and hands back what the byte decoders hand back, a code beyond 32 bits, and a stream that decodes to more
+// bytes than its header promises.  No row of batch_classes either: both batch flows (rsn_api.hip) offer it the members the rows left for
+// the single call, the host form after a scan of the header that allocates nothing (huff_rune_dec_scan), the device form after ONE more
+// plan launch over them (k_huff_dev_rune_plan), and it runs when at least HUFF_RUNE_DEC_GROUP_MIN of them are planned.
+// HUFF_RUNE_DEC_GROUP_MIN: see DESIGN 4.7 for what was measured.  Mirrored as raisin_amd.huffman.RUNE_OUT_MAX / RUNE_PAY_MAX /
+// RUNE_DEC_GROUP_MIN.
+constexpr size_t HUFF_RUNE_DEC_GROUP_MIN = 16;
+constexpr bool huff_rune_dec_takes_the_encoder() {
+    for (uint32_t n = 2; n <= HUFF_RUNE_IN_MAX; n++) {
+        const uint32_t hdr = (n < 256 ? n : 256u) * 10 + 3, pay = huff_rune_stream_max(n) - hdr;
+        if (n > HUFF_RUNE_OUT_MAX || hdr > HUFF_RUNE_HDR_MAX || pay > HUFF_RUNE_PAY_MAX || huff_rune_stream_max(n) > HUFF_RUNE_STREAM_MAX) return false;
+    }
+    return true;
+}
+static_assert(huff_rune_dec_takes_the_encoder(), "header, payload and length of every stream the rune encoder writes are ones the rune decoder takes; valid UTF-8 decodes to the member's own n bytes");
+// the light scan of a stream in host memory: planned (a member for the class, with what it promises and where its payload starts) or not
+HuffDevSummary huff_rune_dec_scan(const uint8_t *in, size_t n);
+// Host form: of the members `rest` (sorted; what the rows left for the single call) those the scan plans run grouped when there are at
+// least the minimum of them -- take() receives their results -- and leave `rest`; what the kernel hands back stays in it.
+int huff_rune_dec_offer(Ctx &c, std::vector<size_t> &rest, const uint8_t *const *ins, const size_t *lens, const SmallTake &take, size_t *failed);
+// Device form: the members of `rest` that k_huff_dev_plan answered PARSE_NOT_MINE and that are short enough are planned where they lie by
+// ONE launch of k_huff_dev_rune_plan (one copy down, one host wait) when there are at least the minimum of them; the planned ones, when
+// still that many, leave `rest` for `idx` and run in run_groups_dev's groups -- answers[k]: GROUP_BACK or member idx[k]'s length.
+int huff_rune_dec_offer_dev(Ctx &c, hipStream_t s, std::vector<size_t> &rest, const rsn_dev_member *mem, const DevPlans &plans,
+                            std::vector<size_t> &idx, std::vector<uint32_t> &answers);
 // the rows of a layer and direction in order of precedence: LZSS asks its small class first, Huffman decompress its mid class (a short
 // stream may promise more output than k_huff_batch_dec's workgroup holds)
 enum class BatchLayer { HUFFMAN, LZSS };

@@ -69,10 +69,15 @@ __global__ __launch_bounds__(GD_THREADS) void k_group_scatter(const GatherEntry 
 
 int run_groups_dev(Ctx &c, hipStream_t s, const char *what, const std::vector<size_t> &idx, const rsn_dev_member *mem,
                    size_t (*in_bytes)(size_t n), size_t (*out_bytes)(size_t n), const GroupLaunch &launch, std::vector<uint32_t> &answers) {
+    return run_groups_dev_sized(c, s, what, idx, mem, [&](size_t k) { return in_bytes(mem[idx[k]].n); }, [&](size_t k) { return out_bytes(mem[idx[k]].n); }, launch, answers);
+}
+
+int run_groups_dev_sized(Ctx &c, hipStream_t s, const char *what, const std::vector<size_t> &idx, const rsn_dev_member *mem,
+                         const GroupSlotBytes &in_bytes, const GroupSlotBytes &out_bytes, const GroupLaunch &launch, std::vector<uint32_t> &answers) {
     const size_t count = idx.size();
     answers.assign(count, GROUP_PENDING);
     if (count == 0) return RSN_OK;
-    auto need = [&](size_t k) { const size_t n = mem[idx[k]].n; return group_need(GD_ENTRY, in_bytes(n), out_bytes(n)); };
+    auto need = [&](size_t k) { return group_need(GD_ENTRY, in_bytes(k), out_bytes(k)); };
     // the groups first: the largest one sizes the staging, and every group's tables have a pinned region of their own -- no group waits
     // for the copy of the one before it
     std::vector<GroupCut> cuts;
@@ -93,7 +98,7 @@ int run_groups_dev(Ctx &c, hipStream_t s, const char *what, const std::vector<si
         GroupLayout lay(g, GD_ENTRY);
         for (size_t q = 0; q < g; q++) {
             const rsn_dev_member &m = mem[idx[j + q]];
-            const size_t ib = in_bytes(m.n), ob = out_bytes(m.n);
+            const size_t ib = in_bytes(j + q), ob = out_bytes(j + q);
             const MemberSlots o = lay.member(ib, ob);
             tab[q] = SmallMember{o.in, (uint32_t)m.n, o.out, o.status};
             gat[q] = GatherEntry{(const uint8_t *)m.d_in, (uint8_t *)m.d_out, m.d_out ? (unsigned long long)m.out_cap : 0ull,

@@ -78,6 +78,11 @@ int run_member_groups(Ctx &c, const char *what, const std::vector<size_t> &idx, 
 using GroupLaunch = std::function<int(hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base)>;
 int run_groups_dev(Ctx &c, hipStream_t s, const char *what, const std::vector<size_t> &idx, const rsn_dev_member *mem,
                    size_t (*in_bytes)(size_t n), size_t (*out_bytes)(size_t n), const GroupLaunch &launch, std::vector<uint32_t> &answers);
+// ... with slots that depend on more than the member's length (the rune decoder's output slot is what its header promises): in_bytes(k) /
+// out_bytes(k) of member idx[k]
+using GroupSlotBytes = std::function<size_t(size_t k)>;
+int run_groups_dev_sized(Ctx &c, hipStream_t s, const char *what, const std::vector<size_t> &idx, const rsn_dev_member *mem,
+                         const GroupSlotBytes &in_bytes, const GroupSlotBytes &out_bytes, const GroupLaunch &launch, std::vector<uint32_t> &answers);
 
 // A class of SmallMember entries is stated ONCE, as a type K -- K::what (the name in messages), K::in_bytes(n) / K::out_bytes(n) (the slots of
 // a member of n bytes, group_layout.h) and K::launch(c, s, g, tab, base, window) (the group's kernel) -- and both of its runners, the

@@ -1,0 +1,296 @@
+// huff_rune_dec.hip -- the grouped Huffman decoder for streams whose header names a rune >= 0x80: what k_huff_batch_rune_enc (huff_rune.hip)
+// and the single call write for UTF-8 text and for bytes that are no UTF-8 at all (rsn_huffman_decompress_batch and its device, layered
+// and round-trip forms).  The byte decoders' plans refuse such a stream; when a call holds HUFF_RUNE_DEC_GROUP_MIN of them they
+// come here instead of taking the single call one by one: ONE launch per group, ONE workgroup of 320 threads per member, and the workgroup
+// makes the plan itself -- the host form and the device form launch the same kernel and neither ships a tree:
+//   header   the member's first min(n, PARSE_RUNE_SCAN_MAX) bytes into LDS; the separator by a block-wide minimum; ONE lane scans the
+//            entries into an LDS table of PARSE_RUNE_SLOTS slots, the encoder's hash -- a later entry for a rune finds its slot and
+//            replaces the count (huff_parse_rune.h: the code the CPU test holds against parse_header);
+//   tree     the symbols compacted, ranked a thread each (plan_rune_ranks over count + 1), and ONE wavefront builds the Go-exact tree of
+//            2 to 256 leaves with the heap, the children and the depths in VGPRs through LaneStore, as the encoder does; the children
+//            become child[] with a leaf's RANK where the byte decoders have its byte;
+//   payload  lane_dec_body (huff_small_body.h): the byte decoders' lookup table, run_path / emit_path, four-entry maps and PathMap
+//            composition, 256 lanes of at most 576 bits, with 510 entries of child[] and without its last store -- a leaf rank per symbol
+//            stays in LDS;
+//   expand   each thread takes a run of symbols, a block scan of utf8_len(leaf_rune[rank]) gives its first byte, every rune is written as
+//            string(rune) into an LDS image, and the image leaves in whole 16-byte units inside the member's output slot.
+// Status word: the decoded length in BYTES, or GROUP_BACK -- anything huff_parse_rune.h refuses, what lane_dec_body hands back (more than
+// four phases, DEC_ROUNDS rounds, a path off the payload, a stream that ends inside a codeword), an output slot smaller than the header
+// promises, and more decoded bytes than it promises.  Fewer is an answer.
+// LDS: one block of 18464 B that is the header and the table, then the payload's words, then the output image (each dead before the next
+// is written); the symbols 16416 B; the compacted symbols, leaves and child[] 5 KiB; lane_dec_body's own 6.6 KiB -- three workgroups to
+// a CU's 160 KiB (DESIGN 4.7 has the compile remarks).
+#include <iterator>
+
+#include "huff_small_body.h"
+#include "huff_parse_rune.h"
+
+namespace rsn {
+namespace {
+
+static_assert(PARSE_RUNE_HDR_MAX == HUFF_RUNE_HDR_MAX && PARSE_RUNE_OUT_MAX == HUFF_RUNE_OUT_MAX && PARSE_RUNE_PAY_MAX == HUFF_RUNE_PAY_MAX &&
+              PARSE_RUNE_STREAM_MAX == HUFF_RUNE_STREAM_MAX && PARSE_RUNE_SYMS_MAX == HUFF_RUNE_SYMS_MAX && PARSE_RUNE_LANES == (uint32_t)DL,
+              "huff_parse_rune.h restates the class's limits without its headers");
+static_assert(PARSE_RUNE_SCAN_MAX % 16 != 0, "the unit that holds the pad byte of the last separator looked for is one the header's load fetches");
+
+constexpr int RD_T = DT;                                                       // lane_dec_body's threads: 256 lanes and the wavefront of the first lane
+constexpr int RD_WAVES = RD_T / 64;
+constexpr int RP_T = 256;                                                      // threads of the plan kernel
+constexpr uint32_t RD_HDR_UNITS = (PARSE_RUNE_SCAN_MAX + 15) / 16;             // 16-byte units of the header in LDS
+constexpr uint32_t RD_PAY_WORDS = DL * PARSE_RUNE_S_MAX / 32 + 8;
+constexpr uint32_t RD_TABLE_AT = (RD_HDR_UNITS + 1) * 16;                      // the table behind the header's bytes
+constexpr uint32_t RD_PLAN_BYTES = RD_TABLE_AT + 2 * PARSE_RUNE_SLOTS * 4;
+constexpr uint32_t RD_IMG_BYTES = HUFF_RUNE_OUT_MAX + 16;
+constexpr uint32_t rd_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
+constexpr uint32_t RD_RAW_BYTES = (rd_max(rd_max(RD_PLAN_BYTES, RD_PAY_WORDS * 4), RD_IMG_BYTES) + 15) & ~15u;
+static_assert(PARSE_RUNE_SLOTS == 2 * RP_T && PARSE_RUNE_SLOTS <= 2 * RD_T && PARSE_RUNE_SYMS_MAX <= (uint32_t)RD_T, "two slots a thread, a thread a symbol");
+
+// the header's bytes in LDS, a word fetched for every four consecutive bytes asked for
+struct LdsBytes {
+    const uint32_t *w;
+    mutable uint32_t at = PARSE_NONE, cur = 0;
+    __device__ __forceinline__ uint32_t get(uint32_t i) const {
+        if ((i >> 2) != at) { at = i >> 2; cur = w[at]; }
+        return (cur >> (8 * (i & 3))) & 0xFFu;
+    }
+};
+
+// words of s_w
+enum { W_SEP = 0, W_SCAN_OK, W_EXPECT, W_OVER, W_HIGH, W_DISTINCT, W_ROOT, W_MIN, W_MAX, W_WORDS };
+
+// The plan in front of the tree, by a workgroup of T threads: the stream's first bytes into s_hdr under the gather's rule -- the unit that
+// reaches beyond src + n is masked, nothing at or behind src + n rounded up to 16 is loaded -- the separator, the entries into the table,
+// the counts' verdict and the stream's bounds.  false (the same for every thread): refused.  On return the table holds s_w[W_DISTINCT] runes.
+template <int T>
+__device__ __forceinline__ bool rune_light_plan(const uint8_t *src_bytes, unsigned long long n64, uint4 *s_hdr /*[RD_HDR_UNITS + 1]*/, uint32_t *s_key, uint32_t *s_c1,
+                                                uint32_t *s_w /*[W_WORDS]*/, HuffDevBounds &b, uint32_t *S, uint32_t *Tl) {
+    const uint32_t tid = threadIdx.x;
+    if (!parse_rune_length_ok(n64)) return false;
+    const uint32_t n = (uint32_t)n64, limit = parse_rune_scan_limit(n);
+    {
+        const uint4 *src = reinterpret_cast<const uint4 *>(src_bytes);
+        const uint32_t full = n / 16, rest = n & 15;
+        for (uint32_t u = tid; u * 16 < limit; u += T) {
+            uint4 v = src[u];                                  // (u * 16 < limit <= n)
+            if (u >= full) {
+                uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (uint32_t k = 0; k < 4; k++) {
+                    const uint32_t keep = rest > 4 * k ? min(rest - 4 * k, 4u) : 0u;
+                    w[k] = keep == 4 ? w[k] : keep == 0 ? 0u : w[k] & ((1u << (8 * keep)) - 1);
+                }
+                v = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+            s_hdr[u] = v;
+        }
+    }
+    for (uint32_t i = tid; i < PARSE_RUNE_SLOTS; i += T) { s_key[i] = PARSE_RUNE_EMPTY; s_c1[i] = 0; }
+    if (tid < W_WORDS) s_w[tid] = tid == W_SEP ? PARSE_NONE : 0u;
+    __syncthreads();
+    const uint8_t *hb = reinterpret_cast<const uint8_t *>(s_hdr);
+    {   // strings.SplitN(content, "\\\n", 2): the first separator among the bytes looked at -- a position at or behind n is never asked
+        uint32_t mine = PARSE_NONE;
+        for (uint32_t i = tid; i + 1 < limit; i += T) if (parse_sep_at(hb[i], hb[i + 1])) { mine = i; break; }
+        if (mine != PARSE_NONE) atomicMin(&s_w[W_SEP], mine);
+    }
+    __syncthreads();
+    const uint32_t sep = s_w[W_SEP];
+    if (sep == PARSE_NONE || sep + 4 > n) return false;
+    if (tid == 0) { LdsBytes h; h.w = reinterpret_cast<const uint32_t *>(s_hdr); s_w[W_SCAN_OK] = parse_rune_scan(h, sep, s_key, s_c1, &s_w[W_DISTINCT]) ? 1u : 0u; }
+    __syncthreads();
+    if (!s_w[W_SCAN_OK]) return false;
+    for (uint32_t i = tid; i < PARSE_RUNE_SLOTS; i += T) {
+        const uint32_t r = s_key[i], c1 = s_c1[i];
+        if (r == PARSE_RUNE_EMPTY) continue;
+        if (c1 - 1 > PARSE_RUNE_COUNT_MAX) s_w[W_OVER] = 1;
+        else atomicAdd(&s_w[W_EXPECT], parse_rune_bytes(r, c1));       // (256 symbols of at most 16384 * 4 bytes: no wrap)
+        if (r >= 0x80) s_w[W_HIGH] = 1;
+    }
+    __syncthreads();
+    if (!parse_rune_counts_ok(s_w[W_DISTINCT], s_w[W_HIGH] != 0, s_w[W_OVER] != 0, s_w[W_EXPECT]) || !parse_rune_bounds(n, sep, hb[sep + 2], b, S, Tl)) return false;
+    b.expect = s_w[W_EXPECT];
+    return true;
+}
+
+__global__ __launch_bounds__(RD_T) void k_huff_batch_rune_dec(const SmallMember *__restrict__ tab, uint8_t *__restrict__ base) {
+    __shared__ uint4 s_raw[RD_RAW_BYTES / 16];                      // the header and the table; then the payload's words; then the output image
+    __shared__ __attribute__((aligned(16))) uint8_t s_sym[HUFF_RUNE_OUT_MAX + 32];   // a leaf rank per symbol
+    __shared__ uint32_t s_rune[PARSE_RUNE_SYMS_MAX], s_rc1[PARSE_RUNE_SYMS_MAX];  // the symbols compacted, in slot order: rune, count + 1
+    __shared__ uint32_t s_lf[PARSE_RUNE_SYMS_MAX], s_leaf_rune[PARSE_RUNE_SYMS_MAX];   // the leaves in (count asc, rune asc) order: count, rune
+    __shared__ __attribute__((aligned(4))) uint16_t s_kid[PARSE_RUNE_CHILD_MAX + 2];
+    __shared__ uint32_t s_wave[RD_WAVES + 1];
+    __shared__ uint32_t s_w[W_WORDS];
+    __shared__ SmallDecArgs s_a;
+    const SmallMember m = tab[blockIdx.x];
+    uint32_t *status = reinterpret_cast<uint32_t *>(base + m.status_off);
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t *s_key = reinterpret_cast<uint32_t *>(s_raw) + RD_TABLE_AT / 4, *s_c1 = s_key + PARSE_RUNE_SLOTS;
+    // every verdict below is the same for the whole workgroup: a hand-back is a return of all its threads
+    HuffDevBounds b{};
+    uint32_t S = 0, T = 0;
+    if (!rune_light_plan<RD_T>(base + m.in_off, m.n, s_raw, s_key, s_c1, s_w, b, &S, &T)) { block_done(status, GROUP_BACK); return; }
+    const uint32_t a = s_w[W_DISTINCT], expect = b.expect;
+    if (huff_dec_out_slot(expect) > m.status_off - m.out_off) { block_done(status, GROUP_BACK); return; }   // (the host sized the slot from the same bytes: it holds)
+    {   // the symbols side by side (two slots a thread), then ranked
+        const uint32_t k0 = 2 * tid < PARSE_RUNE_SLOTS ? s_key[2 * tid] : PARSE_RUNE_EMPTY, k1 = 2 * tid < PARSE_RUNE_SLOTS ? s_key[2 * tid + 1] : PARSE_RUNE_EMPTY;
+        uint32_t at = block_excl_scan<RD_WAVES>((uint32_t)(k0 != PARSE_RUNE_EMPTY) + (uint32_t)(k1 != PARSE_RUNE_EMPTY), s_wave);
+        if (k0 != PARSE_RUNE_EMPTY) { s_rune[at] = k0; s_rc1[at] = s_c1[2 * tid]; at++; }
+        if (k1 != PARSE_RUNE_EMPTY) { s_rune[at] = k1; s_rc1[at] = s_c1[2 * tid + 1]; }
+    }
+    __syncthreads();
+    if (tid < a) {
+        uint32_t lr, rr;
+        plan_rune_ranks(s_rune, s_rc1, a, tid, &lr, &rr);
+        s_lf[lr] = s_rc1[tid] - 1; s_leaf_rune[lr] = s_rune[tid];
+    }
+    __syncthreads();
+    // ---- the tree, the depths and child[]: one wavefront, every index wave-uniform (huffman.go:93-127)
+    if (wave == 0) {
+        const uint32_t au = (uint32_t)__builtin_amdgcn_readfirstlane((int)a);
+        LaneStore<4> heap, kids;
+        LaneStore<8> code;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t l = lane + 64 * k;
+            heap.r[k] = l < au ? plan_item<PLAN_RUNE_IDB>(s_lf[l], l) : 0u;
+            kids.r[k] = 0;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; k++) code.r[k] = 0;
+        const uint32_t root = plan_tree<PLAN_RUNE_IDB>(au, heap, kids);
+        plan_codes<PLAN_RUNE_IDB>(au, root, kids, code);
+        // leaf l is lane l % 64 of code.r[l / 64], internal node k lane k % 64 of kids.r[k / 64]
+        uint32_t mn = 255, mx = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t l = lane + 64 * k;
+            if (l < au) { const uint32_t len = code.r[k] >> 24; mn = min(mn, len); mx = max(mx, len); }
+            if (l + 1 < au) {
+                s_kid[2 * l] = (uint16_t)parse_rune_child(kids.r[k] & ((1u << PLAN_RUNE_IDB) - 1), au);
+                s_kid[2 * l + 1] = (uint16_t)parse_rune_child(kids.r[k] >> PLAN_RUNE_IDB, au);
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { mn = min(mn, (uint32_t)__shfl_xor((int)mn, d, 64)); mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64)); }
+        if (lane == 0) { s_w[W_ROOT] = root - au; s_w[W_MIN] = mn; s_w[W_MAX] = mx; }
+    }
+    __syncthreads();
+    if (!parse_depths(s_w[W_MIN], s_w[W_MAX], b)) { block_done(status, GROUP_BACK); return; }
+    if (tid == 0) {
+        s_a.pay = reinterpret_cast<const uint32_t *>(base + m.in_off + b.A0);   // (A0 a multiple of 4, the slot 16-aligned, zeros behind the stream)
+        s_a.pay_words = b.pay_words; s_a.p0 = b.p0; s_a.end = b.end;
+        s_a.K = b.K; s_a.root = s_w[W_ROOT]; s_a.n_child = 2 * (a - 1);
+        s_a.S = S; s_a.T = T; s_a.flat = b.flat; s_a.seq = 0;
+        s_a.hout = nullptr; s_a.status = nullptr; s_a.g_maps = nullptr; s_a.g_flags = nullptr;
+        s_a.out_max = HUFF_RUNE_OUT_MAX;
+    }
+    __syncthreads();                                                  // (the header and the table are dead: the payload's words take their place)
+    const uint32_t n_sym = lane_dec_body<RD_PAY_WORDS, HUFF_RUNE_OUT_MAX, false, DL, PARSE_RUNE_CHILD_MAX + 2, false>(s_a, s_kid, reinterpret_cast<uint32_t *>(s_raw), s_sym);
+    if (n_sym == DEC_BODY_BACK) { block_done(status, GROUP_BACK); return; }
+    // ---- expand: a run of symbols a thread, their bytes' positions by a block scan, string(rune) into the image (the payload is dead)
+    const uint32_t per = (n_sym + RD_T - 1) / RD_T, lo = min(tid * per, n_sym), hi = min(lo + per, n_sym);
+    uint32_t bytes = 0;
+    for (uint32_t i = lo; i < hi; i++) bytes += plan_rune_utf8_len(s_leaf_rune[s_sym[i]]);
+    uint32_t at = block_excl_scan<RD_WAVES>(bytes, s_wave);
+    const uint32_t total = s_wave[RD_WAVES];
+    if (total == 0 || total > expect) { block_done(status, GROUP_BACK); return; }    // (more than the header promises: the single call's, as the byte decoders do with out_max)
+    uint8_t *img = reinterpret_cast<uint8_t *>(s_raw);
+    for (uint32_t i = lo; i < hi; i++) at += parse_rune_write(s_leaf_rune[s_sym[i]], img + at);
+    __syncthreads();
+    uint4 *hout = reinterpret_cast<uint4 *>(base + m.out_off);
+    for (uint32_t u = tid; u * 16 < total; u += RD_T) hout[u] = s_raw[u];          // (total <= expect: inside the slot, huff_dec_out_slot(expect))
+    block_done(status, total);
+}
+
+// ---- the device form's second plan launch: the light scan where the stream lies, a workgroup a candidate, 16 bytes of summary each
+struct RunePlanEntry { const uint8_t *src; unsigned long long n; };
+static_assert(sizeof(RunePlanEntry) == 16, "16 bytes a candidate go up");
+__global__ __launch_bounds__(RP_T) void k_huff_dev_rune_plan(const RunePlanEntry *__restrict__ tab, HuffDevSummary *__restrict__ sums) {
+    __shared__ uint4 s_hdr[RD_HDR_UNITS + 1];
+    __shared__ uint32_t s_key[PARSE_RUNE_SLOTS], s_c1[PARSE_RUNE_SLOTS];
+    __shared__ uint32_t s_w[W_WORDS];
+    const RunePlanEntry e = tab[blockIdx.x];
+    HuffDevBounds b{};
+    uint32_t S = 0, T = 0;
+    const bool planned = rune_light_plan<RP_T>(e.src, e.n, s_hdr, s_key, s_c1, s_w, b, &S, &T);
+    if (threadIdx.x == 0) sums[blockIdx.x] = planned ? HuffDevSummary{PARSE_PLANNED, b.A0, b.end - b.p0, b.expect} : HuffDevSummary{PARSE_NOT_MINE, 0, 0, 0};
+}
+
+int launch_rune_dec(Ctx &c, hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
+    RSN_LAUNCH("huff_batch_rune_dec", k_huff_batch_rune_dec, dim3(g), dim3(RD_T), 0, s, tab, base);
+    return RSN_OK;
+}
+const char *const RD_WHAT = "huffman batch decompress";
+bool rune_dec_summary_ok(const HuffDevSummary &v, size_t n) {
+    return v.verdict == PARSE_PLANNED && !(v.A0 & 3u) && v.A0 <= n && v.expect >= 1 && v.expect <= HUFF_RUNE_OUT_MAX && (v.span + 7) / 8 <= HUFF_RUNE_PAY_MAX;
+}
+
+}  // namespace
+
+HuffDevSummary huff_rune_dec_scan(const uint8_t *in, size_t n) { return parse_rune_light(in, n); }
+
+int huff_rune_dec_offer(Ctx &c, std::vector<size_t> &rest, const uint8_t *const *ins, const size_t *lens, const SmallTake &take, size_t *failed) {
+    if (rest.size() < HUFF_RUNE_DEC_GROUP_MIN) return RSN_OK;
+    std::vector<size_t> idx, others;
+    std::vector<uint32_t> expect;
+    for (size_t i : rest) {
+        const HuffDevSummary v = lens[i] <= HUFF_RUNE_STREAM_MAX ? huff_rune_dec_scan(ins[i], lens[i]) : HuffDevSummary{PARSE_NOT_MINE, 0, 0, 0};
+        if (rune_dec_summary_ok(v, lens[i])) { idx.push_back(i); expect.push_back(v.expect); }
+        else others.push_back(i);
+    }
+    if (idx.size() < HUFF_RUNE_DEC_GROUP_MIN) return RSN_OK;
+    std::vector<size_t> handed;
+    const int rc = run_groups<SmallMember>(c, RD_WHAT, idx.size(),
+        [&](size_t k) { const size_t i = idx[k], n = lens[i]; return GroupItem{i, ins[i], n, huff_dec_in_slot(n), huff_dec_out_slot(expect[k])}; },
+        [&](SmallMember &m, size_t k, uint8_t *, const MemberSlots &o) { m = SmallMember{o.in, (uint32_t)lens[idx[k]], o.out, o.status}; },
+        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) { return launch_rune_dec(c, s, g, tab, base); },
+        [](const uint32_t *w) { return w[0]; }, take, handed, failed);
+    if (rc) return rc;
+    others.insert(others.end(), handed.begin(), handed.end());
+    std::sort(others.begin(), others.end());
+    rest.swap(others);
+    return RSN_OK;
+}
+
+int huff_rune_dec_offer_dev(Ctx &c, hipStream_t s, std::vector<size_t> &rest, const rsn_dev_member *mem, const DevPlans &plans,
+                            std::vector<size_t> &idx, std::vector<uint32_t> &answers) {
+    idx.clear(); answers.clear();
+    std::vector<size_t> cand;
+    for (size_t i : rest) {
+        const HuffDevSummary *v = plans.of(i);
+        if (v && v->verdict == PARSE_NOT_MINE && mem[i].n <= HUFF_RUNE_STREAM_MAX) cand.push_back(i);
+    }
+    const size_t k = cand.size();
+    if (k < HUFF_RUNE_DEC_GROUP_MIN) return RSN_OK;
+    std::sort(cand.begin(), cand.end());
+    const size_t up = k * sizeof(RunePlanEntry), down = k * sizeof(HuffDevSummary);
+    void *pp, *dp;
+    int rc = pinned_buf(c, up + down, &pp); if (rc) return rc;
+    rc = dev_buf(c, Slot::GD_RUNE_PLANS, up + down, &dp); if (rc) return rc;
+    RunePlanEntry *h_tab = (RunePlanEntry *)pp;
+    HuffDevSummary *h_sum = (HuffDevSummary *)((uint8_t *)pp + up);
+    for (size_t q = 0; q < k; q++) h_tab[q] = RunePlanEntry{(const uint8_t *)mem[cand[q]].d_in, (unsigned long long)mem[cand[q]].n};
+    RunePlanEntry *d_tab = (RunePlanEntry *)dp;
+    HuffDevSummary *d_sum = (HuffDevSummary *)((uint8_t *)dp + up);
+    RSN_HIP(copy_async(d_tab, h_tab, up, hipMemcpyHostToDevice, s));
+    RSN_LAUNCH("huff_dev_rune_plan", k_huff_dev_rune_plan, dim3((uint32_t)k), dim3(RP_T), 0, s, (const RunePlanEntry *)d_tab, d_sum);
+    RSN_HIP(copy_async(h_sum, d_sum, down, hipMemcpyDeviceToHost, s));
+    RSN_HIP(hipStreamSynchronize(s));
+    std::vector<uint32_t> expect;
+    for (size_t q = 0; q < k; q++) {
+        const HuffDevSummary v = h_sum[q];
+        if (v.verdict > PARSE_NOT_MINE) return c.fail(RSN_ERR_DEVICE, "%s: the rune plan kernel left a summary that is none", RD_WHAT);
+        if (rune_dec_summary_ok(v, mem[cand[q]].n)) { idx.push_back(cand[q]); expect.push_back(v.expect); }
+    }
+    if (idx.size() < HUFF_RUNE_DEC_GROUP_MIN) { idx.clear(); return RSN_OK; }
+    {   // the members of the class leave `rest` (both sorted here: idx as cand is)
+        std::vector<size_t> sorted = rest, others;
+        std::sort(sorted.begin(), sorted.end());
+        std::set_difference(sorted.begin(), sorted.end(), idx.begin(), idx.end(), std::back_inserter(others));
+        rest.swap(others);
+    }
+    return run_groups_dev_sized(c, s, RD_WHAT, idx, mem, [&](size_t q) { return huff_dec_in_slot(mem[idx[q]].n); }, [&](size_t q) { return huff_dec_out_slot(expect[q]); },
+        [&](hipStream_t s2, uint32_t g, const SmallMember *tab, uint8_t *base) { return launch_rune_dec(c, s2, g, tab, base); }, answers);
+}
+
+}  // namespace rsn

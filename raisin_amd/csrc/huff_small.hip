@@ -15,7 +15,8 @@
 // Many streams at once (rsn_huffman_decompress_batch): k_huff_batch_dec, ONE block per stream with k_small_dec's body.
 // Many inputs at once (rsn_huffman_compress_batch): k_huff_batch_enc, ONE block per input of 2 B to 16 KiB that builds its own tree.
 // For byte alphabets (every symbol < 0x80); everything else -- runes, a single symbol,
-// foreign headers, malformed streams and their error texts -- returns 1 and takes the general path, which words the errors.
+// foreign headers, malformed streams and their error texts -- returns 1 and takes the general path, which words the errors.  (In a
+// batch, runes have grouped kernels of their own behind these: huff_rune.hip to compress, huff_rune_dec.hip to decompress.)
 #include "huff_small_body.h"
 #include "huff_plan_small.h"
 

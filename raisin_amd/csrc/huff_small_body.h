@@ -172,11 +172,17 @@ __device__ __forceinline__ uint32_t byte_of(uint32_t packed, uint32_t j) { retur
 // The decoder of one block.  MULTI: k_small_dec's up to DEC_BLOCKS blocks of one stream, each waiting for the maps of the blocks before it
 // (they are co-resident: 32 blocks).  !MULTI: the whole stream in this one block, which waits for nobody -- the batch kernel's member.
 // PAY_WORDS / OUT_CAP: the stream words and the output bytes one block holds in LDS.
-template <uint32_t PAY_WORDS, uint32_t OUT_CAP, bool MULTI, int DLN>
-__device__ __forceinline__ void small_dec_body(const SmallDecArgs &a, uint32_t *s_pay /*[PAY_WORDS]*/, uint8_t *s_out /*[OUT_CAP + 32], 16-aligned*/) {
+// What the rune decoder (huff_rune_dec.hip) needs beside that: CHILD_MAX entries of `child` (the byte alphabets' 256 are a.child; a tree of
+// 256 leaves has 510) and !STORE -- the decoded symbols stay in s_out[0 ..) for the caller, nothing is stored to a.hout and no status word
+// is written.  Returns the symbols this block decoded, DEC_BODY_BACK where the stream is not for the lane maps (STORE: status 1 is out).
+constexpr uint32_t DEC_BODY_BACK = 0xFFFFFFFFu;
+template <uint32_t PAY_WORDS, uint32_t OUT_CAP, bool MULTI, int DLN, uint32_t CHILD_MAX, bool STORE>
+__device__ __forceinline__ uint32_t lane_dec_body(const SmallDecArgs &a, const uint16_t *child /*[a.n_child]*/, uint32_t *s_pay /*[PAY_WORDS]*/, uint8_t *s_out /*[OUT_CAP + 32], 16-aligned*/) {
     constexpr int DTN = DLN + 64;                             // the lanes and the wavefront of the block's first lane
+    constexpr int PERC = (CHILD_MAX + DTN - 1) / DTN;         // entries of child[] a thread loads
+    static_assert(STORE || !MULTI, "the symbols stay in LDS only where one block holds the whole stream");
     __shared__ uint32_t s_lut[1u << DEC_K];                   // byte | second byte << 8 | length << 16 | length of both << 21 | two << 26, or 0x80000000 | internal node reached after K bits
-    __shared__ uint16_t s_child[256];
+    __shared__ uint16_t s_child[CHILD_MAX];
     __shared__ uint32_t s_st[DLN], s_ex[DLN], s_n[DLN];          // per lane: its starts (offsets from its subsequence's first bit, a byte each), the exits that belong to them (offsets from the next subsequence's first bit), their number
     __shared__ uint32_t s_exmask;                             // ... the exits that occur among them, a bit each
     __shared__ uint32_t s_ex32[32], s_cn32[32];               // the block's first lane: exit and symbols for every start in its first 32 bits
@@ -192,10 +198,13 @@ __device__ __forceinline__ void small_dec_body(const SmallDecArgs &a, uint32_t *
     {   // every load of the staging in flight at once (the bytes are in host memory, a round trip is microseconds); the table meanwhile
         constexpr int PER = (PAY_WORDS + DTN - 1) / DTN;
         uint32_t v[PER];
-        const uint32_t ch = tid < a.n_child ? a.child[tid] : 0u;               // (asked for first: the table is built while the stream's words are on their way)
+        uint32_t ch[PERC];                                                     // (asked for first: the table is built while the stream's words are on their way)
+#pragma unroll
+        for (int k = 0; k < PERC; k++) { const uint32_t i = tid + k * DTN; ch[k] = i < a.n_child ? child[i] : 0u; }
 #pragma unroll
         for (int k = 0; k < PER; k++) { const uint32_t i = tid + k * DTN; v[k] = (i < n_words && wlo + i < a.pay_words) ? a.pay[wlo + i] : 0u; }
-        if (tid < a.n_child) s_child[tid] = (uint16_t)ch;
+#pragma unroll
+        for (int k = 0; k < PERC; k++) { const uint32_t i = tid + k * DTN; if (i < a.n_child) s_child[i] = (uint16_t)ch[k]; }
         __syncthreads();
         // window v of K bits: down the tree from the root, two windows a lane at a time (the steps depend on each other, the windows do
         // not); a leaf met with bits to spare sends the walk back to the root for a SECOND codeword: an entry holds up to two
@@ -402,11 +411,14 @@ __device__ __forceinline__ void small_dec_body(const SmallDecArgs &a, uint32_t *
     if (real && tid + 1 == L) s_true[0] = blk_cnt_hint;
     __syncthreads();
     const uint32_t blk_cnt = s_true[0];
-    if (bad || blk_cnt + (MULTI ? 16u : 0u) > OUT_CAP || out_base + blk_cnt > (MULTI ? SMALL_MAX : a.out_max)) { block_done(&a.status[b], 1); return; }
+    if (bad || blk_cnt + (MULTI ? 16u : 0u) > OUT_CAP || out_base + blk_cnt > (MULTI ? SMALL_MAX : a.out_max)) {
+        if constexpr (STORE) block_done(&a.status[b], 1);
+        return DEC_BODY_BACK;
+    }
     const uint32_t shift = out_base & 15;                                       // LDS byte i + shift <-> output byte out_base + i: 16-byte units line up
     if (real) emit_path(s_pay, s_lut, s_child, a.K, end, my_lo + my_start, my_cnt, s_out + my_at + shift);
     __syncthreads();
-    {   // whole 16-byte units as they are; the first and the last are shared with the neighbours: their bytes one by one
+    if constexpr (STORE) {   // whole 16-byte units as they are; the first and the last are shared with the neighbours: their bytes one by one
         const uint32_t lo = shift, hi = shift + blk_cnt;                        // LDS byte range
         uint8_t *dst = a.hout + (out_base - shift);
         for (uint32_t u = tid; u * 16 < hi; u += DTN) {
@@ -414,9 +426,15 @@ __device__ __forceinline__ void small_dec_body(const SmallDecArgs &a, uint32_t *
             if (u0 >= lo && u1 <= hi) *reinterpret_cast<uint4 *>(dst + u0) = *reinterpret_cast<const uint4 *>(s_out + u0);
             else for (uint32_t x = max(u0, lo); x < min(u1, hi); x++) dst[x] = s_out[x];
         }
+        if (tid == 0 && b + 1 == n_blk) a.status[MULTI ? DEC_BLOCKS : 1u] = out_base + blk_cnt;
+        block_done(&a.status[b], 0);
     }
-    if (tid == 0 && b + 1 == n_blk) a.status[MULTI ? DEC_BLOCKS : 1u] = out_base + blk_cnt;
-    block_done(&a.status[b], 0);
+    return blk_cnt;
+}
+// the byte alphabets' decoder: the tree in the arguments, the bytes to a.hout, the status words written
+template <uint32_t PAY_WORDS, uint32_t OUT_CAP, bool MULTI, int DLN>
+__device__ __forceinline__ void small_dec_body(const SmallDecArgs &a, uint32_t *s_pay /*[PAY_WORDS]*/, uint8_t *s_out /*[OUT_CAP + 32], 16-aligned*/) {
+    (void)lane_dec_body<PAY_WORDS, OUT_CAP, MULTI, DLN, 256, true>(a, a.child, s_pay, s_out);
 }
 
 // ---------------------------------------------------------------- compress, many members in one launch (the batch call)

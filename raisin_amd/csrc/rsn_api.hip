@@ -1196,9 +1196,12 @@ struct ShardSync : FirstFailure {
 // any failure every outs[i] is NULL and the answer is the lowest-index failing member's code, its message prefixed "member <i>: ".
 // `rows`: the layer's and direction's classes (codecs.h), run in their order; `single(i, small)`: the single call for member i (small =
 // false: the member was handed back by a grouped kernel whose body the single call's small path shares).
-template <class Single>
+// `behind(c, rest, take, &failed)`: a class behind the rows (the Huffman rune decoder, huff_rune_dec.hip) is offered what is left for the
+// single call, sorted, and takes out of it what it ran grouped; the layers that have none pass no_class_behind.
+static int no_class_behind(Ctx &, std::vector<size_t> &, const SmallTake &, size_t *) { return RSN_OK; }
+template <class Single, class Behind>
 static int small_batch(BatchRows rows, int64_t window, size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens,
-                       bool back_skips_small, Single single) {
+                       bool back_skips_small, Single single, Behind behind) {
     Ctx &c = ctx();
     int rc = batch_args(c, n, ins, lens, outs, out_lens, true, true); if (rc || n == 0) return rc;
     rc = ctx_init(c); if (rc) return rc;                                  // (no device: RSN_ERR_DEVICE -- there is no CPU path)
@@ -1220,6 +1223,11 @@ static int small_batch(BatchRows rows, int64_t window, size_t n, const uint8_t *
     for (size_t i : back) if (back_skips_small) handed[i] = 1;
     rest.insert(rest.end(), back.begin(), back.end());
     std::sort(rest.begin(), rest.end());
+    if (f.at == NONE) {
+        size_t failed = NONE;
+        rc = behind(c, rest, take, &failed);
+        if (rc != RSN_OK) note(f, failed, rc, c.err);
+    }
     while (!rest.empty() && rest.back() > f.at) rest.pop_back();          // (what lies behind a known failure cannot change the answer)
     if (!rest.empty()) {
         std::atomic<size_t> stop{f.at};                                   // the lowest failing member found so far: workers do not go past it
@@ -1255,17 +1263,18 @@ static int small_batch(BatchRows rows, int64_t window, size_t n, const uint8_t *
 
 static int rsn_huffman_decompress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
     return small_batch(batch_classes(BatchLayer::HUFFMAN, false), 0, n, ins, lens, outs, out_lens, false,
-                       [&](size_t i, bool small) { return rsn_huffman_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small); });
+                       [&](size_t i, bool small) { return rsn_huffman_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small); },
+                       [&](Ctx &c, std::vector<size_t> &rest, const SmallTake &take, size_t *failed) { return huff_rune_dec_offer(c, rest, ins, lens, take, failed); });
 }
 
 static int rsn_lzss_compress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, int64_t window, uint8_t **outs, size_t *out_lens) {
     return small_batch(batch_classes(BatchLayer::LZSS, true), window, n, ins, lens, outs, out_lens, true,
-                       [&](size_t i, bool small) { return rsn_lzss_compress_impl(ins[i], lens[i], window, &outs[i], &out_lens[i], small); });
+                       [&](size_t i, bool small) { return rsn_lzss_compress_impl(ins[i], lens[i], window, &outs[i], &out_lens[i], small);  }, no_class_behind);
 }
 
 static int rsn_lzss_decompress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
     return small_batch(batch_classes(BatchLayer::LZSS, false), 0, n, ins, lens, outs, out_lens, true,
-                       [&](size_t i, bool small) { return rsn_lzss_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small); });
+                       [&](size_t i, bool small) { return rsn_lzss_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small);  }, no_class_behind);
 }
 
 // ---- the arithmetic codec (arith.hip): the single call is a batch of one -- every member goes through the same two kernels
@@ -1402,6 +1411,12 @@ static int layer_batch_run(Ctx &c, hipStream_t s, const BatchDevLayer &layer, bo
         if (rc) return fails(rc, idx[0]);
         settle(idx);
         rest.insert(rest.end(), runes.begin(), runes.end());
+    }
+    if (planned && !enc) {   // (huff_rune_dec.hip: the rune decoder behind the rows -- a second plan launch over what the first refused, when the call holds enough of it)
+        std::vector<size_t> idx;
+        rc = huff_rune_dec_offer_dev(c, s, rest, mem, plans, idx, answers);
+        if (rc) return fails(rc, idx.empty() ? (rest.empty() ? 0 : *std::min_element(rest.begin(), rest.end())) : idx[0]);
+        settle(idx);
     }
     std::sort(rest.begin(), rest.end());
     for (size_t i : rest) {

@@ -91,6 +91,8 @@ enum class Slot : int {
     LB_XB = 52,         // ... and of those that outgrew theirs in LB_B [layers_batch]
     LB_VERIFY = 53,     // batch round trip (rsn_api.hip: roundtrip_batch_flow): a run's verify table, behind it the stats block -- the members'
                         //   first-difference words and histograms (roundtrip_batch_layout.h) [roundtrip_batch]
+    GD_RUNE_PLANS = 54, // Huffman decompress batch on device buffers (huff_rune_dec.hip): the rune candidates' table entries and their summaries -- written by
+                        //   k_huff_dev_rune_plan, read by the host once; the call's gate gives it back with the plan table [huff_dev]
 };
 constexpr int RING = 3;                                                  // the batch pipeline's depth: RING inputs, RING segments
 constexpr Slot ring_in(int r) { return (Slot)((int)Slot::RING_IN0 + r); }
@@ -116,7 +118,7 @@ constexpr unsigned long long LAYERED_CALL = HOST_CALL | LAYERED;
 constexpr unsigned long long ARITH = slot_mask(S::AR_STATE, S::AR_RAW);   // the arithmetic codec's own: what its device-buffer calls' gate gives back
 constexpr unsigned long long ARITH_HOST = STAGING | ARITH;                // ... and its host-buffer calls', which stage through the staging pair
 constexpr unsigned long long GROUP_DEV = slot_mask(S::GD_STAGE, S::GD_LENS);   // the grouped kernels' staging on the device: what a class's run of the batch calls on device buffers gives back
-constexpr unsigned long long HUFF_DEV_PLANS = slot_mask(S::GD_PLANS);          // the plan table outlives the classes' runs: the call's own gate gives it back, never a class's
+constexpr unsigned long long HUFF_DEV_PLANS = slot_mask(S::GD_PLANS, S::GD_RUNE_PLANS);          // the plan table outlives the classes' runs: the call's own gate gives it back, never a class's
 constexpr unsigned long long LAYERS_BATCH = slot_mask(S::LB_STAGE, S::LB_A, S::LB_B, S::LB_XA, S::LB_XB);   // the layered batch calls' own
 constexpr unsigned long long LAYERS_BATCH_CALL = LZSS_ENC | LAYERS_BATCH;      // ... and what their gate gives back: the single calls that run inside a step leave the LZSS codecs' scratch
 constexpr unsigned long long ROUNDTRIP_BATCH = slot_mask(S::LB_VERIFY);        // the batch round trip's own: the verify table and the stats block
@@ -146,7 +148,7 @@ struct Ctx {
     std::vector<hipEvent_t> free_events;
 
     struct Buf { void *p = nullptr; size_t cap = 0; unsigned long long gen = 0; };   // gen: process-unique number of this allocation (dev_buf) -- an address can come back with other contents
-    enum { N_BUFS = (int)Slot::LB_VERIFY + 1 };   // (the table above)
+    enum { N_BUFS = (int)Slot::GD_RUNE_PLANS + 1 };   // (the table above)
     Buf bufs[N_BUFS];
     Buf &buf(Slot k) { return bufs[(int)k]; }
     void *pinned = nullptr; size_t pinned_cap = 0;

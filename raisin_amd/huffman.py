@@ -52,15 +52,23 @@ MID_GROUP_MIN = 4
 # The rune class of the compress batch calls (csrc/codecs.h HUFF_RUNE_SYMS_MAX / HUFF_RUNE_GROUP_MIN; csrc/huff_rune.hip): chunks
 # of at most BATCH_COMPRESS_INPUT_MAX bytes that hold a byte >= 0x80 -- UTF-8 text, or no UTF-8 at all -- go a workgroup each through one
 # launch per group when a call holds at least RUNE_GROUP_MIN of them; a chunk with more than RUNE_SYMS_MAX distinct runes, or with one, takes
-# the single call's path inside the batch, as every such chunk does in a call with fewer.  Decompress has no such class yet.
+# the single call's path inside the batch, as every such chunk does in a call with fewer.
+# The way back (csrc/codecs.h HUFF_RUNE_DEC_GROUP_MIN, csrc/group_layout.h HUFF_RUNE_OUT_MAX / HUFF_RUNE_PAY_MAX; csrc/huff_rune_dec.hip): streams
+# whose header names a rune >= 0x80, at most RUNE_SYMS_MAX distinct runes, and promises at most RUNE_OUT_MAX bytes from at most RUNE_PAY_MAX
+# bytes of payload go a workgroup each through one launch per group when a decompress batch holds at least RUNE_DEC_GROUP_MIN of them; the
+# others take the single call's path inside the batch.  Every stream the rune class above writes is one of them.
 RUNE_SYMS_MAX = 256
 RUNE_GROUP_MIN = 16
+RUNE_OUT_MAX = 16384
+RUNE_PAY_MAX = 18432
+RUNE_DEC_GROUP_MIN = 16
 
 
 def DecompressBatch(streams):
     """Decompress(stream) for every stream of the list in one call (rsn_huffman_decompress_batch): small streams many to a launch, a
     workgroup each; streams of up to MID_PAY_MAX bytes of payload that decode to at most MID_OUT_MAX bytes likewise (csrc/huff_mid.hip)
-    when the call holds at least MID_GROUP_MIN of them; the rest through the single call's path.  Each result equals Decompress(stream); a failing stream raises for the
+    when the call holds at least MID_GROUP_MIN of them; streams of a rune alphabet that decode to at most RUNE_OUT_MAX bytes likewise
+    (csrc/huff_rune_dec.hip) when it holds at least RUNE_DEC_GROUP_MIN of them; the rest through the single call's path.  Each result equals Decompress(stream); a failing stream raises for the
     whole list (the message names the lowest failing index: "member <i>: ...")."""
     return _lib.call_batch(_lib.lib().rsn_huffman_decompress_batch, streams)
 
