@@ -365,6 +365,46 @@ RSN_API int rsn_layers_roundtrip_batch(size_t n, const uint8_t *const *ins, cons
 RSN_API int rsn_layers_roundtrip_batch_dev(size_t n, const rsn_dev_member *members, const int *layers, size_t n_layers,
                                            rsn_roundtrip_member *res, uint32_t *hists, void *stream);
 
+/* ---- batch suite ---------------------------------------------------------
+ * The reference's whole benchmark loop in one call: MANY members under SEVERAL layer lists (files x algorithm lists, then the best list
+ * per file: ai/helpers/compressor.py:89-108 and ai/helpers/files.py:67-78; engine.BenchmarkSuite, engine.go:213-309), with everything the
+ * lists have in common done once.  lists[l] is a layer list in compress order under rsn_layers_compress_batch's rules; at
+ * most RSN_SUITE_LISTS_MAX lists.  `res` holds n_lists * n rows, list-major: for every list l that succeeds, res[l * n + i] equals, field
+ * for field, res[i] of rsn_layers_roundtrip_batch(n, ins, lens, lists[l].layers, lists[l].n_layers, ...) -- of rsn_layers_roundtrip_batch_dev
+ * for the device form.  `hists_original` is NULL or n * 256 counters, `hists_decompressed` NULL or n_lists * n * 256, list-major:
+ * hists_original[256 * i .. + 256) and hists_decompressed[256 * (l * n + i) .. + 256) are the two halves of that call's
+ * hists[512 * i .. + 512).  hists_original is complete when at least one list succeeded.
+ * What is shared: the lists form a prefix tree over their layers.  Per run (the layered batch calls' runs; RSN_LAYERS_BATCH_BUDGET applies,
+ * the outputs that are kept counted in) the members are staged and go up once (host form) or are read where they lie (device form), every
+ * distinct non-empty prefix is compressed once -- [lzss] and [lzss, huffman] run the LZSS encoder once -- and the originals' bytes are
+ * counted once.  The decompress passes and the compare are per list: a Huffman layer is lossy on bytes that are not UTF-8, so two lists'
+ * streams are not assumed equal on the way back.  Of equal lists one is run and its rows are copied.
+ * best: NULL or n entries; best[i] is the index of the list with the smallest compressed_n for member i among the lists that succeeded,
+ * the lowest index among equals (best_result compares ratios with a strict `<` and does not look at `lossless`); UINT32_MAX when no list
+ * succeeded.  It is computed on the host from the rows.
+ * Arguments, all checked before a device is looked for (RSN_ERR_ARG, every row zeroed), in this order: n == 0 returns RSN_OK before
+ * anything else is looked at; the arrays and members as in rsn_layers_roundtrip_batch / _dev (the device form's d_out and out_cap are
+ * reserved: NULL and 0; the call writes no caller memory on the device); n_lists == 0 returns RSN_OK with nothing written; a null `lists`
+ * or `res`; n_lists > RSN_SUITE_LISTS_MAX; then every list as in rsn_layers_compress, the message prefixed "list <l>: " -- for example
+ * "list 1: layer 1: unknown layer id 3".  Without a device: RSN_ERR_DEVICE.
+ * Failures are per list: the reference's loop catches a failure per file and algorithm and goes on (compressor.py:96-100).  A list fails
+ * exactly when rsn_layers_roundtrip_batch fails for it alone, with that call's code -- the earliest step's lowest member, however the
+ * members were cut into runs, and RSN_ERR_LIMIT for a length above UINT32_MAX -- and only its own rows are zeroed; its
+ * hists_decompressed rows are unspecified.  Every other list's rows are complete and valid.  list_rc is NULL or n_lists codes:
+ * list_rc[l] is the code of list l (RSN_OK: it succeeded).  The call returns RSN_OK when every list succeeded, otherwise the code of
+ * the failing list of the lowest index, and rsn_last_error() reads "list <l>: " followed by that call's message.
+ * A failure of the call as a whole -- an argument, no device, an allocation, anything thrown -- leaves every row zeroed and does not write
+ * list_rc or best: a caller that fills list_rc with a value that is no code beforehand tells the two apart.
+ * The device form queues its work on `stream` (NULL = the thread's own), which is synchronised before the call returns. */
+#define RSN_SUITE_LISTS_MAX 16
+typedef struct { const int *layers; size_t n_layers; } rsn_layer_list;   /* compress order; rsn_layers_compress_batch's rules */
+RSN_API int rsn_layers_suite_batch(size_t n, const uint8_t *const *ins, const size_t *lens, size_t n_lists, const rsn_layer_list *lists,
+                                   rsn_roundtrip_member *res, int *list_rc, uint32_t *hists_original, uint32_t *hists_decompressed,
+                                   uint32_t *best);
+RSN_API int rsn_layers_suite_batch_dev(size_t n, const rsn_dev_member *members, size_t n_lists, const rsn_layer_list *lists,
+                                       rsn_roundtrip_member *res, int *list_rc, uint32_t *hists_original,
+                                       uint32_t *hists_decompressed, uint32_t *best, void *stream);
+
 /* ---- measurement --------------------------------------------------------
  * When enabled, every kernel launch of the calling thread is bracketed by HIP
  * events on the launch stream; rsn_prof_get() reports per-kernel totals since

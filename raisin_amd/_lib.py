@@ -44,6 +44,11 @@ class RoundTripMember(ctypes.Structure):
                 ("first_difference", ctypes.c_uint64), ("lossless", ctypes.c_int)]
 
 
+class LayerList(ctypes.Structure):
+    """rsn_layer_list (include/rsn.h): one layer list of the batch suite, in compress order"""
+    _fields_ = [("layers", ctypes.POINTER(ctypes.c_int)), ("n_layers", ctypes.c_size_t)]
+
+
 class DevMember(ctypes.Structure):
     """rsn_dev_member (include/rsn.h): one member of a batch call on device buffers"""
     _fields_ = [("d_in", ctypes.c_void_p), ("n", ctypes.c_size_t), ("d_out", ctypes.c_void_p), ("out_cap", ctypes.c_size_t)]
@@ -68,6 +73,7 @@ SYMBOLS = [
     "rsn_huffman_compress_batch_dev", "rsn_huffman_decompress_batch_dev",
     "rsn_layers_compress_batch", "rsn_layers_decompress_batch", "rsn_layers_compress_batch_dev", "rsn_layers_decompress_batch_dev",
     "rsn_layers_roundtrip_batch", "rsn_layers_roundtrip_batch_dev",
+    "rsn_layers_suite_batch", "rsn_layers_suite_batch_dev",
 ]
 
 
@@ -151,6 +157,9 @@ def lib():
     rmp, u32p = ctypes.POINTER(RoundTripMember), ctypes.POINTER(ctypes.c_uint32)
     L.rsn_layers_roundtrip_batch.argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, ip, sz, rmp, u32p]
     L.rsn_layers_roundtrip_batch_dev.argtypes = [sz, mp, ip, sz, rmp, u32p, vp]
+    llp, i32p = ctypes.POINTER(LayerList), ctypes.POINTER(ctypes.c_int)
+    L.rsn_layers_suite_batch.argtypes = [sz, ctypes.POINTER(ctypes.c_char_p), szp, sz, llp, rmp, i32p, u32p, u32p, u32p]
+    L.rsn_layers_suite_batch_dev.argtypes = [sz, mp, sz, llp, rmp, i32p, u32p, u32p, u32p, vp]
     L.rsn_prof_copied.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     L.rsn_prof_copied.restype = None
     _lib = L

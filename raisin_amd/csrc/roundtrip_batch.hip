@@ -4,6 +4,7 @@
 // histograms (engine.go:367-370, :412-415, :424) -- for all members in ONE launch.  The flow itself is rsn_api.hip's roundtrip_batch_flow.
 #include "codecs.h"
 #include "roundtrip_batch_layout.h"
+#include "suite_layout.h"
 
 namespace rsn {
 
@@ -25,16 +26,20 @@ static_assert(RB_TILE % (16 * VF_THREADS) == 0 && VF_UNITS % 4 == 0, "a whole ti
 // Output: words[member] and hists[512 * member ..) were zeroed by ONE memset in front of the launch.  The block of a member of one tile owns
 // the member's row and stores it; the blocks of a larger member add their non-zero bins and raise the word -- the COMPLEMENT of the
 // offset, so the lowest offset wins and zero stays "nothing differs".
-template <int COPIES>
+// ORIG = false is the batch suite's second instance (rsn_layers_suite_batch): a run's first list has counted the originals, so
+// every further list compares as above and counts the decompressed side alone -- no LDS counters and no atomics for the original, and
+// hists[256 * member ..) holds the one histogram (suite_layout.h: suite_dec_layout).  ORIG = true is the instance as it has been.
+template <int COPIES, bool ORIG = true>
 __global__ __launch_bounds__(VF_THREADS) void k_members_verify(const RbEntry *__restrict__ tab, unsigned long long *__restrict__ words, uint32_t *__restrict__ hists) {
     static_assert(COPIES >= 1 && COPIES <= 16 && (COPIES & (COPIES - 1)) == 0, "copy = lane % COPIES; both histograms within the 64 KiB a block may hold");
-    __shared__ uint32_t h[2][256 * COPIES];
+    constexpr int SIDES = ORIG ? 2 : 1, DEC = SIDES - 1;                 // the histograms in LDS, and which of them is the decompressed side's
+    __shared__ uint32_t h[SIDES][256 * COPIES];
     __shared__ uint32_t s_min;
     const RbEntry e = tab[blockIdx.x];
     const int tid = threadIdx.x;
     const uint32_t copy = tid & (COPIES - 1);
     const bool counting = hists != nullptr;                              // (the same for every thread of the launch)
-    if (counting) for (int i = tid; i < 2 * 256 * COPIES; i += VF_THREADS) (&h[0][0])[i] = 0;
+    if (counting) for (int i = tid; i < SIDES * 256 * COPIES; i += VF_THREADS) (&h[0][0])[i] = 0;
     if (tid == 0) s_min = VF_NONE;
     __syncthreads();
 
@@ -75,7 +80,7 @@ __global__ __launch_bounds__(VF_THREADS) void k_members_verify(const RbEntry *__
             for (int k = 0; k < 4; k++) { a[k] = po[(k0 + k) * VF_THREADS + tid]; b[k] = pd[(k0 + k) * VF_THREADS + tid]; }
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                if (counting) { add16(h[0], a[k]); add16(h[1], b[k]); }
+                if (counting) { if constexpr (ORIG) add16(h[0], a[k]); add16(h[DEC], b[k]); }
                 const uint32_t at = diff16(a[k], b[k]);
                 if (at < 16 && mine == VF_NONE) mine = (uint32_t)((k0 + k) * VF_THREADS + tid) * 16 + at;
             }
@@ -90,8 +95,8 @@ __global__ __launch_bounds__(VF_THREADS) void k_members_verify(const RbEntry *__
             if (vo) a = po[u];
             if (vd) b = pd[u];
             if (counting) {
-                if (vo == 16) add16(h[0], a); else for (uint32_t j = 0; j < vo; j++) atomicAdd(&h[0][byte_of(a, j) * COPIES + copy], 1u);
-                if (vd == 16) add16(h[1], b); else for (uint32_t j = 0; j < vd; j++) atomicAdd(&h[1][byte_of(b, j) * COPIES + copy], 1u);
+                if constexpr (ORIG) { if (vo == 16) add16(h[0], a); else for (uint32_t j = 0; j < vo; j++) atomicAdd(&h[0][byte_of(a, j) * COPIES + copy], 1u); }
+                if (vd == 16) add16(h[DEC], b); else for (uint32_t j = 0; j < vd; j++) atomicAdd(&h[DEC][byte_of(b, j) * COPIES + copy], 1u);
             }
             const uint32_t at = diff16(a, b), vc = vo < vd ? vo : vd;
             if (at < vc && mine == VF_NONE) mine = 16 * u + at;
@@ -114,18 +119,25 @@ __global__ __launch_bounds__(VF_THREADS) void k_members_verify(const RbEntry *__
 #pragma unroll
         for (int r = 0; r < COPIES; r++) {                               // rotated: the lanes of a group begin at different copies
             const int at = tid * COPIES + ((r + tid) & (COPIES - 1));
-            so += h[0][at]; sd += h[1][at];
+            if constexpr (ORIG) so += h[0][at];
+            sd += h[DEC][at];
         }
-        uint32_t *row = hists + (size_t)e.member * RB_HIST_WORDS;
-        if (alone) { row[tid] = so; row[256 + tid] = sd; }
-        else { if (so) atomicAdd(&row[tid], so); if (sd) atomicAdd(&row[256 + tid], sd); }
+        if constexpr (ORIG) {
+            uint32_t *row = hists + (size_t)e.member * RB_HIST_WORDS;
+            if (alone) { row[tid] = so; row[256 + tid] = sd; }
+            else { if (so) atomicAdd(&row[tid], so); if (sd) atomicAdd(&row[256 + tid], sd); }
+        } else {
+            uint32_t *row = hists + (size_t)e.member * SUITE_HIST_WORDS;
+            if (alone) row[tid] = sd;
+            else if (sd) atomicAdd(&row[tid], sd);
+        }
     }
 }
 
 }  // namespace
 
-int members_verify(Ctx &c, hipStream_t s, const RbEntry *h_tab, size_t tiles, size_t m, bool hists, void *d_slot) {
-    const RbLayout lay = rb_layout(tiles, m, hists);
+// the table checked and sent up, the stats block cleared: what both instances have in front of their launch
+static int verify_prepare(Ctx &c, hipStream_t s, const RbEntry *h_tab, size_t tiles, size_t m, const RbLayout &lay, void *d_slot) {
     if (tiles > 0x7FFFFFFFull || m > 0xFFFFFFFFull) return c.fail(RSN_ERR_LIMIT, "layers: %zu tiles of %zu members to verify in one launch", tiles, m);
     for (size_t t = 0; t < tiles; t++) {
         const RbEntry &e = h_tab[t];
@@ -135,8 +147,25 @@ int members_verify(Ctx &c, hipStream_t s, const RbEntry *h_tab, size_t tiles, si
     uint8_t *d = (uint8_t *)d_slot;
     if (tiles) RSN_HIP(copy_async(d + lay.table, h_tab, tiles * sizeof(RbEntry), hipMemcpyHostToDevice, s));
     RSN_HIP(hipMemsetAsync(d + lay.words, 0, rb_stats_bytes(lay), s));
+    return RSN_OK;
+}
+
+int members_verify(Ctx &c, hipStream_t s, const RbEntry *h_tab, size_t tiles, size_t m, bool hists, void *d_slot) {
+    const RbLayout lay = rb_layout(tiles, m, hists);
+    const int rc = verify_prepare(c, s, h_tab, tiles, m, lay, d_slot); if (rc) return rc;
+    uint8_t *d = (uint8_t *)d_slot;
     if (tiles == 0) return RSN_OK;
     RSN_LAUNCH("members_verify", (k_members_verify<VF_COPIES>), dim3((uint32_t)tiles), dim3(VF_THREADS), 0, s, (const RbEntry *)(d + lay.table),
+               (unsigned long long *)(d + lay.words), hists ? (uint32_t *)(d + lay.hists) : (uint32_t *)nullptr);
+    return RSN_OK;
+}
+
+int members_verify_dec(Ctx &c, hipStream_t s, const RbEntry *h_tab, size_t tiles, size_t m, bool hists, void *d_slot) {
+    const RbLayout lay = suite_dec_layout(tiles, m, hists);
+    const int rc = verify_prepare(c, s, h_tab, tiles, m, lay, d_slot); if (rc) return rc;
+    uint8_t *d = (uint8_t *)d_slot;
+    if (tiles == 0) return RSN_OK;
+    RSN_LAUNCH("members_verify_dec", (k_members_verify<VF_COPIES, false>), dim3((uint32_t)tiles), dim3(VF_THREADS), 0, s, (const RbEntry *)(d + lay.table),
                (unsigned long long *)(d + lay.words), hists ? (uint32_t *)(d + lay.hists) : (uint32_t *)nullptr);
     return RSN_OK;
 }

@@ -5,6 +5,7 @@
 #include "dev_ranges.h"
 #include "layers_batch_layout.h"
 #include "roundtrip_batch_layout.h"
+#include "suite_layout.h"
 #include "group_layout.h"
 #include "rsn_common.h"
 #include "rsn_helpers.h"
@@ -2077,6 +2078,236 @@ static int layers_roundtrip_batch_dev(size_t n, const rsn_dev_member *mem, const
     return roundtrip_batch_flow(c, s, n, nullptr, nullptr, mem, layers, n_layers, res, hists);
 }
 
+// ---- batch suite (rsn.h): the batch round trip of MANY layer lists over the same members -- the reference's benchmark loop,
+// files x algorithm lists -- with everything the lists have in common done once.  The lists form a prefix tree (suite_layout.h); a run
+// stages its members once, walks the tree depth first and compresses every node once -- ONE step of layers_batch_steps, from where the
+// parent's step left the members -- and a list's decompress pass and verify launch start from the node it ends at, as roundtrip_batch_flow's
+// do.  A node with one user writes into the arena a call of that list alone would use at that step; a node with more users (a kept node)
+// into its own slots of LB_KEEP, which the run carves before its first step and no step reuses.  The run's first verify launch is
+// k_members_verify as it has been and counts the originals; every further list's is the instance that counts the decompressed side alone.
+// Every list keeps roundtrip_batch_flow's bookkeeping of its own (the two failures, how far its runs still go, the 32-bit limit), so its
+// answer is the one that call gives for it alone; a node runs while any list through it still goes that far.
+namespace {
+struct SuiteListState { LbFailure fc, fd; size_t limit = 0, big = LB_NONE; };
+int roundtrip_big_failure(Ctx &c, size_t big) {
+    return c.fail(RSN_ERR_LIMIT, "member %zu: a round trip of %zu bytes or more in a batch: the counters are 32 bits (rsn_layers_roundtrip takes one large buffer)", big, (size_t)1 << 32);
+}
+}  // namespace
+
+// The arguments have been checked and res zeroed.  A failure of the call as a whole zeroes every row and leaves list_rc and best alone.
+static int suite_batch_flow(Ctx &c, hipStream_t s, size_t n, const uint8_t *const *ins, const size_t *lens, const rsn_dev_member *mem, size_t n_lists, const rsn_layer_list *lists,
+                            rsn_roundtrip_member *res, int *list_rc, uint32_t *h_orig, uint32_t *h_dec, uint32_t *best) {
+    const bool staged = mem == nullptr, counting = h_orig || h_dec;
+    auto len_of = [&](size_t i) { return staged ? lens[i] : (size_t)mem[i].n; };
+    auto zeroed = [&](int code) { memset(res, 0, n_lists * n * sizeof *res); return code; };
+    const int *lp[RSN_SUITE_LISTS_MAX]; size_t ln[RSN_SUITE_LISTS_MAX];
+    for (size_t l = 0; l < n_lists; l++) { lp[l] = lists[l].layers; ln[l] = lists[l].n_layers; }
+    const SuiteTree tree = suite_tree(lp, ln, n_lists);
+    const size_t V = tree.nodes.size();
+    // under[v]: the lists that are run -- the first of every set of equal lists -- whose path leads through node v; under[SUITE_ROOT]: all that are run
+    std::vector<std::vector<size_t>> under(V);
+    for (size_t v = 0; v < V; v++) {
+        if (tree.nodes[v].ends.empty()) continue;
+        for (size_t u = v;; u = tree.nodes[u].parent) { under[u].push_back(tree.nodes[v].ends[0]); if (u == SUITE_ROOT) break; }
+    }
+    const std::vector<size_t> &ran = under[SUITE_ROOT];
+    auto bound = [](int id, size_t len) { return layer_slot_cap(id, true, len); };
+    const std::vector<LbRun> runs = lb_runs(n, layers_batch_budget(), [&](size_t i) {
+        const size_t len = len_of(i);
+        size_t enc = 0, dec = 0;                                          // (as roundtrip_batch_flow takes them, the largest over the lists)
+        for (size_t l : ran) { enc = std::max(enc, layers_batch_slot(true, lp[l], ln[l], len)); dec = std::max(dec, roundtrip_dec_slot(lp[l], ln[l], len)); }
+        return suite_member_need(staged ? len : 0, enc, dec, suite_keep_bytes(tree, len, bound), len, len, counting);
+    });
+    size_t most = 0;
+    for (const LbRun &r : runs) most = std::max(most, r.bytes);
+    Admission gate(c, slotset::SUITE_BATCH_CALL); gate.admit(most, ADMIT_FROM);
+    std::vector<SuiteListState> ls(n_lists);
+    for (size_t l : ran) ls[l].limit = 2 * ln[l];
+    std::vector<size_t> offs, got, caps;
+    std::vector<const uint8_t *> orig;
+    int rc;
+    auto synced = [&]() { const hipError_t e = hipStreamSynchronize(s); return e == hipSuccess ? RSN_OK : c.fail(RSN_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e)); };
+    for (const LbRun &r : runs) {
+        bool any = false;
+        for (size_t l : ran) any = any || ln[l] == 0 || ls[l].limit > 0;
+        if (!any) break;                                                  // (every list has failed at its first step: no earlier failure is left to find)
+        const size_t m = r.hi - r.lo;
+        LbRunState st0;
+        st0.at.resize(m); st0.len.resize(m); orig.resize(m);
+        if (staged) {                                                     // up, ONCE for all lists: as layers_batch_host; the inputs stay in LB_STAGE to the end of the run
+            rc = layers_batch_stage(c, s, ins + r.lo, lens + r.lo, m, offs, st0); if (rc) return zeroed(rc);
+        } else {
+            for (size_t i = 0; i < m; i++) { st0.at[i] = (const uint8_t *)mem[r.lo + i].d_in; st0.len[i] = mem[r.lo + i].n; }
+        }
+        for (size_t i = 0; i < m; i++) orig[i] = st0.at[i];
+        got.assign(m, 0);
+        // the kept nodes' slots: node-major in LB_KEEP, a slot a member of the compress bounds applied in turn from the root
+        std::vector<std::vector<size_t>> ncap(V, std::vector<size_t>(m));
+        std::vector<std::vector<rsn_dev_member>> keep(V);
+        for (size_t i = 0; i < m; i++) {
+            suite_keep_bytes(tree, st0.len[i], bound, &caps);
+            for (size_t v = 0; v < V; v++) ncap[v][i] = caps[v];
+        }
+        {
+            size_t total = 0;
+            std::vector<size_t> base(V, 0);
+            std::vector<std::vector<size_t>> koffs(V);
+            for (size_t v = 0; v < V; v++) if (tree.nodes[v].kept) { base[v] = total; total += lb_arena(ncap[v].data(), m, koffs[v]); }
+            void *kp = nullptr;
+            if (total) { rc = dev_buf(c, Slot::LB_KEEP, total, &kp); if (rc) return zeroed(rc); }
+            for (size_t v = 0; v < V; v++) {
+                if (!tree.nodes[v].kept) continue;
+                keep[v].resize(m);
+                for (size_t i = 0; i < m; i++) keep[v][i] = rsn_dev_member{nullptr, 0, (uint8_t *)kp + base[v] + koffs[v][i], ncap[v][i]};
+            }
+        }
+        bool verified = false;                                            // has a list of this run been through the verify launch: the originals are counted
+        // list l from the node it ends at (`in`: where that node left the members): the decompress pass and the verify launch
+        auto finish = [&](size_t l, const LbRunState &in) -> int {
+            SuiteListState &q = ls[l];
+            const size_t L = ln[l];
+            if (L && q.limit <= L) return RSN_OK;                         // (the list has failed in or right behind its compress pass: the run only looked for an earlier failure)
+            LbRunState st;
+            st.at = in.at; st.len = in.len;
+            const size_t before = q.fd.step;
+            int rc = layers_batch_steps(c, s, false, lp[l], L, q.limit - L, L & 1, r.lo, m, nullptr, st, got.data(), q.fd);
+            if (rc && q.fd.step == before) return rc;
+            if (rc) { q.limit = L + q.fd.step; return RSN_OK; }
+            if (q.limit < 2 * L || q.big != LB_NONE) return RSN_OK;
+            size_t tiles = 0;
+            for (size_t i = 0; i < m; i++) {
+                if (!rb_fits(len_of(r.lo + i)) || !rb_fits(st.len[i])) { q.big = r.lo + i; return RSN_OK; }
+                tiles += rb_tiles(len_of(r.lo + i), st.len[i]);
+            }
+            const bool first = !verified, cnt = first ? counting : h_dec != nullptr;
+            const RbLayout lay = first ? rb_layout(tiles, m, cnt) : suite_dec_layout(tiles, m, cnt);
+            void *hp, *dp;
+            rc = pinned_buf(c, lay.bytes + 16, &hp); if (rc) return rc;
+            rc = dev_buf(c, Slot::LB_VERIFY, lay.bytes + 16, &dp); if (rc) return rc;
+            RbEntry *tab = (RbEntry *)((uint8_t *)hp + lay.table);
+            tiles = 0;
+            for (size_t i = 0; i < m; i++)
+                for (size_t t = 0, k = rb_tiles(len_of(r.lo + i), st.len[i]); t < k; t++)
+                    tab[tiles++] = RbEntry{orig[i], st.at[i], (uint32_t)len_of(r.lo + i), (uint32_t)st.len[i], (uint32_t)i, (uint32_t)t};
+            rc = first ? members_verify(c, s, tab, tiles, m, cnt, dp) : members_verify_dec(c, s, tab, tiles, m, cnt, dp);
+            if (rc) return rc;
+            {
+                const size_t down = rb_stats_bytes(lay);
+                const hipError_t e = copy_async((uint8_t *)hp + lay.words, (const uint8_t *)dp + lay.words, down, hipMemcpyDeviceToHost, s);
+                if (e != hipSuccess) return c.fail(RSN_ERR_DEVICE, "the download of %zu bytes failed: %s", down, hipGetErrorString(e));
+            }
+            rc = synced(); if (rc) return rc;
+            verified = true;
+            const unsigned long long *words = (const unsigned long long *)((const uint8_t *)hp + lay.words);
+            for (size_t i = 0; i < m; i++) {
+                rsn_roundtrip_member &o = res[l * n + r.lo + i];
+                o.original_n = len_of(r.lo + i); o.compressed_n = in.len[i]; o.decompressed_n = st.len[i];
+                o.first_difference = words[i] ? ~words[i] : (o.original_n == o.decompressed_n ? UINT64_MAX : std::min(o.original_n, o.decompressed_n));
+                o.lossless = o.first_difference == UINT64_MAX;
+            }
+            if (!cnt) return RSN_OK;
+            const uint32_t *rows = (const uint32_t *)((const uint8_t *)hp + lay.hists);
+            uint32_t *dec_rows = h_dec ? h_dec + (l * n + r.lo) * SUITE_HIST_WORDS : nullptr;
+            if (!first) { memcpy(dec_rows, rows, m * SUITE_HIST_BYTES); return RSN_OK; }
+            for (size_t i = 0; i < m; i++) {                              // the round trip's rows: the original's half, then the decompressed half
+                if (h_orig) memcpy(h_orig + (r.lo + i) * SUITE_HIST_WORDS, rows + i * RB_HIST_WORDS, SUITE_HIST_BYTES);
+                if (dec_rows) memcpy(dec_rows + i * SUITE_HIST_WORDS, rows + i * RB_HIST_WORDS + SUITE_HIST_WORDS, SUITE_HIST_BYTES);
+            }
+            return RSN_OK;
+        };
+        // node v and everything below it; `in`: where v's step left the members
+        std::function<int(size_t, const LbRunState &)> walk = [&](size_t v, const LbRunState &in) -> int {
+            const SuiteNode &node = tree.nodes[v];
+            if (!node.ends.empty()) { const int rc = finish(node.ends[0], in); if (rc) return rc; }
+            const size_t step = node.depth;                               // a child's compress step, counted as a call of one of its lists alone counts it
+            for (size_t kid : node.kids) {
+                bool wanted = false;
+                for (size_t l : under[kid]) wanted = wanted || ls[l].limit > step;
+                if (!wanted) continue;
+                const SuiteNode &k = tree.nodes[kid];
+                LbRunState st;
+                st.at = in.at; st.len = in.len;
+                LbFailure f;
+                int rc = layers_batch_steps(c, s, true, &k.layer, 1, 1, step & 1, r.lo, m, k.kept ? keep[kid].data() : nullptr, st, got.data(), f);
+                if (rc && f.step == LB_NONE) return rc;
+                if (rc) {                                                 // the step's failure is every list's that still went this far
+                    f.step = step;
+                    for (size_t l : under[kid]) if (ls[l].limit > step) { ls[l].fc = f; ls[l].limit = step; }
+                    continue;
+                }
+                if (st.tight != LB_NONE) return c.fail(RSN_ERR_DEVICE, "layers: internal error: member %zu outgrew the kept slot of its compress bound", st.tight);
+                rc = walk(kid, st); if (rc) return rc;
+            }
+            return RSN_OK;
+        };
+        rc = walk(SUITE_ROOT, st0); if (rc) return zeroed(rc);
+    }
+    // every list's answer, as roundtrip_batch_flow ends
+    std::vector<int> code(n_lists, RSN_OK);
+    std::vector<std::string> msg(n_lists);
+    for (size_t l : ran) {
+        const SuiteListState &q = ls[l];
+        if (q.fc.step != LB_NONE) code[l] = layers_batch_failure(c, true, lp[l], ln[l], q.fc);
+        else if (q.fd.step != LB_NONE) code[l] = layers_batch_failure(c, false, lp[l], ln[l], q.fd);
+        else if (q.big != LB_NONE) code[l] = roundtrip_big_failure(c, q.big);
+        if (code[l]) { msg[l] = c.err; memset(res + l * n, 0, n * sizeof *res); }
+    }
+    for (const SuiteNode &node : tree.nodes)                             // equal lists: the rows of the one that ran
+        for (size_t k = 1; k < node.ends.size(); k++) {
+            const size_t from = node.ends[0], to = node.ends[k];
+            code[to] = code[from]; msg[to] = msg[from];
+            memcpy(res + to * n, res + from * n, n * sizeof *res);
+            if (h_dec && !code[from]) memcpy(h_dec + to * n * SUITE_HIST_WORDS, h_dec + from * n * SUITE_HIST_WORDS, n * SUITE_HIST_BYTES);
+        }
+    if (list_rc) for (size_t l = 0; l < n_lists; l++) list_rc[l] = code[l];
+    if (best)
+        for (size_t i = 0; i < n; i++)
+            best[i] = suite_best(n_lists, [&](size_t l) { return code[l] == RSN_OK; }, [&](size_t l) { return res[l * n + i].compressed_n; });
+    for (size_t l = 0; l < n_lists; l++) if (code[l]) return c.fail(code[l], "list %zu: %s", l, msg[l].c_str());
+    return RSN_OK;
+}
+
+// the layer lists of a suite call, behind the arrays and members: a null array, too many lists, then every list as layers_check takes it
+static int suite_lists_check(Ctx &c, size_t n_lists, const rsn_layer_list *lists, const rsn_roundtrip_member *res) {
+    if (!lists || !res) return c.fail(RSN_ERR_ARG, "null argument");
+    if (n_lists > RSN_SUITE_LISTS_MAX) return c.fail(RSN_ERR_ARG, "%zu layer lists: at most %d in one call", n_lists, RSN_SUITE_LISTS_MAX);
+    for (size_t l = 0; l < n_lists; l++) {
+        const int rc = layers_check(c, lists[l].layers, lists[l].n_layers);
+        if (rc) { const std::string m = c.err; return c.fail(rc, "list %zu: %s", l, m.c_str()); }
+    }
+    return RSN_OK;
+}
+
+static int layers_suite_batch_host(size_t n, const uint8_t *const *ins, const size_t *lens, size_t n_lists, const rsn_layer_list *lists, rsn_roundtrip_member *res, int *list_rc,
+                                   uint32_t *h_orig, uint32_t *h_dec, uint32_t *best) {
+    Ctx &c = ctx();
+    if (n == 0) return RSN_OK;
+    if (res && n_lists) memset(res, 0, n_lists * n * sizeof *res);
+    if (!ins || !lens) return c.fail(RSN_ERR_ARG, "null argument");
+    for (size_t i = 0; i < n; i++) if (!ins[i] && lens[i]) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
+    if (n_lists == 0) return RSN_OK;
+    int rc = suite_lists_check(c, n_lists, lists, res); if (rc) return rc;
+    rc = ctx_init(c); if (rc) return rc;                                  // (no device: RSN_ERR_DEVICE -- there is no CPU path)
+    return suite_batch_flow(c, c.own_stream, n, ins, lens, nullptr, n_lists, lists, res, list_rc, h_orig, h_dec, best);
+}
+
+static int layers_suite_batch_dev(size_t n, const rsn_dev_member *mem, size_t n_lists, const rsn_layer_list *lists, rsn_roundtrip_member *res, int *list_rc,
+                                  uint32_t *h_orig, uint32_t *h_dec, uint32_t *best, void *stream) {
+    Ctx &c = ctx(); hipStream_t s;
+    if (n == 0) return RSN_OK;
+    if (res && n_lists) memset(res, 0, n_lists * n * sizeof *res);
+    if (!mem) return c.fail(RSN_ERR_ARG, "null argument");
+    for (size_t i = 0; i < n; i++) {                                      // (rsn_layers_roundtrip_batch_dev's rules)
+        if (!mem[i].d_in && mem[i].n) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
+        if (mem[i].d_out || mem[i].out_cap) return c.fail(RSN_ERR_ARG, "member %zu: d_out and out_cap are reserved in a round trip: NULL and 0", i);
+        if ((uintptr_t)mem[i].d_in & 15) return c.fail(RSN_ERR_ARG, "member %zu: layers: device buffers must be 16-byte aligned", i);
+    }
+    if (n_lists == 0) return RSN_OK;
+    int rc = suite_lists_check(c, n_lists, lists, res); if (rc) return rc;
+    rc = dev_prologue(c, stream, &s); if (rc) return rc;
+    return suite_batch_flow(c, s, n, nullptr, nullptr, mem, n_lists, lists, res, list_rc, h_orig, h_dec, best);
+}
+
 static int layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size_t n_layers, rsn_roundtrip_result *res, uint8_t **compressed, size_t *compressed_n) {
     Ctx &c = ctx();
     if (!res || (!in && n) || (compressed && !compressed_n)) return c.fail(RSN_ERR_ARG, "null argument");
@@ -2292,6 +2523,16 @@ int rsn_layers_roundtrip_batch(size_t n, const uint8_t *const *ins, const size_t
 int rsn_layers_roundtrip_batch_dev(size_t n, const rsn_dev_member *members, const int *layers, size_t n_layers, rsn_roundtrip_member *res, uint32_t *hists, void *stream) {
     return guarded_call<int>([&] { return layers_roundtrip_batch_dev(n, members, layers, n_layers, res, hists, stream); },
                              [&](int code, const char *m) { if (res) memset(res, 0, n * sizeof *res); return boundary_error(code, m); });
+}
+int rsn_layers_suite_batch(size_t n, const uint8_t *const *ins, const size_t *lens, size_t n_lists, const rsn_layer_list *lists, rsn_roundtrip_member *res, int *list_rc,
+                           uint32_t *hists_original, uint32_t *hists_decompressed, uint32_t *best) {
+    return guarded_call<int>([&] { return layers_suite_batch_host(n, ins, lens, n_lists, lists, res, list_rc, hists_original, hists_decompressed, best); },
+                             [&](int code, const char *m) { if (res) memset(res, 0, n_lists * n * sizeof *res); return boundary_error(code, m); });
+}
+int rsn_layers_suite_batch_dev(size_t n, const rsn_dev_member *members, size_t n_lists, const rsn_layer_list *lists, rsn_roundtrip_member *res, int *list_rc,
+                               uint32_t *hists_original, uint32_t *hists_decompressed, uint32_t *best, void *stream) {
+    return guarded_call<int>([&] { return layers_suite_batch_dev(n, members, n_lists, lists, res, list_rc, hists_original, hists_decompressed, best, stream); },
+                             [&](int code, const char *m) { if (res) memset(res, 0, n_lists * n * sizeof *res); return boundary_error(code, m); });
 }
 void rsn_prof_copied(uint64_t *h2d_bytes, uint64_t *d2h_bytes) { guarded([&] { if (h2d_bytes) *h2d_bytes = g_copy_count.h2d.load(); if (d2h_bytes) *d2h_bytes = g_copy_count.d2h.load(); return 0; }); }
 void rsn_prof_enable(int on) { guarded([&] { ctx().prof = on != 0; g_copy_count.on.store(on != 0); return 0; }); }

@@ -30,7 +30,7 @@ struct ProfSlot {
 // codec gates that give its block back (E: the LZSS encoder's, D: the LZSS decoder's; X*: released by X's gate though X never allocates
 // it; the masks are below the table).  The gates of the host-buffer calls release what E releases plus the staging pair; the layered
 // calls' gate releases those and its own four slots; the layered batch calls' gate what E releases and its own five; the batch round
-// trip's gate those and its verify slot.
+// trip's gate those and its verify slot; the batch suite's gate those and its keep slot.
 // A slot with two users is shared by convention: every codec call synchronises its stream before it returns, and the calls of one
 // thread -- the layers of a layered call included -- run one after the other, so the two users are never live together.
 // The numbers are fixed: DESIGN 4.8 and comments cite them, and a parked arena is adopted by index.
@@ -93,6 +93,8 @@ enum class Slot : int {
                         //   first-difference words and histograms (roundtrip_batch_layout.h) [roundtrip_batch]
     GD_RUNE_PLANS = 54, // Huffman decompress batch on device buffers (huff_rune_dec.hip): the rune candidates' table entries and their summaries -- written by
                         //   k_huff_dev_rune_plan, read by the host once; the call's gate gives it back with the plan table [huff_dev]
+    LB_KEEP = 55,       // batch suite (rsn_api.hip: suite_batch_flow): a run's kept node outputs -- a slot per kept node of the lists' prefix
+                        //   tree and member (suite_layout.h), written by the node's compress step and read by every user of the node [suite_batch]
 };
 constexpr int RING = 3;                                                  // the batch pipeline's depth: RING inputs, RING segments
 constexpr Slot ring_in(int r) { return (Slot)((int)Slot::RING_IN0 + r); }
@@ -123,6 +125,8 @@ constexpr unsigned long long LAYERS_BATCH = slot_mask(S::LB_STAGE, S::LB_A, S::L
 constexpr unsigned long long LAYERS_BATCH_CALL = LZSS_ENC | LAYERS_BATCH;      // ... and what their gate gives back: the single calls that run inside a step leave the LZSS codecs' scratch
 constexpr unsigned long long ROUNDTRIP_BATCH = slot_mask(S::LB_VERIFY);        // the batch round trip's own: the verify table and the stats block
 constexpr unsigned long long ROUNDTRIP_BATCH_CALL = LAYERS_BATCH_CALL | ROUNDTRIP_BATCH;   // ... and what its gate gives back: both passes are the layered batch calls' steps
+constexpr unsigned long long SUITE_BATCH = slot_mask(S::LB_KEEP);              // the batch suite's own: the kept node outputs
+constexpr unsigned long long SUITE_BATCH_CALL = ROUNDTRIP_BATCH_CALL | SUITE_BATCH;   // ... and what its gate gives back: its passes are the batch round trip's
 // (RING is written out three times: the enumerators, RINGS and this check change together)
 static_assert(ring_in(RING) == Slot::RING_OUT0 && ring_out(RING - 1) == Slot::RING_OUT2, "the ring's slots are RING inputs, then RING segments");
 static_assert(((STAGING | RINGS | LAYERED) & (LZSS_ENC | LZSS_DEC)) == 0, "a codec's gate releases no staging, ring or layered slot: their callers still use them");
@@ -132,6 +136,8 @@ static_assert((GROUP_DEV & (HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | L
 static_assert((HUFF_DEV_PLANS & (GROUP_DEV | HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED | ARITH)) == 0, "no class run and no single call gives the plan table back while the call still reads it");
 static_assert((LAYERS_BATCH & (GROUP_DEV | HUFF_DEV_PLANS | HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED | ARITH)) == 0, "no step of a layered batch call gives an arena back: the next step reads it");
 static_assert((ROUNDTRIP_BATCH & (LAYERS_BATCH | GROUP_DEV | HUFF_DEV_PLANS | HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED | ARITH)) == 0, "no step of either pass gives the verify slot back, and the verify pass regrows no arena it reads");
+static_assert((SUITE_BATCH & (ROUNDTRIP_BATCH | LAYERS_BATCH | GROUP_DEV | HUFF_DEV_PLANS | HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED | ARITH)) == 0, "no step, no verify pass and no other call's gate gives the kept outputs back: a later list of the run still reads them");
+static_assert((int)S::LB_KEEP < 64, "a slot is a bit of a 64-bit mask");
 static_assert((ARITH & (HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED)) == 0, "the arithmetic codec shares no slot of its own with another codec or a caller");
 }  // namespace slotset
 
@@ -148,7 +154,7 @@ struct Ctx {
     std::vector<hipEvent_t> free_events;
 
     struct Buf { void *p = nullptr; size_t cap = 0; unsigned long long gen = 0; };   // gen: process-unique number of this allocation (dev_buf) -- an address can come back with other contents
-    enum { N_BUFS = (int)Slot::GD_RUNE_PLANS + 1 };   // (the table above)
+    enum { N_BUFS = (int)Slot::LB_KEEP + 1 };   // (the table above)
     Buf bufs[N_BUFS];
     Buf &buf(Slot k) { return bufs[(int)k]; }
     void *pinned = nullptr; size_t pinned_cap = 0;

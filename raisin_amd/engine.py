@@ -407,6 +407,60 @@ def BenchmarkFiles(algorithms, files):
     return results
 
 
+def _best_result(results):
+    """ai/helpers/files.py:67-78 (best="ratio"): the first result unless a later one's Ratio is strictly smaller, `Lossless` not looked at;
+    the reference's loop never appends a result that raised (compressor.py:96-100), so `failed` rows do not take part.  None without one."""
+    best = None
+    for r in results:
+        if not r.Failed and (best is None or r.Ratio < best.Ratio):
+            best = r
+    return best
+
+
+def BenchmarkFilesSuite(files, algorithms):
+    """The benchmark loop of files x layer lists (benchmark_files, ai/helpers/compressor.py:89-108, with best_result of files.py:67-78):
+    returns, per file in order, (the list of Results in the order of `algorithms`, the best of them).  BenchmarkFiles' groups (_groups,
+    BATCH_BYTES) and its Ratio / Entropy / ActualEntropy arithmetic, the quirk included; a group of two or more files goes through ONE call
+    for all the lists that are on the device (layers.SuiteBatch: every shared prefix compressed once, the files uploaded and their bytes
+    counted once), with one timer around it: TimeTaken is that wall time divided by the group's file count and by the lists the call ran.
+    A list that is not on the device, and a list the call reports as failed -- an empty file under Huffman --, goes file by file through
+    AsyncBenchmarkFile, as does everything when the call as a whole fails; so do the lists behind the first RSN_SUITE_LISTS_MAX that are
+    on the device.  A layer name that neither the layered calls nor the engine's writers know raises ValueError."""
+    files = list(files)
+    algorithms = [list(a) for a in algorithms]
+    names = [",".join(a) for a in algorithms]
+    _layers.ids([x for a in algorithms for x in a if x not in Writers])   # a name nobody knows: ValueError, before a file is read
+    on_device = [l for l, a in enumerate(algorithms) if 1 <= len(a) <= _layers.LAYERS_MAX and _on_device(a)][:_layers.SUITE_LISTS_MAX]
+    out = []
+    for group, datas, bad in _groups(files, take_empty=True):
+        rows, errors = None, None
+        if on_device and len(group) > 1:
+            try:
+                start = time.perf_counter()
+                rows, _, errors = _layers.SuiteBatch(datas, [algorithms[l] for l in on_device])
+                dur = (time.perf_counter() - start) / len(group) / max(1, sum(e is None for e in errors))
+            except _lib.RsnError:
+                rows = None
+        slot = {l: k for k, l in enumerate(on_device)} if rows is not None else {}
+        for i, (f, data) in enumerate(zip(group, datas)):
+            results = []
+            for l, a in enumerate(algorithms):
+                k = slot.get(l)
+                if k is None or errors[k] is not None:
+                    results.append(AsyncBenchmarkFile(a, f))
+                    continue
+                rt = rows[k][i]
+                entropy = _entropy(rt.hist_original, len(data)) if data else 0.0
+                actual = _entropy(rt.hist_decompressed, rt.compressed_n) if rt.compressed_n else 0.0
+                ratio = rt.compressed_n / len(data) * 100 if data else float("nan")
+                results.append(Result(names[l], _time_taken(dur), ratio, actual, entropy, rt.lossless, False))
+            out.append((results, _best_result(results)))
+        if bad is not None:
+            results = [AsyncBenchmarkFile(a, bad) for a in algorithms]  # a file that cannot be read: failed rows, in order
+            out.append((results, _best_result(results)))
+    return out
+
+
 def _suite_order(results):
     """engine.go:266-276: lossless rows before lossy ones, each group by ascending ratio."""
     return sorted(results, key=lambda r: (not r.Lossless, r.Ratio))

@@ -1,7 +1,8 @@
 """The engine's unit of work over librsn: a LIST of layers applied to one buffer (engine.go:443-479), with the stream kept on the device
 between the layers (rsn_layers_*, include/rsn.h), and the same over MANY buffers in one call, layer-major, every member on the device from
 the first layer to the last (rsn_layers_*_batch, rsn_layers_*_batch_dev) -- and the benchmark's whole body over many buffers, compressed,
-undone, compared and counted on the device (rsn_layers_roundtrip_batch, rsn_layers_roundtrip_batch_dev).  Layers are given by the engine's
+undone, compared and counted on the device (rsn_layers_roundtrip_batch, rsn_layers_roundtrip_batch_dev), under one layer list or under
+several that share their common prefixes' work (rsn_layers_suite_batch, rsn_layers_suite_batch_dev).  Layers are given by the engine's
 names, in compress order."""
 import ctypes
 from dataclasses import dataclass
@@ -10,6 +11,7 @@ from . import _lib
 
 LZSS, HUFFMAN = 1, 2          # RSN_LAYER_LZSS, RSN_LAYER_HUFFMAN
 LAYERS_MAX = 8                # RSN_LAYERS_MAX
+SUITE_LISTS_MAX = 16          # RSN_SUITE_LISTS_MAX
 IDS = {"lzss": LZSS, "huffman": HUFFMAN}
 
 
@@ -152,3 +154,74 @@ def roundtrip_tensors(srcs, layers, hists=True, stream=None):
     n = len(srcs)
     mem = (_lib.DevMember * n)(*[_lib.DevMember(t.data_ptr() if t.numel() else None, t.numel(), None, 0) for t in srcs])
     return _roundtrip_batch(n, hists, lambda res, counts: L.rsn_layers_roundtrip_batch_dev(n, mem, arr, k, res, counts, st))
+
+
+def _suite(n, lists, hists, call):
+    """call(L, n_lists, arr, res, codes, ho, hd, best) over n members under `lists` -> (rows, best, list_errors)"""
+    import numpy as np
+    k = len(lists)
+    keep = [ids(a) for a in lists]                        # (unknown names raise here, before the library is looked for)
+    L = _lib.lib()
+    arr = (_lib.LayerList * max(k, 1))(*[_lib.LayerList(ctypes.cast(a, ctypes.POINTER(ctypes.c_int)), c) for a, c in keep])
+    res = (_lib.RoundTripMember * max(k * n, 1))()
+    NOT_RUN = 1                                           # no code of the library's: the call writes the codes only when it ran its lists
+    codes = (ctypes.c_int * max(k, 1))(*([NOT_RUN] * max(k, 1)))
+    best = np.full(max(n, 1), 0xFFFFFFFF, dtype=np.uint32)
+    ho = np.zeros(256 * max(n, 1), dtype=np.uint32) if hists else None
+    hd = np.zeros(256 * max(k * n, 1), dtype=np.uint32) if hists else None
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    rc = call(L, k, arr, res, codes, ho.ctypes.data_as(u32p) if hists else None, hd.ctypes.data_as(u32p) if hists else None, best.ctypes.data_as(u32p))
+    if n == 0 or k == 0:
+        _lib.check(rc)
+        return [[] for _ in range(k)], [None] * n, [None] * k
+    if rc and any(codes[l] == NOT_RUN for l in range(k)):
+        _lib.check(rc)                                    # the call as a whole failed
+    message = L.rsn_last_error().decode("utf-8", "replace") if rc else ""
+    errors, first = [], True
+    for l in range(k):
+        if codes[l] == 0:
+            errors.append(None)
+            continue
+        errors.append(_lib.RsnError(codes[l], message if first else "list %d: failed" % l))
+        first = False
+    rows = []
+    for l in range(k):
+        if errors[l] is not None:
+            rows.append(None)
+            continue
+        row = []
+        for i in range(n):
+            r = res[l * n + i]
+            m = RoundTripMember(int(r.original_n), int(r.compressed_n), int(r.decompressed_n), int(r.first_difference), bool(r.lossless))
+            if hists:
+                m.hist_original = ho[256 * i:256 * i + 256].tolist()
+                m.hist_decompressed = hd[256 * (l * n + i):256 * (l * n + i) + 256].tolist()
+            row.append(m)
+        rows.append(row)
+    return rows, [None if b == 0xFFFFFFFF else int(b) for b in best[:n]], errors
+
+
+def SuiteBatch(datas, lists, hists=True):
+    """The benchmark loop of files x layer lists in one call (rsn_layers_suite_batch): -> (rows, best, list_errors).  rows[l][i] holds what
+    RoundTripBatch(datas, lists[l])[i] holds -- every shared prefix of the lists is compressed once, the members go up once and their bytes
+    are counted once -- or rows[l] is None where list l failed, list_errors[l] then being the RsnError that call raises for it alone (the
+    message: of the failing list of the lowest index; the code: of every one) and None otherwise.  best[i]: the list with the smallest
+    compressed size of member i among those that succeeded, the lowest index among equals; None when none did."""
+    datas = [bytes(d) for d in datas]
+    n = len(datas)
+    ins = (ctypes.c_char_p * max(n, 1))(*datas)
+    lens = (ctypes.c_size_t * max(n, 1))(*[len(d) for d in datas])
+    return _suite(n, list(lists), hists, lambda L, k, arr, res, codes, ho, hd, best: L.rsn_layers_suite_batch(n, ins, lens, k, arr, res, codes, ho, hd, best))
+
+
+def suite_tensors(srcs, lists, hists=True, stream=None):
+    """the same for a list of uint8 CUDA tensors (16-byte aligned), read where they lie and never written (rsn_layers_suite_batch_dev)"""
+    lists, srcs = list(lists), list(srcs)
+    if not srcs:
+        for a in lists:
+            ids(a)                                        # (unknown names raise all the same)
+        return [[] for _ in lists], [], [None] * len(lists)
+    st = _lib.own_stream(srcs[0], stream)
+    n = len(srcs)
+    mem = (_lib.DevMember * n)(*[_lib.DevMember(t.data_ptr() if t.numel() else None, t.numel(), None, 0) for t in srcs])
+    return _suite(n, lists, hists, lambda L, k, arr, res, codes, ho, hd, best: L.rsn_layers_suite_batch_dev(n, mem, k, arr, res, codes, ho, hd, best, st))
