@@ -51,7 +51,8 @@ int lzss_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **o
 int lzss_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t out_cap, size_t *out_n);
 
 // ---- many members in one launch (the batch calls, rsn_api.hip).  A CLASS of members is what one grouped kernel takes, a
-// workgroup per member: the small and the mid-size members of each layer and direction, eight rows.  The contract of every row:
+// workgroup per member: the small and the mid-size members of each layer and direction, eight rows -- and a ninth whose
+// members take a workgroup per TILE, the big members of Huffman compress (huff_big.hip).  The contract of every row:
 //   takes(in, n, window)   whether the member is of the class, asked in the order of batch_classes' rows (a later row need not exclude
 //                          what an earlier one takes).  Fewer than group_min members of a class in a call are not grouped: a workgroup each
 //                          against the whole device a single call has (the minimums are measured).
@@ -118,6 +119,21 @@ constexpr size_t HUFF_MID_GROUP_MIN = 4;
 static_assert((unsigned long long)HUFF_MID_PAY_MAX * 8 >= (unsigned long long)HUFF_MID_IN_MAX * 7 && HUFF_MID_OUT_MAX >= HUFF_MID_IN_MAX,
               "the decoder takes every stream the encoder writes");
 const BatchClass &huff_small_class(bool compress), &huff_mid_class(bool compress);
+// huff_big.hip: the compress direction above the mid class.  A member of more than HUFF_MID_IN_MAX and at most HUFF_BIG_IN_MAX bytes of a
+// byte alphabet does not fit a workgroup, so it is cut into tiles of HUFF_BIG_TILE bytes and a group is THREE launches with nothing on
+// the host between them: a workgroup per tile counts it, a workgroup per member sums the tiles' counts, builds the Go-exact tree in one
+// wavefront (huff_plan_small.h), writes the header and scans the tiles' bit lengths, and a workgroup per tile codes it at its bit offset
+// (huff_big_layout.h: the tiles, the scratch, which tile stores which byte).  It hands back what the mid class hands back, and a member
+// whose deepest code has more than the 24 bits of the emit table's entry -- possible from fib(27) = 196418 bytes on.  Both forms run on
+// device staging: the host form copies a run's inputs up and its results down (a member is read twice: never out of pinned host memory).
+// Its groups hold up to HUFF_BIG_GROUP_BYTES of staging: a group of the other classes' 16 MiB would hold 32 members of 256 KiB, two tiles a CU.  The streams
+// decode through the single call inside a decompress batch: there is no tiled decoder yet.  HUFF_BIG_GROUP_MIN, HUFF_BIG_IN_MAX: measured,
+// DESIGN 4.7 and profiles/huff_big_batch.txt.  Mirrored as raisin_amd.huffman.BIG_IN_MAX / BIG_TILE / BIG_GROUP_MIN / BIG_GROUP_BYTES.
+constexpr uint32_t HUFF_BIG_IN_MAX = 262144;
+constexpr uint32_t HUFF_BIG_TILE = 16384;
+constexpr size_t HUFF_BIG_GROUP_MIN = 4;
+constexpr size_t HUFF_BIG_GROUP_BYTES = 67108864;
+const BatchClass &huff_big_class();
 // huff_rune.hip: the members of at most HUFF_RUNE_IN_MAX bytes that k_huff_batch_enc hands back as GROUP_BACK_RUNES -- UTF-8 text, bytes
 // that are no UTF-8 at all -- a workgroup each in k_huff_batch_rune_enc: the runes as Go's `range string(b)` yields them counted in an
 // LDS table, the Go-exact tree of 2 to HUFF_RUNE_SYMS_MAX leaves in one wavefront (huff_plan_rune.h), header and code bits as the byte
@@ -171,7 +187,7 @@ struct BatchRows {
     template <size_t N> BatchRows(const BatchClass *const (&rows)[N]) : first(rows), n(N) {}
 };
 inline BatchRows batch_classes(BatchLayer layer, bool compress) {
-    static const BatchClass *const huff_enc[] = {&huff_small_class(true), &huff_mid_class(true)}, *const huff_dec[] = {&huff_mid_class(false), &huff_small_class(false)};
+    static const BatchClass *const huff_enc[] = {&huff_small_class(true), &huff_mid_class(true), &huff_big_class()}, *const huff_dec[] = {&huff_mid_class(false), &huff_small_class(false)};
     static const BatchClass *const lzss_enc[] = {&lzss_small_class(true), &lzss_mid_class(true)}, *const lzss_dec[] = {&lzss_small_class(false), &lzss_mid_class(false)};
     if (layer == BatchLayer::HUFFMAN) return compress ? BatchRows(huff_enc) : BatchRows(huff_dec);
     return compress ? BatchRows(lzss_enc) : BatchRows(lzss_dec);

@@ -73,7 +73,8 @@ int run_groups_dev(Ctx &c, hipStream_t s, const char *what, const std::vector<si
 }
 
 int run_groups_dev_sized(Ctx &c, hipStream_t s, const char *what, const std::vector<size_t> &idx, const rsn_dev_member *mem,
-                         const GroupSlotBytes &in_bytes, const GroupSlotBytes &out_bytes, const GroupLaunch &launch, std::vector<uint32_t> &answers) {
+                         const GroupSlotBytes &in_bytes, const GroupSlotBytes &out_bytes, const GroupLaunch &launch, std::vector<uint32_t> &answers,
+                         size_t group_bytes) {
     const size_t count = idx.size();
     answers.assign(count, GROUP_PENDING);
     if (count == 0) return RSN_OK;
@@ -82,7 +83,7 @@ int run_groups_dev_sized(Ctx &c, hipStream_t s, const char *what, const std::vec
     // for the copy of the one before it
     std::vector<GroupCut> cuts;
     size_t stage = 0;
-    for (size_t j = 0; j < count;) { const GroupCut cut = next_group(j, count, SMALL_GROUP_MAX, SMALL_GROUP_BYTES, need); stage = std::max(stage, cut.bytes); cuts.push_back(cut); j = cut.hi; }
+    for (size_t j = 0; j < count;) { const GroupCut cut = next_group(j, count, SMALL_GROUP_MAX, group_bytes, need); stage = std::max(stage, cut.bytes); cuts.push_back(cut); j = cut.hi; }
     const size_t tables = count * GD_ENTRY, down = round_up(count * sizeof(uint32_t), 16);
     Admission gate(c, slotset::GROUP_DEV); gate.admit(stage + down, ADMIT_FROM);
     void *pp, *d_stage, *d_ans;

@@ -82,7 +82,8 @@ int run_groups_dev(Ctx &c, hipStream_t s, const char *what, const std::vector<si
 // out_bytes(k) of member idx[k]
 using GroupSlotBytes = std::function<size_t(size_t k)>;
 int run_groups_dev_sized(Ctx &c, hipStream_t s, const char *what, const std::vector<size_t> &idx, const rsn_dev_member *mem,
-                         const GroupSlotBytes &in_bytes, const GroupSlotBytes &out_bytes, const GroupLaunch &launch, std::vector<uint32_t> &answers);
+                         const GroupSlotBytes &in_bytes, const GroupSlotBytes &out_bytes, const GroupLaunch &launch, std::vector<uint32_t> &answers,
+                         size_t group_bytes = SMALL_GROUP_BYTES);   // (a class whose members are large states a larger group of its own: huff_big.hip)
 
 // A class of SmallMember entries is stated ONCE, as a type K -- K::what (the name in messages), K::in_bytes(n) / K::out_bytes(n) (the slots of
 // a member of n bytes, group_layout.h) and K::launch(c, s, g, tab, base, window) (the group's kernel) -- and both of its runners, the

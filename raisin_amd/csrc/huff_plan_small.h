@@ -26,6 +26,10 @@ namespace rsn {
 constexpr uint32_t PLAN_SYMS_MAX = 128;           // byte alphabet (every symbol < 0x80; runes take the general path)
 constexpr uint32_t PLAN_NODES_MAX = 2 * PLAN_SYMS_MAX - 1;
 constexpr uint32_t PLAN_COUNT_LIMIT = 1u << 16;   // every count below this
+// ... but for the big class of the compress batch (huff_big.hip), whose members' counts sum to less than PLAN_COUNT_LIMIT_WIDE: the tree and
+// the codes below only ask that a sum of counts and a node id pack into one word -- plan_item<8>, sum << 8 < 2^32.  The parsers
+// (huff_parse_small.h) and the decoders keep PLAN_COUNT_LIMIT.
+constexpr uint32_t PLAN_COUNT_LIMIT_WIDE = 1u << 24;
 
 // A heap item / a node's code: one word each.
 //   item   count << IDB | node id         (sums of counts < 2^23, ids < 255)

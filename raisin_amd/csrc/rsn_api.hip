@@ -1127,7 +1127,8 @@ static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const
         return c.fail(rc, "%s", msg);
     };
     // Members of 2 B to 16 KiB (k_huff_batch_enc) and above that up to HUFF_MID_IN_MAX (k_huff_mid_enc) run grouped on this thread, one
-    // launch per group, every member its own workgroup and its own tree (codecs.h: the rows and their minimums).  The members those
+    // launch per group, every member its own workgroup and its own tree (codecs.h: the rows and their minimums); above that up to
+    // HUFF_BIG_IN_MAX a member is cut into tiles, a workgroup each, three launches per group (huff_big.hip).  The members those
     // kernels hand back because of a byte >= 0x80 run grouped as well, through the rune class behind the rows (huff_rune.hip), when the call
     // holds enough of them that it takes.  The rest -- larger members, and the members a kernel hands back (a single symbol, more runes
     // than the rune class takes) -- take the pipeline below, as every member did before, dealt over the batch workers.

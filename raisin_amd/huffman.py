@@ -25,7 +25,8 @@ def CompressBatch(chunks):
     rsn_huffman_compress_batch runs chunks of 2 to BATCH_COMPRESS_INPUT_MAX bytes many to a launch, a workgroup each that builds the
     chunk's own tree on the device (byte alphabets; a chunk with a single distinct byte is handed back, one with a byte >= 0x80 goes to
     the rune class below, RUNE_GROUP_MIN), when at least two chunks are of that size.  Chunks above that and up to MID_IN_MAX bytes are the mid class (csrc/huff_mid.hip: the same kernel body at
-    1024 threads, the whole chunk in LDS), grouped the same way when the call holds at least MID_GROUP_MIN of them.  The other chunks are dealt out over the batch workers (chunk k -> device k mod G) and go through a
+    1024 threads, the whole chunk in LDS), grouped the same way when the call holds at least MID_GROUP_MIN of them.  Chunks above that and up to BIG_IN_MAX bytes are the big class
+    (csrc/huff_big.hip: tiles of BIG_TILE bytes, three launches a group) when the call holds at least BIG_GROUP_MIN of them.  The other chunks are dealt out over the batch workers (chunk k -> device k mod G) and go through a
     pipeline of upload / encode / download per device.  Each result equals Compress(chunk)."""
     return _lib.call_batch(_lib.lib().rsn_huffman_compress_batch, chunks)
 
@@ -48,6 +49,17 @@ MID_IN_MAX = 65536
 MID_PAY_MAX = 57344
 MID_OUT_MAX = 65536
 MID_GROUP_MIN = 4
+
+# The big class of the compress batch calls (csrc/codecs.h HUFF_BIG_IN_MAX / HUFF_BIG_TILE / HUFF_BIG_GROUP_MIN / HUFF_BIG_GROUP_BYTES;
+# csrc/huff_big.hip): chunks above MID_IN_MAX and up to BIG_IN_MAX bytes of a byte alphabet are cut into tiles of BIG_TILE bytes,
+# a workgroup each, and go through three launches per group -- count, plan, emit -- when a call holds at least BIG_GROUP_MIN of them; a
+# group holds up to BIG_GROUP_BYTES of staging.  A chunk whose deepest code has more than 24 bits (possible from 196418 bytes on) is handed
+# back to the single call's path, like one with a single distinct byte or a byte >= 0x80.  Compress only: the streams of such chunks
+# decode through the single call's path inside DecompressBatch.
+BIG_IN_MAX = 262144
+BIG_TILE = 16384
+BIG_GROUP_MIN = 4
+BIG_GROUP_BYTES = 67108864
 
 # The rune class of the compress batch calls (csrc/codecs.h HUFF_RUNE_SYMS_MAX / HUFF_RUNE_GROUP_MIN; csrc/huff_rune.hip): chunks
 # of at most BATCH_COMPRESS_INPUT_MAX bytes that hold a byte >= 0x80 -- UTF-8 text, or no UTF-8 at all -- go a workgroup each through one
