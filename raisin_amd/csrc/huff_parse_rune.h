@@ -37,7 +37,7 @@ constexpr uint32_t PARSE_RUNE_STREAM_MAX = PARSE_RUNE_SCAN_MAX + PARSE_RUNE_PAY_
 constexpr uint32_t PARSE_RUNE_SYMS_MAX = PLAN_RUNE_SYMS_MAX;
 constexpr uint32_t PARSE_RUNE_COUNT_MAX = PLAN_RUNE_COUNT_MAX;
 constexpr uint32_t PARSE_RUNE_CHILD_MAX = 2 * (PARSE_RUNE_SYMS_MAX - 1);   // entries of child[]
-constexpr uint32_t PARSE_RUNE_SLOTS = 512, PARSE_RUNE_EMPTY = 0xFFFFFFFFu; // the table: twice the symbols it may hold; (no rune)
+constexpr uint32_t PARSE_RUNE_SLOTS = PLAN_RUNE_SLOTS, PARSE_RUNE_EMPTY = 0xFFFFFFFFu; // the table: twice the symbols it may hold; (no rune)
 constexpr uint32_t PARSE_RUNE_ERROR = 0xFFFD;                              // kRuneError (huff_host.h)
 static_assert(PARSE_RUNE_PAY_MAX == 9 * PARSE_RUNE_OUT_MAX / 8 && PARSE_RUNE_OUT_MAX <= PARSE_RUNE_COUNT_MAX, "nine bits a decoded byte; a sum of counts is a count");
 
@@ -50,7 +50,6 @@ struct HuffRunePlan {
 
 RSN_PLAN_FN uint32_t parse_rune_scan_limit(uint32_t n) { return n < PARSE_RUNE_SCAN_MAX ? n : PARSE_RUNE_SCAN_MAX; }
 RSN_PLAN_FN bool parse_rune_length_ok(unsigned long long n) { return n >= 8 && n <= PARSE_RUNE_STREAM_MAX; }
-RSN_PLAN_FN uint32_t parse_rune_hash(uint32_t r) { return (r * 0x9E3779B1u) >> 23; }   // 9 bits (huff_rune.hip's)
 
 // the rune that starts at byte i of h[0, end), as Go's `range string` yields it (go_decode_rune, huff_host.cpp; seq_len, huff_utf8.h);
 // only bytes below `end` are asked for
@@ -75,7 +74,7 @@ RSN_PLAN_FN uint32_t parse_rune_decode(const Bytes &h, uint32_t i, uint32_t end)
 
 // rune r's entry: cnt1 = count + 1 of its LAST entry.  key[] starts as PARSE_RUNE_EMPTY.  false: one rune more than the class takes
 RSN_PLAN_FN bool parse_rune_put(uint32_t *key, uint32_t *cnt1, uint32_t *distinct, uint32_t r, uint32_t c1) {
-    uint32_t slot = parse_rune_hash(r);
+    uint32_t slot = plan_rune_hash(r);
     for (uint32_t p = 0; p < PARSE_RUNE_SLOTS; p++) {
         const uint32_t k = key[slot];
         if (k == r) { cnt1[slot] = c1; return true; }
@@ -175,13 +174,18 @@ inline HuffDevSummary parse_rune_light(const uint8_t *in, unsigned long long n) 
 
 // ---- the whole plan, serially, over array stores: what the kernel does with a workgroup (the separator by a block-wide minimum, one
 // lane's scan, the ranks a thread each, the tree in one wavefront's VGPRs).  The CPU test's subject; in[0, n) is all it reads.
-inline void parse_rune_plan_serial(const uint8_t *in, unsigned long long n64, HuffRunePlan &plan) {
+// info (where asked for): what the plan's fields do not say -- the distinct runes and the deepest code also of a stream that is refused for
+// its depth, and the lanes; zeros where the stream is refused before they are known.
+struct ParseRuneInfo { uint32_t a, deepest, S, T; };
+inline void parse_rune_plan_serial(const uint8_t *in, unsigned long long n64, HuffRunePlan &plan, ParseRuneInfo *info = nullptr) {
     plan = HuffRunePlan{};
+    if (info) *info = ParseRuneInfo{0, 0, 0, 0};
     HuffDevBounds &p = plan.b;
     ParseRuneTable t;
     uint32_t sep, S, T;
     if (!parse_rune_light_serial(in, n64, t, p, &sep, &S, &T)) return;
     const uint32_t a = t.distinct;
+    if (info) { info->a = a; info->S = S; info->T = T; }
     uint32_t rune[PARSE_RUNE_SYMS_MAX], cnt1[PARSE_RUNE_SYMS_MAX];
     for (uint32_t s = 0, at = 0; s < PARSE_RUNE_SLOTS; s++) if (t.key[s] != PARSE_RUNE_EMPTY) { rune[at] = t.key[s]; cnt1[at] = t.cnt1[s]; at++; }
     ParseArrayStore<PARSE_RUNE_SYMS_MAX> heap{}, kids{};
@@ -196,6 +200,7 @@ inline void parse_rune_plan_serial(const uint8_t *in, unsigned long long n64, Hu
     plan_codes<PLAN_RUNE_IDB>(a, root, kids, code);
     uint32_t mn = 255, mx = 0;
     for (uint32_t r = 0; r < a; r++) { const uint32_t l = code.v[r] >> 24; mn = l < mn ? l : mn; mx = l > mx ? l : mx; }
+    if (info) info->deepest = mx;
     if (!parse_depths(mn, mx, p)) return;
     for (uint32_t k = 0; k + 1 < a; k++) {
         plan.child[2 * k] = (uint16_t)parse_rune_child(kids.v[k] & ((1u << PLAN_RUNE_IDB) - 1), a);

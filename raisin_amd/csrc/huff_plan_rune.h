@@ -22,6 +22,12 @@ constexpr uint32_t PLAN_RUNE_IDB = 9;                                  // bits o
 constexpr uint32_t PLAN_RUNE_NODES_MAX = 2 * PLAN_RUNE_SYMS_MAX - 1;
 constexpr uint32_t PLAN_RUNE_COUNT_MAX = 16384;                        // a count, and the sum of all, at most
 static_assert(PLAN_RUNE_NODES_MAX <= (1u << PLAN_RUNE_IDB) && ((unsigned long long)PLAN_RUNE_COUNT_MAX << PLAN_RUNE_IDB) < (1ull << 32), "a heap item is one word");
+constexpr uint32_t PLAN_RUNE_SLOTS = 2 * PLAN_RUNE_SYMS_MAX;           // of the encoder's and the decoder's open-addressing table: twice the symbols it may hold
+static_assert(PLAN_RUNE_SLOTS == 1u << 9, "plan_rune_hash gives 9 bits");
+
+// a rune's first slot in a table of PLAN_RUNE_SLOTS slots: the ONE hash of the encoder's counts (huff_rune.hip) and the decoder's entries
+// (huff_parse_rune.h); tests/huff_rune_parse_test.cpp prints it (`slots`)
+RSN_PLAN_FN uint32_t plan_rune_hash(uint32_t r) { return (r * 0x9E3779B1u) >> 23; }   // 9 bits
 
 // symbol t of the a symbols (rune[], cnt[]): its position in (count asc, rune asc) order and in rune order
 RSN_PLAN_FN void plan_rune_ranks(const uint32_t *rune, const uint32_t *cnt, uint32_t a, uint32_t t, uint32_t *leaf_rank, uint32_t *rune_rank) {

@@ -28,7 +28,7 @@ namespace rsn {
 namespace {
 
 constexpr uint32_t HR_T = 256;
-constexpr uint32_t HR_SLOTS = 512;                // of the table: twice the symbols it may hold
+constexpr uint32_t HR_SLOTS = PLAN_RUNE_SLOTS;    // of the table: twice the symbols it may hold; plan_rune_hash gives a rune's first
 constexpr uint32_t HR_EMPTY = 0xFFFFFFFFu;        // (no rune)
 constexpr uint32_t HR_IMG_WORDS = huff_rune_enc_out_slot(HE_IN_MAX) / 4;
 static_assert(HE_IN_MAX == HUFF_RUNE_IN_MAX && HE_IN_MAX <= PLAN_RUNE_COUNT_MAX && HUFF_RUNE_SYMS_MAX == PLAN_RUNE_SYMS_MAX, "one cutoff, one alphabet");
@@ -39,8 +39,6 @@ constexpr bool hr_sizes_hold() {
     return true;
 }
 static_assert(hr_sizes_hold(), "the image fits the member's slot, and huff_compress_bound covers the stream");
-
-__device__ __forceinline__ uint32_t hr_hash(uint32_t r) { return (r * 0x9E3779B1u) >> 23; }   // 9 bits
 
 // the 16 positions of unit u of the member in LDS (zeros behind its n bytes, a zero unit behind its last)
 __device__ __forceinline__ uint32_t hr_classify(const uint4 *s_in, uint32_t u, uint32_t n, uint32_t rune[16]) {
@@ -97,7 +95,7 @@ __global__ __launch_bounds__(HR_T) void k_huff_batch_rune_enc(const SmallMember 
             if (!((mask >> k) & 1u)) continue;
             if (*(volatile uint32_t *)&s_meta[1]) break;                  // the table holds more than the class takes: handed back below
             const uint32_t r = rune[k];
-            uint32_t slot = hr_hash(r), p = 0;
+            uint32_t slot = plan_rune_hash(r), p = 0;
             for (; p < HR_SLOTS; p++) {
                 const uint32_t old = atomicCAS(&s_key[slot], HR_EMPTY, r);
                 if (old == HR_EMPTY && atomicAdd(&s_meta[0], 1u) >= HUFF_RUNE_SYMS_MAX) s_meta[1] = 1;
@@ -181,7 +179,7 @@ __global__ __launch_bounds__(HR_T) void k_huff_batch_rune_enc(const SmallMember 
 #pragma unroll
             for (int k = 0; k < 16; k++) {
                 if ((mask >> k) & 1u) {
-                    uint32_t slot = hr_hash(rune[k]);
+                    uint32_t slot = plan_rune_hash(rune[k]);
                     while (s_key[slot] != rune[k]) slot = (slot + 1) & (HR_SLOTS - 1);      // (counted above: it is there)
                     e[k] = s_code[slot];
                     bits += e[k] >> 24;

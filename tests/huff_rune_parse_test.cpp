@@ -2,6 +2,8 @@
 // runs per member) against the host's parse_header + build_tree + assign_codes (huff_host.cpp), field by field: verdict, A0, p0, end,
 // expect, K, root, flat, every child[] entry and every leaf's rune.  Built and run by tests/test_huff_rune_parse_host.py.
 // Prints "ok <streams> planned <k> deepest <bits>" and exits 0, or the first disagreement and 1.
+// Two more modes for tests/test_rune_limits_host.py: `slots <rune>...` prints plan_rune_hash of each rune, `plan <file>` the plan's verdict,
+// distinct runes, deepest code and lanes of every stream in a file of length-prefixed records.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -160,9 +162,43 @@ std::vector<uint32_t> distinct_runes(std::mt19937_64 &rng, uint32_t a) {
     while (out.size() < a) { const uint32_t r = rune_of_width(rng, 1 + (int)(rng() % 4)); if (seen.insert(r).second) out.push_back(r); }
     return out;
 }
+
+// `slots <rune>...`: the first slot of each rune (decimal, 0x... or 0...) in the encoder's and the decoder's table, one a line
+int slots_mode(int argc, char **argv) {
+    for (int k = 2; k < argc; k++) printf("%u\n", plan_rune_hash((uint32_t)strtoul(argv[k], nullptr, 0)));
+    return 0;
+}
+
+// `plan <file>`: the file holds streams as records of a 4-byte little-endian length and that many bytes.  One line a stream: the verdict
+// of parse_rune_plan_serial, the distinct runes, the deepest code, and the lanes (zeros where the stream is refused before they are known)
+int plan_mode(const char *path) {
+    FILE *f = fopen(path, "rb");
+    if (!f) { printf("cannot open %s\n", path); return 1; }
+    for (;;) {
+        uint8_t len[4];
+        const size_t got = fread(len, 1, 4, f);
+        if (got == 0) break;
+        const size_t n = (size_t)len[0] | (size_t)len[1] << 8 | (size_t)len[2] << 16 | (size_t)len[3] << 24;
+        if (got != 4 || n > (1u << 24)) { printf("a record's length is cut or beyond 16 MiB\n"); fclose(f); return 1; }
+        uint8_t *exact = (uint8_t *)malloc(n ? n : 1);                  // (exactly n bytes: the sanitizer sees a read at or behind n)
+        if (fread(exact, 1, n, f) != n) { printf("a record of %zu bytes is cut\n", n); free(exact); fclose(f); return 1; }
+        HuffRunePlan plan;
+        ParseRuneInfo info;
+        parse_rune_plan_serial(exact, n, plan, &info);
+        free(exact);
+        printf("%s a %u deepest %u S %u T %u\n", plan.b.verdict == PARSE_PLANNED ? "taken" : "refused", info.a, info.deepest, info.S, info.T);
+    }
+    fclose(f);
+    return 0;
+}
 }  // namespace
 
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "slots")) return slots_mode(argc, argv);
+    if (argc > 1 && !strcmp(argv[1], "plan")) {
+        if (argc != 3) { printf("usage: plan <file>\n"); return 2; }
+        return plan_mode(argv[2]);
+    }
     const long long n_random = argc > 1 ? atoll(argv[1]) : 3000;
     std::mt19937_64 rng(20261019);
     auto run = [&](const std::string &hdr, const char *what, int want = -1) { const std::vector<uint8_t> s = stream_of(hdr, rng); return check(s, s.size(), what, want); };
