@@ -4,7 +4,7 @@ time, a 258-entry cumulative table) and exact.
 
 encode(data) -> bytes                 the packed stream
 decode(stream) -> bytes               raises FormatError where the library returns RSN_ERR_FORMAT
-stats(data) -> dict                   max_pending / end_pending / nbits of an encode
+stats(data) -> dict                   max_pending / end_pending / nbits / runs of an encode
 """
 import bisect
 
@@ -45,10 +45,12 @@ class Model:
 
 
 def encode_bits(data):
-    """the coder's bits (a bytearray of 0/1) and {max_pending, end_pending}"""
+    """the coder's bits (a bytearray of 0/1) and {max_pending, end_pending, nbits, runs}; runs: for each pending run that was flushed,
+    (its length, the position mod 32 of the deciding bit in front of it)"""
     low, high, pending, max_pending = 0, MAX_CODE, 0, 0
     m = Model()
     bits = bytearray()
+    runs = []
     for s in list(bytes(data)) + [EOF]:
         d = high - low + 1
         lo, hi, tot = m.code(s)
@@ -56,10 +58,14 @@ def encode_bits(data):
         low = low + d * lo // tot
         while True:
             if high < HALF:
+                if pending:
+                    runs.append((pending, len(bits) % 32))
                 bits.append(0)
                 bits.extend(b"\x01" * pending)
                 pending = 0
             elif low >= HALF:
+                if pending:
+                    runs.append((pending, len(bits) % 32))
                 bits.append(1)
                 bits.extend(b"\x00" * pending)
                 pending = 0
@@ -72,7 +78,7 @@ def encode_bits(data):
                 break
             high = (2 * high + 1) & MAX_CODE
             low = (2 * low) & MAX_CODE
-    return bits, {"max_pending": max_pending, "end_pending": pending, "nbits": len(bits)}
+    return bits, {"max_pending": max_pending, "end_pending": pending, "nbits": len(bits), "runs": runs}
 
 
 def pack(bits):
@@ -153,22 +159,27 @@ def decode(stream, tail_bits=TAIL_BITS):
             value = (2 * value + nextbit()) & M32
 
 
-def greedy_input(steps=400):
+def greedy_input(steps=400, prefix=b""):
     """At each step the lowest byte whose sub-interval holds both 0x7FFF and 0x8000, else 0x41: the interval keeps straddling the
-    middle, so pending bits pile up (runs of hundreds)."""
+    middle, so pending bits pile up (runs of hundreds).  `prefix` is coded first (and returned in front): the picks start from the
+    coder's state behind it."""
     low, high = 0, MAX_CODE
     m = Model()
     out = bytearray()
-    for _ in range(steps):
+    prefix = bytes(prefix)
+    for k in range(len(prefix) + steps):
         d = high - low + 1
         tot = m.cf[257]
-        pick = 0x41
-        for b in range(256):
-            h = low + d * m.cf[b + 1] // tot - 1
-            lw = low + d * m.cf[b] // tot
-            if lw <= 0x7FFF and h >= 0x8000:
-                pick = b
-                break
+        if k < len(prefix):
+            pick = prefix[k]
+        else:
+            pick = 0x41
+            for b in range(256):
+                h = low + d * m.cf[b + 1] // tot - 1
+                lw = low + d * m.cf[b] // tot
+                if lw <= 0x7FFF and h >= 0x8000:
+                    pick = b
+                    break
         out.append(pick)
         lo, hi, tot = m.code(pick)
         high = low + d * hi // tot - 1

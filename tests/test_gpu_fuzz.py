@@ -271,3 +271,63 @@ def test_stretches_of_short_periods_fuzz(mods, oracle, seed):
         c = lz.CompressAsync(data, False, w)
         assert c == oracle.lzss_compress(data, w), "seed %d, window %d" % (seed, w)
     assert lz.Decompress(c) == data
+
+
+def _arith_input(rng):
+    """an alphabet of 1 to 256 symbols at a random base (it straddles lane boundaries of the table: DESIGN 4.9), uniform or geometric,
+    of a length around the places where the arithmetic kernels change: nothing to a lane's fetch, a few KiB, the table's freeze"""
+    width = rng.choice((1, 2, 3, 4, 5, 16, 64, 255, 256))
+    base = rng.randrange(256 - width + 1)
+    r = rng.random()                                                      # (the model codes about 150 000 symbols a second: few long ones)
+    n = rng.randrange(16120, 16131) if r < 0.02 else rng.randrange(1000, 3001) if r < 0.2 else rng.randrange(0, 65)
+    if rng.random() < 0.5:
+        return bytes(base + rng.randrange(width) for _ in range(n))
+    return bytes(base + min(int(rng.expovariate(0.7)), width - 1) for _ in range(n))
+
+
+def _batch_dev(_lib, fn, ins, caps):
+    """one rsn_*_batch_dev call: the members back to back at 16-byte offsets of ONE allocation with 0xA5 between them, each output a
+    slot of exactly caps[i] bytes in a second one filled with 0xEE -> the results; what lies behind a result must still be 0xEE.
+    Pack and Slots of tests/test_gpu_batch_dev.py do this with torch tensors and cannot be used here: this file also runs in the
+    torch-free leg (tests/test_gpu_no_torch.py), where torch must not be imported -- so device memory comes from the runtime itself
+    (_lib.hip())."""
+    import ctypes
+    H = _lib.hip()
+    src, in_off, out_off, at = bytearray(), [], [], 0
+    for d, c in zip(ins, caps):
+        in_off.append(len(src))
+        src += d + b"\xa5" * (32 - len(d) % 16)
+        out_off.append(at)
+        at += (c + 15) // 16 * 16 + 16
+    d_in, d_out = ctypes.c_void_p(), ctypes.c_void_p()
+    assert H.hipMalloc(ctypes.byref(d_in), len(src) + 64) == 0 and H.hipMalloc(ctypes.byref(d_out), at + 64) == 0
+    try:
+        assert H.hipMemcpy(d_in, bytes(src), len(src), 1) == 0 and H.hipMemset(d_out, 0xEE, at + 64) == 0
+        lens = _lib.call_batch_dev(fn, [(d_in.value + i, len(d), d_out.value + o, c) for d, c, i, o in zip(ins, caps, in_off, out_off)], None)
+        buf = ctypes.create_string_buffer(at + 64)
+        assert H.hipMemcpy(buf, d_out, at + 64, 2) == 0
+    finally:
+        H.hipFree(d_in)
+        H.hipFree(d_out)
+    res = [buf.raw[o:o + k] for o, k in zip(out_off, lens)]
+    for o, k, c in zip(out_off, lens, caps):
+        assert k <= c and buf.raw[o + k:o + (c + 15) // 16 * 16 + 16] == b"\xee" * ((c + 15) // 16 * 16 + 16 - k)
+    return res
+
+
+def test_arithmetic_fuzz():
+    """300 inputs through one CompressBatch and one DecompressBatch, and through the batch calls on device buffers: every member equals
+    tests/arith_model.py.  The empty input's stream, 01 ff, does not decode (tests/test_gpu_arith.py): it is left out of the way back."""
+    import arith_model as M
+    from raisin_amd import _lib, arithmetic
+    L = _lib.lib()
+    _lib.check(L.rsn_device_set(0))
+    rng = random.Random(0xA21F)
+    datas = [_arith_input(rng) for _ in range(300 * MORE)]
+    want = [M.encode(d) for d in datas]
+    assert any(not d for d in datas) and all(w == b"\x01\xff" for d, w in zip(datas, want) if not d)
+    assert arithmetic.CompressBatch(datas) == want
+    full = [(d, w) for d, w in zip(datas, want) if d]
+    assert arithmetic.DecompressBatch([w for _, w in full]) == [d for d, _ in full]
+    assert _batch_dev(_lib, L.rsn_arithmetic_compress_batch_dev, datas, [len(w) for w in want]) == want
+    assert _batch_dev(_lib, L.rsn_arithmetic_decompress_batch_dev, [w for _, w in full], [len(d) for d, _ in full]) == [d for d, _ in full]
