@@ -51,8 +51,9 @@ int lzss_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **o
 int lzss_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t out_cap, size_t *out_n);
 
 // ---- many members in one launch (the batch calls, rsn_api.hip).  A CLASS of members is what one grouped kernel takes, a
-// workgroup per member: the small and the mid-size members of each layer and direction, eight rows -- and a ninth whose
-// members take a workgroup per TILE, the big members of Huffman compress (huff_big.hip).  The contract of every row:
+// workgroup per member: the small and the mid-size members of each layer and direction, eight rows -- and two whose
+// members take a workgroup per TILE, the big members of Huffman compress (huff_big.hip) and of Huffman decompress (huff_big_dec.hip).
+// The contract of every row:
 //   takes(in, n, window)   whether the member is of the class, asked in the order of batch_classes' rows (a later row need not exclude
 //                          what an earlier one takes).  Fewer than group_min members of a class in a call are not grouped: a workgroup each
 //                          against the whole device a single call has (the minimums are measured).
@@ -127,13 +128,29 @@ const BatchClass &huff_small_class(bool compress), &huff_mid_class(bool compress
 // whose deepest code has more than the 24 bits of the emit table's entry -- possible from fib(27) = 196418 bytes on.  Both forms run on
 // device staging: the host form copies a run's inputs up and its results down (a member is read twice: never out of pinned host memory).
 // Its groups hold up to HUFF_BIG_GROUP_BYTES of staging: a group of the other classes' 16 MiB would hold 32 members of 256 KiB, two tiles a CU.  The streams
-// decode through the single call inside a decompress batch: there is no tiled decoder yet.  HUFF_BIG_GROUP_MIN, HUFF_BIG_IN_MAX: measured,
+// decode through the tiled decoder below inside a decompress batch.  HUFF_BIG_GROUP_MIN, HUFF_BIG_IN_MAX: measured,
 // DESIGN 4.7 and profiles/huff_big_batch.txt.  Mirrored as raisin_amd.huffman.BIG_IN_MAX / BIG_TILE / BIG_GROUP_MIN / BIG_GROUP_BYTES.
 constexpr uint32_t HUFF_BIG_IN_MAX = 262144;
 constexpr uint32_t HUFF_BIG_TILE = 16384;
 constexpr size_t HUFF_BIG_GROUP_MIN = 4;
 constexpr size_t HUFF_BIG_GROUP_BYTES = 67108864;
 const BatchClass &huff_big_class();
+// huff_big_dec.hip: the way back.  A stream of a byte alphabet that promises more than HUFF_MID_OUT_MAX and at most HUFF_BIG_OUT_MAX bytes
+// from at most HUFF_BIG_PAY_MAX bytes of payload is cut into tiles of its PAYLOAD (huff_big_dec_layout.h: 960 lanes of 64 code bits, 7680
+// bytes) and a group is three launches with nothing on the host between them: a workgroup per tile answers all 32 bits the tile could be
+// entered at (lane_dec_body's map, huff_small_body.h), a wavefront per member composes the tiles' maps into every tile's true entry, first
+// output byte and symbol count and gives the whole verdict, and a workgroup per tile of a taken member decodes it from its entry and stores
+// its own output bytes.  No workgroup waits for another.  Handed back, to the single call: what the wide plan refuses (huff_parse_small.h:
+// runes, foreign headers, codes beyond 32 bits), more than four phases or DEC_ROUNDS in a tile, a tile of more symbols than the emit
+// image holds (below 1.9 bits a symbol over a whole tile), malformed streams.  Both forms run on device staging, in groups of up to
+// HUFF_BIG_GROUP_BYTES, as the encoder's do.  HUFF_BIG_DEC_GROUP_MIN, HUFF_BIG_OUT_MAX: DESIGN 4.7 and profiles/huff_big_dec_batch.txt.
+// Mirrored as raisin_amd.huffman.BIG_OUT_MAX / BIG_PAY_MAX / BIG_DEC_GROUP_MIN / BIG_DEC_LANES / BIG_DEC_LANE_BITS / BIG_DEC_OUT_CAP.
+constexpr uint32_t HUFF_BIG_OUT_MAX = 262144;
+constexpr uint32_t HUFF_BIG_PAY_MAX = 229376;
+constexpr size_t HUFF_BIG_DEC_GROUP_MIN = 4;
+static_assert((unsigned long long)HUFF_BIG_PAY_MAX * 8 >= (unsigned long long)HUFF_BIG_IN_MAX * 7 && HUFF_BIG_OUT_MAX >= HUFF_BIG_IN_MAX,
+              "the decoder takes every stream the encoder writes");
+const BatchClass &huff_big_dec_class();
 // huff_rune.hip: the members of at most HUFF_RUNE_IN_MAX bytes that k_huff_batch_enc hands back as GROUP_BACK_RUNES -- UTF-8 text, bytes
 // that are no UTF-8 at all -- a workgroup each in k_huff_batch_rune_enc: the runes as Go's `range string(b)` yields them counted in an
 // LDS table, the Go-exact tree of 2 to HUFF_RUNE_SYMS_MAX leaves in one wavefront (huff_plan_rune.h), header and code bits as the byte
@@ -180,14 +197,15 @@ int huff_rune_dec_offer(Ctx &c, std::vector<size_t> &rest, const uint8_t *const 
 int huff_rune_dec_offer_dev(Ctx &c, hipStream_t s, std::vector<size_t> &rest, const rsn_dev_member *mem, const DevPlans &plans,
                             std::vector<size_t> &idx, std::vector<uint32_t> &answers);
 // the rows of a layer and direction in order of precedence: LZSS asks its small class first, Huffman decompress its mid class (a short
-// stream may promise more output than k_huff_batch_dec's workgroup holds)
+// stream may promise more output than k_huff_batch_dec's workgroup holds) and then its tiled class, for the same reason: the small class
+// takes by the stream's length alone, and 8 KiB of payload can promise more than HUFF_MID_OUT_MAX bytes
 enum class BatchLayer { HUFFMAN, LZSS };
 struct BatchRows {
     const BatchClass *const *first; size_t n;
     template <size_t N> BatchRows(const BatchClass *const (&rows)[N]) : first(rows), n(N) {}
 };
 inline BatchRows batch_classes(BatchLayer layer, bool compress) {
-    static const BatchClass *const huff_enc[] = {&huff_small_class(true), &huff_mid_class(true), &huff_big_class()}, *const huff_dec[] = {&huff_mid_class(false), &huff_small_class(false)};
+    static const BatchClass *const huff_enc[] = {&huff_small_class(true), &huff_mid_class(true), &huff_big_class()}, *const huff_dec[] = {&huff_mid_class(false), &huff_big_dec_class(), &huff_small_class(false)};
     static const BatchClass *const lzss_enc[] = {&lzss_small_class(true), &lzss_mid_class(true)}, *const lzss_dec[] = {&lzss_small_class(false), &lzss_mid_class(false)};
     if (layer == BatchLayer::HUFFMAN) return compress ? BatchRows(huff_enc) : BatchRows(huff_dec);
     return compress ? BatchRows(lzss_enc) : BatchRows(lzss_dec);
@@ -228,7 +246,7 @@ int arith_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8
 int arith_members_dev(Ctx &c, hipStream_t s, bool enc, size_t n, const rsn_dev_member *mem, size_t *out_lens, size_t *failed);
 
 // the Huffman decompress batch on device buffers (rsn.h; huff_dev.hip): ONE launch of k_huff_dev_plan over the members a grouped
-// decoder could take (8 <= n <= HUFF_HDR_MAX + 8 + HUFF_MID_PAY_MAX), a workgroup each -- the header parsed, the tree built and the stream's
+// decoder could take (8 <= n <= HUFF_HDR_MAX + 8 + HUFF_BIG_PAY_MAX), a workgroup each -- the header parsed, the tree built and the stream's
 // bounds computed where the stream lies -- then ONE copy down, 16 bytes a candidate, and the one host wait the classes' slots need.
 int huff_dev_plan(Ctx &c, hipStream_t s, size_t n, const rsn_dev_member *mem, DevPlans &plans);
 

@@ -23,6 +23,7 @@ namespace {
 static_assert(PARSE_HDR_MAX == HDR_MAX && PARSE_STREAM_MAX == DEC_STREAM_MAX && PARSE_OUT_MAX == SMALL_MAX && PARSE_K_MAX == (uint32_t)DEC_K,
               "huff_parse_small.h restates the decoders' limits without their headers");
 static_assert(PLAN_COUNT_LIMIT <= SMALL_MAX, "a count the plan takes is one small_dec_plan takes");
+static_assert(PARSE_OUT_MAX_WIDE == HUFF_BIG_OUT_MAX && PARSE_PAY_MAX_WIDE == HUFF_BIG_PAY_MAX, "... and the wide form's are the tiled decoder's class (codecs.h)");
 
 constexpr int HP_T = 128;                                     // threads of the plan kernel: a thread per byte of the alphabet, two wavefronts
 constexpr uint32_t HP_UNITS = (PARSE_SCAN_MAX + 15) / 16;     // 16-byte units of the header in LDS
@@ -46,13 +47,13 @@ __global__ __launch_bounds__(HP_T) void k_huff_dev_plan(const PlanEntry *__restr
     __shared__ uint32_t s_cnt1[PLAN_SYMS_MAX], s_lf[PLAN_SYMS_MAX];
     __shared__ uint8_t s_leaf[PLAN_SYMS_MAX];
     __shared__ __attribute__((aligned(4))) uint16_t s_child[256];
-    __shared__ uint32_t s_w[8];                               // the separator, the scan's verdict, the counts' sum, a count at the limit, root, shortest, deepest
+    __shared__ uint32_t s_w[8];                               // the separator, the scan's verdict, the counts' sum, the largest count, root, shortest, deepest
     static_assert(HP_T == PLAN_SYMS_MAX, "a thread per byte of the alphabet");
     const PlanEntry e = tab[blockIdx.x];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // every verdict below is the same for the whole workgroup: a refusal is a return of all its threads
     auto refuse = [&] { if (tid == 0) sums[blockIdx.x] = HuffDevSummary{PARSE_NOT_MINE, 0, 0, 0}; };
-    if (!parse_length_ok(e.n)) { refuse(); return; }
+    if (!parse_length_ok(e.n, true)) { refuse(); return; }     // (the wide form is allowed: huff_parse_small.h says which streams it judges)
     const uint32_t n = (uint32_t)e.n, limit = parse_scan_limit(n);
     {   // the header into LDS under the gather's rule: the unit that reaches beyond src + n is masked, nothing at or behind src + n rounded up to 16 is loaded
         const uint4 *src = reinterpret_cast<const uint4 *>(e.src);
@@ -84,14 +85,15 @@ __global__ __launch_bounds__(HP_T) void k_huff_dev_plan(const PlanEntry *__restr
     __syncthreads();
     const uint32_t sep = s_w[0];
     if (sep == PARSE_NONE || sep + 4 > n) { refuse(); return; }
-    if (tid == 0) { LdsBytes h; h.w = reinterpret_cast<const uint32_t *>(s_hdr); s_w[1] = parse_scan(h, sep, s_cnt1) ? 1u : 0u; }
+    if (tid == 0) { LdsBytes h; h.w = reinterpret_cast<const uint32_t *>(s_hdr); s_w[1] = parse_scan(h, sep, s_cnt1, PLAN_COUNT_LIMIT_WIDE) ? 1u : 0u; }
     __syncthreads();
     if (!s_w[1]) { refuse(); return; }
     const uint32_t c1 = s_cnt1[tid];
-    if (c1) { atomicAdd(&s_w[2], c1 - 1); if (c1 - 1 >= PLAN_COUNT_LIMIT) s_w[3] = 1; }
+    if (c1) { atomicAdd(&s_w[2], c1 - 1); atomicMax(&s_w[3], c1 - 1); }
     const uint32_t a = (uint32_t)__syncthreads_count(c1 != 0);
     HuffDevBounds b{};
-    if (!parse_counts_ok(a, s_w[3], s_w[2]) || !parse_bounds(n, sep, hb[sep + 2], b)) { refuse(); return; }
+    const bool wide = parse_is_wide(true, n, s_w[2]);
+    if (!parse_counts_ok(a, s_w[3] >= parse_count_limit(wide), s_w[2], wide) || !parse_bounds(n, sep, hb[sep + 2], b)) { refuse(); return; }
     b.expect = s_w[2];
     if (c1) { const uint32_t r = plan_leaf_rank(s_cnt1, tid); s_lf[r] = c1 - 1; s_leaf[r] = (uint8_t)tid; }
     __syncthreads();
@@ -204,7 +206,7 @@ int huff_dev_plan(Ctx &c, hipStream_t s, size_t n, const rsn_dev_member *mem, De
     plans.sum.clear();
     plans.d_table = nullptr;
     std::vector<size_t> cand;
-    for (size_t i = 0; i < n; i++) if (mem[i].n >= 8 && mem[i].n <= HDR_MAX + 8 + HUFF_MID_PAY_MAX) { plans.at[i] = (uint32_t)cand.size(); cand.push_back(i); }
+    for (size_t i = 0; i < n; i++) if (mem[i].n >= 8 && mem[i].n <= HDR_MAX + 8 + HUFF_BIG_PAY_MAX) { plans.at[i] = (uint32_t)cand.size(); cand.push_back(i); }
     const size_t k = cand.size();
     if (k == 0) return RSN_OK;
     if (k >= DEV_PLAN_NONE) return c.fail(RSN_ERR_LIMIT, "huffman: a batch of %zu members", k);
@@ -231,8 +233,8 @@ int huff_dev_plan(Ctx &c, hipStream_t s, size_t n, const rsn_dev_member *mem, De
 
 // run_groups_dev (group_dev.hip) for a decoding class: the same groups and the same staging, the table entry a SmallDecArgs that the gather
 // kernel completes on the device, the input slot the stream from A0 on, the output slot what the header promises.
-int huff_dec_run_dev(Ctx &c, hipStream_t s, const HuffDecShape &shape, HuffDecLaunch launch, const std::vector<size_t> &idx, const rsn_dev_member *mem,
-                     const DevPlans &plans, std::vector<uint32_t> &answers) {
+int huff_dec_run_dev(Ctx &c, hipStream_t s, const HuffDecShape &shape, const HuffDecLaunch &launch, const std::vector<size_t> &idx, const rsn_dev_member *mem,
+                     const DevPlans &plans, std::vector<uint32_t> &answers, size_t group_bytes) {
     const char *what = "huffman batch decompress";
     const size_t count = idx.size();
     answers.assign(count, GROUP_PENDING);
@@ -246,7 +248,7 @@ int huff_dec_run_dev(Ctx &c, hipStream_t s, const HuffDecShape &shape, HuffDecLa
     auto need = [&](size_t k) { return group_need(HD_ENTRY, in_b(k), out_b(k)); };
     std::vector<GroupCut> cuts;
     size_t stage = 0;
-    for (size_t j = 0; j < count;) { const GroupCut cut = next_group(j, count, SMALL_GROUP_MAX, SMALL_GROUP_BYTES, need); stage = std::max(stage, cut.bytes); cuts.push_back(cut); j = cut.hi; }
+    for (size_t j = 0; j < count;) { const GroupCut cut = next_group(j, count, SMALL_GROUP_MAX, group_bytes, need); stage = std::max(stage, cut.bytes); cuts.push_back(cut); j = cut.hi; }
     const size_t tables = count * sizeof(DecEntry), down = round_up(count * sizeof(uint32_t), 16);
     Admission gate(c, slotset::GROUP_DEV); gate.admit(stage + down, ADMIT_FROM);
     void *pp, *d_stage, *d_ans;

@@ -85,20 +85,8 @@ bool mid_dec_wants(size_t pay, unsigned long long expect) {
 }
 bool mid_dec_takes(const uint8_t *in, size_t n, int64_t) {
     if (n < 8 || n > HDR_MAX + 8 + HUFF_MID_PAY_MAX || 8 * n <= HB_OUT_MAX) return false;
-    size_t sep = (size_t)-1;
-    for (size_t i = 0; i + 1 < std::min<size_t>(n, HDR_MAX + 8); i++) if (in[i] == 0x5C && in[i + 1] == 0x0A) { sep = i; break; }
-    if (sep == (size_t)-1 || sep + 4 > n) return false;
-    const size_t pay = n - sep - 3;
-    if (pay > HUFF_MID_PAY_MAX || (pay <= HB_PAY_MAX && 8 * pay <= HB_OUT_MAX)) return false;
-    unsigned long long expect = 0, acc = 0;
-    for (size_t i = 0; i < sep; i++) {
-        const uint8_t ch = in[i];
-        if (ch >= '0' && ch <= '9') { acc = std::min<unsigned long long>(acc * 10 + (ch - '0'), 1ull << 40); continue; }
-        if (ch != '|') continue;
-        expect += acc; acc = 0;
-        i += (i + 2 < sep && in[i + 1] == 0x5C && in[i + 2] == 'n') ? 2 : 1;      // the entry's byte is not a count's digit
-    }
-    return mid_dec_wants(pay, expect);
+    size_t pay = 0; unsigned long long expect = 0;
+    return huff_dec_promise(in, n, &pay, &expect, [](size_t p) { return p <= HUFF_MID_PAY_MAX && !(p <= HB_PAY_MAX && 8 * p <= HB_OUT_MAX); }) && mid_dec_wants(pay, expect);
 }
 // ... and from the plan's figures, once k_huff_dev_plan has read the header where it lies: the code bits in whole bytes stand for the payload
 // (the same number for every stream whose pad byte is below 8, as an encoder writes it)
@@ -125,6 +113,24 @@ int mid_dec_run_dev(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const
     return huff_dec_run_dev(c, s, MID_DEC_SHAPE, launch_mid_dec, idx, mem, *plans, answers);
 }
 }  // namespace
+// (the scan above, for the tiled class too: huff_big_dec.hip)
+bool huff_dec_promise(const uint8_t *in, size_t n, size_t *pay_out, unsigned long long *expect_out, bool (*pay_open)(size_t pay)) {
+    size_t sep = (size_t)-1;
+    for (size_t i = 0; i + 1 < std::min<size_t>(n, HDR_MAX + 8); i++) if (in[i] == 0x5C && in[i + 1] == 0x0A) { sep = i; break; }
+    if (sep == (size_t)-1 || sep + 4 > n) return false;
+    const size_t pay = n - sep - 3;
+    if (pay_open && !pay_open(pay)) return false;
+    unsigned long long expect = 0, acc = 0;
+    for (size_t i = 0; i < sep; i++) {
+        const uint8_t ch = in[i];
+        if (ch >= '0' && ch <= '9') { acc = std::min<unsigned long long>(acc * 10 + (ch - '0'), 1ull << 40); continue; }
+        if (ch != '|') continue;
+        expect += acc; acc = 0;
+        i += (i + 2 < sep && in[i + 1] == 0x5C && in[i + 2] == 'n') ? 2 : 1;      // the entry's byte is not a count's digit
+    }
+    *pay_out = pay; *expect_out = expect;
+    return true;
+}
 const BatchClass &huff_mid_class(bool compress) {
     static const BatchClass enc = {"huffman mid compress", HUFF_MID_GROUP_MIN, mid_enc_takes, class_run<MidEncClass>, class_run_dev<MidEncClass>},
                             dec = {"huffman mid decompress", HUFF_MID_GROUP_MIN, mid_dec_takes, mid_dec_run, mid_dec_run_dev, mid_dec_takes_plan};

@@ -13,6 +13,10 @@
 //              host's > 65536: a count and a node id pack into one word); a sum of counts of 0 or above PARSE_OUT_MAX; a pad byte that
 //              leaves no code bit; a deepest code of 0 bits or of more than 32
 //   tree       leaves by plan_leaf_rank over count + 1 (a count of 0 is a leaf like any other, build_tree), plan_tree, plan_codes for the depths
+// The WIDE form is the same plan for the tiled decoder's class (huff_big_dec.hip; codecs.h: HUFF_BIG_OUT_MAX, HUFF_BIG_PAY_MAX): a stream
+// that the limits above refuse for its SIZE alone -- longer than PARSE_STREAM_MAX, or promising more than PARSE_OUT_MAX bytes -- is planned
+// under PARSE_STREAM_MAX_WIDE, PARSE_OUT_MAX_WIDE and counts below PLAN_COUNT_LIMIT_WIDE (plan_item packs them: huff_plan_small.h).  A
+// stream inside the narrow sizes is judged by the narrow limits in either form, so what the other classes are handed does not change.
 // The scan reads only the member's first min(n, PARSE_SCAN_MAX) bytes, every loop is bounded by that or by the 255 nodes, and the tree's
 // state goes through stores (get / set), so the kernel keeps it in VGPRs as k_huff_batch_enc does.
 #pragma once
@@ -26,6 +30,12 @@ constexpr uint32_t PARSE_SCAN_MAX = PARSE_HDR_MAX + 8;     // bytes of a stream 
 constexpr uint32_t PARSE_STREAM_MAX = 65536 + 2048;        // DEC_STREAM_MAX (huff_small_body.h)
 constexpr uint32_t PARSE_OUT_MAX = 65536;                  // SMALL_MAX
 constexpr uint32_t PARSE_K_MAX = 9;                        // DEC_K
+constexpr uint32_t PARSE_OUT_MAX_WIDE = 262144;            // HUFF_BIG_OUT_MAX (codecs.h)
+constexpr uint32_t PARSE_PAY_MAX_WIDE = 229376;            // HUFF_BIG_PAY_MAX
+constexpr uint32_t PARSE_STREAM_MAX_WIDE = PARSE_HDR_MAX + 8 + PARSE_PAY_MAX_WIDE;
+static_assert(PARSE_OUT_MAX_WIDE < PLAN_COUNT_LIMIT_WIDE && ((unsigned long long)PARSE_OUT_MAX_WIDE << 8) < (1ull << 32), "a sum of counts and a node id pack into one word (plan_item)");
+static_assert(128ull * PLAN_COUNT_LIMIT_WIDE <= (1ull << 31), "the kernel sums 128 saturated counts in one word");
+static_assert(8ull * (PARSE_STREAM_MAX_WIDE + 4) < (1ull << 32), "a bit position in the stream is one word");
 constexpr uint32_t PARSE_NONE = 0xFFFFFFFFu;
 constexpr uint32_t PARSE_PLANNED = 0, PARSE_NOT_MINE = 1;  // the verdicts (small_dec_plan's RSN_OK / 1)
 
@@ -49,19 +59,23 @@ static_assert(sizeof(HuffDevSummary) == 16, "16 bytes a member come down");
 
 // how many of a stream's n bytes are looked at
 RSN_PLAN_FN uint32_t parse_scan_limit(uint32_t n) { return n < PARSE_SCAN_MAX ? n : PARSE_SCAN_MAX; }
-RSN_PLAN_FN bool parse_length_ok(unsigned long long n) { return n >= 8 && n <= PARSE_STREAM_MAX; }
+RSN_PLAN_FN bool parse_length_ok(unsigned long long n, bool allow_wide = false) { return n >= 8 && n <= (allow_wide ? PARSE_STREAM_MAX_WIDE : PARSE_STREAM_MAX); }
+// is the stream judged by the wide limits?  n: its length; sum: the sum of its counts (saturated counts: an upper bound that errs wide, and
+// wide refuses them)
+RSN_PLAN_FN bool parse_is_wide(bool allow_wide, uint32_t n, unsigned long long sum) { return allow_wide && (n > PARSE_STREAM_MAX || sum > PARSE_OUT_MAX); }
 // is position i the separator's?  (i + 1 < parse_scan_limit(n))
 RSN_PLAN_FN bool parse_sep_at(uint32_t b0, uint32_t b1) { return b0 == 0x5Cu && b1 == 0x0Au; }
 
-// The entries of h[0, sep): cnt1[b] = count + 1 of byte b's last entry, 0 where it has none; a count saturates at PLAN_COUNT_LIMIT.
-// h.get(i): byte i of the stream, asked for i < sep only.  false: refused.  cnt1[128] must be zero.
+// The entries of h[0, sep): cnt1[b] = count + 1 of byte b's last entry, 0 where it has none; a count saturates at `limit` (PLAN_COUNT_LIMIT,
+// or PLAN_COUNT_LIMIT_WIDE where the wide form is allowed).  h.get(i): byte i of the stream, asked for i < sep only.  false: refused.
+// cnt1[128] must be zero.
 template <class Bytes>
-RSN_PLAN_FN bool parse_scan(const Bytes &h, uint32_t sep, uint32_t *cnt1) {
+RSN_PLAN_FN bool parse_scan(const Bytes &h, uint32_t sep, uint32_t *cnt1, uint32_t limit = PLAN_COUNT_LIMIT) {
     uint32_t acc = 0;
     for (uint32_t i = 0; i < sep; i++) {
         const uint32_t ch = h.get(i);
         if (ch != '|') {
-            if (ch >= '0' && ch <= '9') { acc = acc * 10 + (ch - '0'); if (acc > PLAN_COUNT_LIMIT) acc = PLAN_COUNT_LIMIT; }
+            if (ch >= '0' && ch <= '9') { acc = acc * 10 + (ch - '0'); if (acc > limit) acc = limit; }
             continue;
         }
         const uint32_t f = acc;
@@ -79,9 +93,10 @@ RSN_PLAN_FN bool parse_scan(const Bytes &h, uint32_t sep, uint32_t *cnt1) {
     return true;
 }
 
-// the counts' verdict: a (distinct bytes) and the sum, from cnt1
-RSN_PLAN_FN bool parse_counts_ok(uint32_t a, uint32_t any_at_limit, unsigned long long sum) {
-    return a >= 2 && a <= PLAN_SYMS_MAX && !any_at_limit && sum != 0 && sum <= PARSE_OUT_MAX;
+// the counts' verdict: a (distinct bytes) and the sum, from cnt1; wide: parse_is_wide's answer, any_at_limit: a count at or above that form's limit
+RSN_PLAN_FN uint32_t parse_count_limit(bool wide) { return wide ? PLAN_COUNT_LIMIT_WIDE : PLAN_COUNT_LIMIT; }
+RSN_PLAN_FN bool parse_counts_ok(uint32_t a, uint32_t any_at_limit, unsigned long long sum, bool wide = false) {
+    return a >= 2 && a <= PLAN_SYMS_MAX && !any_at_limit && sum != 0 && sum <= (wide ? PARSE_OUT_MAX_WIDE : PARSE_OUT_MAX);
 }
 
 // the stream's bounds from the separator (small_dec_plan); diff: the pad byte, in[sep + 2].  false: it leaves no code bit
@@ -123,21 +138,22 @@ struct ParseArrayStore {
     RSN_PLAN_FN uint32_t get(uint32_t i) const { return v[i]; }
     RSN_PLAN_FN void set(uint32_t i, uint32_t x) { v[i] = x; }
 };
-inline void parse_plan_serial(const uint8_t *in, unsigned long long n64, HuffDevPlan &plan) {
+inline void parse_plan_serial(const uint8_t *in, unsigned long long n64, HuffDevPlan &plan, bool allow_wide = false) {
     plan = HuffDevPlan{};
     HuffDevBounds &p = plan.b;
     p.verdict = PARSE_NOT_MINE;
-    if (!parse_length_ok(n64)) return;
+    if (!parse_length_ok(n64, allow_wide)) return;
     const uint32_t n = (uint32_t)n64, limit = parse_scan_limit(n);
     uint32_t sep = PARSE_NONE;
     for (uint32_t i = 0; i + 1 < limit; i++) if (parse_sep_at(in[i], in[i + 1])) { sep = i; break; }
     if (sep == PARSE_NONE || sep + 4 > n) return;
     uint32_t cnt1[PLAN_SYMS_MAX] = {0};
-    if (!parse_scan(ParseArrayBytes{in}, sep, cnt1)) return;
-    uint32_t a = 0, at_limit = 0;
+    if (!parse_scan(ParseArrayBytes{in}, sep, cnt1, parse_count_limit(allow_wide))) return;
+    uint32_t a = 0, most = 0;
     unsigned long long sum = 0;
-    for (uint32_t b = 0; b < PLAN_SYMS_MAX; b++) if (cnt1[b]) { a++; at_limit |= (uint32_t)(cnt1[b] - 1 >= PLAN_COUNT_LIMIT); sum += cnt1[b] - 1; }
-    if (!parse_counts_ok(a, at_limit, sum) || !parse_bounds(n, sep, in[sep + 2], p)) return;
+    for (uint32_t b = 0; b < PLAN_SYMS_MAX; b++) if (cnt1[b]) { a++; most = cnt1[b] - 1 > most ? cnt1[b] - 1 : most; sum += cnt1[b] - 1; }
+    const bool wide = parse_is_wide(allow_wide, n, sum);
+    if (!parse_counts_ok(a, most >= parse_count_limit(wide), sum, wide) || !parse_bounds(n, sep, in[sep + 2], p)) return;
     p.expect = (uint32_t)sum;
     uint8_t leaf_byte[PLAN_SYMS_MAX] = {0};
     ParseArrayStore<PLAN_SYMS_MAX> heap{}, kids{};

@@ -233,8 +233,10 @@ int huff_small_compress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **out
 // The header parsed, the tree built and the kernel's view of the stream (everything in `a` but where its bytes are, the flags and the
 // output): the stream's bytes from in + *A0 on are what the kernel reads, as a.pay.  `lanes`: subsequences the kernel has at most, of at
 // most s_max bits.  1 = not for the small-input decoder (the caller takes the general one, which also words the errors).
-int small_dec_plan(const uint8_t *in, size_t n, uint32_t lanes, uint32_t s_max, SmallDecArgs &a, size_t *A0, unsigned long long *expect_out) {
-    if (n < 8 || n > DEC_STREAM_MAX) return 1;
+int small_dec_plan(const uint8_t *in, size_t n, uint32_t lanes, uint32_t s_max, SmallDecArgs &a, size_t *A0, unsigned long long *expect_out, bool wide) {
+    const size_t stream_max = wide ? PARSE_STREAM_MAX_WIDE : DEC_STREAM_MAX, out_max = wide ? PARSE_OUT_MAX_WIDE : SMALL_MAX;
+    const unsigned long long count_max = wide ? PLAN_COUNT_LIMIT_WIDE - 1 : SMALL_MAX;
+    if (n < 8 || n > stream_max) return 1;
     // ---- strings.SplitN(content, "\\\n", 2) (huffman.go:261); the counts (huffman.go:196-227)
     size_t sep = (size_t)-1;
     for (size_t i = 0; i + 1 < std::min<size_t>(n, HDR_MAX + 8); i++) if (in[i] == 0x5C && in[i + 1] == 0x0A) { sep = i; break; }
@@ -242,8 +244,8 @@ int small_dec_plan(const uint8_t *in, size_t n, uint32_t lanes, uint32_t s_max, 
     std::vector<HuffSym> syms; std::string msg;
     if (!parse_header(in, sep, syms, msg) || syms.size() < 2 || syms.size() > 128) return 1;
     unsigned long long expect = 0;
-    for (const HuffSym &sy : syms) { if (sy.rune >= 0x80 || sy.freq > SMALL_MAX) return 1; expect += sy.freq; }
-    if (expect == 0 || expect > SMALL_MAX) return 1;
+    for (const HuffSym &sy : syms) { if (sy.rune >= 0x80 || sy.freq > count_max) return 1; expect += sy.freq; }
+    if (expect == 0 || expect > out_max) return 1;
     const size_t pay = sep + 3, sn = n - sep - 2;
     const unsigned diff = in[sep + 2];
     const unsigned long long nbits = (unsigned long long)(sn - 1) * 8;
@@ -309,7 +311,7 @@ int huff_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **o
 // The members of a decoding class: a stream the one-workgroup decoder cannot take -- runes, over the cutoff, anything small_dec_plan
 // refuses -- goes to `back` untouched; the rest in groups (run_groups): the table entry is the plan's SmallDecArgs with its pointers into
 // the staging, the input the stream from the 4-byte boundary the kernel reads from, and two status words (done / handed back, decoded bytes).
-int huff_dec_run(Ctx &c, const HuffDecShape &shape, HuffDecLaunch launch, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
+int huff_dec_run(Ctx &c, const HuffDecShape &shape, const HuffDecLaunch &launch, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
                  const SmallTake &take, std::vector<size_t> &back, size_t *failed) {
     struct Plan { size_t i, A0; unsigned long long expect; SmallDecArgs a; };
     std::vector<Plan> plans;

@@ -1,5 +1,5 @@
 // huff_small_body.h -- the device code that the Huffman kernels of huff_small.hip (a single small call, the batch kernels for members of
-// up to 16 KiB) and of huff_mid.hip (the batch kernels for members of 16 to 64 KiB) share: the lane-map decoder of one workgroup, the
+// up to 16 KiB), of huff_mid.hip (the batch kernels for members of 16 to 64 KiB) and of huff_big_dec.hip (the tiled decoder above that) share: the lane-map decoder of one workgroup, the
 // one-workgroup encoder that builds its own tree, their scans and their last store.  The bodies take what differs between the kernels
 // -- lanes, LDS sizes, where the large LDS arrays live -- as template parameters and arguments; DESIGN 4.7.
 #pragma once
@@ -22,14 +22,15 @@ struct SmallDecArgs {
     uint32_t flat;            // every code has this length (0: lengths differ): the boundaries are where the arithmetic says -- as many phases as the code has bits, and none to find
     uint32_t seq;             // this call's number: what a block's flag holds once its map is out
     uint8_t *hout; uint32_t *status;      // status[b]: FLAG_PENDING, then 0 = block b done, 1 = not for this kernel; status[32]: decoded bytes (batch: status[1])
-    uint32_t *g_maps, *g_flags;           // device memory: [block][32] (exit << 24 | symbols), [block] (k_small_dec only)
+    uint32_t *g_maps, *g_flags;           // device memory: [block][32] (exit << 24 | symbols), [block] (k_small_dec; g_maps: k_huff_big_dec_map too, its member's scratch)
     uint32_t out_max, pad_[3];    // batch: bytes the member's output slot takes (k_small_dec: SMALL_MAX)
     uint16_t child[256];      // [2 * node + bit]: 0x8000 | byte for a leaf, else the internal node
 };
 static_assert(sizeof(SmallDecArgs) % 16 == 0, "a batch table entry is copied in dwords and the next one starts 16-aligned");
 // The header parsed, the tree built and the kernel's view of the stream (huff_small.hip).  `lanes`: subsequences the kernel has at most, of
 // at most s_max bits.  1 = not for the lane-map decoder (the caller takes the general one, which also words the errors).
-int small_dec_plan(const uint8_t *in, size_t n, uint32_t lanes, uint32_t s_max, SmallDecArgs &a, size_t *A0, unsigned long long *expect_out);
+// wide: the limits of the tiled class instead (huff_parse_small.h: PARSE_STREAM_MAX_WIDE, PARSE_OUT_MAX_WIDE, counts below PLAN_COUNT_LIMIT_WIDE).
+int small_dec_plan(const uint8_t *in, size_t n, uint32_t lanes, uint32_t s_max, SmallDecArgs &a, size_t *A0, unsigned long long *expect_out, bool wide = false);
 
 // ---- the decoding classes (huff_small.hip's k_huff_batch_dec, huff_mid.hip's k_huff_mid_dec) differ in what one workgroup holds and in the
 // launch: the plan in front of the packer and the packing itself are huff_dec_run's (huff_small.hip; run_groups, group_run.h).
@@ -37,15 +38,20 @@ struct HuffDecShape {
     uint32_t lanes, s_max;                         // subsequences of one workgroup; bits of one at most
     uint32_t pay_max, out_max;                     // payload bytes / decoded bytes of a member at most
 };
-using HuffDecLaunch = int (*)(Ctx &c, hipStream_t s, uint32_t members, const SmallDecArgs *tab);
-int huff_dec_run(Ctx &c, const HuffDecShape &shape, HuffDecLaunch launch, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
+using HuffDecLaunch = std::function<int(Ctx &c, hipStream_t s, uint32_t members, const SmallDecArgs *tab)>;   // (a class's function, or the tiled class's three launches with their grid)
+int huff_dec_run(Ctx &c, const HuffDecShape &shape, const HuffDecLaunch &launch, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
                  const SmallTake &take, std::vector<size_t> &back, size_t *failed);
 // The same classes on device buffers (huff_dev.hip): the members idx[k] of `mem`, every one with a planned summary that the class's
 // takes_plan has accepted, in run_groups_dev's groups on device staging -- a gather kernel copies each stream from its 4-byte boundary into
 // its input slot and completes its SmallDecArgs from the plan table, the decoder is launched unchanged, and a scatter kernel copies what
 // fits to d_out and turns the decoder's two status words into the answer: GROUP_BACK, or the decoded length.
-int huff_dec_run_dev(Ctx &c, hipStream_t s, const HuffDecShape &shape, HuffDecLaunch launch, const std::vector<size_t> &idx, const rsn_dev_member *mem,
-                     const DevPlans &plans, std::vector<uint32_t> &answers);
+// group_bytes: the staging of a group at most (a class whose members are large states a larger group of its own: huff_big_dec.hip).
+int huff_dec_run_dev(Ctx &c, hipStream_t s, const HuffDecShape &shape, const HuffDecLaunch &launch, const std::vector<size_t> &idx, const rsn_dev_member *mem,
+                     const DevPlans &plans, std::vector<uint32_t> &answers, size_t group_bytes = SMALL_GROUP_BYTES);
+// What a stream's header promises, from a scan that allocates nothing (huff_mid.hip: the classes' takes() run it for every member of a
+// batch): the payload behind "\\\n" and the pad byte, and the sum of the counts -- an upper bound that is exact for every header an
+// encoder writes.  pay_open (may be null): asked with the payload before the counts are scanned; false ends the scan.  false: no separator.
+bool huff_dec_promise(const uint8_t *in, size_t n, size_t *pay, unsigned long long *expect, bool (*pay_open)(size_t pay) = nullptr);
 // what a decoding class asks of a planned stream beside its own cutoffs: its lanes hold the code bits
 inline bool huff_dec_shape_takes(const HuffDecShape &shape, const HuffDevSummary &sum) {
     uint32_t S, T;
@@ -175,12 +181,20 @@ __device__ __forceinline__ uint32_t byte_of(uint32_t packed, uint32_t j) { retur
 // What the rune decoder (huff_rune_dec.hip) needs beside that: CHILD_MAX entries of `child` (the byte alphabets' 256 are a.child; a tree of
 // 256 leaves has 510) and !STORE -- the decoded symbols stay in s_out[0 ..) for the caller, nothing is stored to a.hout and no status word
 // is written.  Returns the symbols this block decoded, DEC_BODY_BACK where the stream is not for the lane maps (STORE: status 1 is out).
+// TILE (huff_big_dec.hip: the MULTI form's two halves as two launches, so that no block waits for another; MULTI is set, block b is tile b
+// of a stream whose tiles need not be co-resident).  TILE_MAP: the body up to the publication -- the tile's 32-entry map is stored to
+// a.g_maps[b * 32 ..) and nothing else is.  TILE_EMIT: the body behind the wait -- the tile's true entry and its first output byte are
+// given (a kernel between the two has composed the maps), only that entry of the first lane is answered, the bytes [tile_base, tile_base +
+// count) are stored to a.hout and no status word is: a.out_max bounds the output as it does where one block holds the stream.
 constexpr uint32_t DEC_BODY_BACK = 0xFFFFFFFFu;
-template <uint32_t PAY_WORDS, uint32_t OUT_CAP, bool MULTI, int DLN, uint32_t CHILD_MAX, bool STORE>
-__device__ __forceinline__ uint32_t lane_dec_body(const SmallDecArgs &a, const uint16_t *child /*[a.n_child]*/, uint32_t *s_pay /*[PAY_WORDS]*/, uint8_t *s_out /*[OUT_CAP + 32], 16-aligned*/) {
+constexpr int TILE_NONE = 0, TILE_MAP = 1, TILE_EMIT = 2;
+template <uint32_t PAY_WORDS, uint32_t OUT_CAP, bool MULTI, int DLN, uint32_t CHILD_MAX, bool STORE, int TILE = TILE_NONE>
+__device__ __forceinline__ uint32_t lane_dec_body(const SmallDecArgs &a, const uint16_t *child /*[a.n_child]*/, uint32_t *s_pay /*[PAY_WORDS]*/, uint8_t *s_out /*[OUT_CAP + 32], 16-aligned*/,
+                                                  uint32_t tile_entry = 0, uint32_t tile_base = 0) {
     constexpr int DTN = DLN + 64;                             // the lanes and the wavefront of the block's first lane
     constexpr int PERC = (CHILD_MAX + DTN - 1) / DTN;         // entries of child[] a thread loads
-    static_assert(STORE || !MULTI, "the symbols stay in LDS only where one block holds the whole stream");
+    static_assert(STORE || !MULTI || TILE == TILE_MAP, "the symbols stay in LDS only where one block holds the whole stream");
+    static_assert(TILE == TILE_NONE || MULTI, "a tile is a block of a stream of many");
     __shared__ uint32_t s_lut[1u << DEC_K];                   // byte | second byte << 8 | length << 16 | length of both << 21 | two << 26, or 0x80000000 | internal node reached after K bits
     __shared__ uint16_t s_child[CHILD_MAX];
     __shared__ uint32_t s_st[DLN], s_ex[DLN], s_n[DLN];          // per lane: its starts (offsets from its subsequence's first bit, a byte each), the exits that belong to them (offsets from the next subsequence's first bit), their number
@@ -188,7 +202,7 @@ __device__ __forceinline__ uint32_t lane_dec_body(const SmallDecArgs &a, const u
     __shared__ uint32_t s_ex32[32], s_cn32[32];               // the block's first lane: exit and symbols for every start in its first 32 bits
     __shared__ uint32_t s_wto[DLN / 64 + 1], s_wc[DLN / 64 + 1][4];                 // the wavefronts' maps
     __shared__ uint32_t s_blk[4][2];                          // entry j of lane 1 -> (exit of the block's last lane, symbols of lanes 1..)
-    __shared__ uint32_t s_all[MULTI ? DEC_BLOCKS * 32 : 1];   // the maps of the blocks before this one
+    __shared__ uint32_t s_all[MULTI && TILE == TILE_NONE ? DEC_BLOCKS * 32 : 1];   // the maps of the blocks before this one
     __shared__ uint32_t s_true[3];                            // this block's true entry (a start of its first lane), its first output byte, a failure
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = MULTI ? blockIdx.x : 0u, n_blk = MULTI ? gridDim.x : 1u;
     const uint32_t S = a.S;
@@ -249,7 +263,7 @@ __device__ __forceinline__ uint32_t lane_dec_body(const SmallDecArgs &a, const u
     };
     // ---- the block's first lane, entered at every bit a codeword could start at (block 0: at the stream's first code bit, nowhere else)
     const uint32_t flat0 = a.flat ? (a.flat - (b * DLN * S) % a.flat) % a.flat : 0u;      // flat code: the one bit this block can be entered at
-    if (tid >= DLN && tid < DLN + 32 && (b == 0 ? tid == DLN : (a.flat == 0 || (uint32_t)(tid - DLN) == flat0))) {
+    if (tid >= DLN && tid < DLN + 32 && (TILE == TILE_EMIT ? (uint32_t)(tid - DLN) == tile_entry : b == 0 ? tid == DLN : (a.flat == 0 || (uint32_t)(tid - DLN) == flat0))) {
         const uint32_t hi0 = min(end, blk_lo - base_bit + S);
         uint32_t e, c;
         run_in(blk_lo - base_bit, hi0, tid - DLN, e, c);
@@ -362,13 +376,14 @@ __device__ __forceinline__ uint32_t lane_dec_body(const SmallDecArgs &a, const u
         for (int k = 0; k < 4; k++) if ((uint32_t)k < n1 && byte_of(s1, k) == off) j = k;
         return j;
     };
-    if constexpr (MULTI) {                                                      // (one block alone: entered at its first bit, nothing to publish or wait for)
+    if constexpr (MULTI && TILE != TILE_EMIT) {                                 // (one block alone: entered at its first bit, nothing to publish or wait for)
         if (tid < 32) {
             uint32_t e = s_ex32[tid], c = s_cn32[tid];
             if (L > 1 && e != OFF_BAD) { const uint32_t j = lane1_index(e); if (j < 4) { c += s_blk[j][1]; e = s_blk[j][0]; } else e = OFF_BAD; }
             if (lost) e = OFF_BAD;
             a.g_maps[b * 32 + tid] = e << 24 | (c & 0xFFFFFFu);
         }
+        if constexpr (TILE == TILE_MAP) return 0;                               // (the launch's end publishes it)
         __threadfence();
         __syncthreads();
         if (tid == 0) {
@@ -380,8 +395,8 @@ __device__ __forceinline__ uint32_t lane_dec_body(const SmallDecArgs &a, const u
         __syncthreads();
     }
     if (tid == 0) {
-        uint32_t c = 0, base = 0, fail = lost ? 1u : 0u;                        // (block 0 is entered at its first bit)
-        for (uint32_t i = 0; i < b && !fail; i++) {
+        uint32_t c = TILE ? tile_entry : 0u, base = TILE ? tile_base : 0u, fail = lost ? 1u : 0u;   // (block 0 is entered at its first bit)
+        for (uint32_t i = 0; TILE == TILE_NONE && i < b && !fail; i++) {
             const uint32_t e = s_all[i * 32 + c];
             if ((e >> 24) == OFF_BAD || (e >> 24) >= 32) { fail = 1; break; }
             base += e & 0xFFFFFFu; c = e >> 24;
@@ -411,8 +426,8 @@ __device__ __forceinline__ uint32_t lane_dec_body(const SmallDecArgs &a, const u
     if (real && tid + 1 == L) s_true[0] = blk_cnt_hint;
     __syncthreads();
     const uint32_t blk_cnt = s_true[0];
-    if (bad || blk_cnt + (MULTI ? 16u : 0u) > OUT_CAP || out_base + blk_cnt > (MULTI ? SMALL_MAX : a.out_max)) {
-        if constexpr (STORE) block_done(&a.status[b], 1);
+    if (bad || blk_cnt + (MULTI ? 16u : 0u) > OUT_CAP || out_base + blk_cnt > (MULTI && TILE == TILE_NONE ? SMALL_MAX : a.out_max)) {
+        if constexpr (STORE && TILE == TILE_NONE) block_done(&a.status[b], 1);
         return DEC_BODY_BACK;
     }
     const uint32_t shift = out_base & 15;                                       // LDS byte i + shift <-> output byte out_base + i: 16-byte units line up
@@ -426,8 +441,10 @@ __device__ __forceinline__ uint32_t lane_dec_body(const SmallDecArgs &a, const u
             if (u0 >= lo && u1 <= hi) *reinterpret_cast<uint4 *>(dst + u0) = *reinterpret_cast<const uint4 *>(s_out + u0);
             else for (uint32_t x = max(u0, lo); x < min(u1, hi); x++) dst[x] = s_out[x];
         }
-        if (tid == 0 && b + 1 == n_blk) a.status[MULTI ? DEC_BLOCKS : 1u] = out_base + blk_cnt;
-        block_done(&a.status[b], 0);
+        if constexpr (TILE == TILE_NONE) {
+            if (tid == 0 && b + 1 == n_blk) a.status[MULTI ? DEC_BLOCKS : 1u] = out_base + blk_cnt;
+            block_done(&a.status[b], 0);
+        }
     }
     return blk_cnt;
 }

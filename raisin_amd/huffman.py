@@ -54,12 +54,24 @@ MID_GROUP_MIN = 4
 # csrc/huff_big.hip): chunks above MID_IN_MAX and up to BIG_IN_MAX bytes of a byte alphabet are cut into tiles of BIG_TILE bytes,
 # a workgroup each, and go through three launches per group -- count, plan, emit -- when a call holds at least BIG_GROUP_MIN of them; a
 # group holds up to BIG_GROUP_BYTES of staging.  A chunk whose deepest code has more than 24 bits (possible from 196418 bytes on) is handed
-# back to the single call's path, like one with a single distinct byte or a byte >= 0x80.  Compress only: the streams of such chunks
-# decode through the single call's path inside DecompressBatch.
+# back to the single call's path, like one with a single distinct byte or a byte >= 0x80.
 BIG_IN_MAX = 262144
 BIG_TILE = 16384
 BIG_GROUP_MIN = 4
 BIG_GROUP_BYTES = 67108864
+# The way back (csrc/codecs.h HUFF_BIG_OUT_MAX / HUFF_BIG_PAY_MAX / HUFF_BIG_DEC_GROUP_MIN; csrc/huff_big_dec_layout.h BIGD_LANES / BIGD_S /
+# BIGD_OUT_CAP; csrc/huff_big_dec.hip): streams of a byte alphabet whose header promises more than MID_OUT_MAX and at most
+# BIG_OUT_MAX bytes from at most BIG_PAY_MAX bytes of payload are cut into tiles of BIG_DEC_LANES lanes of BIG_DEC_LANE_BITS code bits, a
+# workgroup each, and go through three launches per group -- map, chain, emit -- when a decompress batch holds at least BIG_DEC_GROUP_MIN
+# of them.  A stream with a tile of more than BIG_DEC_OUT_CAP - 16 symbols (fewer than 1.875 bits a symbol over the whole tile), one whose
+# tiles need more than four phases a lane, and a malformed one take the single call's path inside the batch.  Every stream the big class
+# above writes is one of the class.
+BIG_OUT_MAX = 262144
+BIG_PAY_MAX = 229376
+BIG_DEC_GROUP_MIN = 4
+BIG_DEC_LANES = 960
+BIG_DEC_LANE_BITS = 64
+BIG_DEC_OUT_CAP = 32768
 
 # The rune class of the compress batch calls (csrc/codecs.h HUFF_RUNE_SYMS_MAX / HUFF_RUNE_GROUP_MIN; csrc/huff_rune.hip): chunks
 # of at most BATCH_COMPRESS_INPUT_MAX bytes that hold a byte >= 0x80 -- UTF-8 text, or no UTF-8 at all -- go a workgroup each through one
@@ -80,7 +92,8 @@ def DecompressBatch(streams):
     """Decompress(stream) for every stream of the list in one call (rsn_huffman_decompress_batch): small streams many to a launch, a
     workgroup each; streams of up to MID_PAY_MAX bytes of payload that decode to at most MID_OUT_MAX bytes likewise (csrc/huff_mid.hip)
     when the call holds at least MID_GROUP_MIN of them; streams of a rune alphabet that decode to at most RUNE_OUT_MAX bytes likewise
-    (csrc/huff_rune_dec.hip) when it holds at least RUNE_DEC_GROUP_MIN of them; the rest through the single call's path.  Each result equals Decompress(stream); a failing stream raises for the
+    (csrc/huff_rune_dec.hip) when it holds at least RUNE_DEC_GROUP_MIN of them; streams of a byte alphabet that decode to more than MID_OUT_MAX and at most
+    BIG_OUT_MAX bytes in tiles, three launches a group (csrc/huff_big_dec.hip), when it holds at least BIG_DEC_GROUP_MIN of them; the rest through the single call's path.  Each result equals Decompress(stream); a failing stream raises for the
     whole list (the message names the lowest failing index: "member <i>: ...")."""
     return _lib.call_batch(_lib.lib().rsn_huffman_decompress_batch, streams)
 
