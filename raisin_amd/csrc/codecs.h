@@ -1,6 +1,7 @@
 // codecs.h -- device-resident codec entry points shared between translation units.
 #pragma once
 
+#include <algorithm>
 #include <functional>
 
 #include "group_layout.h"
@@ -8,6 +9,7 @@
 #include "lzss_legacy.h"
 #include "rsn_common.h"
 #include "huff_parse_small.h"   // (behind the HIP runtime: its functions are __host__ __device__ under hipcc)
+#include "huff_rune_select.h"
 
 namespace rsn {
 
@@ -85,7 +87,7 @@ struct BatchClass {
     bool (*takes)(const uint8_t *in, size_t n, int64_t window);
     int (*run)(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
                const SmallTake &take, std::vector<size_t> &back, size_t *failed, std::vector<size_t> *back_runes);
-    // the device-buffer form (the batch calls on device buffers; group_run.h: run_groups_dev): the members `idx` of `mem` through the same
+    // the device-buffer form (the batch calls on device buffers; group_run.h: run_groups_staged): the members `idx` of `mem` through the same
     // groups and the same kernel on `s`, the staging in device scratch; answers[k]: GROUP_BACK, or member idx[k]'s length -- its bytes are in
     // its d_out when that is at most its out_cap.  plans: null but for the Huffman decoders, whose table entries are completed on the device
     // from the plans.
@@ -151,20 +153,32 @@ constexpr size_t HUFF_BIG_DEC_GROUP_MIN = 4;
 static_assert((unsigned long long)HUFF_BIG_PAY_MAX * 8 >= (unsigned long long)HUFF_BIG_IN_MAX * 7 && HUFF_BIG_OUT_MAX >= HUFF_BIG_IN_MAX,
               "the decoder takes every stream the encoder writes");
 const BatchClass &huff_big_dec_class();
+// ---- the second stage.  A class BEHIND the rows has no takes(): what the rows' kernels answered says which members are its.  Once the
+// rows have run, every flow (rsn_api.hip: batch_front, layer_batch_run) OFFERS it one POOL of members -- RUNES: those the rows handed back
+// as GROUP_BACK_RUNES; REST: everything left for the single call so far -- in one loop over what batch_classes lists behind the rows, and
+// it runs grouped those it chooses when there are at least its minimum of them (huff_rune_select.h: the rules).
+//   offer       host form: the members it runs leave the pool, take() receives their results; whatever else a RUNES pool held, and what
+//               its kernel hands back, joins `rest` (a REST pool is `rest`), which the flow sorts afterwards.  *failed as run() sets it.
+//   offer_dev   device form, the same choice: the members it runs leave the pool for `idx` (which comes empty), answers[k] is idx[k]'s, and the flow settles
+//               them as a row's.  A failure is about behind_failed: the first member chosen, or, when none was yet, the lowest offered.
+struct BehindClass {
+    enum Pool { RUNES, REST } pool;
+    int (*offer)(Ctx &c, std::vector<size_t> &pool, std::vector<size_t> &rest, const uint8_t *const *ins, const size_t *lens, const SmallTake &take, size_t *failed);
+    int (*offer_dev)(Ctx &c, hipStream_t s, std::vector<size_t> &pool, std::vector<size_t> &rest, const rsn_dev_member *mem, const DevPlans *plans,
+                     std::vector<size_t> &idx, std::vector<uint32_t> &answers);
+};
+inline size_t behind_failed(const std::vector<size_t> &idx, const std::vector<size_t> &pool) { return !idx.empty() ? idx[0] : pool.empty() ? 0 : *std::min_element(pool.begin(), pool.end()); }
 // huff_rune.hip: the members of at most HUFF_RUNE_IN_MAX bytes that k_huff_batch_enc hands back as GROUP_BACK_RUNES -- UTF-8 text, bytes
 // that are no UTF-8 at all -- a workgroup each in k_huff_batch_rune_enc: the runes as Go's `range string(b)` yields them counted in an
 // LDS table, the Go-exact tree of 2 to HUFF_RUNE_SYMS_MAX leaves in one wavefront (huff_plan_rune.h), header and code bits as the byte
-// encoder writes them.  It hands back more distinct runes than that, and a single one.  No row of batch_classes: no member is asked
-// whether it is of the class -- the byte encoder's answer says so -- and both batch flows (rsn_api.hip) run it behind the rows when a
-// call holds at least HUFF_RUNE_GROUP_MIN such members; fewer take the single call, as every one did before.
+// encoder writes them.  It hands back more distinct runes than that, and a single one.  Behind the rows of Huffman compress, pool RUNES:
+// a call that holds at least HUFF_RUNE_GROUP_MIN such members runs them; fewer take the single call, as every one did before.
 // HUFF_RUNE_GROUP_MIN = 16 is the floor, not a crossover: calls with up to 12 such members keep their launches as they were, and at 16
 // members the grouped route already is 8 to 27 times as fast as the single calls it replaces, at 25 B, 1 KiB and 16 KiB, from host and
 // from device buffers -- no count tried (16 to 4096) loses at any size (profiles/huff_rune_batch.txt).
 // Mirrored as raisin_amd.huffman.RUNE_SYMS_MAX / RUNE_GROUP_MIN.
-constexpr uint32_t HUFF_RUNE_IN_MAX = 16384;
 constexpr uint32_t HUFF_RUNE_SYMS_MAX = 256;
-constexpr size_t HUFF_RUNE_GROUP_MIN = 16;
-const BatchClass &huff_rune_class();
+const BehindClass &huff_rune_class();
 // huff_rune_dec.hip: the way back.  A stream whose header names a rune >= 0x80 -- what the byte decoders' plans refuse -- a workgroup each
 // in k_huff_batch_rune_dec: the workgroup parses the header itself (huff_parse_rune.h: at most HUFF_RUNE_SYMS_MAX distinct runes, the
 // Go-exact tree in one wavefront), decodes the payload with the byte decoders' lane maps (huff_small_body.h: lane_dec_body) to a leaf rank
@@ -172,12 +186,12 @@ const BatchClass &huff_rune_class();
 // HUFF_RUNE_OUT_MAX bytes from at most HUFF_RUNE_PAY_MAX bytes of payload (group_layout.h) -- so every stream the rune encoder writes for a
 // member of valid UTF-8 is one this decoder takes; a byte that is no UTF-8 comes back as the three bytes of U+FFFD, so a lossy member's
 // stream may promise up to three times the member's size and goes to the single call when that passes HUFF_RUNE_OUT_MAX -- and hands back what the byte decoders hand back, a code beyond 32 bits, and a stream that decodes to more
-// bytes than its header promises.  No row of batch_classes either: both batch flows (rsn_api.hip) offer it the members the rows left for
-// the single call, the host form after a scan of the header that allocates nothing (huff_rune_dec_scan), the device form after ONE more
-// plan launch over them (k_huff_dev_rune_plan), and it runs when at least HUFF_RUNE_DEC_GROUP_MIN of them are planned.
+// bytes than its header promises.  Behind the rows of Huffman decompress, pool REST: the host form plans its candidates with a scan of the
+// header that allocates nothing (parse_rune_light), the device form -- whose candidates are what k_huff_dev_plan answered PARSE_NOT_MINE
+// -- with ONE more plan launch over them where they lie (k_huff_dev_rune_plan: one copy down, one host wait), and it runs when at least
+// HUFF_RUNE_DEC_GROUP_MIN are candidates and as many of them are planned.  What the kernel hands back stays in `rest`.
 // HUFF_RUNE_DEC_GROUP_MIN: see DESIGN 4.7 for what was measured.  Mirrored as raisin_amd.huffman.RUNE_OUT_MAX / RUNE_PAY_MAX /
 // RUNE_DEC_GROUP_MIN.
-constexpr size_t HUFF_RUNE_DEC_GROUP_MIN = 16;
 constexpr bool huff_rune_dec_takes_the_encoder() {
     for (uint32_t n = 2; n <= HUFF_RUNE_IN_MAX; n++) {
         const uint32_t hdr = (n < 256 ? n : 256u) * 10 + 3, pay = huff_rune_stream_max(n) - hdr;
@@ -186,28 +200,22 @@ constexpr bool huff_rune_dec_takes_the_encoder() {
     return true;
 }
 static_assert(huff_rune_dec_takes_the_encoder(), "header, payload and length of every stream the rune encoder writes are ones the rune decoder takes; valid UTF-8 decodes to the member's own n bytes");
-// the light scan of a stream in host memory: planned (a member for the class, with what it promises and where its payload starts) or not
-HuffDevSummary huff_rune_dec_scan(const uint8_t *in, size_t n);
-// Host form: of the members `rest` (sorted; what the rows left for the single call) those the scan plans run grouped when there are at
-// least the minimum of them -- take() receives their results -- and leave `rest`; what the kernel hands back stays in it.
-int huff_rune_dec_offer(Ctx &c, std::vector<size_t> &rest, const uint8_t *const *ins, const size_t *lens, const SmallTake &take, size_t *failed);
-// Device form: the members of `rest` that k_huff_dev_plan answered PARSE_NOT_MINE and that are short enough are planned where they lie by
-// ONE launch of k_huff_dev_rune_plan (one copy down, one host wait) when there are at least the minimum of them; the planned ones, when
-// still that many, leave `rest` for `idx` and run in run_groups_dev's groups -- answers[k]: GROUP_BACK or member idx[k]'s length.
-int huff_rune_dec_offer_dev(Ctx &c, hipStream_t s, std::vector<size_t> &rest, const rsn_dev_member *mem, const DevPlans &plans,
-                            std::vector<size_t> &idx, std::vector<uint32_t> &answers);
-// the rows of a layer and direction in order of precedence: LZSS asks its small class first, Huffman decompress its mid class (a short
-// stream may promise more output than k_huff_batch_dec's workgroup holds) and then its tiled class, for the same reason: the small class
-// takes by the stream's length alone, and 8 KiB of payload can promise more than HUFF_MID_OUT_MAX bytes
+const BehindClass &huff_rune_dec_class();
+// the rows of a layer and direction in order of precedence, and the classes behind them: LZSS asks its small class first, Huffman
+// decompress its mid class (a short stream may promise more output than k_huff_batch_dec's workgroup holds) and then its tiled class, for
+// the same reason: the small class takes by the stream's length alone, and 8 KiB of payload can promise more than HUFF_MID_OUT_MAX bytes
 enum class BatchLayer { HUFFMAN, LZSS };
 struct BatchRows {
     const BatchClass *const *first; size_t n;
+    const BehindClass *const *behind = nullptr; size_t n_behind = 0;
     template <size_t N> BatchRows(const BatchClass *const (&rows)[N]) : first(rows), n(N) {}
+    template <size_t N, size_t M> BatchRows(const BatchClass *const (&rows)[N], const BehindClass *const (&after)[M]) : first(rows), n(N), behind(after), n_behind(M) {}
 };
 inline BatchRows batch_classes(BatchLayer layer, bool compress) {
     static const BatchClass *const huff_enc[] = {&huff_small_class(true), &huff_mid_class(true), &huff_big_class()}, *const huff_dec[] = {&huff_mid_class(false), &huff_big_dec_class(), &huff_small_class(false)};
+    static const BehindClass *const huff_enc_behind[] = {&huff_rune_class()}, *const huff_dec_behind[] = {&huff_rune_dec_class()};
     static const BatchClass *const lzss_enc[] = {&lzss_small_class(true), &lzss_mid_class(true)}, *const lzss_dec[] = {&lzss_small_class(false), &lzss_mid_class(false)};
-    if (layer == BatchLayer::HUFFMAN) return compress ? BatchRows(huff_enc) : BatchRows(huff_dec);
+    if (layer == BatchLayer::HUFFMAN) return compress ? BatchRows(huff_enc, huff_enc_behind) : BatchRows(huff_dec, huff_dec_behind);
     return compress ? BatchRows(lzss_enc) : BatchRows(lzss_dec);
 }
 // until none of flags[0 .. n) is GROUP_PENDING (group_layout.h; the single small calls): polled for 5 ms, then the stream is waited for the

@@ -1,8 +1,9 @@
 // group_dev.hip -- the grouped batch kernels on members that lie in device memory (the batch calls on device buffers, rsn.h).
 // The host form (group_run.h: run_groups) packs a group's members into pinned staging with memcpy and reads the results out of it; here the
 // staging is device scratch and two kernels stand where the host's copies stood: k_group_gather in front of the class's kernel,
-// k_group_scatter behind it.  The class's kernel is the host form's, launched unchanged with the device staging as `base`.  What crosses
-// PCIe per group is its tables (64 bytes a member, one copy up) and per class its answers (4 bytes a member, one copy down).
+// k_group_scatter behind it.  The class's kernel is the host form's, launched unchanged with the device staging as `base`.  The loop over
+// the groups is run_groups_staged (group_run.h), the one driver of every family; this unit is the family of SmallMember entries.  What
+// crosses PCIe per group is its tables (64 bytes a member, one copy up) and per class its answers (4 bytes a member, one copy down).
 #include "group_run.h"
 
 namespace rsn {
@@ -67,60 +68,22 @@ __global__ __launch_bounds__(GD_THREADS) void k_group_scatter(const GatherEntry 
 
 }  // namespace
 
-int run_groups_dev(Ctx &c, hipStream_t s, const char *what, const std::vector<size_t> &idx, const rsn_dev_member *mem,
-                   size_t (*in_bytes)(size_t n), size_t (*out_bytes)(size_t n), const GroupLaunch &launch, std::vector<uint32_t> &answers) {
-    return run_groups_dev_sized(c, s, what, idx, mem, [&](size_t k) { return in_bytes(mem[idx[k]].n); }, [&](size_t k) { return out_bytes(mem[idx[k]].n); }, launch, answers);
-}
-
-int run_groups_dev_sized(Ctx &c, hipStream_t s, const char *what, const std::vector<size_t> &idx, const rsn_dev_member *mem,
-                         const GroupSlotBytes &in_bytes, const GroupSlotBytes &out_bytes, const GroupLaunch &launch, std::vector<uint32_t> &answers,
-                         size_t group_bytes) {
-    const size_t count = idx.size();
-    answers.assign(count, GROUP_PENDING);
-    if (count == 0) return RSN_OK;
-    auto need = [&](size_t k) { return group_need(GD_ENTRY, in_bytes(k), out_bytes(k)); };
-    // the groups first: the largest one sizes the staging, and every group's tables have a pinned region of their own -- no group waits
-    // for the copy of the one before it
-    std::vector<GroupCut> cuts;
-    size_t stage = 0;
-    for (size_t j = 0; j < count;) { const GroupCut cut = next_group(j, count, SMALL_GROUP_MAX, group_bytes, need); stage = std::max(stage, cut.bytes); cuts.push_back(cut); j = cut.hi; }
-    const size_t tables = count * GD_ENTRY, down = round_up(count * sizeof(uint32_t), 16);
-    Admission gate(c, slotset::GROUP_DEV); gate.admit(stage + down, ADMIT_FROM);
-    void *pp, *d_stage, *d_ans;
-    int rc = pinned_buf(c, tables + down, &pp); if (rc) return rc;
-    rc = dev_buf(c, Slot::GD_STAGE, stage + 64, &d_stage); if (rc) return rc;
-    rc = dev_buf(c, Slot::GD_LENS, down, &d_ans); if (rc) return rc;
-    uint8_t *pin = (uint8_t *)pp, *base = (uint8_t *)d_stage;
-    size_t j = 0;
-    for (const GroupCut &cut : cuts) {
-        const size_t g = cut.hi - j;
-        SmallMember *tab = (SmallMember *)(pin + j * GD_ENTRY);
-        GatherEntry *gat = (GatherEntry *)(tab + g);
-        GroupLayout lay(g, GD_ENTRY);
-        for (size_t q = 0; q < g; q++) {
-            const rsn_dev_member &m = mem[idx[j + q]];
-            const size_t ib = in_bytes(j + q), ob = out_bytes(j + q);
-            const MemberSlots o = lay.member(ib, ob);
-            tab[q] = SmallMember{o.in, (uint32_t)m.n, o.out, o.status};
-            gat[q] = GatherEntry{(const uint8_t *)m.d_in, (uint8_t *)m.d_out, m.d_out ? (unsigned long long)m.out_cap : 0ull,
-                                 (uint32_t)m.n, o.in, (uint32_t)ib, o.out, (uint32_t)ob, o.status};
-        }
-        if (lay.end() != cut.bytes || lay.end() > 0xFFFFFFFFull) return c.fail(RSN_ERR_DEVICE, "%s: internal error: a group of %zu members lays out to %zu bytes, cut at %zu", what, g, lay.end(), cut.bytes);
-        RSN_HIP(copy_async(base, tab, g * GD_ENTRY, hipMemcpyHostToDevice, s));
-        const GatherEntry *d_gat = (const GatherEntry *)(base + g * sizeof(SmallMember));
-        RSN_LAUNCH("group_gather", k_group_gather, dim3((uint32_t)g), dim3(GD_THREADS), 0, s, d_gat, base);
-        rc = launch(s, (uint32_t)g, (const SmallMember *)base, base); if (rc) return rc;
-        RSN_LAUNCH("group_scatter", k_group_scatter, dim3((uint32_t)g), dim3(GD_THREADS), 0, s, d_gat, (const uint8_t *)base, (uint32_t *)d_ans + j);
-        j = cut.hi;
-    }
-    uint32_t *h_ans = (uint32_t *)(pin + tables);
-    RSN_HIP(copy_async(h_ans, d_ans, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    RSN_HIP(hipStreamSynchronize(s));
-    for (size_t k = 0; k < count; k++) {
-        if (h_ans[k] == GROUP_PENDING) return c.fail(RSN_ERR_DEVICE, "%s: the grouped kernel finished without an answer for one of its members", what);
-        answers[k] = h_ans[k];
-    }
-    return RSN_OK;
+int run_groups_dev(Ctx &c, hipStream_t s, const char *what, const std::vector<size_t> &idx, const rsn_dev_member *mem, const GroupSlotBytes &in_bytes,
+                   const GroupSlotBytes &out_bytes, const GroupLaunch &launch, std::vector<uint32_t> &answers, size_t group_bytes) {
+    return run_groups_staged<GD_ENTRY, GD_ENTRY>(c, s, what, idx.size(), group_bytes, in_bytes, out_bytes,
+        [&](uint8_t *tab, size_t g, size_t q, size_t k, const MemberSlots &o, size_t ib, size_t ob) {
+            const rsn_dev_member &m = mem[idx[k]];
+            ((SmallMember *)tab)[q] = SmallMember{o.in, (uint32_t)m.n, o.out, o.status};
+            ((GatherEntry *)((SmallMember *)tab + g))[q] = GatherEntry{(const uint8_t *)m.d_in, (uint8_t *)m.d_out, m.d_out ? (unsigned long long)m.out_cap : 0ull,
+                                                                      (uint32_t)m.n, o.in, (uint32_t)ib, o.out, (uint32_t)ob, o.status};
+        }, [](size_t) { return (size_t)0; },
+        [&](uint32_t g, uint8_t *base, uint8_t *, uint32_t *d_ans) {
+            const GatherEntry *d_gat = (const GatherEntry *)(base + g * sizeof(SmallMember));
+            RSN_LAUNCH("group_gather", k_group_gather, dim3(g), dim3(GD_THREADS), 0, s, d_gat, base);
+            const int rc = launch(s, g, (const SmallMember *)base, base); if (rc) return rc;
+            RSN_LAUNCH("group_scatter", k_group_scatter, dim3(g), dim3(GD_THREADS), 0, s, d_gat, (const uint8_t *)base, d_ans);
+            return RSN_OK;
+        }, answers);
 }
 
 }  // namespace rsn

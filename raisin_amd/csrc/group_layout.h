@@ -1,6 +1,6 @@
 // group_layout.h -- the arithmetic of a group of batch members in pinned staging, as plain host code: no HIP include, so a CPU
 // test (tests/group_layout_test.cpp) checks what keeps a grouped kernel inside its buffers -- slots that do not overlap, zero padding
-// behind every input, 16-byte aligned offsets.  group_run.h's run_groups and group_dev.hip's run_groups_dev (the same groups on device staging) are the users.
+// behind every input, 16-byte aligned offsets.  group_run.h's run_groups and run_groups_staged (the same groups on device staging) are the users.
 //
 // Staging of a group of g members: a table of g entries of E bytes (E a multiple of 16), then per member its input slot (the member's
 // bytes, zeros behind them), its output slot and 16 bytes of status.  Input and output slots are whole 16-byte units.
@@ -76,5 +76,28 @@ constexpr uint32_t HUFF_RUNE_PAY_MAX = 9 * HUFF_RUNE_OUT_MAX / 8;
 constexpr uint32_t HUFF_RUNE_STREAM_MAX = HUFF_RUNE_HDR_MAX + 8 + HUFF_RUNE_PAY_MAX;   // bytes of a stream the class takes
 constexpr size_t huff_dec_in_slot(size_t sn) { return group_round16(sn) + 64; }       // sn: the stream from the 4-byte boundary the kernel reads from
 constexpr size_t huff_dec_out_slot(size_t expect) { return group_round16(expect) + 16; }   // expect: the bytes the header promises
+
+// ---- a RUN of host members through a class's device form (group_run.h: run_members_staged; tests/run_layout_test.cpp) is two
+// blocks.  The input block goes up in one copy: a table of g entries of T bytes (T = 0: none; the tiled decoder's plans otherwise), then
+// every member's input slot.  The output block holds every member's output slot; slots are whole 16-byte units, T a multiple of 16.
+// run_need: what one member adds to its run (next_group's need: runs are cut as groups are)
+constexpr size_t run_need(size_t table_entry, size_t in_bytes, size_t out_bytes) { return table_entry + in_bytes + out_bytes; }
+struct RunSlots { size_t in, out; };   // a member's offsets, handed out in order: into the input block (behind the table) / the output block
+class RunLayout {
+    size_t in_, out_ = 0;
+public:
+    RunLayout(size_t members, size_t table_entry) : in_(members * table_entry) {}
+    RunSlots member(size_t in_bytes, size_t out_bytes) { const RunSlots m{in_, out_}; in_ += in_bytes; out_ += out_bytes; return m; }
+    size_t in_total() const { return in_; }      // the table and the input slots so far: what goes up
+    size_t out_total() const { return out_; }
+};
+// the bytes of the output block that come down, in one copy: up to the end of the last member a kernel answered (out_at[q]: its slot;
+// answers[q]: a length, not a hand-back), 0 when every member was handed back
+template <class Answers, class OutAt>
+size_t run_down(size_t g, const Answers &answers, const OutAt &out_at) {
+    size_t down = 0;
+    for (size_t q = 0; q < g; q++) if (!group_is_back(answers[q])) down = out_at[q] + answers[q];
+    return down;
+}
 
 }  // namespace rsn

@@ -234,66 +234,20 @@ int big_enc_run_dev(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const
     size_t n_max = 0;
     for (size_t i : idx) n_max = std::max(n_max, (size_t)mem[i].n);
     const uint32_t gx = std::max(1u, big_tiles((uint32_t)std::min<size_t>(n_max, HUFF_BIG_IN_MAX)));
-    return run_groups_dev_sized(c, s, BIG_WHAT, idx, mem, [&](size_t k) { return big_in_bytes(mem[idx[k]].n); }, [&](size_t k) { return big_out_bytes(mem[idx[k]].n); },
+    return run_groups_dev(c, s, BIG_WHAT, idx, mem, [&](size_t k) { return big_in_bytes(mem[idx[k]].n); }, [&](size_t k) { return big_out_bytes(mem[idx[k]].n); },
         [&](hipStream_t s2, uint32_t g, const SmallMember *tab, uint8_t *base) { return big_launch(c, s2, g, gx, tab, base); }, answers, HUFF_BIG_GROUP_BYTES);
 }
 
-// The host form.  The kernels read a member twice and store its stream in pieces, so they never run on pinned host memory: a RUN of
-// members -- up to BIG_RUN_BYTES of inputs and output slots -- is packed into the pinned staging and goes up in ONE copy (Slot::STAGE_IN),
-// the device form above runs it into Slot::STAGE_OUT, and the output slots come down in one copy.  The pinned staging is the device
-// form's too (its tables and answers), so the copy up is waited for before it and the copy down is queued behind it.
-constexpr size_t BIG_RUN_BYTES = 4 * HUFF_BIG_GROUP_BYTES;
+// The host form.  The kernels read a member twice and store its stream in pieces, so they never run on pinned host memory: the members go
+// through the device form above in runs (group_run.h: run_members_staged), the input slot a member's bytes rounded up to 16.
 int big_enc_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
                 const SmallTake &take, std::vector<size_t> &back, size_t *failed, std::vector<size_t> *back_runes) {
-    if (idx.empty()) return RSN_OK;
-    int rc = ctx_init(c); if (rc) { *failed = idx[0]; return rc; }
-    hipStream_t s = c.own_stream;
-    auto need = [&](size_t k) { return group_round16(lens[idx[k]]) + big_out_bytes(lens[idx[k]]); };
-    std::vector<rsn_dev_member> mem;
-    std::vector<size_t> all, out_at;
-    std::vector<uint32_t> answers;
-    for (size_t j = 0; j < idx.size();) {
-        const GroupCut cut = next_group(j, idx.size(), SMALL_GROUP_MAX, BIG_RUN_BYTES, need);
-        const size_t g = cut.hi - j, first = idx[j];
-        *failed = first;
-        size_t in_total = 0, out_total = 0;
-        for (size_t q = 0; q < g; q++) { in_total += group_round16(lens[idx[j + q]]); out_total += big_out_bytes(lens[idx[j + q]]); }
-        Admission gate(c, slotset::STAGING | slotset::GROUP_DEV); gate.admit(2 * (in_total + out_total), ADMIT_FROM);
-        void *pp, *d_in, *d_out;
-        rc = pinned_buf(c, std::max(in_total, out_total) + 64, &pp); if (rc) return rc;
-        rc = dev_buf(c, Slot::STAGE_IN, in_total + 64, &d_in); if (rc) return rc;
-        rc = dev_buf(c, Slot::STAGE_OUT, out_total + 64, &d_out); if (rc) return rc;
-        uint8_t *pin = (uint8_t *)pp;
-        mem.assign(g, rsn_dev_member{}); all.resize(g); out_at.resize(g);
-        size_t in_at = 0, o_at = 0;
-        for (size_t q = 0; q < g; q++) {
-            const size_t i = idx[j + q], n = lens[i];
-            memcpy(pin + in_at, ins[i], n);
-            mem[q].d_in = (uint8_t *)d_in + in_at; mem[q].n = n; mem[q].d_out = (uint8_t *)d_out + o_at; mem[q].out_cap = big_out_bytes(n);
-            all[q] = q; out_at[q] = o_at;
-            in_at += group_round16(n); o_at += big_out_bytes(n);
-        }
-        RSN_HIP(copy_async(d_in, pin, in_total, hipMemcpyHostToDevice, s));
-        RSN_HIP(hipStreamSynchronize(s));                                 // (the staging is the device form's from here on)
-        rc = big_enc_run_dev(c, s, all, mem.data(), window, nullptr, answers); if (rc) return rc;
-        size_t down = 0;                                                  // up to the end of the last stream a kernel wrote
-        for (size_t q = 0; q < g; q++) if (!group_is_back(answers[q])) down = out_at[q] + answers[q];
-        if (down) {
-            rc = pinned_buf(c, std::max(in_total, out_total) + 64, &pp); if (rc) return rc;
-            pin = (uint8_t *)pp;
-            RSN_HIP(copy_async(pin, d_out, down, hipMemcpyDeviceToHost, s));
-            RSN_HIP(hipStreamSynchronize(s));
-        }
-        for (size_t q = 0; q < g; q++) {
-            const size_t i = idx[j + q];
-            const uint32_t v = answers[q];
-            if (group_is_back(v)) { (v == GROUP_BACK_RUNES && back_runes ? *back_runes : back).push_back(i); continue; }
-            if (v > mem[q].out_cap) { *failed = i; return c.fail(RSN_ERR_DEVICE, "%s: internal error: a stream of %u bytes in a slot of %zu", BIG_WHAT, v, (size_t)mem[q].out_cap); }
-            rc = take(i, pin + out_at[q], v); if (rc) { *failed = i; return rc; }
-        }
-        j = cut.hi;
-    }
-    return RSN_OK;
+    std::vector<RunItem> items;
+    for (size_t i : idx) items.push_back(RunItem{i, group_round16(lens[i]), big_out_bytes(lens[i]), big_out_bytes(lens[i])});
+    return run_members_staged<0>(c, BIG_WHAT, "%s: internal error: a stream of %u bytes in a slot of %zu", items,
+        [&](size_t k, size_t, size_t, const void *, uint8_t *, uint8_t *in) { memcpy(in, ins[idx[k]], lens[idx[k]]); return lens[idx[k]]; },
+        [&](hipStream_t s, const std::vector<size_t> &all, const rsn_dev_member *mem, std::vector<uint32_t> &answers) { return big_enc_run_dev(c, s, all, mem, window, nullptr, answers); },
+        take, back, failed, back_runes);
 }
 
 }  // namespace

@@ -147,82 +147,40 @@ int big_dec_run_dev(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const
 }
 
 // The host form.  The kernels read the payload twice and store the output in pieces, so they never run on pinned host memory: the host
-// plans every stream (small_dec_plan's wide form; what it refuses goes back untouched), a RUN of members -- up to BIGD_RUN_BYTES of plans,
-// streams and output slots -- is packed into the pinned staging and goes up in ONE copy (Slot::STAGE_IN: the run's plan table, then the
-// streams from the 4-byte boundary their kernel reads from), the device form above runs it into Slot::STAGE_OUT, and the output slots come
-// down in one copy.  The pinned staging is the device form's too (its tables and answers), so the copy up is waited for before it and the
-// copy down is queued behind it.
-constexpr size_t BIGD_RUN_BYTES = 4 * HUFF_BIG_GROUP_BYTES;
+// plans every stream (small_dec_plan's wide form; what it refuses goes back untouched) and the planned ones go through the device form in
+// runs (group_run.h: run_members_staged) -- the table a run's plans (member r is entry r), an input slot the stream from its 4-byte boundary.
 int big_dec_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
                 const SmallTake &take, std::vector<size_t> &back, size_t *failed, std::vector<size_t> *) {
-    struct Plan { size_t i, A0; unsigned long long expect; SmallDecArgs a; };
+    struct Plan { size_t A0; unsigned long long expect; SmallDecArgs a; };
     std::vector<Plan> planned;
+    std::vector<RunItem> items;
     planned.reserve(idx.size());
     for (size_t i : idx) {
-        Plan p; p.i = i;
+        Plan p;
         if (small_dec_plan(ins[i], lens[i], BIG_DEC_SHAPE.lanes, BIG_DEC_SHAPE.s_max, p.a, &p.A0, &p.expect, true) != RSN_OK ||
             !big_dec_wants((p.a.end - p.a.p0 + 7) / 8, p.expect)) { back.push_back(i); continue; }
         planned.push_back(p);
+        items.push_back(RunItem{i, group_round16(lens[i] - p.A0), huff_dec_out_slot(p.expect), group_round16(p.expect)});
     }
     if (planned.empty()) return RSN_OK;
-    int rc = ctx_init(c); if (rc) { *failed = planned[0].i; return rc; }
-    hipStream_t s = c.own_stream;
-    auto in_b = [&](size_t k) { return group_round16(lens[planned[k].i] - planned[k].A0); };
-    auto out_b = [&](size_t k) { return huff_dec_out_slot(planned[k].expect); };
-    auto need = [&](size_t k) { return sizeof(HuffDevPlan) + in_b(k) + out_b(k); };
-    std::vector<rsn_dev_member> mem;
-    std::vector<size_t> all, out_at;
-    std::vector<uint32_t> answers;
     DevPlans plans;
-    for (size_t j = 0; j < planned.size();) {
-        const GroupCut cut = next_group(j, planned.size(), SMALL_GROUP_MAX, BIGD_RUN_BYTES, need);
-        const size_t g = cut.hi - j, table = g * sizeof(HuffDevPlan);
-        *failed = planned[j].i;
-        size_t in_total = table, out_total = 0;
-        for (size_t q = 0; q < g; q++) { in_total += in_b(j + q); out_total += out_b(j + q); }
-        Admission gate(c, slotset::STAGING | slotset::GROUP_DEV); gate.admit(2 * (in_total + out_total), ADMIT_FROM);
-        void *pp, *d_in, *d_out;
-        rc = pinned_buf(c, std::max(in_total, out_total) + 64, &pp); if (rc) return rc;
-        rc = dev_buf(c, Slot::STAGE_IN, in_total + 64, &d_in); if (rc) return rc;
-        rc = dev_buf(c, Slot::STAGE_OUT, out_total + 64, &d_out); if (rc) return rc;
-        uint8_t *pin = (uint8_t *)pp;
-        mem.assign(g, rsn_dev_member{}); all.resize(g); out_at.resize(g);
-        plans.at.resize(g); plans.sum.resize(g); plans.d_table = (const HuffDevPlan *)d_in;
-        size_t in_at = table, o_at = 0;
-        for (size_t q = 0; q < g; q++) {
-            const Plan &p = planned[j + q];
-            const size_t sn = lens[p.i] - p.A0;
+    const int rc = run_members_staged<sizeof(HuffDevPlan)>(c, BIGD_WHAT, "%s: internal error: %u decoded bytes in a slot of %zu", items,
+        [&](size_t k, size_t r, size_t g, const void *d_table, uint8_t *tab, uint8_t *in) {
+            const Plan &p = planned[k];
+            const size_t i = items[k].i, sn = lens[i] - p.A0;
             HuffDevPlan hp{};                                             // (the stream is staged from A0 on: the member's own A0 is 0)
             hp.b.verdict = PARSE_PLANNED; hp.b.p0 = p.a.p0; hp.b.end = p.a.end; hp.b.pay_words = p.a.pay_words; hp.b.expect = (uint32_t)p.expect;
             hp.b.K = p.a.K; hp.b.root = p.a.root; hp.b.n_child = p.a.n_child; hp.b.flat = p.a.flat;
             memcpy(hp.child, p.a.child, sizeof hp.child);
-            memcpy(pin + q * sizeof(HuffDevPlan), &hp, sizeof hp);
-            memcpy(pin + in_at, ins[p.i] + p.A0, sn); memset(pin + in_at + sn, 0, in_b(j + q) - sn);
-            mem[q].d_in = (uint8_t *)d_in + in_at; mem[q].n = sn; mem[q].d_out = (uint8_t *)d_out + o_at; mem[q].out_cap = group_round16(p.expect);
-            all[q] = q; out_at[q] = o_at;
-            plans.at[q] = (uint32_t)q; plans.sum[q] = HuffDevSummary{PARSE_PLANNED, 0, p.a.end - p.a.p0, (uint32_t)p.expect};
-            in_at += in_b(j + q); o_at += out_b(j + q);
-        }
-        RSN_HIP(copy_async(d_in, pin, in_total, hipMemcpyHostToDevice, s));
-        RSN_HIP(hipStreamSynchronize(s));                                 // (the staging is the device form's from here on)
-        rc = big_dec_run_dev(c, s, all, mem.data(), window, &plans, answers); if (rc) return rc;
-        size_t down = 0;                                                  // up to the end of the last member a kernel decoded
-        for (size_t q = 0; q < g; q++) if (!group_is_back(answers[q])) down = out_at[q] + answers[q];
-        if (down) {
-            rc = pinned_buf(c, std::max(in_total, out_total) + 64, &pp); if (rc) return rc;
-            pin = (uint8_t *)pp;
-            RSN_HIP(copy_async(pin, d_out, down, hipMemcpyDeviceToHost, s));
-            RSN_HIP(hipStreamSynchronize(s));
-        }
-        for (size_t q = 0; q < g; q++) {
-            const size_t i = planned[j + q].i;
-            const uint32_t v = answers[q];
-            if (group_is_back(v)) { back.push_back(i); continue; }
-            if (v > mem[q].out_cap) { *failed = i; return c.fail(RSN_ERR_DEVICE, "%s: internal error: %u decoded bytes in a slot of %zu", BIGD_WHAT, v, (size_t)mem[q].out_cap); }
-            rc = take(i, pin + out_at[q], v); if (rc) { *failed = i; return rc; }
-        }
-        j = cut.hi;
-    }
+            memcpy(tab, &hp, sizeof hp);
+            memcpy(in, ins[i] + p.A0, sn); memset(in + sn, 0, items[k].in_bytes - sn);
+            if (r == 0) { plans.at.resize(g); plans.sum.resize(g); plans.d_table = (const HuffDevPlan *)d_table; }
+            plans.at[r] = (uint32_t)r; plans.sum[r] = HuffDevSummary{PARSE_PLANNED, 0, p.a.end - p.a.p0, (uint32_t)p.expect};
+            return sn;
+        },
+        [&](hipStream_t s, const std::vector<size_t> &all, const rsn_dev_member *mem, std::vector<uint32_t> &answers) { return big_dec_run_dev(c, s, all, mem, window, &plans, answers); },
+        take, back, failed, nullptr);
+    if (rc) return rc;
     std::sort(back.begin(), back.end());
     return RSN_OK;
 }

@@ -29,9 +29,6 @@ constexpr int HP_T = 128;                                     // threads of the 
 constexpr uint32_t HP_UNITS = (PARSE_SCAN_MAX + 15) / 16;     // 16-byte units of the header in LDS
 constexpr int GD_THREADS = 256;
 
-struct PlanEntry { const uint8_t *src; unsigned long long n; };
-static_assert(sizeof(PlanEntry) == 16, "16 bytes a candidate go up");
-
 // the header's bytes in LDS, a word fetched for every four consecutive bytes asked for
 struct LdsBytes {
     const uint32_t *w;
@@ -210,81 +207,44 @@ int huff_dev_plan(Ctx &c, hipStream_t s, size_t n, const rsn_dev_member *mem, De
     const size_t k = cand.size();
     if (k == 0) return RSN_OK;
     if (k >= DEV_PLAN_NONE) return c.fail(RSN_ERR_LIMIT, "huffman: a batch of %zu members", k);
-    const size_t table = k * sizeof(HuffDevPlan), up = k * sizeof(PlanEntry), down = k * sizeof(HuffDevSummary);
-    void *pp, *dp;
-    int rc = pinned_buf(c, up + down, &pp); if (rc) return rc;
-    rc = dev_buf(c, Slot::GD_PLANS, table + up + down, &dp); if (rc) return rc;
-    PlanEntry *h_tab = (PlanEntry *)pp;
-    HuffDevSummary *h_sum = (HuffDevSummary *)((uint8_t *)pp + up);
-    for (size_t q = 0; q < k; q++) h_tab[q] = PlanEntry{(const uint8_t *)mem[cand[q]].d_in, (unsigned long long)mem[cand[q]].n};
-    HuffDevPlan *d_plans = (HuffDevPlan *)dp;
-    PlanEntry *d_tab = (PlanEntry *)((uint8_t *)dp + table);
-    HuffDevSummary *d_sum = (HuffDevSummary *)((uint8_t *)dp + table + up);
-    RSN_HIP(copy_async(d_tab, h_tab, up, hipMemcpyHostToDevice, s));
-    RSN_LAUNCH("huff_dev_plan", k_huff_dev_plan, dim3((uint32_t)k), dim3(HP_T), 0, s, (const PlanEntry *)d_tab, d_plans, d_sum);
-    RSN_HIP(copy_async(h_sum, d_sum, down, hipMemcpyDeviceToHost, s));
-    RSN_HIP(hipStreamSynchronize(s));
+    void *d_plans; const HuffDevSummary *h_sum;
+    const int rc = plan_where_they_lie(c, s, Slot::GD_PLANS, k * sizeof(HuffDevPlan), cand, mem, [&](const PlanEntry *d_tab, void *d_table, HuffDevSummary *d_sum) {
+        RSN_LAUNCH("huff_dev_plan", k_huff_dev_plan, dim3((uint32_t)k), dim3(HP_T), 0, s, d_tab, (HuffDevPlan *)d_table, d_sum);
+        return RSN_OK;
+    }, &d_plans, &h_sum);
+    if (rc) return rc;
     plans.sum.assign(h_sum, h_sum + k);
-    plans.d_table = d_plans;
+    plans.d_table = (const HuffDevPlan *)d_plans;
     for (const HuffDevSummary &v : plans.sum)
         if (v.verdict > PARSE_NOT_MINE || (v.verdict == PARSE_PLANNED && (v.A0 & 3u))) return c.fail(RSN_ERR_DEVICE, "huffman batch decompress: the plan kernel left a summary that is none");
     return RSN_OK;
 }
 
-// run_groups_dev (group_dev.hip) for a decoding class: the same groups and the same staging, the table entry a SmallDecArgs that the gather
-// kernel completes on the device, the input slot the stream from A0 on, the output slot what the header promises.
+// The decoding classes through the one driver (group_run.h: run_groups_staged), every member asked up front whether it is of the class.
+// The gather kernel completes the layout's SmallDecArgs on the device, so only the DecEntry table goes up, behind them.
 int huff_dec_run_dev(Ctx &c, hipStream_t s, const HuffDecShape &shape, const HuffDecLaunch &launch, const std::vector<size_t> &idx, const rsn_dev_member *mem,
                      const DevPlans &plans, std::vector<uint32_t> &answers, size_t group_bytes) {
     const char *what = "huffman batch decompress";
-    const size_t count = idx.size();
-    answers.assign(count, GROUP_PENDING);
-    if (count == 0) return RSN_OK;
+    answers.assign(idx.size(), GROUP_PENDING);
     for (size_t i : idx) {
         const HuffDevSummary *v = plans.of(i);
         if (!v || v->verdict != PARSE_PLANNED || v->A0 > mem[i].n || !huff_dec_shape_takes(shape, *v)) return c.fail(RSN_ERR_DEVICE, "%s: internal error: member %zu is not of the class", what, i);
     }
-    auto in_b = [&](size_t k) { return huff_dec_in_slot(mem[idx[k]].n - plans.of(idx[k])->A0); };
-    auto out_b = [&](size_t k) { return huff_dec_out_slot(plans.of(idx[k])->expect); };
-    auto need = [&](size_t k) { return group_need(HD_ENTRY, in_b(k), out_b(k)); };
-    std::vector<GroupCut> cuts;
-    size_t stage = 0;
-    for (size_t j = 0; j < count;) { const GroupCut cut = next_group(j, count, SMALL_GROUP_MAX, group_bytes, need); stage = std::max(stage, cut.bytes); cuts.push_back(cut); j = cut.hi; }
-    const size_t tables = count * sizeof(DecEntry), down = round_up(count * sizeof(uint32_t), 16);
-    Admission gate(c, slotset::GROUP_DEV); gate.admit(stage + down, ADMIT_FROM);
-    void *pp, *d_stage, *d_ans;
-    int rc = pinned_buf(c, tables + down, &pp); if (rc) return rc;
-    rc = dev_buf(c, Slot::GD_STAGE, stage + 64, &d_stage); if (rc) return rc;
-    rc = dev_buf(c, Slot::GD_LENS, down, &d_ans); if (rc) return rc;
-    uint8_t *pin = (uint8_t *)pp, *base = (uint8_t *)d_stage;
-    size_t j = 0;
-    for (const GroupCut &cut : cuts) {
-        const size_t g = cut.hi - j;
-        DecEntry *gat = (DecEntry *)(pin + j * sizeof(DecEntry));
-        GroupLayout lay(g, HD_ENTRY);
-        for (size_t q = 0; q < g; q++) {
-            const rsn_dev_member &m = mem[idx[j + q]];
-            const HuffDevSummary &v = *plans.of(idx[j + q]);
-            const size_t ib = in_b(j + q), ob = out_b(j + q);
-            const MemberSlots o = lay.member(ib, ob);
-            gat[q] = DecEntry{(const uint8_t *)m.d_in + v.A0, (uint8_t *)m.d_out, m.d_out ? (unsigned long long)m.out_cap : 0ull,
-                              (uint32_t)(m.n - v.A0), o.in, (uint32_t)ib, o.out, (uint32_t)ob, o.status, plans.at[idx[j + q]], {0, 0, 0}};
-        }
-        if (lay.end() != cut.bytes || lay.end() > 0xFFFFFFFFull) return c.fail(RSN_ERR_DEVICE, "%s: internal error: a group of %zu members lays out to %zu bytes, cut at %zu", what, g, lay.end(), cut.bytes);
-        DecEntry *d_gat = (DecEntry *)(base + g * sizeof(SmallDecArgs));
-        RSN_HIP(copy_async(d_gat, gat, g * sizeof(DecEntry), hipMemcpyHostToDevice, s));
-        RSN_LAUNCH("huff_dev_gather", k_huff_dev_gather, dim3((uint32_t)g), dim3(GD_THREADS), 0, s, (const DecEntry *)d_gat, base, plans.d_table, shape.lanes, shape.s_max);
-        rc = launch(c, s, (uint32_t)g, (const SmallDecArgs *)base); if (rc) return rc;
-        RSN_LAUNCH("huff_dev_scatter", k_huff_dev_scatter, dim3((uint32_t)g), dim3(GD_THREADS), 0, s, (const DecEntry *)d_gat, (const uint8_t *)base, (uint32_t *)d_ans + j);
-        j = cut.hi;
-    }
-    uint32_t *h_ans = (uint32_t *)(pin + tables);
-    RSN_HIP(copy_async(h_ans, d_ans, count * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    RSN_HIP(hipStreamSynchronize(s));
-    for (size_t k = 0; k < count; k++) {
-        if (h_ans[k] == GROUP_PENDING) return c.fail(RSN_ERR_DEVICE, "%s: the grouped kernel finished without an answer for one of its members", what);
-        answers[k] = h_ans[k];
-    }
-    return RSN_OK;
+    return run_groups_staged<HD_ENTRY, sizeof(DecEntry)>(c, s, what, idx.size(), group_bytes,
+        [&](size_t k) { return huff_dec_in_slot(mem[idx[k]].n - plans.of(idx[k])->A0); }, [&](size_t k) { return huff_dec_out_slot(plans.of(idx[k])->expect); },
+        [&](uint8_t *tab, size_t, size_t q, size_t k, const MemberSlots &o, size_t ib, size_t ob) {
+            const rsn_dev_member &m = mem[idx[k]];
+            const HuffDevSummary &v = *plans.of(idx[k]);
+            ((DecEntry *)tab)[q] = DecEntry{(const uint8_t *)m.d_in + v.A0, (uint8_t *)m.d_out, m.d_out ? (unsigned long long)m.out_cap : 0ull,
+                                            (uint32_t)(m.n - v.A0), o.in, (uint32_t)ib, o.out, (uint32_t)ob, o.status, plans.at[idx[k]], {0, 0, 0}};
+        }, [](size_t g) { return g * sizeof(SmallDecArgs); },
+        [&](uint32_t g, uint8_t *base, uint8_t *d_tab, uint32_t *d_ans) {
+            const DecEntry *d_gat = (const DecEntry *)d_tab;
+            RSN_LAUNCH("huff_dev_gather", k_huff_dev_gather, dim3(g), dim3(GD_THREADS), 0, s, d_gat, base, plans.d_table, shape.lanes, shape.s_max);
+            const int rc = launch(c, s, g, (const SmallDecArgs *)base); if (rc) return rc;
+            RSN_LAUNCH("huff_dev_scatter", k_huff_dev_scatter, dim3(g), dim3(GD_THREADS), 0, s, d_gat, (const uint8_t *)base, d_ans);
+            return RSN_OK;
+        }, answers);
 }
 
 }  // namespace rsn

@@ -196,7 +196,6 @@ __global__ __launch_bounds__(HR_T) void k_huff_batch_rune_enc(const SmallMember 
     block_done(status, total);
 }
 
-bool rune_enc_takes(const uint8_t *, size_t n, int64_t) { return n >= 2 && n <= HUFF_RUNE_IN_MAX; }
 struct RuneEncClass {
     static constexpr const char *what = "huffman batch compress";
     static size_t in_bytes(size_t n) { return huff_enc_in_slot(n); }
@@ -207,10 +206,23 @@ struct RuneEncClass {
     }
 };
 
+int rune_enc_offer(Ctx &c, std::vector<size_t> &runes, std::vector<size_t> &rest, const uint8_t *const *ins, const size_t *lens, const SmallTake &take, size_t *failed) {
+    runes.resize(rune_class_members(runes, rest, [&](size_t i) { return lens[i]; }));
+    const int rc = runes.empty() ? RSN_OK : class_run<RuneEncClass>(c, runes, ins, lens, 0, take, rest, failed, nullptr);
+    runes.clear();
+    return rc;
+}
+int rune_enc_offer_dev(Ctx &c, hipStream_t s, std::vector<size_t> &runes, std::vector<size_t> &rest, const rsn_dev_member *mem, const DevPlans *,
+                       std::vector<size_t> &idx, std::vector<uint32_t> &answers) {
+    runes.resize(rune_class_members(runes, rest, [&](size_t i) { return mem[i].n; }));
+    idx.swap(runes);                                                      // (idx comes empty: the pool is left so)
+    return idx.empty() ? RSN_OK : class_run_dev<RuneEncClass>(c, s, idx, mem, 0, nullptr, answers);
+}
+
 }  // namespace
 
-const BatchClass &huff_rune_class() {
-    static const BatchClass enc = {"huffman rune compress", HUFF_RUNE_GROUP_MIN, rune_enc_takes, class_run<RuneEncClass>, class_run_dev<RuneEncClass>};
+const BehindClass &huff_rune_class() {
+    static const BehindClass enc = {BehindClass::RUNES, rune_enc_offer, rune_enc_offer_dev};
     return enc;
 }
 

@@ -203,13 +203,11 @@ __global__ __launch_bounds__(RD_T) void k_huff_batch_rune_dec(const SmallMember 
 }
 
 // ---- the device form's second plan launch: the light scan where the stream lies, a workgroup a candidate, 16 bytes of summary each
-struct RunePlanEntry { const uint8_t *src; unsigned long long n; };
-static_assert(sizeof(RunePlanEntry) == 16, "16 bytes a candidate go up");
-__global__ __launch_bounds__(RP_T) void k_huff_dev_rune_plan(const RunePlanEntry *__restrict__ tab, HuffDevSummary *__restrict__ sums) {
+__global__ __launch_bounds__(RP_T) void k_huff_dev_rune_plan(const PlanEntry *__restrict__ tab, HuffDevSummary *__restrict__ sums) {
     __shared__ uint4 s_hdr[RD_HDR_UNITS + 1];
     __shared__ uint32_t s_key[PARSE_RUNE_SLOTS], s_c1[PARSE_RUNE_SLOTS];
     __shared__ uint32_t s_w[W_WORDS];
-    const RunePlanEntry e = tab[blockIdx.x];
+    const PlanEntry e = tab[blockIdx.x];
     HuffDevBounds b{};
     uint32_t S = 0, T = 0;
     const bool planned = rune_light_plan<RP_T>(e.src, e.n, s_hdr, s_key, s_c1, s_w, b, &S, &T);
@@ -221,76 +219,57 @@ int launch_rune_dec(Ctx &c, hipStream_t s, uint32_t g, const SmallMember *tab, u
     return RSN_OK;
 }
 const char *const RD_WHAT = "huffman batch decompress";
-bool rune_dec_summary_ok(const HuffDevSummary &v, size_t n) {
-    return v.verdict == PARSE_PLANNED && !(v.A0 & 3u) && v.A0 <= n && v.expect >= 1 && v.expect <= HUFF_RUNE_OUT_MAX && (v.span + 7) / 8 <= HUFF_RUNE_PAY_MAX;
-}
 
-}  // namespace
-
-HuffDevSummary huff_rune_dec_scan(const uint8_t *in, size_t n) { return parse_rune_light(in, n); }
-
-int huff_rune_dec_offer(Ctx &c, std::vector<size_t> &rest, const uint8_t *const *ins, const size_t *lens, const SmallTake &take, size_t *failed) {
-    if (rest.size() < HUFF_RUNE_DEC_GROUP_MIN) return RSN_OK;
-    std::vector<size_t> idx, others;
+// The two offers (codecs.h: BehindClass; pool REST, so `rest` is the pool itself), huff_rune_select.h choosing.  The chosen run in the groups
+// of the SmallMember classes, the input slot the whole stream, the output slot what the header promises.
+int rune_dec_offer(Ctx &c, std::vector<size_t> &rest, std::vector<size_t> &, const uint8_t *const *ins, const size_t *lens, const SmallTake &take, size_t *failed) {
+    const std::vector<size_t> cand = rune_dec_candidates(rest, [&](size_t i) { return lens[i] <= HUFF_RUNE_STREAM_MAX; });
+    if (cand.empty()) return RSN_OK;
+    std::vector<HuffDevSummary> sums;
+    for (size_t i : cand) sums.push_back(parse_rune_light(ins[i], lens[i]));
+    std::vector<size_t> idx, others = rest;                               // (`rest` stays as it is when the run fails)
     std::vector<uint32_t> expect;
-    for (size_t i : rest) {
-        const HuffDevSummary v = lens[i] <= HUFF_RUNE_STREAM_MAX ? huff_rune_dec_scan(ins[i], lens[i]) : HuffDevSummary{PARSE_NOT_MINE, 0, 0, 0};
-        if (rune_dec_summary_ok(v, lens[i])) { idx.push_back(i); expect.push_back(v.expect); }
-        else others.push_back(i);
-    }
-    if (idx.size() < HUFF_RUNE_DEC_GROUP_MIN) return RSN_OK;
-    std::vector<size_t> handed;
-    const int rc = run_groups<SmallMember>(c, RD_WHAT, idx.size(),
-        [&](size_t k) { const size_t i = idx[k], n = lens[i]; return GroupItem{i, ins[i], n, huff_dec_in_slot(n), huff_dec_out_slot(expect[k])}; },
-        [&](SmallMember &m, size_t k, uint8_t *, const MemberSlots &o) { m = SmallMember{o.in, (uint32_t)lens[idx[k]], o.out, o.status}; },
-        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) { return launch_rune_dec(c, s, g, tab, base); },
-        [](const uint32_t *w) { return w[0]; }, take, handed, failed);
+    rune_dec_planned(cand, cand.size(), sums.data(), [&](size_t i) { return lens[i]; }, idx, expect);
+    if (!rune_dec_leave(others, idx)) return RSN_OK;
+    const int rc = run_member_groups(c, RD_WHAT, idx, ins, lens, [&](size_t k) { return huff_dec_in_slot(lens[idx[k]]); }, [&](size_t k) { return huff_dec_out_slot(expect[k]); },
+        [&](hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) { return launch_rune_dec(c, s, g, tab, base); }, take, others, failed, nullptr);
     if (rc) return rc;
-    others.insert(others.end(), handed.begin(), handed.end());
     std::sort(others.begin(), others.end());
     rest.swap(others);
     return RSN_OK;
 }
 
-int huff_rune_dec_offer_dev(Ctx &c, hipStream_t s, std::vector<size_t> &rest, const rsn_dev_member *mem, const DevPlans &plans,
-                            std::vector<size_t> &idx, std::vector<uint32_t> &answers) {
-    idx.clear(); answers.clear();
-    std::vector<size_t> cand;
-    for (size_t i : rest) {
-        const HuffDevSummary *v = plans.of(i);
-        if (v && v->verdict == PARSE_NOT_MINE && mem[i].n <= HUFF_RUNE_STREAM_MAX) cand.push_back(i);
-    }
+int rune_dec_offer_dev(Ctx &c, hipStream_t s, std::vector<size_t> &rest, std::vector<size_t> &, const rsn_dev_member *mem, const DevPlans *plans,
+                       std::vector<size_t> &idx, std::vector<uint32_t> &answers) {
+    const std::vector<size_t> cand = rune_dec_candidates(rest, [&](size_t i) {
+        const HuffDevSummary *v = plans->of(i);
+        return v && v->verdict == PARSE_NOT_MINE && mem[i].n <= HUFF_RUNE_STREAM_MAX;
+    });
     const size_t k = cand.size();
-    if (k < HUFF_RUNE_DEC_GROUP_MIN) return RSN_OK;
-    std::sort(cand.begin(), cand.end());
-    const size_t up = k * sizeof(RunePlanEntry), down = k * sizeof(HuffDevSummary);
-    void *pp, *dp;
-    int rc = pinned_buf(c, up + down, &pp); if (rc) return rc;
-    rc = dev_buf(c, Slot::GD_RUNE_PLANS, up + down, &dp); if (rc) return rc;
-    RunePlanEntry *h_tab = (RunePlanEntry *)pp;
-    HuffDevSummary *h_sum = (HuffDevSummary *)((uint8_t *)pp + up);
-    for (size_t q = 0; q < k; q++) h_tab[q] = RunePlanEntry{(const uint8_t *)mem[cand[q]].d_in, (unsigned long long)mem[cand[q]].n};
-    RunePlanEntry *d_tab = (RunePlanEntry *)dp;
-    HuffDevSummary *d_sum = (HuffDevSummary *)((uint8_t *)dp + up);
-    RSN_HIP(copy_async(d_tab, h_tab, up, hipMemcpyHostToDevice, s));
-    RSN_LAUNCH("huff_dev_rune_plan", k_huff_dev_rune_plan, dim3((uint32_t)k), dim3(RP_T), 0, s, (const RunePlanEntry *)d_tab, d_sum);
-    RSN_HIP(copy_async(h_sum, d_sum, down, hipMemcpyDeviceToHost, s));
-    RSN_HIP(hipStreamSynchronize(s));
+    if (k == 0) return RSN_OK;
+    void *d_none; const HuffDevSummary *sums;
+    const int rc = plan_where_they_lie(c, s, Slot::GD_RUNE_PLANS, 0, cand, mem, [&](const PlanEntry *d_tab, void *, HuffDevSummary *d_sum) {
+        RSN_LAUNCH("huff_dev_rune_plan", k_huff_dev_rune_plan, dim3((uint32_t)k), dim3(RP_T), 0, s, d_tab, d_sum);
+        return RSN_OK;
+    }, &d_none, &sums);
+    if (rc) return rc;
     std::vector<uint32_t> expect;
-    for (size_t q = 0; q < k; q++) {
-        const HuffDevSummary v = h_sum[q];
-        if (v.verdict > PARSE_NOT_MINE) return c.fail(RSN_ERR_DEVICE, "%s: the rune plan kernel left a summary that is none", RD_WHAT);
-        if (rune_dec_summary_ok(v, mem[cand[q]].n)) { idx.push_back(cand[q]); expect.push_back(v.expect); }
+    auto len = [&](size_t i) { return (size_t)mem[i].n; };
+    for (size_t q = 0; q < k; q++) if (sums[q].verdict > PARSE_NOT_MINE) {
+        rune_dec_planned(cand, q, sums, len, idx, expect);                // (the failure is about the first member chosen in front of it)
+        return c.fail(RSN_ERR_DEVICE, "%s: the rune plan kernel left a summary that is none", RD_WHAT);
     }
-    if (idx.size() < HUFF_RUNE_DEC_GROUP_MIN) { idx.clear(); return RSN_OK; }
-    {   // the members of the class leave `rest` (both sorted here: idx as cand is)
-        std::vector<size_t> sorted = rest, others;
-        std::sort(sorted.begin(), sorted.end());
-        std::set_difference(sorted.begin(), sorted.end(), idx.begin(), idx.end(), std::back_inserter(others));
-        rest.swap(others);
-    }
-    return run_groups_dev_sized(c, s, RD_WHAT, idx, mem, [&](size_t q) { return huff_dec_in_slot(mem[idx[q]].n); }, [&](size_t q) { return huff_dec_out_slot(expect[q]); },
+    rune_dec_planned(cand, k, sums, len, idx, expect);
+    if (!rune_dec_leave(rest, idx)) return RSN_OK;
+    return run_groups_dev(c, s, RD_WHAT, idx, mem, [&](size_t q) { return huff_dec_in_slot(mem[idx[q]].n); }, [&](size_t q) { return huff_dec_out_slot(expect[q]); },
         [&](hipStream_t s2, uint32_t g, const SmallMember *tab, uint8_t *base) { return launch_rune_dec(c, s2, g, tab, base); }, answers);
+}
+
+}  // namespace
+
+const BehindClass &huff_rune_dec_class() {
+    static const BehindClass dec = {BehindClass::REST, rune_dec_offer, rune_dec_offer_dev};
+    return dec;
 }
 
 }  // namespace rsn

@@ -42,9 +42,10 @@ using HuffDecLaunch = std::function<int(Ctx &c, hipStream_t s, uint32_t members,
 int huff_dec_run(Ctx &c, const HuffDecShape &shape, const HuffDecLaunch &launch, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens,
                  const SmallTake &take, std::vector<size_t> &back, size_t *failed);
 // The same classes on device buffers (huff_dev.hip): the members idx[k] of `mem`, every one with a planned summary that the class's
-// takes_plan has accepted, in run_groups_dev's groups on device staging -- a gather kernel copies each stream from its 4-byte boundary into
-// its input slot and completes its SmallDecArgs from the plan table, the decoder is launched unchanged, and a scatter kernel copies what
-// fits to d_out and turns the decoder's two status words into the answer: GROUP_BACK, or the decoded length.
+// takes_plan has accepted (asked again here, up front), through the one driver of groups on device staging (group_run.h:
+// run_groups_staged) as the decoders' family -- a gather kernel copies each stream from its 4-byte boundary into its input slot and
+// completes its SmallDecArgs from the plan table, the decoder is launched unchanged, and a scatter kernel copies what fits to d_out and
+// turns the decoder's two status words into the answer: GROUP_BACK, or the decoded length.
 // group_bytes: the staging of a group at most (a class whose members are large states a larger group of its own: huff_big_dec.hip).
 int huff_dec_run_dev(Ctx &c, hipStream_t s, const HuffDecShape &shape, const HuffDecLaunch &launch, const std::vector<size_t> &idx, const rsn_dev_member *mem,
                      const DevPlans &plans, std::vector<uint32_t> &answers, size_t group_bytes = SMALL_GROUP_BYTES);

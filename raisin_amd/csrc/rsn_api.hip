@@ -1100,22 +1100,23 @@ static void classify_by(BatchRows rows, size_t n, Takes takes, std::vector<std::
     for (size_t r = 0; r < rows.n; r++)
         if (per[r].size() < rows.first[r]->group_min) { rest.insert(rest.end(), per[r].begin(), per[r].end()); per[r].clear(); }
 }
-static void classify(BatchRows rows, size_t n, const uint8_t *const *ins, const size_t *lens, int64_t window,
-                     std::vector<std::vector<size_t>> &per, std::vector<size_t> &rest) {
-    classify_by(rows, n, [&](const BatchClass &k, size_t i) { return k.takes(ins[i], lens[i], window); }, per, rest);
-}
 
-// The members the Huffman byte encoders handed back as GROUP_BACK_RUNES, sorted: those the rune class takes (huff_rune.hip: at most 16 KiB)
-// move to the front of `runes` and their number is returned, when there are at least its minimum of them; the others -- all of them
-// when there are fewer -- join `rest`, and go where they went before there was such a class.  len(i): member i's length.
-template <class Len>
-static size_t rune_class_members(std::vector<size_t> &runes, std::vector<size_t> &rest, Len len) {
-    const BatchClass &k = huff_rune_class();
-    std::sort(runes.begin(), runes.end());
-    auto mid = std::stable_partition(runes.begin(), runes.end(), [&](size_t i) { return k.takes(nullptr, len(i), 0); });
-    if ((size_t)(mid - runes.begin()) < k.group_min) mid = runes.begin();
-    rest.insert(rest.end(), mid, runes.end());
-    return (size_t)(mid - runes.begin());
+// The front of both host flows (the Huffman compress batch, small_batch): the members by class, the rows in their order, then the classes behind
+// them (codecs.h: BehindClass).  `back`, what the rows handed back, has joined `rest`, which is sorted.  A device failure stops it: its code.
+static int batch_front(Ctx &c, BatchRows rows, int64_t window, size_t n, const uint8_t *const *ins, const size_t *lens, const SmallTake &take,
+                       std::vector<size_t> &rest, std::vector<size_t> &back, size_t *failed) {
+    std::vector<std::vector<size_t>> per;
+    std::vector<size_t> runes;
+    classify_by(rows, n, [&](const BatchClass &k, size_t i) { return k.takes(ins[i], lens[i], window); }, per, rest);
+    int rc = RSN_OK;
+    for (size_t r = 0; r < rows.n && rc == RSN_OK; r++)
+        if (!per[r].empty()) rc = rows.first[r]->run(c, per[r], ins, lens, window, take, back, failed, &runes);
+    rest.insert(rest.end(), back.begin(), back.end());
+    for (size_t q = 0; q < rows.n_behind && rc == RSN_OK; q++)
+        rc = rows.behind[q]->offer(c, rows.behind[q]->pool == BehindClass::RUNES ? runes : rest, rest, ins, lens, take, failed);
+    rest.insert(rest.end(), runes.begin(), runes.end());                  // (no class behind the rows drew from them, or a failure came first)
+    std::sort(rest.begin(), rest.end());
+    return rc;
 }
 
 static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
@@ -1126,33 +1127,12 @@ static int rsn_huffman_compress_batch_impl(size_t n_chunks, const uint8_t *const
         drop_results(n_chunks, outs, out_lens);
         return c.fail(rc, "%s", msg);
     };
-    // Members of 2 B to 16 KiB (k_huff_batch_enc) and above that up to HUFF_MID_IN_MAX (k_huff_mid_enc) run grouped on this thread, one
-    // launch per group, every member its own workgroup and its own tree (codecs.h: the rows and their minimums); above that up to
-    // HUFF_BIG_IN_MAX a member is cut into tiles, a workgroup each, three launches per group (huff_big.hip).  The members those
-    // kernels hand back because of a byte >= 0x80 run grouped as well, through the rune class behind the rows (huff_rune.hip), when the call
-    // holds enough of them that it takes.  The rest -- larger members, and the members a kernel hands back (a single symbol, more runes
-    // than the rune class takes) -- take the pipeline below, as every member did before, dealt over the batch workers.
-    const BatchRows rows = batch_classes(BatchLayer::HUFFMAN, true);
-    std::vector<std::vector<size_t>> per;
-    std::vector<size_t> rest, runes;
-    classify(rows, n_chunks, ins, lens, 0, per, rest);
-    const SmallTake take = take_into(c, outs, out_lens);
-    auto run_class = [&](const BatchClass &k, const std::vector<size_t> &idx, std::vector<size_t> *back_runes) {
-        size_t failed = 0;
-        return k.run(c, idx, ins, lens, 0, take, rest, &failed, back_runes);
-    };
-    for (size_t r = 0; r < rows.n; r++) {
-        if (per[r].empty()) continue;
-        const int rc = run_class(*rows.first[r], per[r], &runes);
-        if (rc != RSN_OK) { const std::string msg = c.err; return undo(rc, msg.c_str()); }
-    }
-    const size_t n_rune = rune_class_members(runes, rest, [&](size_t i) { return lens[i]; });
-    if (n_rune) {
-        runes.resize(n_rune);
-        const int rc = run_class(huff_rune_class(), runes, nullptr);
-        if (rc != RSN_OK) { const std::string msg = c.err; return undo(rc, msg.c_str()); }
-    }
-    std::sort(rest.begin(), rest.end());
+    // The members a class takes run grouped on this thread (codecs.h: the rows up to HUFF_BIG_IN_MAX, the rune class behind them, their
+    // minimums).  The rest -- larger members, and those a kernel hands back -- take the pipeline below, dealt over the batch workers.
+    std::vector<size_t> rest, back;
+    size_t failed = 0;
+    const int rc = batch_front(c, batch_classes(BatchLayer::HUFFMAN, true), 0, n_chunks, ins, lens, take_into(c, outs, out_lens), rest, back, &failed);
+    if (rc != RSN_OK) { const std::string msg = c.err; return undo(rc, msg.c_str()); }
     if (rest.empty()) return RSN_OK;
     std::vector<int> rcs;
     std::vector<std::string> msgs;
@@ -1198,12 +1178,9 @@ struct ShardSync : FirstFailure {
 // any failure every outs[i] is NULL and the answer is the lowest-index failing member's code, its message prefixed "member <i>: ".
 // `rows`: the layer's and direction's classes (codecs.h), run in their order; `single(i, small)`: the single call for member i (small =
 // false: the member was handed back by a grouped kernel whose body the single call's small path shares).
-// `behind(c, rest, take, &failed)`: a class behind the rows (the Huffman rune decoder, huff_rune_dec.hip) is offered what is left for the
-// single call, sorted, and takes out of it what it ran grouped; the layers that have none pass no_class_behind.
-static int no_class_behind(Ctx &, std::vector<size_t> &, const SmallTake &, size_t *) { return RSN_OK; }
-template <class Single, class Behind>
+template <class Single>
 static int small_batch(BatchRows rows, int64_t window, size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens,
-                       bool back_skips_small, Single single, Behind behind) {
+                       bool back_skips_small, Single single) {
     Ctx &c = ctx();
     int rc = batch_args(c, n, ins, lens, outs, out_lens, true, true); if (rc || n == 0) return rc;
     rc = ctx_init(c); if (rc) return rc;                                  // (no device: RSN_ERR_DEVICE -- there is no CPU path)
@@ -1211,25 +1188,12 @@ static int small_batch(BatchRows rows, int64_t window, size_t n, const uint8_t *
     struct Fail { size_t at = NONE; int rc = RSN_OK; std::string msg; };
     Fail f;
     auto note = [](Fail &x, size_t i, int code, const std::string &m) { if (i < x.at) { x.at = i; x.rc = code; x.msg = m; } };
-    std::vector<std::vector<size_t>> per;
     std::vector<size_t> rest, back;
-    classify(rows, n, ins, lens, window, per, rest);                      // (rest is sorted below)
-    const SmallTake take = take_into(c, outs, out_lens);
-    for (size_t r = 0; r < rows.n && f.at == NONE; r++) {                 // (a device failure: nothing more is launched)
-        if (per[r].empty()) continue;
-        size_t failed = NONE;
-        rc = rows.first[r]->run(c, per[r], ins, lens, window, take, back, &failed, nullptr);
-        if (rc != RSN_OK) note(f, failed, rc, c.err);
-    }
+    size_t failed = NONE;
+    rc = batch_front(c, rows, window, n, ins, lens, take_into(c, outs, out_lens), rest, back, &failed);
+    if (rc != RSN_OK) note(f, failed, rc, c.err);
     std::vector<char> handed(back_skips_small ? n : 0, 0);
     for (size_t i : back) if (back_skips_small) handed[i] = 1;
-    rest.insert(rest.end(), back.begin(), back.end());
-    std::sort(rest.begin(), rest.end());
-    if (f.at == NONE) {
-        size_t failed = NONE;
-        rc = behind(c, rest, take, &failed);
-        if (rc != RSN_OK) note(f, failed, rc, c.err);
-    }
     while (!rest.empty() && rest.back() > f.at) rest.pop_back();          // (what lies behind a known failure cannot change the answer)
     if (!rest.empty()) {
         std::atomic<size_t> stop{f.at};                                   // the lowest failing member found so far: workers do not go past it
@@ -1265,18 +1229,17 @@ static int small_batch(BatchRows rows, int64_t window, size_t n, const uint8_t *
 
 static int rsn_huffman_decompress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
     return small_batch(batch_classes(BatchLayer::HUFFMAN, false), 0, n, ins, lens, outs, out_lens, false,
-                       [&](size_t i, bool small) { return rsn_huffman_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small); },
-                       [&](Ctx &c, std::vector<size_t> &rest, const SmallTake &take, size_t *failed) { return huff_rune_dec_offer(c, rest, ins, lens, take, failed); });
+                       [&](size_t i, bool small) { return rsn_huffman_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small); });
 }
 
 static int rsn_lzss_compress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, int64_t window, uint8_t **outs, size_t *out_lens) {
     return small_batch(batch_classes(BatchLayer::LZSS, true), window, n, ins, lens, outs, out_lens, true,
-                       [&](size_t i, bool small) { return rsn_lzss_compress_impl(ins[i], lens[i], window, &outs[i], &out_lens[i], small);  }, no_class_behind);
+                       [&](size_t i, bool small) { return rsn_lzss_compress_impl(ins[i], lens[i], window, &outs[i], &out_lens[i], small);  });
 }
 
 static int rsn_lzss_decompress_batch_impl(size_t n, const uint8_t *const *ins, const size_t *lens, uint8_t **outs, size_t *out_lens) {
     return small_batch(batch_classes(BatchLayer::LZSS, false), 0, n, ins, lens, outs, out_lens, true,
-                       [&](size_t i, bool small) { return rsn_lzss_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small);  }, no_class_behind);
+                       [&](size_t i, bool small) { return rsn_lzss_decompress_impl(ins[i], lens[i], &outs[i], &out_lens[i], small);  });
 }
 
 // ---- the arithmetic codec (arith.hip): the single call is a batch of one -- every member goes through the same two kernels
@@ -1406,20 +1369,14 @@ static int layer_batch_run(Ctx &c, hipStream_t s, const BatchDevLayer &layer, bo
         if (rc) return fails(rc, per[r][0]);                              // (a device failure: nothing more is launched)
         settle(per[r]);
     }
-    if (const size_t n_rune = rune_class_members(runes, rest, [&](size_t i) { return mem[i].n; })) {   // (huff_rune.hip: the rune class behind the rows)
-        const std::vector<size_t> idx(runes.begin(), runes.begin() + (long)n_rune);
-        runes.clear();                                                    // (the class answers GROUP_BACK alone)
-        rc = huff_rune_class().run_dev(c, s, idx, mem, window, nullptr, answers);
-        if (rc) return fails(rc, idx[0]);
-        settle(idx);
-        rest.insert(rest.end(), runes.begin(), runes.end());
-    }
-    if (planned && !enc) {   // (huff_rune_dec.hip: the rune decoder behind the rows -- a second plan launch over what the first refused, when the call holds enough of it)
-        std::vector<size_t> idx;
-        rc = huff_rune_dec_offer_dev(c, s, rest, mem, plans, idx, answers);
-        if (rc) return fails(rc, idx.empty() ? (rest.empty() ? 0 : *std::min_element(rest.begin(), rest.end())) : idx[0]);
+    for (size_t q = 0; q < rows.n_behind; q++) {                          // (codecs.h: the classes behind the rows, each over its pool)
+        const BehindClass &k = *rows.behind[q];
+        std::vector<size_t> idx, &pool = k.pool == BehindClass::RUNES ? runes : rest;
+        rc = k.offer_dev(c, s, pool, rest, mem, planned ? &plans : nullptr, idx, answers);
+        if (rc) return fails(rc, behind_failed(idx, pool));
         settle(idx);
     }
+    rest.insert(rest.end(), runes.begin(), runes.end());                  // (what no class behind the rows drew, and what one answered with the same word)
     std::sort(rest.begin(), rest.end());
     for (size_t i : rest) {
         size_t got = 0;
