@@ -265,13 +265,12 @@ struct MoveEntry { const uint8_t *src; uint8_t *dst; unsigned long long len; };
 int members_move(Ctx &c, hipStream_t s, const MoveEntry *h_tab, MoveEntry *d_tab, size_t tiles);
 
 // the batch round trip's verify pass (rsn.h; roundtrip_batch.hip): `tiles` entries of h_tab (pinned; roundtrip_batch_layout.h)
-// over the run's m members go up into d_slot -- a block of rb_layout(tiles, m, hists).bytes -- in one copy, ONE memset clears the stats
-// block behind the table and ONE launch of k_members_verify, a workgroup an entry, fills it.  Only queues work on `s`.
+// over the run's m members go up into d_slot -- a block of verify_layout(both, tiles, m, hists).bytes (suite_layout.h) -- in one copy, ONE
+// memset clears the stats block behind the table and ONE launch of k_members_verify, a workgroup an entry, fills it.  both: the instance
+// that counts both sides (profile name members_verify); otherwise the batch suite's for the further lists of a run (DESIGN 4.13;
+// members_verify_dec), which compares as the first and counts the decompressed side alone, 256 counters a member.  Only queues work on `s`.
 struct RbEntry;
-int members_verify(Ctx &c, hipStream_t s, const RbEntry *h_tab, size_t tiles, size_t m, bool hists, void *d_slot);
-// the batch suite's further lists of a run (rsn.h): the same over a block of suite_dec_layout(tiles, m, hists).bytes
-// (suite_layout.h) -- the kernel's second instance compares as the first and counts the decompressed side alone, 256 counters a member
-int members_verify_dec(Ctx &c, hipStream_t s, const RbEntry *h_tab, size_t tiles, size_t m, bool hists, void *d_slot);
+int members_verify(Ctx &c, hipStream_t s, bool both, const RbEntry *h_tab, size_t tiles, size_t m, bool hists, void *d_slot);
 
 // exclusive scan of n counts on the stream (huff_encode.hip); *total (may be null) receives the sum; in and out must not overlap
 int scan_u64(Ctx &c, hipStream_t s, const char *name, const unsigned long long *in, unsigned long long *out, uint32_t n, unsigned long long *total);

@@ -1,7 +1,8 @@
 // roundtrip_batch.hip -- k_members_verify, the one kernel of the batch round trip (rsn.h: rsn_layers_roundtrip_batch,
 // rsn_layers_roundtrip_batch_dev).  Behind the two passes of such a call every member has an original and a decompressed
 // buffer on the device; this kernel compares them and counts their bytes -- engine.BenchmarkFile's reflect.DeepEqual and its two
-// histograms (engine.go:367-370, :412-415, :424) -- for all members in ONE launch.  The flow itself is rsn_api.hip's roundtrip_batch_flow.
+// histograms (engine.go:367-370, :412-415, :424) -- for all members in ONE launch.  The flow itself is rsn_api.hip's suite_batch_flow,
+// which the round trip runs over its one list.
 #include "codecs.h"
 #include "roundtrip_batch_layout.h"
 #include "suite_layout.h"
@@ -150,23 +151,16 @@ static int verify_prepare(Ctx &c, hipStream_t s, const RbEntry *h_tab, size_t ti
     return RSN_OK;
 }
 
-int members_verify(Ctx &c, hipStream_t s, const RbEntry *h_tab, size_t tiles, size_t m, bool hists, void *d_slot) {
-    const RbLayout lay = rb_layout(tiles, m, hists);
+int members_verify(Ctx &c, hipStream_t s, bool both, const RbEntry *h_tab, size_t tiles, size_t m, bool hists, void *d_slot) {
+    const RbLayout lay = verify_layout(both, tiles, m, hists);
     const int rc = verify_prepare(c, s, h_tab, tiles, m, lay, d_slot); if (rc) return rc;
     uint8_t *d = (uint8_t *)d_slot;
     if (tiles == 0) return RSN_OK;
-    RSN_LAUNCH("members_verify", (k_members_verify<VF_COPIES>), dim3((uint32_t)tiles), dim3(VF_THREADS), 0, s, (const RbEntry *)(d + lay.table),
-               (unsigned long long *)(d + lay.words), hists ? (uint32_t *)(d + lay.hists) : (uint32_t *)nullptr);
-    return RSN_OK;
-}
-
-int members_verify_dec(Ctx &c, hipStream_t s, const RbEntry *h_tab, size_t tiles, size_t m, bool hists, void *d_slot) {
-    const RbLayout lay = suite_dec_layout(tiles, m, hists);
-    const int rc = verify_prepare(c, s, h_tab, tiles, m, lay, d_slot); if (rc) return rc;
-    uint8_t *d = (uint8_t *)d_slot;
-    if (tiles == 0) return RSN_OK;
-    RSN_LAUNCH("members_verify_dec", (k_members_verify<VF_COPIES, false>), dim3((uint32_t)tiles), dim3(VF_THREADS), 0, s, (const RbEntry *)(d + lay.table),
-               (unsigned long long *)(d + lay.words), hists ? (uint32_t *)(d + lay.hists) : (uint32_t *)nullptr);
+    const RbEntry *tab = (const RbEntry *)(d + lay.table);
+    unsigned long long *words = (unsigned long long *)(d + lay.words);
+    uint32_t *counts = hists ? (uint32_t *)(d + lay.hists) : (uint32_t *)nullptr;
+    if (both) RSN_LAUNCH("members_verify", (k_members_verify<VF_COPIES>), dim3((uint32_t)tiles), dim3(VF_THREADS), 0, s, tab, words, counts);
+    else RSN_LAUNCH("members_verify_dec", (k_members_verify<VF_COPIES, false>), dim3((uint32_t)tiles), dim3(VF_THREADS), 0, s, tab, words, counts);
     return RSN_OK;
 }
 

@@ -1,8 +1,8 @@
 // roundtrip_batch_layout.h -- the arithmetic of the batch round trip (rsn.h: rsn_layers_roundtrip_batch, rsn_layers_roundtrip_batch_dev;
 // DESIGN 4.12), as plain host code: no HIP include, so a CPU test (tests/roundtrip_batch_layout_test.cpp) checks it -- the tiles of a
 // member cover the longer of its two buffers exactly once, the verify table and the stats block lie apart at 16-byte offsets, the counters'
-// 32-bit limit, and a run need that grows with both lengths.  rsn_api.hip's roundtrip_batch_flow is the user, roundtrip_batch.hip's
-// k_members_verify reads the table and writes the stats.
+// 32-bit limit, and a run need that grows with both lengths.  rsn_api.hip's suite_batch_flow is the user (the round trip is its
+// one-list form), roundtrip_batch.hip's k_members_verify reads the table and writes the stats.
 //
 // A run of m members ends in ONE launch over a table of tiles: an entry per 64 KiB of max(original, decompressed) of every member.  The
 // launch writes the run's stats block: a first-difference word per member and, when the caller asked for them, 512 counters per member.

@@ -1719,6 +1719,18 @@ size_t layers_batch_slot(bool enc, const int *layers, size_t n_layers, size_t n)
 struct LbFailure { size_t step = LB_NONE, member = 0; int rc = RSN_OK; std::string msg; };
 // where a run's members are and how long, step by step; tight: the lowest member that did not fit the caller's buffer behind the last step
 struct LbRunState { std::vector<const uint8_t *> at; std::vector<size_t> len; size_t tight = LB_NONE; std::string tight_msg; };
+// a call's members in its form: ins / lens (the host form: a run's inputs are staged in LB_STAGE and stay there to the end of the run),
+// or mem (the device form: read where they lie)
+struct LbMembers {
+    const uint8_t *const *ins; const size_t *lens; const rsn_dev_member *mem;
+    bool staged() const { return mem == nullptr; }
+    size_t len(size_t i) const { return mem ? (size_t)mem[i].n : lens[i]; }
+};
+// the wait every flow of this family ends a run with
+int stream_synced(Ctx &c, hipStream_t s) {
+    const hipError_t e = hipStreamSynchronize(s);
+    return e == hipSuccess ? RSN_OK : c.fail(RSN_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+}
 }  // namespace
 
 // The steps [0, steps) of the run [lo, lo + m) of a call's members; st.at / st.len: where they lie going in, and coming out.  `last`: the
@@ -1794,8 +1806,16 @@ static int layers_batch_stage(Ctx &c, hipStream_t s, const uint8_t *const *ins, 
         const hipError_t e = copy_async(dp, hp, up, hipMemcpyHostToDevice, s);
         if (e != hipSuccess) return c.fail(RSN_ERR_DEVICE, "the upload of %zu bytes failed: %s", up, hipGetErrorString(e));
     }
-    const hipError_t e = hipStreamSynchronize(s);
-    return e == hipSuccess ? RSN_OK : c.fail(RSN_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    return stream_synced(c, s);
+}
+// Where the run [lo, lo + m) of a call's members lies going in: the host form's staged (layers_batch_stage), the device form's where the
+// caller has them.
+static int layers_batch_enter(Ctx &c, hipStream_t s, const LbMembers &in, size_t lo, size_t m, LbRunState &st) {
+    std::vector<size_t> offs;
+    if (in.staged()) return layers_batch_stage(c, s, in.ins + lo, in.lens + lo, m, offs, st);
+    st.at.resize(m); st.len.resize(m);
+    for (size_t i = 0; i < m; i++) { st.at[i] = (const uint8_t *)in.mem[lo + i].d_in; st.len[i] = in.mem[lo + i].n; }
+    return RSN_OK;
 }
 // the members' bytes as tiles of the move table; returns the entries written
 static size_t move_tiles(MoveEntry *tab, const uint8_t *src, uint8_t *dst, size_t len) {
@@ -1826,7 +1846,7 @@ static int layers_batch_dev(bool enc, size_t n, const rsn_dev_member *mem, const
             if (tight == LB_NONE) tight = i;
         }
         rc = members_move(c, s, tab, (MoveEntry *)dp, tiles); if (rc) return cleared(rc);
-        { const hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) return cleared(c.fail(RSN_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e))); }
+        rc = stream_synced(c, s); if (rc) return cleared(rc);
         if (tight == LB_NONE) return RSN_OK;
         return c.fail(RSN_ERR_CAPACITY, "member %zu: layers: output needs %zu bytes, buffer holds %zu", tight, (size_t)mem[tight].n, mem[tight].d_out ? (size_t)mem[tight].out_cap : (size_t)0);
     }
@@ -1841,8 +1861,7 @@ static int layers_batch_dev(bool enc, size_t n, const rsn_dev_member *mem, const
         if (steps == 0) break;
         const size_t m = r.hi - r.lo;
         LbRunState st;
-        st.at.resize(m); st.len.resize(m);
-        for (size_t i = 0; i < m; i++) { st.at[i] = (const uint8_t *)mem[r.lo + i].d_in; st.len[i] = mem[r.lo + i].n; }
+        rc = layers_batch_enter(c, s, LbMembers{nullptr, nullptr, mem}, r.lo, m, st); if (rc) return cleared(rc);
         const size_t before = f.step;
         rc = layers_batch_steps(c, s, enc, layers, n_layers, steps, 0, r.lo, m, mem + r.lo, st, out_lens + r.lo, f);
         if (rc && f.step == before) return cleared(rc);
@@ -1900,17 +1919,26 @@ static int layers_batch_host(bool enc, size_t n, const uint8_t *const *ins, cons
             const hipError_t e = copy_async((uint8_t *)hp + tb, (const uint8_t *)dp + tb, down, hipMemcpyDeviceToHost, s);
             if (e != hipSuccess) return dropped(c.fail(RSN_ERR_DEVICE, "the download of %zu bytes failed: %s", down, hipGetErrorString(e)));
         }
-        { const hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) return dropped(c.fail(RSN_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e))); }
+        rc = stream_synced(c, s); if (rc) return dropped(rc);
         for (size_t i = 0; i < m; i++) { rc = result_from_host(c, (const uint8_t *)hp + tb + offs[i], st.len[i], &outs[r.lo + i], &out_lens[r.lo + i]); if (rc) return dropped(rc); }
     }
     if (f.step != LB_NONE) return dropped(layers_batch_failure(c, enc, layers, n_layers, f));
     return RSN_OK;
 }
 
-// ---- batch round trip (rsn.h): engine.BenchmarkFile's body over many members.  The layered batch calls' runs and steps, twice
-// -- the compress pass, then the decompress pass from where the first left every member, beginning in the other arena -- and behind them ONE
-// launch of k_members_verify (roundtrip_batch.hip) over a table of the run's tiles; the run's stats block is all that comes down.  A round
-// trip is 2 L steps; `limit` is how far the runs still go: behind a failure the later runs go as far as the steps in front of it.
+// ---- batch round trip and batch suite (rsn.h): ONE flow, suite_batch_flow.  The suite is engine.BenchmarkFile's body
+// over many members under MANY layer lists -- the reference's benchmark loop, files x algorithm lists -- with everything the lists have in
+// common done once; the batch round trip is the suite of its one list, whose tree is a chain with nothing kept, and differs in what it
+// hands the flow: its own slot set, answers without the "list <l>: " in front, and its histograms as the first verify launch's rows whole.
+// The lists form a prefix tree (suite_layout.h).  A run stages its members once, walks the tree depth first and compresses every node
+// once -- ONE step of layers_batch_steps, from where the parent's step left the members, in the arena a call of that list alone would
+// use at that step -- or, a node with more users (a kept node), into its own slots of LB_KEEP, which the run carves before its first
+// step and no step reuses.  From the node a list ends at: its decompress pass, beginning in the arena the compress pass did not end in,
+// and ONE launch of k_members_verify (roundtrip_batch.hip) over a table of the run's tiles; the stats block is all that comes down.  The
+// run's first verify launch counts both sides; every further list's is the instance that counts the decompressed side alone.
+// A list's round trip is 2 L steps and every list keeps its own bookkeeping -- the two passes' failures, `limit`: how far its runs still
+// go (behind a failure the later runs go as far as the steps in front of it), the 32-bit limit -- so its answer does not depend on the
+// lists beside it; a node runs while any list through it still goes that far.
 namespace {
 // the largest slot of the decompress pass of a member of n bytes, for the run cuts: the stream behind compress layer k is at most its bound
 // and taken as at most twice the member and a header -- an estimate, as layers_batch_slot's is for a decompress call
@@ -1922,91 +1950,246 @@ size_t roundtrip_dec_slot(const int *layers, size_t n_layers, size_t n) {
     }
     return most;
 }
-}  // namespace
-
-// ins / lens: the host form (a run's inputs are staged in LB_STAGE and stay there to the end of the run); mem: the device form (read where
-// they lie).  The arguments have been checked and res zeroed.
-static int roundtrip_batch_flow(Ctx &c, hipStream_t s, size_t n, const uint8_t *const *ins, const size_t *lens, const rsn_dev_member *mem, const int *layers, size_t n_layers,
-                                rsn_roundtrip_member *res, uint32_t *hists) {
-    const bool staged = mem == nullptr;
-    auto len_of = [&](size_t i) { return staged ? lens[i] : (size_t)mem[i].n; };
-    auto zeroed = [&](int code) { memset(res, 0, n * sizeof *res); return code; };
-    const std::vector<LbRun> runs = lb_runs(n, layers_batch_budget(), [&](size_t i) {
-        const size_t len = len_of(i);
+size_t suite_bound(int id, size_t len) { return layer_slot_cap(id, true, len); }
+struct SuiteListState { LbFailure fc, fd; size_t limit = 0, big = LB_NONE; };   // big: the lowest member the 32-bit counters do not hold
+int roundtrip_big_failure(Ctx &c, size_t big) {
+    return c.fail(RSN_ERR_LIMIT, "member %zu: a round trip of %zu bytes or more in a batch: the counters are 32 bits (rsn_layers_roundtrip takes one large buffer)", big, (size_t)1 << 32);
+}
+// where a call's answers go: n_lists * n rows, and what the caller asked for beside them (null: not asked for).  rows: the one-list form's
+// histograms, 512 words a member -- the first verify launch's stats rows, copied whole; h_orig / h_dec: the suite's, those rows split
+struct SuiteOut {
+    rsn_roundtrip_member *res; int *list_rc; uint32_t *h_orig, *h_dec, *rows, *best;
+    bool counting() const { return h_orig || h_dec || rows; }
+};
+// The plan of a call: the lists, their tree, under[v]: the lists that are run -- the first of every set of equal lists -- whose path
+// leads through node v (under[SUITE_ROOT]: all that are run), the run cuts and the largest run's bytes, for the admission.
+struct SuitePlan {
+    const int *lp[RSN_SUITE_LISTS_MAX]; size_t ln[RSN_SUITE_LISTS_MAX];
+    SuiteTree tree;
+    std::vector<size_t> kept;                                             // the kept nodes, ascending (one list: none)
+    std::vector<std::vector<size_t>> under;
+    std::vector<LbRun> runs; size_t most = 0;
+    const std::vector<size_t> &ran() const { return under[SUITE_ROOT]; }
+};
+SuitePlan suite_plan(const LbMembers &mem, size_t n, size_t n_lists, const rsn_layer_list *lists, bool counting) {
+    SuitePlan p;
+    for (size_t l = 0; l < n_lists; l++) { p.lp[l] = lists[l].layers; p.ln[l] = lists[l].n_layers; }
+    p.tree = suite_tree(p.lp, p.ln, n_lists);
+    const std::vector<SuiteNode> &nodes = p.tree.nodes;
+    p.under.resize(nodes.size());
+    for (size_t v = 0; v < nodes.size(); v++) {
+        if (nodes[v].kept) p.kept.push_back(v);
+        if (nodes[v].ends.empty()) continue;
+        for (size_t u = v;; u = nodes[u].parent) { p.under[u].push_back(nodes[v].ends[0]); if (u == SUITE_ROOT) break; }
+    }
+    std::vector<size_t> caps;
+    p.runs = lb_runs(n, layers_batch_budget(), [&](size_t i) {
+        const size_t len = mem.len(i);
+        size_t enc = 0, dec = 0;                                          // the largest over the lists of the two passes' largest slots
+        for (size_t l : p.ran()) { enc = std::max(enc, layers_batch_slot(true, p.lp[l], p.ln[l], len)); dec = std::max(dec, roundtrip_dec_slot(p.lp[l], p.ln[l], len)); }
         // (what comes back is taken as long as what went in: a member that comes back longer -- the Huffman codec's treatment of bytes that are
         //  not UTF-8 -- may take a table entry of 32 bytes more than the run was cut for)
-        return rb_member_need(staged ? len : 0, layers_batch_slot(true, layers, n_layers, len), roundtrip_dec_slot(layers, n_layers, len), len, len, hists != nullptr);
+        const size_t keep = p.kept.empty() ? 0 : suite_keep_bytes(p.tree, len, suite_bound, &caps);
+        return suite_member_need(mem.staged() ? len : 0, enc, dec, keep, len, len, counting);
     });
-    size_t most = 0;
-    for (const LbRun &r : runs) most = std::max(most, r.bytes);
-    Admission gate(c, slotset::ROUNDTRIP_BATCH_CALL); gate.admit(most, ADMIT_FROM);
-    LbFailure fc, fd;                                                     // the compress pass's and the decompress pass's
-    size_t limit = 2 * n_layers, big = LB_NONE;                           // big: the lowest member the 32-bit counters do not hold
-    std::vector<size_t> offs, got, comp;
+    for (const LbRun &r : p.runs) p.most = std::max(p.most, r.bytes);
+    return p;
+}
+
+// The run [lo, lo + m) of a call on its way through the tree.  orig: where its members lie going in; keep[v]: the m slots of kept node v
+// as the d_out / out_cap of its step; verified: a list of this run has been through the verify launch, so the originals are counted.
+struct SuiteRun {
+    Ctx &c; hipStream_t s; const LbMembers &mem; size_t n; const SuitePlan &p; const SuiteOut &out; std::vector<SuiteListState> &ls;
+    size_t lo, m;
     std::vector<const uint8_t *> orig;
-    int rc;
-    auto synced = [&]() { const hipError_t e = hipStreamSynchronize(s); return e == hipSuccess ? RSN_OK : c.fail(RSN_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e)); };
-    for (const LbRun &r : runs) {
-        if (n_layers && limit == 0) break;
-        const size_t m = r.hi - r.lo;
-        LbRunState st;
-        st.at.resize(m); st.len.resize(m); orig.resize(m);
-        void *hp, *dp;
-        if (staged) {                                                     // up: as layers_batch_host; the inputs stay in LB_STAGE to the end of the run
-            rc = layers_batch_stage(c, s, ins + r.lo, lens + r.lo, m, offs, st); if (rc) return zeroed(rc);
-        } else {
-            for (size_t i = 0; i < m; i++) { st.at[i] = (const uint8_t *)mem[r.lo + i].d_in; st.len[i] = mem[r.lo + i].n; }
-        }
-        for (size_t i = 0; i < m; i++) orig[i] = st.at[i];
-        got.assign(m, 0);
-        // the compress pass: steps 0 .. L - 1 of the round trip
-        size_t before = fc.step;
-        rc = layers_batch_steps(c, s, true, layers, n_layers, std::min(limit, n_layers), 0, r.lo, m, nullptr, st, got.data(), fc);
-        if (rc && fc.step == before) return zeroed(rc);
-        if (rc) { limit = fc.step; continue; }
-        if (n_layers && limit <= n_layers) continue;                      // (the call has failed in or right behind this pass: the run only looked for an earlier failure)
-        comp = st.len;
-        // the decompress pass: steps L .. 2 L - 1, from the arena the compress pass did not end in
-        before = fd.step;
-        rc = layers_batch_steps(c, s, false, layers, n_layers, limit - n_layers, n_layers & 1, r.lo, m, nullptr, st, got.data(), fd);
-        if (rc && fd.step == before) return zeroed(rc);
-        if (rc) { limit = n_layers + fd.step; continue; }
-        if (limit < 2 * n_layers || big != LB_NONE) continue;
-        // verify: the table up, ONE launch, the stats block down
-        size_t tiles = 0;
-        for (size_t i = 0; i < m; i++) {
-            if (!rb_fits(len_of(r.lo + i)) || !rb_fits(st.len[i])) { big = r.lo + i; break; }
-            tiles += rb_tiles(len_of(r.lo + i), st.len[i]);
-        }
-        if (big != LB_NONE) continue;
-        const bool counting = hists != nullptr;
-        const RbLayout lay = rb_layout(tiles, m, counting);
-        rc = pinned_buf(c, lay.bytes + 16, &hp); if (rc) return zeroed(rc);
-        rc = dev_buf(c, Slot::LB_VERIFY, lay.bytes + 16, &dp); if (rc) return zeroed(rc);
-        RbEntry *tab = (RbEntry *)((uint8_t *)hp + lay.table);
-        tiles = 0;
-        for (size_t i = 0; i < m; i++)
-            for (size_t t = 0, k = rb_tiles(len_of(r.lo + i), st.len[i]); t < k; t++)
-                tab[tiles++] = RbEntry{orig[i], st.at[i], (uint32_t)len_of(r.lo + i), (uint32_t)st.len[i], (uint32_t)i, (uint32_t)t};
-        rc = members_verify(c, s, tab, tiles, m, counting, dp); if (rc) return zeroed(rc);
-        {
-            const size_t down = rb_stats_bytes(lay);
-            const hipError_t e = copy_async((uint8_t *)hp + lay.words, (const uint8_t *)dp + lay.words, down, hipMemcpyDeviceToHost, s);
-            if (e != hipSuccess) return zeroed(c.fail(RSN_ERR_DEVICE, "the download of %zu bytes failed: %s", down, hipGetErrorString(e)));
-        }
-        rc = synced(); if (rc) return zeroed(rc);
-        const unsigned long long *words = (const unsigned long long *)((const uint8_t *)hp + lay.words);
-        for (size_t i = 0; i < m; i++) {
-            rsn_roundtrip_member &o = res[r.lo + i];
-            o.original_n = len_of(r.lo + i); o.compressed_n = comp[i]; o.decompressed_n = st.len[i];
-            o.first_difference = words[i] ? ~words[i] : (o.original_n == o.decompressed_n ? UINT64_MAX : std::min(o.original_n, o.decompressed_n));
-            o.lossless = o.first_difference == UINT64_MAX;
-        }
-        if (counting) memcpy(hists + r.lo * RB_HIST_WORDS, (const uint8_t *)hp + lay.hists, m * RB_HIST_BYTES);
+    std::vector<size_t> got;
+    std::vector<std::vector<rsn_dev_member>> keep;
+    bool verified = false;
+
+    int carve(const LbRunState &st0);
+    int verify(size_t l, const LbRunState &in, const LbRunState &st);
+    int list_finish(size_t l, const LbRunState &in);
+    int node_walk(size_t v, const LbRunState &in);
+};
+
+// the kept nodes' slots: node-major in LB_KEEP, a slot a member of the compress bounds applied in turn from the root
+int SuiteRun::carve(const LbRunState &st0) {
+    const size_t V = p.tree.nodes.size();
+    const std::vector<size_t> &kept = p.kept;
+    keep.assign(V, {});
+    if (kept.empty()) return RSN_OK;
+    std::vector<size_t> caps, base(V, 0);
+    std::vector<std::vector<size_t>> ncap(V), koffs(V);
+    for (size_t v : kept) ncap[v].resize(m);
+    for (size_t i = 0; i < m; i++) {
+        suite_keep_bytes(p.tree, st0.len[i], suite_bound, &caps);
+        for (size_t v : kept) ncap[v][i] = caps[v];
     }
-    if (fc.step != LB_NONE) return zeroed(layers_batch_failure(c, true, layers, n_layers, fc));
-    if (fd.step != LB_NONE) return zeroed(layers_batch_failure(c, false, layers, n_layers, fd));
-    if (big != LB_NONE) return zeroed(c.fail(RSN_ERR_LIMIT, "member %zu: a round trip of %zu bytes or more in a batch: the counters are 32 bits (rsn_layers_roundtrip takes one large buffer)", big, (size_t)1 << 32));
+    size_t total = 0;
+    for (size_t v : kept) { base[v] = total; total += lb_arena(ncap[v].data(), m, koffs[v]); }
+    void *kp = nullptr;
+    if (total) { const int rc = dev_buf(c, Slot::LB_KEEP, total, &kp); if (rc) return rc; }
+    for (size_t v : kept) {
+        keep[v].resize(m);
+        for (size_t i = 0; i < m; i++) keep[v][i] = rsn_dev_member{nullptr, 0, (uint8_t *)kp + base[v] + koffs[v][i], ncap[v][i]};
+    }
+    return RSN_OK;
+}
+
+// The verify pass of list l.  in: where its compress pass left the members (their compressed sizes); st: where its decompress pass did.
+// The table up, ONE launch, the stats block down; then the rows, and the histograms where the caller wants them.
+int SuiteRun::verify(size_t l, const LbRunState &in, const LbRunState &st) {
+    size_t tiles = 0;
+    for (size_t i = 0; i < m; i++) {
+        if (!rb_fits(mem.len(lo + i)) || !rb_fits(st.len[i])) { ls[l].big = lo + i; return RSN_OK; }
+        tiles += rb_tiles(mem.len(lo + i), st.len[i]);
+    }
+    const bool first = !verified, cnt = first ? out.counting() : out.h_dec != nullptr;
+    const RbLayout lay = verify_layout(first, tiles, m, cnt);
+    void *hp, *dp;
+    int rc = pinned_buf(c, lay.bytes + 16, &hp); if (rc) return rc;
+    rc = dev_buf(c, Slot::LB_VERIFY, lay.bytes + 16, &dp); if (rc) return rc;
+    RbEntry *tab = (RbEntry *)((uint8_t *)hp + lay.table);
+    tiles = 0;
+    for (size_t i = 0; i < m; i++)
+        for (size_t t = 0, k = rb_tiles(mem.len(lo + i), st.len[i]); t < k; t++)
+            tab[tiles++] = RbEntry{orig[i], st.at[i], (uint32_t)mem.len(lo + i), (uint32_t)st.len[i], (uint32_t)i, (uint32_t)t};
+    rc = members_verify(c, s, first, tab, tiles, m, cnt, dp); if (rc) return rc;
+    {
+        const size_t down = rb_stats_bytes(lay);
+        const hipError_t e = copy_async((uint8_t *)hp + lay.words, (const uint8_t *)dp + lay.words, down, hipMemcpyDeviceToHost, s);
+        if (e != hipSuccess) return c.fail(RSN_ERR_DEVICE, "the download of %zu bytes failed: %s", down, hipGetErrorString(e));
+    }
+    rc = stream_synced(c, s); if (rc) return rc;
+    verified = true;
+    const unsigned long long *words = (const unsigned long long *)((const uint8_t *)hp + lay.words);
+    for (size_t i = 0; i < m; i++) {
+        rsn_roundtrip_member &o = out.res[l * n + lo + i];
+        o.original_n = mem.len(lo + i); o.compressed_n = in.len[i]; o.decompressed_n = st.len[i];
+        o.first_difference = words[i] ? ~words[i] : (o.original_n == o.decompressed_n ? UINT64_MAX : std::min(o.original_n, o.decompressed_n));
+        o.lossless = o.first_difference == UINT64_MAX;
+    }
+    if (!cnt) return RSN_OK;
+    const uint32_t *rows = (const uint32_t *)((const uint8_t *)hp + lay.hists);
+    uint32_t *dec_rows = out.h_dec ? out.h_dec + (l * n + lo) * SUITE_HIST_WORDS : nullptr;
+    if (!first) { memcpy(dec_rows, rows, m * SUITE_HIST_BYTES); return RSN_OK; }
+    if (out.rows) memcpy(out.rows + lo * RB_HIST_WORDS, rows, m * RB_HIST_BYTES);
+    if (!out.h_orig && !dec_rows) return RSN_OK;
+    for (size_t i = 0; i < m; i++) {                                      // the rows split: the original's half, then the decompressed half
+        if (out.h_orig) memcpy(out.h_orig + (lo + i) * SUITE_HIST_WORDS, rows + i * RB_HIST_WORDS, SUITE_HIST_BYTES);
+        if (dec_rows) memcpy(dec_rows + i * SUITE_HIST_WORDS, rows + i * RB_HIST_WORDS + SUITE_HIST_WORDS, SUITE_HIST_BYTES);
+    }
+    return RSN_OK;
+}
+
+// list l from the node it ends at (`in`: where that node left the members): the decompress pass -- steps L .. 2 L - 1 of its round trip,
+// from the arena the compress pass did not end in -- and the verify pass
+int SuiteRun::list_finish(size_t l, const LbRunState &in) {
+    SuiteListState &q = ls[l];
+    const size_t L = p.ln[l];
+    if (L && q.limit <= L) return RSN_OK;                                 // (the list has failed in or right behind its compress pass: the run only looked for an earlier failure)
+    LbRunState st;
+    st.at = in.at; st.len = in.len;
+    const size_t before = q.fd.step;
+    const int rc = layers_batch_steps(c, s, false, p.lp[l], L, q.limit - L, L & 1, lo, m, nullptr, st, got.data(), q.fd);
+    if (rc && q.fd.step == before) return rc;
+    if (rc) { q.limit = L + q.fd.step; return RSN_OK; }
+    if (q.limit < 2 * L || q.big != LB_NONE) return RSN_OK;
+    return verify(l, in, st);
+}
+
+// node v and everything below it; `in`: where v's step left the members
+int SuiteRun::node_walk(size_t v, const LbRunState &in) {
+    const SuiteNode &node = p.tree.nodes[v];
+    if (!node.ends.empty()) { const int rc = list_finish(node.ends[0], in); if (rc) return rc; }
+    const size_t step = node.depth;                                       // a child's compress step, counted as a call of one of its lists alone counts it
+    for (size_t kid : node.kids) {
+        bool wanted = false;
+        for (size_t l : p.under[kid]) wanted = wanted || ls[l].limit > step;
+        if (!wanted) continue;
+        const SuiteNode &k = p.tree.nodes[kid];
+        LbRunState st;
+        st.at = in.at; st.len = in.len;
+        LbFailure f;
+        int rc = layers_batch_steps(c, s, true, &k.layer, 1, 1, step & 1, lo, m, k.kept ? keep[kid].data() : nullptr, st, got.data(), f);
+        if (rc && f.step == LB_NONE) return rc;
+        if (rc) {                                                         // the step's failure is every list's that still went this far
+            f.step = step;
+            for (size_t l : p.under[kid]) if (ls[l].limit > step) { ls[l].fc = f; ls[l].limit = step; }
+            continue;
+        }
+        if (st.tight != LB_NONE) return c.fail(RSN_ERR_DEVICE, "layers: internal error: member %zu outgrew the kept slot of its compress bound", st.tight);
+        rc = node_walk(kid, st); if (rc) return rc;
+    }
+    return RSN_OK;
+}
+
+// every list's answer once the runs are through: its code, its rows zeroed when it failed, the equal lists' copies, list_rc and best;
+// the call's answer is the lowest failing list's, prefixed: with "list <l>: " in front (the suite)
+int suite_answers(Ctx &c, const SuitePlan &p, const std::vector<SuiteListState> &ls, size_t n, const SuiteOut &out, bool prefixed) {
+    const size_t n_lists = ls.size();
+    rsn_roundtrip_member *res = out.res;
+    std::vector<int> code(n_lists, RSN_OK);
+    std::vector<std::string> msg(n_lists);
+    for (size_t l : p.ran()) {
+        const SuiteListState &q = ls[l];
+        if (q.fc.step != LB_NONE) code[l] = layers_batch_failure(c, true, p.lp[l], p.ln[l], q.fc);
+        else if (q.fd.step != LB_NONE) code[l] = layers_batch_failure(c, false, p.lp[l], p.ln[l], q.fd);
+        else if (q.big != LB_NONE) code[l] = roundtrip_big_failure(c, q.big);
+        if (code[l]) { msg[l] = c.err; memset(res + l * n, 0, n * sizeof *res); }
+    }
+    for (const SuiteNode &node : p.tree.nodes)                            // equal lists: the rows of the one that ran
+        for (size_t k = 1; k < node.ends.size(); k++) {
+            const size_t from = node.ends[0], to = node.ends[k];
+            code[to] = code[from]; msg[to] = msg[from];
+            memcpy(res + to * n, res + from * n, n * sizeof *res);
+            if (out.h_dec && !code[from]) memcpy(out.h_dec + to * n * SUITE_HIST_WORDS, out.h_dec + from * n * SUITE_HIST_WORDS, n * SUITE_HIST_BYTES);
+        }
+    if (out.list_rc) for (size_t l = 0; l < n_lists; l++) out.list_rc[l] = code[l];
+    if (out.best)
+        for (size_t i = 0; i < n; i++)
+            out.best[i] = suite_best(n_lists, [&](size_t l) { return code[l] == RSN_OK; }, [&](size_t l) { return res[l * n + i].compressed_n; });
+    for (size_t l = 0; l < n_lists; l++)
+        if (code[l]) return prefixed ? c.fail(code[l], "list %zu: %s", l, msg[l].c_str()) : c.fail(code[l], "%s", msg[l].c_str());
+    return RSN_OK;
+}
+}  // namespace
+
+// The arguments have been checked and out.res zeroed.  slots: what the call's gate gives back.  A failure of the call as a whole zeroes
+// every row and leaves list_rc and best alone.
+static int suite_batch_flow(Ctx &c, hipStream_t s, size_t n, const LbMembers &mem, size_t n_lists, const rsn_layer_list *lists, unsigned long long slots, bool prefixed,
+                            const SuiteOut &out) {
+    auto zeroed = [&](int code) { memset(out.res, 0, n_lists * n * sizeof *out.res); return code; };
+    const SuitePlan p = suite_plan(mem, n, n_lists, lists, out.counting());
+    Admission gate(c, slots); gate.admit(p.most, ADMIT_FROM);
+    std::vector<SuiteListState> ls(n_lists);
+    for (size_t l : p.ran()) ls[l].limit = 2 * p.ln[l];
+    for (const LbRun &r : p.runs) {
+        bool any = false;
+        for (size_t l : p.ran()) any = any || p.ln[l] == 0 || ls[l].limit > 0;
+        if (!any) break;                                                  // (every list has failed at its first step: no earlier failure is left to find)
+        SuiteRun run{c, s, mem, n, p, out, ls, r.lo, r.hi - r.lo};
+        LbRunState st0;                                                   // up, ONCE for all lists; the host form's inputs stay in LB_STAGE to the end of the run
+        int rc = layers_batch_enter(c, s, mem, r.lo, run.m, st0); if (rc) return zeroed(rc);
+        run.orig = st0.at; run.got.assign(run.m, 0);
+        rc = run.carve(st0); if (rc) return zeroed(rc);
+        rc = run.node_walk(SUITE_ROOT, st0); if (rc) return zeroed(rc);
+    }
+    return suite_answers(c, p, ls, n, out, prefixed);
+}
+
+// the members of the round trip's and the suite's host forms, behind the arrays' own null checks
+static int roundtrip_members_host(Ctx &c, size_t n, const uint8_t *const *ins, const size_t *lens) {
+    for (size_t i = 0; i < n; i++) if (!ins[i] && lens[i]) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
+    return RSN_OK;
+}
+// ... and of their device forms: batch_dev_args' rules on d_in; these calls write no caller memory on the device
+static int roundtrip_members_dev(Ctx &c, size_t n, const rsn_dev_member *mem) {
+    for (size_t i = 0; i < n; i++) {
+        if (!mem[i].d_in && mem[i].n) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
+        if (mem[i].d_out || mem[i].out_cap) return c.fail(RSN_ERR_ARG, "member %zu: d_out and out_cap are reserved in a round trip: NULL and 0", i);
+        if ((uintptr_t)mem[i].d_in & 15) return c.fail(RSN_ERR_ARG, "member %zu: layers: device buffers must be 16-byte aligned", i);
+    }
     return RSN_OK;
 }
 
@@ -2015,10 +2198,11 @@ static int layers_roundtrip_batch_host(size_t n, const uint8_t *const *ins, cons
     if (n == 0) return RSN_OK;
     if (!ins || !lens || !res) return c.fail(RSN_ERR_ARG, "null argument");
     memset(res, 0, n * sizeof *res);
-    for (size_t i = 0; i < n; i++) if (!ins[i] && lens[i]) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
-    int rc = layers_check(c, layers, n_layers); if (rc) return rc;
+    int rc = roundtrip_members_host(c, n, ins, lens); if (rc) return rc;
+    rc = layers_check(c, layers, n_layers); if (rc) return rc;
     rc = ctx_init(c); if (rc) return rc;                                  // (no device: RSN_ERR_DEVICE -- there is no CPU path)
-    return roundtrip_batch_flow(c, c.own_stream, n, ins, lens, nullptr, layers, n_layers, res, hists);
+    const rsn_layer_list one{layers, n_layers};
+    return suite_batch_flow(c, c.own_stream, n, LbMembers{ins, lens, nullptr}, 1, &one, slotset::ROUNDTRIP_BATCH_CALL, false, SuiteOut{res, nullptr, nullptr, nullptr, hists, nullptr});
 }
 
 static int layers_roundtrip_batch_dev(size_t n, const rsn_dev_member *mem, const int *layers, size_t n_layers, rsn_roundtrip_member *res, uint32_t *hists, void *stream) {
@@ -2026,203 +2210,11 @@ static int layers_roundtrip_batch_dev(size_t n, const rsn_dev_member *mem, const
     if (n == 0) return RSN_OK;
     if (!mem || !res) return c.fail(RSN_ERR_ARG, "null argument");
     memset(res, 0, n * sizeof *res);
-    for (size_t i = 0; i < n; i++) {                                      // (batch_dev_args' rules on d_in; this call writes no caller memory on the device)
-        if (!mem[i].d_in && mem[i].n) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
-        if (mem[i].d_out || mem[i].out_cap) return c.fail(RSN_ERR_ARG, "member %zu: d_out and out_cap are reserved in a round trip: NULL and 0", i);
-        if ((uintptr_t)mem[i].d_in & 15) return c.fail(RSN_ERR_ARG, "member %zu: layers: device buffers must be 16-byte aligned", i);
-    }
-    int rc = layers_check(c, layers, n_layers); if (rc) return rc;
+    int rc = roundtrip_members_dev(c, n, mem); if (rc) return rc;
+    rc = layers_check(c, layers, n_layers); if (rc) return rc;
     rc = dev_prologue(c, stream, &s); if (rc) return rc;
-    return roundtrip_batch_flow(c, s, n, nullptr, nullptr, mem, layers, n_layers, res, hists);
-}
-
-// ---- batch suite (rsn.h): the batch round trip of MANY layer lists over the same members -- the reference's benchmark loop,
-// files x algorithm lists -- with everything the lists have in common done once.  The lists form a prefix tree (suite_layout.h); a run
-// stages its members once, walks the tree depth first and compresses every node once -- ONE step of layers_batch_steps, from where the
-// parent's step left the members -- and a list's decompress pass and verify launch start from the node it ends at, as roundtrip_batch_flow's
-// do.  A node with one user writes into the arena a call of that list alone would use at that step; a node with more users (a kept node)
-// into its own slots of LB_KEEP, which the run carves before its first step and no step reuses.  The run's first verify launch is
-// k_members_verify as it has been and counts the originals; every further list's is the instance that counts the decompressed side alone.
-// Every list keeps roundtrip_batch_flow's bookkeeping of its own (the two failures, how far its runs still go, the 32-bit limit), so its
-// answer is the one that call gives for it alone; a node runs while any list through it still goes that far.
-namespace {
-struct SuiteListState { LbFailure fc, fd; size_t limit = 0, big = LB_NONE; };
-int roundtrip_big_failure(Ctx &c, size_t big) {
-    return c.fail(RSN_ERR_LIMIT, "member %zu: a round trip of %zu bytes or more in a batch: the counters are 32 bits (rsn_layers_roundtrip takes one large buffer)", big, (size_t)1 << 32);
-}
-}  // namespace
-
-// The arguments have been checked and res zeroed.  A failure of the call as a whole zeroes every row and leaves list_rc and best alone.
-static int suite_batch_flow(Ctx &c, hipStream_t s, size_t n, const uint8_t *const *ins, const size_t *lens, const rsn_dev_member *mem, size_t n_lists, const rsn_layer_list *lists,
-                            rsn_roundtrip_member *res, int *list_rc, uint32_t *h_orig, uint32_t *h_dec, uint32_t *best) {
-    const bool staged = mem == nullptr, counting = h_orig || h_dec;
-    auto len_of = [&](size_t i) { return staged ? lens[i] : (size_t)mem[i].n; };
-    auto zeroed = [&](int code) { memset(res, 0, n_lists * n * sizeof *res); return code; };
-    const int *lp[RSN_SUITE_LISTS_MAX]; size_t ln[RSN_SUITE_LISTS_MAX];
-    for (size_t l = 0; l < n_lists; l++) { lp[l] = lists[l].layers; ln[l] = lists[l].n_layers; }
-    const SuiteTree tree = suite_tree(lp, ln, n_lists);
-    const size_t V = tree.nodes.size();
-    // under[v]: the lists that are run -- the first of every set of equal lists -- whose path leads through node v; under[SUITE_ROOT]: all that are run
-    std::vector<std::vector<size_t>> under(V);
-    for (size_t v = 0; v < V; v++) {
-        if (tree.nodes[v].ends.empty()) continue;
-        for (size_t u = v;; u = tree.nodes[u].parent) { under[u].push_back(tree.nodes[v].ends[0]); if (u == SUITE_ROOT) break; }
-    }
-    const std::vector<size_t> &ran = under[SUITE_ROOT];
-    auto bound = [](int id, size_t len) { return layer_slot_cap(id, true, len); };
-    const std::vector<LbRun> runs = lb_runs(n, layers_batch_budget(), [&](size_t i) {
-        const size_t len = len_of(i);
-        size_t enc = 0, dec = 0;                                          // (as roundtrip_batch_flow takes them, the largest over the lists)
-        for (size_t l : ran) { enc = std::max(enc, layers_batch_slot(true, lp[l], ln[l], len)); dec = std::max(dec, roundtrip_dec_slot(lp[l], ln[l], len)); }
-        return suite_member_need(staged ? len : 0, enc, dec, suite_keep_bytes(tree, len, bound), len, len, counting);
-    });
-    size_t most = 0;
-    for (const LbRun &r : runs) most = std::max(most, r.bytes);
-    Admission gate(c, slotset::SUITE_BATCH_CALL); gate.admit(most, ADMIT_FROM);
-    std::vector<SuiteListState> ls(n_lists);
-    for (size_t l : ran) ls[l].limit = 2 * ln[l];
-    std::vector<size_t> offs, got, caps;
-    std::vector<const uint8_t *> orig;
-    int rc;
-    auto synced = [&]() { const hipError_t e = hipStreamSynchronize(s); return e == hipSuccess ? RSN_OK : c.fail(RSN_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e)); };
-    for (const LbRun &r : runs) {
-        bool any = false;
-        for (size_t l : ran) any = any || ln[l] == 0 || ls[l].limit > 0;
-        if (!any) break;                                                  // (every list has failed at its first step: no earlier failure is left to find)
-        const size_t m = r.hi - r.lo;
-        LbRunState st0;
-        st0.at.resize(m); st0.len.resize(m); orig.resize(m);
-        if (staged) {                                                     // up, ONCE for all lists: as layers_batch_host; the inputs stay in LB_STAGE to the end of the run
-            rc = layers_batch_stage(c, s, ins + r.lo, lens + r.lo, m, offs, st0); if (rc) return zeroed(rc);
-        } else {
-            for (size_t i = 0; i < m; i++) { st0.at[i] = (const uint8_t *)mem[r.lo + i].d_in; st0.len[i] = mem[r.lo + i].n; }
-        }
-        for (size_t i = 0; i < m; i++) orig[i] = st0.at[i];
-        got.assign(m, 0);
-        // the kept nodes' slots: node-major in LB_KEEP, a slot a member of the compress bounds applied in turn from the root
-        std::vector<std::vector<size_t>> ncap(V, std::vector<size_t>(m));
-        std::vector<std::vector<rsn_dev_member>> keep(V);
-        for (size_t i = 0; i < m; i++) {
-            suite_keep_bytes(tree, st0.len[i], bound, &caps);
-            for (size_t v = 0; v < V; v++) ncap[v][i] = caps[v];
-        }
-        {
-            size_t total = 0;
-            std::vector<size_t> base(V, 0);
-            std::vector<std::vector<size_t>> koffs(V);
-            for (size_t v = 0; v < V; v++) if (tree.nodes[v].kept) { base[v] = total; total += lb_arena(ncap[v].data(), m, koffs[v]); }
-            void *kp = nullptr;
-            if (total) { rc = dev_buf(c, Slot::LB_KEEP, total, &kp); if (rc) return zeroed(rc); }
-            for (size_t v = 0; v < V; v++) {
-                if (!tree.nodes[v].kept) continue;
-                keep[v].resize(m);
-                for (size_t i = 0; i < m; i++) keep[v][i] = rsn_dev_member{nullptr, 0, (uint8_t *)kp + base[v] + koffs[v][i], ncap[v][i]};
-            }
-        }
-        bool verified = false;                                            // has a list of this run been through the verify launch: the originals are counted
-        // list l from the node it ends at (`in`: where that node left the members): the decompress pass and the verify launch
-        auto finish = [&](size_t l, const LbRunState &in) -> int {
-            SuiteListState &q = ls[l];
-            const size_t L = ln[l];
-            if (L && q.limit <= L) return RSN_OK;                         // (the list has failed in or right behind its compress pass: the run only looked for an earlier failure)
-            LbRunState st;
-            st.at = in.at; st.len = in.len;
-            const size_t before = q.fd.step;
-            int rc = layers_batch_steps(c, s, false, lp[l], L, q.limit - L, L & 1, r.lo, m, nullptr, st, got.data(), q.fd);
-            if (rc && q.fd.step == before) return rc;
-            if (rc) { q.limit = L + q.fd.step; return RSN_OK; }
-            if (q.limit < 2 * L || q.big != LB_NONE) return RSN_OK;
-            size_t tiles = 0;
-            for (size_t i = 0; i < m; i++) {
-                if (!rb_fits(len_of(r.lo + i)) || !rb_fits(st.len[i])) { q.big = r.lo + i; return RSN_OK; }
-                tiles += rb_tiles(len_of(r.lo + i), st.len[i]);
-            }
-            const bool first = !verified, cnt = first ? counting : h_dec != nullptr;
-            const RbLayout lay = first ? rb_layout(tiles, m, cnt) : suite_dec_layout(tiles, m, cnt);
-            void *hp, *dp;
-            rc = pinned_buf(c, lay.bytes + 16, &hp); if (rc) return rc;
-            rc = dev_buf(c, Slot::LB_VERIFY, lay.bytes + 16, &dp); if (rc) return rc;
-            RbEntry *tab = (RbEntry *)((uint8_t *)hp + lay.table);
-            tiles = 0;
-            for (size_t i = 0; i < m; i++)
-                for (size_t t = 0, k = rb_tiles(len_of(r.lo + i), st.len[i]); t < k; t++)
-                    tab[tiles++] = RbEntry{orig[i], st.at[i], (uint32_t)len_of(r.lo + i), (uint32_t)st.len[i], (uint32_t)i, (uint32_t)t};
-            rc = first ? members_verify(c, s, tab, tiles, m, cnt, dp) : members_verify_dec(c, s, tab, tiles, m, cnt, dp);
-            if (rc) return rc;
-            {
-                const size_t down = rb_stats_bytes(lay);
-                const hipError_t e = copy_async((uint8_t *)hp + lay.words, (const uint8_t *)dp + lay.words, down, hipMemcpyDeviceToHost, s);
-                if (e != hipSuccess) return c.fail(RSN_ERR_DEVICE, "the download of %zu bytes failed: %s", down, hipGetErrorString(e));
-            }
-            rc = synced(); if (rc) return rc;
-            verified = true;
-            const unsigned long long *words = (const unsigned long long *)((const uint8_t *)hp + lay.words);
-            for (size_t i = 0; i < m; i++) {
-                rsn_roundtrip_member &o = res[l * n + r.lo + i];
-                o.original_n = len_of(r.lo + i); o.compressed_n = in.len[i]; o.decompressed_n = st.len[i];
-                o.first_difference = words[i] ? ~words[i] : (o.original_n == o.decompressed_n ? UINT64_MAX : std::min(o.original_n, o.decompressed_n));
-                o.lossless = o.first_difference == UINT64_MAX;
-            }
-            if (!cnt) return RSN_OK;
-            const uint32_t *rows = (const uint32_t *)((const uint8_t *)hp + lay.hists);
-            uint32_t *dec_rows = h_dec ? h_dec + (l * n + r.lo) * SUITE_HIST_WORDS : nullptr;
-            if (!first) { memcpy(dec_rows, rows, m * SUITE_HIST_BYTES); return RSN_OK; }
-            for (size_t i = 0; i < m; i++) {                              // the round trip's rows: the original's half, then the decompressed half
-                if (h_orig) memcpy(h_orig + (r.lo + i) * SUITE_HIST_WORDS, rows + i * RB_HIST_WORDS, SUITE_HIST_BYTES);
-                if (dec_rows) memcpy(dec_rows + i * SUITE_HIST_WORDS, rows + i * RB_HIST_WORDS + SUITE_HIST_WORDS, SUITE_HIST_BYTES);
-            }
-            return RSN_OK;
-        };
-        // node v and everything below it; `in`: where v's step left the members
-        std::function<int(size_t, const LbRunState &)> walk = [&](size_t v, const LbRunState &in) -> int {
-            const SuiteNode &node = tree.nodes[v];
-            if (!node.ends.empty()) { const int rc = finish(node.ends[0], in); if (rc) return rc; }
-            const size_t step = node.depth;                               // a child's compress step, counted as a call of one of its lists alone counts it
-            for (size_t kid : node.kids) {
-                bool wanted = false;
-                for (size_t l : under[kid]) wanted = wanted || ls[l].limit > step;
-                if (!wanted) continue;
-                const SuiteNode &k = tree.nodes[kid];
-                LbRunState st;
-                st.at = in.at; st.len = in.len;
-                LbFailure f;
-                int rc = layers_batch_steps(c, s, true, &k.layer, 1, 1, step & 1, r.lo, m, k.kept ? keep[kid].data() : nullptr, st, got.data(), f);
-                if (rc && f.step == LB_NONE) return rc;
-                if (rc) {                                                 // the step's failure is every list's that still went this far
-                    f.step = step;
-                    for (size_t l : under[kid]) if (ls[l].limit > step) { ls[l].fc = f; ls[l].limit = step; }
-                    continue;
-                }
-                if (st.tight != LB_NONE) return c.fail(RSN_ERR_DEVICE, "layers: internal error: member %zu outgrew the kept slot of its compress bound", st.tight);
-                rc = walk(kid, st); if (rc) return rc;
-            }
-            return RSN_OK;
-        };
-        rc = walk(SUITE_ROOT, st0); if (rc) return zeroed(rc);
-    }
-    // every list's answer, as roundtrip_batch_flow ends
-    std::vector<int> code(n_lists, RSN_OK);
-    std::vector<std::string> msg(n_lists);
-    for (size_t l : ran) {
-        const SuiteListState &q = ls[l];
-        if (q.fc.step != LB_NONE) code[l] = layers_batch_failure(c, true, lp[l], ln[l], q.fc);
-        else if (q.fd.step != LB_NONE) code[l] = layers_batch_failure(c, false, lp[l], ln[l], q.fd);
-        else if (q.big != LB_NONE) code[l] = roundtrip_big_failure(c, q.big);
-        if (code[l]) { msg[l] = c.err; memset(res + l * n, 0, n * sizeof *res); }
-    }
-    for (const SuiteNode &node : tree.nodes)                             // equal lists: the rows of the one that ran
-        for (size_t k = 1; k < node.ends.size(); k++) {
-            const size_t from = node.ends[0], to = node.ends[k];
-            code[to] = code[from]; msg[to] = msg[from];
-            memcpy(res + to * n, res + from * n, n * sizeof *res);
-            if (h_dec && !code[from]) memcpy(h_dec + to * n * SUITE_HIST_WORDS, h_dec + from * n * SUITE_HIST_WORDS, n * SUITE_HIST_BYTES);
-        }
-    if (list_rc) for (size_t l = 0; l < n_lists; l++) list_rc[l] = code[l];
-    if (best)
-        for (size_t i = 0; i < n; i++)
-            best[i] = suite_best(n_lists, [&](size_t l) { return code[l] == RSN_OK; }, [&](size_t l) { return res[l * n + i].compressed_n; });
-    for (size_t l = 0; l < n_lists; l++) if (code[l]) return c.fail(code[l], "list %zu: %s", l, msg[l].c_str());
-    return RSN_OK;
+    const rsn_layer_list one{layers, n_layers};
+    return suite_batch_flow(c, s, n, LbMembers{nullptr, nullptr, mem}, 1, &one, slotset::ROUNDTRIP_BATCH_CALL, false, SuiteOut{res, nullptr, nullptr, nullptr, hists, nullptr});
 }
 
 // the layer lists of a suite call, behind the arrays and members: a null array, too many lists, then every list as layers_check takes it
@@ -2242,11 +2234,11 @@ static int layers_suite_batch_host(size_t n, const uint8_t *const *ins, const si
     if (n == 0) return RSN_OK;
     if (res && n_lists) memset(res, 0, n_lists * n * sizeof *res);
     if (!ins || !lens) return c.fail(RSN_ERR_ARG, "null argument");
-    for (size_t i = 0; i < n; i++) if (!ins[i] && lens[i]) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
+    int rc = roundtrip_members_host(c, n, ins, lens); if (rc) return rc;
     if (n_lists == 0) return RSN_OK;
-    int rc = suite_lists_check(c, n_lists, lists, res); if (rc) return rc;
+    rc = suite_lists_check(c, n_lists, lists, res); if (rc) return rc;
     rc = ctx_init(c); if (rc) return rc;                                  // (no device: RSN_ERR_DEVICE -- there is no CPU path)
-    return suite_batch_flow(c, c.own_stream, n, ins, lens, nullptr, n_lists, lists, res, list_rc, h_orig, h_dec, best);
+    return suite_batch_flow(c, c.own_stream, n, LbMembers{ins, lens, nullptr}, n_lists, lists, slotset::SUITE_BATCH_CALL, true, SuiteOut{res, list_rc, h_orig, h_dec, nullptr, best});
 }
 
 static int layers_suite_batch_dev(size_t n, const rsn_dev_member *mem, size_t n_lists, const rsn_layer_list *lists, rsn_roundtrip_member *res, int *list_rc,
@@ -2255,15 +2247,11 @@ static int layers_suite_batch_dev(size_t n, const rsn_dev_member *mem, size_t n_
     if (n == 0) return RSN_OK;
     if (res && n_lists) memset(res, 0, n_lists * n * sizeof *res);
     if (!mem) return c.fail(RSN_ERR_ARG, "null argument");
-    for (size_t i = 0; i < n; i++) {                                      // (rsn_layers_roundtrip_batch_dev's rules)
-        if (!mem[i].d_in && mem[i].n) return c.fail(RSN_ERR_ARG, "member %zu: null argument", i);
-        if (mem[i].d_out || mem[i].out_cap) return c.fail(RSN_ERR_ARG, "member %zu: d_out and out_cap are reserved in a round trip: NULL and 0", i);
-        if ((uintptr_t)mem[i].d_in & 15) return c.fail(RSN_ERR_ARG, "member %zu: layers: device buffers must be 16-byte aligned", i);
-    }
+    int rc = roundtrip_members_dev(c, n, mem); if (rc) return rc;
     if (n_lists == 0) return RSN_OK;
-    int rc = suite_lists_check(c, n_lists, lists, res); if (rc) return rc;
+    rc = suite_lists_check(c, n_lists, lists, res); if (rc) return rc;
     rc = dev_prologue(c, stream, &s); if (rc) return rc;
-    return suite_batch_flow(c, s, n, nullptr, nullptr, mem, n_lists, lists, res, list_rc, h_orig, h_dec, best);
+    return suite_batch_flow(c, s, n, LbMembers{nullptr, nullptr, mem}, n_lists, lists, slotset::SUITE_BATCH_CALL, true, SuiteOut{res, list_rc, h_orig, h_dec, nullptr, best});
 }
 
 static int layers_roundtrip(const uint8_t *in, size_t n, const int *layers, size_t n_layers, rsn_roundtrip_result *res, uint8_t **compressed, size_t *compressed_n) {

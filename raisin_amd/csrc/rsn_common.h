@@ -89,7 +89,7 @@ enum class Slot : int {
     LB_B = 50,          // ... the two arenas taking turns [layers_batch]
     LB_XA = 51,         // layered batch calls: the slots of the members that outgrew their first slot in LB_A and were run again alone ... [layers_batch]
     LB_XB = 52,         // ... and of those that outgrew theirs in LB_B [layers_batch]
-    LB_VERIFY = 53,     // batch round trip (rsn_api.hip: roundtrip_batch_flow): a run's verify table, behind it the stats block -- the members'
+    LB_VERIFY = 53,     // batch round trip (rsn_api.hip: suite_batch_flow over one list): a run's verify table, behind it the stats block -- the members'
                         //   first-difference words and histograms (roundtrip_batch_layout.h) [roundtrip_batch]
     GD_RUNE_PLANS = 54, // Huffman decompress batch on device buffers (huff_rune_dec.hip): the rune candidates' table entries and their summaries -- written by
                         //   k_huff_dev_rune_plan, read by the host once; the call's gate gives it back with the plan table [huff_dev]

@@ -2,7 +2,8 @@
 // code: no HIP include, so a CPU test (tests/suite_layout_test.cpp) checks it -- the prefix tree of the layer lists holds every distinct
 // prefix once, a node's output is kept exactly where more than one user reads it, the decompress-only stats block lies apart at 16-byte
 // offsets, and a member's run need counts the kept bytes and is at least the need of every list run alone.  rsn_api.hip's
-// suite_batch_flow is the user, roundtrip_batch.hip's second instance of k_members_verify writes the decompress-only stats.
+// suite_batch_flow is the user -- for the batch round trip too, whose one list is a chain with nothing kept --, roundtrip_batch.hip's
+// second instance of k_members_verify writes the decompress-only stats.
 //
 // The lists of a call form a prefix tree over their layers in compress order: node 0 is the empty prefix (the member as it came), every
 // other node one more compress layer behind its parent.  A run compresses every node once, walking the tree depth first; a list's
@@ -66,17 +67,19 @@ inline SuiteTree suite_tree(const int *const *layers, const size_t *n_layers, si
 
 // The kept bytes of a member of `len` bytes: a slot (its slack included) for every kept node, of the compress bounds applied in turn
 // from the root -- an upper bound of what the node's step is given, as bound(layer, n) grows with n.  caps: per node, the bound chain's
-// figure (the root: len), for the caller that carves the slot.
+// figure (the root: len), for the caller that carves the slot -- and the vector a caller with many members hands in again, so that a
+// member costs no allocation.
 template <class Bound>
 size_t suite_keep_bytes(const SuiteTree &t, size_t len, Bound bound, std::vector<size_t> *caps = nullptr) {
-    std::vector<size_t> cap(t.nodes.size());
+    std::vector<size_t> own;
+    std::vector<size_t> &cap = caps ? *caps : own;
+    cap.resize(t.nodes.size());
     cap[SUITE_ROOT] = len;
     size_t bytes = 0;
     for (size_t v = 1; v < t.nodes.size(); v++) {
         cap[v] = bound(t.nodes[v].layer, cap[t.nodes[v].parent]);
         if (t.nodes[v].kept) bytes += lb_slot_bytes(cap[v]);
     }
-    if (caps) *caps = cap;
     return bytes;
 }
 
@@ -94,6 +97,8 @@ constexpr RbLayout suite_dec_layout(size_t tiles, size_t m, bool hists) {
     return RbLayout{0, words, h, h + (hists ? m * SUITE_HIST_BYTES : 0)};
 }
 static_assert(SUITE_HIST_BYTES * 2 == RB_HIST_BYTES, "the decompress-only row is the second half of the round trip's");
+// the verify slot of either instance of k_members_verify: both sides counted (a run's first list), or the decompressed side alone
+constexpr RbLayout verify_layout(bool both, size_t tiles, size_t m, bool hists) { return both ? rb_layout(tiles, m, hists) : suite_dec_layout(tiles, m, hists); }
 
 // best[i] of a call: the list with the smallest compressed size among those that succeeded, the lowest index among equals; UINT32_MAX
 // when none did.  ok(l): list l succeeded; size(l): the member's compressed size under list l

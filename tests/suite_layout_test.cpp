@@ -2,7 +2,8 @@
 // promises: the prefix tree holds every distinct prefix of the lists exactly once, a list ends at the node of its own layers, a node is
 // kept exactly where more than one user reads it -- the tree branches, or a list ends while another goes on --, the kept bytes are the
 // kept nodes' slots of the bounds applied in turn, a member's run need is monotone in its length and at least the need of every list run
-// alone, the decompress-only stats block lies apart at 16-byte offsets, and best is the first smallest among the lists that succeeded.
+// alone -- and exactly the round trip's need when there is one list, whose tree keeps nothing --, the decompress-only stats block lies
+// apart at 16-byte offsets, and best is the first smallest among the lists that succeeded.
 // Prints the number of checks it made.
 #include <algorithm>
 #include <cstdio>
@@ -127,6 +128,26 @@ static void test_need(const Lists &lists, size_t len, bool staged, bool hists) {
     for (size_t more : {(size_t)1, (size_t)15, (size_t)16, RB_TILE, 3 * RB_TILE + 1}) CHECK(need_of(len + more) >= need);
 }
 
+// What lets the batch round trip run as the suite of its one list: the tree of one list is a chain with no kept node, so no kept bytes,
+// and the member's run need is the round trip's own, whatever its two slot figures are
+static void test_one_list(size_t layers) {
+    std::vector<int> list(layers);
+    for (size_t k = 0; k < layers; k++) list[k] = 1 + (int)(k % 2);
+    const SuiteTree t = tree_of({list});
+    CHECK(t.nodes.size() == layers + 1 && t.end[0] == layers);
+    for (size_t v = 0; v < t.nodes.size(); v++) {
+        CHECK(!t.nodes[v].kept && suite_users(t.nodes[v]) == 1);
+        CHECK(t.nodes[v].depth == v && t.nodes[v].kids.size() == (v < layers ? 1u : 0u) && t.nodes[v].ends.size() == (v == layers ? 1u : 0u));
+    }
+    for (size_t len : {(size_t)0, (size_t)1, (size_t)65535, (size_t)65536, (size_t)65537, (size_t)UINT32_MAX})
+        for (bool hists : {false, true})
+            for (bool staged : {false, true}) {
+                const size_t keep = suite_keep_bytes(t, len, bound), enc = enc_slot(list, len), dec = dec_slot(list, len);
+                CHECK(keep == 0);
+                CHECK(suite_member_need(staged ? len : 0, enc, dec, keep, len, len, hists) == rb_member_need(staged ? len : 0, enc, dec, len, len, hists));
+            }
+}
+
 static void test_dec_layout(size_t tiles, size_t m, bool hists) {
     const RbLayout l = suite_dec_layout(tiles, m, hists), full = rb_layout(tiles, m, hists);
     const size_t table = tiles * sizeof(RbEntry), words = m * RB_WORD, counts = hists ? m * SUITE_HIST_BYTES : 0;
@@ -183,6 +204,7 @@ int main(int argc, char **argv) {
         test_tree(lists);
         for (size_t len : {(size_t)0, (size_t)1, (size_t)25, (size_t)1024, RB_TILE, RB_TILE + 1}) { test_need(lists, len, true, true); test_need(lists, len, false, false); }
     }
+    for (size_t layers : {(size_t)0, (size_t)1, (size_t)3, (size_t)8}) test_one_list(layers);
     // best: the first smallest among the lists that succeeded
     {
         const uint64_t sizes[4] = {7, 5, 5, 9};

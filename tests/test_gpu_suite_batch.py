@@ -279,6 +279,38 @@ def test_forced_run_cuts_give_the_same_answers(mods, monkeypatch):
         assert prof.get("members_verify_dec") == runs * 5, prof           # a run: the first list through the first instance, the five other distinct lists through the second
 
 
+# ---------------------------------------------------------------- the one-list call runs the suite's flow: calls in turn, one process
+SEQ_LISTS = [[LZ], [LZ, HU], [HU]]                                           # the lzss node is kept: LB_KEEP is live in the suite calls
+SEQ_MEMBERS = [_text(20 + k, 500 + 100 * k) for k in range(5)] + [_text(1, 1), _text(9, TILE + 1)]   # the last: two verify tiles, rows that add
+
+
+@pytest.mark.parametrize("budget", [None, "1"], ids=["one_run", "a_run_a_member"])
+def test_a_one_list_call_between_two_suite_calls(mods, oracle, monkeypatch, budget):
+    """suite, one list, suite again: every answer is the oracle's, whatever the call before left in the slots the two share (the arenas,
+    the verify slot) and in the one only the suite has; the one-list call launches the first instance of the verify kernel once a run
+    and never the second"""
+    from test_gpu_roundtrip_batch import _dev as one_dev, _host as one_host, _wants
+    _lib, _ = mods
+    assert [len(d) for d in SEQ_MEMBERS] == [500, 600, 700, 800, 900, 1, TILE + 1]
+    want = [_wants(oracle, SEQ_MEMBERS, names) for names in SEQ_LISTS]
+    if budget:
+        monkeypatch.setenv("RSN_LAYERS_BATCH_BUDGET", budget)
+    runs = len(SEQ_MEMBERS) if budget else 1
+    for form, one in (("host", one_host), ("dev", one_dev)):
+        first = _suite(_lib, form, SEQ_MEMBERS, SEQ_LISTS)
+        (rc, got, hists, msg), prof, _ = _prof(_lib, lambda: one(_lib, SEQ_MEMBERS, SEQ_LISTS[1]))
+        second = _suite(_lib, form, SEQ_MEMBERS, SEQ_LISTS)
+        for s_rc, rows, h_o, h_d, codes, best, s_msg in (first, second):
+            assert s_rc == OK and codes == [OK] * 3, (form, s_msg)
+            for l, (fields, counts) in enumerate(want):
+                assert rows[l] == fields, (form, l, [i for i in range(len(fields)) if rows[l][i] != fields[i]])
+                assert [a + b for a, b in zip(h_o, h_d[l])] == counts, (form, l)
+            assert best == [_argmin(rows, range(3), i) for i in range(len(SEQ_MEMBERS))], form
+        assert first == second, form
+        assert rc == OK and got == want[1][0] and hists == want[1][1], (form, msg)
+        assert prof.get("members_verify") == runs and "members_verify_dec" not in prof, (form, prof)
+
+
 # ---------------------------------------------------------------- the engine
 def test_benchmark_files_suite_is_the_loop_of_benchmark_files(mods, tmp_path):
     from raisin_amd import engine
