@@ -117,6 +117,8 @@ RSN_API int rsn_huffman_compress_batch(size_t n_chunks, const uint8_t *const *in
  * Null arrays, or a null ins[i] with a non-zero length, return RSN_ERR_ARG; without a device every call returns RSN_ERR_DEVICE.
  * Small members run many to a launch, a workgroup each, on the calling thread: LZSS compress inputs of at most
  * 1 KiB (window <= 0xFFFF) and, through a kernel of their own, of at most 64 KiB (window 1 to 4096) that escape to at most 68 KiB;
+ * LZSS compress inputs above 64 KiB and up to 256 KiB (window 1 to 4096), cut into tiles over the whole device, when the call holds
+ * at least 16 such members;
  * LZSS streams of at most 2 KiB that expand to at most 8 KiB and, likewise, of at most 68 KiB that expand to at most 68 KiB
  * (the mid-size classes only when the call holds at least 64 such members); Huffman streams of a byte alphabet
  * (2 to 128 symbols, codes of at most 32 bits) with at most 16 KiB of payload and 32 KiB of output and, through a kernel of

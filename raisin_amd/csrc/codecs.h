@@ -53,8 +53,9 @@ int lzss_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **o
 int lzss_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t out_cap, size_t *out_n);
 
 // ---- many members in one launch (the batch calls, rsn_api.hip).  A CLASS of members is what one grouped kernel takes, a
-// workgroup per member: the small and the mid-size members of each layer and direction, eight rows -- and two whose
-// members take a workgroup per TILE, the big members of Huffman compress (huff_big.hip) and of Huffman decompress (huff_big_dec.hip).
+// workgroup per member: the small and the mid-size members of each layer and direction, eight rows -- and three whose
+// members take a workgroup per TILE, the big members of Huffman compress (huff_big.hip), of Huffman decompress (huff_big_dec.hip) and of
+// LZSS compress (lzss_tile.hip).
 // The contract of every row:
 //   takes(in, n, window)   whether the member is of the class, asked in the order of batch_classes' rows (a later row need not exclude
 //                          what an earlier one takes).  Fewer than group_min members of a class in a call are not grouped: a workgroup each
@@ -106,6 +107,32 @@ constexpr uint32_t LZSS_MID_IN_MAX = 65536;
 constexpr uint32_t LZSS_MID_E_MAX = 69632;
 constexpr size_t LZSS_MID_GROUP_MIN = 64;
 const BatchClass &lzss_small_class(bool compress), &lzss_mid_class(bool compress);
+// lzss_tile.hip: the compress direction above the mid class.  A member of more than LZSS_MID_IN_MAX and at most LZSS_TILE_IN_MAX bytes
+// (window 1 to 4096) does not fit a workgroup, and a workgroup a member would leave the device idle, so its escaped stream is cut into
+// tiles of LZSS_TILE_POS positions and a group is FOUR launches with nothing on the host between them: a workgroup per member escapes it
+// into scratch, a workgroup per tile searches it (the window in front and the look-ahead behind in LDS; the chain walk is the mid
+// kernel's, lzss_match.h), a workgroup per member walks the greedy chain and sizes the items, and a workgroup per tile stores its bytes
+// (lzss_tile_layout.h: the tiles, the scratch, which tile stores which byte).  It hands back what escapes to more than LZSS_TILE_E_MAX
+// bytes or to more than one and a half times the member, and -- as the mid class -- runs and short periods (the step cap).  Both forms
+// run on device staging, in groups of up to LZSS_TILE_GROUP_BYTES.  The streams decode through the single call inside a decompress
+// batch when they are longer than LZSS_MID_E_MAX.  LZSS_TILE_IN_MAX, LZSS_TILE_GROUP_MIN: DESIGN 4.7 and profiles/lzss_tile_batch.txt.
+// Mirrored as raisin_amd.lz.TILE_IN_MAX / TILE_E_MAX / TILE_POS / TILE_GROUP_MIN / TILE_GROUP_BYTES.
+// A PROBE build widens the class to measure where it should end (scripts/probes/lzss_tile_batch.py; Makefile: EXTRA=-DRSN_LZSS_TILE_IN_MAX=...
+// -DRSN_LZSS_TILE_GROUP_MIN=...); every other build has the two measured values.
+#ifndef RSN_LZSS_TILE_IN_MAX
+#define RSN_LZSS_TILE_IN_MAX 262144
+#endif
+#ifndef RSN_LZSS_TILE_GROUP_MIN
+#define RSN_LZSS_TILE_GROUP_MIN 16
+#endif
+constexpr uint32_t LZSS_TILE_IN_MAX = RSN_LZSS_TILE_IN_MAX;
+constexpr uint32_t LZSS_TILE_E_MAX = LZSS_TILE_IN_MAX + LZSS_TILE_IN_MAX / 16;
+constexpr uint32_t LZSS_TILE_POS = 2048;
+constexpr size_t LZSS_TILE_GROUP_MIN = RSN_LZSS_TILE_GROUP_MIN;
+constexpr size_t LZSS_TILE_GROUP_BYTES = 67108864;
+static_assert(LZSS_TILE_E_MAX < (1u << 31) && 4096 < (1u << 15) && LZSS_TILE_IN_MAX > LZSS_MID_IN_MAX && LZSS_TILE_GROUP_MIN >= 2,
+              "a key is L << 16 | distance with its top bit free: L <= distance <= the window, 13 bits each, exact whatever E is; positions are words");
+const BatchClass &lzss_tile_class();
 // huff_small.hip: inputs of 2 B to 16 KiB (two members at least: a group's one serial tree against the host's); streams short enough for
 // k_huff_batch_dec's workgroup.
 // huff_mid.hip: a workgroup of 1024 threads keeps the whole member and the whole image of its stream in LDS, one workgroup to a CU.  The
@@ -214,7 +241,7 @@ struct BatchRows {
 inline BatchRows batch_classes(BatchLayer layer, bool compress) {
     static const BatchClass *const huff_enc[] = {&huff_small_class(true), &huff_mid_class(true), &huff_big_class()}, *const huff_dec[] = {&huff_mid_class(false), &huff_big_dec_class(), &huff_small_class(false)};
     static const BehindClass *const huff_enc_behind[] = {&huff_rune_class()}, *const huff_dec_behind[] = {&huff_rune_dec_class()};
-    static const BatchClass *const lzss_enc[] = {&lzss_small_class(true), &lzss_mid_class(true)}, *const lzss_dec[] = {&lzss_small_class(false), &lzss_mid_class(false)};
+    static const BatchClass *const lzss_enc[] = {&lzss_small_class(true), &lzss_mid_class(true), &lzss_tile_class()}, *const lzss_dec[] = {&lzss_small_class(false), &lzss_mid_class(false)};
     if (layer == BatchLayer::HUFFMAN) return compress ? BatchRows(huff_enc, huff_enc_behind) : BatchRows(huff_dec, huff_dec_behind);
     return compress ? BatchRows(lzss_enc) : BatchRows(lzss_dec);
 }

@@ -29,7 +29,7 @@ constexpr uint32_t MID_TILE = 2048;               // positions of a tile (two pe
 constexpr uint32_t MID_W_MAX = 4096;              // the largest window (what the pipelined host call takes, too)
 constexpr uint32_t MID_RING = 8192;               // links kept: the window, rounded down to a sub-tile, and the tile in hand
 constexpr uint32_t MID_HEADS = 4096;              // chains (a 12-bit hash of the two-byte key)
-constexpr uint32_t MID_NONE = 0xFFFFFFFFu;
+constexpr uint32_t MID_NONE = CHAIN_NONE;
 constexpr uint32_t MID_STEP_CAP = 4096;           // eight-byte extension steps a thread spends on a tile (its two positions) before the member is handed back -- lzss_small.hip's SL_STEP_CAP, for the same two positions
 constexpr uint32_t E_PAD = 64;                    // zeros behind the escaped stream (an eight-byte load may start at its last byte)
 constexpr uint32_t E_MAX = LZSS_MID_E_MAX;
@@ -67,29 +67,10 @@ __device__ __forceinline__ void mid_done(uint32_t *flag, uint32_t value) {
     if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// exclusive scan of one value per thread over the workgroup; *total: the sum
-__device__ __forceinline__ uint32_t mid_scan(uint32_t v, uint32_t *s_wave /*[MT / 64 + 1]*/, uint32_t *total) {
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += o; }
-    __syncthreads();                                                      // (the previous scan's readers are done with s_wave)
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        uint32_t w = threadIdx.x < MT / 64 ? s_wave[threadIdx.x] : 0u, wi = w;
-#pragma unroll
-        for (int d = 1; d < MT / 64; d <<= 1) { const uint32_t o = __shfl_up(wi, d, 64); if (lane >= (uint32_t)d) wi += o; }
-        if (threadIdx.x < MT / 64) s_wave[threadIdx.x] = wi - w;
-        if (threadIdx.x == MT / 64 - 1) s_wave[MT / 64] = wi;
-    }
-    __syncthreads();
-    *total = s_wave[MT / 64];
-    return s_wave[wave] + inc - v;
-}
-
-__device__ __forceinline__ uint32_t mid_digits(uint32_t v) { return v < 10 ? 1u : v < 100 ? 2u : v < 1000 ? 3u : v < 10000 ? 4u : 5u; }
-__device__ __forceinline__ uint32_t mid_hash(uint32_t b0, uint32_t b1) { return ((b0 | (b1 << 8)) * 0x9E3779B1u) >> 20; }
+// the scan, the hash and the chain walk are lzss_match.h's, shared with the tiled class (lzss_tile.hip)
+__device__ __forceinline__ uint32_t mid_scan(uint32_t v, uint32_t *s_wave /*[MT / 64 + 1]*/, uint32_t *total) { return chain_scan<MT>(v, s_wave, total); }
+__device__ __forceinline__ uint32_t mid_digits(uint32_t v) { return chain_digits(v); }
+__device__ __forceinline__ uint32_t mid_hash(uint32_t b0, uint32_t b1) { return chain_hash(b0, b1); }
 
 // ---------------------------------------------------------------- compress
 __global__ __launch_bounds__(MT) void k_lzss_mid_enc(const SmallMember *__restrict__ tab, uint8_t *__restrict__ base, uint32_t W) {
@@ -130,7 +111,6 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_enc(const SmallMember *__restri
     __syncthreads();                                                              // (the raw member is no longer read: its LDS is the tile's now)
     for (uint32_t i = tid; i < MID_HEADS; i += MT) s_head[i] = MID_NONE;
     __syncthreads();
-    const uint32_t *fw = reinterpret_cast<const uint32_t *>(s_fc);
     uint32_t entry = 0;                                                           // the greedy chain's first position in the tile, from the tile's start
     uint32_t flushed = 0, carry = 0;                                              // bytes of the result in hout; bytes waiting at the front of s_out (< 16)
     for (uint32_t t0 = 0; t0 < E; t0 += MID_TILE) {
@@ -144,36 +124,7 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_enc(const SmallMember *__restri
             __syncthreads();
             // ---- the longest L >= 2 with fc[i, i + L) inside the window (L <= distance, L <= E - i), at its largest distance
             if (live && i < E) {
-                const uint32_t cap = E - i;
-                uint32_t best = 0;
-                if (cap >= 2 && i >= 2) {
-                    const uint32_t jlo = i - min(i, W), floor_ = jlo & ~(uint32_t)(MT - 1);   // (a chain entry below floor_: everything behind it is older still)
-                    const unsigned long long pat = lds_load8(fw, i);
-                    uint32_t j = s_head[h];
-                    for (uint32_t visits = 0; j < E && j >= floor_ && visits < MID_RING && steps <= MID_STEP_CAP; visits++) {
-                        const uint32_t nxt = s_ring[j & (MID_RING - 1)];
-                        if (j + 2 <= i && j >= jlo) {
-                            const uint32_t d = i - j, lim = min(d, cap), bl = best >> 16;
-                            // (a candidate counts if it is at least as long as the best so far: the byte at that length decides for most)
-                            if (lim >= bl && (bl == 0 || s_fc[j + bl - 1] == s_fc[i + bl - 1])) {
-                                unsigned long long x = lds_load8(fw, j) ^ pat;
-                                uint32_t L = x ? (uint32_t)__builtin_ctzll(x) >> 3 : 8u;
-                                if (!x) {
-                                    uint32_t off = 8;
-                                    while (off < lim) {
-                                        x = lds_load8(fw, j + off) ^ lds_load8(fw, i + off);
-                                        steps++;
-                                        if (x) { off += (uint32_t)__builtin_ctzll(x) >> 3; break; }
-                                        off += 8;
-                                    }
-                                    L = off;
-                                }
-                                best = max(best, (min(L, lim) << 16) | d);        // longest, then farthest back (bytes.Index finds the leftmost, lzss.go:419)
-                            }
-                        }
-                        j = nxt;
-                    }
-                }
+                const uint32_t best = chain_best<MID_RING, MT, MID_STEP_CAP>(s_fc, s_ring, s_head[h], i, E, W, 0u, steps);
                 s_key[sub + tid] = best;
             }
             __syncthreads();                                                      // (the next sub-tile's links are written behind this)

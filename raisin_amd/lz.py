@@ -10,6 +10,16 @@ DefaultWindowSize = 4096  # lzss.go:35
 MID_IN_MAX = 65536
 MID_E_MAX = 69632
 MID_GROUP_MIN = 64
+# The members of a compress batch above MID_IN_MAX (csrc/codecs.h: LZSS_TILE_IN_MAX, LZSS_TILE_E_MAX, LZSS_TILE_POS, LZSS_TILE_GROUP_MIN,
+# LZSS_TILE_GROUP_BYTES; tests/test_lzss_tile_host.py holds the two together): inputs up to TILE_IN_MAX bytes (window 1 to 4096) are cut
+# into tiles of TILE_POS escaped positions, a workgroup each, and a group of them is four launches, when a call holds at least
+# TILE_GROUP_MIN of them.  A member that escapes to more than TILE_E_MAX bytes, or to more than one and a half times its length, and
+# a member of runs or short periods take the single call's path.  Compress only: their streams decompress through the single call's path.
+TILE_IN_MAX = 262144
+TILE_E_MAX = 278528
+TILE_POS = 2048
+TILE_GROUP_MIN = 16
+TILE_GROUP_BYTES = 67108864
 
 
 def CompressAsync(fileContents, useProgressBar=False, maxSearchBufferLength=DefaultWindowSize):
@@ -32,7 +42,9 @@ def Decompress(fileContents, useProgressBar=False):
 def CompressAsyncBatch(files, maxSearchBufferLength=DefaultWindowSize):
     """CompressAsync(f, False, maxSearchBufferLength) for every buffer of the list in one call (rsn_lzss_compress_batch): inputs of at most
     1 KiB many to a launch, a workgroup each; inputs up to MID_IN_MAX bytes likewise, through a kernel of their own, when the window is 1 to
-    4096 and the list holds at least MID_GROUP_MIN of them; the rest through the single call's path.  Each result equals CompressAsync(f)."""
+    4096 and the list holds at least MID_GROUP_MIN of them; inputs above that and up to TILE_IN_MAX bytes tiled over the whole device, four
+    launches a group, when the list holds at least TILE_GROUP_MIN of them; the rest through the single call's path.  Each result equals
+    CompressAsync(f)."""
     return _lib.call_batch(_lib.lib().rsn_lzss_compress_batch, files, int(maxSearchBufferLength))
 
 
