@@ -663,12 +663,30 @@ __global__ __launch_bounds__(FDB) void k_dec_flat(FlatArgs a) {
     __shared__ uint32_t s_data[WORDS + WORDS / 32 + 2];
     __shared__ uint32_t s_lut[(1 << L) << RL];
     const int tid = threadIdx.x;
-    {   // the table is read through the kernel-argument segment pointer: indexing the by-value copy would spill it to scratch
+    // A block takes ONE chunk (the launch gives every chunk a block; the loop only serves a launch with fewer blocks), so the table is
+    // staged per chunk and has to be cheap: a group of 32 lanes takes the (1 << L) / 8 entries that lie side by side in the
+    // kernel-argument segment with dword loads, issued behind the chunk's own loads so that both are in flight together.
+    // (Through the segment pointer: indexing the by-value copy would spill it to scratch.)
+    bool staged = false;
+    auto stage = [&]() {
         const uint8_t *lut = (const uint8_t *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(FlatArgs, lut);
-        for (int i = tid; i < ((1 << L) << RL); i += FDB) s_lut[i] = lut[i >> RL];
-    }
+        constexpr int PER_G = (1 << L) / (FDB >> RL);           // entries per group of 32 lanes: 16 at L = 7
+        if constexpr (PER_G >= 4) {
+            static_assert(offsetof(FlatArgs, lut) % 4 == 0, "dword loads of the table");
+            const int g = tid >> RL;
+            const uint32_t *l4 = reinterpret_cast<const uint32_t *>(lut) + g * (PER_G / 4);
+            uint32_t x[PER_G / 4];
+#pragma unroll
+            for (int j = 0; j < PER_G / 4; j++) x[j] = l4[j];
+#pragma unroll
+            for (int j = 0; j < PER_G; j++) s_lut[((g * PER_G + j) << RL) | (tid & ((1 << RL) - 1))] = (x[j >> 2] >> (8 * (j & 3))) & 0xFF;
+        } else {
+            for (int i = tid; i < ((1 << L) << RL); i += FDB) s_lut[i] = lut[i >> RL];
+        }
+        staged = true;
+    };
     const uint32_t n_chunks = (uint32_t)((a.n_sym + FLAT_SYMS - 1) / FLAT_SYMS);
-    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {   // persistent: the table is staged once
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
     const unsigned long long sym0 = (unsigned long long)chunk * FLAT_SYMS;
     const unsigned long long bit0 = a.p0 + sym0 * L;            // FLAT_SYMS*L is a multiple of 32: bit0 % 32 == p0 % 32
     const size_t w0 = (size_t)(bit0 >> 5);
@@ -679,9 +697,11 @@ __global__ __launch_bounds__(FDB) void k_dec_flat(FlatArgs a) {
         uint32_t v[PER];
 #pragma unroll
         for (int k = 0; k < PER; k++) { const int i = tid + k * FDB; if (i < WORDS) v[k] = ld4<(RSN_NT_MASK & 8) != 0>(src + i); }
+        if (!staged) stage();
 #pragma unroll
         for (int k = 0; k < PER; k++) { const int i = tid + k * FDB; if (i < WORDS) s_data[swz(i)] = __builtin_bswap32(v[k]); }
     } else {
+        if (!staged) stage();
         for (int i = tid; i < WORDS; i += FDB) {
             const size_t off = (w0 + i) * 4;
             uint32_t v = 0;
@@ -943,10 +963,10 @@ int huff_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_
             }
             fa.p0 = p0_all + q0 * L; fa.n_sym = q1 - q0; fa.out = d_out + q0;
             const size_t chunks = ceil_div((size_t)(q1 - q0), FLAT_SYMS);
-            dim3 grid;
+            if (chunks > 0x7FFFFFFFu) return c.fail(RSN_ERR_LIMIT, "huffman: %zu chunks of flat codes in one launch", chunks);
+            const dim3 grid((uint32_t)chunks);                    // a block a chunk: not persistent
             switch (L) {
 #define RSN_FLAT_CASE(LL) case LL:                                                                                \
-                rc = persistent_grid(c, reinterpret_cast<const void *>(k_dec_flat<LL>), FDB, chunks, &grid); if (rc) return rc; \
                 RSN_LAUNCH("huff_dec_flat", k_dec_flat<LL>, grid, dim3(FDB), 0, s, fa); break;
                 RSN_FLAT_CASE(1) RSN_FLAT_CASE(2) RSN_FLAT_CASE(3) RSN_FLAT_CASE(4) RSN_FLAT_CASE(5) RSN_FLAT_CASE(6)
                 RSN_FLAT_CASE(7)   // ASCII alphabets hold at most 2^7 symbols

@@ -791,14 +791,26 @@ __global__ __launch_bounds__(HB) void k_emit_flat(FlatEmitArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     // (through the kernel-argument segment pointer: indexing the by-value copy would spill it to scratch)
     const uint8_t *tab = a.codes ? a.codes : (const uint8_t *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(FlatEmitArgs, inl);
-    for (int i = tid; i < 128 * 32; i += HB) s_code[i] = tab[i >> 5];
-    __syncthreads();
     const uint32_t rep = tid & 31;
+    // A block takes ONE chunk (the launch gives every chunk a block; the loop only serves a launch with fewer blocks), so the table is
+    // staged per chunk and has to be cheap: a group of 32 lanes takes 16 symbols' codes with four dword loads, issued behind the
+    // chunk's own loads so that both are in flight together.
+    static_assert(HB == 256 && offsetof(FlatEmitArgs, inl) % 4 == 0, "eight groups of 32 lanes, dword loads of the table");
+    bool staged = false;
+    auto stage = [&]() {
+        const int g = tid >> 5;
+        const uint32_t *t4 = reinterpret_cast<const uint32_t *>(tab) + g * 4;
+        uint32_t x[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) x[j] = t4[j];
+#pragma unroll
+        for (int j = 0; j < 16; j++) s_code[((g * 16 + j) << 5) | rep] = (x[j >> 2] >> (8 * (j & 3))) & 0xFF;
+        staged = true;
+    };
     const uint32_t n_chunks = (uint32_t)((a.n + FE_SYMS - 1) / FE_SYMS);
-    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {   // persistent: the code table is staged once
+    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
     const size_t s0 = (size_t)chunk * FE_SYMS + (size_t)tid * FE_SPL;
-    auto pack32 = [&](size_t first, uint32_t *v) {                // 32 symbols at `first` -> L big-endian words
-        uint32_t w[8];
+    auto load32 = [&](size_t first, uint32_t *w) {                // the 32 symbols at `first`, zeros past the end of the input
         if (first + 32 <= a.n) {
             const uint4 *src = reinterpret_cast<const uint4 *>(a.in + first);
             const uint4 x = ld16<(RSN_NT_MASK & 2) != 0>(src), y = ld16<(RSN_NT_MASK & 2) != 0>(src + 1);
@@ -811,6 +823,8 @@ __global__ __launch_bounds__(HB) void k_emit_flat(FlatEmitArgs a) {
 #pragma unroll 1
             for (int k = 0; k < 32 && first + k < a.n; k++) w[k >> 2] |= (uint32_t)a.in[first + k] << (8 * (k & 3));
         }
+    };
+    auto pack32 = [&](size_t first, const uint32_t *w, uint32_t *v) {   // those 32 symbols -> L big-endian words
 #pragma unroll
         for (int j = 0; j < L; j++) v[j] = 0;
 #pragma unroll
@@ -822,8 +836,10 @@ __global__ __launch_bounds__(HB) void k_emit_flat(FlatEmitArgs a) {
             else { v[wi] |= code >> (sh + L - 32); v[wi + 1 < L ? wi + 1 : wi] |= code << (64 - sh - L); }
         }
     };
-    uint32_t v[L];
-    if (s0 < a.n) pack32(s0, v);
+    uint32_t v[L], w[8];
+    if (s0 < a.n) load32(s0, w);
+    if (!staged) { stage(); __syncthreads(); }
+    if (s0 < a.n) pack32(s0, w, v);
     else {
 #pragma unroll
         for (int j = 0; j < L; j++) v[j] = 0;
@@ -835,7 +851,7 @@ __global__ __launch_bounds__(HB) void k_emit_flat(FlatEmitArgs a) {
     __syncthreads();
     if (lane == 0) {
         if (wv > 0) prev = s_last[wv - 1];
-        else if (chunk > 0) { uint32_t pv[L]; pack32(s0 - 32, pv); prev = pv[L - 1]; }
+        else if (chunk > 0) { uint32_t pw[8], pv[L]; load32(s0 - 32, pw); pack32(s0 - 32, pw, pv); prev = pv[L - 1]; }
         else prev = 0;                                            // in front of the stream: header bytes, merged below
     }
     const uint32_t o0 = (uint32_t)(a.base_bits & 31);
@@ -1020,10 +1036,10 @@ int huff_slice_emit(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, const 
             RSN_HIP(copy_async(p, hcodes, 128 + H, hipMemcpyHostToDevice, s));
             fa.codes = (const uint8_t *)p;
         }
-        dim3 grid;
+        if (ceil_div(n, FE_SYMS) > 0x7FFFFFFFu) return c.fail(RSN_ERR_LIMIT, "huffman: %zu chunks of flat codes in one launch", ceil_div(n, FE_SYMS));
+        const dim3 grid((uint32_t)ceil_div(n, FE_SYMS));              // a block a chunk: not persistent
         switch (L) {
 #define RSN_FE(LL) case LL:                                                                                      \
-            rc = persistent_grid(c, reinterpret_cast<const void *>(k_emit_flat<LL>), HB, ceil_div(n, FE_SYMS), &grid); if (rc) return rc; \
             RSN_LAUNCH("huff_emit", k_emit_flat<LL>, grid, dim3(HB), 0, s, fa); break;
             RSN_FE(1) RSN_FE(2) RSN_FE(3) RSN_FE(4) RSN_FE(5) RSN_FE(6) RSN_FE(7)
 #undef RSN_FE
