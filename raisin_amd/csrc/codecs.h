@@ -10,6 +10,7 @@
 #include "rsn_common.h"
 #include "huff_parse_small.h"   // (behind the HIP runtime: its functions are __host__ __device__ under hipcc)
 #include "huff_rune_select.h"
+#include "lzss_tile_layout.h"    // (behind the HIP runtime as well: lzt_e_cap, for the closure of the tiled LZSS decoder over the tiled encoder)
 
 namespace rsn {
 
@@ -53,9 +54,9 @@ int lzss_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **o
 int lzss_decode_dev(Ctx &c, hipStream_t s, const uint8_t *d_in, size_t n, uint8_t *d_out, size_t out_cap, size_t *out_n);
 
 // ---- many members in one launch (the batch calls, rsn_api.hip).  A CLASS of members is what one grouped kernel takes, a
-// workgroup per member: the small and the mid-size members of each layer and direction, eight rows -- and three whose
-// members take a workgroup per TILE, the big members of Huffman compress (huff_big.hip), of Huffman decompress (huff_big_dec.hip) and of
-// LZSS compress (lzss_tile.hip).
+// workgroup per member: the small and the mid-size members of each layer and direction, eight rows -- and four whose
+// members take a workgroup per TILE, the big members of Huffman compress (huff_big.hip), of Huffman decompress (huff_big_dec.hip), of
+// LZSS compress (lzss_tile.hip) and, behind the rows, of LZSS decompress (lzss_tile_dec.hip).
 // The contract of every row:
 //   takes(in, n, window)   whether the member is of the class, asked in the order of batch_classes' rows (a later row need not exclude
 //                          what an earlier one takes).  Fewer than group_min members of a class in a call are not grouped: a workgroup each
@@ -114,8 +115,8 @@ const BatchClass &lzss_small_class(bool compress), &lzss_mid_class(bool compress
 // kernel's, lzss_match.h), a workgroup per member walks the greedy chain and sizes the items, and a workgroup per tile stores its bytes
 // (lzss_tile_layout.h: the tiles, the scratch, which tile stores which byte).  It hands back what escapes to more than LZSS_TILE_E_MAX
 // bytes or to more than one and a half times the member, and -- as the mid class -- runs and short periods (the step cap).  Both forms
-// run on device staging, in groups of up to LZSS_TILE_GROUP_BYTES.  The streams decode through the single call inside a decompress
-// batch when they are longer than LZSS_MID_E_MAX.  LZSS_TILE_IN_MAX, LZSS_TILE_GROUP_MIN: DESIGN 4.7 and profiles/lzss_tile_batch.txt.
+// run on device staging, in groups of up to LZSS_TILE_GROUP_BYTES.  The streams decode through the tiled decoder below inside a
+// decompress batch.  LZSS_TILE_IN_MAX, LZSS_TILE_GROUP_MIN: DESIGN 4.7 and profiles/lzss_tile_batch.txt.
 // Mirrored as raisin_amd.lz.TILE_IN_MAX / TILE_E_MAX / TILE_POS / TILE_GROUP_MIN / TILE_GROUP_BYTES.
 // A PROBE build widens the class to measure where it should end (scripts/probes/lzss_tile_batch.py; Makefile: EXTRA=-DRSN_LZSS_TILE_IN_MAX=...
 // -DRSN_LZSS_TILE_GROUP_MIN=...); every other build has the two measured values.
@@ -228,6 +229,32 @@ constexpr bool huff_rune_dec_takes_the_encoder() {
 }
 static_assert(huff_rune_dec_takes_the_encoder(), "header, payload and length of every stream the rune encoder writes are ones the rune decoder takes; valid UTF-8 decodes to the member's own n bytes");
 const BehindClass &huff_rune_dec_class();
+// lzss_tile_dec.hip: the way back for what no workgroup holds.  A stream of at most LZSS_TILE_DEC_IN_MAX bytes that expands to at most
+// LZSS_TILE_DEC_OUT_MAX escaped bytes is cut into tiles of LZSS_TILE_POS bytes -- of the stream for the parse, of the escaped output for
+// the copies -- and a group is FOUR launches with nothing on the host between them: a workgroup per stream tile parses its tokens, a
+// workgroup per member scans the tiles' outputs and gives the verdict, a workgroup per output tile settles the copy chains inside the
+// tile and leaves a descriptor for every byte that copies an earlier tile, and a workgroup per member finishes its tiles in order, unescapes
+// them and stores the result (lzss_tile_dec_layout.h: the tiles, the scratch, which tile stores which byte).  What a stream expands to is
+// not known before it is parsed -- a stream the mid class takes by its length is handed back when it expands beyond LZSS_MID_E_MAX, the
+// ordinary case for what lzss_tile.hip writes -- so the class stands behind the rows of LZSS decompress, pool REST: its candidates are the
+// members left for the single call whose stream is longer than the small decoder's 2 KiB and at most LZSS_TILE_DEC_IN_MAX, and it runs
+// when there are at least LZSS_TILE_DEC_GROUP_MIN of them.  It hands back malformed streams, a pointer that starts before the data, an
+// empty result and more than LZSS_TILE_DEC_OUT_MAX escaped bytes; they stay in `rest`, and the single call words the errors.  Both forms
+// run on device staging, in groups of up to LZSS_TILE_GROUP_BYTES.  LZSS_TILE_DEC_GROUP_MIN: DESIGN 4.7.
+// Mirrored as raisin_amd.lz.TILE_DEC_IN_MAX / TILE_DEC_OUT_MAX / TILE_DEC_GROUP_MIN.
+constexpr uint32_t LZSS_TILE_DEC_IN_MAX = LZSS_TILE_E_MAX;
+constexpr uint32_t LZSS_TILE_DEC_OUT_MAX = LZSS_TILE_E_MAX;
+// A PROBE build lowers the minimum to measure where it should be (scripts/probes/lzss_tile_dec_batch.py; Makefile: EXTRA=-DRSN_LZSS_TILE_DEC_GROUP_MIN=2).
+#ifndef RSN_LZSS_TILE_DEC_GROUP_MIN
+#define RSN_LZSS_TILE_DEC_GROUP_MIN 8
+#endif
+constexpr size_t LZSS_TILE_DEC_GROUP_MIN = RSN_LZSS_TILE_DEC_GROUP_MIN;
+static_assert(LZSS_TILE_DEC_GROUP_MIN >= 2, "a group of one is the single call's");
+// (lzss_tile_layout.h: a taken member's stream has at most lzt_e_cap(n) <= LZSS_TILE_E_MAX bytes -- an item is never longer than what it
+// stands for -- and its escaped length is at most the same)
+static_assert(LZSS_TILE_DEC_IN_MAX >= lzt_e_cap(LZSS_TILE_IN_MAX) && LZSS_TILE_DEC_OUT_MAX >= LZSS_TILE_E_MAX && lzt_e_cap(LZSS_TILE_IN_MAX) <= LZSS_TILE_E_MAX,
+              "the decoder takes every stream the encoder writes");
+const BehindClass &lzss_tile_dec_class();
 // the rows of a layer and direction in order of precedence, and the classes behind them: LZSS asks its small class first, Huffman
 // decompress its mid class (a short stream may promise more output than k_huff_batch_dec's workgroup holds) and then its tiled class, for
 // the same reason: the small class takes by the stream's length alone, and 8 KiB of payload can promise more than HUFF_MID_OUT_MAX bytes
@@ -240,10 +267,10 @@ struct BatchRows {
 };
 inline BatchRows batch_classes(BatchLayer layer, bool compress) {
     static const BatchClass *const huff_enc[] = {&huff_small_class(true), &huff_mid_class(true), &huff_big_class()}, *const huff_dec[] = {&huff_mid_class(false), &huff_big_dec_class(), &huff_small_class(false)};
-    static const BehindClass *const huff_enc_behind[] = {&huff_rune_class()}, *const huff_dec_behind[] = {&huff_rune_dec_class()};
+    static const BehindClass *const huff_enc_behind[] = {&huff_rune_class()}, *const huff_dec_behind[] = {&huff_rune_dec_class()}, *const lzss_dec_behind[] = {&lzss_tile_dec_class()};
     static const BatchClass *const lzss_enc[] = {&lzss_small_class(true), &lzss_mid_class(true), &lzss_tile_class()}, *const lzss_dec[] = {&lzss_small_class(false), &lzss_mid_class(false)};
     if (layer == BatchLayer::HUFFMAN) return compress ? BatchRows(huff_enc, huff_enc_behind) : BatchRows(huff_dec, huff_dec_behind);
-    return compress ? BatchRows(lzss_enc) : BatchRows(lzss_dec);
+    return compress ? BatchRows(lzss_enc) : BatchRows(lzss_dec, lzss_dec_behind);
 }
 // until none of flags[0 .. n) is GROUP_PENDING (group_layout.h; the single small calls): polled for 5 ms, then the stream is waited for the
 // ordinary way -- a kernel that has not answered by then is RSN_ERR_DEVICE

@@ -19,6 +19,7 @@
 // What the kernels do not take is handed back (GROUP_BACK) and goes through the single call, which also words the errors.
 // No loop waits for another workgroup, and every loop is bounded: the chain walk by the ring's size, the extensions by MID_STEP_CAP.
 #include "group_run.h"
+#include "lzss_dec_body.h"
 #include "lzss_match.h"
 
 namespace rsn {
@@ -225,14 +226,11 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_dec(const SmallMember *__restri
         for (int k = 0; k < 2; k++) {
             const uint32_t p = k0 + k;
             if (p >= n || s_in[p] != '<') continue;
-            uint32_t q = p + 1; unsigned long long v = 0; int nd = 0;
-            while (q < n && nd < 10 && s_in[q] >= '0' && s_in[q] <= '9') { v = v * 10 + (s_in[q] - '0'); q++; nd++; }
-            bool ok = nd && q < n && s_in[q] == ',' && v <= (unsigned long long)E_MAX;
-            tptr[k] = (uint32_t)v; q++; v = 0; nd = 0;
-            while (ok && q < n && nd < 10 && s_in[q] >= '0' && s_in[q] <= '9') { v = v * 10 + (s_in[q] - '0'); q++; nd++; }
-            ok = ok && nd && q < n && s_in[q] == '>' && v <= (unsigned long long)E_MAX && (uint32_t)v <= tptr[k];   // (len <= ptr: lzss.go:350's slice stays inside the data)
+            uint32_t ptr, len, text;                                              // (scalars, not the arrays' elements: the kernel keeps its 55 VGPRs so)
+            const bool ok = lzd_token(s_in, 0u, p, n, E_MAX, ptr, len, text);
+            tptr[k] = ptr;
             if (!ok) { bad = true; continue; }
-            tlen[k] = (uint32_t)v; ttl[k] = q + 1 - p;
+            tlen[k] = len; ttl[k] = text;
             for (uint32_t t = 0; t < ttl[k]; t++) s_cov[p - c0 + t] = 1;
         }
         if (__syncthreads_or(bad)) { mid_done(flag, GROUP_BACK); return; }       // (malformed: the single call words the error)
@@ -256,18 +254,7 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_dec(const SmallMember *__restri
             }
             __syncthreads();
             // every byte's source: src <- src[src] while it lies in the tile and is not a literal (a copied byte lies before the byte that copies it)
-            int cur = 0;
-            for (int round = 0; round < 13; round++) {
-                bool moved = false;
-                const uint32_t *sa = s_src + cur * MID_TILE;
-                uint32_t *sb = s_src + (cur ^ 1) * MID_TILE;
-                for (uint32_t r = tid; r < s1 - s0; r += MT) {
-                    const uint32_t x = sa[r], y = x >= s0 ? sa[x - s0] : x;
-                    sb[r] = y; moved = moved || x != y;
-                }
-                cur ^= 1;
-                if (!__syncthreads_or(moved)) break;
-            }
+            const int cur = lzd_jump<MT, MID_TILE>(s_src, s0, s1 - s0, 13);
             for (uint32_t r = tid; r < s1 - s0; r += MT) { const uint32_t x = s_src[cur * MID_TILE + r]; if (x != s0 + r) s_val[s0 + r] = s_val[x]; }   // (x: a literal of the tile, or final in an earlier one)
             __syncthreads();
         }
@@ -277,35 +264,11 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_dec(const SmallMember *__restri
     // ---- DecodeOpeningSymbols (lzss.go:391-406): a byte is escaped iff the run of 5C right in front of it has odd length, counted from the
     //      last byte that is not 5C (as lzss_small.hip).  A run of ceil(E / MT) bytes per thread.
     const uint32_t per = (E + MT - 1) / MT, q0 = min(E, tid * per), q1 = min(E, q0 + per);
-    uint32_t mine = 0;                                                            // 1 + the last of this thread's positions whose byte is not 5C; 0: none
-    for (uint32_t q = q0; q < q1; q++) if (s_val[q] != 0x5C) mine = q + 1;
-    uint32_t inc = mine, before = 0;                                              // before: the same for every position in front of q0
-    {
-        const uint32_t lane = tid & 63, wave = tid >> 6;
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc = max(inc, o); }
-        __syncthreads();
-        if (lane == 63) s_wave[wave] = inc;
-        __syncthreads();
-        for (uint32_t w = 0; w < wave; w++) before = max(before, s_wave[w]);
-        uint32_t prev = __shfl_up(inc, 1, 64);
-        if (lane == 0) prev = 0;
-        before = max(before, prev);
-    }
-    uint32_t cnt = 0;
-    for (uint32_t q = q0, bq = before; q < q1; q++) {
-        const uint32_t b = s_val[q];
-        cnt += (((q - bq) & 1u) || b != 0x5C) ? 1u : 0u;
-        if (b != 0x5C) bq = q + 1;
-    }
+    const uint32_t before = lzd_plain_before<MT>(lzd_last_plain(s_val, 0u, q0, q1), s_wave);   // 1 + the last position in front of q0 whose byte is not 5C; 0: none
     uint32_t total;
-    uint32_t o = mid_scan(cnt, s_wave, &total);
+    const uint32_t o = mid_scan(lzd_unesc_count(s_val, 0u, q0, q1, before), s_wave, &total);
     uint8_t *s_res = s_in;                                                         // (the stream is parsed: its LDS takes the result)
-    for (uint32_t q = q0, bq = before; q < q1; q++) {
-        const uint32_t b = s_val[q];
-        const bool esc = (q - bq) & 1u;
-        if (esc || b != 0x5C) s_res[o++] = (uint8_t)(esc ? b : (b == 0xFF ? 0x3Cu : b));
-        if (b != 0x5C) bq = q + 1;
-    }
+    lzd_unesc_write(s_val, 0u, q0, q1, before, s_res, o);
     __syncthreads();
     for (uint32_t u = tid; u * 16 < total; u += MT) reinterpret_cast<uint4 *>(hout)[u] = reinterpret_cast<const uint4 *>(s_res)[u];
     mid_done(flag, total);

@@ -47,7 +47,7 @@ LZT_FN uint32_t lzt_tile_len(uint32_t e, uint32_t t) {                       // 
     return e - lo < LZT_TILE ? e - lo : LZT_TILE;
 }
 // the escaped bytes a member of n bytes is taken with (n beyond the class counts as the class's largest: the kernels size by this)
-LZT_FN uint32_t lzt_e_cap(uint32_t n) {
+LZT_FN constexpr uint32_t lzt_e_cap(uint32_t n) {
     const uint32_t m = n < LZT_IN_MAX ? n : LZT_IN_MAX, half = m + m / 2;
     return half < LZT_E_MAX ? half : LZT_E_MAX;
 }

@@ -14,12 +14,19 @@ MID_GROUP_MIN = 64
 # LZSS_TILE_GROUP_BYTES; tests/test_lzss_tile_host.py holds the two together): inputs up to TILE_IN_MAX bytes (window 1 to 4096) are cut
 # into tiles of TILE_POS escaped positions, a workgroup each, and a group of them is four launches, when a call holds at least
 # TILE_GROUP_MIN of them.  A member that escapes to more than TILE_E_MAX bytes, or to more than one and a half times its length, and
-# a member of runs or short periods take the single call's path.  Compress only: their streams decompress through the single call's path.
+# a member of runs or short periods take the single call's path.
 TILE_IN_MAX = 262144
 TILE_E_MAX = 278528
 TILE_POS = 2048
 TILE_GROUP_MIN = 16
 TILE_GROUP_BYTES = 67108864
+# The way back (csrc/codecs.h: LZSS_TILE_DEC_IN_MAX, LZSS_TILE_DEC_OUT_MAX, LZSS_TILE_DEC_GROUP_MIN; tests/test_lzss_tile_dec_host.py holds
+# the two together): the streams of a decompress batch that the small and the mid class leave -- longer than 2 KiB and at most
+# TILE_DEC_IN_MAX bytes, expanding to at most TILE_DEC_OUT_MAX escaped bytes -- are cut into tiles of TILE_POS bytes and a group of them is
+# four launches, when a call holds at least TILE_DEC_GROUP_MIN of them.  Every stream the tiled encoder writes is one of them.
+TILE_DEC_IN_MAX = TILE_E_MAX
+TILE_DEC_OUT_MAX = TILE_E_MAX
+TILE_DEC_GROUP_MIN = 8
 
 
 def CompressAsync(fileContents, useProgressBar=False, maxSearchBufferLength=DefaultWindowSize):
@@ -50,8 +57,8 @@ def CompressAsyncBatch(files, maxSearchBufferLength=DefaultWindowSize):
 
 def DecompressBatch(streams):
     """Decompress(s) for every stream of the list in one call (rsn_lzss_decompress_batch); each result equals Decompress(s): streams of
-    at most 2 KiB many to a launch, streams up to MID_E_MAX bytes likewise (at least MID_GROUP_MIN of them), the rest through the single
-    call's path.  A failing
+    at most 2 KiB many to a launch, streams up to MID_E_MAX bytes likewise (at least MID_GROUP_MIN of them), what those leave up to
+    TILE_DEC_IN_MAX bytes tiled over workgroups (at least TILE_DEC_GROUP_MIN of them), the rest through the single call's path.  A failing
     stream raises for the whole list (the message names the lowest failing index: "member <i>: ...")."""
     return _lib.call_batch(_lib.lib().rsn_lzss_decompress_batch, streams)
 
