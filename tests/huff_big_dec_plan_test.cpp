@@ -304,7 +304,7 @@ int main(int argc, char **argv) {
         if (!taken) { printf("the Fibonacci member is handed back\n"); return 1; }
     }
     bool periodic_taken = false;
-    if (argc > 1) {   // periodic data: the model has no phases to lose, so it is taken here; the kernel may hand it back
+    if (argc > 1) {   // periodic data: the model has no phases to lose, so it is taken here; the lanes' model (tests/lane_maps.py) takes it too
         FILE *f = fopen(argv[1], "rb");
         if (!f) { printf("cannot open %s\n", argv[1]); return 1; }
         std::vector<uint8_t> one(1 << 16);

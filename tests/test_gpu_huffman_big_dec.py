@@ -6,11 +6,14 @@ AND with the library's single huffman.Decompress; what the chain hands back (a t
 streams) and what the wide plan refuses must come out of the single call with the same bytes or the same error.  Every list is padded to
 BIG_DEC_GROUP_MIN members of the class with text of MID_OUT_MAX + 1 + 100 i bytes.
 
-Which members are taken is not read off the library: _tiles() restates the chain from the ENCODER's side -- the code lengths of the
-member's bytes, summed -- into every tile's first output byte and symbol count, and _taken() applies the emit image's cap to them."""
+Which members are taken is not read off the library: _taken() is the verdict of the CPU model of the lane maps (tests/lane_maps.py, held
+on a CPU by tests/test_lane_maps_host.py) -- phases, rounds, the emit image's cap -- on the member's stream, with its reason; _tiles()
+restates the chain from the ENCODER's side -- the code lengths of the member's bytes, summed -- into every tile's first output byte and
+symbol count, and the model's records must be those."""
 import numpy as np
 import pytest
 
+import lane_limit_cases as C
 import long_codes
 from test_gpu_batch_dev import E_CAP, OK, SINGLE_WORDS, Pack, _batch, _fenced_call, _out_bytes, _prof, _ru16
 from test_gpu_huffman_batch_dev import _run_slots
@@ -85,8 +88,15 @@ def _tiles(oracle, huffman, d):
 
 
 def _taken(oracle, huffman, d):
-    """a member of the class whose every tile fits the emit image"""
-    return _in_class(huffman, d) and all(n + 16 <= huffman.BIG_DEC_OUT_CAP for _, n in _tiles(oracle, huffman, d))
+    """a member of the class that the model of the lane maps takes: no tile lost to phases or rounds, every tile within the emit image"""
+    if not _in_class(huffman, d):
+        return False
+    ln, taken, why = C.lanes(d, "tiled")
+    if taken:
+        assert [(base, n) for _, base, n in ln.records] == _tiles(oracle, huffman, d)
+    else:
+        assert why != "image" or any(n + 16 > huffman.BIG_DEC_OUT_CAP for _, n in _tiles(oracle, huffman, d))
+    return taken
 
 
 def _pad(huffman, members, seed=700):
@@ -149,11 +159,9 @@ def test_cutoffs(mods, oracle):
     dec, prof, _ = _prof(_lib, lambda: huffman.DecompressBatch([s] * K))
     assert _new_once(prof) and "huff_batch_mid_dec" not in prof, prof         # one byte more: this class's
     assert dec == [two] * K == [_single_call(huffman, s)] * K == [_dec(oracle, s)] * K
-    taken = _taken(oracle, huffman, two)                                      # (a bit a symbol: two tiles, the first of 61440 symbols)
-    print("two symbols at 65537 bytes: %s" % ("taken" if taken else "handed back by the chain"))
-    assert not taken or prof == HOST_PROF, prof                               # (a handed-back member's single call is a batch worker's: not in this thread's profile)
-    prof, _ = _dev(mods, oracle, [two] * K)
-    assert _new_once(prof) and (prof == DEV_PROF) == taken, prof              # ... in the device form it is this thread's
+    assert not _taken(oracle, huffman, two) and C.verdict(two, "tiled") == (False, "image")   # (a bit a symbol: two tiles, the first of 61440 symbols)
+    prof, _ = _dev(mods, oracle, [two] * K)                                   # (a handed-back member's single call is a batch worker's in the host form: not in this
+    assert _new_once(prof) and _general(prof), prof                           #  thread's profile; in the device form it is this thread's)
     # the payload limit: 128 symbols of 7 bits each
     flat = _with_counts(61, {b: 2048 for b in range(128)}, True)
     s = _enc(oracle, flat)
@@ -204,6 +212,7 @@ def test_tile_edges(mods, oracle):
     print("taken by the shape: %r" % verdicts)
     assert verdicts["fibonacci"]                                              # 24-bit codes that straddle tiles: taken, not handed back
     assert verdicts == {"two symbols": False, "fibonacci": True, "skewed": False}   # the cap: fewer than 1.875 bits a symbol over a tile is the single call's
+    assert C.verdict(two, "tiled") == C.verdict(skew, "tiled") == (False, "image")
     assert _host(mods, oracle, texts + [fib]) == HOST_PROF
     assert _dev(mods, oracle, texts + [fib])[0] == DEV_PROF
     members = [two, texts[0], fib, skew] + texts[1:]
@@ -326,8 +335,10 @@ def test_the_decoder_takes_every_stream_the_big_encoder_writes(mods, oracle, sam
     plain = [_text(10 + i, n) for i, n in enumerate([65537, 5 * 16384 - 1, 5 * 16384 + 1, 100000, 200000, 262144])] + [flat]   # tests 1 and 2: text and alphabets
     periodic = (samiam * (150000 // len(samiam) + 1))[:150000]
     two = np.random.default_rng(80).choice(np.frombuffer(b"ab", dtype=np.uint8), 262144).tobytes()
-    may_go_back = [periodic, two, _skewed(81, 150000)]
-    members = plain + may_go_back + [long_codes.fib_data(25, seed=4)]
+    named = [("periodic", periodic), ("two symbols", two), ("skewed", _skewed(81, 150000))]   # the model's verdicts on them: the lanes take the periodic one
+    assert [C.verdict(d, "tiled") for _, d in named] == [(True, None), (False, "image"), (False, "image")]
+    assert all(C.EITHER_WANT[k] == ("tiled",) + C.verdict(d, "tiled") for k, (_, d) in zip(("big: periodic samiam", "big: two symbols, 262144", "big: skewed"), named))
+    members = plain + [d for _, d in named] + [long_codes.fib_data(25, seed=4)]
     assert all(huffman.MID_IN_MAX < len(d) <= huffman.BIG_IN_MAX for d in members)
     streams, prof, _ = _prof(_lib, lambda: huffman.CompressBatch(members))
     assert prof.get("huff_batch_big_emit") == 1 and streams == [_enc(oracle, d) for d in members]    # every one a taken member of the big encoder's class
@@ -336,18 +347,11 @@ def test_the_decoder_takes_every_stream_the_big_encoder_writes(mods, oracle, sam
         assert _payload(s) <= huffman.BIG_PAY_MAX
         _, prof, _ = _prof(_lib, lambda: huffman.DecompressBatch([s] * huffman.BIG_DEC_GROUP_MIN))
         assert _new_once(prof), (len(s), prof)
-    # the cap on hand-backs: of the text and alphabet members none, only the periodic, the two-symbol and the skewed one may be
-    assert _host(mods, oracle, plain + [members[-1]]) == HOST_PROF
-    assert _dev(mods, oracle, plain + [members[-1]])[0] == DEV_PROF
-    back = []
-    for d, name in zip(may_go_back, ("periodic", "two symbols", "skewed")):   # (the device form: a single call's launches are this thread's there)
+    # the hand-backs are the model's: of the text and alphabet members none, the periodic one neither; the two-symbol and the skewed one
+    assert _host(mods, oracle, plain + [periodic, members[-1]]) == HOST_PROF
+    assert _dev(mods, oracle, plain + [periodic, members[-1]])[0] == DEV_PROF
+    for name, d in named:                                                     # (the device form: a single call's launches are this thread's there)
         lst = _pad(huffman, [d])
         _host(mods, oracle, lst)
-        caps = [_ru16(len(x)) + 16 for x in lst]
-        got, prof, _ = _run_slots(_lib, DEC, [_enc(oracle, x) for x in lst], caps, loose=range(len(lst)))
-        assert got == lst and _new_once(prof), (name, prof)
-        if prof != DEV_PROF:
-            assert _general(prof), (name, prof)
-            back.append(name)
-    print("handed back to the single call: %r" % back)
-    assert set(back) <= {"periodic", "two symbols", "skewed"}
+        prof, _ = _dev(mods, oracle, lst)                                     # (exact capacities wherever the model says taken)
+        assert _new_once(prof) and (prof == DEV_PROF) == _taken(oracle, huffman, d) == (not _general(prof)), (name, prof)

@@ -8,8 +8,10 @@ One place where a list is narrower than "every stream": text of 17 KiB codes to 
 small decoder's (huff_batch_dec), whatever wrote it -- no byte alphabet reaches 16 KiB of payload from 17 KiB.  So the one-launch and the
 closure tests assert `{"huff_batch_mid_dec": groups}` for the streams of the mid class (payload above 16 KiB, or output above 32 KiB) and
 the two grouped kernels, no single call, for the whole list.  The closure test's list holds the code shapes in shuffled order only: built in
-sorted order they are runs of one codeword, periodic data that the decoder may hand back for more than four phases (their bytes are
-pinned both ways all the same)."""
+sorted order they are runs of one codeword, periodic data that the decoder hands back where a lane is offered a fifth start.  Which of
+those and of test_periodic_data's members it hands back is the verdict of the CPU model of the lane maps (tests/lane_maps.py;
+tests/lane_limit_cases.py: EITHER_WANT pins it), and _held_to_the_model holds the kernels to it: of the sorted shapes the seventh, of
+the periodic members none."""
 import ctypes
 import os
 import random
@@ -141,6 +143,31 @@ def _check_decompress(mods, oracle, streams, members):
     return prof
 
 
+def _held_to_the_model(mods, oracle, names, members, pads):
+    """The device form over the members' streams, out_cap exactly the result size wherever the model of the lane maps takes the member
+    and the single call's figure where it hands it back: the single call's decoder runs if and only if the model hands a member back,
+    and not at all on the members it takes, run on their own.  names: the members' keys in lane_limit_cases.EITHER_WANT."""
+    import lane_limit_cases as C
+    from test_gpu_batch_dev import _ru16
+    from test_gpu_huffman_batch_dev import DEC, _run_slots
+    _lib, huffman = mods
+    _lib.check(_lib.lib().rsn_device_set(0))
+    verdicts = [(C.class_of(d),) + C.verdict(d, C.class_of(d)) for d in members]
+    assert verdicts == [C.EITHER_WANT[k] for k in names], verdicts
+    assert all(C.verdict(d, C.class_of(d)) == (True, None) for d in pads)
+    taken = [v[1] for v in verdicts] + [True] * len(pads)
+    lists = [(list(members) + list(pads), taken)]
+    if not all(taken):
+        lists.append(([d for d, t in zip(list(members) + list(pads), taken) if t], [True] * sum(taken)))
+    for lst, took in lists:
+        caps = [len(d) if t else _ru16(len(d)) + 16 for d, t in zip(lst, took)]
+        got, prof, _ = _run_slots(_lib, DEC, [oracle.huffman_compress(d) for d in lst], caps, loose=[i for i, t in enumerate(took) if not t])
+        assert got == lst
+        general = {k for k in prof if k.startswith("huff_dec_") or k == "huff_small_dec"}
+        assert prof.get("huff_batch_mid_dec") == 1 and bool(general) == (not all(took)), prof
+    return taken
+
+
 # ---------------------------------------------------------------- 1: sizes
 def test_sizes(mods, oracle, K):
     _, huffman = mods
@@ -192,12 +219,16 @@ def test_code_shapes(mods, oracle, K):
     got, prof = _check_compress(mods, oracle, members, record=False)
     assert prof == {"huff_batch_mid_enc": 1}, prof
     # the closure test takes the shuffled ones: in sorted order a member is a few runs of one codeword thousands of symbols long, periodic
-    # data with as many phases as the codeword has bits, which the decoder may hand back like test_periodic_data's
+    # data with as many phases as the codeword has bits, of which the decoder hands back the seventh (below: the model's verdicts)
     PRODUCED.extend((d, g) for d, g in list(zip(members, got))[0:2 * len(_shape_tables()):2])
     # (the shapes of 19 to 24 KB are the small decoder's; K text streams of the mid class beside them, so that the class is grouped)
     more = [_text(100 + i, 40000) for i in range(K)]
     prof = _check_decompress(mods, oracle, got + [oracle.huffman_compress(d) for d in more], members + more)
     assert prof.get("huff_batch_mid_dec", 0) >= 1, prof
+    # the sorted ones against the model of the lane maps: the runs of one codeword are taken, the seventh table's 90 runs are not
+    n = len(_shape_tables())
+    taken = _held_to_the_model(mods, oracle, ["mid: sorted shape %d" % k for k in range(n)], members[1:2 * n:2], more)
+    assert taken[:n] == [True] * (n - 1) + [False]
 
 
 # ---------------------------------------------------------------- 3: hand-backs
@@ -254,8 +285,10 @@ def test_periodic_data(mods, oracle, samiam, K):
     block = _alpha(50, 4096, b"abcdefghijklmnopqrstuvwxyz ,.\n")
     per = [(samiam * (n // len(samiam) + 1))[:n] for n in (20000, 40000, 65536)] + [b"ab" * 16000, block * 12, block * 16]
     members = _pad(per, K)
-    got, _ = _check_compress(mods, oracle, members, record=False)             # (more than four phases: the decoder may hand these back)
+    got, _ = _check_compress(mods, oracle, members, record=False)
     _check_decompress(mods, oracle, got, members)
+    # two or three phases, never a fifth start: the model of the lane maps takes all six, and so do the kernels
+    assert all(_held_to_the_model(mods, oracle, ["mid: periodic %d" % i for i in range(len(per))], per, [_text(960 + i, 40000) for i in range(4)]))
 
 
 # ---------------------------------------------------------------- 6: the decoder's cutoffs from the host plan

@@ -176,7 +176,8 @@ def _shuffled(text, seed):
 def _counter(v):
     """256 distinct runes in ASCENDING order, as the encoder's test has them: equal counts give them consecutive codes, so the payload is a
     counter, in which a wrong start stays a consistent parse -- at variants 0 and 10 one lane sees five starts, and more than four phases
-    is the lane maps' hand-back (huff_small_body.h).  The class may take it or leave it; the bytes are the oracle's either way."""
+    is the lane maps' hand-back (huff_small_body.h).  Which variants the class takes is the verdict of the CPU model of the lane maps
+    (tests/lane_maps.py; tests/lane_limit_cases.py: EITHER_WANT pins it): all but 0 and 10."""
     return (_runes(0x100 + 7 * v, 256) + _runes(0x100 + 7 * v, 40 + v)).encode()
 
 
@@ -194,9 +195,12 @@ def _not_taken(oracle, v):
 
 def _all_shapes(oracle, copies):
     """every shape in `copies` copies with variation: (streams, expected bytes, taken, names)"""
-    streams, taken, names = [], [], []                                 # taken: True, False, or None -- either (_counter)
+    import lane_limit_cases as C
+    streams, taken, names = [], [], []
     for v in range(copies):
-        streams.append(_enc(oracle, _counter(v))); taken.append(None); names.append("256 distinct runes, ascending")
+        took, why = C.verdict(_counter(v), "rune")                         # the model's: handed back for "phases" at variants 0 and 10
+        assert ("rune", took, why) == C.EITHER_WANT["rune counter %d" % v] and why in (None, "phases")
+        streams.append(_enc(oracle, _counter(v))); taken.append(took); names.append("256 distinct runes, ascending")
         for name, variant in _taken_shapes():
             streams.append(_enc(oracle, variant(v))); taken.append(True); names.append(name)
         for name, s in _hand(v):

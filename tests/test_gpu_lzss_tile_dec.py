@@ -301,14 +301,18 @@ def test_layered(mods, oracle):
     _lib, lz = mods
     from raisin_amd import layers
     names = ["lzss", "huffman"]
-    # the tiled HUFFMAN decoder hands a stream back for reasons of its own (phases and rounds of a tile) -- of these texts the
-    # LZSS stream of seed 6111 -- so the members are fifteen texts whose streams it takes, repeated to the class's minimum, and the check
-    # in front says so: what the decode profile then shows of a single call would be the LZSS step's
+    # the tiled HUFFMAN decoder hands back the LZSS stream of seed 6111: the model of its lane maps (tests/lane_maps.py) loses tile 10 to a
+    # fifth start at lane 1 and takes the other fifteen -- so the members are those fifteen texts, repeated to the class's minimum, and
+    # the check in front says that the kernels take them too: what the decode profile then shows of a single call would be the LZSS step's
+    import lane_limit_cases as C
     from raisin_amd import huffman
-    distinct = [_text(6100 + i, 200000) for i in range(16) if i != 11]
+    verdicts = {seed: C.verdict(C.layered_member(seed), "tiled") for seed in C.LAYERED_SEEDS}
+    assert verdicts == {seed: (False, "phases") if seed == C.LAYERED_BACK else (True, None) for seed in range(6100, 6116)} and C.LAYERED_BACK == 6111
+    distinct = [_text(seed, 200000) for seed in C.LAYERED_SEEDS if verdicts[seed][0]]
     members = (distinct * 3)[:max(16, lz.TILE_DEC_GROUP_MIN)]
-    assert len(members) >= lz.TILE_DEC_GROUP_MIN
+    assert len(distinct) == 15 and len(members) >= lz.TILE_DEC_GROUP_MIN
     streams = layers.CompressBatch(members, names)
+    assert streams[:15] == [C.enc(C.layered_member(seed)) for seed in C.LAYERED_SEEDS if verdicts[seed][0]]    # the streams the model judged
     _, prof, _ = _prof(_lib, lambda: huffman.DecompressBatch(streams))
     assert not [k for k in prof if not k.startswith(GROUPED)], sorted(prof)
     got, prof, _ = _prof(_lib, lambda: layers.DecompressBatch(streams, names))
