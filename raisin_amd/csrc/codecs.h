@@ -10,6 +10,7 @@
 #include "rsn_common.h"
 #include "huff_parse_small.h"   // (behind the HIP runtime: its functions are __host__ __device__ under hipcc)
 #include "huff_rune_select.h"
+#include "huff_rune_mid_select.h"
 #include "lzss_tile_layout.h"    // (behind the HIP runtime as well: lzt_e_cap, for the closure of the tiled LZSS decoder over the tiled encoder)
 
 namespace rsn {
@@ -185,8 +186,10 @@ const BatchClass &huff_big_dec_class();
 // rows have run, every flow (rsn_api.hip: batch_front, layer_batch_run) OFFERS it one POOL of members -- RUNES: those the rows handed back
 // as GROUP_BACK_RUNES; REST: everything left for the single call so far -- in one loop over what batch_classes lists behind the rows, and
 // it runs grouped those it chooses when there are at least its minimum of them (huff_rune_select.h: the rules).
-//   offer       host form: the members it runs leave the pool, take() receives their results; whatever else a RUNES pool held, and what
-//               its kernel hands back, joins `rest` (a REST pool is `rest`), which the flow sorts afterwards.  *failed as run() sets it.
+//   offer       host form: the members it runs leave the pool, take() receives their results; what its kernel hands back joins `rest`
+//               (a REST pool is `rest`), which the flow sorts afterwards.  *failed as run() sets it.  The classes of a RUNES pool are
+//               offered it in the order listed: one that is not the last leaves in the pool, sorted, whatever it does not run, for the
+//               next; the LAST sends whatever else the pool held to `rest` and leaves the pool empty.
 //   offer_dev   device form, the same choice: the members it runs leave the pool for `idx` (which comes empty), answers[k] is idx[k]'s, and the flow settles
 //               them as a row's.  A failure is about behind_failed: the first member chosen, or, when none was yet, the lowest offered.
 struct BehindClass {
@@ -207,6 +210,19 @@ inline size_t behind_failed(const std::vector<size_t> &idx, const std::vector<si
 // Mirrored as raisin_amd.huffman.RUNE_SYMS_MAX / RUNE_GROUP_MIN.
 constexpr uint32_t HUFF_RUNE_SYMS_MAX = 256;
 const BehindClass &huff_rune_class();
+// huff_rune_mid.hip: the same for the members of more than HUFF_RUNE_IN_MAX and at most HUFF_RUNE_MID_IN_MAX bytes that k_huff_mid_enc hands
+// back as GROUP_BACK_RUNES -- a workgroup of 1024 threads each in k_huff_mid_rune_enc, the member and the image of its stream in LDS, one
+// workgroup to a CU as in the mid class: the 16 KiB kernel's runes, table, plan and header, counts up to 65535 (PLAN_RUNE_MID_COUNT_MAX),
+// the bits a round of 16 KiB at a time.  It hands back what the 16 KiB class hands back: more than HUFF_RUNE_SYMS_MAX distinct runes, a
+// single one.  Behind the rows of Huffman compress, pool RUNES, listed AHEAD of huff_rune_class (which would send these members to `rest`,
+// where nothing says any more that they were rune members): a call that holds at least HUFF_RUNE_MID_GROUP_MIN such members runs them and
+// leaves the others in the pool; fewer stay in the pool, all of them, and take the single call as every one did before.  Rune members above
+// HUFF_RUNE_MID_IN_MAX (huff_big.hip's hand-backs) are not this class's.  Its streams decode through the single call inside a decompress
+// batch: the rune decoder below ends at HUFF_RUNE_OUT_MAX.  HUFF_RUNE_MID_GROUP_MIN = 16 is the floor, for the reason HUFF_RUNE_GROUP_MIN
+// gives, not a crossover: at 16 members the grouped route is 6.8 to 11 times as fast as the single calls it replaces, at 20, 32 and 64 KiB,
+// from host and from device buffers, and no count tried (16 to 256) loses at any size, so HUFF_RUNE_MID_IN_MAX stays at the mid class's
+// 65536 (profiles/huff_rune_mid_batch.txt).  Mirrored as raisin_amd.huffman.RUNE_MID_IN_MAX / RUNE_MID_GROUP_MIN.
+const BehindClass &huff_rune_mid_class();
 // huff_rune_dec.hip: the way back.  A stream whose header names a rune >= 0x80 -- what the byte decoders' plans refuse -- a workgroup each
 // in k_huff_batch_rune_dec: the workgroup parses the header itself (huff_parse_rune.h: at most HUFF_RUNE_SYMS_MAX distinct runes, the
 // Go-exact tree in one wavefront), decodes the payload with the byte decoders' lane maps (huff_small_body.h: lane_dec_body) to a leaf rank
@@ -267,7 +283,7 @@ struct BatchRows {
 };
 inline BatchRows batch_classes(BatchLayer layer, bool compress) {
     static const BatchClass *const huff_enc[] = {&huff_small_class(true), &huff_mid_class(true), &huff_big_class()}, *const huff_dec[] = {&huff_mid_class(false), &huff_big_dec_class(), &huff_small_class(false)};
-    static const BehindClass *const huff_enc_behind[] = {&huff_rune_class()}, *const huff_dec_behind[] = {&huff_rune_dec_class()}, *const lzss_dec_behind[] = {&lzss_tile_dec_class()};
+    static const BehindClass *const huff_enc_behind[] = {&huff_rune_mid_class(), &huff_rune_class()}, *const huff_dec_behind[] = {&huff_rune_dec_class()}, *const lzss_dec_behind[] = {&lzss_tile_dec_class()};
     static const BatchClass *const lzss_enc[] = {&lzss_small_class(true), &lzss_mid_class(true), &lzss_tile_class()}, *const lzss_dec[] = {&lzss_small_class(false), &lzss_mid_class(false)};
     if (layer == BatchLayer::HUFFMAN) return compress ? BatchRows(huff_enc, huff_enc_behind) : BatchRows(huff_dec, huff_dec_behind);
     return compress ? BatchRows(lzss_enc) : BatchRows(lzss_dec, lzss_dec_behind);

@@ -22,7 +22,13 @@ constexpr uint32_t PLAN_RUNE_IDB = 9;                                  // bits o
 constexpr uint32_t PLAN_RUNE_NODES_MAX = 2 * PLAN_RUNE_SYMS_MAX - 1;
 constexpr uint32_t PLAN_RUNE_COUNT_MAX = 16384;                        // a count, and the sum of all, at most
 static_assert(PLAN_RUNE_NODES_MAX <= (1u << PLAN_RUNE_IDB) && ((unsigned long long)PLAN_RUNE_COUNT_MAX << PLAN_RUNE_IDB) < (1ull << 32), "a heap item is one word");
-constexpr uint32_t PLAN_RUNE_SLOTS = 2 * PLAN_RUNE_SYMS_MAX;           // of the encoder's and the decoder's open-addressing table: twice the symbols it may hold
+// ... but for the mid-size class (huff_rune_mid.hip), whose members' counts sum to at most PLAN_RUNE_MID_COUNT_MAX: ranks, tree and codes
+// only ask that a sum of counts and a node id pack into one word, and a count of 65536 still has five digits, as the header's bound has it
+// (tests/huff_rune_mid_plan_test.cpp).  The parser (huff_parse_rune.h) and the decoder keep PLAN_RUNE_COUNT_MAX.
+constexpr uint32_t PLAN_RUNE_MID_COUNT_MAX = 65536;
+static_assert(PLAN_RUNE_MID_COUNT_MAX < (1u << 23) && ((unsigned long long)PLAN_RUNE_MID_COUNT_MAX << PLAN_RUNE_IDB) < (1ull << 32) && PLAN_RUNE_MID_COUNT_MAX < 100000,
+              "every sum of counts stays below 2^23: a heap item count << 9 | id is one word; five digits a count");
+constexpr uint32_t PLAN_RUNE_SLOTS =2 * PLAN_RUNE_SYMS_MAX;           // of the encoder's and the decoder's open-addressing table: twice the symbols it may hold
 static_assert(PLAN_RUNE_SLOTS == 1u << 9, "plan_rune_hash gives 9 bits");
 
 // a rune's first slot in a table of PLAN_RUNE_SLOTS slots: the ONE hash of the encoder's counts (huff_rune.hip) and the decoder's entries

@@ -25,7 +25,7 @@ def CompressBatch(chunks):
     rsn_huffman_compress_batch runs chunks of 2 to BATCH_COMPRESS_INPUT_MAX bytes many to a launch, a workgroup each that builds the
     chunk's own tree on the device (byte alphabets; a chunk with a single distinct byte is handed back, one with a byte >= 0x80 goes to
     the rune class below, RUNE_GROUP_MIN), when at least two chunks are of that size.  Chunks above that and up to MID_IN_MAX bytes are the mid class (csrc/huff_mid.hip: the same kernel body at
-    1024 threads, the whole chunk in LDS), grouped the same way when the call holds at least MID_GROUP_MIN of them.  Chunks above that and up to BIG_IN_MAX bytes are the big class
+    1024 threads, the whole chunk in LDS), grouped the same way when the call holds at least MID_GROUP_MIN of them; those of them with a byte >= 0x80 go to the mid-size rune class below, RUNE_MID_GROUP_MIN.  Chunks above that and up to BIG_IN_MAX bytes are the big class
     (csrc/huff_big.hip: tiles of BIG_TILE bytes, three launches a group) when the call holds at least BIG_GROUP_MIN of them.  The other chunks are dealt out over the batch workers (chunk k -> device k mod G) and go through a
     pipeline of upload / encode / download per device.  Each result equals Compress(chunk)."""
     return _lib.call_batch(_lib.lib().rsn_huffman_compress_batch, chunks)
@@ -86,6 +86,12 @@ RUNE_GROUP_MIN = 16
 RUNE_OUT_MAX = 16384
 RUNE_PAY_MAX = 18432
 RUNE_DEC_GROUP_MIN = 16
+# The mid-size rune class of the compress batch calls (csrc/huff_rune_mid_select.h HUFF_RUNE_MID_IN_MAX / HUFF_RUNE_MID_GROUP_MIN;
+# csrc/huff_rune_mid.hip): chunks of more than BATCH_COMPRESS_INPUT_MAX and at most RUNE_MID_IN_MAX bytes that hold a byte >= 0x80
+# go a workgroup each through one launch per group when a call holds at least RUNE_MID_GROUP_MIN of them; what it hands back is what the rune
+# class above hands back.  There is no grouped way back yet: inside a decompress batch these streams take the single call's path.
+RUNE_MID_IN_MAX = 65536
+RUNE_MID_GROUP_MIN = 16
 
 
 def DecompressBatch(streams):
