@@ -11,7 +11,10 @@
 #include "huff_parse_small.h"   // (behind the HIP runtime: its functions are __host__ __device__ under hipcc)
 #include "huff_rune_select.h"
 #include "huff_rune_mid_select.h"
-#include "lzss_tile_layout.h"    // (behind the HIP runtime as well: lzt_e_cap, for the closure of the tiled LZSS decoder over the tiled encoder)
+#include "huff_big_layout.h"      // (the tiled classes' layout headers, behind the HIP runtime as well: their limits are stated there and named here)
+#include "huff_big_dec_layout.h"
+#include "lzss_tile_layout.h"
+#include "lzss_tile_dec_layout.h"
 
 namespace rsn {
 
@@ -120,18 +123,16 @@ const BatchClass &lzss_small_class(bool compress), &lzss_mid_class(bool compress
 // decompress batch.  LZSS_TILE_IN_MAX, LZSS_TILE_GROUP_MIN: DESIGN 4.7 and profiles/lzss_tile_batch.txt.
 // Mirrored as raisin_amd.lz.TILE_IN_MAX / TILE_E_MAX / TILE_POS / TILE_GROUP_MIN / TILE_GROUP_BYTES.
 // A PROBE build widens the class to measure where it should end (scripts/probes/lzss_tile_batch.py; Makefile: EXTRA=-DRSN_LZSS_TILE_IN_MAX=...
-// -DRSN_LZSS_TILE_GROUP_MIN=...); every other build has the two measured values.
-#ifndef RSN_LZSS_TILE_IN_MAX
-#define RSN_LZSS_TILE_IN_MAX 262144
-#endif
+// -DRSN_LZSS_TILE_GROUP_MIN=...); every other build has the two measured values (RSN_LZSS_TILE_IN_MAX's: lzss_tile_layout.h).
 #ifndef RSN_LZSS_TILE_GROUP_MIN
 #define RSN_LZSS_TILE_GROUP_MIN 16
 #endif
-constexpr uint32_t LZSS_TILE_IN_MAX = RSN_LZSS_TILE_IN_MAX;
-constexpr uint32_t LZSS_TILE_E_MAX = LZSS_TILE_IN_MAX + LZSS_TILE_IN_MAX / 16;
-constexpr uint32_t LZSS_TILE_POS = 2048;
+constexpr uint32_t LZSS_TILE_IN_MAX = LZT_IN_MAX;
+constexpr uint32_t LZSS_TILE_E_MAX = LZT_E_MAX;
+constexpr uint32_t LZSS_TILE_POS = LZT_TILE;
 constexpr size_t LZSS_TILE_GROUP_MIN = RSN_LZSS_TILE_GROUP_MIN;
 constexpr size_t LZSS_TILE_GROUP_BYTES = 67108864;
+static_assert(LZT_IN_MIN == LZSS_MID_IN_MAX, "the tiled class begins where the mid class ends");
 static_assert(LZSS_TILE_E_MAX < (1u << 31) && 4096 < (1u << 15) && LZSS_TILE_IN_MAX > LZSS_MID_IN_MAX && LZSS_TILE_GROUP_MIN >= 2,
               "a key is L << 16 | distance with its top bit free: L <= distance <= the window, 13 bits each, exact whatever E is; positions are words");
 const BatchClass &lzss_tile_class();
@@ -161,8 +162,8 @@ const BatchClass &huff_small_class(bool compress), &huff_mid_class(bool compress
 // Its groups hold up to HUFF_BIG_GROUP_BYTES of staging: a group of the other classes' 16 MiB would hold 32 members of 256 KiB, two tiles a CU.  The streams
 // decode through the tiled decoder below inside a decompress batch.  HUFF_BIG_GROUP_MIN, HUFF_BIG_IN_MAX: measured,
 // DESIGN 4.7 and profiles/huff_big_batch.txt.  Mirrored as raisin_amd.huffman.BIG_IN_MAX / BIG_TILE / BIG_GROUP_MIN / BIG_GROUP_BYTES.
-constexpr uint32_t HUFF_BIG_IN_MAX = 262144;
-constexpr uint32_t HUFF_BIG_TILE = 16384;
+constexpr uint32_t HUFF_BIG_IN_MAX = BIGL_IN_MAX;
+constexpr uint32_t HUFF_BIG_TILE = BIGL_TILE;
 constexpr size_t HUFF_BIG_GROUP_MIN = 4;
 constexpr size_t HUFF_BIG_GROUP_BYTES = 67108864;
 const BatchClass &huff_big_class();
@@ -176,8 +177,8 @@ const BatchClass &huff_big_class();
 // image holds (below 1.9 bits a symbol over a whole tile), malformed streams.  Both forms run on device staging, in groups of up to
 // HUFF_BIG_GROUP_BYTES, as the encoder's do.  HUFF_BIG_DEC_GROUP_MIN, HUFF_BIG_OUT_MAX: DESIGN 4.7 and profiles/huff_big_dec_batch.txt.
 // Mirrored as raisin_amd.huffman.BIG_OUT_MAX / BIG_PAY_MAX / BIG_DEC_GROUP_MIN / BIG_DEC_LANES / BIG_DEC_LANE_BITS / BIG_DEC_OUT_CAP.
-constexpr uint32_t HUFF_BIG_OUT_MAX = 262144;
-constexpr uint32_t HUFF_BIG_PAY_MAX = 229376;
+constexpr uint32_t HUFF_BIG_OUT_MAX = BIGD_OUT_MAX;
+constexpr uint32_t HUFF_BIG_PAY_MAX = BIGD_PAY_MAX;
 constexpr size_t HUFF_BIG_DEC_GROUP_MIN = 4;
 static_assert((unsigned long long)HUFF_BIG_PAY_MAX * 8 >= (unsigned long long)HUFF_BIG_IN_MAX * 7 && HUFF_BIG_OUT_MAX >= HUFF_BIG_IN_MAX,
               "the decoder takes every stream the encoder writes");
@@ -258,8 +259,8 @@ const BehindClass &huff_rune_dec_class();
 // empty result and more than LZSS_TILE_DEC_OUT_MAX escaped bytes; they stay in `rest`, and the single call words the errors.  Both forms
 // run on device staging, in groups of up to LZSS_TILE_GROUP_BYTES.  LZSS_TILE_DEC_GROUP_MIN: DESIGN 4.7.
 // Mirrored as raisin_amd.lz.TILE_DEC_IN_MAX / TILE_DEC_OUT_MAX / TILE_DEC_GROUP_MIN.
-constexpr uint32_t LZSS_TILE_DEC_IN_MAX = LZSS_TILE_E_MAX;
-constexpr uint32_t LZSS_TILE_DEC_OUT_MAX = LZSS_TILE_E_MAX;
+constexpr uint32_t LZSS_TILE_DEC_IN_MAX = LZTD_IN_MAX;
+constexpr uint32_t LZSS_TILE_DEC_OUT_MAX = LZTD_OUT_MAX;
 // A PROBE build lowers the minimum to measure where it should be (scripts/probes/lzss_tile_dec_batch.py; Makefile: EXTRA=-DRSN_LZSS_TILE_DEC_GROUP_MIN=2).
 #ifndef RSN_LZSS_TILE_DEC_GROUP_MIN
 #define RSN_LZSS_TILE_DEC_GROUP_MIN 8

@@ -211,6 +211,26 @@ int run_members_staged(Ctx &c, const char *what, const char *slot_error, const s
     return RSN_OK;
 }
 
+// The same for a class whose input goes up as it is (huff_big.hip, lzss_tile.hip, lzss_tile_dec.hip): no table, an input slot the member's
+// bytes rounded up to 16, an output slot of out_bytes(n).  noun: what the internal error calls a result beyond its slot.
+template <class OutBytes, class RunDev>
+int run_members_copied(Ctx &c, const char *what, const char *noun, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, OutBytes out_bytes,
+                       RunDev run_dev, const SmallTake &take, std::vector<size_t> &back, size_t *failed, std::vector<size_t> *back_runes) {
+    std::vector<RunItem> items;
+    for (size_t i : idx) items.push_back(RunItem{i, group_round16(lens[i]), out_bytes(lens[i]), out_bytes(lens[i])});
+    const std::string slot_error = std::string("%s: internal error: ") + noun + " of %u bytes in a slot of %zu";
+    return run_members_staged<0>(c, what, slot_error.c_str(), items,
+        [&](size_t k, size_t, size_t, const void *, uint8_t *, uint8_t *in) { memcpy(in, ins[idx[k]], lens[idx[k]]); return lens[idx[k]]; },
+        run_dev, take, back, failed, back_runes);
+}
+// the x of a tiled class's grid: tiles(n) of the largest of the members idx of `mem`, n at most n_cap, one at least
+template <class Tiles>
+uint32_t grid_tiles_of_largest(const std::vector<size_t> &idx, const rsn_dev_member *mem, size_t n_cap, Tiles tiles) {
+    size_t n_max = 0;
+    for (size_t i : idx) n_max = std::max(n_max, (size_t)mem[i].n);
+    return std::max(1u, (uint32_t)tiles((uint32_t)std::min(n_max, n_cap)));
+}
+
 // A class of SmallMember entries is stated ONCE, as a type K -- K::what (the name in messages), K::in_bytes(n) / K::out_bytes(n) (the slots of
 // a member of n bytes, group_layout.h) and K::launch(c, s, g, tab, base, window) (the group's kernel) -- and both of its runners, the
 // host-buffer form and the device-buffer form (BatchClass::run / run_dev, codecs.h), are these two.

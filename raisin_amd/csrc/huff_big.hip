@@ -16,22 +16,19 @@
 //   emit    k_huff_big_emit, a workgroup per tile of a member that was taken: 16 bytes a thread again, their codes' first bits by a block
 //           scan, ORed into an LDS image that starts at the 16-byte unit of the output the tile's first bit lies in (pack_codes16), and
 //           stored 16 bytes at a time.  An output byte belongs to the tile its FIRST bit lies in: the tile codes on into the next tile's
-//           first symbols until its last byte is full, and leaves the byte its own first bit lies in to the tile before.  So no output byte
-//           is stored by two workgroups, nothing is ORed into the output, and what the slot held before does not matter.
-// The status word of a taken member is stored by the LAST of its tiles to finish (a device-scope counter in the member's scratch, zeroed
-// by the plan), behind a fence: when it holds the length, every byte is in place.  Nothing polls it: k_group_scatter reads it, on the
-// same stream.  No workgroup waits for another; every loop is bounded by the tile, the alphabet or the tiles of a member.
-// The grid of count and emit is (tiles of the call's largest member, members of the group); a workgroup beyond its member's tiles leaves
-// at once -- a few microseconds for a group of many short members, and no tile table to build and copy up.
+//           first symbols until its last byte is full, and leaves the byte its own first bit lies in to the tile before.
+// Ownership, the member's status word by the last of its tiles, the grid and the host form are the tiled classes' common shape (DESIGN
+// 4.7; tile_dev.h); the done-counter is zeroed by the plan.  No workgroup waits for another; every loop is bounded by the tile, the
+// alphabet or the tiles of a member.
 #include "huff_small_body.h"
 #include "huff_big_layout.h"
+#include "tile_dev.h"
 
 namespace rsn {
 namespace {
 
 constexpr int BG_T = 1024;                        // threads of a tile's workgroup: 16 bytes each are the tile
 constexpr int BG_PT = 256;                        // threads of a member's planning workgroup
-static_assert(HUFF_BIG_IN_MAX == BIGL_IN_MAX && HUFF_BIG_TILE == BIGL_TILE, "huff_big_layout.h states the same class");
 static_assert(HUFF_BIG_TILE == 16 * BG_T, "a tile is one round of 16 bytes a thread");
 static_assert(BIGL_TILES_MAX <= BG_PT - 128 && BIGL_TILES_MAX <= 128, "the plan reads a tile's flag in a thread behind the 128 of the counts, and a tile's bits a thread");
 // ---- the encoder's arithmetic at n <= HUFF_BIG_IN_MAX (what plan_tree, plan_codes and the scans rely on)
@@ -158,7 +155,7 @@ __global__ __launch_bounds__(BG_T) void k_huff_big_emit(const SmallMember *__res
     if (my[BIG_SCR_META + BIG_META_VERDICT] != 0) return;                // handed back by the plan, which has stored its word
     const uint32_t T = big_tiles(n), b0 = my[BIG_SCR_OFF + t], b1 = my[BIG_SCR_OFF + t + 1], total = my[BIG_SCR_META + BIG_META_TOTAL];
     // the image's first byte is the output's byte u0, a 16-byte unit's first: bit positions below are the image's
-    const uint32_t u0 = (b0 >> 3) & ~15u, i0 = b0 - 8 * u0, i1 = b1 - 8 * u0;
+    const uint32_t u0 = big_tile_origin(b0), i0 = b0 - 8 * u0, i1 = b1 - 8 * u0;
     const uint32_t img_words = min(BG_IMG_WORDS, (i1 + 31) / 32 + 3);    // what the tile and the symbols behind it can reach
     for (uint32_t i = tid; i < img_words; i += BG_T) s_img[i] = 0;
     if (tid < 128) s_tab[tid] = my[BIG_SCR_TAB + tid];
@@ -194,23 +191,10 @@ __global__ __launch_bounds__(BG_T) void k_huff_big_emit(const SmallMember *__res
         }
     }
     __syncthreads();
-    // ---- the tile's own bytes out: whole 16-byte units as they are; the first and the last unit are shared with the neighbours, their
-    // bytes go one by one
-    const uint32_t lo = big_tile_first_byte(t, b0) - u0, hi = big_tile_end_byte(b1) - u0;   // (image bytes; hi - lo may be 0)
-    uint8_t *dst = base + m.out_off + u0;
-    const uint8_t *img = reinterpret_cast<const uint8_t *>(s_img);
-    for (uint32_t u = tid; u * 16 < hi; u += BG_T) {
-        const uint32_t x0 = u * 16, x1 = x0 + 16;
-        if (x0 >= lo && x1 <= hi) *reinterpret_cast<uint4 *>(dst + x0) = reinterpret_cast<const uint4 *>(s_img)[u];
-        else for (uint32_t x = max(x0, lo); x < min(x1, hi); x++) dst[x] = img[x];
-    }
-    // ---- the member's word, by the last of its tiles to get here: every byte of the stream is then in place
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) {
-        const uint32_t done = __hip_atomic_fetch_add(&my[BIG_SCR_META + BIG_META_DONE], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (done + 1 == T) __hip_atomic_store(reinterpret_cast<uint32_t *>(base + m.status_off), total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    // ---- the tile's own bytes out (the range may be empty, and begin in the unit behind u0), and the member's word by its last tile
+    tile_store_out<BG_T>(base + m.out_off, reinterpret_cast<const uint8_t *>(s_img), u0, big_tile_first_byte(t, b0), big_tile_end_byte(b1));
+    if (tile_finish(&my[BIG_SCR_META + BIG_META_DONE], T))
+        __hip_atomic_store(reinterpret_cast<uint32_t *>(base + m.status_off), total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // the three launches of a group of g members; gx: tiles of the largest member the call holds
@@ -226,26 +210,19 @@ int big_launch(Ctx &c, hipStream_t s, uint32_t g, uint32_t gx, const SmallMember
 
 constexpr const char *BIG_WHAT = "huffman batch compress";
 bool big_enc_takes(const uint8_t *, size_t n, int64_t) { return n > HUFF_MID_IN_MAX && n <= HUFF_BIG_IN_MAX; }   // (the length alone: both forms)
-size_t big_in_bytes(size_t n) { return huff_enc_in_slot(n); }
 size_t big_out_bytes(size_t n) { return huff_big_enc_out_slot((uint32_t)n); }
 
 // The device form: run_groups_dev's groups -- k_group_gather, the three launches, k_group_scatter -- of up to HUFF_BIG_GROUP_BYTES of staging.
 int big_enc_run_dev(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const rsn_dev_member *mem, int64_t, const DevPlans *, std::vector<uint32_t> &answers) {
-    size_t n_max = 0;
-    for (size_t i : idx) n_max = std::max(n_max, (size_t)mem[i].n);
-    const uint32_t gx = std::max(1u, big_tiles((uint32_t)std::min<size_t>(n_max, HUFF_BIG_IN_MAX)));
-    return run_groups_dev(c, s, BIG_WHAT, idx, mem, [&](size_t k) { return big_in_bytes(mem[idx[k]].n); }, [&](size_t k) { return big_out_bytes(mem[idx[k]].n); },
+    const uint32_t gx = grid_tiles_of_largest(idx, mem, HUFF_BIG_IN_MAX, big_tiles);
+    return run_groups_dev(c, s, BIG_WHAT, idx, mem, [&](size_t k) { return huff_enc_in_slot(mem[idx[k]].n); }, [&](size_t k) { return big_out_bytes(mem[idx[k]].n); },
         [&](hipStream_t s2, uint32_t g, const SmallMember *tab, uint8_t *base) { return big_launch(c, s2, g, gx, tab, base); }, answers, HUFF_BIG_GROUP_BYTES);
 }
 
-// The host form.  The kernels read a member twice and store its stream in pieces, so they never run on pinned host memory: the members go
-// through the device form above in runs (group_run.h: run_members_staged), the input slot a member's bytes rounded up to 16.
+// The host form: the members through the device form above (the kernels read a member twice: never out of pinned host memory).
 int big_enc_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
                 const SmallTake &take, std::vector<size_t> &back, size_t *failed, std::vector<size_t> *back_runes) {
-    std::vector<RunItem> items;
-    for (size_t i : idx) items.push_back(RunItem{i, group_round16(lens[i]), big_out_bytes(lens[i]), big_out_bytes(lens[i])});
-    return run_members_staged<0>(c, BIG_WHAT, "%s: internal error: a stream of %u bytes in a slot of %zu", items,
-        [&](size_t k, size_t, size_t, const void *, uint8_t *, uint8_t *in) { memcpy(in, ins[idx[k]], lens[idx[k]]); return lens[idx[k]]; },
+    return run_members_copied(c, BIG_WHAT, "a stream", idx, ins, lens, big_out_bytes,
         [&](hipStream_t s, const std::vector<size_t> &all, const rsn_dev_member *mem, std::vector<uint32_t> &answers) { return big_enc_run_dev(c, s, all, mem, window, nullptr, answers); },
         take, back, failed, back_runes);
 }

@@ -24,13 +24,12 @@
 // starts from the same first guess -- so every (lane, start) it meets the map launch met no later: it needs no more starts a lane and no
 // more rounds, and it arrives at the count the chain computed.  Were that ever not so, the tile stores no length and the member's word
 // stays GROUP_PENDING, which the host reports as an error: never wrong bytes.
-// The decoded length of a taken member is stored by the LAST of its tiles to finish (a device-scope counter in the member's scratch, zeroed
-// by the chain), behind a fence: when the status word says "done", every byte is in place.  Nothing polls it: k_huff_dev_scatter reads it,
-// on the same stream.  No workgroup waits for another; every loop is bounded by the tile's bits, DEC_ROUNDS, the tiles of a member or a
-// constant.  The grid of map and emit is (tiles of the call's largest member, members of the group); a workgroup beyond its member's
-// tiles leaves at once.
+// The member's two status words by the last of its tiles and the grid are the tiled classes' common shape (tile_dev.h); the
+// done-counter is zeroed by the chain, and k_huff_dev_scatter reads the words.  No workgroup waits for another; every loop is bounded by
+// the tile's bits, DEC_ROUNDS, the tiles of a member or a constant.
 #include "huff_small_body.h"
 #include "huff_big_dec_layout.h"
+#include "tile_dev.h"
 
 namespace rsn {
 namespace {
@@ -38,7 +37,7 @@ namespace {
 constexpr int BD_T = 1024;                        // threads of a tile's workgroup
 constexpr int BD_DL = BD_T - 64;                  // ... 15 wavefronts of lanes and the sixteenth for the first lane's 32 entries
 constexpr int BD_CT = 64;                         // threads of a member's chain: one wavefront
-static_assert(HUFF_BIG_OUT_MAX == BIGD_OUT_MAX && HUFF_BIG_PAY_MAX == BIGD_PAY_MAX && (uint32_t)BD_DL == BIGD_LANES, "huff_big_dec_layout.h states the same class");
+static_assert((uint32_t)BD_DL == BIGD_LANES, "a thread a lane, and the sixteenth wavefront");
 static_assert(BIGD_OFF_BAD == OFF_BAD && BIGD_S >= 64 && BIGD_S <= DEC_S_MAX, "the lanes are lane_dec_body's: an exit is a byte, a lane 64 bits at least");
 static_assert(HUFF_BIG_OUT_MAX < (1u << 24), "a tile's symbols and a member's are the low 24 bits of a map entry");
 constexpr uint32_t BD_PAY_WORDS = BIGD_LANES * BIGD_S / 32 + 8;   // the tile's words, the six behind it a 32-bit codeword and the reader's look-ahead reach, two of zeros
@@ -99,14 +98,9 @@ __global__ __launch_bounds__(BD_T) void k_huff_big_dec_emit(const SmallDecArgs *
     const uint32_t n = lane_dec_body<BD_PAY_WORDS, BIGD_OUT_CAP, true, BD_DL, 256, true, TILE_EMIT>(s_a, s_a.child, s_pay, s_out, entry, base);
     if (n != count) return;                                               // (cannot be, see above: the member stays without an answer)
     // ---- the member's words, by the last of its tiles to get here: every byte of the output is then in place
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t done = __hip_atomic_fetch_add(&my[BIGD_SCR_META + BIGD_META_DONE], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (done + 1 == tiles) {
-            __hip_atomic_store(&s_a.status[1], total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&s_a.status[0], 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        }
+    if (tile_finish(&my[BIGD_SCR_META + BIGD_META_DONE], tiles)) {
+        __hip_atomic_store(&s_a.status[1], total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&s_a.status[0], 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 

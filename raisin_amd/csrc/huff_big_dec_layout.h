@@ -3,8 +3,8 @@
 // A stream that promises more than HUFF_MID_OUT_MAX bytes does not fit a workgroup's LDS (huff_mid.hip).  It is one bit string without an
 // index, so it is cut in the PAYLOAD:
 //   tiles      a tile is BIGD_LANES lanes of BIGD_S code bits, counted from the stream's first code bit: BIGD_TILE_BITS bits, 7680 bytes of
-//              payload, a workgroup.  A stream of `span` code bits has bigd_lanes(span) lanes and bigd_tiles(span) tiles, the last one
-//              shorter; the kernels' grid is (tiles of the call's largest member, members) and a workgroup beyond its member's tiles leaves;
+//              payload, a workgroup (the tiled classes' common shape).  A stream of `span` code bits has bigd_lanes(span)
+//              lanes and bigd_tiles(span) tiles, the last one shorter;
 //   scratch    BIGD_SCR_WORDS words a member of the group (Slot::GD_BIG_DEC): per tile its 32-entry map -- "entered at bit c of the tile,
 //              the codewords that start in it number n and the last one ends at bit c' of the next tile": c' << 24 | n, BIGD_OFF_BAD for
 //              c' where the path is lost or runs off the payload -- then per tile its true entry, its first output byte and its symbols,
@@ -22,7 +22,7 @@
 
 namespace rsn {
 
-// (codecs.h: HUFF_BIG_OUT_MAX / HUFF_BIG_PAY_MAX are the first two; huff_big_dec.hip asserts it)
+// the class's limits: codecs.h names the first two HUFF_BIG_OUT_MAX / HUFF_BIG_PAY_MAX
 constexpr uint32_t BIGD_OUT_MAX = 262144;                                    // decoded bytes of a member at most
 constexpr uint32_t BIGD_PAY_MAX = 229376;                                    // payload bytes of a member at most: 7/8 of BIGD_OUT_MAX
 constexpr uint32_t BIGD_LANES = 960;                                         // lanes of a tile: 15 wavefronts (the sixteenth answers the first lane's entries)
@@ -34,8 +34,8 @@ constexpr uint32_t BIGD_OFF_BAD = 0xFF;                                      // 
 static_assert(BIGD_TILES_MAX == 30 && BIGD_S % 32 == 0 && BIGD_S >= 64, "whole words a lane, 64 bits at least: an exit lies within 32 bits of the next lane's first");
 static_assert(8ull * BIGD_PAY_MAX == 7ull * BIGD_OUT_MAX, "a byte alphabet codes in at most 7 bits a byte");
 
-RSN_PLAN_FN uint32_t bigd_lanes(uint32_t span) { return (span + BIGD_S - 1) / BIGD_S; }
-RSN_PLAN_FN uint32_t bigd_tiles(uint32_t span) { return (bigd_lanes(span) + BIGD_LANES - 1) / BIGD_LANES; }
+RSN_HD_FN uint32_t bigd_lanes(uint32_t span) { return (span + BIGD_S - 1) / BIGD_S; }
+RSN_HD_FN uint32_t bigd_tiles(uint32_t span) { return (bigd_lanes(span) + BIGD_LANES - 1) / BIGD_LANES; }
 // what parse_lanes (huff_parse_small.h) is asked for the class: BIGD_TILES_MAX tiles' lanes of at most BIGD_S bits -- it answers S = BIGD_S
 // for every span the class takes, so a tile's bits do not depend on the stream
 constexpr uint32_t BIGD_LANES_ALL = BIGD_TILES_MAX * BIGD_LANES;
@@ -53,7 +53,7 @@ constexpr uint32_t BIGD_TILE_ENTRY = 0, BIGD_TILE_BASE = 1, BIGD_TILE_COUNT = 2;
 // The maps of a member's `tiles` tiles composed in order.  maps[t * 32 + c]: tile t's answer for entry c.  rec[t * 4 ..): tile t's true
 // entry, first output byte and symbols.  out_max: the bytes the header promises (the output slot holds them).  Returns true with *total =
 // the decoded bytes, or false: the member is handed back.  Bounded by the tiles.
-RSN_PLAN_FN bool bigd_chain(const uint32_t *maps, uint32_t tiles, uint32_t out_max, uint32_t *rec, uint32_t *total) {
+RSN_HD_FN bool bigd_chain(const uint32_t *maps, uint32_t tiles, uint32_t out_max, uint32_t *rec, uint32_t *total) {
     uint32_t c = 0, base = 0;
     if (tiles == 0 || tiles > BIGD_TILES_MAX) return false;
     for (uint32_t t = 0; t < tiles; t++) {

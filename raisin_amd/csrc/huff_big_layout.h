@@ -1,8 +1,6 @@
 // huff_big_layout.h -- the arithmetic of the big class of the Huffman compress batch (huff_big.hip) as plain code: no HIP
 // include, so a CPU test (tests/huff_big_plan_test.cpp) holds it against naive loops.  A member above HUFF_MID_IN_MAX bytes does not fit a
-// workgroup's LDS, so it is cut into TILES of BIGL_TILE input bytes, a workgroup each:
-//   tiles      big_tiles(n) of BIGL_TILE bytes, the last one shorter; the kernels' grid is (tiles of the call's largest member, members) and
-//              a workgroup whose tile index lies beyond its member's tiles leaves at once -- no tile table is built or copied up;
+// workgroup's LDS, so it is cut into TILES of BIGL_TILE input bytes, a workgroup each (the tiled classes' common shape):
 //   scratch    BIG_SCR_WORDS words a member of the group (Slot::GD_BIG_TILES): the tiles' 128 counts, a "byte >= 0x80" flag a tile, the 128
 //              code table entries, the tiles' first bits and four words of the member's own (verdict, stream length, tiles done);
 //   bit offsets  a tile's code bits are sum(count * code length) over its own counts; tile t's first bit is the header, the pad in front
@@ -16,20 +14,18 @@
 #include <cstdint>
 
 #include "huff_plan_small.h"
+#include "tile_layout.h"
 
 namespace rsn {
 
-// (codecs.h: HUFF_BIG_IN_MAX / HUFF_BIG_TILE are these; huff_big.hip asserts it)
+// the class's limits: codecs.h names them HUFF_BIG_IN_MAX / HUFF_BIG_TILE
 constexpr uint32_t BIGL_IN_MAX = 1u << 18;
 constexpr uint32_t BIGL_TILE = 16384;
 constexpr uint32_t BIGL_TILES_MAX = BIGL_IN_MAX / BIGL_TILE;
 static_assert(BIGL_IN_MAX % BIGL_TILE == 0 && BIGL_TILE % 16 == 0, "whole tiles, whole 16-byte units");
 
-RSN_PLAN_FN uint32_t big_tiles(uint32_t n) { return (n + BIGL_TILE - 1) / BIGL_TILE; }
-RSN_PLAN_FN uint32_t big_tile_len(uint32_t n, uint32_t t) {                   // t < big_tiles(n)
-    const uint32_t lo = t * BIGL_TILE;
-    return n - lo < BIGL_TILE ? n - lo : BIGL_TILE;
-}
+RSN_HD_FN uint32_t big_tiles(uint32_t n) { return tile_count(n, BIGL_TILE); }
+RSN_HD_FN uint32_t big_tile_len(uint32_t n, uint32_t t) { return tile_len(n, BIGL_TILE, t); }   // t < big_tiles(n)
 
 // ---- the header's bound.  The entries are "<count>|<byte>" (the newline's byte takes two), at most 128 of them, and the counts sum to
 // the member's length, so not all of them can be long: a count of d digits is at least 10^(d-1).  Start from a symbols of one digit (a
@@ -71,25 +67,27 @@ constexpr uint32_t BIG_META_VERDICT = 0, BIG_META_TOTAL = 1, BIG_META_DONE = 2;
 
 // ---- what the plan refuses once the tree is built: a code beyond the 24 bits of the emit table's entry, a header beyond its bound, a
 // stream beyond the member's output slot (none of the last two can occur for n <= BIGL_IN_MAX: the slot is sized by the two bounds)
-RSN_PLAN_FN bool big_plan_refuses(uint32_t max_len, uint32_t hdr, uint32_t total, uint32_t slot) {
+RSN_HD_FN bool big_plan_refuses(uint32_t max_len, uint32_t hdr, uint32_t total, uint32_t slot) {
     return max_len > 24 || hdr > HUFF_BIG_HDR_MAX || total > slot;
 }
 
 // the code bits of a tile: hist[128] its counts, tab[128] the code table
-RSN_PLAN_FN uint32_t big_tile_bits(const uint32_t *hist, const uint32_t *tab) {
+RSN_HD_FN uint32_t big_tile_bits(const uint32_t *hist, const uint32_t *tab) {
     uint32_t bits = 0;
     for (uint32_t b = 0; b < PLAN_SYMS_MAX; b++) bits += hist[b] * (tab[b] >> 24);
     return bits;
 }
 // off[t] = base + the bits of the tiles before t, for t in [0, tiles]; base: 8 * header + the pad in front
-RSN_PLAN_FN void big_tile_offsets(const uint32_t *tile_bits, uint32_t tiles, uint32_t base, uint32_t *off) {
+RSN_HD_FN void big_tile_offsets(const uint32_t *tile_bits, uint32_t tiles, uint32_t base, uint32_t *off) {
     uint32_t at = base;
     for (uint32_t t = 0; t < tiles; t++) { off[t] = at; at += tile_bits[t]; }
     off[tiles] = at;
 }
 // the bytes tile t stores: [first, end) -- b0 / b1: its first bit and the next tile's.  Tile 0 starts behind the pad, inside the first
-// payload byte, which is its own
-RSN_PLAN_FN uint32_t big_tile_first_byte(uint32_t t, uint32_t b0) { return t == 0 ? b0 >> 3 : (b0 + 7) >> 3; }
-RSN_PLAN_FN uint32_t big_tile_end_byte(uint32_t b1) { return (b1 + 7) >> 3; }
+// payload byte, which is its own.  The tile's image begins at the unit b0 lies in: for t > 0 and b0 inside the LAST byte of a unit the
+// tile's first byte is the next unit's, and unit 0 of the image stores nothing
+RSN_HD_FN uint32_t big_tile_origin(uint32_t b0) { return tile_origin(b0 >> 3); }
+RSN_HD_FN uint32_t big_tile_first_byte(uint32_t t, uint32_t b0) { return t == 0 ? b0 >> 3 : (b0 + 7) >> 3; }
+RSN_HD_FN uint32_t big_tile_end_byte(uint32_t b1) { return (b1 + 7) >> 3; }
 
 }  // namespace rsn

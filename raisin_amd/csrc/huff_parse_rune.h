@@ -48,13 +48,13 @@ struct HuffRunePlan {
     uint32_t leaf_rune[PARSE_RUNE_SYMS_MAX];
 };
 
-RSN_PLAN_FN uint32_t parse_rune_scan_limit(uint32_t n) { return n < PARSE_RUNE_SCAN_MAX ? n : PARSE_RUNE_SCAN_MAX; }
-RSN_PLAN_FN bool parse_rune_length_ok(unsigned long long n) { return n >= 8 && n <= PARSE_RUNE_STREAM_MAX; }
+RSN_HD_FN uint32_t parse_rune_scan_limit(uint32_t n) { return n < PARSE_RUNE_SCAN_MAX ? n : PARSE_RUNE_SCAN_MAX; }
+RSN_HD_FN bool parse_rune_length_ok(unsigned long long n) { return n >= 8 && n <= PARSE_RUNE_STREAM_MAX; }
 
 // the rune that starts at byte i of h[0, end), as Go's `range string` yields it (go_decode_rune, huff_host.cpp; seq_len, huff_utf8.h);
 // only bytes below `end` are asked for
 template <class Bytes>
-RSN_PLAN_FN uint32_t parse_rune_decode(const Bytes &h, uint32_t i, uint32_t end) {
+RSN_HD_FN uint32_t parse_rune_decode(const Bytes &h, uint32_t i, uint32_t end) {
     const uint32_t b0 = h.get(i);
     if (b0 < 0x80) return b0;
     if (b0 < 0xC2 || b0 > 0xF4) return PARSE_RUNE_ERROR;
@@ -73,7 +73,7 @@ RSN_PLAN_FN uint32_t parse_rune_decode(const Bytes &h, uint32_t i, uint32_t end)
 }
 
 // rune r's entry: cnt1 = count + 1 of its LAST entry.  key[] starts as PARSE_RUNE_EMPTY.  false: one rune more than the class takes
-RSN_PLAN_FN bool parse_rune_put(uint32_t *key, uint32_t *cnt1, uint32_t *distinct, uint32_t r, uint32_t c1) {
+RSN_HD_FN bool parse_rune_put(uint32_t *key, uint32_t *cnt1, uint32_t *distinct, uint32_t r, uint32_t c1) {
     uint32_t slot = plan_rune_hash(r);
     for (uint32_t p = 0; p < PARSE_RUNE_SLOTS; p++) {
         const uint32_t k = key[slot];
@@ -91,7 +91,7 @@ RSN_PLAN_FN bool parse_rune_put(uint32_t *key, uint32_t *cnt1, uint32_t *distinc
 // The entries of h[0, sep) into the table; a count saturates at PARSE_RUNE_COUNT_MAX + 1.  h.get(i) is asked for i < sep only.
 // false: refused.
 template <class Bytes>
-RSN_PLAN_FN bool parse_rune_scan(const Bytes &h, uint32_t sep, uint32_t *key, uint32_t *cnt1, uint32_t *distinct) {
+RSN_HD_FN bool parse_rune_scan(const Bytes &h, uint32_t sep, uint32_t *key, uint32_t *cnt1, uint32_t *distinct) {
     uint32_t acc = 0;
     for (uint32_t i = 0; i < sep; i++) {
         const uint32_t ch = h.get(i);
@@ -115,7 +115,7 @@ RSN_PLAN_FN bool parse_rune_scan(const Bytes &h, uint32_t sep, uint32_t *key, ui
 }
 
 // string(rune) for a rune the scan yields (never a surrogate, never beyond U+10FFFF): its bytes to out, their number returned
-RSN_PLAN_FN uint32_t parse_rune_write(uint32_t r, uint8_t *out) {
+RSN_HD_FN uint32_t parse_rune_write(uint32_t r, uint8_t *out) {
     if (r < 0x80) { out[0] = (uint8_t)r; return 1; }
     if (r < 0x800) { out[0] = (uint8_t)(0xC0 | r >> 6); out[1] = (uint8_t)(0x80 | (r & 0x3F)); return 2; }
     if (r < 0x10000) { out[0] = (uint8_t)(0xE0 | r >> 12); out[1] = (uint8_t)(0x80 | ((r >> 6) & 0x3F)); out[2] = (uint8_t)(0x80 | (r & 0x3F)); return 3; }
@@ -124,17 +124,17 @@ RSN_PLAN_FN uint32_t parse_rune_write(uint32_t r, uint8_t *out) {
 }
 
 // one symbol's part of the counts' verdict
-RSN_PLAN_FN uint32_t parse_rune_bytes(uint32_t r, uint32_t c1) { return (c1 - 1) * plan_rune_utf8_len(r); }
+RSN_HD_FN uint32_t parse_rune_bytes(uint32_t r, uint32_t c1) { return (c1 - 1) * plan_rune_utf8_len(r); }
 // the counts' verdict: a distinct runes, one of them >= 0x80, none with a count beyond the limit, expect bytes in all
-RSN_PLAN_FN bool parse_rune_counts_ok(uint32_t a, bool any_high, bool any_over, unsigned long long expect) {
+RSN_HD_FN bool parse_rune_counts_ok(uint32_t a, bool any_high, bool any_over, unsigned long long expect) {
     return a >= 2 && a <= PARSE_RUNE_SYMS_MAX && any_high && !any_over && expect != 0 && expect <= PARSE_RUNE_OUT_MAX;
 }
 // the stream's bounds (parse_bounds) and the class's lanes
-RSN_PLAN_FN bool parse_rune_bounds(uint32_t n, uint32_t sep, uint32_t diff, HuffDevBounds &p, uint32_t *S, uint32_t *T) {
+RSN_HD_FN bool parse_rune_bounds(uint32_t n, uint32_t sep, uint32_t diff, HuffDevBounds &p, uint32_t *S, uint32_t *T) {
     return parse_bounds(n, sep, diff, p) && parse_lanes(p.end - p.p0, PARSE_RUNE_LANES, PARSE_RUNE_S_MAX, S, T);
 }
 // a node of plan_tree as an entry of child[]: a leaf's rank, or the internal node
-RSN_PLAN_FN uint32_t parse_rune_child(uint32_t id, uint32_t a) { return id < a ? 0x8000u | id : id - a; }
+RSN_HD_FN uint32_t parse_rune_child(uint32_t id, uint32_t a) { return id < a ? 0x8000u | id : id - a; }
 
 // ---- the plan in front of the tree, serially (the "light scan"): what the host's classifier asks of a member and what
 // k_huff_dev_rune_plan answers where the stream lies.  The table lives on the caller's stack; in[0, n) is all it reads.  A planned

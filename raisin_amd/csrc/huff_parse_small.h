@@ -58,19 +58,19 @@ struct HuffDevSummary { uint32_t verdict, A0, span, expect; };   // span = end -
 static_assert(sizeof(HuffDevSummary) == 16, "16 bytes a member come down");
 
 // how many of a stream's n bytes are looked at
-RSN_PLAN_FN uint32_t parse_scan_limit(uint32_t n) { return n < PARSE_SCAN_MAX ? n : PARSE_SCAN_MAX; }
-RSN_PLAN_FN bool parse_length_ok(unsigned long long n, bool allow_wide = false) { return n >= 8 && n <= (allow_wide ? PARSE_STREAM_MAX_WIDE : PARSE_STREAM_MAX); }
+RSN_HD_FN uint32_t parse_scan_limit(uint32_t n) { return n < PARSE_SCAN_MAX ? n : PARSE_SCAN_MAX; }
+RSN_HD_FN bool parse_length_ok(unsigned long long n, bool allow_wide = false) { return n >= 8 && n <= (allow_wide ? PARSE_STREAM_MAX_WIDE : PARSE_STREAM_MAX); }
 // is the stream judged by the wide limits?  n: its length; sum: the sum of its counts (saturated counts: an upper bound that errs wide, and
 // wide refuses them)
-RSN_PLAN_FN bool parse_is_wide(bool allow_wide, uint32_t n, unsigned long long sum) { return allow_wide && (n > PARSE_STREAM_MAX || sum > PARSE_OUT_MAX); }
+RSN_HD_FN bool parse_is_wide(bool allow_wide, uint32_t n, unsigned long long sum) { return allow_wide && (n > PARSE_STREAM_MAX || sum > PARSE_OUT_MAX); }
 // is position i the separator's?  (i + 1 < parse_scan_limit(n))
-RSN_PLAN_FN bool parse_sep_at(uint32_t b0, uint32_t b1) { return b0 == 0x5Cu && b1 == 0x0Au; }
+RSN_HD_FN bool parse_sep_at(uint32_t b0, uint32_t b1) { return b0 == 0x5Cu && b1 == 0x0Au; }
 
 // The entries of h[0, sep): cnt1[b] = count + 1 of byte b's last entry, 0 where it has none; a count saturates at `limit` (PLAN_COUNT_LIMIT,
 // or PLAN_COUNT_LIMIT_WIDE where the wide form is allowed).  h.get(i): byte i of the stream, asked for i < sep only.  false: refused.
 // cnt1[128] must be zero.
 template <class Bytes>
-RSN_PLAN_FN bool parse_scan(const Bytes &h, uint32_t sep, uint32_t *cnt1, uint32_t limit = PLAN_COUNT_LIMIT) {
+RSN_HD_FN bool parse_scan(const Bytes &h, uint32_t sep, uint32_t *cnt1, uint32_t limit = PLAN_COUNT_LIMIT) {
     uint32_t acc = 0;
     for (uint32_t i = 0; i < sep; i++) {
         const uint32_t ch = h.get(i);
@@ -94,13 +94,13 @@ RSN_PLAN_FN bool parse_scan(const Bytes &h, uint32_t sep, uint32_t *cnt1, uint32
 }
 
 // the counts' verdict: a (distinct bytes) and the sum, from cnt1; wide: parse_is_wide's answer, any_at_limit: a count at or above that form's limit
-RSN_PLAN_FN uint32_t parse_count_limit(bool wide) { return wide ? PLAN_COUNT_LIMIT_WIDE : PLAN_COUNT_LIMIT; }
-RSN_PLAN_FN bool parse_counts_ok(uint32_t a, uint32_t any_at_limit, unsigned long long sum, bool wide = false) {
+RSN_HD_FN uint32_t parse_count_limit(bool wide) { return wide ? PLAN_COUNT_LIMIT_WIDE : PLAN_COUNT_LIMIT; }
+RSN_HD_FN bool parse_counts_ok(uint32_t a, uint32_t any_at_limit, unsigned long long sum, bool wide = false) {
     return a >= 2 && a <= PLAN_SYMS_MAX && !any_at_limit && sum != 0 && sum <= (wide ? PARSE_OUT_MAX_WIDE : PARSE_OUT_MAX);
 }
 
 // the stream's bounds from the separator (small_dec_plan); diff: the pad byte, in[sep + 2].  false: it leaves no code bit
-RSN_PLAN_FN bool parse_bounds(uint32_t n, uint32_t sep, uint32_t diff, HuffDevBounds &p) {
+RSN_HD_FN bool parse_bounds(uint32_t n, uint32_t sep, uint32_t diff, HuffDevBounds &p) {
     const uint32_t pay = sep + 3, nbits = (n - sep - 3) * 8;
     if (diff >= nbits) return false;
     p.A0 = pay & ~3u;
@@ -111,7 +111,7 @@ RSN_PLAN_FN bool parse_bounds(uint32_t n, uint32_t sep, uint32_t diff, HuffDevBo
 }
 
 // bits per lane and lanes in use of a class of `lanes` subsequences of at most s_max bits; false: the stream is not for that class
-RSN_PLAN_FN bool parse_lanes(uint32_t span, uint32_t lanes, uint32_t s_max, uint32_t *S, uint32_t *T) {
+RSN_HD_FN bool parse_lanes(uint32_t span, uint32_t lanes, uint32_t s_max, uint32_t *S, uint32_t *T) {
     uint32_t s = ((span + lanes - 1) / lanes + 31) & ~31u;
     if (s < 64) s = 64;
     *S = s; *T = (span + s - 1) / s;
@@ -119,10 +119,10 @@ RSN_PLAN_FN bool parse_lanes(uint32_t span, uint32_t lanes, uint32_t s_max, uint
 }
 
 // internal node k's two entries of child[]: kids = left | right << 8 as plan_tree leaves them, a leaves, leaf_byte[rank]
-RSN_PLAN_FN uint32_t parse_child(uint32_t id, uint32_t a, const uint8_t *leaf_byte) { return id < a ? 0x8000u | leaf_byte[id] : id - a; }
+RSN_HD_FN uint32_t parse_child(uint32_t id, uint32_t a, const uint8_t *leaf_byte) { return id < a ? 0x8000u | leaf_byte[id] : id - a; }
 
 // K, flat and the verdict on the code lengths; mn / mx: the shortest and the deepest leaf
-RSN_PLAN_FN bool parse_depths(uint32_t mn, uint32_t mx, HuffDevBounds &p) {
+RSN_HD_FN bool parse_depths(uint32_t mn, uint32_t mx, HuffDevBounds &p) {
     if (mx == 0 || mx > 32) return false;
     p.K = mx < PARSE_K_MAX ? mx : PARSE_K_MAX;
     p.flat = mn == mx ? mx : 0u;
@@ -131,12 +131,12 @@ RSN_PLAN_FN bool parse_depths(uint32_t mn, uint32_t mx, HuffDevBounds &p) {
 
 // ---- the whole plan, serially, over array stores: what the kernel does with a workgroup (the separator by a block-wide minimum, the
 // ranks a thread each, the tree in one wavefront's VGPRs).  The CPU test's subject; in[0, n) is all it reads.
-struct ParseArrayBytes { const uint8_t *p; RSN_PLAN_FN uint32_t get(uint32_t i) const { return p[i]; } };
+struct ParseArrayBytes { const uint8_t *p; RSN_HD_FN uint32_t get(uint32_t i) const { return p[i]; } };
 template <int N>
 struct ParseArrayStore {
     uint32_t v[N];
-    RSN_PLAN_FN uint32_t get(uint32_t i) const { return v[i]; }
-    RSN_PLAN_FN void set(uint32_t i, uint32_t x) { v[i] = x; }
+    RSN_HD_FN uint32_t get(uint32_t i) const { return v[i]; }
+    RSN_HD_FN void set(uint32_t i, uint32_t x) { v[i] = x; }
 };
 inline void parse_plan_serial(const uint8_t *in, unsigned long long n64, HuffDevPlan &plan, bool allow_wide = false) {
     plan = HuffDevPlan{};

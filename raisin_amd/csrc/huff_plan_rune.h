@@ -33,10 +33,10 @@ static_assert(PLAN_RUNE_SLOTS == 1u << 9, "plan_rune_hash gives 9 bits");
 
 // a rune's first slot in a table of PLAN_RUNE_SLOTS slots: the ONE hash of the encoder's counts (huff_rune.hip) and the decoder's entries
 // (huff_parse_rune.h); tests/huff_rune_parse_test.cpp prints it (`slots`)
-RSN_PLAN_FN uint32_t plan_rune_hash(uint32_t r) { return (r * 0x9E3779B1u) >> 23; }   // 9 bits
+RSN_HD_FN uint32_t plan_rune_hash(uint32_t r) { return (r * 0x9E3779B1u) >> 23; }   // 9 bits
 
 // symbol t of the a symbols (rune[], cnt[]): its position in (count asc, rune asc) order and in rune order
-RSN_PLAN_FN void plan_rune_ranks(const uint32_t *rune, const uint32_t *cnt, uint32_t a, uint32_t t, uint32_t *leaf_rank, uint32_t *rune_rank) {
+RSN_HD_FN void plan_rune_ranks(const uint32_t *rune, const uint32_t *cnt, uint32_t a, uint32_t t, uint32_t *leaf_rank, uint32_t *rune_rank) {
     const uint32_t r = rune[t], f = cnt[t];
     uint32_t lr = 0, rr = 0;
     for (uint32_t j = 0; j < a; j++) {
@@ -48,14 +48,14 @@ RSN_PLAN_FN void plan_rune_ranks(const uint32_t *rune, const uint32_t *cnt, uint
 }
 
 // bytes of string(rune) for a rune Go's decoding yields (never a surrogate, never beyond U+10FFFF)
-RSN_PLAN_FN uint32_t plan_rune_utf8_len(uint32_t r) { return r < 0x80 ? 1u : r < 0x800 ? 2u : r < 0x10000 ? 3u : 4u; }
+RSN_HD_FN uint32_t plan_rune_utf8_len(uint32_t r) { return r < 0x80 ? 1u : r < 0x800 ? 2u : r < 0x10000 ? 3u : 4u; }
 // one header entry: strconv.Itoa(count) '|' string(rune), newline as "\n" (huffman.go:314-316)
-RSN_PLAN_FN uint32_t plan_rune_entry_len(uint32_t count, uint32_t r) {
+RSN_HD_FN uint32_t plan_rune_entry_len(uint32_t count, uint32_t r) {
     uint32_t d = 1;
     for (uint32_t v = count; v >= 10; v /= 10) d++;
     return d + 1 + (r == 10 ? 2u : plan_rune_utf8_len(r));
 }
-RSN_PLAN_FN uint32_t plan_rune_entry(uint32_t count, uint32_t r, uint8_t *out) {
+RSN_HD_FN uint32_t plan_rune_entry(uint32_t count, uint32_t r, uint8_t *out) {
     uint32_t d = 1;
     for (uint32_t v = count; v >= 10; v /= 10) d++;
     uint32_t at = d;

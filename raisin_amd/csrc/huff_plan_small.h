@@ -15,11 +15,7 @@
 
 #include <cstdint>
 
-#ifdef __HIPCC__
-#define RSN_PLAN_FN __host__ __device__ __forceinline__
-#else
-#define RSN_PLAN_FN inline
-#endif
+#include "tile_layout.h"   // (RSN_HD_FN: the one qualifier of plain code that the kernels call too)
 
 namespace rsn {
 
@@ -36,11 +32,11 @@ constexpr uint32_t PLAN_COUNT_LIMIT_WIDE = 1u << 24;
 //   code   len << 24 | code (low 24 bits)  (k_small_emit's table entry; only meaningful while len <= 24)
 // IDB: bits of a node id -- 8 for this alphabet; 9 for the rune alphabet of up to 256 leaves (huff_plan_rune.h: ids reach 510), which
 // shares the tree and the codes below.
-template <uint32_t IDB = 8> RSN_PLAN_FN uint32_t plan_item(uint32_t count, uint32_t id) { return count << IDB | id; }
-template <uint32_t IDB = 8> RSN_PLAN_FN uint32_t plan_count(uint32_t item) { return item >> IDB; }
+template <uint32_t IDB = 8> RSN_HD_FN uint32_t plan_item(uint32_t count, uint32_t id) { return count << IDB | id; }
+template <uint32_t IDB = 8> RSN_HD_FN uint32_t plan_count(uint32_t item) { return item >> IDB; }
 
 // position of byte b among the present bytes in (count asc, byte asc) order; cnt[128], cnt[b] > 0
-RSN_PLAN_FN uint32_t plan_leaf_rank(const uint32_t *cnt, uint32_t b) {
+RSN_HD_FN uint32_t plan_leaf_rank(const uint32_t *cnt, uint32_t b) {
     const uint32_t f = cnt[b];
     uint32_t r = 0;
     for (uint32_t c = 0; c < PLAN_SYMS_MAX; c++) {
@@ -54,7 +50,7 @@ RSN_PLAN_FN uint32_t plan_leaf_rank(const uint32_t *cnt, uint32_t b) {
 // so heap.Init moves nothing, huffman.go:93).  Internal node a + k gets kids.set(k, left | right << IDB).  Returns the root's id.
 // Pop and push carry the moving item and shift the others past it: heap.go's swaps give the same final layout.
 template <uint32_t IDB = 8, class Heap, class Kids>
-RSN_PLAN_FN uint32_t plan_tree(uint32_t a, Heap &h, Kids &kids) {
+RSN_HD_FN uint32_t plan_tree(uint32_t a, Heap &h, Kids &kids) {
     constexpr uint32_t IDM = (1u << IDB) - 1;
     uint32_t n = a, next = a;
     auto pop = [&]() -> uint32_t {                                    // heap.Pop: swap(0, n-1), down(0, n-1), take the last
@@ -94,7 +90,7 @@ RSN_PLAN_FN uint32_t plan_tree(uint32_t a, Heap &h, Kids &kids) {
 
 // Codes of every node [0, 2a - 1), parents before children: code.set(id, len << 24 | code).  Slots must start at 0 (the root's code).
 template <uint32_t IDB = 8, class Kids, class Codes>
-RSN_PLAN_FN void plan_codes(uint32_t a, uint32_t root, const Kids &kids, Codes &code) {
+RSN_HD_FN void plan_codes(uint32_t a, uint32_t root, const Kids &kids, Codes &code) {
     for (uint32_t id = root + 1; id-- > a;) {
         const uint32_t p = code.get(id), l = (p >> 24) + 1, base = (p << 1) & 0xFFFFFEu;
         const uint32_t k = kids.get(id - a);
@@ -104,12 +100,12 @@ RSN_PLAN_FN void plan_codes(uint32_t a, uint32_t root, const Kids &kids, Codes &
 }
 
 // one header entry: strconv.Itoa(count) '|' byte, newline as "\n" (huffman.go:314-316)
-RSN_PLAN_FN uint32_t plan_entry_len(uint32_t count, uint32_t b) {
+RSN_HD_FN uint32_t plan_entry_len(uint32_t count, uint32_t b) {
     uint32_t d = 1;
     for (uint32_t v = count; v >= 10; v /= 10) d++;
     return d + 1 + (b == 10 ? 2u : 1u);
 }
-RSN_PLAN_FN uint32_t plan_entry(uint32_t count, uint32_t b, uint8_t *out) {
+RSN_HD_FN uint32_t plan_entry(uint32_t count, uint32_t b, uint8_t *out) {
     const uint32_t len = plan_entry_len(count, b);
     uint32_t at = len - (b == 10 ? 3u : 2u);
     for (uint32_t v = count;;) { out[--at] = (uint8_t)('0' + v % 10); v /= 10; if (!v) break; }
@@ -120,13 +116,13 @@ RSN_PLAN_FN uint32_t plan_entry(uint32_t count, uint32_t b, uint8_t *out) {
     return len;
 }
 // '\\' as the LAST entry makes the reference decoder index past the header (huffman.go:210): it goes first instead
-RSN_PLAN_FN bool plan_backslash_first(const uint32_t *cnt) {
+RSN_HD_FN bool plan_backslash_first(const uint32_t *cnt) {
     uint32_t hi = 0, a = 0;
     for (uint32_t b = 0; b < PLAN_SYMS_MAX; b++) if (cnt[b]) { hi = b; a++; }
     return a > 1 && hi == 0x5C;
 }
 // The whole header, serially: the entries, "\\\n" and the pad byte (huffman.go:245-255,312-318).  Returns its length.
-RSN_PLAN_FN uint32_t plan_header(const uint32_t *cnt, uint32_t total_bits, uint8_t *out) {
+RSN_HD_FN uint32_t plan_header(const uint32_t *cnt, uint32_t total_bits, uint8_t *out) {
     uint32_t at = 0;
     const bool bs = plan_backslash_first(cnt);
     if (bs) at += plan_entry(cnt[0x5C], 0x5C, out + at);

@@ -21,15 +21,15 @@
 //            item sized (a token iff 3 + digits(d) + digits(L) < L, lzss.go:143), and the tiles' first output bytes and the stream's
 //            length as the running sum.
 //   emit     k_lzss_tile_emit, a workgroup per tile: the tile's items into an LDS image that begins at the 16-byte unit its first byte
-//            lies in, whole units stored as they are, the first and the last unit -- shared with the neighbours -- byte by byte
-//            (lzt_tile_store).  No output byte is stored by two workgroups and what the slot held before does not matter.
-// The status word of a taken member is stored by the LAST of its tiles to finish the emit (a device-scope counter in the member's
-// scratch, zeroed by esc), behind a fence.  Nothing polls it: k_group_scatter reads it, on the same stream.  No workgroup waits for
-// another; every loop is bounded by the tile, the ring, the step cap or the tiles of a member.  Nothing a launch reads from scratch is
-// left from an earlier group: esc writes the table, the member's words and the stream, search every key below E, chain every offset.
+//            lies in, and the tile's own bytes out of it.
+// Ownership, the member's status word by the last of its tiles, the grid and the host form are the tiled classes' common shape (DESIGN
+// 4.7; tile_dev.h); the done-counter is zeroed by esc.  No workgroup waits for another; every loop is bounded by the tile, the ring,
+// the step cap or the tiles of a member.  Nothing a launch reads from scratch is left from an earlier group: esc writes the table, the
+// member's words and the stream, search every key below E, chain every offset.
 #include "group_run.h"
 #include "lzss_match.h"
 #include "lzss_tile_layout.h"
+#include "tile_dev.h"
 
 namespace rsn {
 namespace {
@@ -42,7 +42,6 @@ constexpr uint32_t T_STEP_CAP = 4096;             // eight-byte extension steps 
 constexpr uint32_t T_FC_BYTES = LZT_W_MAX + TILE + LZT_W_MAX + 64;   // the window, the tile, the look-ahead of the longest match, the loads' reach behind it
 constexpr uint32_t T_ESC_ROUND = 16 * TT;         // input bytes of a round of the escape pass
 constexpr uint32_t T_IMG = TILE + 64;             // the emit image: up to 15 bytes in front of the tile's first, its items, slack
-static_assert(LZSS_TILE_IN_MAX == LZT_IN_MAX && LZSS_TILE_E_MAX == LZT_E_MAX && LZSS_TILE_POS == LZT_TILE && LZSS_MID_IN_MAX == LZT_IN_MIN, "lzss_tile_layout.h states the same class");
 static_assert(TILE == 2 * TT, "two positions a thread");
 static_assert(T_RING >= LZT_W_MAX + TILE + TT && (T_RING & (T_RING - 1)) == 0, "a link is never overwritten while a walk may still read it");
 static_assert(T_FC_BYTES % 16 == 0 && T_FC_BYTES + T_RING * 4 + T_HEADS * 4 + 64 <= 80 * 1024, "static LDS of k_lzss_tile_search; two workgroups to a CU");
@@ -256,21 +255,10 @@ __global__ __launch_bounds__(TT) void k_lzss_tile_emit(const SmallMember *__rest
     }
     __syncthreads();
     // ---- the tile's own bytes out (sum == off1 - off0: chain sized the same items)
-    uint8_t *dst = base + m.out_off;
-    if (sum == off1 - off0 && off1 <= lzt_out_slot(n)) {
-        for (uint32_t u = tid; u0 + 16 * u < off1; u += TT) {
-            const LztStore st = lzt_tile_store(off0, off1, u);
-            if (st.whole) *reinterpret_cast<uint4 *>(dst + st.lo) = reinterpret_cast<const uint4 *>(s_out)[u];
-            else for (uint32_t x = st.lo; x < st.hi; x++) dst[x] = s_out[x - u0];
-        }
-    }
+    if (sum == off1 - off0 && off1 <= lzt_out_slot(n)) tile_store_out<TT>(base + m.out_off, s_out, u0, off0, off1);
     // ---- the member's word, by the last of its tiles to get here: every byte of the stream is then in place
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) {
-        const uint32_t done = __hip_atomic_fetch_add(&my[LZT_SCR_META + LZT_META_DONE], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (done + 1 == T) __hip_atomic_store(reinterpret_cast<uint32_t *>(base + m.status_off), total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (tile_finish(&my[LZT_SCR_META + LZT_META_DONE], T))
+        __hip_atomic_store(reinterpret_cast<uint32_t *>(base + m.status_off), total, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // the launches of a group of g members; gx: tiles of the largest member the call holds; scr_words: what the slot must hold
@@ -290,29 +278,24 @@ constexpr const char *TILE_WHAT = "lzss batch compress";
 bool tile_enc_takes(const uint8_t *, size_t n, int64_t window) {                  // (the length and the window alone: both forms)
     return lzt_takes(n, window);
 }
-size_t tile_in_bytes(size_t n) { return lzt_in_slot(n); }
 size_t tile_out_bytes(size_t n) { return lzt_out_slot((uint32_t)std::min<size_t>(n, LZSS_TILE_IN_MAX)); }
 
 // The device form: run_groups_dev's groups -- k_group_gather, the launches, k_group_scatter -- of up to LZSS_TILE_GROUP_BYTES of staging.
 // A member's scratch is less than four times its staging (its two slots hold 2 n bytes at least, lzss_tile_layout.h), so the slot that
 // holds the call's whole scratch, or four times a group's staging when that is less, holds every group's.
 int tile_enc_run_dev(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const rsn_dev_member *mem, int64_t window, const DevPlans *, std::vector<uint32_t> &answers) {
-    size_t n_max = 0, words = 0;
-    for (size_t i : idx) { n_max = std::max(n_max, (size_t)mem[i].n); words += lzt_scr_words((uint32_t)std::min<size_t>(mem[i].n, LZSS_TILE_IN_MAX)); }
-    const uint32_t gx = std::max(1u, lzt_tiles(lzt_e_cap((uint32_t)std::min<size_t>(n_max, LZSS_TILE_IN_MAX))));
+    size_t words = 0;
+    for (size_t i : idx) words += lzt_scr_words((uint32_t)std::min<size_t>(mem[i].n, LZSS_TILE_IN_MAX));
+    const uint32_t gx = grid_tiles_of_largest(idx, mem, LZSS_TILE_IN_MAX, [](uint32_t n) { return lzt_tiles(lzt_e_cap(n)); });
     const size_t scr_words = lzt_front_words((uint32_t)std::min(idx.size(), SMALL_GROUP_MAX)) + std::min(words, LZSS_TILE_GROUP_BYTES + lzt_scr_words(LZSS_TILE_IN_MAX));
-    return run_groups_dev(c, s, TILE_WHAT, idx, mem, [&](size_t k) { return tile_in_bytes(mem[idx[k]].n); }, [&](size_t k) { return tile_out_bytes(mem[idx[k]].n); },
+    return run_groups_dev(c, s, TILE_WHAT, idx, mem, [&](size_t k) { return lzt_in_slot(mem[idx[k]].n); }, [&](size_t k) { return tile_out_bytes(mem[idx[k]].n); },
         [&](hipStream_t s2, uint32_t g, const SmallMember *tab, uint8_t *base) { return tile_launch(c, s2, g, gx, scr_words, tab, base, window); }, answers, LZSS_TILE_GROUP_BYTES);
 }
 
-// The host form.  The kernels read a member's stream from scratch and store its result in pieces, so they never run on pinned host
-// memory: the members go through the device form above in runs (group_run.h: run_members_staged), as huff_big.hip's do.
+// The host form: the members through the device form above (the kernels read a member's stream from scratch: never out of pinned host memory).
 int tile_enc_run(Ctx &c, const std::vector<size_t> &idx, const uint8_t *const *ins, const size_t *lens, int64_t window,
                  const SmallTake &take, std::vector<size_t> &back, size_t *failed, std::vector<size_t> *back_runes) {
-    std::vector<RunItem> items;
-    for (size_t i : idx) items.push_back(RunItem{i, group_round16(lens[i]), tile_out_bytes(lens[i]), tile_out_bytes(lens[i])});
-    return run_members_staged<0>(c, TILE_WHAT, "%s: internal error: a stream of %u bytes in a slot of %zu", items,
-        [&](size_t k, size_t, size_t, const void *, uint8_t *, uint8_t *in) { memcpy(in, ins[idx[k]], lens[idx[k]]); return lens[idx[k]]; },
+    return run_members_copied(c, TILE_WHAT, "a stream", idx, ins, lens, tile_out_bytes,
         [&](hipStream_t s, const std::vector<size_t> &all, const rsn_dev_member *mem, std::vector<uint32_t> &answers) { return tile_enc_run_dev(c, s, all, mem, window, nullptr, answers); },
         take, back, failed, back_runes);
 }

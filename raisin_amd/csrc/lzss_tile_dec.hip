@@ -21,7 +21,7 @@
 //   finish   k_lzss_tile_dec_finish, a workgroup per member, its output tiles in order: every descriptor's byte is read from the image --
 //            its tile is one this workgroup has finished, so pointers of any reach are allowed -- and written back; the tile is unescaped
 //            (DecodeOpeningSymbols, lzss.go:391-406) with the 5C run's parity carried from tile to tile; the result goes to the output slot
-//            at the running offset, whole 16-byte units where it can (lzt_tile_store).  Between tiles: a barrier between a release and an
+//            at the running offset, whole 16-byte units where it can (tile_dev.h: tile_store_out).  Between tiles: a barrier between a release and an
 //            acquire fence of workgroup scope -- the image is read again by this workgroup alone, whose waves share one CU's cache.  The
 //            image is read with ordinary loads through a pointer that promises nothing.  The member's length goes into its status word
 //            last, as an agent-scope release.
@@ -33,6 +33,7 @@
 #include "lzss_dec_body.h"
 #include "lzss_match.h"
 #include "lzss_tile_dec_layout.h"
+#include "tile_dev.h"
 
 namespace rsn {
 namespace {
@@ -44,7 +45,6 @@ constexpr uint32_t D_IN_BYTES = LZTD_HALO + TILE + LZTD_HALO;   // the stream a 
 constexpr uint32_t D_COV_BYTES = TILE + 64;       // cover marks: the tile and a token's reach behind it
 constexpr uint32_t D_IMG = TILE + 64;             // the finish image: up to 15 bytes in front of the tile's first, its bytes, slack
 constexpr int D_ROUNDS = 13;                      // doublings of the pointer jumping: 2048 positions need 12 (k_lzss_mid_dec's count)
-static_assert(LZSS_TILE_DEC_IN_MAX == LZTD_IN_MAX && LZSS_TILE_DEC_OUT_MAX == LZTD_OUT_MAX && LZSS_TILE_POS == LZTD_TILE, "lzss_tile_dec_layout.h states the same class");
 static_assert(TILE == 2 * TT && LZTD_IN_TILES_MAX <= PT && D_IN_BYTES % 16 == 0 && LZTD_REACH + 1 <= 64, "two bytes a thread; a plan thread a stream tile");
 static_assert(15 + TILE <= D_IMG && D_IMG % 16 == 0, "the image holds the longest tile: unescaping never adds a byte");
 
@@ -229,11 +229,7 @@ __global__ __launch_bounds__(TT) void k_lzss_tile_dec_finish(const SmallMember *
         const uint32_t off0 = out_at, off1 = out_at + tot, u0 = lzt_image_first(off0);
         lzd_unesc_write(s_val, s0, q0, q1, before, s_res, off0 - u0 + at);
         __syncthreads();
-        for (uint32_t u = tid; u0 + 16 * u < off1; u += TT) {                     // (off1 <= E: inside the slot, lzss_dec_out_slot)
-            const LztStore st = lzt_tile_store(off0, off1, u);
-            if (st.whole) *reinterpret_cast<uint4 *>(dst + st.lo) = reinterpret_cast<const uint4 *>(s_res)[u];
-            else for (uint32_t x = st.lo; x < st.hi; x++) dst[x] = s_res[x - u0];
-        }
+        tile_store_out<TT>(dst, s_res, u0, off0, off1);                           // (off1 <= E: inside the slot, lzss_dec_out_slot)
         plain = s_last; out_at = off1;
         // ---- the tile is final.  Its bytes are read again by this workgroup alone, whose waves share the CU's cache: a release and an
         //      acquire at WORKGROUP scope around the barrier order every wave's stores of the tile before any wave's loads of the next.
@@ -247,9 +243,6 @@ __global__ __launch_bounds__(TT) void k_lzss_tile_dec_finish(const SmallMember *
 }
 
 constexpr const char *DEC_WHAT = "lzss batch decompress";
-size_t dec_in_bytes(size_t n) { return lzss_in_slot(n); }
-size_t dec_out_bytes() { return lzss_dec_out_slot(LZSS_TILE_DEC_OUT_MAX); }
-static_assert(lzss_in_slot(4097) == lztd_in_slot(4097) && lzss_dec_out_slot(LZSS_TILE_DEC_OUT_MAX) == lztd_out_slot(), "lzss_tile_dec_layout.h restates the slots");
 
 // the launches of a group of g members; members: how many the slot must hold
 int dec_launch(Ctx &c, hipStream_t s, uint32_t g, size_t members, const SmallMember *tab, uint8_t *base) {
@@ -268,8 +261,8 @@ int dec_launch(Ctx &c, hipStream_t s, uint32_t g, size_t members, const SmallMem
 // Every member's output slot is the class's largest, so a group holds at most LZSS_TILE_GROUP_BYTES / that slot members (one, where a
 // member alone is more), and its scratch is at most LZTD_SCR_PER_STAGING times its staging.
 int tile_dec_run_dev(Ctx &c, hipStream_t s, const std::vector<size_t> &idx, const rsn_dev_member *mem, std::vector<uint32_t> &answers) {
-    const size_t members = std::min(std::min(idx.size(), SMALL_GROUP_MAX), LZSS_TILE_GROUP_BYTES / dec_out_bytes() + 1);
-    return run_groups_dev(c, s, DEC_WHAT, idx, mem, [&](size_t k) { return dec_in_bytes(mem[idx[k]].n); }, [&](size_t) { return dec_out_bytes(); },
+    const size_t members = std::min(std::min(idx.size(), SMALL_GROUP_MAX), LZSS_TILE_GROUP_BYTES / lztd_out_slot() + 1);
+    return run_groups_dev(c, s, DEC_WHAT, idx, mem, [&](size_t k) { return lztd_in_slot(mem[idx[k]].n); }, [&](size_t) { return lztd_out_slot(); },
         [&](hipStream_t s2, uint32_t g, const SmallMember *tab, uint8_t *base) { return dec_launch(c, s2, g, members, tab, base); }, answers, LZSS_TILE_GROUP_BYTES);
 }
 
@@ -285,16 +278,13 @@ std::vector<size_t> dec_candidates(std::vector<size_t> &rest, Len len) {
 }
 
 // The two offers (codecs.h: BehindClass; pool REST, so `rest` is the pool itself).  The kernels read the stream in pieces and keep a
-// member's image in scratch, so they never run on pinned host memory: the host form goes through the device form in runs
-// (group_run.h: run_members_staged), as lzss_tile.hip's does.  What the kernels hand back stays in `rest`.
+// member's image in scratch, so they never run on pinned host memory: the host form goes through the device form (the tiled
+// classes' common shape).  What the kernels hand back stays in `rest`.
 int tile_dec_offer(Ctx &c, std::vector<size_t> &rest, std::vector<size_t> &, const uint8_t *const *ins, const size_t *lens, const SmallTake &take, size_t *failed) {
     std::vector<size_t> others = rest;                                    // (`rest` stays as it is when the run fails)
     const std::vector<size_t> idx = dec_candidates(others, [&](size_t i) { return lens[i]; });
     if (idx.empty()) return RSN_OK;
-    std::vector<RunItem> items;
-    for (size_t i : idx) items.push_back(RunItem{i, group_round16(lens[i]), dec_out_bytes(), dec_out_bytes()});
-    const int rc = run_members_staged<0>(c, DEC_WHAT, "%s: internal error: a result of %u bytes in a slot of %zu", items,
-        [&](size_t k, size_t, size_t, const void *, uint8_t *, uint8_t *in) { memcpy(in, ins[idx[k]], lens[idx[k]]); return lens[idx[k]]; },
+    const int rc = run_members_copied(c, DEC_WHAT, "a result", idx, ins, lens, [](size_t) { return lztd_out_slot(); },
         [&](hipStream_t s, const std::vector<size_t> &all, const rsn_dev_member *mem, std::vector<uint32_t> &answers) { return tile_dec_run_dev(c, s, all, mem, answers); },
         take, others, failed, nullptr);
     if (rc) return rc;

@@ -10,8 +10,7 @@
 //              output tile the stream tile and the offset inside that tile's output where it begins, the escaped image (a byte a
 //              position) and a descriptor a position (the earlier position it copies, LZTD_NONE: none).  LZTD_SCR_PER_STAGING times a
 //              member's staging holds it, whatever the member: lzss_tile_dec.hip sizes the slot by that;
-//   ownership  output tile t's bytes unescape to [off0, off1) of the result; lzt_tile_store (lzss_tile_layout.h) says which 16-byte unit
-//              goes out whole and which byte by byte, so every byte of the result is stored by exactly one tile.
+//   ownership  output tile t's bytes unescape to [off0, off1) of the result (the tiled classes' common shape).
 #pragma once
 
 #include <cstddef>
@@ -21,7 +20,7 @@
 
 namespace rsn {
 
-// (codecs.h: LZSS_TILE_DEC_IN_MAX / LZSS_TILE_DEC_OUT_MAX are these; lzss_tile_dec.hip asserts it)
+// the class's limits: codecs.h names them LZSS_TILE_DEC_IN_MAX / LZSS_TILE_DEC_OUT_MAX
 constexpr uint32_t LZTD_IN_MIN = 2048;                        // candidates are longer than the small decoder's cutoff
 constexpr uint32_t LZTD_IN_MAX = LZT_E_MAX;                   // bytes of stream
 constexpr uint32_t LZTD_OUT_MAX = LZT_E_MAX;                  // escaped bytes a stream may expand to
@@ -36,16 +35,13 @@ static_assert(LZTD_REACH <= LZTD_HALO && LZTD_HALO % 16 == 0 && LZTD_TILE % 16 =
 // the sum of the tiles' output counts, each clamped to LZTD_OUT_MAX + 1, is a word
 static_assert((unsigned long long)LZTD_IN_TILES_MAX * (LZTD_OUT_MAX + 1ull) < (1ull << 32), "the scan of the tiles' outputs does not overflow");
 
-LZT_FN bool lztd_candidate(size_t n) { return n > LZTD_IN_MIN && n <= LZTD_IN_MAX; }
-LZT_FN uint32_t lztd_tiles(uint32_t bytes) { return (bytes + LZTD_TILE - 1) / LZTD_TILE; }
-LZT_FN uint32_t lztd_tile_len(uint32_t bytes, uint32_t t) {                  // t < lztd_tiles(bytes)
-    const uint32_t lo = t * LZTD_TILE;
-    return bytes - lo < LZTD_TILE ? bytes - lo : LZTD_TILE;
-}
+RSN_HD_FN bool lztd_candidate(size_t n) { return n > LZTD_IN_MIN && n <= LZTD_IN_MAX; }
+RSN_HD_FN uint32_t lztd_tiles(uint32_t bytes) { return tile_count(bytes, LZTD_TILE); }
+RSN_HD_FN uint32_t lztd_tile_len(uint32_t bytes, uint32_t t) { return tile_len(bytes, LZTD_TILE, t); }   // t < lztd_tiles(bytes)
 
-// ---- the slots of a member in a group's staging (group_layout.h: lzss_in_slot, lzss_dec_out_slot, restated here without its include)
-constexpr size_t lztd_in_slot(size_t n) { return ((n + 15) & ~(size_t)15) + 32; }
-constexpr size_t lztd_out_slot() { return (size_t)LZTD_OUT_MAX + 16; }
+// ---- a member's slots (group_layout.h's): the input of its stream, the output the class's largest whatever the stream
+constexpr size_t lztd_in_slot(size_t n) { return lzss_in_slot(n); }
+constexpr size_t lztd_out_slot() { return lzss_dec_out_slot(LZTD_OUT_MAX); }
 
 // ---- a member's scratch, in words from the member's offset; every region begins at a multiple of four words
 constexpr uint32_t lztd_round4(uint32_t w) { return (w + 3) & ~3u; }
@@ -62,12 +58,12 @@ constexpr uint32_t LZTD_SCR_DESC = LZTD_SCR_IMG + (LZTD_OUT_MAX + LZTD_IMG_PAD) 
 constexpr uint32_t LZTD_SCR_WORDS = LZTD_SCR_DESC + lztd_round4(LZTD_OUT_MAX);
 constexpr uint32_t LZTD_SCR_PER_STAGING = 5;                  // a member's scratch is at most this many times its two slots
 static_assert((unsigned long long)LZTD_SCR_WORDS * 4 <= (unsigned long long)LZTD_SCR_PER_STAGING * (lztd_in_slot(LZTD_IN_MIN + 1) + lztd_out_slot()), "the multiple that sizes the slot");
-LZT_FN unsigned long long lztd_scr_at(uint32_t q) { return (unsigned long long)q * LZTD_SCR_WORDS; }
+RSN_HD_FN unsigned long long lztd_scr_at(uint32_t q) { return (unsigned long long)q * LZTD_SCR_WORDS; }
 
 // the output tile that holds the output byte `at`, and where stream tile t's output lies, from the tiles' first bytes: the plan launch
 // gives output tile o the LAST stream tile whose first byte is at or before the tile's (stream tiles that put out nothing share their
 // first byte with the next one that does)
-LZT_FN uint32_t lztd_entry_tile(const uint32_t *first, uint32_t tiles, uint32_t at) {   // first[0 .. tiles]: ascending, first[tiles] = E > at
+RSN_HD_FN uint32_t lztd_entry_tile(const uint32_t *first, uint32_t tiles, uint32_t at) {   // first[0 .. tiles]: ascending, first[tiles] = E > at
     uint32_t lo = 0, hi = tiles;                                                 // the last t with first[t] <= at
     while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (first[mid] <= at) lo = mid; else hi = mid; }
     return lo;

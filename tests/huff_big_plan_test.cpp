@@ -3,7 +3,8 @@
 //     tree, codes and header (huff_host.cpp), field by field, and what the plan refuses (huff_big_layout.h: big_plan_refuses);
 //   * the tiles, a member's scratch, the slot sizes and the tiles' bit offsets against naive loops;
 //   * the rule "a byte belongs to the tile its first bit lies in": every tile coded on its own, the way k_huff_big_emit does it, into a
-//     slot full of 0xAA -- the stream must equal the serial one, every byte stored once, nothing behind its end.
+//     slot full of 0xAA and stored by tile_store's units (tile_layout.h) -- the stream must equal the serial one, every byte stored once,
+//     nothing behind its end; some tile's first own byte must lie in the unit behind its image's first.
 // Built and run by tests/test_huff_big_host.py.  Modes:
 //   huff_big_plan_test [n_random]             all of the above; prints "ok <tables> <members>"
 //   huff_big_plan_test table b:c [b:c ...]    one table of counts; prints "max_len <l> header <h> refused <0|1>"
@@ -30,7 +31,7 @@ struct Arr {
 };
 constexpr uint32_t MID_IN_MAX = 65536;                                      // codecs.h: HUFF_MID_IN_MAX, where the class begins
 
-long long g_tables = 0, g_members = 0;
+long long g_tables = 0, g_members = 0, g_next_unit = 0;                     // (tiles whose first own byte lies in the unit behind the image's first)
 
 struct Plan { uint32_t a, max_len, total_bits, H; uint32_t tab[128]; uint8_t hdr[2048]; };
 
@@ -174,7 +175,7 @@ bool member_of(const std::vector<uint8_t> &in, const char *what) {
     memcpy(out.data(), p.hdr, p.H);
     for (uint32_t i = 0; i < p.H; i++) stored[i]++;
     for (uint32_t t = 0; t < T; t++) {
-        const uint32_t b0 = off[t], b1 = off[t + 1], u0 = (b0 >> 3) & ~15u, i0 = b0 - 8 * u0, i1 = b1 - 8 * u0;
+        const uint32_t b0 = off[t], b1 = off[t + 1], u0 = big_tile_origin(b0), i0 = b0 - 8 * u0, i1 = b1 - 8 * u0;
         std::vector<uint8_t> img((i1 + 7 + 24) / 8 + 8, 0);
         uint32_t q = i0;
         for (uint32_t i = t * BIGL_TILE; i < t * BIGL_TILE + big_tile_len(n, t); i++) { put_bits(img, q, p.tab[in[i]]); q += p.tab[in[i]] >> 24; }
@@ -188,8 +189,12 @@ bool member_of(const std::vector<uint8_t> &in, const char *what) {
             }
             if (q < stop) { printf("%s: tile %u cannot fill its last byte\n", what, t); return false; }
         }
-        const uint32_t lo = big_tile_first_byte(t, b0) - u0, hi = big_tile_end_byte(b1) - u0;
-        for (uint32_t x = lo; x < hi; x++) { out[u0 + x] = img[x]; stored[u0 + x]++; }
+        const uint32_t lo = big_tile_first_byte(t, b0), hi = big_tile_end_byte(b1);
+        if (lo >= u0 + 16) g_next_unit++;
+        for (uint32_t u = 0; u0 + 16 * u < hi; u++) {
+            const TileStore st = tile_store(u0, lo, hi, u);
+            for (uint32_t x = st.lo; x < st.hi; x++) { out[x] = img[x - u0]; stored[x]++; }
+        }
     }
     for (uint32_t i = 0; i < total; i++) if (out[i] != want[i] || stored[i] != 1) { printf("%s: byte %u of %u: %02x for %02x, stored %d times\n", what, i, total, out[i], want[i], stored[i]); return false; }
     for (uint32_t i = total; i < slot + 16; i++) if (out[i] != 0xAA || stored[i]) { printf("%s: byte %u behind the stream's %u was written\n", what, i, total); return false; }
@@ -305,6 +310,7 @@ int main(int argc, char **argv) {
         }
     }
     if (!member_of(draw(rng, BIGL_IN_MAX, wide, skew, false), "the largest member")) return 1;
+    if (g_next_unit == 0) { printf("no tile's first own byte lies in the unit behind its image's first\n"); return 1; }
     printf("ok %lld %lld\n", g_tables, g_members);
     return 0;
 }

@@ -1,6 +1,7 @@
 // The arithmetic of the tiled class of the LZSS compress batch (csrc/lzss_tile_layout.h) against a serial restatement, as a plain program
 // (tests/test_lzss_tile_host.py builds and runs it, also under the address and undefined-behaviour sanitizers):
-//   lzss_tile_layout_test            the member lengths at the tile edges: tiles, scratch, slots, the window's first position, and a stream
+//   lzss_tile_layout_test            tile_store (csrc/tile_layout.h) itself over every alignment of origin, first and last byte; then the
+//                                    member lengths at the tile edges: tiles, scratch, slots, the window's first position, and a stream
 //                                    stored tile by tile -- prints "ok <members> <bytes stored>"
 //   lzss_tile_layout_test takes N W  prints 1 when the class takes a member of N bytes at window W, else 0
 //   lzss_tile_layout_test constants  prints the header's constants, "NAME value" a line
@@ -41,6 +42,59 @@ static size_t store_once(const std::vector<uint32_t> &off, uint32_t n) {
     }
     for (uint32_t x = 0; x < slot; x++) CHECK(hit[x] == (x < total ? 1 : 0), "n %u: byte %u of %u stored %u times", n, x, total, hit[x]);
     return total;
+}
+
+// ---- tile_store itself.  One tile: the units a workgroup walks (tile_dev.h: tile_store_out's loop, origin + 16 u < hi) store exactly
+// [lo, hi), every byte once; a unit inside the range goes out whole, and only the range's first and last unit go byte by byte.
+static uint32_t one_tile(uint32_t origin, uint32_t lo, uint32_t hi, std::vector<uint8_t> &hit) {
+    uint32_t partial = 0, u = 0;
+    for (; origin + 16 * u < hi; u++) {
+        const TileStore s = tile_store(origin, lo, hi, u);
+        const uint32_t x0 = origin + 16 * u, x1 = x0 + 16;
+        CHECK(s.lo <= s.hi, "origin %u [%u, %u) unit %u", origin, lo, hi, u);
+        if (s.lo < s.hi) CHECK(s.lo >= lo && s.hi <= hi && s.lo >= x0 && s.hi <= x1, "origin %u [%u, %u) unit %u: [%u, %u)", origin, lo, hi, u, s.lo, s.hi);
+        CHECK(s.whole == (x0 >= lo && x1 <= hi), "origin %u [%u, %u) unit %u: whole", origin, lo, hi, u);
+        if (s.whole) CHECK(s.lo == x0 && s.hi == x1 && x0 % 16 == 0, "origin %u [%u, %u) unit %u: a whole unit", origin, lo, hi, u);
+        else if (s.lo < s.hi) partial++;
+        for (uint32_t x = s.lo; x < s.hi; x++) hit[x]++;
+    }
+    CHECK(partial <= 2, "origin %u [%u, %u): %u units byte by byte", origin, lo, hi, partial);
+    for (uint32_t k = 0; k < 3; k++) {                                           // (the units behind the walk hold nothing of the range)
+        const TileStore s = tile_store(origin, lo, hi, u + k);
+        CHECK(s.lo == s.hi && !s.whole, "origin %u [%u, %u) unit %u behind the range", origin, lo, hi, u + k);
+    }
+    return hi - lo;
+}
+static size_t store_sweep() {
+    size_t ranges = 0;
+    std::vector<uint8_t> hit(256, 0);
+    // origins of several units; lo from the origin to two units behind it -- lo in the NEXT unit is huff_big.hip's tile whose first bit
+    // lies in a unit's last byte: unit 0 stores nothing -- and hi from lo (an empty range) over every alignment to three units on
+    for (uint32_t origin = 0; origin <= 48; origin += 16)
+        for (uint32_t lo = origin; lo <= origin + 32; lo++)
+            for (uint32_t hi = lo; hi <= lo + 56; hi++) {
+                std::fill(hit.begin(), hit.end(), 0);
+                one_tile(origin, lo, hi, hit);
+                for (uint32_t x = 0; x < hit.size(); x++) CHECK(hit[x] == (x >= lo && x < hi ? 1 : 0), "origin %u [%u, %u): byte %u stored %u times", origin, lo, hi, x, hit[x]);
+                if (lo >= origin + 16) { const TileStore s = tile_store(origin, lo, hi, 0); CHECK(s.lo == s.hi && !s.whole, "origin %u [%u, %u): unit 0 stores nothing", origin, lo, hi); }
+                ranges++;
+            }
+    // three tiles side by side, the cuts b and c at every alignment two units to either side (b == c: the middle tile is empty); a tile's
+    // image begins at the unit of its first byte (back == 0: the LZSS classes) or of the byte in front of it (back == 1: huff_big.hip's
+    // tile whose first bit lies inside the byte before its first own byte).  No byte twice, none left out, none outside.
+    const uint32_t a = 5, d = 160;
+    for (uint32_t b = 32 - 2; b <= 96 + 2; b++)
+        for (uint32_t c = b; c <= 128 + 2; c++)
+            for (uint32_t back = 0; back < 2; back++) {
+                std::fill(hit.begin(), hit.end(), 0);
+                const uint32_t cut[4] = {a, b, c, d};
+                for (uint32_t t = 0; t < 3; t++) one_tile(tile_origin(cut[t] - (t ? back : 0)), cut[t], cut[t + 1], hit);
+                for (uint32_t x = 0; x < hit.size(); x++) CHECK(hit[x] == (x >= a && x < d ? 1 : 0), "cuts %u %u back %u: byte %u stored %u times", b, c, back, x, hit[x]);
+                ranges++;
+            }
+    CHECK(tile_origin(0) == 0 && tile_origin(15) == 0 && tile_origin(16) == 16 && tile_origin(0xFFFFFFFFu) == 0xFFFFFFF0u, "the unit an offset lies in");
+    CHECK(tile_count(1, 16) == 1 && tile_count(16, 16) == 1 && tile_count(17, 16) == 2 && tile_len(17, 16, 0) == 16 && tile_len(17, 16, 1) == 1 && tile_len(32, 16, 1) == 16, "tiles of any size");
+    return ranges;
 }
 
 static size_t member(uint32_t n, uint32_t e) {
@@ -95,6 +149,7 @@ int main(int argc, char **argv) {
         return 0;
     }
     size_t members = 0, bytes = 0;
+    CHECK(store_sweep() > 10000, "the sweep of tile_store");
     std::vector<uint32_t> lens = {LZT_IN_MIN + 1, LZT_IN_MAX - 1, LZT_IN_MAX};
     for (uint32_t k = LZT_IN_MIN / LZT_TILE; k * LZT_TILE <= LZT_IN_MAX; k++)
         for (int d = -1; d <= 1; d++) lens.push_back(k * LZT_TILE + d);

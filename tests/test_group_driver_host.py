@@ -47,9 +47,11 @@ def test_the_drivers_go_by_the_headers_under_test():
     # ... the one run takes its cut, its offsets and `down` from the first, and both tiled classes go through that run
     runner = open(os.path.join(SRC, "group_run.h")).read()
     assert '#include "group_layout.h"' in runner and "run_need(" in runner and "RunLayout " in runner and "run_down(" in runner
-    for unit in ("huff_big.hip", "huff_big_dec.hip"):
+    # (the decoder, which packs a plan table, by its own call; the classes whose input goes up as it is through run_members_copied, its one user)
+    assert runner.count("run_members_staged<") == 1 and runner.count("return run_members_staged<0>(") == 1 and runner.count("int run_members_copied(") == 1
+    for unit, call in (("huff_big.hip", "run_members_copied("), ("huff_big_dec.hip", "run_members_staged<"), ("lzss_tile.hip", "run_members_copied("), ("lzss_tile_dec.hip", "run_members_copied(")):
         text = open(os.path.join(SRC, unit)).read()
-        assert text.count("run_members_staged<") == 1 and "STAGE_IN" not in text and "next_group(" not in text, unit
+        assert text.count(call) == 1 and text.count("run_members_staged<") + text.count("run_members_copied(") == 1 and "STAGE_IN" not in text and "next_group(" not in text, unit
     # ... and both forms of both offers choose through the second: the flows hold no selection of their own
     enc, dec = (open(os.path.join(SRC, u)).read() for u in ("huff_rune.hip", "huff_rune_dec.hip"))
     assert enc.count("rune_class_members(") == 2

@@ -3,7 +3,7 @@ header against naive loops; the wide form of the stream plan against the host's 
 262143 and sums of 262144 and 262145, the narrow form refusing what it refused; a model of the three phases -- every tile's map from all
 32 entries, the maps chained, every tile emitted from its entry -- byte for byte against the serial decoder on whole members
 (tests/huff_big_dec_plan_test.cpp, also under the address and undefined-behaviour sanitizers as a plain program); and the constants of
-csrc/codecs.h and csrc/huff_big_dec_layout.h against their mirrors in raisin_amd/huffman.py.  Runs on any machine."""
+csrc/huff_big_dec_layout.h, their one home, and of csrc/codecs.h against their mirrors in raisin_amd/huffman.py.  Runs on any machine."""
 import os
 import re
 import shutil
@@ -47,19 +47,27 @@ def test_the_same_under_the_sanitizers(tmp_path_factory):
     assert _run(exe)[2] == 9
 
 
-def _constants(path, names):
+def _texts(path, names):
     src = open(os.path.join(SRC, path)).read()
     out = {}
     for name in names:
         m = re.search(r"constexpr\s+\w+\s+%s\s*=\s*([^;]+);" % name, src)
         assert m, name
-        out[name] = int(eval(m.group(1).replace("u", ""), {}))
+        out[name] = m.group(1).strip()
     return out
+
+
+def _constants(path, names):
+    return {k: int(eval(v.replace("u", ""), {})) for k, v in _texts(path, names).items()}
 
 
 def test_mirrored_constants_are_the_headers():
     from raisin_amd import huffman
-    h = _constants("codecs.h", ["HUFF_BIG_OUT_MAX", "HUFF_BIG_PAY_MAX", "HUFF_BIG_DEC_GROUP_MIN", "HUFF_BIG_IN_MAX", "HUFF_MID_OUT_MAX", "HUFF_BIG_GROUP_BYTES"])
+    # the classes' limits are stated in the layout headers alone; codecs.h names them
+    assert _texts("codecs.h", ["HUFF_BIG_OUT_MAX", "HUFF_BIG_PAY_MAX", "HUFF_BIG_IN_MAX"]) == {"HUFF_BIG_OUT_MAX": "BIGD_OUT_MAX", "HUFF_BIG_PAY_MAX": "BIGD_PAY_MAX", "HUFF_BIG_IN_MAX": "BIGL_IN_MAX"}
+    h = _constants("codecs.h", ["HUFF_BIG_DEC_GROUP_MIN", "HUFF_MID_OUT_MAX", "HUFF_BIG_GROUP_BYTES"])
+    h.update({"HUFF_BIG_" + k[5:]: v for k, v in _constants("huff_big_dec_layout.h", ["BIGD_OUT_MAX", "BIGD_PAY_MAX"]).items()})
+    h["HUFF_BIG_IN_MAX"] = _constants("huff_big_layout.h", ["BIGL_IN_MAX"])["BIGL_IN_MAX"]
     assert (huffman.BIG_OUT_MAX, huffman.BIG_PAY_MAX, huffman.BIG_DEC_GROUP_MIN) == (h["HUFF_BIG_OUT_MAX"], h["HUFF_BIG_PAY_MAX"], h["HUFF_BIG_DEC_GROUP_MIN"])
     assert huffman.MID_OUT_MAX == h["HUFF_MID_OUT_MAX"] < huffman.BIG_OUT_MAX and huffman.BIG_GROUP_BYTES == h["HUFF_BIG_GROUP_BYTES"]
     lay = _constants("huff_big_dec_layout.h", ["BIGD_OUT_MAX", "BIGD_PAY_MAX", "BIGD_LANES", "BIGD_S", "BIGD_OUT_CAP"])

@@ -2,7 +2,7 @@
 class's counts against the host's Go-exact tree, codes and header; what the plan refuses (a code beyond 24 bits, a header beyond its
 derived bound); the tiles, the scratch, the slots and the tiles' bit offsets against naive loops; a member coded tile by tile against the
 serial stream (tests/huff_big_plan_test.cpp, also under the address and undefined-behaviour sanitizers as a plain program); and the
-constants of csrc/codecs.h against their mirrors in raisin_amd/huffman.py.  Runs on any machine."""
+constants of csrc/huff_big_layout.h, their one home, and of csrc/codecs.h against their mirrors in raisin_amd/huffman.py.  Runs on any machine."""
 import os
 import re
 import shutil
@@ -30,14 +30,18 @@ def plan_test(tmp_path_factory):
     return _build(tmp_path_factory, "huff_big_plan_test", ["-O2"])
 
 
-def _constants(path, names):
+def _texts(path, names):
     src = open(os.path.join(SRC, path)).read()
     out = {}
     for name in names:
         m = re.search(r"constexpr\s+\w+\s+%s\s*=\s*([^;]+);" % name, src)
         assert m, name
-        out[name] = int(eval(m.group(1).replace("u", ""), {}))              # (a number, or 1u << 20)
+        out[name] = m.group(1).strip()
     return out
+
+
+def _constants(path, names):
+    return {k: int(eval(v.replace("u", ""), {})) for k, v in _texts(path, names).items()}   # (a number, or 1u << 20)
 
 
 def test_plan_layout_and_tiled_members(plan_test):
@@ -110,13 +114,14 @@ def test_the_header_bound_is_reached_and_not_exceeded(plan_test):
 
 def test_mirrored_constants_are_the_headers():
     from raisin_amd import huffman
-    h = _constants("codecs.h", ["HUFF_BIG_IN_MAX", "HUFF_BIG_TILE", "HUFF_BIG_GROUP_MIN", "HUFF_BIG_GROUP_BYTES", "HUFF_MID_IN_MAX"])
+    # the class's limits are stated in the layout header alone; codecs.h names them
+    assert _texts("codecs.h", ["HUFF_BIG_IN_MAX", "HUFF_BIG_TILE"]) == {"HUFF_BIG_IN_MAX": "BIGL_IN_MAX", "HUFF_BIG_TILE": "BIGL_TILE"}
+    h = _constants("codecs.h", ["HUFF_BIG_GROUP_MIN", "HUFF_BIG_GROUP_BYTES", "HUFF_MID_IN_MAX"])
+    h.update({"HUFF_BIG_" + k[5:]: v for k, v in _constants("huff_big_layout.h", ["BIGL_IN_MAX", "BIGL_TILE"]).items()})
     assert huffman.BIG_IN_MAX == h["HUFF_BIG_IN_MAX"]
     assert huffman.BIG_TILE == h["HUFF_BIG_TILE"]
     assert huffman.BIG_GROUP_MIN == h["HUFF_BIG_GROUP_MIN"]
     assert huffman.BIG_GROUP_BYTES == h["HUFF_BIG_GROUP_BYTES"]
-    lay = _constants("huff_big_layout.h", ["BIGL_IN_MAX", "BIGL_TILE"])
-    assert (lay["BIGL_IN_MAX"], lay["BIGL_TILE"]) == (h["HUFF_BIG_IN_MAX"], h["HUFF_BIG_TILE"])
     assert huffman.MID_IN_MAX == h["HUFF_MID_IN_MAX"] < huffman.BIG_IN_MAX
     assert huffman.BIG_IN_MAX % huffman.BIG_TILE == 0 and huffman.BIG_GROUP_MIN >= 4
     assert (huffman.BIG_IN_MAX << 8) < 1 << 32                                # a count and a node id in one word

@@ -44,6 +44,11 @@ def test_the_header_compiles_for_the_device_too():
     text = open(os.path.join(SRC, "huff_parse_small.h")).read()
     includes = [line.split()[1] for line in text.splitlines() if line.startswith("#include")]
     assert includes == ['"huff_plan_small.h"'], includes                # no HIP include on the host side
-    assert "RSN_PLAN_FN" in text and "__host__ __device__" in open(os.path.join(SRC, "huff_plan_small.h")).read()
+    # the qualifier is tile_layout.h's, the one every plain-code header uses, which huff_plan_small.h includes and nothing else
+    plan = open(os.path.join(SRC, "huff_plan_small.h")).read()
+    assert [line.split()[1] for line in plan.splitlines() if line.startswith("#include")] == ["<cstdint>", '"tile_layout.h"']
+    shared = open(os.path.join(SRC, "tile_layout.h")).read()
+    assert "RSN_HD_FN" in text and "#define RSN_HD_FN __host__ __device__" in shared
+    assert [line.split()[1] for line in shared.splitlines() if line.startswith("#include")] == ["<cstdint>"]
     kernel = open(os.path.join(SRC, "huff_dev.hip")).read()
     assert '#include "huff_parse_small.h"' in kernel and "parse_scan(" in kernel and "plan_tree(" in kernel

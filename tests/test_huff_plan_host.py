@@ -29,6 +29,9 @@ def test_planner_equals_host_on_tie_heavy_and_random_tables(planner_test):
 
 def test_planner_header_compiles_for_the_device_too():
     # the kernel includes the same header (huff_small.hip); the host half of it must not need the device compiler
+    # (the qualifier that says so is tile_layout.h's RSN_HD_FN, the one every plain-code header uses)
     text = open(os.path.join(SRC, "huff_plan_small.h")).read()
-    assert "__host__ __device__" in text and "#ifdef __HIPCC__" in text
+    shared = open(os.path.join(SRC, "tile_layout.h")).read()
+    assert '#include "tile_layout.h"' in text and "RSN_HD_FN" in text and "__HIPCC__" not in text
+    assert "#if defined(__HIPCC__)\n#define RSN_HD_FN __host__ __device__" in shared and "#else\n#define RSN_HD_FN inline\n#endif" in shared
     assert '#include "huff_plan_small.h"' in open(os.path.join(SRC, "huff_small.hip")).read()

@@ -1,7 +1,7 @@
 """The tiled class of the LZSS decompress batch (csrc/lzss_tile_dec.hip) as far as it shows without a device: the tiles of
 the stream and of the output, the entries of the output tiles, the scratch and which tile stores which byte against a serial restatement
 (tests/lzss_tile_dec_layout_test.cpp, also under the address and undefined-behaviour sanitizers as a plain program); the constants of
-csrc/codecs.h and csrc/lzss_tile_dec_layout.h against their mirrors in raisin_amd/lz.py; the closure over the tiled encoder's caps; where
+csrc/lzss_tile_dec_layout.h, their one home, and the names csrc/codecs.h gives them against their mirrors in raisin_amd/lz.py; the closure over the tiled encoder's caps; where
 the class sits in the routing.  Runs on any machine."""
 import os
 import re
@@ -62,7 +62,9 @@ def test_the_same_under_the_sanitizers(tmp_path_factory):
 
 def test_mirrored_constants_are_the_headers(layout_test):
     from raisin_amd import lz
-    assert _constant("codecs.h", "LZSS_TILE_DEC_IN_MAX") == "LZSS_TILE_E_MAX" and _constant("codecs.h", "LZSS_TILE_DEC_OUT_MAX") == "LZSS_TILE_E_MAX"
+    assert _constant("codecs.h", "LZSS_TILE_DEC_IN_MAX") == "LZTD_IN_MAX" and _constant("codecs.h", "LZSS_TILE_DEC_OUT_MAX") == "LZTD_OUT_MAX"
+    assert _constant("lzss_tile_dec_layout.h", "LZTD_IN_MAX") == "LZT_E_MAX" and _constant("lzss_tile_dec_layout.h", "LZTD_OUT_MAX") == "LZT_E_MAX"
+    assert _constant("codecs.h", "LZSS_TILE_E_MAX") == "LZT_E_MAX"
     assert lz.TILE_DEC_IN_MAX == lz.TILE_DEC_OUT_MAX == lz.TILE_E_MAX
     m = re.search(r"#ifndef RSN_LZSS_TILE_DEC_GROUP_MIN\n#define RSN_LZSS_TILE_DEC_GROUP_MIN (\d+)\n#endif", open(os.path.join(SRC, "codecs.h")).read())
     assert m and lz.TILE_DEC_GROUP_MIN == int(m.group(1)) >= 2 and _constant("codecs.h", "LZSS_TILE_DEC_GROUP_MIN") == "RSN_LZSS_TILE_DEC_GROUP_MIN"

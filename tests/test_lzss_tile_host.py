@@ -1,7 +1,8 @@
 """The tiled class of the LZSS compress batch (csrc/lzss_tile.hip) as far as it shows without a device: the tiles, the
 scratch, the slots, the window's first position and which tile stores which byte against a serial restatement
-(tests/lzss_tile_layout_test.cpp, also under the address and undefined-behaviour sanitizers as a plain program); the constants of
-csrc/codecs.h and csrc/lzss_tile_layout.h against their mirrors in raisin_amd/lz.py; what the class takes.  Runs on any machine."""
+(tests/lzss_tile_layout_test.cpp, which sweeps csrc/tile_layout.h's tile_store first; also under the address and undefined-behaviour
+sanitizers as a plain program); the constants of csrc/lzss_tile_layout.h, their one home, and the names csrc/codecs.h gives them against
+their mirrors in raisin_amd/lz.py; what the class takes.  Runs on any machine."""
 import os
 import re
 import shutil
@@ -62,13 +63,16 @@ def _constant(path, name):
 
 def test_mirrored_constants_are_the_headers(layout_test):
     from raisin_amd import lz
-    assert lz.TILE_IN_MAX == _defined("codecs.h", "RSN_LZSS_TILE_IN_MAX") == _defined("lzss_tile_layout.h", "RSN_LZSS_TILE_IN_MAX")
+    # the class's limits are stated in the layout header alone; codecs.h names them
+    assert lz.TILE_IN_MAX == _defined("lzss_tile_layout.h", "RSN_LZSS_TILE_IN_MAX")
+    assert "#define RSN_LZSS_TILE_IN_MAX" not in open(os.path.join(SRC, "codecs.h")).read()
     assert lz.TILE_GROUP_MIN == _defined("codecs.h", "RSN_LZSS_TILE_GROUP_MIN") >= 2
-    assert _constant("codecs.h", "LZSS_TILE_IN_MAX") == "RSN_LZSS_TILE_IN_MAX" and _constant("codecs.h", "LZSS_TILE_GROUP_MIN") == "RSN_LZSS_TILE_GROUP_MIN"
-    assert _constant("codecs.h", "LZSS_TILE_E_MAX") == "LZSS_TILE_IN_MAX + LZSS_TILE_IN_MAX / 16"
+    assert _constant("codecs.h", "LZSS_TILE_IN_MAX") == "LZT_IN_MAX" and _constant("lzss_tile_layout.h", "LZT_IN_MAX") == "RSN_LZSS_TILE_IN_MAX"
+    assert _constant("codecs.h", "LZSS_TILE_GROUP_MIN") == "RSN_LZSS_TILE_GROUP_MIN"
+    assert _constant("codecs.h", "LZSS_TILE_E_MAX") == "LZT_E_MAX" and _constant("lzss_tile_layout.h", "LZT_E_MAX") == "LZT_IN_MAX + LZT_IN_MAX / 16"
     assert lz.TILE_E_MAX == lz.TILE_IN_MAX + lz.TILE_IN_MAX // 16             # the mid class's proportion
     assert lz.MID_E_MAX == lz.MID_IN_MAX + lz.MID_IN_MAX // 16
-    assert lz.TILE_POS == int(_constant("codecs.h", "LZSS_TILE_POS")) == 2048
+    assert _constant("codecs.h", "LZSS_TILE_POS") == "LZT_TILE" and lz.TILE_POS == int(_constant("lzss_tile_layout.h", "LZT_TILE")) == 2048
     assert lz.TILE_GROUP_BYTES == int(_constant("codecs.h", "LZSS_TILE_GROUP_BYTES"))
     r = subprocess.run([layout_test, "constants"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -78,7 +82,7 @@ def test_mirrored_constants_are_the_headers(layout_test):
     assert lay["LZT_TILES_MAX"] * lz.TILE_POS >= lz.TILE_E_MAX > (lay["LZT_TILES_MAX"] - 1) * lz.TILE_POS
     assert lz.TILE_E_MAX < 1 << 31 and lay["LZT_W_MAX"] < 1 << 15             # a key is L << 16 | distance, its top bit the chain's mark
     src = open(os.path.join(SRC, "Makefile")).read()
-    assert "lzss_tile.hip" in src and "lzss_tile_layout.h" in src
+    assert "lzss_tile.hip" in src and "lzss_tile_layout.h" in src and "tile_layout.h tile_dev.h" in src
 
 
 def test_what_the_class_takes(layout_test):
