@@ -767,10 +767,11 @@ __global__ __launch_bounds__(HB) void k_emit_ascii32(EmitArgs a) {
 // ---------------------------------------------------------------- K5f: emit, flat code
 // Every code has the same length L (balanced tree: alphabets of 2^L near-equal symbols,
 // config 2a).  Bit offsets are arithmetic: no per-tile bit counts, no scan, no LDS bit window.
-// A lane packs 32 symbols into exactly L words with compile-time field positions; the
-// stream's start phase (base_bits % 32) is one block-uniform funnel shift against the last
-// word of the lane before.  Every output word has ONE owner (plain stores); only the word
-// that also holds header bytes is merged with atomicOr.
+// A lane packs 32 symbols into exactly L words with compile-time field positions and leaves
+// them unshifted in LDS; the stream's start phase (base_bits % 32) is one block-uniform funnel
+// shift of two neighbouring words in the drain.  Two block barriers: behind the table's staging
+// and in front of the drain.  Every output word has ONE owner (plain stores); the word that
+// also holds header bytes is merged in registers by that owner.
 constexpr int FE_INLINE = 128 + 2304;    // code table + header carried in the kernel-argument segment (no upload, no extra stream op)
 struct FlatEmitArgs {
     const uint8_t *in; size_t n;
@@ -786,17 +787,16 @@ constexpr int FE_SYMS = HB * FE_SPL;     // symbols per block
 template <int L>
 __global__ __launch_bounds__(HB) void k_emit_flat(FlatEmitArgs a) {
     __shared__ uint32_t s_code[128 * 32];                         // 32 dword copies per symbol: the copy index IS the bank
-    __shared__ uint32_t s_o[HB * L + HB * L / 32 + 2];            // block's output words (swizzled), drained coalesced
-    __shared__ uint32_t s_last[HB / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    constexpr int SO = HB * L + 1;                                // slot 0: the word in front of the chunk; slot 1 + i: the chunk's word i
+    __shared__ uint32_t s_o[SO + SO / 32 + 2];                    // unshifted words (swizzled); the drain shifts them and stores coalesced
+    const int tid = threadIdx.x;
     // (through the kernel-argument segment pointer: indexing the by-value copy would spill it to scratch)
     const uint8_t *tab = a.codes ? a.codes : (const uint8_t *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(FlatEmitArgs, inl);
     const uint32_t rep = tid & 31;
-    // A block takes ONE chunk (the launch gives every chunk a block; the loop only serves a launch with fewer blocks), so the table is
-    // staged per chunk and has to be cheap: a group of 32 lanes takes 16 symbols' codes with four dword loads, issued behind the
-    // chunk's own loads so that both are in flight together.
+    // A block takes ONE chunk (every launch gives every chunk a block), so the table is staged per chunk and has to be
+    // cheap: a group of 32 lanes takes 16 symbols' codes with four dword loads, issued behind the chunk's own loads so that both are
+    // in flight together.
     static_assert(HB == 256 && offsetof(FlatEmitArgs, inl) % 4 == 0, "eight groups of 32 lanes, dword loads of the table");
-    bool staged = false;
     auto stage = [&]() {
         const int g = tid >> 5;
         const uint32_t *t4 = reinterpret_cast<const uint32_t *>(tab) + g * 4;
@@ -805,10 +805,9 @@ __global__ __launch_bounds__(HB) void k_emit_flat(FlatEmitArgs a) {
         for (int j = 0; j < 4; j++) x[j] = t4[j];
 #pragma unroll
         for (int j = 0; j < 16; j++) s_code[((g * 16 + j) << 5) | rep] = (x[j >> 2] >> (8 * (j & 3))) & 0xFF;
-        staged = true;
     };
     const uint32_t n_chunks = (uint32_t)((a.n + FE_SYMS - 1) / FE_SYMS);
-    for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+    const uint32_t chunk = blockIdx.x;                            // (the grid IS the chunk count)
     const size_t s0 = (size_t)chunk * FE_SYMS + (size_t)tid * FE_SPL;
     auto load32 = [&](size_t first, uint32_t *w) {                // the 32 symbols at `first`, zeros past the end of the input
         if (first + 32 <= a.n) {
@@ -836,49 +835,75 @@ __global__ __launch_bounds__(HB) void k_emit_flat(FlatEmitArgs a) {
             else { v[wi] |= code >> (sh + L - 32); v[wi + 1 < L ? wi + 1 : wi] |= code << (64 - sh - L); }
         }
     };
-    uint32_t v[L], w[8];
+    // The words in front of the chunk end in the last word of the chunk before (chunks are whole multiples of 32 symbols).  Only its low
+    // o0 bits reach this chunk's first word, and only its last LB_SYMS symbols lie in that word: lane 0 loads the LB_BYTES that hold
+    // them WITH the chunk's own loads and looks them up behind the staging barrier.  Nothing is loaded in front of the first chunk
+    // (header bytes, merged below) or at phase 0.
+    constexpr int LB_FIRST = 32 * (L - 1) / L, LB_SYMS = 32 - LB_FIRST, LB_BYTES = LB_SYMS <= 8 ? 8 : LB_SYMS <= 16 ? 16 : 32;
+    const uint32_t o0 = (uint32_t)(a.base_bits & 31);
+    const bool look_back = tid == 0 && chunk > 0 && o0 != 0;
+    uint32_t v[L], w[8], pb[LB_BYTES / 4];
     if (s0 < a.n) load32(s0, w);
-    if (!staged) { stage(); __syncthreads(); }
+    if (look_back) {
+        if constexpr (LB_BYTES == 8) {
+            const uint2 x = *reinterpret_cast<const uint2 *>(a.in + s0 - 8);
+            pb[0] = x.x; pb[1] = x.y;
+        } else {
+#pragma unroll
+            for (int q = 0; q < LB_BYTES / 16; q++) {
+                const uint4 x = ld16<(RSN_NT_MASK & 2) != 0>(reinterpret_cast<const uint4 *>(a.in + s0 - LB_BYTES) + q);
+                pb[4 * q] = x.x; pb[4 * q + 1] = x.y; pb[4 * q + 2] = x.z; pb[4 * q + 3] = x.w;
+            }
+        }
+    }
+    stage();
+    __syncthreads();
     if (s0 < a.n) pack32(s0, w, v);
     else {
 #pragma unroll
         for (int j = 0; j < L; j++) v[j] = 0;
     }
-    // last word of the previous lane's group: DPP inside the wavefront, LDS across wavefronts,
-    // recomputed from the input across blocks
-    uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v[L - 1], 0x138, 0xF, 0xF, false);   // wave_shr:1
-    if (lane == 63) s_last[wv] = v[L - 1];
-    __syncthreads();
-    if (lane == 0) {
-        if (wv > 0) prev = s_last[wv - 1];
-        else if (chunk > 0) { uint32_t pw[8], pv[L]; load32(s0 - 32, pw); pack32(s0 - 32, pw, pv); prev = pv[L - 1]; }
-        else prev = 0;                                            // in front of the stream: header bytes, merged below
+    if (tid == 0) {
+        uint32_t prev = 0;
+        if (look_back) {
+#pragma unroll
+            for (int k = LB_FIRST; k < 32; k++) {                 // symbol k of the 32 in front of the chunk: the fields of pack32 that meet word L - 1
+                constexpr int AT = 32 - LB_BYTES;
+                const uint32_t code = s_code[(((pb[(k - AT) >> 2] >> (8 * ((k - AT) & 3))) & 0x7F) << 5) | rep];
+                const int bp = k * L, wi = bp >> 5, sh = bp & 31;
+                if (wi == L - 1) prev |= code << (32 - sh - L);
+                else prev |= code << (64 - sh - L);               // (the field starts in word L - 2)
+            }
+        }
+        s_o[0] = prev;
     }
-    const uint32_t o0 = (uint32_t)(a.base_bits & 31);
 #pragma unroll
     for (int j = 0; j < L; j++) {
-        const uint32_t hi = j ? v[j - 1] : prev;
-        const uint32_t ow = (uint32_t)((((unsigned long long)hi << 32) | v[j]) >> o0);   // (hi << (32-o0)) | (v[j] >> o0)
-        const uint32_t i = tid * L + j;
-        s_o[i + (i >> 5)] = __builtin_bswap32(ow);
+        const uint32_t i = 1 + tid * L + j;
+        s_o[i + (i >> 5)] = v[j];
     }
     __syncthreads();
-    // drain: the block's HB*L words are contiguous in the output
+    // drain: the block's HB*L words are contiguous in the output.  Output word i is slots i and i + 1 funnel-shifted by the stream's
+    // phase: (slot[i] << (32 - o0)) | (slot[i + 1] >> o0)
+    auto slot = [&](uint32_t i) { return s_o[i + (i >> 5)]; };
+    auto out_word = [&](uint32_t hi, uint32_t lo) { return __builtin_bswap32((uint32_t)((((unsigned long long)hi << 32) | lo) >> o0)); };
     const unsigned long long total_syms = a.n;
     const unsigned long long wbase = (a.base_bits >> 5) + (unsigned long long)chunk * (HB * L);
     const unsigned long long end_word = (a.base_bits + total_syms * L + 31) >> 5;                 // one past the last word holding stream bits
     if (chunk > 0 && wbase + (unsigned long long)(HB * L) <= end_word) {
         // interior block: four words per store (the payload is only dword-aligned, which global stores accept)
         for (int q = tid; q < HB * L / 4; q += HB) {
-            const int i = 4 * q;                                   // 4 | 32: the four words never straddle a swizzle step
-            const uint32_t *sp = s_o + i + (i >> 5);
-            st16_a4<(RSN_NT_MASK & 4) != 0>(a.out_words + wbase + i, sp[0], sp[1], sp[2], sp[3]);
+            const int i = 4 * q;
+            uint32_t x[5];
+#pragma unroll
+            for (int k = 0; k < 5; k++) x[k] = slot(i + k);
+            st16_a4<(RSN_NT_MASK & 4) != 0>(a.out_words + wbase + i, out_word(x[0], x[1]), out_word(x[1], x[2]), out_word(x[2], x[3]), out_word(x[3], x[4]));
         }
     } else
     for (int i = tid; i < HB * L; i += HB) {
         const unsigned long long g = wbase + i;
         if (g >= end_word) break;
-        const uint32_t val = s_o[i + (i >> 5)];
+        const uint32_t val = out_word(slot(i), slot(i + 1));
         if (g == (a.base_bits >> 5)) {
             // this dword also holds the last header bytes (and the pad bits): merge them in registers
             uint32_t hb = 0;
@@ -892,8 +917,6 @@ __global__ __launch_bounds__(HB) void k_emit_flat(FlatEmitArgs a) {
         const unsigned long long g = wbase + (unsigned long long)(HB * L);
         const bool last_block = chunk + 1 == n_chunks;
         if (last_block && g < end_word) a.out_words[g] = __builtin_bswap32(v[L - 1] << (32 - o0));
-    }
-    __syncthreads();                                               // s_o / s_last are reused by the next chunk
     }
     if (blockIdx.x == 0) {                                         // header bytes in front of the first payload dword
         const uint32_t whole = (uint32_t)(a.base_bits >> 5) * 4;
