@@ -201,7 +201,7 @@ struct BehindClass {
 };
 inline size_t behind_failed(const std::vector<size_t> &idx, const std::vector<size_t> &pool) { return !idx.empty() ? idx[0] : pool.empty() ? 0 : *std::min_element(pool.begin(), pool.end()); }
 // huff_rune.hip: the members of at most HUFF_RUNE_IN_MAX bytes that k_huff_batch_enc hands back as GROUP_BACK_RUNES -- UTF-8 text, bytes
-// that are no UTF-8 at all -- a workgroup each in k_huff_batch_rune_enc: the runes as Go's `range string(b)` yields them counted in an
+// that are no UTF-8 at all -- a workgroup each in k_huff_batch_rune_enc (its body: huff_rune_body.h): the runes as Go's `range string(b)` yields them counted in an
 // LDS table, the Go-exact tree of 2 to HUFF_RUNE_SYMS_MAX leaves in one wavefront (huff_plan_rune.h), header and code bits as the byte
 // encoder writes them.  It hands back more distinct runes than that, and a single one.  Behind the rows of Huffman compress, pool RUNES:
 // a call that holds at least HUFF_RUNE_GROUP_MIN such members runs them; fewer take the single call, as every one did before.
@@ -213,7 +213,7 @@ constexpr uint32_t HUFF_RUNE_SYMS_MAX = 256;
 const BehindClass &huff_rune_class();
 // huff_rune_mid.hip: the same for the members of more than HUFF_RUNE_IN_MAX and at most HUFF_RUNE_MID_IN_MAX bytes that k_huff_mid_enc hands
 // back as GROUP_BACK_RUNES -- a workgroup of 1024 threads each in k_huff_mid_rune_enc, the member and the image of its stream in LDS, one
-// workgroup to a CU as in the mid class: the 16 KiB kernel's runes, table, plan and header, counts up to 65535 (PLAN_RUNE_MID_COUNT_MAX),
+// workgroup to a CU as in the mid class: the 16 KiB kernel's body (huff_rune_body.h) with its runes, table, plan and header, counts up to 65535 (PLAN_RUNE_MID_COUNT_MAX),
 // the bits a round of 16 KiB at a time.  It hands back what the 16 KiB class hands back: more than HUFF_RUNE_SYMS_MAX distinct runes, a
 // single one.  Behind the rows of Huffman compress, pool RUNES, listed AHEAD of huff_rune_class (which would send these members to `rest`,
 // where nothing says any more that they were rune members): a call that holds at least HUFF_RUNE_MID_GROUP_MIN such members runs them and

@@ -62,7 +62,7 @@ constexpr size_t huff_enc_in_slot(size_t n) { return group_round16(n) + 16; }
 constexpr uint32_t HUFF_HDR_MAX = 1100;         // 128 entries of at most 5 digits + '|' + 2 bytes, + "\\\n" + pad
 constexpr uint32_t huff_small_enc_out_slot(uint32_t n) { return (HUFF_HDR_MAX + n + 15) & ~15u; }                    // holds header + 7n/8 + pad
 constexpr uint32_t huff_mid_enc_out_slot(uint32_t n) { return (HUFF_HDR_MAX + (7 * n + 7) / 8 + 3 + 15) & ~15u; }    // header + payload in whole words
-// the rune encoder (huff_rune.hip): at most 256 entries of 5 digits + '|' + 4 bytes of UTF-8, + "\\\n" + pad -- a header maximum of its
+// the rune encoders (huff_rune_body.h): at most 256 entries of 5 digits + '|' + 4 bytes of UTF-8, + "\\\n" + pad -- a header maximum of its
 // own, the decoders and huff_parse_small.h keep HUFF_HDR_MAX; fewer than 9 bits a rune (a Huffman code's average is below the entropy + 1,
 // and 256 symbols have at most 8 bits of it) and at most a rune a byte.  huff_rune_stream_max(n): the longest stream of a member of n bytes.
 constexpr uint32_t HUFF_RUNE_HDR_MAX = 256 * (5 + 1 + 4) + 3;

@@ -8,7 +8,7 @@
 //   count   k_huff_big_count, a workgroup per tile: the tile's 16 KiB, 16 bytes a thread, counted into per-wavefront LDS histograms as
 //           huff_enc_body counts a member; the 128 counts and a "byte >= 0x80" flag go to the member's scratch.
 //   plan    k_huff_big_plan, a workgroup per member: the tiles' counts summed; ranks and header entries by block scans and ONE wavefront
-//           that builds the Go-exact tree and codes with plan_tree / plan_codes over LaneStore, exactly as huff_enc_body does (the code
+//           that builds the Go-exact tree and codes with wave_tree (huff_small_body.h), exactly as huff_enc_body does (the code
 //           tests/huff_big_plan_test.cpp holds against huff_host.cpp at these counts); the header and the pad byte into the member's output
 //           slot; every tile's bit length as sum(count x length) over the tile's OWN counts -- the input is not read for it -- and their
 //           scan, the pad in front folded into the base.  The code table and the offsets stay in scratch.  A member it does not take --
@@ -38,8 +38,7 @@ static_assert((unsigned long long)HUFF_BIG_IN_MAX * 24 + 8ull * HUFF_BIG_HDR_MAX
 static_assert(HUFF_BIG_HDR_MAX <= HUFF_HDR_MAX, "the counts cannot all be long: the class's header bound lies below the other classes'");
 // a code of d bits needs counts that sum to at least fib(d + 2): fib(26) = 121393 is within the class, so codes of 24 bits occur and are
 // taken; fib(27) = 196418 is too, so a code of 25 bits can occur and the plan hands such a member back -- the emit table is not widened
-constexpr unsigned long long bg_fib(int k) { unsigned long long a = 0, b = 1; for (int i = 0; i < k; i++) { const unsigned long long t = a + b; a = b; b = t; } return a; }
-static_assert(bg_fib(26) <= HUFF_BIG_IN_MAX && bg_fib(27) == 196418 && bg_fib(27) <= HUFF_BIG_IN_MAX, "24-bit codes are taken, 25-bit codes are possible and handed back");
+static_assert(plan_fib(26) <= HUFF_BIG_IN_MAX && plan_fib(27) == 196418 && plan_fib(27) <= HUFF_BIG_IN_MAX, "24-bit codes are taken, 25-bit codes are possible and handed back");
 // the image of a tile: at most 24 bits a byte behind the up to 127 bits in front of its first (the 16-byte unit's), the next tile's up to 7
 // symbols that fill its last byte, and the word pack_codes16 may OR zeros into behind the last
 constexpr uint32_t BG_IMG_WORDS = HUFF_BIG_TILE * 24 / 32 + 16;
@@ -84,7 +83,7 @@ __global__ __launch_bounds__(BG_PT) void k_huff_big_plan(const SmallMember *__re
     const SmallMember m = tab[blockIdx.x];
     uint32_t *status = reinterpret_cast<uint32_t *>(base + m.status_off);
     uint32_t *my = scr + (size_t)blockIdx.x * BIG_SCR_WORDS;
-    const uint32_t n = m.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t n = m.n, tid = threadIdx.x, wave = tid >> 6;
     // a member that is not taken: no byte of it will be written, so its word is stored here; the emit launch reads the verdict and leaves
     auto hand_back = [&](uint32_t v) { if (tid == 0) { my[BIG_SCR_META + BIG_META_VERDICT] = v; *status = v; } };
     if (n < 2 || n > HUFF_BIG_IN_MAX) { hand_back(GROUP_BACK); return; }   // (the host never sends one)
@@ -109,22 +108,10 @@ __global__ __launch_bounds__(BG_PT) void k_huff_big_plan(const SmallMember *__re
     // ---- the tree and the codes: one wavefront (huffman.go:93-127)
     if (wave == 0) {
         const uint32_t au = (uint32_t)__builtin_amdgcn_readfirstlane((int)a);
-        LaneStore<2> heap, kids;
+        LaneStore<2> kids;
         LaneStore<4> code;
-        heap.r[0] = lane < au ? plan_item(s_lf[lane], lane) : 0u;
-        heap.r[1] = lane + 64 < au ? plan_item(s_lf[lane + 64], lane + 64) : 0u;
-        kids.r[0] = kids.r[1] = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) code.r[k] = 0;
-        const uint32_t root = plan_tree(au, heap, kids);
-        plan_codes(au, root, kids, code);
-        // leaf slot l is lane l of code.r[0], slot 64 + l lane l of code.r[1]
-        uint32_t mx = 0, bits = 0;
-        if (lane < au) { s_tab[s_leaf[lane]] = code.r[0]; mx = code.r[0] >> 24; bits = s_lf[lane] * mx; }
-        if (lane + 64 < au) { const uint32_t l1 = code.r[1] >> 24; s_tab[s_leaf[lane + 64]] = code.r[1]; mx = max(mx, l1); bits += s_lf[lane + 64] * l1; }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64)); bits += (uint32_t)__shfl_xor((int)bits, d, 64); }
-        if (lane == 0) { s_plan[0] = mx; s_plan[1] = bits; }
+        wave_tree<8>(s_lf, au, kids, code);
+        wave_codes_out(code, au, s_lf, s_leaf, s_tab, s_plan);
     }
     __syncthreads();
     const uint32_t max_len = s_plan[0], pay_bits = s_plan[1];

@@ -54,20 +54,7 @@ __global__ __launch_bounds__(HP_T) void k_huff_dev_plan(const PlanEntry *__restr
     const uint32_t n = (uint32_t)e.n, limit = parse_scan_limit(n);
     {   // the header into LDS under the gather's rule: the unit that reaches beyond src + n is masked, nothing at or behind src + n rounded up to 16 is loaded
         const uint4 *src = reinterpret_cast<const uint4 *>(e.src);
-        const uint32_t full = n / 16, rest = n & 15;
-        for (uint32_t u = tid; u * 16 < limit; u += HP_T) {
-            uint4 v = src[u];                                  // (u * 16 < limit <= n)
-            if (u >= full) {
-                uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (uint32_t k = 0; k < 4; k++) {
-                    const uint32_t keep = rest > 4 * k ? min(rest - 4 * k, 4u) : 0u;
-                    w[k] = keep == 4 ? w[k] : keep == 0 ? 0u : w[k] & ((1u << (8 * keep)) - 1);
-                }
-                v = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-            s_hdr[u] = v;
-        }
+        for (uint32_t u = tid; u * 16 < limit; u += HP_T) s_hdr[u] = unit_head(src[u], n - 16 * u);      // (u * 16 < limit <= n)
     }
     s_cnt1[tid] = 0;
     reinterpret_cast<uint32_t *>(s_child)[tid] = 0;
@@ -96,20 +83,11 @@ __global__ __launch_bounds__(HP_T) void k_huff_dev_plan(const PlanEntry *__restr
     __syncthreads();
     if (wave == 0) {   // the tree, the depths and child[]: one wavefront, every index wave-uniform (huff_small_body.h: LaneStore)
         const uint32_t au = (uint32_t)__builtin_amdgcn_readfirstlane((int)a);
-        LaneStore<2> heap, kids;
+        LaneStore<2> kids;
         LaneStore<4> code;
-        heap.r[0] = lane < au ? plan_item(s_lf[lane], lane) : 0u;
-        heap.r[1] = lane + 64 < au ? plan_item(s_lf[lane + 64], lane + 64) : 0u;
-        kids.r[0] = kids.r[1] = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) code.r[k] = 0;
-        const uint32_t root = plan_tree(au, heap, kids);
-        plan_codes(au, root, kids, code);
-        uint32_t mn = 255, mx = 0;                              // leaf slot l is lane l of code.r[0], slot 64 + l lane l of code.r[1]
-        if (lane < au) { mn = mx = code.r[0] >> 24; }
-        if (lane + 64 < au) { const uint32_t l1 = code.r[1] >> 24; mn = min(mn, l1); mx = max(mx, l1); }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { mn = min(mn, (uint32_t)__shfl_xor((int)mn, d, 64)); mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64)); }
+        const uint32_t root = wave_tree<8>(s_lf, au, kids, code);
+        uint32_t mn, mx;
+        wave_depths(code, au, &mn, &mx);
         // internal node k is lane k of kids.r[0], node 64 + k lane k of kids.r[1]
         if (lane + 1 < au) { s_child[2 * lane] = (uint16_t)parse_child(kids.r[0] & 0xFFu, au, s_leaf); s_child[2 * lane + 1] = (uint16_t)parse_child(kids.r[0] >> 8, au, s_leaf); }
         if (lane + 65 < au) { s_child[2 * lane + 128] = (uint16_t)parse_child(kids.r[1] & 0xFFu, au, s_leaf); s_child[2 * lane + 129] = (uint16_t)parse_child(kids.r[1] >> 8, au, s_leaf); }

@@ -25,8 +25,7 @@ static_assert(HUFF_MID_IN_MAX - 1 < PLAN_COUNT_LIMIT, "two distinct bytes at lea
 static_assert(((unsigned long long)HUFF_MID_IN_MAX << 8) < (1ull << 32) && HUFF_MID_IN_MAX < (1u << 24), "a sum of counts and a node id pack into one word (plan_item)");
 static_assert(128 * (5 + 1 + 1) + 1 + 3 <= HDR_MAX, "128 entries of five digits, '|' and a byte (the newline's: two), \"\\\\\\n\" and the pad byte");
 // a code of d bits needs counts that sum to at least fib(d + 2) (Fibonacci counts are the worst case): fib(24) = 46368 <= 65536 < fib(25)
-constexpr unsigned long long hm_fib(int k) { unsigned long long a = 0, b = 1; for (int i = 0; i < k; i++) { const unsigned long long t = a + b; a = b; b = t; } return a; }
-static_assert(hm_fib(24) <= HUFF_MID_IN_MAX && hm_fib(25) > HUFF_MID_IN_MAX, "the deepest code of a member is 22 bits: inside the 24 of the emit table");
+static_assert(plan_fib(24) <= HUFF_MID_IN_MAX && plan_fib(25) > HUFF_MID_IN_MAX, "the deepest code of a member is 22 bits: inside the 24 of the emit table");
 // the flat 7-bit code is a prefix code of a byte alphabet, and Huffman's is no longer than any: the payload is at most 7 n / 8 bytes
 static_assert((unsigned long long)HUFF_MID_IN_MAX * 7 <= (unsigned long long)HUFF_MID_PAY_MAX * 8, "the payload of the largest member");
 constexpr uint32_t HM_IMG_WORDS = ((HDR_MAX + HUFF_MID_PAY_MAX + 64) / 4 + 3) & ~3u;

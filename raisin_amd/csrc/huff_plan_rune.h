@@ -1,5 +1,5 @@
 // huff_plan_rune.h -- the Go-exact leaf order, tree, codes and header of a small RUNE alphabet, as code that compiles for the host and the
-// device.  k_huff_batch_rune_enc (huff_rune.hip) runs it per member; tests/test_huff_rune_plan_host.py compiles it with huff_host.cpp and
+// device.  huff_rune_enc_body (huff_rune_body.h: k_huff_batch_rune_enc's and k_huff_mid_rune_enc's body) runs it per member; tests/test_huff_rune_plan_host.py compiles it with huff_host.cpp and
 // checks it against build_tree / assign_codes / emit_header.  The alphabet: 2 to 256 distinct runes in no particular order (the kernel's
 // come out of a hash table), every count at most 16384.
 //   leaves   (count asc, rune asc) and the header's order (rune asc): plan_rune_ranks                huffman.go:64-87 (sort_leaves)
@@ -31,7 +31,7 @@ static_assert(PLAN_RUNE_MID_COUNT_MAX < (1u << 23) && ((unsigned long long)PLAN_
 constexpr uint32_t PLAN_RUNE_SLOTS =2 * PLAN_RUNE_SYMS_MAX;           // of the encoder's and the decoder's open-addressing table: twice the symbols it may hold
 static_assert(PLAN_RUNE_SLOTS == 1u << 9, "plan_rune_hash gives 9 bits");
 
-// a rune's first slot in a table of PLAN_RUNE_SLOTS slots: the ONE hash of the encoder's counts (huff_rune.hip) and the decoder's entries
+// a rune's first slot in a table of PLAN_RUNE_SLOTS slots: the ONE hash of the encoder's counts (huff_rune_body.h) and the decoder's entries
 // (huff_parse_rune.h); tests/huff_rune_parse_test.cpp prints it (`slots`)
 RSN_HD_FN uint32_t plan_rune_hash(uint32_t r) { return (r * 0x9E3779B1u) >> 23; }   // 9 bits
 

@@ -9,7 +9,7 @@
 //   header   ascending by byte, '\\' first when it would be last; "<count>|<byte>", newline as "\n": plan_entry / plan_header
 //                                                                                                 huffman.go:312-318 (emit_header)
 // The heap and the children are reached through a store (get / set of slot i): an array on the host, VGPRs read and written a lane at a
-// time on the device (huff_small.hip) -- every index is wave-uniform, so a sift level is a few scalar-indexed lane accesses instead of a
+// time on the device (huff_small_body.h: LaneStore, wave_tree) -- every index is wave-uniform, so a sift level is a few scalar-indexed lane accesses instead of a
 // dependent LDS round trip.
 #pragma once
 
@@ -26,6 +26,9 @@ constexpr uint32_t PLAN_COUNT_LIMIT = 1u << 16;   // every count below this
 // the codes below only ask that a sum of counts and a node id pack into one word -- plan_item<8>, sum << 8 < 2^32.  The parsers
 // (huff_parse_small.h) and the decoders keep PLAN_COUNT_LIMIT.
 constexpr uint32_t PLAN_COUNT_LIMIT_WIDE = 1u << 24;
+// How deep a code can be: a code of d bits needs counts that sum to at least fib(d + 2), Fibonacci counts being the worst case.  The classes
+// state their depth with it, each at its own member size (huff_mid.hip, huff_big.hip, huff_rune_mid.hip).
+constexpr unsigned long long plan_fib(int k) { unsigned long long a = 0, b = 1; for (int i = 0; i < k; i++) { const unsigned long long t = a + b; a = b; b = t; } return a; }
 
 // A heap item / a node's code: one word each.
 //   item   count << IDB | node id         (sums of counts < 2^23, ids < 255)

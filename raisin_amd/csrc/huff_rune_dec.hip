@@ -69,20 +69,7 @@ __device__ __forceinline__ bool rune_light_plan(const uint8_t *src_bytes, unsign
     const uint32_t n = (uint32_t)n64, limit = parse_rune_scan_limit(n);
     {
         const uint4 *src = reinterpret_cast<const uint4 *>(src_bytes);
-        const uint32_t full = n / 16, rest = n & 15;
-        for (uint32_t u = tid; u * 16 < limit; u += T) {
-            uint4 v = src[u];                                  // (u * 16 < limit <= n)
-            if (u >= full) {
-                uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (uint32_t k = 0; k < 4; k++) {
-                    const uint32_t keep = rest > 4 * k ? min(rest - 4 * k, 4u) : 0u;
-                    w[k] = keep == 4 ? w[k] : keep == 0 ? 0u : w[k] & ((1u << (8 * keep)) - 1);
-                }
-                v = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-            s_hdr[u] = v;
-        }
+        for (uint32_t u = tid; u * 16 < limit; u += T) s_hdr[u] = unit_head(src[u], n - 16 * u);      // (u * 16 < limit <= n)
     }
     for (uint32_t i = tid; i < PARSE_RUNE_SLOTS; i += T) { s_key[i] = PARSE_RUNE_EMPTY; s_c1[i] = 0; }
     if (tid < W_WORDS) s_w[tid] = tid == W_SEP ? PARSE_NONE : 0u;
@@ -147,31 +134,19 @@ __global__ __launch_bounds__(RD_T) void k_huff_batch_rune_dec(const SmallMember 
     // ---- the tree, the depths and child[]: one wavefront, every index wave-uniform (huffman.go:93-127)
     if (wave == 0) {
         const uint32_t au = (uint32_t)__builtin_amdgcn_readfirstlane((int)a);
-        LaneStore<4> heap, kids;
+        LaneStore<4> kids;
         LaneStore<8> code;
+        const uint32_t root = wave_tree<PLAN_RUNE_IDB>(s_lf, au, kids, code);
+        uint32_t mn, mx;
+        wave_depths(code, au, &mn, &mx);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            const uint32_t l = lane + 64 * k;
-            heap.r[k] = l < au ? plan_item<PLAN_RUNE_IDB>(s_lf[l], l) : 0u;
-            kids.r[k] = 0;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) code.r[k] = 0;
-        const uint32_t root = plan_tree<PLAN_RUNE_IDB>(au, heap, kids);
-        plan_codes<PLAN_RUNE_IDB>(au, root, kids, code);
-        // leaf l is lane l % 64 of code.r[l / 64], internal node k lane k % 64 of kids.r[k / 64]
-        uint32_t mn = 255, mx = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t l = lane + 64 * k;
-            if (l < au) { const uint32_t len = code.r[k] >> 24; mn = min(mn, len); mx = max(mx, len); }
+            const uint32_t l = lane + 64 * k;                             // internal node l
             if (l + 1 < au) {
                 s_kid[2 * l] = (uint16_t)parse_rune_child(kids.r[k] & ((1u << PLAN_RUNE_IDB) - 1), au);
                 s_kid[2 * l + 1] = (uint16_t)parse_rune_child(kids.r[k] >> PLAN_RUNE_IDB, au);
             }
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { mn = min(mn, (uint32_t)__shfl_xor((int)mn, d, 64)); mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64)); }
         if (lane == 0) { s_w[W_ROOT] = root - au; s_w[W_MIN] = mn; s_w[W_MAX] = mx; }
     }
     __syncthreads();

@@ -1,6 +1,7 @@
 // huff_small_body.h -- the device code that the Huffman kernels of huff_small.hip (a single small call, the batch kernels for members of
 // up to 16 KiB), of huff_mid.hip (the batch kernels for members of 16 to 64 KiB) and of huff_big_dec.hip (the tiled decoder above that) share: the lane-map decoder of one workgroup, the
-// one-workgroup encoder that builds its own tree, their scans and their last store.  The bodies take what differs between the kernels
+// one-workgroup encoder that builds its own tree, the tree in one wavefront's VGPRs (wave_tree: every kernel that builds one calls it,
+// the rune kernels and the device plans too), their scans and their last store.  The bodies take what differs between the kernels
 // -- lanes, LDS sizes, where the large LDS arrays live -- as template parameters and arguments; DESIGN 4.7.
 #pragma once
 
@@ -87,6 +88,18 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_wave
     if (threadIdx.x == 0) { uint32_t acc = 0; for (int w = 0; w < WAVES; w++) { const uint32_t t = s_wave[w]; s_wave[w] = acc; acc += t; } s_wave[WAVES] = acc; }
     __syncthreads();
     return s_wave[wave] + inc - v;
+}
+
+// a 16-byte unit as loaded, of which the first `keep` bytes are the member's (16 or more: all): zeros from byte `keep` on
+__device__ __forceinline__ uint4 unit_head(uint4 v, uint32_t keep) {
+    if (keep >= 16) return v;
+    uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+        const uint32_t mine = keep > 4 * k ? min(keep - 4 * k, 4u) : 0u;
+        w[k] = mine == 4 ? w[k] : mine == 0 ? 0u : w[k] & ((1u << (8 * mine)) - 1);
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
 // ---------------------------------------------------------------- decompress (huffman.go:131-153,258-297)
@@ -458,9 +471,8 @@ __device__ __forceinline__ void small_dec_body(const SmallDecArgs &a, uint32_t *
 // ---------------------------------------------------------------- compress, many members in one launch (the batch call)
 // ONE block per member, whatever the grid, and nothing on the host between the histogram and the emit: the block loads its member (a
 // SmallMember entry in pinned memory: where its bytes, its output slot and its status word are) into LDS once and counts it there, ranks
-// the leaves, and ONE wavefront builds the Go-exact tree and codes (huff_plan_small.h -- the code the CPU test checks against the host's
-// build_tree / assign_codes) with the heap, the children and the codes held in VGPRs, a slot per lane: a read is a readlane, a write a select in
-// the one lane, both at a wave-uniform index.  The other wavefronts wait; the header's entries are already in place (a scan of their lengths).  Then every
+// the leaves, and ONE wavefront builds the Go-exact tree and codes (wave_tree below) with the heap, the children and the codes held in
+// VGPRs, a slot per lane: a read is a readlane, a write a select in the one lane, both at a wave-uniform index.  The other wavefronts wait; the header's entries are already in place (a scan of their lengths).  Then every
 // byte's first bit is a block scan of the code lengths and the codes are ORed into an LDS image of the output words, as k_small_emit does.
 // Status word: the stream's length, GROUP_BACK_RUNES -- a byte >= 0x80 (runes, huffman.go:309) -- or GROUP_BACK: fewer than two distinct bytes, a code beyond
 // 24 bits or a header beyond HDR_MAX (none of the last two below the member cutoff: counts below 2^15 give codes of at most 20 bits).
@@ -486,6 +498,54 @@ struct LaneStore {
         for (int k = 0; k < R; k++) if (q == (uint32_t)k && me == l) r[k] = v;
     }
 };
+
+// The Go-exact tree and codes in ONE wavefront's VGPRs (huff_plan_small.h: plan_tree and plan_codes, the code the CPU tests hold against
+// huff_host.cpp): the `a` leaves in rank order with their counts in s_lf[0 .. a), a wave-uniform and at most 64 R; the heap (64 R slots),
+// the children (64 R - 1 pairs) and the codes (128 R - 1) in LaneStores.  IDB: bits of a node id (8 for the byte alphabets' R = 2,
+// PLAN_RUNE_IDB for the runes' R = 4).  On return leaf l is lane l % 64 of code.r[l / 64], internal node a + k is lane k % 64 of
+// kids.r[k / 64] (left | right << IDB).  Returns the root's id.  Every lane of the wavefront calls it; the other wavefronts wait.
+template <uint32_t IDB, int R>
+__device__ __forceinline__ uint32_t wave_tree(const uint32_t *s_lf, uint32_t a, LaneStore<R> &kids, LaneStore<2 * R> &code) {
+    static_assert(128u * R <= (1u << IDB), "a node id has IDB bits");
+    const uint32_t lane = threadIdx.x & 63;
+    LaneStore<R> heap;
+#pragma unroll
+    for (int k = 0; k < R; k++) {
+        const uint32_t l = lane + 64 * k;
+        heap.r[k] = l < a ? plan_item<IDB>(s_lf[l], l) : 0u;
+        kids.r[k] = 0;
+    }
+#pragma unroll
+    for (int k = 0; k < 2 * R; k++) code.r[k] = 0;
+    const uint32_t root = plan_tree<IDB>(a, heap, kids);
+    plan_codes<IDB>(a, root, kids, code);
+    return root;
+}
+// what the encoders take from it: leaf l's len << 24 | code to s_tab[s_at[l]], (deepest code, payload bits) to s_plan[0 .. 2)
+template <int RC, class At>
+__device__ __forceinline__ void wave_codes_out(const LaneStore<RC> &code, uint32_t a, const uint32_t *s_lf, const At *s_at, uint32_t *s_tab, uint32_t *s_plan) {
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t mx = 0, bits = 0;
+#pragma unroll
+    for (int k = 0; k < RC / 2; k++) {
+        const uint32_t l = lane + 64 * k;
+        if (l < a) { const uint32_t cd = code.r[k], len = cd >> 24; s_tab[s_at[l]] = cd; mx = max(mx, len); bits += s_lf[l] * len; }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64)); bits += (uint32_t)__shfl_xor((int)bits, d, 64); }
+    if (lane == 0) { s_plan[0] = mx; s_plan[1] = bits; }
+}
+// what the decoders' plans take from it: the shallowest and the deepest leaf, in every lane
+template <int RC>
+__device__ __forceinline__ void wave_depths(const LaneStore<RC> &code, uint32_t a, uint32_t *shallowest, uint32_t *deepest) {
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t mn = 255, mx = 0;
+#pragma unroll
+    for (int k = 0; k < RC / 2; k++) if (lane + 64 * k < a) { const uint32_t len = code.r[k] >> 24; mn = min(mn, len); mx = max(mx, len); }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { mn = min(mn, (uint32_t)__shfl_xor((int)mn, d, 64)); mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64)); }
+    *shallowest = mn; *deepest = mx;
+}
 
 // A lane's up to 16 codes (len << 24 | code, len <= 24; 0: none) into the image from bit pos0 on: MSB first, words byte-swapped; the
 // lane's first and last words may be shared with its neighbours (LDS atomics), the words between are its own.
@@ -520,7 +580,7 @@ __device__ __forceinline__ void huff_enc_body(const SmallMember *__restrict__ ta
     __shared__ uint32_t s_plan[2];                     // max code length, payload bits
     const SmallMember m = tab[blockIdx.x];
     uint32_t *status = reinterpret_cast<uint32_t *>(base + m.status_off);
-    const uint32_t n = m.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t n = m.n, tid = threadIdx.x, wave = tid >> 6;
     if (n < 2 || n > IN_MAX) { block_done(status, GROUP_BACK); return; }    // (the host never sends one)
     for (uint32_t i = tid; i < T / 64 * 128; i += T) (&s_cnt[0][0])[i] = 0;
     for (uint32_t i = tid; i < IMG_WORDS; i += T) s_img[i] = 0;
@@ -559,22 +619,10 @@ __device__ __forceinline__ void huff_enc_body(const SmallMember *__restrict__ ta
     // ---- the tree and the codes: one wavefront (huffman.go:93-127)
     if (wave == 0) {
         const uint32_t au = (uint32_t)__builtin_amdgcn_readfirstlane((int)a);
-        LaneStore<2> heap, kids;
+        LaneStore<2> kids;
         LaneStore<4> code;
-        heap.r[0] = lane < au ? plan_item(s_lf[lane], lane) : 0u;
-        heap.r[1] = lane + 64 < au ? plan_item(s_lf[lane + 64], lane + 64) : 0u;
-        kids.r[0] = kids.r[1] = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) code.r[k] = 0;
-        const uint32_t root = plan_tree(au, heap, kids);
-        plan_codes(au, root, kids, code);
-        // leaf slot l is lane l of code.r[0], slot 64 + l lane l of code.r[1]
-        uint32_t mx = 0, bits = 0;
-        if (lane < au) { s_tab[s_leaf[lane]] = code.r[0]; mx = code.r[0] >> 24; bits = s_lf[lane] * mx; }
-        if (lane + 64 < au) { const uint32_t l1 = code.r[1] >> 24; s_tab[s_leaf[lane + 64]] = code.r[1]; mx = max(mx, l1); bits += s_lf[lane + 64] * l1; }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { mx = max(mx, (uint32_t)__shfl_xor((int)mx, d, 64)); bits += (uint32_t)__shfl_xor((int)bits, d, 64); }
-        if (lane == 0) { s_plan[0] = mx; s_plan[1] = bits; }
+        wave_tree<8>(s_lf, au, kids, code);
+        wave_codes_out(code, au, s_lf, s_leaf, s_tab, s_plan);
     }
     __syncthreads();
     const uint32_t max_len = s_plan[0], pay_bits = s_plan[1];

@@ -1,5 +1,5 @@
 // huff_utf8.h -- Go's UTF-8 decoding (`range string(b)`, huffman.go:235,309) on the device, for the units that count and code runes:
-// huff_encode.hip (the flat rune path, on global memory) and huff_rune.hip (the grouped rune encoder, on a member held in LDS).
+// huff_encode.hip (the flat rune path, on global memory) and huff_rune_body.h (the grouped rune encoders' body, on a member held in LDS).
 #pragma once
 
 #include "huff_host.h"

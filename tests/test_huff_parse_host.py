@@ -51,4 +51,7 @@ def test_the_header_compiles_for_the_device_too():
     assert "RSN_HD_FN" in text and "#define RSN_HD_FN __host__ __device__" in shared
     assert [line.split()[1] for line in shared.splitlines() if line.startswith("#include")] == ["<cstdint>"]
     kernel = open(os.path.join(SRC, "huff_dev.hip")).read()
-    assert '#include "huff_parse_small.h"' in kernel and "parse_scan(" in kernel and "plan_tree(" in kernel
+    assert '#include "huff_parse_small.h"' in kernel and "parse_scan(" in kernel and "wave_tree<8>(" in kernel
+    # ... the tree through the one wavefront helper, which is where plan_tree is called
+    body = open(os.path.join(SRC, "huff_small_body.h")).read()
+    assert '#include "huff_small_body.h"' in kernel and body.count("plan_tree<IDB>(") == 1 and body.count("plan_codes<IDB>(") == 1

@@ -61,10 +61,19 @@ def test_the_class_is_wired_through_the_shared_pieces():
     assert [ln.split()[1] for ln in open(os.path.join(SRC, "huff_rune_mid_select.h")) if ln.startswith("#include")] == ['"huff_rune_select.h"']
     unit = open(os.path.join(SRC, "huff_rune_mid.hip")).read()
     assert unit.count("rune_mid_class_members(") == 2 and "class_run<RuneMidEncClass>" in unit and "class_run_dev<RuneMidEncClass>" in unit
-    assert '"huff_batch_rune_mid_enc"' in unit and "func_dyn_lds(" in unit and "plan_tree<PLAN_RUNE_IDB>" in unit and "asm" not in unit
+    assert '"huff_batch_rune_mid_enc"' in unit and "func_dyn_lds(" in unit and "asm" not in unit
+    # the kernel is the one body of both rune encoders: each unit instantiates it and holds no count loop of its own, and the body holds
+    # the tree of the rune alphabet, through the one wavefront helper (huff_small_body.h)
+    small = open(os.path.join(SRC, "huff_rune.hip")).read()
+    for text in (unit, small):
+        assert '#include "huff_rune_body.h"' in text and text.count("huff_rune_enc_body<") == 1 and "atomicCAS(" not in text and "plan_tree" not in text
+    body = open(os.path.join(SRC, "huff_rune_body.h")).read()
+    assert body.count("atomicCAS(") == 1 and body.count("wave_tree<PLAN_RUNE_IDB>(") == 1 and "asm" not in body
+    shared = open(os.path.join(SRC, "huff_small_body.h")).read()
+    assert '#include "huff_small_body.h"' in body and shared.count("plan_tree<IDB>(") == 1 and "asm" not in shared
     rows = open(os.path.join(SRC, "codecs.h")).read()
     assert "{&huff_rune_mid_class(), &huff_rune_class()}" in rows
     api = open(os.path.join(SRC, "rsn_api.hip")).read()
     assert "rune_mid" not in api
     make = open(os.path.join(SRC, "Makefile")).read()
-    assert "huff_rune_mid.hip" in make and "huff_rune_mid_select.h" in make
+    assert "huff_rune_mid.hip" in make and "huff_rune_mid_select.h" in make and "huff_rune_body.h" in make

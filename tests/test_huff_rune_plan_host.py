@@ -34,7 +34,15 @@ def test_rune_planner_is_the_code_the_kernel_runs():
     # one header for the host test and the kernel, the tree and the codes shared with the byte planner, the UTF-8 rule shared with the flat path
     text = open(os.path.join(SRC, "huff_plan_rune.h")).read()
     assert '#include "huff_plan_small.h"' in text and "plan_rune_ranks" in text
-    kernel = open(os.path.join(SRC, "huff_rune.hip")).read()
-    assert '#include "huff_plan_rune.h"' in kernel and '#include "huff_utf8.h"' in kernel and "plan_tree<PLAN_RUNE_IDB>" in kernel
+    # both rune encoders reach them through their one body, and the body reaches the tree through the one wavefront helper: the planner's
+    # code is named there and nowhere beside it
+    body = open(os.path.join(SRC, "huff_rune_body.h")).read()
+    assert '#include "huff_plan_rune.h"' in body and '#include "huff_utf8.h"' in body and '#include "huff_small_body.h"' in body
+    assert body.count("wave_tree<PLAN_RUNE_IDB>(") == 1 and "plan_tree<" not in body
+    shared = open(os.path.join(SRC, "huff_small_body.h")).read()
+    assert '#include "huff_plan_small.h"' in shared and shared.count("plan_tree<IDB>(") == 1 and shared.count("plan_codes<IDB>(") == 1
+    for unit in ("huff_rune.hip", "huff_rune_mid.hip"):
+        kernel = open(os.path.join(SRC, unit)).read()
+        assert '#include "huff_rune_body.h"' in kernel and "huff_rune_enc_body<" in kernel and "plan_tree" not in kernel, unit
     flat = open(os.path.join(SRC, "huff_encode.hip")).read()
     assert '#include "huff_utf8.h"' in flat and "int seq_len(" not in flat
