@@ -116,7 +116,7 @@ const BatchClass &lzss_small_class(bool compress), &lzss_mid_class(bool compress
 // (window 1 to 4096) does not fit a workgroup, and a workgroup a member would leave the device idle, so its escaped stream is cut into
 // tiles of LZSS_TILE_POS positions and a group is FOUR launches with nothing on the host between them: a workgroup per member escapes it
 // into scratch, a workgroup per tile searches it (the window in front and the look-ahead behind in LDS; the chain walk is the mid
-// kernel's, lzss_match.h), a workgroup per member walks the greedy chain and sizes the items, and a workgroup per tile stores its bytes
+// kernel's, lzss_enc_body.h), a workgroup per member walks the greedy chain and sizes the items, and a workgroup per tile stores its bytes
 // (lzss_tile_layout.h: the tiles, the scratch, which tile stores which byte).  It hands back what escapes to more than LZSS_TILE_E_MAX
 // bytes or to more than one and a half times the member, and -- as the mid class -- runs and short periods (the step cap).  Both forms
 // run on device staging, in groups of up to LZSS_TILE_GROUP_BYTES.  The streams decode through the tiled decoder below inside a

@@ -4,6 +4,12 @@
 // k_group_scatter behind it.  The class's kernel is the host form's, launched unchanged with the device staging as `base`.  The loop over
 // the groups is run_groups_staged (group_run.h), the one driver of every family; this unit is the family of SmallMember entries.  What
 // crosses PCIe per group is its tables (64 bytes a member, one copy up) and per class its answers (4 bytes a member, one copy down).
+// Here too: the two waits for words in pinned memory (codecs.h: flags_wait, group_wait) that every grouped class and single small call
+// of every codec ends with.
+#include <atomic>
+#include <chrono>
+#include <thread>
+
 #include "group_run.h"
 
 namespace rsn {
@@ -67,6 +73,43 @@ __global__ __launch_bounds__(GD_THREADS) void k_group_scatter(const GatherEntry 
 }
 
 }  // namespace
+
+int flags_wait(Ctx &c, hipStream_t s, const uint32_t *flags, uint32_t n, const char *what) {
+    const volatile uint32_t *vf = flags;
+    auto pending = [&] { uint32_t p = 0; for (uint32_t i = 0; i < n; i++) p |= vf[i] == GROUP_PENDING; return p != 0; };
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t spins = 1;; spins++) {
+        if (!pending()) { std::atomic_thread_fence(std::memory_order_acquire); return RSN_OK; }
+        if ((spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) {
+            RSN_HIP(hipStreamSynchronize(s));
+            if (pending()) return c.fail(RSN_ERR_DEVICE, "%s: a small-input kernel finished without its answer", what);
+            return RSN_OK;
+        }
+        __builtin_ia32_pause();
+    }
+}
+
+int group_wait(Ctx &c, hipStream_t s, const uint8_t *base, const std::vector<uint32_t> &off, uint32_t pending, const char *what) {
+    auto at = [&](size_t k) { return *reinterpret_cast<const volatile uint32_t *>(base + off[k]); };
+    const auto t0 = std::chrono::steady_clock::now();
+    size_t k = 0;                                                                  // every member before k has answered
+    for (uint32_t spins = 1;; spins++) {
+        while (k < off.size() && at(k) != pending) k++;
+        if (k == off.size()) { std::atomic_thread_fence(std::memory_order_acquire); return RSN_OK; }
+        if ((spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
+        __builtin_ia32_pause();
+    }
+    for (;;) {                                                                     // (a large group, or a busy device: the stream, with a limit)
+        const hipError_t e = hipStreamQuery(s);
+        if (e == hipSuccess) break;
+        if (e != hipErrorNotReady) return c.fail(RSN_ERR_DEVICE, "%s: hipStreamQuery: %s", what, hipGetErrorString(e));
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) return c.fail(RSN_ERR_DEVICE, "%s: the grouped kernel did not finish within 20 s", what);
+        std::this_thread::sleep_for(std::chrono::microseconds(20));
+    }
+    for (; k < off.size(); k++) if (at(k) == pending) return c.fail(RSN_ERR_DEVICE, "%s: the grouped kernel finished without an answer for one of its members", what);
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return RSN_OK;
+}
 
 int run_groups_dev(Ctx &c, hipStream_t s, const char *what, const std::vector<size_t> &idx, const rsn_dev_member *mem, const GroupSlotBytes &in_bytes,
                    const GroupSlotBytes &out_bytes, const GroupLaunch &launch, std::vector<uint32_t> &answers, size_t group_bytes) {

@@ -1,10 +1,11 @@
 // huff_small_body.h -- the device code that the Huffman kernels of huff_small.hip (a single small call, the batch kernels for members of
 // up to 16 KiB), of huff_mid.hip (the batch kernels for members of 16 to 64 KiB) and of huff_big_dec.hip (the tiled decoder above that) share: the lane-map decoder of one workgroup, the
 // one-workgroup encoder that builds its own tree, the tree in one wavefront's VGPRs (wave_tree: every kernel that builds one calls it,
-// the rune kernels and the device plans too), their scans and their last store.  The bodies take what differs between the kernels
+// the rune kernels and the device plans too) and their scans; their last store is block_dev.h's block_done.  The bodies take what differs between the kernels
 // -- lanes, LDS sizes, where the large LDS arrays live -- as template parameters and arguments; DESIGN 4.7.
 #pragma once
 
+#include "block_dev.h"
 #include "group_run.h"
 #include "huff_host.h"
 #include "huff_pathmap.h"
@@ -67,15 +68,9 @@ constexpr uint32_t DEC_STREAM_MAX = 65536 + 2048;   // bytes of a stream the dec
 constexpr int DEC_K = 9;                        // index bits of the decoder's table, at most (every block builds the table: 11 bits cost 2 us more than they save on 64 KiB)
 constexpr int DEC_ROUNDS = 64;                  // rounds of the synchronisation before the general decoder is asked instead
 
-// A block's last act: its stores to host memory made visible, then ONE word the host is polling (the host does not wait for the stream: a
-// hipStreamSynchronize is 5-10 us of wake-up, the kernel is as long).
+// what a block's word holds until its last act (block_dev.h: block_done)
 constexpr uint32_t FLAG_PENDING = 0xFFFFFFFFu;
 static_assert(FLAG_PENDING == GROUP_PENDING, "flags_wait and group_wait poll the decoder's words too");
-__device__ __forceinline__ void block_done(uint32_t *flag, uint32_t value) {
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 template <int WAVES>
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *s_wave /*[WAVES + 1]*/) {

@@ -1,9 +1,10 @@
-// lzss_dec_body.h -- what the grouped LZSS decoders share (lzss_mid.hip: a member a workgroup; lzss_tile_dec.hip: a tile a workgroup), as
-// __device__ functions: a token's parse (lzss.go:331-352), the pointer jumping that settles the copy chains inside a tile of output, and
-// DecodeOpeningSymbols (lzss.go:391-406) by the parity of the 5C run in front of a byte.
+// lzss_dec_body.h -- what the LZSS batch decoders share (lzss_small.hip, the parse only, and lzss_mid.hip: a member a workgroup;
+// lzss_tile_dec.hip: a tile a workgroup), as __device__ functions: a token's parse (lzss.go:331-352), the items of a chunk of the stream two bytes a thread, the
+// pointer jumping that settles the copy chains inside a tile of output, and DecodeOpeningSymbols (lzss.go:391-406) by the parity of the 5C
+// run in front of a byte.  The counterpart of lzss_enc_body.h.
 #pragma once
 
-#include "rsn_common.h"
+#include "block_dev.h"
 
 namespace rsn {
 
@@ -20,6 +21,30 @@ __device__ __forceinline__ bool lzd_token(const uint8_t *s, uint32_t org, uint32
     ok = ok && nd && q < n && s[q - org] == '>' && v <= (unsigned long long)vmax && (uint32_t)v <= ptr;
     len = ok ? (uint32_t)v : 0u; ttl = ok ? q + 1 - p : 0u;
     return ok;
+}
+
+// The items of the chunk of the stream that begins at byte c0, two bytes of it a thread (2 * threadIdx.x and the next): every '<' parses
+// its token and covers its text in s_cov (s_cov[q - c0] for byte q; zeroed by the caller but for what a token begun in front of c0
+// covers).  ttl != 0: a token (its text's length), with tptr and tlen; outl: the bytes the item gives -- a token's tlen, 1 for a literal, 0
+// for a byte of a token's text (an escaped stream holds no '<' of its own: once every token has parsed none lies in another's text).
+// bad: a '<' of this thread's is no token.  s_in, org, n, vmax: lzd_token's.  outl is computed behind a barrier.
+struct TileItems { uint32_t tptr[2], tlen[2], ttl[2], outl[2]; bool bad; };
+__device__ __forceinline__ void lzd_items(const uint8_t *s_in, uint32_t org, uint32_t c0, uint32_t n, uint32_t vmax, uint8_t *s_cov, TileItems &it) {
+    const uint32_t k0 = c0 + 2 * threadIdx.x;
+    it.bad = false;
+    for (int k = 0; k < 2; k++) {
+        const uint32_t p = k0 + k;
+        it.tptr[k] = 0; it.tlen[k] = 0; it.ttl[k] = 0;
+        if (p >= n || s_in[p - org] != '<') continue;
+        uint32_t ptr, len, text;                                                  // (scalars, not the arrays' elements: fewer VGPRs in k_lzss_mid_dec)
+        const bool ok = lzd_token(s_in, org, p, n, vmax, ptr, len, text);
+        it.tptr[k] = ptr;
+        if (!ok) { it.bad = true; continue; }
+        it.tlen[k] = len; it.ttl[k] = text;
+        for (uint32_t t = 0; t < text; t++) s_cov[p - c0 + t] = 1;
+    }
+    __syncthreads();
+    for (int k = 0; k < 2; k++) { const uint32_t p = k0 + k; it.outl[k] = p < n ? (it.ttl[k] ? it.tlen[k] : (s_cov[p - c0] ? 0u : 1u)) : 0u; }
 }
 
 // Every byte's source inside a tile of `cnt` output bytes that begins at s0: src <- src[src] while it lies in the tile and is not a literal

@@ -42,73 +42,6 @@ __device__ __forceinline__ unsigned long long lds_load8(const uint32_t *sw, uint
     const uint32_t w0 = sw[q], w1 = sw[q + 1], w2 = sw[q + 2];
     return (unsigned long long)__builtin_amdgcn_alignbyte(w1, w0, rel) | ((unsigned long long)__builtin_amdgcn_alignbyte(w2, w1, rel) << 32);   // v_alignbyte uses rel[1:0]
 }
-
-// ---- the hash-chain search of the grouped batch encoders (lzss_mid.hip: a member a workgroup; lzss_tile.hip: a tile a workgroup).  The
-// positions of a sub-tile of SUB threads join the chains of their two-byte keys (head[hash] <- i, ring[i & (RING - 1)] <- the head it
-// replaced), so between sub-tiles a chain is in descending order and inside one in any order.
-constexpr uint32_t CHAIN_NONE = 0xFFFFFFFFu;
-__device__ __forceinline__ uint32_t chain_hash(uint32_t b0, uint32_t b1) { return ((b0 | (b1 << 8)) * 0x9E3779B1u) >> 20; }
-__device__ __forceinline__ uint32_t chain_digits(uint32_t v) { return v < 10 ? 1u : v < 100 ? 2u : v < 1000 ? 3u : v < 10000 ? 4u : 5u; }
-// Position i of an escaped stream of E bytes walks the chain that begins at j: the longest L >= 2 with fc[i, i + L) inside the window
-// (L <= distance <= W, L <= E - i), at its largest distance (lzss.go:166-184,418-421), as L << 16 | distance; 0: none.  s_fc[p - fc0] is
-// the stream's byte p (fc0 a multiple of 4, at or below every position the walk reads: i - W rounded down to a sub-tile), with eleven
-// readable bytes behind the last one a match may reach.  The walk is bounded by the ring, the eight-byte extensions are counted into
-// `steps` and the walk ends once they exceed STEP_CAP: the caller hands the member back then.
-template <uint32_t RING, uint32_t SUB, uint32_t STEP_CAP>
-__device__ __forceinline__ uint32_t chain_best(const uint8_t *s_fc, const uint32_t *s_ring, uint32_t j, uint32_t i, uint32_t E, uint32_t W, uint32_t fc0, uint32_t &steps) {
-    const uint32_t *fw = reinterpret_cast<const uint32_t *>(s_fc);
-    const uint32_t cap = E - i;
-    uint32_t best = 0;
-    if (cap >= 2 && i >= 2) {
-        const uint32_t jlo = i - min(i, W), floor_ = jlo & ~(uint32_t)(SUB - 1);   // (a chain entry below floor_: everything behind it is older still)
-        const unsigned long long pat = lds_load8(fw, i - fc0);
-        for (uint32_t visits = 0; j < E && j >= floor_ && visits < RING && steps <= STEP_CAP; visits++) {
-            const uint32_t nxt = s_ring[j & (RING - 1)];
-            if (j + 2 <= i && j >= jlo) {
-                const uint32_t d = i - j, lim = min(d, cap), bl = best >> 16;
-                // (a candidate counts if it is at least as long as the best so far: the byte at that length decides for most)
-                if (lim >= bl && (bl == 0 || s_fc[j + bl - 1 - fc0] == s_fc[i + bl - 1 - fc0])) {
-                    unsigned long long x = lds_load8(fw, j - fc0) ^ pat;
-                    uint32_t L = x ? (uint32_t)__builtin_ctzll(x) >> 3 : 8u;
-                    if (!x) {
-                        uint32_t off = 8;
-                        while (off < lim) {
-                            x = lds_load8(fw, j + off - fc0) ^ lds_load8(fw, i + off - fc0);
-                            steps++;
-                            if (x) { off += (uint32_t)__builtin_ctzll(x) >> 3; break; }
-                            off += 8;
-                        }
-                        L = off;
-                    }
-                    best = max(best, (min(L, lim) << 16) | d);        // longest, then farthest back (bytes.Index finds the leftmost, lzss.go:419)
-                }
-            }
-            j = nxt;
-        }
-    }
-    return best;
-}
-// exclusive scan of one value per thread over a workgroup of T threads; *total: the sum
-template <int T>
-__device__ __forceinline__ uint32_t chain_scan(uint32_t v, uint32_t *s_wave /*[T / 64 + 1]*/, uint32_t *total) {
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += o; }
-    __syncthreads();                                                      // (the previous scan's readers are done with s_wave)
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        uint32_t w = threadIdx.x < T / 64 ? s_wave[threadIdx.x] : 0u, wi = w;
-#pragma unroll
-        for (int d = 1; d < T / 64; d <<= 1) { const uint32_t o = __shfl_up(wi, d, 64); if (lane >= (uint32_t)d) wi += o; }
-        if (threadIdx.x < T / 64) s_wave[threadIdx.x] = wi - w;
-        if (threadIdx.x == T / 64 - 1) s_wave[T / 64] = wi;
-    }
-    __syncthreads();
-    *total = s_wave[T / 64];
-    return s_wave[wave] + inc - v;
-}
 #endif
 
 // the launches (lzss_match.hip); shmem2: k_match2's dynamic LDS for this window

@@ -20,7 +20,7 @@
 // No loop waits for another workgroup, and every loop is bounded: the chain walk by the ring's size, the extensions by MID_STEP_CAP.
 #include "group_run.h"
 #include "lzss_dec_body.h"
-#include "lzss_match.h"
+#include "lzss_enc_body.h"
 
 namespace rsn {
 namespace {
@@ -62,17 +62,6 @@ static_assert(DL_BYTES <= 160 * 1024 && DL_VAL % 16 == 0 && DL_SRC % 16 == 0 && 
 constexpr uint32_t MID_TOKEN_TEXT = 23;                         // '<' ten digits ',' ten digits '>'
 static_assert(MID_TOKEN_TEXT <= 32, "a token's text spills at most 32 bytes into the next chunk");
 
-__device__ __forceinline__ void mid_done(uint32_t *flag, uint32_t value) {
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// the scan, the hash and the chain walk are lzss_match.h's, shared with the tiled class (lzss_tile.hip)
-__device__ __forceinline__ uint32_t mid_scan(uint32_t v, uint32_t *s_wave /*[MT / 64 + 1]*/, uint32_t *total) { return chain_scan<MT>(v, s_wave, total); }
-__device__ __forceinline__ uint32_t mid_digits(uint32_t v) { return chain_digits(v); }
-__device__ __forceinline__ uint32_t mid_hash(uint32_t b0, uint32_t b1) { return chain_hash(b0, b1); }
-
 // ---------------------------------------------------------------- compress
 __global__ __launch_bounds__(MT) void k_lzss_mid_enc(const SmallMember *__restrict__ tab, uint8_t *__restrict__ base, uint32_t W) {
     extern __shared__ uint4 mid_lds[];
@@ -92,7 +81,7 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_enc(const SmallMember *__restri
     uint8_t *hout = base + m.out_off;
     uint32_t *flag = reinterpret_cast<uint32_t *>(base + m.status_off);
     const uint32_t tid = threadIdx.x, n = m.n;
-    if (n > LZSS_MID_IN_MAX || W == 0 || W > MID_W_MAX) { mid_done(flag, GROUP_BACK); return; }   // (the host does not send these)
+    if (n > LZSS_MID_IN_MAX || W == 0 || W > MID_W_MAX) { block_done(flag, GROUP_BACK); return; }   // (the host does not send these)
     for (uint32_t u = tid; u * 16 < n; u += MT) reinterpret_cast<uint4 *>(sm + EL_IN)[u] = reinterpret_cast<const uint4 *>(hin)[u];   // (pinned host memory, zero behind n)
     for (uint32_t i = tid; i < (E_MAX + E_PAD) / 4; i += MT) reinterpret_cast<uint32_t *>(s_fc)[i] = 0;
     __syncthreads();
@@ -101,13 +90,10 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_enc(const SmallMember *__restri
     {
         const uint32_t per = (n + MT - 1) / MT, i0 = min(n, tid * per), i1 = min(n, i0 + per);
         uint32_t cnt = 0;
-        for (uint32_t i = i0; i < i1; i++) { const uint32_t b = s_in[i]; cnt += (b == 0x5C || b == 0xFF) ? 2u : 1u; }
-        uint32_t at = mid_scan(cnt, s_wave, &E);
-        if (E > E_MAX) { mid_done(flag, GROUP_BACK); return; }                  // (uniform)
-        for (uint32_t i = i0; i < i1; i++) {
-            const uint32_t b = s_in[i];
-            if (b == 0x5C || b == 0xFF) { s_fc[at++] = 0x5C; s_fc[at++] = (uint8_t)b; } else s_fc[at++] = b == 0x3C ? (uint8_t)0xFF : (uint8_t)b;
-        }
+        for (uint32_t i = i0; i < i1; i++) cnt += lzss_esc_len(s_in[i]);
+        uint32_t at = block_scan<MT>(cnt, s_wave, &E);
+        if (E > E_MAX) { block_done(flag, GROUP_BACK); return; }                  // (uniform)
+        for (uint32_t i = i0; i < i1; i++) at = lzss_esc_put(s_fc, at, s_in[i]);
     }
     __syncthreads();                                                              // (the raw member is no longer read: its LDS is the tile's now)
     for (uint32_t i = tid; i < MID_HEADS; i += MT) s_head[i] = MID_NONE;
@@ -120,7 +106,7 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_enc(const SmallMember *__restri
         for (uint32_t sub = 0; sub < MID_TILE; sub += MT) {
             // ---- the sub-tile's positions join their chains.  Between sub-tiles a chain is in descending order; inside one, in any order.
             const uint32_t i = t0 + sub + tid;
-            const uint32_t h = i < E ? mid_hash(s_fc[i], s_fc[i + 1]) : 0u;
+            const uint32_t h = i < E ? chain_hash(s_fc[i], s_fc[i + 1]) : 0u;
             if (i < E) s_ring[i & (MID_RING - 1)] = atomicExch(&s_head[h], i);
             __syncthreads();
             // ---- the longest L >= 2 with fc[i, i + L) inside the window (L <= distance, L <= E - i), at its largest distance
@@ -131,8 +117,9 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_enc(const SmallMember *__restri
             __syncthreads();                                                      // (the next sub-tile's links are written behind this)
         }
         if (!live) { entry -= MID_TILE; continue; }
-        if (__syncthreads_or(steps > MID_STEP_CAP)) { mid_done(flag, GROUP_BACK); return; }
+        if (__syncthreads_or(steps > MID_STEP_CAP)) { block_done(flag, GROUP_BACK); return; }
         // ---- the greedy chain inside the tile: r -> r + max(1, L) (lzss.go:139-142), MID_TILE: beyond the tile
+        // (the kernel's own copy of lzss_greedy_chain: through the helper 256 x 64 KiB measured 1 % slower, above the parent's spread; LEDGER)
         const uint32_t R = min(MID_TILE, E - t0);
         for (uint32_t r = tid; r <= MID_TILE; r += MT) {
             s_jmp[r] = (uint16_t)(r < R ? min(MID_TILE, r + max(1u, s_key[r] >> 16)) : MID_TILE);
@@ -152,30 +139,19 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_enc(const SmallMember *__restri
         uint32_t total = 0;
         {
             const uint32_t r0 = 2 * tid;
-            uint32_t sz[2] = {0, 0}, el[2] = {0, 0};
+            LzssItem it[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};                        // (sz 0: not on the chain)
             for (int k = 0; k < 2; k++) {
                 const uint32_t r = r0 + k;
                 if (r < R && s_on[r]) {
-                    const uint32_t key = s_key[r], L = key >> 16, d = key & 0xFFFFu;
-                    el[k] = L ? 3 + mid_digits(d) + mid_digits(L) : 0u;
-                    sz[k] = L == 0 ? 1u : (el[k] < L ? el[k] : L);
-                    if (r + max(1u, L) >= MID_TILE) s_misc[0] = r + max(1u, L) - MID_TILE;   // (one position of the tile: the chain's last in it)
+                    it[k] = lzss_item(s_key[r] >> 16, s_key[r] & 0xFFFFu);
+                    if (r + max(1u, it[k].L) >= MID_TILE) s_misc[0] = r + max(1u, it[k].L) - MID_TILE;   // (one position of the tile: the chain's last in it)
                 }
             }
-            uint32_t at = carry + mid_scan(sz[0] + sz[1], s_wave, &total);
+            uint32_t at = carry + block_scan<MT>(it[0].sz + it[1].sz, s_wave, &total);
             for (int k = 0; k < 2; k++) {
-                const uint32_t r = r0 + k;
-                if (!sz[k]) continue;
-                const uint32_t key = s_key[r], L = key >> 16, d = key & 0xFFFFu;
-                if (L && el[k] < L) {                                              // "<" + itoa(d) + "," + itoa(L) + ">" (lzss.go:318-320)
-                    uint32_t p = at + el[k];
-                    s_out[--p] = '>';
-                    for (uint32_t v = L; ; v /= 10) { s_out[--p] = (uint8_t)('0' + v % 10); if (v < 10) break; }
-                    s_out[--p] = ',';
-                    for (uint32_t v = d; ; v /= 10) { s_out[--p] = (uint8_t)('0' + v % 10); if (v < 10) break; }
-                    s_out[--p] = '<';
-                } else for (uint32_t q = 0; q < sz[k]; q++) s_out[at + q] = s_fc[t0 + r + q];
-                at += sz[k];
+                if (!it[k].sz) continue;
+                lzss_item_put(s_out, at, it[k], s_fc + t0 + r0 + k);
+                at += it[k].sz;
             }
         }
         __syncthreads();
@@ -190,7 +166,7 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_enc(const SmallMember *__restri
         __syncthreads();
     }
     if (tid == 0 && carry) reinterpret_cast<uint4 *>(hout + flushed)[0] = reinterpret_cast<const uint4 *>(s_out)[0];   // (the slot ends on a whole unit)
-    mid_done(flag, flushed + carry);
+    block_done(flag, flushed + carry);
 }
 
 // ---------------------------------------------------------------- decompress
@@ -207,7 +183,7 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_dec(const SmallMember *__restri
     uint8_t *hout = base + m.out_off;
     uint32_t *flag = reinterpret_cast<uint32_t *>(base + m.status_off);
     const uint32_t tid = threadIdx.x, n = m.n;
-    if (n > E_MAX) { mid_done(flag, GROUP_BACK); return; }                       // (the host does not send these)
+    if (n > E_MAX) { block_done(flag, GROUP_BACK); return; }                       // (the host does not send these)
     for (uint32_t u = tid; u * 16 < n + 32; u += MT) reinterpret_cast<uint4 *>(s_in)[u] = u * 16 < n ? reinterpret_cast<const uint4 *>(hin)[u] : make_uint4(0, 0, 0, 0);
     for (uint32_t i = tid; i < MID_TILE + 64; i += MT) s_cov[i] = 0;
     __syncthreads();
@@ -219,38 +195,25 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_dec(const SmallMember *__restri
             for (uint32_t i = tid; i < MID_TILE + 64; i += MT) s_cov[i] = i < 32 ? (uint8_t)spill : (uint8_t)0;
             __syncthreads();
         }
-        // ---- two bytes of the chunk per thread: a '<' parses its token (lzss.go:331-352) and covers its text
-        const uint32_t k0 = c0 + 2 * tid;
-        uint32_t tptr[2] = {0, 0}, tlen[2] = {0, 0}, ttl[2] = {0, 0};
-        bool bad = false;
-        for (int k = 0; k < 2; k++) {
-            const uint32_t p = k0 + k;
-            if (p >= n || s_in[p] != '<') continue;
-            uint32_t ptr, len, text;                                              // (scalars, not the arrays' elements: the kernel keeps its 55 VGPRs so)
-            const bool ok = lzd_token(s_in, 0u, p, n, E_MAX, ptr, len, text);
-            tptr[k] = ptr;
-            if (!ok) { bad = true; continue; }
-            tlen[k] = len; ttl[k] = text;
-            for (uint32_t t = 0; t < ttl[k]; t++) s_cov[p - c0 + t] = 1;
-        }
-        if (__syncthreads_or(bad)) { mid_done(flag, GROUP_BACK); return; }       // (malformed: the single call words the error)
-        uint32_t outl[2] = {0, 0};
-        for (int k = 0; k < 2; k++) { const uint32_t p = k0 + k; if (p < n) outl[k] = ttl[k] ? tlen[k] : (s_cov[p - c0] ? 0u : 1u); }
+        // ---- the chunk's items, two bytes of it per thread
+        TileItems it;
+        lzd_items(s_in, 0u, c0, n, E_MAX, s_cov, it);
         uint32_t tot;
-        const uint32_t at0 = E + mid_scan(outl[0] + outl[1], s_wave, &tot);
-        if (tot > E_MAX - E) { mid_done(flag, GROUP_BACK); return; }             // expands beyond the limit (uniform; every outl <= E_MAX, 2048 of them: no overflow)
-        bad = (ttl[0] && tptr[0] > at0) || (ttl[1] && tptr[1] > at0 + outl[0]);   // the slice starts before the data (lzss.go:349)
-        if (__syncthreads_or(bad)) { mid_done(flag, GROUP_BACK); return; }
+        const uint32_t at0 = E + block_scan<MT>(it.outl[0] + it.outl[1], s_wave, &tot);
+        if (tot > E_MAX - E) { block_done(flag, GROUP_BACK); return; }             // expands beyond the limit (uniform; every outl <= E_MAX, 2048 of them: no overflow)
+        // malformed (the single call words the error), or the slice starts before the data (lzss.go:349): one answer for both, GROUP_BACK
+        const bool bad = it.bad || (it.ttl[0] && it.tptr[0] > at0) || (it.ttl[1] && it.tptr[1] > at0 + it.outl[0]);
+        if (__syncthreads_or(bad)) { block_done(flag, GROUP_BACK); return; }
         // ---- the chunk's output, a tile at a time in output order
         for (uint32_t s0 = E; s0 < E + tot; s0 += MID_TILE) {
             const uint32_t s1 = min(s0 + MID_TILE, E + tot);
             uint32_t a = at0;
             for (int k = 0; k < 2; k++) {
-                if (!outl[k]) continue;
-                const uint32_t lo = max(a, s0), hi = min(a + outl[k], s1);
-                if (ttl[k]) for (uint32_t q = lo; q < hi; q++) s_src[q - s0] = q - tptr[k];
-                else if (lo < hi) { s_src[a - s0] = a; s_val[a] = s_in[k0 + k]; }
-                a += outl[k];
+                if (!it.outl[k]) continue;
+                const uint32_t lo = max(a, s0), hi = min(a + it.outl[k], s1);
+                if (it.ttl[k]) for (uint32_t q = lo; q < hi; q++) s_src[q - s0] = q - it.tptr[k];
+                else if (lo < hi) { s_src[a - s0] = a; s_val[a] = s_in[c0 + 2 * tid + k]; }
+                a += it.outl[k];
             }
             __syncthreads();
             // every byte's source: src <- src[src] while it lies in the tile and is not a literal (a copied byte lies before the byte that copies it)
@@ -260,18 +223,18 @@ __global__ __launch_bounds__(MT) void k_lzss_mid_dec(const SmallMember *__restri
         }
         E += tot;
     }
-    if (E == 0) { mid_done(flag, GROUP_BACK); return; }                          // (an empty result is the single call's to word)
+    if (E == 0) { block_done(flag, GROUP_BACK); return; }                          // (an empty result is the single call's to word)
     // ---- DecodeOpeningSymbols (lzss.go:391-406): a byte is escaped iff the run of 5C right in front of it has odd length, counted from the
     //      last byte that is not 5C (as lzss_small.hip).  A run of ceil(E / MT) bytes per thread.
     const uint32_t per = (E + MT - 1) / MT, q0 = min(E, tid * per), q1 = min(E, q0 + per);
     const uint32_t before = lzd_plain_before<MT>(lzd_last_plain(s_val, 0u, q0, q1), s_wave);   // 1 + the last position in front of q0 whose byte is not 5C; 0: none
     uint32_t total;
-    const uint32_t o = mid_scan(lzd_unesc_count(s_val, 0u, q0, q1, before), s_wave, &total);
+    const uint32_t o = block_scan<MT>(lzd_unesc_count(s_val, 0u, q0, q1, before), s_wave, &total);
     uint8_t *s_res = s_in;                                                         // (the stream is parsed: its LDS takes the result)
     lzd_unesc_write(s_val, 0u, q0, q1, before, s_res, o);
     __syncthreads();
     for (uint32_t u = tid; u * 16 < total; u += MT) reinterpret_cast<uint4 *>(hout)[u] = reinterpret_cast<const uint4 *>(s_res)[u];
-    mid_done(flag, total);
+    block_done(flag, total);
 }
 
 }  // namespace

@@ -17,12 +17,9 @@
 // of a group packed into pinned memory.
 // What the path does not take returns 1 and goes through the general path, which also words the errors: inputs above the sizes below,
 // streams whose tokens are malformed or point outside the data, outputs above 8 KiB.
-#include <atomic>
-#include <chrono>
-#include <thread>
-
 #include "group_run.h"
-#include "lzss_match.h"
+#include "lzss_dec_body.h"
+#include "lzss_enc_body.h"
 
 namespace rsn {
 namespace {
@@ -36,33 +33,6 @@ constexpr int SLT = 1024;                       // threads of the one block
 // pinned staging of one call: offsets into Ctx::pinned
 constexpr size_t SP_IN = 0, SP_OUT = 4096, SP_FLAG = SP_OUT + SL_DEC_E_MAX + 64, SP_BYTES = SP_FLAG + 64;
 
-__device__ __forceinline__ void sl_done(uint32_t *flag, uint32_t value) {
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// exclusive scan of one value per thread over the block; *total: the sum
-__device__ __forceinline__ uint32_t sl_scan(uint32_t v, uint32_t *s_wave /*[SLT / 64 + 1]*/, uint32_t *total) {
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += o; }
-    __syncthreads();                                                      // (the previous scan's readers are done with s_wave)
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        uint32_t w = threadIdx.x < SLT / 64 ? s_wave[threadIdx.x] : 0u, wi = w;
-#pragma unroll
-        for (int d = 1; d < SLT / 64; d <<= 1) { const uint32_t o = __shfl_up(wi, d, 64); if (lane >= (uint32_t)d) wi += o; }
-        if (threadIdx.x < SLT / 64) s_wave[threadIdx.x] = wi - w;
-        if (threadIdx.x == SLT / 64 - 1) s_wave[SLT / 64] = wi;
-    }
-    __syncthreads();
-    *total = s_wave[SLT / 64];
-    return s_wave[wave] + inc - v;
-}
-
 // 0xFF in every byte of w that equals the byte c (exact per byte)
 __device__ __forceinline__ uint32_t sl_bytes_equal(uint32_t w, uint32_t c) {
     const uint32_t t = w ^ (c * 0x01010101u);
@@ -70,8 +40,6 @@ __device__ __forceinline__ uint32_t sl_bytes_equal(uint32_t w, uint32_t c) {
     return (z >> 7) * 0xFFu;
 }
 constexpr uint32_t SL_STEP_CAP = 4096;          // eight-byte extension steps a thread spends before the call is handed to the general path (runs, short periods: every candidate matches as far as it may)
-
-__device__ __forceinline__ uint32_t sl_digits(uint32_t v) { return v < 10 ? 1u : v < 100 ? 2u : v < 1000 ? 3u : v < 10000 ? 4u : 5u; }
 
 // ---------------------------------------------------------------- compress
 // (r06, measured: the same search spread over sixteen blocks of two wavefronts with the last block to finish walking the chain was no
@@ -97,11 +65,10 @@ __device__ __forceinline__ void lzss_small_enc_body(const uint8_t *__restrict__ 
     {
         const uint32_t i0 = 2 * tid;
         const uint32_t b0 = i0 < n ? s_in[i0] : 0u, b1 = i0 + 1 < n ? s_in[i0 + 1] : 0u;
-        const uint32_t c0 = i0 < n ? ((b0 == 0x5C || b0 == 0xFF) ? 2u : 1u) : 0u, c1 = i0 + 1 < n ? ((b1 == 0x5C || b1 == 0xFF) ? 2u : 1u) : 0u;
-        uint32_t at = sl_scan(c0 + c1, s_wave, &E);
-        if (E > SL_E_MAX) { sl_done(flag, GROUP_BACK); return; }                 // (block-uniform)
-        if (c0 == 2) { s_fc[at++] = 0x5C; s_fc[at++] = (uint8_t)b0; } else if (c0 == 1) s_fc[at++] = b0 == 0x3C ? (uint8_t)0xFF : (uint8_t)b0;
-        if (c1 == 2) { s_fc[at++] = 0x5C; s_fc[at++] = (uint8_t)b1; } else if (c1 == 1) s_fc[at++] = b1 == 0x3C ? (uint8_t)0xFF : (uint8_t)b1;
+        uint32_t at = block_scan<SLT>((i0 < n ? lzss_esc_len(b0) : 0u) + (i0 + 1 < n ? lzss_esc_len(b1) : 0u), s_wave, &E);
+        if (E > SL_E_MAX) { block_done(flag, GROUP_BACK); return; }                 // (block-uniform)
+        if (i0 < n) at = lzss_esc_put(s_fc, at, b0);
+        if (i0 + 1 < n) at = lzss_esc_put(s_fc, at, b1);
     }
     __syncthreads();
     // ---- every position: the longest L >= 1 with fc[i, i + L) inside the window (L <= distance, L <= E - i), at its largest distance.
@@ -149,52 +116,25 @@ __device__ __forceinline__ void lzss_small_enc_body(const uint8_t *__restrict__ 
     }
     if (steps > SL_STEP_CAP) s_bail = 1;
     __syncthreads();
-    if (s_bail) { sl_done(flag, GROUP_BACK); return; }
-    // ---- the greedy chain from 0: i -> i + max(1, L) (lzss.go:139-142), marked by pointer doubling
-    for (uint32_t i = tid; i <= E; i += SLT) {
-        s_jmp[0][i] = (uint16_t)(i < E ? min(E, i + max(1u, s_key[i] >> 16)) : E);
-        s_on[i] = i == 0;
-    }
-    __syncthreads();
-    int cur = 0;
-    for (uint32_t reach = 1; reach < E + 1; reach <<= 1) {                        // after the round: everything within 2 * reach - 1 steps of 0
-        for (uint32_t i = tid; i < E; i += SLT) if (s_on[i]) s_on[s_jmp[cur][i]] = 1;
-        for (uint32_t i = tid; i <= E; i += SLT) s_jmp[cur ^ 1][i] = s_jmp[cur][s_jmp[cur][i]];
-        cur ^= 1;
-        __syncthreads();
-    }
+    if (s_bail) { block_done(flag, GROUP_BACK); return; }
+    // ---- the greedy chain from 0 over the whole stream
+    lzss_greedy_chain<SLT, SL_E_MAX + 1>(s_key, &s_jmp[0][0], s_on, E, E, 0u);
     // ---- what every chain position puts out: a token iff it is shorter than what it stands for (lzss.go:143), else the bytes
     uint32_t total = 0;
     {
         const uint32_t i0 = 2 * tid;
-        uint32_t sz[2] = {0, 0}, el[2] = {0, 0};
+        LzssItem it[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};                            // (sz 0: not on the chain)
+        for (int k = 0; k < 2; k++) if (i0 + k < E && s_on[i0 + k]) it[k] = lzss_item(s_key[i0 + k] >> 16, s_key[i0 + k] & 0xFFFFu);
+        uint32_t at = block_scan<SLT>(it[0].sz + it[1].sz, s_wave, &total);
         for (int k = 0; k < 2; k++) {
-            const uint32_t i = i0 + k;
-            if (i < E && s_on[i]) {
-                const uint32_t key = s_key[i], L = key >> 16, d = key & 0xFFFFu;
-                el[k] = L ? 3 + sl_digits(d) + sl_digits(L) : 0u;
-                sz[k] = L == 0 ? 1u : (el[k] < L ? el[k] : L);
-            }
-        }
-        uint32_t at = sl_scan(sz[0] + sz[1], s_wave, &total);
-        for (int k = 0; k < 2; k++) {
-            const uint32_t i = i0 + k;
-            if (!sz[k]) continue;
-            const uint32_t key = s_key[i], L = key >> 16, d = key & 0xFFFFu;
-            if (L && el[k] < L) {                                                  // "<" + itoa(d) + "," + itoa(L) + ">" (lzss.go:318-320)
-                uint32_t p = at + el[k];
-                s_out[--p] = '>';
-                for (uint32_t v = L; ; v /= 10) { s_out[--p] = (uint8_t)('0' + v % 10); if (v < 10) break; }
-                s_out[--p] = ',';
-                for (uint32_t v = d; ; v /= 10) { s_out[--p] = (uint8_t)('0' + v % 10); if (v < 10) break; }
-                s_out[--p] = '<';
-            } else for (uint32_t q = 0; q < sz[k]; q++) s_out[at + q] = s_fc[i + q];
-            at += sz[k];
+            if (!it[k].sz) continue;
+            lzss_item_put(s_out, at, it[k], s_fc + i0 + k);
+            at += it[k].sz;
         }
     }
     __syncthreads();
     if (tid * 16 < total) reinterpret_cast<uint4 *>(hout)[tid] = reinterpret_cast<const uint4 *>(s_out)[tid];
-    sl_done(flag, total);
+    block_done(flag, total);
 }
 
 // ---------------------------------------------------------------- decompress
@@ -210,41 +150,23 @@ __device__ __forceinline__ void lzss_small_dec_body(const uint8_t *__restrict__ 
     for (uint32_t i = tid; i < SL_DEC_IN_MAX + 32; i += SLT) s_cov[i] = 0;
     if (tid == 0) s_bad = 0;
     __syncthreads();
-    // ---- two input bytes per thread: a '<' parses its token (lzss.go:331-352) and covers its text
-    const uint32_t k0 = 2 * tid;
-    uint32_t tptr[2] = {0, 0}, tlen[2] = {0, 0}, ttl[2] = {0, 0};
-    for (int k = 0; k < 2; k++) {
-        const uint32_t p = k0 + k;
-        if (p >= n || s_in[p] != '<') continue;
-        uint32_t q = p + 1; unsigned long long v = 0; int nd = 0;
-        while (q < n && nd < 10 && s_in[q] >= '0' && s_in[q] <= '9') { v = v * 10 + (s_in[q] - '0'); q++; nd++; }
-        bool ok = nd && q < n && s_in[q] == ',' && v <= 0xFFFFull;
-        tptr[k] = (uint32_t)v; q++; v = 0; nd = 0;
-        while (ok && q < n && nd < 10 && s_in[q] >= '0' && s_in[q] <= '9') { v = v * 10 + (s_in[q] - '0'); q++; nd++; }
-        ok = ok && nd && q < n && s_in[q] == '>' && v <= 0xFFFFull && (uint32_t)v <= tptr[k];   // (len <= ptr: lzss.go:350's slice stays inside the data)
-        if (!ok) { s_bad = 1; continue; }
-        tlen[k] = (uint32_t)v; ttl[k] = q + 1 - p;
-        for (uint32_t t = 0; t < ttl[k]; t++) s_cov[p + t] = 1;
-    }
-    __syncthreads();
-    if (s_bad) { sl_done(flag, GROUP_BACK); return; }                             // (a '<' inside a token's text is a malformed token too: it set s_bad itself or parses as one -- checked below)
-    // a '<' inside another token's text: the outer token's digits would have stopped at it, so it cannot happen once every token parsed
-    uint32_t outl[2] = {0, 0};
-    for (int k = 0; k < 2; k++) { const uint32_t p = k0 + k; if (p < n) outl[k] = ttl[k] ? tlen[k] : (s_cov[p] ? 0u : 1u); }
+    // ---- the stream's items, two bytes of it per thread: the one chunk
+    TileItems it;
+    lzd_items(s_in, 0u, 0u, n, 0xFFFFu, s_cov, it);
     uint32_t E;
-    uint32_t at = sl_scan(outl[0] + outl[1], s_wave, &E);
-    if (E > SL_DEC_E_MAX || E == 0) { sl_done(flag, E == 0 ? 0u : GROUP_BACK); return; }
+    uint32_t at = block_scan<SLT>(it.outl[0] + it.outl[1], s_wave, &E);
+    if (E > SL_DEC_E_MAX || E == 0) { block_done(flag, E == 0 ? 0u : GROUP_BACK); return; }   // (a '<' that is no token counts as a literal: a malformed stream has E >= 1 and is answered below)
+    if (it.bad) s_bad = 1;                                                        // malformed: the general path words the error
     for (int k = 0; k < 2; k++) {
-        const uint32_t p = k0 + k;
-        if (!outl[k]) continue;
-        if (ttl[k]) {
-            if (tptr[k] > at) s_bad = 1;                                           // the slice starts before the data (lzss.go:349)
-            else for (uint32_t t = 0; t < tlen[k]; t++) s_src[0][at + t] = (uint16_t)(at + t - tptr[k]);
-        } else { s_src[0][at] = (uint16_t)at; s_val[at] = s_in[p]; }
-        at += outl[k];
+        if (!it.outl[k]) continue;
+        if (it.ttl[k]) {
+            if (it.tptr[k] > at) s_bad = 1;                                       // the slice starts before the data (lzss.go:349)
+            else for (uint32_t t = 0; t < it.tlen[k]; t++) s_src[0][at + t] = (uint16_t)(at + t - it.tptr[k]);
+        } else { s_src[0][at] = (uint16_t)at; s_val[at] = s_in[2 * tid + k]; }
+        at += it.outl[k];
     }
     __syncthreads();
-    if (s_bad) { sl_done(flag, GROUP_BACK); return; }
+    if (s_bad) { block_done(flag, GROUP_BACK); return; }
     // ---- every byte's literal: src <- src[src] until nothing moves (a copied byte always lies before the byte that copies it)
     int cur = 0;
     for (int round = 0; round < 14; round++) {
@@ -261,6 +183,7 @@ __device__ __forceinline__ void lzss_small_dec_body(const uint8_t *__restrict__ 
     // ---- DecodeOpeningSymbols (lzss.go:391-406): a byte is escaped iff the run of 5C right in front of it has odd length AND that run's
     //      first 5C is itself unescaped -- i.e. counting from the last byte that is not 5C.  last[q] = the last position <= q whose byte is
     //      not 5C (a max-scan); the run in front of q + 1 is q - last[q] long.
+    //      (the unit's own copy of lzss_dec_body.h's lzd_* unescape: through the helpers, three passes over s_val, a single call measured 0.3 to 0.5 us slower; LEDGER)
     uint32_t mine = 0;                                                            // 1 + the last of this thread's eight positions whose byte is not 5C; 0: none
     for (int k = 0; k < 8; k++) { const uint32_t q = 8 * tid + k; if (q < E && s_val[q] != 0x5C) mine = q + 1; }
     uint32_t inc = mine;
@@ -297,12 +220,12 @@ __device__ __forceinline__ void lzss_small_dec_body(const uint8_t *__restrict__ 
         }
     }
     uint32_t total;
-    uint32_t o = sl_scan(cnt, s_wave, &total);
+    uint32_t o = block_scan<SLT>(cnt, s_wave, &total);
     __shared__ __attribute__((aligned(16))) uint8_t s_res[SL_DEC_E_MAX + 16];
     for (int k = 0; k < 8; k++) if (keep[k]) s_res[o++] = (uint8_t)ov[k];
     __syncthreads();
     for (uint32_t u = tid; u * 16 < total; u += SLT) reinterpret_cast<uint4 *>(hout)[u] = reinterpret_cast<const uint4 *>(s_res)[u];
-    sl_done(flag, total);
+    block_done(flag, total);
 }
 
 __global__ __launch_bounds__(SLT) void k_lzss_small_enc(const uint8_t *__restrict__ hin, uint32_t n, uint32_t W, uint8_t *__restrict__ hout, uint32_t *__restrict__ flag) {
@@ -328,61 +251,41 @@ __global__ __launch_bounds__(SLT) void k_lzss_batch_dec(const SmallMember *__res
 bool small_enc_takes(const uint8_t *, size_t n, int64_t window) { return n != 0 && n <= SL_IN_MAX && window <= 0xFFFF; }
 bool small_dec_takes(const uint8_t *, size_t n, int64_t) { return n != 0 && n <= SL_DEC_IN_MAX; }
 
-}  // namespace
-
-// 1: not an input for this path (the caller takes the general one).  *out: the result in the context's pinned staging.
-int lzss_small_compress(Ctx &c, const uint8_t *in, size_t n, int64_t window, const uint8_t **out, size_t *out_n) {
-    if (!small_enc_takes(in, n, window)) return 1;
+// The host side of a single call: the input and `pad` zero bytes behind it into the context's pinned staging, launch(in, out, flag), the
+// wait for the flag.  1: the kernel handed the input back (the caller takes the general path).  *out: the result in the staging.
+template <class Launch>
+int small_call(Ctx &c, const uint8_t *in, size_t n, size_t pad, const uint8_t **out, size_t *out_n, const Launch &launch) {
     int rc = ctx_init(c); if (rc) return rc;
     hipStream_t s = c.own_stream;
     void *pp; rc = pinned_buf(c, SP_BYTES, &pp); if (rc) return rc;
     uint8_t *pin = (uint8_t *)pp;
     memcpy(pin + SP_IN, in, n);
-    memset(pin + SP_IN + n, 0, 16);
+    memset(pin + SP_IN + n, 0, pad);
     uint32_t *flag = (uint32_t *)(pin + SP_FLAG);
     *flag = GROUP_PENDING;
-    RSN_LAUNCH("lzss_small_enc", k_lzss_small_enc, dim3(1), dim3(SLT), 0, s, (const uint8_t *)(pin + SP_IN), (uint32_t)n, (uint32_t)(window <= 0 ? 0 : window), pin + SP_OUT, flag);
+    rc = launch(s, (const uint8_t *)(pin + SP_IN), pin + SP_OUT, flag); if (rc) return rc;
     rc = flags_wait(c, s, flag, 1, "lzss"); if (rc) return rc;
     if (*flag == GROUP_BACK) return 1;
     *out = pin + SP_OUT; *out_n = *flag;
     return RSN_OK;
 }
 
-int flags_wait(Ctx &c, hipStream_t s, const uint32_t *flags, uint32_t n, const char *what) {
-    const volatile uint32_t *vf = flags;
-    auto pending = [&] { uint32_t p = 0; for (uint32_t i = 0; i < n; i++) p |= vf[i] == GROUP_PENDING; return p != 0; };
-    const auto t0 = std::chrono::steady_clock::now();
-    for (uint32_t spins = 1;; spins++) {
-        if (!pending()) { std::atomic_thread_fence(std::memory_order_acquire); return RSN_OK; }
-        if ((spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) {
-            RSN_HIP(hipStreamSynchronize(s));
-            if (pending()) return c.fail(RSN_ERR_DEVICE, "%s: a small-input kernel finished without its answer", what);
-            return RSN_OK;
-        }
-        __builtin_ia32_pause();
-    }
-}
+}  // namespace
 
-int group_wait(Ctx &c, hipStream_t s, const uint8_t *base, const std::vector<uint32_t> &off, uint32_t pending, const char *what) {
-    auto at = [&](size_t k) { return *reinterpret_cast<const volatile uint32_t *>(base + off[k]); };
-    const auto t0 = std::chrono::steady_clock::now();
-    size_t k = 0;                                                                  // every member before k has answered
-    for (uint32_t spins = 1;; spins++) {
-        while (k < off.size() && at(k) != pending) k++;
-        if (k == off.size()) { std::atomic_thread_fence(std::memory_order_acquire); return RSN_OK; }
-        if ((spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) break;
-        __builtin_ia32_pause();
-    }
-    for (;;) {                                                                     // (a large group, or a busy device: the stream, with a limit)
-        const hipError_t e = hipStreamQuery(s);
-        if (e == hipSuccess) break;
-        if (e != hipErrorNotReady) return c.fail(RSN_ERR_DEVICE, "%s: hipStreamQuery: %s", what, hipGetErrorString(e));
-        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) return c.fail(RSN_ERR_DEVICE, "%s: the grouped kernel did not finish within 20 s", what);
-        std::this_thread::sleep_for(std::chrono::microseconds(20));
-    }
-    for (; k < off.size(); k++) if (at(k) == pending) return c.fail(RSN_ERR_DEVICE, "%s: the grouped kernel finished without an answer for one of its members", what);
-    std::atomic_thread_fence(std::memory_order_acquire);
-    return RSN_OK;
+// 1: not an input for this path (the caller takes the general one).  *out: the result in the context's pinned staging.
+int lzss_small_compress(Ctx &c, const uint8_t *in, size_t n, int64_t window, const uint8_t **out, size_t *out_n) {
+    if (!small_enc_takes(in, n, window)) return 1;
+    return small_call(c, in, n, 16, out, out_n, [&](hipStream_t s, const uint8_t *pin, uint8_t *pout, uint32_t *flag) -> int {
+        RSN_LAUNCH("lzss_small_enc", k_lzss_small_enc, dim3(1), dim3(SLT), 0, s, pin, (uint32_t)n, (uint32_t)(window <= 0 ? 0 : window), pout, flag);
+        return RSN_OK;
+    });
+}
+int lzss_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **out, size_t *out_n) {
+    if (!small_dec_takes(in, n, 0)) return 1;
+    return small_call(c, in, n, 32, out, out_n, [&](hipStream_t s, const uint8_t *pin, uint8_t *pout, uint32_t *flag) -> int {
+        RSN_LAUNCH("lzss_small_dec", k_lzss_small_dec, dim3(1), dim3(SLT), 0, s, pin, (uint32_t)n, pout, flag);
+        return RSN_OK;
+    });
 }
 
 // ---------------------------------------------------------------- the two classes of the batch calls (codecs.h; the packers: group_run.h)
@@ -410,23 +313,6 @@ const BatchClass &lzss_small_class(bool compress) {
     static const BatchClass enc = {"lzss small compress", 1, small_enc_takes, class_run<SmallEncClass>, class_run_dev<SmallEncClass>},
                             dec = {"lzss small decompress", 1, small_dec_takes, class_run<SmallDecClass>, class_run_dev<SmallDecClass>};
     return compress ? enc : dec;
-}
-
-int lzss_small_decompress(Ctx &c, const uint8_t *in, size_t n, const uint8_t **out, size_t *out_n) {
-    if (!small_dec_takes(in, n, 0)) return 1;
-    int rc = ctx_init(c); if (rc) return rc;
-    hipStream_t s = c.own_stream;
-    void *pp; rc = pinned_buf(c, SP_BYTES, &pp); if (rc) return rc;
-    uint8_t *pin = (uint8_t *)pp;
-    memcpy(pin + SP_IN, in, n);
-    memset(pin + SP_IN + n, 0, 32);
-    uint32_t *flag = (uint32_t *)(pin + SP_FLAG);
-    *flag = GROUP_PENDING;
-    RSN_LAUNCH("lzss_small_dec", k_lzss_small_dec, dim3(1), dim3(SLT), 0, s, (const uint8_t *)(pin + SP_IN), (uint32_t)n, pin + SP_OUT, flag);
-    rc = flags_wait(c, s, flag, 1, "lzss"); if (rc) return rc;
-    if (*flag == GROUP_BACK) return 1;
-    *out = pin + SP_OUT; *out_n = *flag;
-    return RSN_OK;
 }
 
 }  // namespace rsn

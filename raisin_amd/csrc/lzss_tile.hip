@@ -13,7 +13,7 @@
 //   search   k_lzss_tile_search, a workgroup per escaped tile: fc[t0 - W', t0 + TILE + 4096 + 64) into LDS (W': the window rounded down
 //            to a sub-tile; a match may be as long as its distance, hence the look-ahead), the window's positions linked into the hash
 //            chains without searching them, then the tile's positions linked and searched sub-tile by sub-tile by chain_best
-//            (lzss_match.h) -- the walk k_lzss_mid_enc calls, so the keys are the same keys.  L << 16 | distance of every position goes
+//            (lzss_enc_body.h) -- the walk k_lzss_mid_enc calls, so the keys are the same keys.  L << 16 | distance of every position goes
 //            to scratch.  A tile that exceeds the step cap sets the member's give-up word.
 //   chain    k_lzss_tile_chain, a workgroup per member: a member of which a tile gave up is answered GROUP_BACK.  Otherwise the greedy
 //            chain r -> r + max(1, L) (lzss.go:134-151) tile by tile with the mid kernel's pointer doubling, the entry into a tile where
@@ -27,7 +27,7 @@
 // the step cap or the tiles of a member.  Nothing a launch reads from scratch is left from an earlier group: esc writes the table, the
 // member's words and the stream, search every key below E, chain every offset.
 #include "group_run.h"
-#include "lzss_match.h"
+#include "lzss_enc_body.h"
 #include "lzss_tile_layout.h"
 #include "tile_dev.h"
 
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(TT) void k_lzss_tile_esc(const SmallMember *__restr
     // ---- the member's place: behind the table and the scratch of the members in front of it
     uint32_t mine = 0, before;
     for (uint32_t q = tid; q < blockIdx.x; q += TT) mine += lzt_scr_words(tab[q].n);
-    chain_scan<TT>(mine, s_wave, &before);
+    block_scan<TT>(mine, s_wave, &before);
     const unsigned long long off = (unsigned long long)lzt_front_words(g) + before;
     const bool fits = off + lzt_scr_words(n) <= scr_words;
     if (n == 0 || n > LZSS_TILE_IN_MAX || W == 0 || W > LZT_W_MAX || !fits) {     // (the host does not send these)
@@ -89,16 +89,12 @@ __global__ __launch_bounds__(TT) void k_lzss_tile_esc(const SmallMember *__restr
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
         uint32_t cnt = 0;
 #pragma unroll
-        for (int k = 0; k < 16; k++) { const uint32_t b = (w[k >> 2] >> (8 * (k & 3))) & 0xFF; if ((uint32_t)k < valid) cnt += (b == 0x5C || b == 0xFF) ? 2u : 1u; }
+        for (int k = 0; k < 16; k++) if ((uint32_t)k < valid) cnt += lzss_esc_len((w[k >> 2] >> (8 * (k & 3))) & 0xFF);
         uint32_t tot;
-        uint32_t at = E + chain_scan<TT>(cnt, s_wave, &tot);
+        uint32_t at = E + block_scan<TT>(cnt, s_wave, &tot);
         if (tot > ecap - E) { over = true; break; }                             // (uniform)
 #pragma unroll
-        for (int k = 0; k < 16; k++) {
-            const uint32_t b = (w[k >> 2] >> (8 * (k & 3))) & 0xFF;
-            if ((uint32_t)k >= valid) continue;
-            if (b == 0x5C || b == 0xFF) { fc[at++] = 0x5C; fc[at++] = (uint8_t)b; } else fc[at++] = b == 0x3C ? (uint8_t)0xFF : (uint8_t)b;
-        }
+        for (int k = 0; k < 16; k++) if ((uint32_t)k < valid) at = lzss_esc_put(fc, at, (w[k >> 2] >> (8 * (k & 3))) & 0xFF);
         E += tot;
     }
     if (!over && tid < LZT_FC_PAD) fc[E + tid] = 0;                              // (E <= ecap: the pad lies inside the member's scratch)
@@ -180,6 +176,7 @@ __global__ __launch_bounds__(TT) void k_lzss_tile_chain(const SmallMember *__res
         for (uint32_t r = tid; r < TILE; r += TT) s_key[r] = r < R ? keys[t0 + r] : 0u;
         __syncthreads();
         // ---- the greedy chain inside the tile: r -> r + max(1, L) (lzss.go:139-142), TILE: beyond the tile
+        // (the kernel's own copy of lzss_greedy_chain, as k_lzss_mid_enc's: through the helper 16 x 128 KiB sat above the parent's spread in five runs of seven; LEDGER)
         for (uint32_t r = tid; r <= TILE; r += TT) {
             s_jmp[0][r] = (uint16_t)(r < R ? min(TILE, r + max(1u, s_key[r] >> 16)) : TILE);
             s_on[r] = r == entry;
@@ -198,14 +195,14 @@ __global__ __launch_bounds__(TT) void k_lzss_tile_chain(const SmallMember *__res
         uint32_t sz = 0, total;
         for (uint32_t r = 2 * tid; r < 2 * tid + 2; r++) {
             if (r < R && s_on[r]) {
-                const uint32_t key = s_key[r], L = key >> 16, d = key & 0xFFFFu;
-                const uint32_t el = L ? 3 + chain_digits(d) + chain_digits(L) : 0u;
-                sz += L == 0 ? 1u : (el < L ? el : L);
+                const uint32_t key = s_key[r];                                   // (as the search stored it: LZT_KEY_ON is not set)
+                const LzssItem it = lzss_item(key >> 16, key & 0xFFFFu);
+                sz += it.sz;
                 keys[t0 + r] = key | LZT_KEY_ON;
-                if (r + max(1u, L) >= TILE) s_misc[0] = r + max(1u, L) - TILE;   // (one position of the tile: the chain's last in it)
+                if (r + max(1u, it.L) >= TILE) s_misc[0] = r + max(1u, it.L) - TILE;   // (one position of the tile: the chain's last in it)
             }
         }
-        chain_scan<TT>(sz, s_wave, &total);
+        block_scan<TT>(sz, s_wave, &total);
         out_at += total;
         entry = s_misc[0];
         __syncthreads();
@@ -228,30 +225,17 @@ __global__ __launch_bounds__(TT) void k_lzss_tile_emit(const SmallMember *__rest
     const uint8_t *fc = reinterpret_cast<const uint8_t *>(my + lzt_scr_fc(n));
     const uint32_t off0 = my[LZT_SCR_OFF + t], off1 = my[LZT_SCR_OFF + t + 1], total = my[LZT_SCR_META + LZT_META_TOTAL];
     const uint32_t u0 = lzt_image_first(off0), R = lzt_tile_len(E, t);
-    uint32_t key[2] = {0, 0}, el[2] = {0, 0}, sz[2] = {0, 0};
+    LzssItem it[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};                                // (sz 0: not on the chain)
     for (int k = 0; k < 2; k++) {
-        const uint32_t r = 2 * tid + k;
-        if (r < R) key[k] = keys[t0 + r];
-        if (key[k] & LZT_KEY_ON) {
-            const uint32_t L = (key[k] & ~LZT_KEY_ON) >> 16, d = key[k] & 0xFFFFu;
-            el[k] = L ? 3 + chain_digits(d) + chain_digits(L) : 0u;
-            sz[k] = L == 0 ? 1u : (el[k] < L ? el[k] : L);
-        }
+        const uint32_t r = 2 * tid + k, key = r < R ? keys[t0 + r] : 0u;
+        if (key & LZT_KEY_ON) it[k] = lzss_item((key & ~LZT_KEY_ON) >> 16, key & 0xFFFFu);
     }
     uint32_t sum;
-    uint32_t at = off0 - u0 + chain_scan<TT>(sz[0] + sz[1], s_wave, &sum);
+    uint32_t at = off0 - u0 + block_scan<TT>(it[0].sz + it[1].sz, s_wave, &sum);
     for (int k = 0; k < 2; k++) {
-        if (!sz[k] || at + sz[k] > T_IMG) continue;                              // (the image holds every tile: the assert above)
-        const uint32_t r = 2 * tid + k, L = (key[k] & ~LZT_KEY_ON) >> 16, d = key[k] & 0xFFFFu;
-        if (L && el[k] < L) {                                                    // "<" + itoa(d) + "," + itoa(L) + ">" (lzss.go:318-320)
-            uint32_t p = at + el[k];
-            s_out[--p] = '>';
-            for (uint32_t v = L; ; v /= 10) { s_out[--p] = (uint8_t)('0' + v % 10); if (v < 10) break; }
-            s_out[--p] = ',';
-            for (uint32_t v = d; ; v /= 10) { s_out[--p] = (uint8_t)('0' + v % 10); if (v < 10) break; }
-            s_out[--p] = '<';
-        } else for (uint32_t q = 0; q < sz[k]; q++) s_out[at + q] = fc[t0 + r + q];
-        at += sz[k];
+        if (!it[k].sz || at + it[k].sz > T_IMG) continue;                        // (the image holds every tile: the assert above)
+        lzss_item_put(s_out, at, it[k], fc + t0 + 2 * tid + k);
+        at += it[k].sz;
     }
     __syncthreads();
     // ---- the tile's own bytes out (sum == off1 - off0: chain sized the same items)

@@ -31,7 +31,6 @@
 // position below E.
 #include "group_run.h"
 #include "lzss_dec_body.h"
-#include "lzss_match.h"
 #include "lzss_tile_dec_layout.h"
 #include "tile_dev.h"
 
@@ -53,11 +52,9 @@ __device__ __forceinline__ uint32_t *dec_scr(uint32_t *scr, unsigned long long s
     return lztd_scr_at(q + 1) <= scr_words ? scr + lztd_scr_at(q) : nullptr;
 }
 
-// The items of the stream tile that begins at c0 (a multiple of TILE, below n), two bytes of it a thread, as k_lzss_mid_dec parses a
-// chunk: ttl != 0: a token (its text's length), with ptr and len; outl: the bytes the item gives -- a token's len, 1 for a literal, 0 for
-// a byte of a token's text.  s_in: uint8[D_IN_BYTES], the stream from c0 - LZTD_HALO on (zeros outside it); s_cov: uint8[D_COV_BYTES].
-// bad: a '<' of this thread's is no token.  Ends behind a barrier.
-struct TileItems { uint32_t tptr[2], tlen[2], ttl[2], outl[2]; bool bad; };
+// The items of the stream tile that begins at c0 (a multiple of TILE, below n), as k_lzss_mid_dec parses a chunk (lzss_dec_body.h:
+// lzd_items).  s_in: uint8[D_IN_BYTES], the stream from c0 - LZTD_HALO on (zeros outside it); s_cov: uint8[D_COV_BYTES].  Ends behind a
+// barrier.
 __device__ __forceinline__ void tile_items(const uint8_t *in, uint32_t n, uint32_t c0, uint8_t *s_in, uint8_t *s_cov, TileItems &it) {
     const uint32_t tid = threadIdx.x, org = c0 - LZTD_HALO;                      // (wraps for the first tile: s_in[q - org] is byte q all the same)
     const uint32_t slot = (n + 15) & ~15u;                                       // (the input slot holds whole units)
@@ -74,17 +71,7 @@ __device__ __forceinline__ void tile_items(const uint8_t *in, uint32_t n, uint32
         if (s_in[p - org] == '<' && lzd_token(s_in, org, p, n, LZSS_TILE_DEC_OUT_MAX, ptr, len, ttl))
             for (uint32_t t = c0 - p; t < ttl; t++) s_cov[p + t - c0] = 1;
     }
-    const uint32_t k0 = c0 + 2 * tid;
-    it.bad = false;
-    for (int k = 0; k < 2; k++) {
-        const uint32_t p = k0 + k;
-        it.tptr[k] = 0; it.tlen[k] = 0; it.ttl[k] = 0;
-        if (p >= n || s_in[p - org] != '<') continue;
-        if (!lzd_token(s_in, org, p, n, LZSS_TILE_DEC_OUT_MAX, it.tptr[k], it.tlen[k], it.ttl[k])) { it.bad = true; continue; }
-        for (uint32_t t = 0; t < it.ttl[k]; t++) s_cov[p - c0 + t] = 1;
-    }
-    __syncthreads();
-    for (int k = 0; k < 2; k++) { const uint32_t p = k0 + k; it.outl[k] = p < n ? (it.ttl[k] ? it.tlen[k] : (s_cov[p - c0] ? 0u : 1u)) : 0u; }
+    lzd_items(s_in, org, c0, n, LZSS_TILE_DEC_OUT_MAX, s_cov, it);
 }
 
 // ---------------------------------------------------------------- parse: a workgroup per stream tile
@@ -101,7 +88,7 @@ __global__ __launch_bounds__(TT) void k_lzss_tile_dec_parse(const SmallMember *_
     TileItems it;
     tile_items(base + m.in_off, n, c0, s_in, s_cov, it);
     uint32_t tot;
-    const uint32_t at = chain_scan<TT>(it.outl[0] + it.outl[1], s_wave, &tot);   // (every outl <= OUT_MAX < 2^19, 2048 of them: no overflow)
+    const uint32_t at = block_scan<TT>(it.outl[0] + it.outl[1], s_wave, &tot);   // (every outl <= OUT_MAX < 2^19, 2048 of them: no overflow)
     // a token at the tile's output byte l starts inside the data iff ptr <= first + l: the tile's need is the largest ptr - l
     uint32_t need = 0;
     if (it.ttl[0] && it.tptr[0] > at) need = it.tptr[0] - at;
@@ -130,7 +117,7 @@ __global__ __launch_bounds__(PT) void k_lzss_tile_dec_plan(const SmallMember *__
     const uint32_t T = lztd_tiles(n);
     const uint32_t cnt = tid < T ? my[LZTD_SCR_CNT + tid] : 0u;
     uint32_t E;
-    const uint32_t first = chain_scan<PT>(cnt, s_wave, &E);
+    const uint32_t first = block_scan<PT>(cnt, s_wave, &E);
     const bool bad = tid < T && (my[LZTD_SCR_FLAG + tid] != 0 || my[LZTD_SCR_NEED + tid] > first);
     if (tid < T) { s_first[tid] = first; my[LZTD_SCR_FIRST + tid] = first; }
     if (tid == 0) { s_first[T] = E; my[LZTD_SCR_FIRST + T] = E; }
@@ -172,7 +159,7 @@ __global__ __launch_bounds__(TT) void k_lzss_tile_dec_resolve(const SmallMember 
         TileItems it;
         tile_items(base + m.in_off, n, c0, s_in, s_cov, it);
         uint32_t tot;
-        uint32_t a = first + chain_scan<TT>(it.outl[0] + it.outl[1], s_wave, &tot);
+        uint32_t a = first + block_scan<TT>(it.outl[0] + it.outl[1], s_wave, &tot);
         for (int k = 0; k < 2; k++) {
             if (!it.outl[k]) continue;
             const uint32_t lo = max(a, s0), hi = min(a + it.outl[k], s1);
@@ -225,7 +212,7 @@ __global__ __launch_bounds__(TT) void k_lzss_tile_dec_finish(const SmallMember *
         const uint32_t before = max(plain, lzd_plain_before<TT>(mine, s_wave));
         if (tid == TT - 1) s_last = max(before, mine);
         uint32_t tot;
-        const uint32_t at = chain_scan<TT>(lzd_unesc_count(s_val, s0, q0, q1, before), s_wave, &tot);
+        const uint32_t at = block_scan<TT>(lzd_unesc_count(s_val, s0, q0, q1, before), s_wave, &tot);
         const uint32_t off0 = out_at, off1 = out_at + tot, u0 = lzt_image_first(off0);
         lzd_unesc_write(s_val, s0, q0, q1, before, s_res, off0 - u0 + at);
         __syncthreads();

@@ -7,13 +7,13 @@ plain Python and numpy over oracle/oracle.py.
 
 A case is (name, members, window, expect); `expect` says per member index what the host test proves and the GPU test asserts.
 
-What the search counts (lzss_match.h: chain_best).  Position i meets the candidates j of its two-byte chain with 2 <= d = i - j <= min(i, W).
+What the search counts (lzss_enc_body.h: chain_best).  Position i meets the candidates j of its two-byte chain with 2 <= d = i - j <= min(i, W).
 One whose first eight bytes are i's is extended eight bytes at a time while off < lim = min(d, E - i), a step each, the step that finds the
 mismatch included: a candidate with a common prefix of lcp bytes costs min(ceil((lim - 8) / 8), lcp // 8) steps -- IF it is extended.  It is
 skipped when it cannot reach the best length so far, and the order of the walk is the chains': sub-tiles of 1024 positions from the
 nearest to the farthest, inside one sub-tile any order.  So the sum over every candidate is an UPPER bound whatever the order.  The LOWER
 bound leaves out the candidates that lie in i's own sub-tile and are shorter than another candidate of i; it takes the candidates of one
-OLDER sub-tile as met nearest first, which is the order the waves of a workgroup link them in but not one the comment in lzss_match.h
+OLDER sub-tile as met nearest first, which is the order the waves of a workgroup link them in but not one the comment in lzss_enc_body.h
 promises.  A thread's figure is the sum over its two positions of a tile, t0 + tid and t0 + 1024 + tid."""
 import functools
 

@@ -35,6 +35,13 @@ def _cases():
     return out
 
 
+def _seam_streams():
+    """A 5C run of either parity that ends exactly where a thread's eight positions, a wavefront's 512 and the block's half of 1024 end,
+    with a dangling escape behind it; streams that give nothing (E = 0); a 5C run in front of a token that copies it."""
+    out = [b"a" * (B - r) + b"\\" * r + b"\xffz\\" for B in (8, 512, 1024) for r in (1, 2, 3, 8, 9)]
+    return out + [b"<0,0>", b"<0,0><0,0>", b"\\<1,1>", b"\\\\<2,2>", b"a\\<1,1>\\"]
+
+
 def test_small_lzss_compress_is_the_oracles(lz, oracle):
     for data in _cases():
         for w in (4096, 16, 100, 0, 1):
@@ -48,17 +55,28 @@ def test_small_lzss_compress_is_the_oracles(lz, oracle):
 
 def test_small_lzss_decompress(lz, oracle):
     """Streams the reference's encoder writes, and hand-written ones: chains of tokens that copy tokens, zero-length tokens, a token of
-    8192 bytes, escapes whose 5C runs cross token seams, a dangling escape; what the path does not take (malformed tokens, pointers
-    before the data, outputs above 8 KiB) comes back from the general path with its error or its bytes."""
+    8192 bytes, escapes whose 5C runs cross token seams, a dangling escape, 5C runs that end on the unescape's thread, wavefront and block
+    seams, empty results; what the path does not take (malformed tokens, pointers before the data, outputs above 8 KiB) comes back from
+    the general path with its error or its bytes.  The seam streams once more as the members of one batch call: one launch."""
     from raisin_amd import RsnError
     streams = [oracle.lzss_compress(d, w) for d in _cases() for w in (4096, 7)]
     streams += [b"a<1,1><1,1><2,2><4,4><8,8>", b"abc<3,3><6,6><12,12>x<1,1>", b"ab<0,0>c<2,0>", b"x" + b"<1,1>" * 400, b"0123456789" * 5 + b"<50,50>" * 40,
                 b"\\\\\\a<1,1>", b"\\", b"a\\", b"\\\xff\xff\\\\<3,2>", b"q" * 2000 + b"<2000,2000><4000,4000>", b"lit>,1<2,1>>"]
+    streams += _seam_streams()
     for c in streams:
         want = oracle.lzss_decompress(c)
         assert lz.Decompress(c) == want, c[:60]
         if len(c) >= 16:
             assert _general("rsn_lzss_decompress_dev", c, len(want) + 64) == want, c[:60]
+    from raisin_amd import _lib
+    _lib.prof_enable(True)
+    _lib.prof_reset()
+    try:
+        got = lz.DecompressBatch(_seam_streams())
+        launches = {k: v[0] for k, v in _lib.prof_get().items() if v[0]}
+    finally:
+        _lib.prof_enable(False)
+    assert got == [oracle.lzss_decompress(c) for c in _seam_streams()] and launches == {"lzss_batch_dec": 1}, launches
     big = b"q" * 2000 + b"<2000,2000>" * 4                      # 10 000 bytes: above what the block expands -- the general path's bytes
     assert lz.Decompress(big) == oracle.lzss_decompress(big)
     for bad, code in ((b"ab<9,2>", -3), (b"<1,1>", -3), (b"abc<2,3>", -3), (b"abc<x,1>", -3), (b"ab<1<1,1>", -3)):
