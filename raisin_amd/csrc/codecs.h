@@ -11,6 +11,7 @@
 #include "huff_parse_small.h"   // (behind the HIP runtime: its functions are __host__ __device__ under hipcc)
 #include "huff_rune_select.h"
 #include "huff_rune_mid_select.h"
+#include "huff_rune_mid_dec_select.h"
 #include "huff_big_layout.h"      // (the tiled classes' layout headers, behind the HIP runtime as well: their limits are stated there and named here)
 #include "huff_big_dec_layout.h"
 #include "lzss_tile_layout.h"
@@ -218,8 +219,8 @@ const BehindClass &huff_rune_class();
 // single one.  Behind the rows of Huffman compress, pool RUNES, listed AHEAD of huff_rune_class (which would send these members to `rest`,
 // where nothing says any more that they were rune members): a call that holds at least HUFF_RUNE_MID_GROUP_MIN such members runs them and
 // leaves the others in the pool; fewer stay in the pool, all of them, and take the single call as every one did before.  Rune members above
-// HUFF_RUNE_MID_IN_MAX (huff_big.hip's hand-backs) are not this class's.  Its streams decode through the single call inside a decompress
-// batch: the rune decoder below ends at HUFF_RUNE_OUT_MAX.  HUFF_RUNE_MID_GROUP_MIN = 16 is the floor, for the reason HUFF_RUNE_GROUP_MIN
+// HUFF_RUNE_MID_IN_MAX (huff_big.hip's hand-backs) are not this class's.  Its streams decode grouped too, through huff_rune_mid_dec_class
+// below (the 16 KiB rune decoder ends at HUFF_RUNE_OUT_MAX).  HUFF_RUNE_MID_GROUP_MIN = 16 is the floor, for the reason HUFF_RUNE_GROUP_MIN
 // gives, not a crossover: at 16 members the grouped route is 6.8 to 11 times as fast as the single calls it replaces, at 20, 32 and 64 KiB,
 // from host and from device buffers, and no count tried (16 to 256) loses at any size, so HUFF_RUNE_MID_IN_MAX stays at the mid class's
 // 65536 (profiles/huff_rune_mid_batch.txt).  Mirrored as raisin_amd.huffman.RUNE_MID_IN_MAX / RUNE_MID_GROUP_MIN.
@@ -234,7 +235,8 @@ const BehindClass &huff_rune_mid_class();
 // bytes than its header promises.  Behind the rows of Huffman decompress, pool REST: the host form plans its candidates with a scan of the
 // header that allocates nothing (parse_rune_light), the device form -- whose candidates are what k_huff_dev_plan answered PARSE_NOT_MINE
 // -- with ONE more plan launch over them where they lie (k_huff_dev_rune_plan: one copy down, one host wait), and it runs when at least
-// HUFF_RUNE_DEC_GROUP_MIN are candidates and as many of them are planned.  What the kernel hands back stays in `rest`.
+// HUFF_RUNE_DEC_GROUP_MIN are candidates and as many of them are planned.  What the kernel hands back stays in `rest`, and so does a rune
+// stream that promises more than HUFF_RUNE_OUT_MAX bytes: huff_rune_mid_dec_class, listed behind this one, is offered it next.
 // HUFF_RUNE_DEC_GROUP_MIN: see DESIGN 4.7 for what was measured.  Mirrored as raisin_amd.huffman.RUNE_OUT_MAX / RUNE_PAY_MAX /
 // RUNE_DEC_GROUP_MIN.
 constexpr bool huff_rune_dec_takes_the_encoder() {
@@ -246,6 +248,29 @@ constexpr bool huff_rune_dec_takes_the_encoder() {
 }
 static_assert(huff_rune_dec_takes_the_encoder(), "header, payload and length of every stream the rune encoder writes are ones the rune decoder takes; valid UTF-8 decodes to the member's own n bytes");
 const BehindClass &huff_rune_dec_class();
+// huff_rune_mid_dec.hip: the way back for what k_huff_mid_rune_enc writes.  A rune stream of at most HUFF_RUNE_MID_STREAM_MAX bytes whose
+// header promises MORE than HUFF_RUNE_OUT_MAX and at most HUFF_RUNE_MID_OUT_MAX bytes from at most HUFF_RUNE_MID_PAY_MAX bytes of payload
+// (huff_rune_mid_dec_select.h) -- the lower bound is the promise, not the payload: a stream that promises less from more than
+// HUFF_RUNE_PAY_MAX bytes, which no encoder writes, stays the single call's -- a workgroup of 1024 threads each in k_huff_mid_rune_dec:
+// the 16 KiB kernel's steps with its code (huff_rune_dec_plan.h, huff_parse_rune.h at ParseRuneMid's limits: counts up to
+// PLAN_RUNE_MID_COUNT_MAX; lane_dec_body at 960 lanes of 576 bits), payload, ranks and image in dynamic LDS, one workgroup to a CU.  It
+// hands back what the 16 KiB class hands back.  Behind the rows of Huffman decompress, pool REST, listed behind huff_rune_dec_class: its
+// candidates are what that class left in `rest` with at least HUFF_RUNE_MID_DEC_PAY_MIN bytes of payload (fewer cannot decode to more than
+// HUFF_RUNE_OUT_MAX), planned as that class plans -- parse_rune_light<ParseRuneMid> on the host, ONE launch of k_huff_dev_rune_mid_plan
+// over what k_huff_dev_plan answered PARSE_NOT_MINE on the device -- and it runs when at least HUFF_RUNE_MID_DEC_GROUP_MIN are candidates
+// and as many of them are planned.  HUFF_RUNE_MID_DEC_GROUP_MIN = 16 is the rune classes' floor (DESIGN 4.7 says what was measured).
+// Mirrored as raisin_amd.huffman.RUNE_MID_OUT_MAX / RUNE_MID_PAY_MAX / RUNE_MID_DEC_GROUP_MIN.
+constexpr bool huff_rune_mid_dec_takes_the_encoder() {
+    for (uint32_t n = HUFF_RUNE_IN_MAX + 1; n <= HUFF_RUNE_MID_IN_MAX; n++) {
+        const uint32_t hdr = (n < 256 ? n : 256u) * 10 + 3, pay = huff_rune_mid_stream_max(n) - hdr;
+        if (n <= HUFF_RUNE_OUT_MAX || n > HUFF_RUNE_MID_OUT_MAX || hdr > HUFF_RUNE_HDR_MAX || pay > HUFF_RUNE_MID_PAY_MAX ||
+            ((n + 3) / 4 + 7) / 8 < HUFF_RUNE_MID_DEC_PAY_MIN ||                  // (a rune is four bytes at most and takes a bit at least: the prefilter passes it)
+            huff_rune_mid_stream_max(n) > HUFF_RUNE_MID_STREAM_MAX) return false;
+    }
+    return true;
+}
+static_assert(huff_rune_mid_dec_takes_the_encoder(), "header, payload and length of every stream the mid-size rune encoder writes are ones the mid-size rune decoder takes; valid UTF-8 promises the member's own n bytes (a lossy member up to 3 n: the single call's above HUFF_RUNE_MID_OUT_MAX)");
+const BehindClass &huff_rune_mid_dec_class();
 // lzss_tile_dec.hip: the way back for what no workgroup holds.  A stream of at most LZSS_TILE_DEC_IN_MAX bytes that expands to at most
 // LZSS_TILE_DEC_OUT_MAX escaped bytes is cut into tiles of LZSS_TILE_POS bytes -- of the stream for the parse, of the escaped output for
 // the copies -- and a group is FOUR launches with nothing on the host between them: a workgroup per stream tile parses its tokens, a
@@ -284,7 +309,7 @@ struct BatchRows {
 };
 inline BatchRows batch_classes(BatchLayer layer, bool compress) {
     static const BatchClass *const huff_enc[] = {&huff_small_class(true), &huff_mid_class(true), &huff_big_class()}, *const huff_dec[] = {&huff_mid_class(false), &huff_big_dec_class(), &huff_small_class(false)};
-    static const BehindClass *const huff_enc_behind[] = {&huff_rune_mid_class(), &huff_rune_class()}, *const huff_dec_behind[] = {&huff_rune_dec_class()}, *const lzss_dec_behind[] = {&lzss_tile_dec_class()};
+    static const BehindClass *const huff_enc_behind[] = {&huff_rune_mid_class(), &huff_rune_class()}, *const huff_dec_behind[] = {&huff_rune_dec_class(), &huff_rune_mid_dec_class()}, *const lzss_dec_behind[] = {&lzss_tile_dec_class()};
     static const BatchClass *const lzss_enc[] = {&lzss_small_class(true), &lzss_mid_class(true), &lzss_tile_class()}, *const lzss_dec[] = {&lzss_small_class(false), &lzss_mid_class(false)};
     if (layer == BatchLayer::HUFFMAN) return compress ? BatchRows(huff_enc, huff_enc_behind) : BatchRows(huff_dec, huff_dec_behind);
     return compress ? BatchRows(lzss_enc) : BatchRows(lzss_dec, lzss_dec_behind);

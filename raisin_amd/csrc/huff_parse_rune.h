@@ -21,6 +21,8 @@
 //              plan_codes<PLAN_RUNE_IDB> for the depths; child[2 * node + bit] = 0x8000 | leaf rank, or the internal node; leaf_rune[rank]
 // expect is in BYTES: what the stream decodes to once every rune is written as string(rune).  Every loop is bounded by the bytes looked
 // at, by the table's slots or by the 510 nodes.
+// The limits named above are the 16 KiB class's, ParseRuneSmall, the default of every function's template argument L; the mid-size
+// decoder (huff_rune_mid_dec.hip) runs the same text at ParseRuneMid's (below).
 #pragma once
 
 #include "huff_parse_small.h"
@@ -40,6 +42,22 @@ constexpr uint32_t PARSE_RUNE_CHILD_MAX = 2 * (PARSE_RUNE_SYMS_MAX - 1);   // en
 constexpr uint32_t PARSE_RUNE_SLOTS = PLAN_RUNE_SLOTS, PARSE_RUNE_EMPTY = 0xFFFFFFFFu; // the table: twice the symbols it may hold; (no rune)
 constexpr uint32_t PARSE_RUNE_ERROR = 0xFFFD;                              // kRuneError (huff_host.h)
 static_assert(PARSE_RUNE_PAY_MAX == 9 * PARSE_RUNE_OUT_MAX / 8 && PARSE_RUNE_OUT_MAX <= PARSE_RUNE_COUNT_MAX, "nine bits a decoded byte; a sum of counts is a count");
+// ---- the limits as a template argument: what differs between the classes that run this parse.  ParseRuneSmall -- the default everywhere
+// below -- is the constants above, k_huff_batch_rune_dec's (huff_rune_dec.hip); ParseRuneMid is k_huff_mid_rune_dec's (huff_rune_mid_dec.hip):
+// 960 lanes of the same 576 bits, a promise of at most 65536 bytes, counts up to PLAN_RUNE_MID_COUNT_MAX.  The header, the table, the
+// alphabet and the tree are the same for both.
+struct ParseRuneSmall {
+    static constexpr uint32_t OUT_MAX = PARSE_RUNE_OUT_MAX, LANES = PARSE_RUNE_LANES, S_MAX = PARSE_RUNE_S_MAX, PAY_MAX = PARSE_RUNE_PAY_MAX;
+    static constexpr uint32_t STREAM_MAX = PARSE_RUNE_STREAM_MAX, COUNT_MAX = PARSE_RUNE_COUNT_MAX;
+};
+struct ParseRuneMid {
+    static constexpr uint32_t OUT_MAX = 65536, LANES = 960, S_MAX = 576, PAY_MAX = LANES * S_MAX / 8;          // HUFF_RUNE_MID_OUT_MAX, _PAY_MAX
+    static constexpr uint32_t STREAM_MAX = PARSE_RUNE_SCAN_MAX + PAY_MAX, COUNT_MAX = PLAN_RUNE_MID_COUNT_MAX;  // HUFF_RUNE_MID_STREAM_MAX
+};
+// the promise, the sum of count * utf8_len <= OUT_MAX, bounds every sum of counts: a heap item count << 9 | id stays one word; and 256
+// symbols of at most COUNT_MAX + 1 counts of 4 bytes do not wrap the word the kernel accumulates them in
+static_assert(ParseRuneMid::OUT_MAX <= ParseRuneMid::COUNT_MAX && ParseRuneMid::OUT_MAX < (1u << 23) && 256ull * (ParseRuneMid::COUNT_MAX + 1) * 4 < (1ull << 32) &&
+              ParseRuneMid::PAY_MAX >= ParseRuneMid::OUT_MAX, "a sum of counts is a count; no wrap; a payload of 8 bits a decoded byte fits the lanes");
 
 struct HuffRunePlan {
     HuffDevBounds b;                   // expect in bytes
@@ -49,7 +67,8 @@ struct HuffRunePlan {
 };
 
 RSN_HD_FN uint32_t parse_rune_scan_limit(uint32_t n) { return n < PARSE_RUNE_SCAN_MAX ? n : PARSE_RUNE_SCAN_MAX; }
-RSN_HD_FN bool parse_rune_length_ok(unsigned long long n) { return n >= 8 && n <= PARSE_RUNE_STREAM_MAX; }
+template <class L = ParseRuneSmall>
+RSN_HD_FN bool parse_rune_length_ok(unsigned long long n) { return n >= 8 && n <= L::STREAM_MAX; }
 
 // the rune that starts at byte i of h[0, end), as Go's `range string` yields it (go_decode_rune, huff_host.cpp; seq_len, huff_utf8.h);
 // only bytes below `end` are asked for
@@ -88,15 +107,15 @@ RSN_HD_FN bool parse_rune_put(uint32_t *key, uint32_t *cnt1, uint32_t *distinct,
     return false;                                                      // (at most half the slots are ever taken: not reached)
 }
 
-// The entries of h[0, sep) into the table; a count saturates at PARSE_RUNE_COUNT_MAX + 1.  h.get(i) is asked for i < sep only.
+// The entries of h[0, sep) into the table; a count saturates at the class's COUNT_MAX + 1.  h.get(i) is asked for i < sep only.
 // false: refused.
-template <class Bytes>
+template <class L = ParseRuneSmall, class Bytes>
 RSN_HD_FN bool parse_rune_scan(const Bytes &h, uint32_t sep, uint32_t *key, uint32_t *cnt1, uint32_t *distinct) {
     uint32_t acc = 0;
     for (uint32_t i = 0; i < sep; i++) {
         const uint32_t ch = h.get(i);
         if (ch != '|') {
-            if (ch >= '0' && ch <= '9') { acc = acc * 10 + (ch - '0'); if (acc > PARSE_RUNE_COUNT_MAX) acc = PARSE_RUNE_COUNT_MAX + 1; }
+            if (ch >= '0' && ch <= '9') { acc = acc * 10 + (ch - '0'); if (acc > L::COUNT_MAX) acc = L::COUNT_MAX + 1; }
             continue;
         }
         const uint32_t f = acc;
@@ -126,12 +145,14 @@ RSN_HD_FN uint32_t parse_rune_write(uint32_t r, uint8_t *out) {
 // one symbol's part of the counts' verdict
 RSN_HD_FN uint32_t parse_rune_bytes(uint32_t r, uint32_t c1) { return (c1 - 1) * plan_rune_utf8_len(r); }
 // the counts' verdict: a distinct runes, one of them >= 0x80, none with a count beyond the limit, expect bytes in all
+template <class L = ParseRuneSmall>
 RSN_HD_FN bool parse_rune_counts_ok(uint32_t a, bool any_high, bool any_over, unsigned long long expect) {
-    return a >= 2 && a <= PARSE_RUNE_SYMS_MAX && any_high && !any_over && expect != 0 && expect <= PARSE_RUNE_OUT_MAX;
+    return a >= 2 && a <= PARSE_RUNE_SYMS_MAX && any_high && !any_over && expect != 0 && expect <= L::OUT_MAX;
 }
 // the stream's bounds (parse_bounds) and the class's lanes
+template <class L = ParseRuneSmall>
 RSN_HD_FN bool parse_rune_bounds(uint32_t n, uint32_t sep, uint32_t diff, HuffDevBounds &p, uint32_t *S, uint32_t *T) {
-    return parse_bounds(n, sep, diff, p) && parse_lanes(p.end - p.p0, PARSE_RUNE_LANES, PARSE_RUNE_S_MAX, S, T);
+    return parse_bounds(n, sep, diff, p) && parse_lanes(p.end - p.p0, L::LANES, L::S_MAX, S, T);
 }
 // a node of plan_tree as an entry of child[]: a leaf's rank, or the internal node
 RSN_HD_FN uint32_t parse_rune_child(uint32_t id, uint32_t a) { return id < a ? 0x8000u | id : id - a; }
@@ -140,35 +161,37 @@ RSN_HD_FN uint32_t parse_rune_child(uint32_t id, uint32_t a) { return id < a ? 0
 // k_huff_dev_rune_plan answers where the stream lies.  The table lives on the caller's stack; in[0, n) is all it reads.  A planned
 // answer may still be handed back by the decoder: the depth of the deepest code needs the tree.
 struct ParseRuneTable { uint32_t key[PARSE_RUNE_SLOTS], cnt1[PARSE_RUNE_SLOTS], distinct; };
+template <class L = ParseRuneSmall>
 inline bool parse_rune_light_serial(const uint8_t *in, unsigned long long n64, ParseRuneTable &t, HuffDevBounds &p, uint32_t *sep_out, uint32_t *S, uint32_t *T) {
     p = HuffDevBounds{};
     p.verdict = PARSE_NOT_MINE;
-    if (!parse_rune_length_ok(n64)) return false;
+    if (!parse_rune_length_ok<L>(n64)) return false;
     const uint32_t n = (uint32_t)n64, limit = parse_rune_scan_limit(n);
     uint32_t sep = PARSE_NONE;
     for (uint32_t i = 0; i + 1 < limit; i++) if (parse_sep_at(in[i], in[i + 1])) { sep = i; break; }
     if (sep == PARSE_NONE || sep + 4 > n) return false;
     for (uint32_t s = 0; s < PARSE_RUNE_SLOTS; s++) { t.key[s] = PARSE_RUNE_EMPTY; t.cnt1[s] = 0; }
     t.distinct = 0;
-    if (!parse_rune_scan(ParseArrayBytes{in}, sep, t.key, t.cnt1, &t.distinct)) return false;
+    if (!parse_rune_scan<L>(ParseArrayBytes{in}, sep, t.key, t.cnt1, &t.distinct)) return false;
     bool high = false, over = false;
     unsigned long long expect = 0;
     for (uint32_t s = 0; s < PARSE_RUNE_SLOTS; s++) {
         if (t.key[s] == PARSE_RUNE_EMPTY) continue;
         high = high || t.key[s] >= 0x80;
-        over = over || t.cnt1[s] - 1 > PARSE_RUNE_COUNT_MAX;
+        over = over || t.cnt1[s] - 1 > L::COUNT_MAX;
         expect += parse_rune_bytes(t.key[s], t.cnt1[s]);
     }
-    if (!parse_rune_counts_ok(t.distinct, high, over, expect) || !parse_rune_bounds(n, sep, in[sep + 2], p, S, T)) return false;
+    if (!parse_rune_counts_ok<L>(t.distinct, high, over, expect) || !parse_rune_bounds<L>(n, sep, in[sep + 2], p, S, T)) return false;
     p.expect = (uint32_t)expect;
     *sep_out = sep;
     return true;
 }
+template <class L = ParseRuneSmall>
 inline HuffDevSummary parse_rune_light(const uint8_t *in, unsigned long long n) {
     ParseRuneTable t;
     HuffDevBounds p;
     uint32_t sep, S, T;
-    if (!parse_rune_light_serial(in, n, t, p, &sep, &S, &T)) return HuffDevSummary{PARSE_NOT_MINE, 0, 0, 0};
+    if (!parse_rune_light_serial<L>(in, n, t, p, &sep, &S, &T)) return HuffDevSummary{PARSE_NOT_MINE, 0, 0, 0};
     return HuffDevSummary{PARSE_PLANNED, p.A0, p.end - p.p0, p.expect};
 }
 
@@ -177,13 +200,14 @@ inline HuffDevSummary parse_rune_light(const uint8_t *in, unsigned long long n) 
 // info (where asked for): what the plan's fields do not say -- the distinct runes and the deepest code also of a stream that is refused for
 // its depth, and the lanes; zeros where the stream is refused before they are known.
 struct ParseRuneInfo { uint32_t a, deepest, S, T; };
+template <class L = ParseRuneSmall>
 inline void parse_rune_plan_serial(const uint8_t *in, unsigned long long n64, HuffRunePlan &plan, ParseRuneInfo *info = nullptr) {
     plan = HuffRunePlan{};
     if (info) *info = ParseRuneInfo{0, 0, 0, 0};
     HuffDevBounds &p = plan.b;
     ParseRuneTable t;
     uint32_t sep, S, T;
-    if (!parse_rune_light_serial(in, n64, t, p, &sep, &S, &T)) return;
+    if (!parse_rune_light_serial<L>(in, n64, t, p, &sep, &S, &T)) return;
     const uint32_t a = t.distinct;
     if (info) { info->a = a; info->S = S; info->T = T; }
     uint32_t rune[PARSE_RUNE_SYMS_MAX], cnt1[PARSE_RUNE_SYMS_MAX];

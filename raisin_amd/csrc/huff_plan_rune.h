@@ -24,7 +24,8 @@ constexpr uint32_t PLAN_RUNE_COUNT_MAX = 16384;                        // a coun
 static_assert(PLAN_RUNE_NODES_MAX <= (1u << PLAN_RUNE_IDB) && ((unsigned long long)PLAN_RUNE_COUNT_MAX << PLAN_RUNE_IDB) < (1ull << 32), "a heap item is one word");
 // ... but for the mid-size class (huff_rune_mid.hip), whose members' counts sum to at most PLAN_RUNE_MID_COUNT_MAX: ranks, tree and codes
 // only ask that a sum of counts and a node id pack into one word, and a count of 65536 still has five digits, as the header's bound has it
-// (tests/huff_rune_mid_plan_test.cpp).  The parser (huff_parse_rune.h) and the decoder keep PLAN_RUNE_COUNT_MAX.
+// (tests/huff_rune_mid_plan_test.cpp).  The parser (huff_parse_rune.h) keeps PLAN_RUNE_COUNT_MAX at its default limits, the 16 KiB
+// decoder's, and takes counts up to this one at the mid-size decoder's (ParseRuneMid; huff_rune_mid_dec.hip).
 constexpr uint32_t PLAN_RUNE_MID_COUNT_MAX = 65536;
 static_assert(PLAN_RUNE_MID_COUNT_MAX < (1u << 23) && ((unsigned long long)PLAN_RUNE_MID_COUNT_MAX << PLAN_RUNE_IDB) < (1ull << 32) && PLAN_RUNE_MID_COUNT_MAX < 100000,
               "every sum of counts stays below 2^23: a heap item count << 9 | id is one word; five digits a count");

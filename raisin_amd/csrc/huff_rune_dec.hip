@@ -3,9 +3,10 @@
 // and round-trip forms).  The byte decoders' plans refuse such a stream; when a call holds HUFF_RUNE_DEC_GROUP_MIN of them they
 // come here instead of taking the single call one by one: ONE launch per group, ONE workgroup of 320 threads per member, and the workgroup
 // makes the plan itself -- the host form and the device form launch the same kernel and neither ships a tree:
-//   header   the member's first min(n, PARSE_RUNE_SCAN_MAX) bytes into LDS; the separator by a block-wide minimum; ONE lane scans the
-//            entries into an LDS table of PARSE_RUNE_SLOTS slots, the encoder's hash -- a later entry for a rune finds its slot and
-//            replaces the count (huff_parse_rune.h: the code the CPU test holds against parse_header);
+//   header   rune_light_plan (huff_rune_dec_plan.h, k_huff_mid_rune_dec's too): the member's first min(n, PARSE_RUNE_SCAN_MAX) bytes into
+//            LDS; the separator by a block-wide minimum; ONE lane's parse_rune_scan(...) puts the entries into an LDS table of
+//            PARSE_RUNE_SLOTS slots, the encoder's hash -- a later entry for a rune finds its slot and replaces the count
+//            (huff_parse_rune.h: the code the CPU test holds against parse_header);
 //   tree     the symbols compacted, ranked a thread each (plan_rune_ranks over count + 1), and ONE wavefront builds the Go-exact tree of
 //            2 to 256 leaves with the heap, the children and the depths in VGPRs through LaneStore, as the encoder does; the children
 //            become child[] with a leaf's RANK where the byte decoders have its byte;
@@ -24,6 +25,7 @@
 
 #include "huff_small_body.h"
 #include "huff_parse_rune.h"
+#include "huff_rune_dec_plan.h"
 
 namespace rsn {
 namespace {
@@ -31,73 +33,13 @@ namespace {
 static_assert(PARSE_RUNE_HDR_MAX == HUFF_RUNE_HDR_MAX && PARSE_RUNE_OUT_MAX == HUFF_RUNE_OUT_MAX && PARSE_RUNE_PAY_MAX == HUFF_RUNE_PAY_MAX &&
               PARSE_RUNE_STREAM_MAX == HUFF_RUNE_STREAM_MAX && PARSE_RUNE_SYMS_MAX == HUFF_RUNE_SYMS_MAX && PARSE_RUNE_LANES == (uint32_t)DL,
               "huff_parse_rune.h restates the class's limits without its headers");
-static_assert(PARSE_RUNE_SCAN_MAX % 16 != 0, "the unit that holds the pad byte of the last separator looked for is one the header's load fetches");
-
 constexpr int RD_T = DT;                                                       // lane_dec_body's threads: 256 lanes and the wavefront of the first lane
 constexpr int RD_WAVES = RD_T / 64;
-constexpr int RP_T = 256;                                                      // threads of the plan kernel
-constexpr uint32_t RD_HDR_UNITS = (PARSE_RUNE_SCAN_MAX + 15) / 16;             // 16-byte units of the header in LDS
 constexpr uint32_t RD_PAY_WORDS = DL * PARSE_RUNE_S_MAX / 32 + 8;
-constexpr uint32_t RD_TABLE_AT = (RD_HDR_UNITS + 1) * 16;                      // the table behind the header's bytes
-constexpr uint32_t RD_PLAN_BYTES = RD_TABLE_AT + 2 * PARSE_RUNE_SLOTS * 4;
 constexpr uint32_t RD_IMG_BYTES = HUFF_RUNE_OUT_MAX + 16;
 constexpr uint32_t rd_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
 constexpr uint32_t RD_RAW_BYTES = (rd_max(rd_max(RD_PLAN_BYTES, RD_PAY_WORDS * 4), RD_IMG_BYTES) + 15) & ~15u;
-static_assert(PARSE_RUNE_SLOTS == 2 * RP_T && PARSE_RUNE_SLOTS <= 2 * RD_T && PARSE_RUNE_SYMS_MAX <= (uint32_t)RD_T, "two slots a thread, a thread a symbol");
-
-// the header's bytes in LDS, a word fetched for every four consecutive bytes asked for
-struct LdsBytes {
-    const uint32_t *w;
-    mutable uint32_t at = PARSE_NONE, cur = 0;
-    __device__ __forceinline__ uint32_t get(uint32_t i) const {
-        if ((i >> 2) != at) { at = i >> 2; cur = w[at]; }
-        return (cur >> (8 * (i & 3))) & 0xFFu;
-    }
-};
-
-// words of s_w
-enum { W_SEP = 0, W_SCAN_OK, W_EXPECT, W_OVER, W_HIGH, W_DISTINCT, W_ROOT, W_MIN, W_MAX, W_WORDS };
-
-// The plan in front of the tree, by a workgroup of T threads: the stream's first bytes into s_hdr under the gather's rule -- the unit that
-// reaches beyond src + n is masked, nothing at or behind src + n rounded up to 16 is loaded -- the separator, the entries into the table,
-// the counts' verdict and the stream's bounds.  false (the same for every thread): refused.  On return the table holds s_w[W_DISTINCT] runes.
-template <int T>
-__device__ __forceinline__ bool rune_light_plan(const uint8_t *src_bytes, unsigned long long n64, uint4 *s_hdr /*[RD_HDR_UNITS + 1]*/, uint32_t *s_key, uint32_t *s_c1,
-                                                uint32_t *s_w /*[W_WORDS]*/, HuffDevBounds &b, uint32_t *S, uint32_t *Tl) {
-    const uint32_t tid = threadIdx.x;
-    if (!parse_rune_length_ok(n64)) return false;
-    const uint32_t n = (uint32_t)n64, limit = parse_rune_scan_limit(n);
-    {
-        const uint4 *src = reinterpret_cast<const uint4 *>(src_bytes);
-        for (uint32_t u = tid; u * 16 < limit; u += T) s_hdr[u] = unit_head(src[u], n - 16 * u);      // (u * 16 < limit <= n)
-    }
-    for (uint32_t i = tid; i < PARSE_RUNE_SLOTS; i += T) { s_key[i] = PARSE_RUNE_EMPTY; s_c1[i] = 0; }
-    if (tid < W_WORDS) s_w[tid] = tid == W_SEP ? PARSE_NONE : 0u;
-    __syncthreads();
-    const uint8_t *hb = reinterpret_cast<const uint8_t *>(s_hdr);
-    {   // strings.SplitN(content, "\\\n", 2): the first separator among the bytes looked at -- a position at or behind n is never asked
-        uint32_t mine = PARSE_NONE;
-        for (uint32_t i = tid; i + 1 < limit; i += T) if (parse_sep_at(hb[i], hb[i + 1])) { mine = i; break; }
-        if (mine != PARSE_NONE) atomicMin(&s_w[W_SEP], mine);
-    }
-    __syncthreads();
-    const uint32_t sep = s_w[W_SEP];
-    if (sep == PARSE_NONE || sep + 4 > n) return false;
-    if (tid == 0) { LdsBytes h; h.w = reinterpret_cast<const uint32_t *>(s_hdr); s_w[W_SCAN_OK] = parse_rune_scan(h, sep, s_key, s_c1, &s_w[W_DISTINCT]) ? 1u : 0u; }
-    __syncthreads();
-    if (!s_w[W_SCAN_OK]) return false;
-    for (uint32_t i = tid; i < PARSE_RUNE_SLOTS; i += T) {
-        const uint32_t r = s_key[i], c1 = s_c1[i];
-        if (r == PARSE_RUNE_EMPTY) continue;
-        if (c1 - 1 > PARSE_RUNE_COUNT_MAX) s_w[W_OVER] = 1;
-        else atomicAdd(&s_w[W_EXPECT], parse_rune_bytes(r, c1));       // (256 symbols of at most 16384 * 4 bytes: no wrap)
-        if (r >= 0x80) s_w[W_HIGH] = 1;
-    }
-    __syncthreads();
-    if (!parse_rune_counts_ok(s_w[W_DISTINCT], s_w[W_HIGH] != 0, s_w[W_OVER] != 0, s_w[W_EXPECT]) || !parse_rune_bounds(n, sep, hb[sep + 2], b, S, Tl)) return false;
-    b.expect = s_w[W_EXPECT];
-    return true;
-}
+static_assert(PARSE_RUNE_SLOTS <= 2 * RD_T && PARSE_RUNE_SYMS_MAX <= (uint32_t)RD_T, "two slots a thread, a thread a symbol");
 
 __global__ __launch_bounds__(RD_T) void k_huff_batch_rune_dec(const SmallMember *__restrict__ tab, uint8_t *__restrict__ base) {
     __shared__ uint4 s_raw[RD_RAW_BYTES / 16];                      // the header and the table; then the payload's words; then the output image
@@ -177,17 +119,8 @@ __global__ __launch_bounds__(RD_T) void k_huff_batch_rune_dec(const SmallMember 
     block_done(status, total);
 }
 
-// ---- the device form's second plan launch: the light scan where the stream lies, a workgroup a candidate, 16 bytes of summary each
-__global__ __launch_bounds__(RP_T) void k_huff_dev_rune_plan(const PlanEntry *__restrict__ tab, HuffDevSummary *__restrict__ sums) {
-    __shared__ uint4 s_hdr[RD_HDR_UNITS + 1];
-    __shared__ uint32_t s_key[PARSE_RUNE_SLOTS], s_c1[PARSE_RUNE_SLOTS];
-    __shared__ uint32_t s_w[W_WORDS];
-    const PlanEntry e = tab[blockIdx.x];
-    HuffDevBounds b{};
-    uint32_t S = 0, T = 0;
-    const bool planned = rune_light_plan<RP_T>(e.src, e.n, s_hdr, s_key, s_c1, s_w, b, &S, &T);
-    if (threadIdx.x == 0) sums[blockIdx.x] = planned ? HuffDevSummary{PARSE_PLANNED, b.A0, b.end - b.p0, b.expect} : HuffDevSummary{PARSE_NOT_MINE, 0, 0, 0};
-}
+// ---- the device form's second plan launch (huff_rune_dec_plan.h: rune_plan_body), at this class's limits
+__global__ __launch_bounds__(RP_T) void k_huff_dev_rune_plan(const PlanEntry *__restrict__ tab, HuffDevSummary *__restrict__ sums) { rune_plan_body<ParseRuneSmall>(tab, sums); }
 
 int launch_rune_dec(Ctx &c, hipStream_t s, uint32_t g, const SmallMember *tab, uint8_t *base) {
     RSN_LAUNCH("huff_batch_rune_dec", k_huff_batch_rune_dec, dim3(g), dim3(RD_T), 0, s, tab, base);

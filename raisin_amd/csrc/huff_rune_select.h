@@ -27,11 +27,12 @@ size_t rune_class_members(std::vector<size_t> &runes, std::vector<size_t> &rest,
 }
 // ---- the rune decoder, in three steps with the planning between the first two.  The members of `rest` that may be planned at all
 // (may(i): short enough, and in the device form refused by the byte decoders' plan), sorted; none when there are fewer than the minimum.
+// (The minimum and the summaries' predicate are arguments for the mid-size class, huff_rune_mid_dec_select.h; the defaults are this class's.)
 template <class May>
-std::vector<size_t> rune_dec_candidates(const std::vector<size_t> &rest, May may) {
+std::vector<size_t> rune_dec_candidates(const std::vector<size_t> &rest, May may, size_t group_min = HUFF_RUNE_DEC_GROUP_MIN) {
     std::vector<size_t> cand;
     for (size_t i : rest) if (may(i)) cand.push_back(i);
-    if (cand.size() < HUFF_RUNE_DEC_GROUP_MIN) cand.clear();
+    if (cand.size() < group_min) cand.clear();
     std::sort(cand.begin(), cand.end());
     return cand;
 }
@@ -41,12 +42,13 @@ inline bool rune_dec_summary_ok(const HuffDevSummary &v, size_t n) {
 }
 // of the first k candidates those whose summary the class takes, in order: idx, and what each one's header promises
 template <class Len>
-void rune_dec_planned(const std::vector<size_t> &cand, size_t k, const HuffDevSummary *sums, Len len, std::vector<size_t> &idx, std::vector<uint32_t> &expect) {
-    for (size_t q = 0; q < k; q++) if (rune_dec_summary_ok(sums[q], len(cand[q]))) { idx.push_back(cand[q]); expect.push_back(sums[q].expect); }
+void rune_dec_planned(const std::vector<size_t> &cand, size_t k, const HuffDevSummary *sums, Len len, std::vector<size_t> &idx, std::vector<uint32_t> &expect,
+                      bool (*ok)(const HuffDevSummary &, size_t) = rune_dec_summary_ok) {
+    for (size_t q = 0; q < k; q++) if (ok(sums[q], len(cand[q]))) { idx.push_back(cand[q]); expect.push_back(sums[q].expect); }
 }
 // still the minimum of them (idx sorted): they leave `rest`, which is sorted afterwards, and true; fewer: none is taken, idx is emptied
-inline bool rune_dec_leave(std::vector<size_t> &rest, std::vector<size_t> &idx) {
-    if (idx.size() < HUFF_RUNE_DEC_GROUP_MIN) { idx.clear(); return false; }
+inline bool rune_dec_leave(std::vector<size_t> &rest, std::vector<size_t> &idx, size_t group_min = HUFF_RUNE_DEC_GROUP_MIN) {
+    if (idx.size() < group_min) { idx.clear(); return false; }
     std::vector<size_t> others;
     std::sort(rest.begin(), rest.end());
     std::set_difference(rest.begin(), rest.end(), idx.begin(), idx.end(), std::back_inserter(others));

@@ -105,6 +105,8 @@ enum class Slot : int {
     GD_LZSS_TILE_DEC = 59, // LZSS decompress batch, tiled class (lzss_tile_dec.hip; lzss_tile_dec_layout.h): per member of a group its verdict and E, its stream
                         //   tiles' outputs, flags, needs and first output bytes, its output tiles' entries, its escaped image and a descriptor a position --
                         //   written by the parse, plan and resolve launches, read by the finish launch [group_dev]
+    GD_RUNE_MID_PLANS = 60, // Huffman decompress batch on device buffers (huff_rune_mid_dec.hip): the mid-size rune candidates' table entries and their
+                        //   summaries -- written by k_huff_dev_rune_mid_plan, read by the host once; the call's gate gives it back with the plan table [huff_dev]
 };
 constexpr int RING = 3;                                                  // the batch pipeline's depth: RING inputs, RING segments
 constexpr Slot ring_in(int r) { return (Slot)((int)Slot::RING_IN0 + r); }
@@ -130,7 +132,7 @@ constexpr unsigned long long LAYERED_CALL = HOST_CALL | LAYERED;
 constexpr unsigned long long ARITH = slot_mask(S::AR_STATE, S::AR_RAW);   // the arithmetic codec's own: what its device-buffer calls' gate gives back
 constexpr unsigned long long ARITH_HOST = STAGING | ARITH;                // ... and its host-buffer calls', which stage through the staging pair
 constexpr unsigned long long GROUP_DEV = slot_mask(S::GD_STAGE, S::GD_LENS, S::GD_BIG_TILES, S::GD_BIG_DEC, S::GD_LZSS_TILES, S::GD_LZSS_TILE_DEC);   // the grouped kernels' staging on the device: what a class's run of the batch calls on device buffers gives back
-constexpr unsigned long long HUFF_DEV_PLANS = slot_mask(S::GD_PLANS, S::GD_RUNE_PLANS);          // the plan table outlives the classes' runs: the call's own gate gives it back, never a class's
+constexpr unsigned long long HUFF_DEV_PLANS = slot_mask(S::GD_PLANS, S::GD_RUNE_PLANS, S::GD_RUNE_MID_PLANS);          // the plan table outlives the classes' runs: the call's own gate gives it back, never a class's
 constexpr unsigned long long LAYERS_BATCH = slot_mask(S::LB_STAGE, S::LB_A, S::LB_B, S::LB_XA, S::LB_XB);   // the layered batch calls' own
 constexpr unsigned long long LAYERS_BATCH_CALL = LZSS_ENC | LAYERS_BATCH;      // ... and what their gate gives back: the single calls that run inside a step leave the LZSS codecs' scratch
 constexpr unsigned long long ROUNDTRIP_BATCH = slot_mask(S::LB_VERIFY);        // the batch round trip's own: the verify table and the stats block
@@ -147,7 +149,7 @@ static_assert((HUFF_DEV_PLANS & (GROUP_DEV | HUFF_OWN | LZSS_ENC | LZSS_DEC | ST
 static_assert((LAYERS_BATCH & (GROUP_DEV | HUFF_DEV_PLANS | HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED | ARITH)) == 0, "no step of a layered batch call gives an arena back: the next step reads it");
 static_assert((ROUNDTRIP_BATCH & (LAYERS_BATCH | GROUP_DEV | HUFF_DEV_PLANS | HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED | ARITH)) == 0, "no step of either pass gives the verify slot back, and the verify pass regrows no arena it reads");
 static_assert((SUITE_BATCH & (ROUNDTRIP_BATCH | LAYERS_BATCH | GROUP_DEV | HUFF_DEV_PLANS | HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED | ARITH)) == 0, "no step, no verify pass and no other call's gate gives the kept outputs back: a later list of the run still reads them");
-static_assert((int)S::GD_LZSS_TILE_DEC < 64, "a slot is a bit of a 64-bit mask");
+static_assert((int)S::GD_RUNE_MID_PLANS < 64, "a slot is a bit of a 64-bit mask");
 static_assert((ARITH & (HUFF_OWN | LZSS_ENC | LZSS_DEC | STAGING | RINGS | LAYERED)) == 0, "the arithmetic codec shares no slot of its own with another codec or a caller");
 }  // namespace slotset
 
@@ -164,7 +166,7 @@ struct Ctx {
     std::vector<hipEvent_t> free_events;
 
     struct Buf { void *p = nullptr; size_t cap = 0; unsigned long long gen = 0; };   // gen: process-unique number of this allocation (dev_buf) -- an address can come back with other contents
-    enum { N_BUFS = (int)Slot::GD_LZSS_TILE_DEC + 1 };   // (the table above)
+    enum { N_BUFS = (int)Slot::GD_RUNE_MID_PLANS + 1 };   // (the table above)
     Buf bufs[N_BUFS];
     Buf &buf(Slot k) { return bufs[(int)k]; }
     void *pinned = nullptr; size_t pinned_cap = 0;

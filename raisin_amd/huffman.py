@@ -89,16 +89,24 @@ RUNE_DEC_GROUP_MIN = 16
 # The mid-size rune class of the compress batch calls (csrc/huff_rune_mid_select.h HUFF_RUNE_MID_IN_MAX / HUFF_RUNE_MID_GROUP_MIN;
 # csrc/huff_rune_mid.hip): chunks of more than BATCH_COMPRESS_INPUT_MAX and at most RUNE_MID_IN_MAX bytes that hold a byte >= 0x80
 # go a workgroup each through one launch per group when a call holds at least RUNE_MID_GROUP_MIN of them; what it hands back is what the rune
-# class above hands back.  There is no grouped way back yet: inside a decompress batch these streams take the single call's path.
+# class above hands back.
+# The way back (csrc/huff_rune_mid_dec_select.h HUFF_RUNE_MID_OUT_MAX / HUFF_RUNE_MID_PAY_MAX / HUFF_RUNE_MID_DEC_GROUP_MIN;
+# csrc/huff_rune_mid_dec.hip): rune streams that promise more than RUNE_OUT_MAX and at most RUNE_MID_OUT_MAX bytes from at most
+# RUNE_MID_PAY_MAX bytes of payload go a workgroup each through one launch per group when a decompress batch holds at least
+# RUNE_MID_DEC_GROUP_MIN of them.  Every stream the mid-size rune class writes for valid UTF-8 is one of them.
 RUNE_MID_IN_MAX = 65536
 RUNE_MID_GROUP_MIN = 16
+RUNE_MID_OUT_MAX = 65536
+RUNE_MID_PAY_MAX = 69120
+RUNE_MID_DEC_GROUP_MIN = 16
 
 
 def DecompressBatch(streams):
     """Decompress(stream) for every stream of the list in one call (rsn_huffman_decompress_batch): small streams many to a launch, a
     workgroup each; streams of up to MID_PAY_MAX bytes of payload that decode to at most MID_OUT_MAX bytes likewise (csrc/huff_mid.hip)
     when the call holds at least MID_GROUP_MIN of them; streams of a rune alphabet that decode to at most RUNE_OUT_MAX bytes likewise
-    (csrc/huff_rune_dec.hip) when it holds at least RUNE_DEC_GROUP_MIN of them; streams of a byte alphabet that decode to more than MID_OUT_MAX and at most
+    (csrc/huff_rune_dec.hip) when it holds at least RUNE_DEC_GROUP_MIN of them, and those that promise more than that and at most RUNE_MID_OUT_MAX
+    bytes (csrc/huff_rune_mid_dec.hip) when it holds at least RUNE_MID_DEC_GROUP_MIN of them; streams of a byte alphabet that decode to more than MID_OUT_MAX and at most
     BIG_OUT_MAX bytes in tiles, three launches a group (csrc/huff_big_dec.hip), when it holds at least BIG_DEC_GROUP_MIN of them; the rest through the single call's path.  Each result equals Decompress(stream); a failing stream raises for the
     whole list (the message names the lowest failing index: "member <i>: ...")."""
     return _lib.call_batch(_lib.lib().rsn_huffman_decompress_batch, streams)

@@ -1,0 +1,116 @@
+"""The host side of the mid-size grouped rune decoder (raisin_amd/csrc/huff_rune_mid_dec.hip), on any machine: the parse at the
+mid limits against the host's parse_header, build_tree and assign_codes, the default limits against today's constants, and the select
+rules against a brute-force statement (tests/huff_rune_mid_dec_plan_test.cpp: g++ alone, a stand-alone program, once more under the address
+and undefined-behaviour sanitizers); the constants the Python package mirrors; how the class is wired through the shared pieces; and the
+verdict of the CPU model of the lane maps (tests/lane_maps.py, unchanged, with this class's shape) on every member the GPU tests run
+(tests/rune_mid_dec_cases.py)."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+import rune_mid_dec_cases as C
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "raisin_amd", "csrc")
+SANITIZERS = ("-fsanitize=address,undefined", "-fno-sanitize-recover=all")
+
+
+def _run(tmp_path, *flags):
+    if shutil.which("g++") is None:
+        pytest.fail("g++ is needed to build the host tests")
+    exe = str(tmp_path / "huff_rune_mid_dec_plan_test")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", *flags, "-I" + SRC, os.path.join(ROOT, "tests", "huff_rune_mid_dec_plan_test.cpp"),
+                    os.path.join(SRC, "huff_host.cpp"), "-o", exe], check=True, capture_output=True)
+    r = subprocess.run([exe, "400"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.startswith("rune mid dec: ok"), r.stdout
+    w = r.stdout.split()
+    return {w[k]: int(w[k + 1]) for k in (3, 5, 7, 9, 11)}, [int(x) for x in w[w.index("consts") + 1:]]
+
+
+@pytest.mark.parametrize("flags", [(), SANITIZERS], ids=["plain", "sanitizers"])
+def test_parse_and_rules_against_the_host(tmp_path, flags):
+    # a stand-alone program of host code: AddressSanitizer and UBSan link into it directly
+    figures, _ = _run(tmp_path, *flags)
+    # (400 random streams and the 18 edges, each at both sets of limits)
+    assert figures["ok"] >= 2 * (400 + 18) and figures["planned"] >= 200 and figures["trials"] >= 3000 and figures["took"] >= 500 and figures["below"] >= 20, figures
+
+
+def test_mirrored_constants_are_the_headers(tmp_path):
+    from raisin_amd import huffman
+    _, consts = _run(tmp_path)
+    out_max, pay_max, group_min, stream_max, pay_min = consts
+    assert (huffman.RUNE_MID_OUT_MAX, huffman.RUNE_MID_PAY_MAX, huffman.RUNE_MID_DEC_GROUP_MIN) == (out_max, pay_max, group_min) == (65536, 69120, 16)
+    assert pay_max == 960 * 576 // 8 and stream_max == 256 * 10 + 3 + 8 + pay_max and pay_min == 513
+    assert (C.OUT_MAX, C.PAY_MAX, C.N, C.OUT_MIN) == (out_max, pay_max, group_min, huffman.RUNE_OUT_MAX)
+    assert (C.SHAPE.lanes, C.SHAPE.blocks, C.SHAPE.s_max, C.SHAPE.pay_max, C.SHAPE.out_max, C.SHAPE.runes) == (960, 1, 576, pay_max, out_max, True)
+    # the values the other rune tests pin stay
+    assert (huffman.RUNE_GROUP_MIN, huffman.RUNE_SYMS_MAX, huffman.RUNE_OUT_MAX, huffman.RUNE_PAY_MAX, huffman.RUNE_DEC_GROUP_MIN) == (16, 256, 16384, 18432, 16)
+    assert "RUNE_MID_OUT_MAX" in huffman.DecompressBatch.__doc__
+
+
+def test_the_class_is_wired_through_the_shared_pieces():
+    # plain host selection through the 16 KiB class's three steps; both offers choose through it; listed behind the 16 KiB class; the API
+    # unit names no class
+    sel = open(os.path.join(SRC, "huff_rune_mid_dec_select.h")).read()
+    assert [ln.split()[1] for ln in sel.splitlines() if ln.startswith("#include")] == ['"huff_rune_mid_select.h"'] and "hip" not in sel.replace(".hip", "")
+    assert "rune_dec_candidates(" in sel and "rune_dec_planned(" in sel and "rune_dec_leave(" in sel
+    unit = open(os.path.join(SRC, "huff_rune_mid_dec.hip")).read()
+    assert unit.count("rune_mid_dec_candidates(") == 2 and unit.count("rune_mid_dec_leave(") == 2 and unit.count("rune_mid_dec_planned(") == 3
+    assert '"huff_batch_rune_mid_dec"' in unit and '"huff_dev_rune_mid_plan"' in unit and "func_dyn_lds(" in unit and "Slot::GD_RUNE_MID_PLANS" in unit and "asm" not in unit
+    # no count loop, scan, table or tree of its own: the plan in front of the tree and the plan kernel's body are the shared header's, at
+    # this class's limits; the tree is the one wavefront helper; the payload's decoder is the one body
+    assert '#include "huff_rune_dec_plan.h"' in unit and "rune_light_plan<MD_T, ML>(" in unit and "rune_plan_body<ML>(" in unit and "parse_rune_light<ML>(" in unit
+    for own in ("parse_rune_scan", "parse_rune_put", "parse_rune_decode", "parse_sep_at", "plan_tree", "plan_codes", "atomicMin", "atomicAdd", "atomicCAS", "run_path(", "emit_path("):
+        assert own not in unit, own
+    assert unit.count("wave_tree<PLAN_RUNE_IDB>(") == 1 and unit.count("plan_rune_ranks(") == 1 and unit.count("lane_dec_body<") == 1
+    shared = open(os.path.join(SRC, "huff_rune_dec_plan.h")).read()
+    small = open(os.path.join(SRC, "huff_rune_dec.hip")).read()
+    assert shared.count("bool rune_light_plan(") == 1 and shared.count("void rune_plan_body(") == 1 and "rune_light_plan(" not in small.replace("rune_light_plan<RD_T>(", "")
+    assert '#include "huff_rune_dec_plan.h"' in small and "rune_plan_body<ParseRuneSmall>(" in small
+    body = open(os.path.join(SRC, "huff_small_body.h")).read()
+    assert body.count("uint32_t run_path(") == 1 and body.count("void emit_path(") == 1 and body.count("uint32_t lane_dec_body(") == 1
+    parse = open(os.path.join(SRC, "huff_parse_rune.h")).read()
+    assert parse.count("bool parse_rune_scan(") == 1 and parse.count("void parse_rune_plan_serial(") == 1 and "struct ParseRuneMid" in parse
+    rows = open(os.path.join(SRC, "codecs.h")).read()
+    assert "huff_dec_behind[] = {&huff_rune_dec_class(), &huff_rune_mid_dec_class()}" in rows and "huff_rune_mid_dec_takes_the_encoder()" in rows
+    api = open(os.path.join(SRC, "rsn_api.hip")).read()
+    assert "rune_mid" not in api
+    common = open(os.path.join(SRC, "rsn_common.h")).read()
+    assert "GD_RUNE_MID_PLANS = 60," in common and "HUFF_DEV_PLANS = slot_mask(S::GD_PLANS, S::GD_RUNE_PLANS, S::GD_RUNE_MID_PLANS)" in common
+    make = open(os.path.join(SRC, "Makefile")).read()
+    assert "huff_rune_mid_dec.hip" in make and "huff_rune_mid_dec_select.h" in make and "huff_rune_dec_plan.h" in make
+
+
+# ---------------------------------------------------------------- the lane model's verdicts on the GPU tests' members
+@pytest.mark.parametrize("n", C.MODEL_SIZES)
+def test_model_takes_the_texts(n):
+    took, why, S, T = C.verdict_of_member(C.text(n, 0))
+    assert (took, why) == (True, None) and T <= 960
+    assert S == {16385: 96, 16400: 96, 20000: 96, 32768: 160, 40001: 192, 49152: 256, 65535: 320, 65536: 320}[n]
+
+
+def test_model_takes_the_hand_built_members():
+    s, leaves = C.two_kinds(0)
+    assert C.verdict(s, C.table_of(leaves)) == (True, None, 64, 256) and C.payload(s) == 2048
+    assert C.verdict_of_member(C.counter(0)) [:3] == (True, None, 288)
+    s, leaves = C.one_bit(0)
+    assert C.verdict(s, C.table_of(leaves))[:2] == (True, None) and sum(c * len(r.encode()) for c, r in leaves) == 64373
+    assert {len(code) for code in C._codes([(c, ord(r)) for c, r in leaves]).values()} == {1}
+
+
+def test_model_verdicts_of_every_gpu_member():
+    """every variant of every shape: what the GPU tests expect is what the model says, and it says taken -- a hand-back for phases or rounds
+    would be expected back on the GPU, never "either" """
+    for v in range(C.N):
+        for name, s, (took, why) in C.shapes(v) + C.limits_taken(v):
+            assert (took, why) == (True, None), (name, v, why)
+            assert C.payload(s) >= 513 and C.payload(s) <= C.PAY_MAX, (name, v)
+    rows = C.limits_taken(0)
+    assert C.payload(rows[0][1]) == C.PAY_MAX and C.R.DEPTH_OF_Z[57] == 32 and C.R.DEPTH_OF_Z[58] == 33
+    assert C.R.depth(C.R.deep_leaves(57, True, (20000, 20001))) == 32 and C.R.depth(C.R.deep_leaves(58, True, (20000, 20001))) == 33
+    nt = dict(C.not_taken(0))
+    assert C.payload(nt["a payload of 69121 bytes"]) == C.PAY_MAX + 1 and C.payload(nt["promises 16384 from more than 18432 bytes"]) == 18433
+    assert b"65537|a" in nt["a count of 65537"]
