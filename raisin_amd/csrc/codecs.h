@@ -11,7 +11,7 @@
 #include "huff_parse_small.h"   // (behind the HIP runtime: its functions are __host__ __device__ under hipcc)
 #include "huff_rune_select.h"
 #include "huff_rune_mid_select.h"
-#include "huff_rune_mid_dec_select.h"
+#include "huff_parse_rune.h"    // (the rune decoders' limits, named below)
 #include "huff_big_layout.h"      // (the tiled classes' layout headers, behind the HIP runtime as well: their limits are stated there and named here)
 #include "huff_big_dec_layout.h"
 #include "lzss_tile_layout.h"
@@ -229,7 +229,7 @@ const BehindClass &huff_rune_mid_class();
 // in k_huff_batch_rune_dec: the workgroup parses the header itself (huff_parse_rune.h: at most HUFF_RUNE_SYMS_MAX distinct runes, the
 // Go-exact tree in one wavefront), decodes the payload with the byte decoders' lane maps (huff_small_body.h: lane_dec_body) to a leaf rank
 // per symbol, and writes every rune as string(rune).  It takes a stream of at most HUFF_RUNE_STREAM_MAX bytes that promises at most
-// HUFF_RUNE_OUT_MAX bytes from at most HUFF_RUNE_PAY_MAX bytes of payload (group_layout.h) -- so every stream the rune encoder writes for a
+// HUFF_RUNE_OUT_MAX bytes from at most HUFF_RUNE_PAY_MAX bytes of payload (huff_parse_rune.h: ParseRuneSmall) -- so every stream the rune encoder writes for a
 // member of valid UTF-8 is one this decoder takes; a byte that is no UTF-8 comes back as the three bytes of U+FFFD, so a lossy member's
 // stream may promise up to three times the member's size and goes to the single call when that passes HUFF_RUNE_OUT_MAX -- and hands back what the byte decoders hand back, a code beyond 32 bits, and a stream that decodes to more
 // bytes than its header promises.  Behind the rows of Huffman decompress, pool REST: the host form plans its candidates with a scan of the
@@ -250,9 +250,9 @@ static_assert(huff_rune_dec_takes_the_encoder(), "header, payload and length of 
 const BehindClass &huff_rune_dec_class();
 // huff_rune_mid_dec.hip: the way back for what k_huff_mid_rune_enc writes.  A rune stream of at most HUFF_RUNE_MID_STREAM_MAX bytes whose
 // header promises MORE than HUFF_RUNE_OUT_MAX and at most HUFF_RUNE_MID_OUT_MAX bytes from at most HUFF_RUNE_MID_PAY_MAX bytes of payload
-// (huff_rune_mid_dec_select.h) -- the lower bound is the promise, not the payload: a stream that promises less from more than
+// (huff_parse_rune.h: ParseRuneMid) -- the lower bound is the promise, not the payload: a stream that promises less from more than
 // HUFF_RUNE_PAY_MAX bytes, which no encoder writes, stays the single call's -- a workgroup of 1024 threads each in k_huff_mid_rune_dec:
-// the 16 KiB kernel's steps with its code (huff_rune_dec_plan.h, huff_parse_rune.h at ParseRuneMid's limits: counts up to
+// the 16 KiB kernel's steps with its code (huff_rune_dec_body.h: one body, one pair of offers; huff_parse_rune.h at ParseRuneMid's limits: counts up to
 // PLAN_RUNE_MID_COUNT_MAX; lane_dec_body at 960 lanes of 576 bits), payload, ranks and image in dynamic LDS, one workgroup to a CU.  It
 // hands back what the 16 KiB class hands back.  Behind the rows of Huffman decompress, pool REST, listed behind huff_rune_dec_class: its
 // candidates are what that class left in `rest` with at least HUFF_RUNE_MID_DEC_PAY_MIN bytes of payload (fewer cannot decode to more than

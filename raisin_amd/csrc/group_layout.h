@@ -68,12 +68,9 @@ constexpr uint32_t huff_mid_enc_out_slot(uint32_t n) { return (HUFF_HDR_MAX + (7
 constexpr uint32_t HUFF_RUNE_HDR_MAX = 256 * (5 + 1 + 4) + 3;
 constexpr uint32_t huff_rune_stream_max(uint32_t n) { return (n < 256 ? n : 256u) * 10 + 3 + (9 * n + 7) / 8; }
 constexpr uint32_t huff_rune_enc_out_slot(uint32_t n) { return (HUFF_RUNE_HDR_MAX + (9 * n + 7) / 8 + 64 + 15) & ~15u; }   // header + payload in whole words, and the image's slack
-// the rune decoder (huff_rune_dec.hip): a member decodes to at most HUFF_RUNE_OUT_MAX bytes from at most HUFF_RUNE_PAY_MAX bytes of payload --
-// nine bits a decoded byte, what the encoder's bound above writes at most.  Its input slot is the whole stream (the workgroup reads the
+// the rune decoders (huff_rune_dec_body.h; their limits: huff_parse_rune.h, which states HUFF_RUNE_OUT_MAX, _PAY_MAX and _STREAM_MAX -- nine
+// bits a decoded byte, what the encoder's bound above writes at most).  A member's input slot is the whole stream (the workgroup reads the
 // header itself), huff_dec_in_slot of its length; its output slot huff_dec_out_slot of what the header promises.
-constexpr uint32_t HUFF_RUNE_OUT_MAX = 16384;
-constexpr uint32_t HUFF_RUNE_PAY_MAX = 9 * HUFF_RUNE_OUT_MAX / 8;
-constexpr uint32_t HUFF_RUNE_STREAM_MAX = HUFF_RUNE_HDR_MAX + 8 + HUFF_RUNE_PAY_MAX;   // bytes of a stream the class takes
 constexpr size_t huff_dec_in_slot(size_t sn) { return group_round16(sn) + 64; }       // sn: the stream from the 4-byte boundary the kernel reads from
 constexpr size_t huff_dec_out_slot(size_t expect) { return group_round16(expect) + 16; }   // expect: the bytes the header promises
 

@@ -25,39 +25,64 @@
 // decoder (huff_rune_mid_dec.hip) runs the same text at ParseRuneMid's (below).
 #pragma once
 
+#include "group_layout.h"
 #include "huff_parse_small.h"
 #include "huff_plan_rune.h"
 
 namespace rsn {
 
-constexpr uint32_t PARSE_RUNE_HDR_MAX = 256 * (5 + 1 + 4) + 3;             // HUFF_RUNE_HDR_MAX (group_layout.h)
+constexpr uint32_t PARSE_RUNE_HDR_MAX = HUFF_RUNE_HDR_MAX;                 // the longest header the rune encoders write (group_layout.h)
 constexpr uint32_t PARSE_RUNE_SCAN_MAX = PARSE_RUNE_HDR_MAX + 8;           // bytes of a stream the separator is looked for in
-constexpr uint32_t PARSE_RUNE_OUT_MAX = 16384;                             // HUFF_RUNE_OUT_MAX: decoded bytes
+constexpr uint32_t PARSE_RUNE_OUT_MAX = 16384;                             // decoded bytes
 constexpr uint32_t PARSE_RUNE_LANES = 256, PARSE_RUNE_S_MAX = 576;         // the class's lanes: subsequences, bits of one at most
-constexpr uint32_t PARSE_RUNE_PAY_MAX = PARSE_RUNE_LANES * PARSE_RUNE_S_MAX / 8;   // HUFF_RUNE_PAY_MAX: 9 bits a byte of output
-constexpr uint32_t PARSE_RUNE_STREAM_MAX = PARSE_RUNE_SCAN_MAX + PARSE_RUNE_PAY_MAX;
+constexpr uint32_t PARSE_RUNE_PAY_MAX = PARSE_RUNE_LANES * PARSE_RUNE_S_MAX / 8;   // 9 bits a byte of output
+constexpr uint32_t PARSE_RUNE_STREAM_MAX = PARSE_RUNE_SCAN_MAX + PARSE_RUNE_PAY_MAX;   // bytes of a stream the class takes
 constexpr uint32_t PARSE_RUNE_SYMS_MAX = PLAN_RUNE_SYMS_MAX;
 constexpr uint32_t PARSE_RUNE_COUNT_MAX = PLAN_RUNE_COUNT_MAX;
 constexpr uint32_t PARSE_RUNE_CHILD_MAX = 2 * (PARSE_RUNE_SYMS_MAX - 1);   // entries of child[]
 constexpr uint32_t PARSE_RUNE_SLOTS = PLAN_RUNE_SLOTS, PARSE_RUNE_EMPTY = 0xFFFFFFFFu; // the table: twice the symbols it may hold; (no rune)
 constexpr uint32_t PARSE_RUNE_ERROR = 0xFFFD;                              // kRuneError (huff_host.h)
 static_assert(PARSE_RUNE_PAY_MAX == 9 * PARSE_RUNE_OUT_MAX / 8 && PARSE_RUNE_OUT_MAX <= PARSE_RUNE_COUNT_MAX, "nine bits a decoded byte; a sum of counts is a count");
-// ---- the limits as a template argument: what differs between the classes that run this parse.  ParseRuneSmall -- the default everywhere
-// below -- is the constants above, k_huff_batch_rune_dec's (huff_rune_dec.hip); ParseRuneMid is k_huff_mid_rune_dec's (huff_rune_mid_dec.hip):
-// 960 lanes of the same 576 bits, a promise of at most 65536 bytes, counts up to PLAN_RUNE_MID_COUNT_MAX.  The header, the table, the
-// alphabet and the tree are the same for both.
+// ---- a class's limits as a template argument: what differs between the classes that run this parse, each limit stated HERE and nowhere
+// else -- every other name for one (HUFF_RUNE_*, below) is an alias.  ParseRuneSmall -- the default everywhere below -- is the constants
+// above, k_huff_batch_rune_dec's (huff_rune_dec.hip); ParseRuneMid is k_huff_mid_rune_dec's (huff_rune_mid_dec.hip): 960 lanes of 576 bits
+// (k_huff_mid_rune_enc bounds a member's payload by its n <= 65536 bytes, and 960 lanes of 544 bits fall short of that), a promise of at
+// most 65536 bytes, counts up to PLAN_RUNE_MID_COUNT_MAX.  The header, the table, the alphabet and the tree are the same for both.
+// Beside the parse's limits a class states which members of a call it takes (huff_rune_select.h: the three steps that read these):
+//   len_may    may a stream of this length be a candidate at all?
+//   OUT_MIN    the least a taken stream's header promises: the range [OUT_MIN, OUT_MAX] is the class's, whatever the payload
+//   GROUP_MIN  a call holds that many candidates, and as many planned ones, or the class takes none (codecs.h says what was measured)
 struct ParseRuneSmall {
     static constexpr uint32_t OUT_MAX = PARSE_RUNE_OUT_MAX, LANES = PARSE_RUNE_LANES, S_MAX = PARSE_RUNE_S_MAX, PAY_MAX = PARSE_RUNE_PAY_MAX;
     static constexpr uint32_t STREAM_MAX = PARSE_RUNE_STREAM_MAX, COUNT_MAX = PARSE_RUNE_COUNT_MAX;
+    static constexpr uint32_t OUT_MIN = 1;
+    static constexpr size_t GROUP_MIN = 16;
+    static constexpr bool len_may(size_t n) { return n <= STREAM_MAX; }
 };
 struct ParseRuneMid {
-    static constexpr uint32_t OUT_MAX = 65536, LANES = 960, S_MAX = 576, PAY_MAX = LANES * S_MAX / 8;          // HUFF_RUNE_MID_OUT_MAX, _PAY_MAX
-    static constexpr uint32_t STREAM_MAX = PARSE_RUNE_SCAN_MAX + PAY_MAX, COUNT_MAX = PLAN_RUNE_MID_COUNT_MAX;  // HUFF_RUNE_MID_STREAM_MAX
+    static constexpr uint32_t OUT_MAX = 65536, LANES = 960, S_MAX = 576, PAY_MAX = LANES * S_MAX / 8;
+    static constexpr uint32_t STREAM_MAX = PARSE_RUNE_SCAN_MAX + PAY_MAX, COUNT_MAX = PLAN_RUNE_MID_COUNT_MAX;
+    static constexpr uint32_t OUT_MIN = ParseRuneSmall::OUT_MAX + 1;       // (up to there a stream is k_huff_batch_rune_dec's)
+    static constexpr size_t GROUP_MIN = 16;
+    // A symbol takes a bit at least and a rune four bytes at most: fewer than 513 bytes of payload cannot DECODE to OUT_MIN bytes, whatever
+    // the header promises, and in front of the payload lie the separator and the pad byte at least.  Shorter leftovers are no candidates:
+    // they do not count towards the minimum and cost no plan launch.  (One whose header promises more all the same would be an answer of
+    // fewer bytes here; it takes the single call, which gives the same bytes.)
+    static constexpr uint32_t PAY_MIN = ParseRuneSmall::OUT_MAX / 32 + 1;
+    static constexpr bool len_may(size_t n) { return n >= PAY_MIN + 3 && n <= STREAM_MAX; }
 };
 // the promise, the sum of count * utf8_len <= OUT_MAX, bounds every sum of counts: a heap item count << 9 | id stays one word; and 256
 // symbols of at most COUNT_MAX + 1 counts of 4 bytes do not wrap the word the kernel accumulates them in
 static_assert(ParseRuneMid::OUT_MAX <= ParseRuneMid::COUNT_MAX && ParseRuneMid::OUT_MAX < (1u << 23) && 256ull * (ParseRuneMid::COUNT_MAX + 1) * 4 < (1ull << 32) &&
               ParseRuneMid::PAY_MAX >= ParseRuneMid::OUT_MAX, "a sum of counts is a count; no wrap; a payload of 8 bits a decoded byte fits the lanes");
+static_assert(ParseRuneMid::OUT_MAX > ParseRuneSmall::OUT_MAX && (ParseRuneMid::LANES * (ParseRuneMid::S_MAX - 32)) / 8 < ParseRuneMid::OUT_MAX &&
+              ParseRuneSmall::GROUP_MIN >= 16 && ParseRuneMid::GROUP_MIN >= 16 && (ParseRuneMid::PAY_MIN - 1) * 8 * 4 == ParseRuneSmall::OUT_MAX,
+              "above the 16 KiB class; one word less a lane would not hold 8 bits a decoded byte; smaller calls keep their launches; 512 bytes of payload decode to 16384 at most");
+// the names the library, raisin_amd/huffman.py and the tests know the decoders' limits by
+constexpr uint32_t HUFF_RUNE_OUT_MAX = ParseRuneSmall::OUT_MAX, HUFF_RUNE_PAY_MAX = ParseRuneSmall::PAY_MAX, HUFF_RUNE_STREAM_MAX = ParseRuneSmall::STREAM_MAX;
+constexpr uint32_t HUFF_RUNE_MID_OUT_MAX = ParseRuneMid::OUT_MAX, HUFF_RUNE_MID_PAY_MAX = ParseRuneMid::PAY_MAX, HUFF_RUNE_MID_STREAM_MAX = ParseRuneMid::STREAM_MAX;
+constexpr uint32_t HUFF_RUNE_MID_DEC_PAY_MIN = ParseRuneMid::PAY_MIN;
+constexpr size_t HUFF_RUNE_DEC_GROUP_MIN = ParseRuneSmall::GROUP_MIN, HUFF_RUNE_MID_DEC_GROUP_MIN = ParseRuneMid::GROUP_MIN;
 
 struct HuffRunePlan {
     HuffDevBounds b;                   // expect in bytes

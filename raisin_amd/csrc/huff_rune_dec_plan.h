@@ -1,5 +1,5 @@
 // huff_rune_dec_plan.h -- the grouped rune decoders' plan in front of the tree as a workgroup makes it, for the kernels of both classes
-// (huff_rune_dec.hip: k_huff_batch_rune_dec, k_huff_dev_rune_plan; huff_rune_mid_dec.hip: k_huff_mid_rune_dec, k_huff_dev_rune_mid_plan).
+// (huff_rune_dec_body.h: rune_dec_body, k_huff_batch_rune_dec's and k_huff_mid_rune_dec's; k_huff_dev_rune_plan, k_huff_dev_rune_mid_plan).
 // The steps are huff_parse_rune.h's -- the separator by a block-wide minimum, parse_rune_scan(...) by ONE lane into the LDS table, the
 // counts' verdict and the stream's bounds -- at the limits of the class L (ParseRuneSmall, ParseRuneMid); the device form's plan kernels
 // are this and 16 bytes of summary.

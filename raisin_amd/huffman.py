@@ -77,7 +77,7 @@ BIG_DEC_OUT_CAP = 32768
 # of at most BATCH_COMPRESS_INPUT_MAX bytes that hold a byte >= 0x80 -- UTF-8 text, or no UTF-8 at all -- go a workgroup each through one
 # launch per group when a call holds at least RUNE_GROUP_MIN of them; a chunk with more than RUNE_SYMS_MAX distinct runes, or with one, takes
 # the single call's path inside the batch, as every such chunk does in a call with fewer.
-# The way back (csrc/codecs.h HUFF_RUNE_DEC_GROUP_MIN, csrc/group_layout.h HUFF_RUNE_OUT_MAX / HUFF_RUNE_PAY_MAX; csrc/huff_rune_dec.hip): streams
+# The way back (csrc/huff_parse_rune.h HUFF_RUNE_DEC_GROUP_MIN / HUFF_RUNE_OUT_MAX / HUFF_RUNE_PAY_MAX; csrc/huff_rune_dec.hip): streams
 # whose header names a rune >= 0x80, at most RUNE_SYMS_MAX distinct runes, and promises at most RUNE_OUT_MAX bytes from at most RUNE_PAY_MAX
 # bytes of payload go a workgroup each through one launch per group when a decompress batch holds at least RUNE_DEC_GROUP_MIN of them; the
 # others take the single call's path inside the batch.  Every stream the rune class above writes is one of them.
@@ -90,7 +90,7 @@ RUNE_DEC_GROUP_MIN = 16
 # csrc/huff_rune_mid.hip): chunks of more than BATCH_COMPRESS_INPUT_MAX and at most RUNE_MID_IN_MAX bytes that hold a byte >= 0x80
 # go a workgroup each through one launch per group when a call holds at least RUNE_MID_GROUP_MIN of them; what it hands back is what the rune
 # class above hands back.
-# The way back (csrc/huff_rune_mid_dec_select.h HUFF_RUNE_MID_OUT_MAX / HUFF_RUNE_MID_PAY_MAX / HUFF_RUNE_MID_DEC_GROUP_MIN;
+# The way back (csrc/huff_parse_rune.h HUFF_RUNE_MID_OUT_MAX / HUFF_RUNE_MID_PAY_MAX / HUFF_RUNE_MID_DEC_GROUP_MIN;
 # csrc/huff_rune_mid_dec.hip): rune streams that promise more than RUNE_OUT_MAX and at most RUNE_MID_OUT_MAX bytes from at most
 # RUNE_MID_PAY_MAX bytes of payload go a workgroup each through one launch per group when a decompress batch holds at least
 # RUNE_MID_DEC_GROUP_MIN of them.  Every stream the mid-size rune class writes for valid UTF-8 is one of them.

@@ -5,8 +5,8 @@
 //               of 69120 and 69121 bytes, codes of 32 and 33 bits -- and over random alphabets;
 //   the default the same inputs through the default limits and through ParseRuneSmall: bit-identical plans, and the host's answer at the
 //               16 KiB class's figures written out here as numbers;
-//   the rules   huff_rune_mid_dec_select.h against a brute-force statement: the 513-byte prefilter, the promise's lower bound, the minimum,
-//               `rest` untouched below it.
+//   the rules   huff_rune_select.h's one selection at both classes' rules (ParseRuneMid, ParseRuneSmall) against a brute-force statement: the
+//               513-byte prefilter, the promise's lower bound, the minimum, `rest` untouched below it.
 // Built and run by tests/test_huff_rune_mid_dec_host.py, plain and under the address and undefined-behaviour sanitizers.
 // Prints "rune mid dec: ok <streams> planned <k> trials <t> took <t1> below <t2> consts <OUT_MAX> <PAY_MAX> <GROUP_MIN> <STREAM_MAX> <PAY_MIN>" and exits 0, or
 // the first disagreement and 1.
@@ -20,7 +20,7 @@
 
 #include "huff_host.h"
 #include "huff_parse_rune.h"
-#include "huff_rune_mid_dec_select.h"
+#include "huff_rune_select.h"
 
 using namespace rsn;
 
@@ -210,24 +210,29 @@ bool random_streams(std::mt19937_64 &rng, int count) {
     return true;
 }
 
-// ---- the select rules against a brute-force statement
+// ---- the select rules against a brute-force statement: the one selection (huff_rune_select.h) at each class's rules, the statement from
+// the class's figures written out here as numbers
+struct Rules { size_t len_min, stream_max; uint32_t out_min, out_max, pay_max; size_t group_min; };
+constexpr Rules MID_RULES = {513 + 3, MID.stream_max, 16385, 65536, 69120, 16};     // the prefilter: 513 bytes of payload behind separator and pad byte
+constexpr Rules SMALL_RULES = {0, SMALL.stream_max, 1, 16384, 18432, 16};
 struct Member { size_t len; HuffDevSummary sum; bool may; };
 long long g_trials = 0, g_took = 0, g_below = 0;       // trials; those in which members left `rest`; those with candidates and too few planned
 
-bool select_trial(std::mt19937_64 &rng) {
+template <class L>
+bool select_trial(std::mt19937_64 &rng, const Rules &R) {
     g_trials++;
     const size_t n = 1 + rng() % 60;
     static const size_t LENS[] = {8, 515, 516, 517, 21003, 21004, HUFF_RUNE_MID_STREAM_MAX - 1, HUFF_RUNE_MID_STREAM_MAX, HUFF_RUNE_MID_STREAM_MAX + 1, 200000};
-    static const uint32_t EXPECTS[] = {1, 16384, 16385, 40000, 65536, 65537}, SPANS[] = {1, 8 * 18432 + 8, 8 * 69120 - 7, 8 * 69120, 8 * 69120 + 1};
+    static const uint32_t EXPECTS[] = {1, 16384, 16385, 40000, 65536, 65537, 0}, SPANS[] = {1, 8 * 18432 + 8, 8 * 69120 - 7, 8 * 69120, 8 * 69120 + 1, 8 * 18432, 8 * 18432 + 1};
     std::vector<Member> m(n);
     const bool mostly_good = rng() % 2;
     for (Member &x : m) {
         const bool good = mostly_good && rng() % 8 != 0;
-        x.len = good ? 516 + rng() % (HUFF_RUNE_MID_STREAM_MAX - 515) : LENS[rng() % 10];
+        x.len = good ? R.len_min + rng() % (R.stream_max - R.len_min + 1) : LENS[rng() % 10];
         x.sum.verdict = good || rng() % 3 ? PARSE_PLANNED : PARSE_NOT_MINE;
         x.sum.A0 = good || rng() % 4 ? 4 * (uint32_t)(rng() % 128) : 1 + (uint32_t)(rng() % 300000);
-        x.sum.expect = good ? 16385 + (uint32_t)(rng() % (65536 - 16384)) : EXPECTS[rng() % 6];
-        x.sum.span = good ? 1 + (uint32_t)(rng() % (8 * 69120)) : SPANS[rng() % 5];
+        x.sum.expect = good ? R.out_min + (uint32_t)(rng() % (R.out_max - R.out_min + 1)) : EXPECTS[rng() % 7];
+        x.sum.span = good ? 1 + (uint32_t)(rng() % (8 * R.pay_max)) : SPANS[rng() % 7];
         x.may = good || rng() % 4 != 0;
     }
     std::vector<size_t> rest;
@@ -235,14 +240,14 @@ bool select_trial(std::mt19937_64 &rng) {
     std::shuffle(rest.begin(), rest.end(), rng);
     // the statement
     std::vector<size_t> cand_want, idx_want, rest_want = rest;
-    for (size_t i : rest) if (m[i].may && m[i].len >= 513 + 3 && m[i].len <= HUFF_RUNE_MID_STREAM_MAX) cand_want.push_back(i);
+    for (size_t i : rest) if (m[i].may && m[i].len >= R.len_min && m[i].len <= R.stream_max) cand_want.push_back(i);
     std::sort(cand_want.begin(), cand_want.end());
-    if (cand_want.size() < 16) cand_want.clear();
+    if (cand_want.size() < R.group_min) cand_want.clear();
     for (size_t i : cand_want) {
         const HuffDevSummary &v = m[i].sum;
-        if (v.verdict == PARSE_PLANNED && v.A0 % 4 == 0 && v.A0 <= m[i].len && v.expect > 16384 && v.expect <= 65536 && (v.span + 7) / 8 <= 69120) idx_want.push_back(i);
+        if (v.verdict == PARSE_PLANNED && v.A0 % 4 == 0 && v.A0 <= m[i].len && v.expect >= R.out_min && v.expect <= R.out_max && (v.span + 7) / 8 <= R.pay_max) idx_want.push_back(i);
     }
-    if (idx_want.size() < 16) idx_want.clear();
+    if (idx_want.size() < R.group_min) idx_want.clear();
     else {
         rest_want.clear();
         for (size_t i : rest) if (!std::binary_search(idx_want.begin(), idx_want.end(), i)) rest_want.push_back(i);
@@ -250,14 +255,14 @@ bool select_trial(std::mt19937_64 &rng) {
     }
     // the rules, as both offers call them
     auto len = [&](size_t i) { return m[i].len; };
-    const std::vector<size_t> cand = rune_mid_dec_candidates(rest, [&](size_t i) { return m[i].may; }, len);
+    const std::vector<size_t> cand = rune_dec_candidates<L>(rest, [&](size_t i) { return m[i].may; }, len);
     if (cand != cand_want) { printf("select trial %lld: the candidates differ\n", g_trials); return false; }
     std::vector<HuffDevSummary> sums;
     for (size_t i : cand) sums.push_back(m[i].sum);
     std::vector<size_t> idx;
     std::vector<uint32_t> expect;
-    rune_mid_dec_planned(cand, cand.size(), sums.data(), len, idx, expect);
-    const bool left = rune_mid_dec_leave(rest, idx);
+    rune_dec_planned<L>(cand, cand.size(), sums.data(), len, idx, expect);
+    const bool left = rune_dec_leave<L>(rest, idx);
     g_took += left; g_below += !left && !cand.empty();
     if (left != !idx_want.empty() || idx != idx_want || rest != rest_want) { printf("select trial %lld: who leaves `rest` differs\n", g_trials); return false; }
     for (size_t q = 0; q < idx.size(); q++) if (expect[q] != m[idx[q]].sum.expect) { printf("select trial %lld: a promise differs\n", g_trials); return false; }
@@ -270,9 +275,13 @@ int main(int argc, char **argv) {
     const int random_count = argc > 1 ? atoi(argv[1]) : 300;
     std::mt19937_64 rng(0x5EEDull);
     if (!edges(rng) || !random_streams(rng, random_count)) return 1;
-    for (int t = 0; t < 3000; t++) if (!select_trial(rng)) return 1;
+    for (int t = 0; t < 3000; t++) if (!select_trial<ParseRuneMid>(rng, MID_RULES)) return 1;
+    const long long mid_took = g_took, mid_below = g_below;
+    for (int t = 0; t < 3000; t++) if (!select_trial<ParseRuneSmall>(rng, SMALL_RULES)) return 1;
+    if (mid_took < 500 || mid_below < 20 || g_took - mid_took < 500 || g_below - mid_below < 20) { printf("too few trials took or fell below: %lld %lld %lld %lld\n", mid_took, mid_below, g_took, g_below); return 1; }
     // the prefilter's own statement: 512 bytes of payload at a bit a symbol and four bytes a rune promise 16384 bytes, no more
-    if (!rune_mid_dec_len_may(516) || rune_mid_dec_len_may(515) || !rune_mid_dec_len_may(HUFF_RUNE_MID_STREAM_MAX) || rune_mid_dec_len_may(HUFF_RUNE_MID_STREAM_MAX + 1)) { printf("the length rule\n"); return 1; }
+    if (!ParseRuneMid::len_may(516) || ParseRuneMid::len_may(515) || !ParseRuneMid::len_may(HUFF_RUNE_MID_STREAM_MAX) || ParseRuneMid::len_may(HUFF_RUNE_MID_STREAM_MAX + 1)) { printf("the length rule\n"); return 1; }
+    if (!ParseRuneSmall::len_may(0) || !ParseRuneSmall::len_may(HUFF_RUNE_STREAM_MAX) || ParseRuneSmall::len_may(HUFF_RUNE_STREAM_MAX + 1)) { printf("the 16 KiB class's length rule\n"); return 1; }
     printf("rune mid dec: ok %lld planned %lld trials %lld took %lld below %lld consts %u %u %zu %u %u\n", g_streams, g_planned, g_trials, g_took, g_below, HUFF_RUNE_MID_OUT_MAX, HUFF_RUNE_MID_PAY_MAX,
            HUFF_RUNE_MID_DEC_GROUP_MIN, HUFF_RUNE_MID_STREAM_MAX, HUFF_RUNE_MID_DEC_PAY_MIN);
     return 0;

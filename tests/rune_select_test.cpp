@@ -1,5 +1,6 @@
 // Which members the two classes behind the rows take (raisin_amd/csrc/huff_rune_select.h; codecs.h: BehindClass) as plain host code: the
-// rune encoder's rune_class_members and the rune decoder's candidates / planned / leave -- one below the minimum takes none and all join
+// rune encoder's rune_class_members and the rune decoders' candidates / planned / leave, the one selection at the rules of both classes
+// (huff_parse_rune.h: ParseRuneSmall, ParseRuneMid) -- one below the minimum takes none and all join
 // `rest`, exactly the minimum is taken in sorted order, the remainder keeps its order, and members over the size limit never count
 // towards the minimum.  Prints the number of checks it made.
 #include <cstdio>
@@ -7,6 +8,7 @@
 #include <map>
 #include <vector>
 
+#include "huff_parse_rune.h"
 #include "huff_rune_select.h"
 
 using namespace rsn;
@@ -64,49 +66,67 @@ static void test_encoder() {
 
 static HuffDevSummary planned(uint32_t expect, uint32_t A0 = 12, uint32_t span = 64) { return HuffDevSummary{PARSE_PLANNED, A0, span, expect}; }
 
+// the classes' rules as numbers: what the one selection reads out of each
+static_assert(ParseRuneSmall::OUT_MIN == 1 && ParseRuneSmall::OUT_MAX == 16384 && ParseRuneSmall::PAY_MAX == 18432 && ParseRuneSmall::GROUP_MIN == 16 &&
+              ParseRuneSmall::len_may(0) && ParseRuneSmall::len_may(21003) && !ParseRuneSmall::len_may(21004), "the 16 KiB class");
+static_assert(ParseRuneMid::OUT_MIN == 16385 && ParseRuneMid::OUT_MAX == 65536 && ParseRuneMid::PAY_MAX == 69120 && ParseRuneMid::GROUP_MIN == 16 &&
+              !ParseRuneMid::len_may(515) && ParseRuneMid::len_may(516) && ParseRuneMid::len_may(71691) && !ParseRuneMid::len_may(71692), "the mid-size class");
+static_assert(HUFF_RUNE_OUT_MAX == 16384 && HUFF_RUNE_PAY_MAX == 18432 && HUFF_RUNE_DEC_GROUP_MIN == 16 && HUFF_RUNE_STREAM_MAX == 21003, "the names the library knows them by");
+
+// the three steps at the class L's rules
+template <class L>
 static void test_decoder() {
-    const size_t MIN = HUFF_RUNE_DEC_GROUP_MIN;
-    auto len = [](size_t) { return (size_t)100; };
-    // a summary the class takes: planned, A0 a multiple of 4 inside the stream, 1 to HUFF_RUNE_OUT_MAX bytes from at most HUFF_RUNE_PAY_MAX of payload
-    CHECK(rune_dec_summary_ok(planned(1), 100) && rune_dec_summary_ok(planned(HUFF_RUNE_OUT_MAX, 100, 8 * HUFF_RUNE_PAY_MAX), 100));
-    CHECK(!rune_dec_summary_ok(planned(0), 100) && !rune_dec_summary_ok(planned(HUFF_RUNE_OUT_MAX + 1), 100));
-    CHECK(!rune_dec_summary_ok(planned(5, 10), 100) && !rune_dec_summary_ok(planned(5, 104), 100) && !rune_dec_summary_ok(planned(5, 12, 8 * HUFF_RUNE_PAY_MAX + 1), 100));
-    CHECK(!rune_dec_summary_ok(HuffDevSummary{PARSE_NOT_MINE, 12, 64, 5}, 100));
+    const size_t MIN = L::GROUP_MIN;
+    constexpr size_t N = 1000;                                                                 // a length both classes take
+    CHECK(L::len_may(N));
+    auto len = [](size_t) { return N; };
+    auto ok = [](const HuffDevSummary &v, size_t n) { return rune_dec_summary_ok<L>(v, n); };
+    // a summary the class takes: planned, A0 a multiple of 4 inside the stream, L::OUT_MIN to L::OUT_MAX bytes from at most L::PAY_MAX of payload
+    CHECK(ok(planned(L::OUT_MIN), N) && ok(planned(L::OUT_MAX, N, 8 * L::PAY_MAX), N));
+    CHECK(!ok(planned(L::OUT_MIN - 1), N) && !ok(planned(L::OUT_MAX + 1), N));
+    CHECK(!ok(planned(L::OUT_MIN, 10), N) && !ok(planned(L::OUT_MIN, N + 4), N) && !ok(planned(L::OUT_MIN, 12, 8 * L::PAY_MAX + 1), N));
+    CHECK(!ok(HuffDevSummary{PARSE_NOT_MINE, 12, 64, L::OUT_MIN}, N));
     // the candidates: one below the minimum -- none; the minimum -- sorted, whatever rest's order; those that may not be planned never count
     Idx rest;
     for (size_t k = 0; k < MIN + 4; k++) rest.push_back(3 * ((7 * k) % (MIN + 4)));            // a permutation of 0, 3, 6, ...
     auto small = [&](size_t lim) { return [lim](size_t i) { return i < lim; }; };
-    CHECK(rune_dec_candidates(rest, small(3 * (MIN - 1))).empty());
-    Idx cand = rune_dec_candidates(rest, small(3 * MIN));
+    CHECK(rune_dec_candidates<L>(rest, small(3 * (MIN - 1)), len).empty());
+    Idx cand = rune_dec_candidates<L>(rest, small(3 * MIN), len);
     CHECK(cand.size() == MIN);
     for (size_t k = 0; k < MIN; k++) CHECK(cand[k] == 3 * k);
-    CHECK(rune_dec_candidates(Idx(rest.begin(), rest.begin() + MIN - 1), small(1000)).empty());
+    CHECK(rune_dec_candidates<L>(Idx(rest.begin(), rest.begin() + MIN - 1), small(1000), len).empty());
+    // ... and neither do those whose length the class does not take, whatever may() says
+    auto long_from = [&](size_t lim) { return [lim](size_t i) { return i < lim ? N : (size_t)L::STREAM_MAX + 1; }; };
+    CHECK(rune_dec_candidates<L>(rest, small(1000), long_from(3 * (MIN - 1))).empty());
+    CHECK(rune_dec_candidates<L>(rest, small(1000), long_from(3 * MIN)) == cand);
     // planned, among the first k candidates only, in order, with what each promises
-    cand = rune_dec_candidates(rest, small(1000));
+    cand = rune_dec_candidates<L>(rest, small(1000), len);
     CHECK(cand.size() == MIN + 4);
+    const uint32_t P = L::OUT_MIN + 9;
     std::vector<HuffDevSummary> sums;
-    for (size_t q = 0; q < cand.size(); q++) sums.push_back(q == 2 || q == 9 ? HuffDevSummary{PARSE_NOT_MINE, 0, 0, 0} : planned(10 + (uint32_t)q));
+    for (size_t q = 0; q < cand.size(); q++) sums.push_back(q == 2 || q == 9 ? HuffDevSummary{PARSE_NOT_MINE, 0, 0, 0} : planned(P + (uint32_t)q));
     Idx idx; std::vector<uint32_t> expect;
-    rune_dec_planned(cand, 5, sums.data(), len, idx, expect);
-    CHECK((idx == Idx{0, 3, 9, 12}) && (expect == std::vector<uint32_t>{10, 11, 13, 14}));
+    rune_dec_planned<L>(cand, 5, sums.data(), len, idx, expect);
+    CHECK((idx == Idx{0, 3, 9, 12}) && (expect == std::vector<uint32_t>{P, P + 1, P + 3, P + 4}));
     idx.clear(); expect.clear();
-    rune_dec_planned(cand, cand.size(), sums.data(), len, idx, expect);
+    rune_dec_planned<L>(cand, cand.size(), sums.data(), len, idx, expect);
     CHECK(idx.size() == MIN + 2 && expect.size() == idx.size() && std::is_sorted(idx.begin(), idx.end()));
     // still the minimum: they leave rest, which is sorted afterwards and keeps the others
     Idx left = rest;
-    CHECK(rune_dec_leave(left, idx) && idx.size() == MIN + 2);
+    CHECK(rune_dec_leave<L>(left, idx) && idx.size() == MIN + 2);
     CHECK((left == Idx{6, 27}));
     // exactly the minimum leaves too; one fewer: none is taken, idx is emptied, rest stays as it came
     Idx exact(idx.begin(), idx.begin() + MIN), below(idx.begin(), idx.begin() + MIN - 1);
     left = rest;
-    CHECK(rune_dec_leave(left, exact) && exact.size() == MIN && left.size() == 4 && std::is_sorted(left.begin(), left.end()));
+    CHECK(rune_dec_leave<L>(left, exact) && exact.size() == MIN && left.size() == 4 && std::is_sorted(left.begin(), left.end()));
     left = rest;
-    CHECK(!rune_dec_leave(left, below) && below.empty() && left == rest);
+    CHECK(!rune_dec_leave<L>(left, below) && below.empty() && left == rest);
 }
 
 int main() {
     test_encoder();
-    test_decoder();
+    test_decoder<ParseRuneSmall>();
+    test_decoder<ParseRuneMid>();
     std::printf("rune select: %llu checks\n", checks);
     return 0;
 }

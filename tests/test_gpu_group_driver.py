@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 SMALL_GROUP_MIN = 2                                     # huff_small.hip: the small encoder's (the small decoder groups from one member on)
 HB_OUT_MAX = 32768                                      # huff_small_body.h: what k_huff_batch_dec's workgroup decodes at most
-RUNE_STREAM_MAX = 256 * 10 + 3 + 8 + 9 * 16384 // 8     # group_layout.h: HUFF_RUNE_STREAM_MAX
+RUNE_STREAM_MAX = 256 * 10 + 3 + 8 + 9 * 16384 // 8     # huff_parse_rune.h: HUFF_RUNE_STREAM_MAX
 BIG = ("huff_batch_big_count", "huff_batch_big_plan", "huff_batch_big_emit")
 BIG_DEC = ("huff_batch_big_dec_map", "huff_batch_big_dec_chain", "huff_batch_big_dec_emit")
 GROUPED = ("huff_batch_enc", "huff_batch_mid_enc", "huff_batch_rune_enc", "huff_batch_dec", "huff_batch_mid_dec", "huff_batch_rune_dec",

@@ -1,6 +1,6 @@
 """The arithmetic under the grouped batch classes' shared host code, compiled alone with g++ and run on any machine: the layout of a run of
 host members through a class's device form (raisin_amd/csrc/group_layout.h's RunLayout, group_run.h's run_members_staged -- production runs are 256 MiB,
-so this is where the cut into runs is covered), and which members the two classes behind the rows take (raisin_amd/csrc/huff_rune_select.h,
+so this is where the cut into runs is covered), and which members the rune classes behind the rows take (raisin_amd/csrc/huff_rune_select.h,
 codecs.h's BehindClass)."""
 import os
 import shutil
@@ -53,9 +53,13 @@ def test_the_drivers_go_by_the_headers_under_test():
         text = open(os.path.join(SRC, unit)).read()
         assert text.count(call) == 1 and text.count("run_members_staged<") + text.count("run_members_copied(") == 1 and "STAGE_IN" not in text and "next_group(" not in text, unit
     # ... and both forms of both offers choose through the second: the flows hold no selection of their own
-    enc, dec = (open(os.path.join(SRC, u)).read() for u in ("huff_rune.hip", "huff_rune_dec.hip"))
+    # (the decoders' two offers are one pair for both classes, huff_rune_dec_body.h, and each unit instantiates the pair once)
+    enc, dec = (open(os.path.join(SRC, u)).read() for u in ("huff_rune.hip", "huff_rune_dec_body.h"))
     assert enc.count("rune_class_members(") == 2
-    assert dec.count("rune_dec_candidates(") == 2 and dec.count("rune_dec_leave(") == 2 and dec.count("rune_dec_planned(") == 3
+    assert dec.count("rune_dec_candidates<L>(") == 2 and dec.count("rune_dec_leave<L>(") == 2 and dec.count("rune_dec_planned<L>(") == 3
+    for u in ("huff_rune_dec.hip", "huff_rune_mid_dec.hip"):
+        text = open(os.path.join(SRC, u)).read()
+        assert text.count("rune_dec_offer<") == 1 and text.count("rune_dec_offer_dev<") == 1 and "rune_dec_candidates" not in text and "rune_dec_leave" not in text and "rune_dec_planned" not in text, u
     api = open(os.path.join(SRC, "rsn_api.hip")).read()
     assert "rune_class_members" not in api and "rune_dec_" not in api and "huff_rune_class(" not in api and "huff_rune_dec_class(" not in api
     assert api.count("->offer(") + api.count(".offer(") == 1 and api.count("offer_dev(") == 1

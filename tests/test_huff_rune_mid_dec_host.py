@@ -5,6 +5,7 @@ and undefined-behaviour sanitizers); the constants the Python package mirrors; h
 verdict of the CPU model of the lane maps (tests/lane_maps.py, unchanged, with this class's shape) on every member the GPU tests run
 (tests/rune_mid_dec_cases.py)."""
 import os
+import re
 import shutil
 import subprocess
 
@@ -52,36 +53,62 @@ def test_mirrored_constants_are_the_headers(tmp_path):
 
 
 def test_the_class_is_wired_through_the_shared_pieces():
-    # plain host selection through the 16 KiB class's three steps; both offers choose through it; listed behind the 16 KiB class; the API
-    # unit names no class
-    sel = open(os.path.join(SRC, "huff_rune_mid_dec_select.h")).read()
-    assert [ln.split()[1] for ln in sel.splitlines() if ln.startswith("#include")] == ['"huff_rune_mid_select.h"'] and "hip" not in sel.replace(".hip", "")
-    assert "rune_dec_candidates(" in sel and "rune_dec_planned(" in sel and "rune_dec_leave(" in sel
+    # plain host selection, one set of three steps for both decoders, at the class's rules; both forms of both classes choose through it;
+    # listed behind the 16 KiB class; the API unit names no class
+    sel = open(os.path.join(SRC, "huff_rune_select.h")).read()
+    assert [ln.split()[1] for ln in sel.splitlines() if ln.startswith("#include") and '"' in ln] == ['"group_layout.h"', '"huff_parse_small.h"'] and "hip" not in sel.replace(".hip", "")
+    for step in ("std::vector<size_t> rune_dec_candidates(", "void rune_dec_planned(", "bool rune_dec_leave(", "bool rune_dec_summary_ok("):
+        assert sel.count(step) == 1, step
+    assert "L::len_may(" in sel and "L::GROUP_MIN" in sel and "L::OUT_MIN" in sel and "L::OUT_MAX" in sel and "L::PAY_MAX" in sel
+    assert "HUFF_RUNE_DEC_GROUP_MIN" not in sel and "HUFF_RUNE_OUT_MAX" not in sel and "class L =" not in sel and "group_min" not in sel      # (no class's figures, no default class, no default argument)
+    assert not os.path.exists(os.path.join(SRC, "huff_rune_mid_dec_select.h"))
+    body = open(os.path.join(SRC, "huff_rune_dec_body.h")).read()
+    assert body.count("rune_dec_candidates<L>(") == 2 and body.count("rune_dec_leave<L>(") == 2 and body.count("rune_dec_planned<L>(") == 3
+    assert body.count("int rune_dec_offer(") == 1 and body.count("int rune_dec_offer_dev(") == 1 and body.count("void rune_dec_body(") == 1
+    assert '#include "huff_rune_dec_plan.h"' in body and body.count("rune_light_plan<T, L>(") == 1 and body.count("parse_rune_light<L>(") == 1
+    assert body.count("wave_tree<PLAN_RUNE_IDB>(") == 1 and body.count("plan_rune_ranks(") == 1 and body.count("lane_dec_body<") == 1
+    assert body.count("block_excl_scan<") == 2 and body.count("parse_rune_child(") == 2 and body.count("parse_rune_write(") == 1      # (compaction and expand; the two children)
+    code = body.split("#pragma once")[1]
+    assert "rune_mid" not in code and "ParseRuneMid" not in code and "ParseRuneSmall" not in code and "asm" not in code and '"huffman batch decompress"' in code       # (names no class)
+    assert "the %s plan kernel left a summary that is none" in body
     unit = open(os.path.join(SRC, "huff_rune_mid_dec.hip")).read()
-    assert unit.count("rune_mid_dec_candidates(") == 2 and unit.count("rune_mid_dec_leave(") == 2 and unit.count("rune_mid_dec_planned(") == 3
-    assert '"huff_batch_rune_mid_dec"' in unit and '"huff_dev_rune_mid_plan"' in unit and "func_dyn_lds(" in unit and "Slot::GD_RUNE_MID_PLANS" in unit and "asm" not in unit
-    # no count loop, scan, table or tree of its own: the plan in front of the tree and the plan kernel's body are the shared header's, at
-    # this class's limits; the tree is the one wavefront helper; the payload's decoder is the one body
-    assert '#include "huff_rune_dec_plan.h"' in unit and "rune_light_plan<MD_T, ML>(" in unit and "rune_plan_body<ML>(" in unit and "parse_rune_light<ML>(" in unit
-    for own in ("parse_rune_scan", "parse_rune_put", "parse_rune_decode", "parse_sep_at", "plan_tree", "plan_codes", "atomicMin", "atomicAdd", "atomicCAS", "run_path(", "emit_path("):
-        assert own not in unit, own
-    assert unit.count("wave_tree<PLAN_RUNE_IDB>(") == 1 and unit.count("plan_rune_ranks(") == 1 and unit.count("lane_dec_body<") == 1
-    shared = open(os.path.join(SRC, "huff_rune_dec_plan.h")).read()
     small = open(os.path.join(SRC, "huff_rune_dec.hip")).read()
-    assert shared.count("bool rune_light_plan(") == 1 and shared.count("void rune_plan_body(") == 1 and "rune_light_plan(" not in small.replace("rune_light_plan<RD_T>(", "")
-    assert '#include "huff_rune_dec_plan.h"' in small and "rune_plan_body<ParseRuneSmall>(" in small
-    body = open(os.path.join(SRC, "huff_small_body.h")).read()
-    assert body.count("uint32_t run_path(") == 1 and body.count("void emit_path(") == 1 and body.count("uint32_t lane_dec_body(") == 1
+    assert '"huff_batch_rune_mid_dec"' in unit and '"huff_dev_rune_mid_plan"' in unit and unit.count("func_dyn_lds(") == 1 and "Slot::GD_RUNE_MID_PLANS" in unit and '"mid rune"' in unit
+    assert '"huff_batch_rune_dec"' in small and '"huff_dev_rune_plan"' in small and "func_dyn_lds(" not in small and "Slot::GD_RUNE_PLANS" in small and '"rune"' in small
+    assert "extern __shared__ uint4 md_lds[]" in unit and "extern __shared__" not in small and small.count("__shared__") == 2
+    # no count loop, scan, table, tree or selection of its own in either unit: each is its LDS, one call of the one body at its class's
+    # limits, the plan kernel's one-liner and the class struct the one pair of offers is instantiated with
+    for text, L, C in ((unit, "ML", "RuneMidDecClass"), (small, "RS", "RuneDecClass")):
+        assert '#include "huff_rune_dec_body.h"' in text and text.count("#include") == 1
+        assert text.count("rune_dec_body<%s>(" % L) == 1 and text.count("rune_dec_body<") == 1 and text.count("rune_plan_body<%s>(" % L) == 1 and text.count("rune_plan_body<") == 1
+        assert text.count("rune_dec_offer<%s>" % C) == 1 and text.count("rune_dec_offer_dev<%s>" % C) == 1 and text.count("rune_dec_offer<") == 1 and text.count("rune_dec_offer_dev<") == 1
+        for own in ("parse_rune_scan", "parse_rune_put", "parse_rune_decode", "parse_sep_at", "plan_tree", "plan_codes", "atomicMin", "atomicAdd", "atomicCAS", "run_path(", "emit_path(",
+                    "rune_light_plan", "wave_tree", "plan_rune_ranks", "lane_dec_body<", "block_excl_scan", "parse_rune_child", "parse_rune_write", "parse_rune_light",
+                    "rune_dec_candidates", "rune_dec_planned", "rune_dec_leave", "run_member_groups", "run_groups_dev", "plan_where_they_lie", "asm", "for ("):
+            assert own not in text, own
+    assert "using ML = ParseRuneMid;" in unit and "using RS = ParseRuneSmall;" in small
+    shared = open(os.path.join(SRC, "huff_rune_dec_plan.h")).read()
+    assert shared.count("bool rune_light_plan(") == 1 and shared.count("void rune_plan_body(") == 1
+    lanes = open(os.path.join(SRC, "huff_small_body.h")).read()
+    assert lanes.count("uint32_t run_path(") == 1 and lanes.count("void emit_path(") == 1 and lanes.count("uint32_t lane_dec_body(") == 1
     parse = open(os.path.join(SRC, "huff_parse_rune.h")).read()
-    assert parse.count("bool parse_rune_scan(") == 1 and parse.count("void parse_rune_plan_serial(") == 1 and "struct ParseRuneMid" in parse
+    assert parse.count("bool parse_rune_scan(") == 1 and parse.count("void parse_rune_plan_serial(") == 1 and "struct ParseRuneMid" in parse and "struct ParseRuneSmall" in parse
+    # each limit's figure stated once a class, and only there
+    csrc = {f: open(os.path.join(SRC, f)).read() for f in os.listdir(SRC) if f.endswith((".h", ".hip", ".cpp"))}
+    for literal, where in ((" = 16384", 1), (" = 65536", 1), (" = 960", 1), (" = 576", 2)):
+        assert parse.count(literal) == where, literal
+    for f in ("huff_rune_dec.hip", "huff_rune_mid_dec.hip", "huff_rune_dec_body.h", "huff_rune_dec_plan.h", "huff_rune_select.h", "group_layout.h"):
+        code = re.sub(r"//.*", "", csrc[f])                                # (comments may say the figures)
+        assert not re.search(r"\b(16384|65536|960|576)\b", code.replace("HUFF_RUNE_IN_MAX = 16384", "")), f
     rows = open(os.path.join(SRC, "codecs.h")).read()
-    assert "huff_dec_behind[] = {&huff_rune_dec_class(), &huff_rune_mid_dec_class()}" in rows and "huff_rune_mid_dec_takes_the_encoder()" in rows
+    assert "huff_dec_behind[] = {&huff_rune_dec_class(), &huff_rune_mid_dec_class()}" in rows and "huff_rune_mid_dec_takes_the_encoder()" in rows and "huff_rune_dec_takes_the_encoder()" in rows
+    assert '#include "huff_parse_rune.h"' in rows and "huff_rune_mid_dec_select.h" not in "".join(csrc.values())
     api = open(os.path.join(SRC, "rsn_api.hip")).read()
-    assert "rune_mid" not in api
+    assert "rune_mid" not in api and "rune_dec" not in api
     common = open(os.path.join(SRC, "rsn_common.h")).read()
-    assert "GD_RUNE_MID_PLANS = 60," in common and "HUFF_DEV_PLANS = slot_mask(S::GD_PLANS, S::GD_RUNE_PLANS, S::GD_RUNE_MID_PLANS)" in common
+    assert "GD_RUNE_PLANS = 54," in common and "GD_RUNE_MID_PLANS = 60," in common and "HUFF_DEV_PLANS = slot_mask(S::GD_PLANS, S::GD_RUNE_PLANS, S::GD_RUNE_MID_PLANS)" in common
     make = open(os.path.join(SRC, "Makefile")).read()
-    assert "huff_rune_mid_dec.hip" in make and "huff_rune_mid_dec_select.h" in make and "huff_rune_dec_plan.h" in make
+    assert "huff_rune_mid_dec.hip" in make and "huff_rune_dec.hip" in make and "huff_rune_dec_body.h" in make and "huff_rune_dec_plan.h" in make and "huff_rune_select.h" in make and "huff_rune_mid_dec_select.h" not in make
 
 
 # ---------------------------------------------------------------- the lane model's verdicts on the GPU tests' members

@@ -36,10 +36,14 @@ def test_rune_parse_is_the_code_the_kernels_run():
     # with the byte decoders
     text = open(os.path.join(SRC, "huff_parse_rune.h")).read()
     assert '#include "huff_plan_rune.h"' in text and '#include "huff_parse_small.h"' in text and "parse_rune_plan_serial" in text
-    kernel = open(os.path.join(SRC, "huff_rune_dec.hip")).read()
-    assert '#include "huff_parse_rune.h"' in kernel and '#include "huff_small_body.h"' in kernel and "wave_tree<PLAN_RUNE_IDB>(" in kernel
-    assert "parse_rune_scan(" in kernel and "plan_rune_ranks(" in kernel and "lane_dec_body<" in kernel
-    assert "k_huff_batch_rune_dec" in kernel and "k_huff_dev_rune_plan" in kernel
+    # (the kernel's text is the one body of both rune decoders; the unit is its LDS and one call of it)
+    kernel = open(os.path.join(SRC, "huff_rune_dec_body.h")).read()
+    assert '#include "huff_parse_rune.h"' in kernel and '#include "huff_small_body.h"' in kernel and kernel.count("wave_tree<PLAN_RUNE_IDB>(") == 1
+    assert "rune_light_plan<T, L>(" in kernel and kernel.count("plan_rune_ranks(") == 1 and kernel.count("lane_dec_body<") == 1
+    assert "parse_rune_scan<L>(" in open(os.path.join(SRC, "huff_rune_dec_plan.h")).read()
+    unit = open(os.path.join(SRC, "huff_rune_dec.hip")).read()
+    assert '#include "huff_rune_dec_body.h"' in unit and "rune_dec_body<RS>(" in unit and "rune_plan_body<RS>(" in unit and "using RS = ParseRuneSmall;" in unit
+    assert "void k_huff_batch_rune_dec(" in unit and "void k_huff_dev_rune_plan(" in unit
     body = open(os.path.join(SRC, "huff_small_body.h")).read()
     assert body.count("uint32_t run_path(") == 1 and body.count("void emit_path(") == 1      # one decoder, not two
     assert body.count("plan_tree<IDB>(") == 1 and body.count("plan_codes<IDB>(") == 1          # ... and one tree in a wavefront: wave_tree calls them
